@@ -11,6 +11,7 @@ Weights are seeded random-init (no checkpoints reachable), noise is device Philo
     python bench.py --gpus N --steps K --warmup W    # N > 1 without a launcher: starts its own ranks (a child `torch.distributed.run`)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --config c5 [--gpus N]           # BASELINE configs[4]: ViPC-conditioned sampling, 32 shapes per GPU, 32 tokens
+    python bench.py ... --dump-outputs DIR           # + DIR/points.npy, DIR/eps.npy: what the LAST timed sample() call returned
 
 Rank 0 prints ONE JSON line: metric shapes/sec (whole job) and, at N=1,
   roofline      dominant kernel of the Score forward, HIP-event timed inside this process, with ITS OWN PMC traffic / MFMA utilisation
@@ -24,6 +25,9 @@ Rank 0 prints ONE JSON line: metric shapes/sec (whole job) and, at N=1,
   extra         the headline workload on the LayerNorm-kernel path (the LN-fold guard's fallback), BASELINE configs[3] (Compressor
                 B=1024), configs[4]'s per-GPU share (ViPC, B=32, T=32), shipped T=32
   rccl_ranks_seen  ranks that met in a one-int RCCL all-gather before the model was built (0: no launcher / single process)
+
+--dump-outputs DIR: weights, x0 and the Philox keys all come from the CPU generator seeded in main(), so the same arguments give the
+same inputs on every run, and the files two builds of the kernels write can be compared array for array (`dump_outputs`).
 """
 import argparse
 import ctypes
@@ -91,7 +95,11 @@ def parse(argv=None):
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the configs[3] / configs[4] / T=32 blocks")
     ap.add_argument("--budget-s", type=float, default=540.0, help="extras are skipped once the run is older than this")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (decoded points, sampled latents) as DIR/<name>.npy")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 (the timed region, and what --dump-outputs writes, is its last call) and --warmup at least 0")
     if args.tokens is None:
         args.tokens = 256 if args.config == "c2" else 32
     if args.batch_per_gpu is None:
@@ -152,6 +160,30 @@ def self_launch(args, argv, attempts=3):
             return rc
         log("rendezvous port %d was taken before the child bound it (attempt %d of %d)" % (port, attempt + 1, attempts))
     return rc
+
+
+DUMP_CAP_BYTES = 64 << 20              # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(outdir, arrays, cap=DUMP_CAP_BYTES):
+    """`arrays`: name -> tensor with the batch on dim 0 (the same batch in each).  Writes outdir/<name>.npy, float32 (float64 stays
+    float64).  When the files together would be larger than `cap` bytes, every array keeps the same subset of its batch rows: drawn once
+    from a fixed seed, in ascending order, a function of the batch size and the row sizes only — so two runs with the same arguments
+    keep the same rows.  -> {name: shape written}"""
+    import numpy as np
+    host = {k: (v.detach().cpu() if v.dtype == torch.float64 else v.detach().float().cpu()).contiguous().numpy() for k, v in arrays.items()}
+    B = next(iter(host.values())).shape[0]
+    assert B > 0 and all(a.shape[0] == B for a in host.values()), {k: a.shape for k, a in host.items()}
+    row_bytes = sum(a.nbytes // B for a in host.values())
+    keep = min(B, (cap - 1024 * len(host)) // row_bytes)     # the cap is on the files: 1 KiB each covers the .npy header
+    assert keep >= 1, "one batch row of the outputs (%d bytes) is larger than the cap of %d" % (row_bytes, cap)
+    if keep < B:
+        rows = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+        host = {k: np.ascontiguousarray(a[rows]) for k, a in host.items()}
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
+    return {k: tuple(a.shape) for k, a in host.items()}
 
 
 def score_flops_per_sample_step(cfg):
@@ -770,6 +802,8 @@ def main():
         assert len({d for _, d in seen}) == min(world, local_world) or world > local_world, "two ranks share a device: %s" % seen
         ranks_seen = len(seen)
     device = "cuda:%d" % local_rank
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)    # an unwritable DIR fails here, not after the timed region
 
     import ldt_amd
     cfg = ldt_amd.airplane_config(latent_tokens=args.tokens, sample_N=args.sde_steps)
@@ -808,6 +842,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert pts.shape == (B, cfg.data.tr_max_sample_points, 3) and bool(torch.isfinite(eps).all())
+    if args.dump_outputs and rank == 0:                  # before anything else runs on the device: (points, eps) of the last timed call
+        log("dumped %s to %s" % (dump_outputs(args.dump_outputs, {"points": pts, "eps": eps}), args.dump_outputs))
 
     if rank == 0:
         value = B * args.steps / dt

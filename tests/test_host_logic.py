@@ -246,23 +246,24 @@ def test_unsupported_options_raise(tiny_cfg):
     assert sorted(ldt_amd.Compressor(c.compressor).state_dict()) == sorted(ldt_amd.Compressor(tiny_cfg.compressor).state_dict())
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/model"), reason="reference tree not present")
 def test_default_init_draws_same_weights_as_reference(tiny_cfg):
-    """Same construction order => torch.manual_seed(s); Score(cfg)/Compressor(cfg) equal upstream's draws."""
+    """Same construction order => torch.manual_seed(s); Score(cfg)/Compressor(cfg) equal upstream's draws, bit for bit: names in
+    state_dict order, shapes, dtypes and the SHA-256 of each entry's bytes as captured from the reference
+    (oracle/gen_default_init_golden.py -> tests/golden/default_init.json)."""
+    import hashlib
+    import json
     import ldt_amd
-    from oracle import ref_import as R
-    R.setup()
-    from model.scorenet.score import Score as RScore
-    from model.Compressor.Network import Compressor as RComp
-    torch.manual_seed(7)
-    rs = RScore(tiny_cfg.score); rc = RComp(tiny_cfg.compressor)
-    torch.manual_seed(7)
+    with open(os.path.join(ROOT, "tests", "golden", "default_init.json")) as f:
+        gold = json.load(f)
+    torch.manual_seed(gold["seed"])
     ms = ldt_amd.Score(tiny_cfg.score); mc = ldt_amd.Compressor(tiny_cfg.compressor)
-    for a, b in ((rs, ms), (rc, mc)):
-        sa, sb = a.state_dict(), b.state_dict()
-        assert list(sa) == list(sb)
-        for k in sa:
-            assert torch.equal(sa[k], sb[k]), k
+    for ref, b in ((gold["score"], ms), (gold["compressor"], mc)):
+        sb = b.state_dict()
+        assert [e[0] for e in ref] == list(sb)
+        for k, shape, dtype, sha in ref:
+            v = sb[k].detach().cpu().contiguous()
+            assert (list(v.shape), str(v.dtype)) == (shape, "torch." + dtype), k
+            assert hashlib.sha256(v.numpy().tobytes()).hexdigest() == sha, k
 
 
 def test_resume_reads_reference_checkpoint_layout():
@@ -562,3 +563,33 @@ def test_bench_preflight_fails_fast_before_any_model_is_built(monkeypatch):
     with pytest.raises(AssertionError, match="LOCAL_RANK=3 outside"):
         bench.main()
     assert not touched                                       # nothing selected a device, nothing was built
+
+
+def test_bench_dump_outputs_writes_float_arrays_under_the_cap(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed call's (points, eps) as DIR/<name>.npy in float32 (float64 kept), whole when they
+    fit the cap; above it every array keeps the same fixed ascending subset of batch rows, identical from call to call."""
+    import bench
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d" and bench.parse([]).dump_outputs is None
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    g = torch.Generator().manual_seed(3)
+    pts, eps = torch.randn(16, 32, 3, generator=g).to(torch.bfloat16), torch.randn(16, 8, 5, generator=g, dtype=torch.float64)
+    d = tmp_path / "whole" / "nested"
+    assert bench.dump_outputs(str(d), {"points": pts, "eps": eps}) == {"points": (16, 32, 3), "eps": (16, 8, 5)}
+    assert sorted(os.listdir(d)) == ["eps.npy", "points.npy"]
+    p, e = np.load(d / "points.npy"), np.load(d / "eps.npy")
+    assert p.dtype == np.float32 and e.dtype == np.float64
+    assert np.array_equal(p, pts.float().numpy()) and np.array_equal(e, eps.numpy())
+    row = 32 * 3 * 4 + 8 * 5 * 8                              # bytes of one batch row as written
+    cap = 5 * row + 2 * 1024 + 17                             # room for five rows and the two files' headers, not for six
+    for sub in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / sub), {"points": pts, "eps": eps}, cap=cap)
+        assert shapes == {"points": (5, 32, 3), "eps": (5, 8, 5)}
+        assert 5 * row < sum(os.path.getsize(tmp_path / sub / f) for f in os.listdir(tmp_path / sub)) <= cap
+    pa, ea = np.load(tmp_path / "a" / "points.npy"), np.load(tmp_path / "a" / "eps.npy")
+    assert np.array_equal(pa, np.load(tmp_path / "b" / "points.npy")) and np.array_equal(ea, np.load(tmp_path / "b" / "eps.npy"))
+    rows = [int(np.flatnonzero((p == r).all(axis=(1, 2)))[0]) for r in pa]          # which batch rows were kept
+    assert rows == sorted(set(rows)) and np.array_equal(ea, e[rows])                 # ascending, and the same rows in every array
+    assert bench.DUMP_CAP_BYTES == 64 << 20
+    with pytest.raises(AssertionError, match="larger than the cap"):
+        bench.dump_outputs(str(tmp_path / "c"), {"points": pts, "eps": eps}, cap=row + 2 * 1024 - 1)
