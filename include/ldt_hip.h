@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define LDT_ABI_VERSION 22
+#define LDT_ABI_VERSION 23
 #define LDT_OK 0
 #define LDT_EARG (-1)    /* null / inconsistent argument */
 #define LDT_ESHAPE (-2)  /* unsupported shape */
@@ -249,6 +249,30 @@ int ldt_actnorm(float* x, const float* shift, const float* log_scale, int64_t B,
 int ldt_reparam(const float* post, const float* noise, float* out, int64_t ldo, float* mu_out, float* logvar_out,
                 int64_t rows, int32_t z, float lo, float hi, void* stream);
 int ldt_chamfer(const float* a, const float* b, int32_t B, int32_t na, int32_t nb, float* dl, float* dr, void* stream);
+
+/* ---- held-out evaluation: the loss arithmetic between the encode, the Score forward and the metrics (eval_loss.hip) ----
+ * Single-pass fp32 kernels, fixed summation order (no atomics): two calls on the same input return the same bits.
+ * ldt_reparam_kl: ldt_reparam (out / mu_out / logvar_out are bit-identical to it) plus, per element and in the reference's fp32 operation
+ *   order (model/Compressor/Network.py:12-19 log_p_var_normal / log_p_normal, :221-224 top_down):
+ *       logqz = -0.5 (eps - mu)^2 / exp(logvar) - 0.5 logvar - 0.9189385332,  logpz = -0.5 eps^2 - 0.9189385332,  kl = logqz - logpz
+ *   written token-major [rows][z] to logqz_out / kl_out, and kl_sample_sum[b] = the sum of kl over sample b's rows_per_sample x z elements
+ *   (rows = samples x rows_per_sample).  Every output but `out` may be NULL (mu_out / logvar_out together).  16-byte accesses when z and ldo
+ *   are multiples of 4 and the buffers 16-byte aligned; any other shape takes the scalar form of the same kernel.
+ * ldt_diffuse_q: DiffusionBase.sample_q with per-sample scalars (diffusion/diffusion_continuous.py:78-81; trainer/Latent_SDE_Trainer.py:79-81
+ *   `xt = eps * e2int_f + torch.sqrt(var) * eta`): xt[b][i] = x0[b][i] * m[b] + sqrtf(var[b]) * eta[b][i], each product and the sum rounded
+ *   separately and the root correctly rounded (bit-equal to the fp32 expression evaluated with IEEE operations).  eta_in given: that noise (also copied to eta_out when eta_out is given).  eta_in NULL:
+ *   eta is drawn from the Philox stream exactly as ldt_philox_normal(eta_out, B * per_sample, 0, step, seed) would fill it, and written to
+ *   eta_out (required then).  m, var: DEVICE fp32 [B].  per_sample % 4 == 0, buffers 16-byte aligned.
+ * ldt_dsm_loss: the denoising score-matching loss (trainer/Latent_SDE_Trainer.py:83-87): distance = |eta - params| (l1 != 0) or
+ *   (eta - params)^2, times weight[b] (DEVICE fp32 [B]; NULL = 1); sample_loss[b] (required: it is the first stage's output) = the mean
+ *   over sample b, *mean_loss (nullable) = the mean over everything.  The results stay on the device: no host synchronisation. */
+int ldt_reparam_kl(const float* post, const float* noise, float* out, int64_t ldo, float* mu_out, float* logvar_out,
+                   float* kl_out, float* logqz_out, float* kl_sample_sum, int64_t rows, int64_t rows_per_sample, int32_t z,
+                   float lo, float hi, void* stream);
+int ldt_diffuse_q(const float* x0, const float* eta_in, const float* m, const float* var, float* xt, float* eta_out,
+                  int64_t B, int64_t per_sample, uint64_t seed, int32_t step, void* stream);
+int ldt_dsm_loss(const float* eta, const float* params, const float* weight, int64_t B, int64_t per_sample, int32_t l1,
+                 float* sample_loss, float* mean_loss, void* stream);
 
 /* ---- fused MLP half of a narrow ResidualBlock (the Compressor's d = 128 blocks; model/layers.py:219,226 + :110-133) ----
  * In place on x fp32 [M][ldx]:  x += gate * (W_dn . GELU(W_up . h + b_up) + b_dn),  h = LN(x) * ln_w + ln_b  (affine,

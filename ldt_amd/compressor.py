@@ -407,11 +407,14 @@ class Compressor(nn.Module):
 
     # ------------------------------------------------------------------ encode (Network.py:188-249)
     @torch.no_grad()
-    def forward(self, x, num_points=None, label=None, *, post_noise=None, want_stats=False, seed_eps=None):
+    def forward(self, x, num_points=None, label=None, *, post_noise=None, want_stats=False, seed_eps=None, want_kl=False):
         """Bidirectional inference: x (B, N, 3) -> dict with 'all_eps' (B, tokens, n_layers*z_dim) and the
         reconstruction 'set' (B, N, 3).  `post_noise`: optional list of n_layers tensors (B, tokens, z_dim) replacing
-        the N(0,1) draws of `sample(mu, logvar)` (Network.py:26-29).  Training-only entries of the reference dict
-        ('kls', 'all_logqz') are not produced; 'posteriors' holds token-major (mu, logvar) when want_stats."""
+        the N(0,1) draws of `sample(mu, logvar)` (Network.py:26-29).  'posteriors' holds token-major (mu, logvar) when want_stats.
+        `want_kl`: the ELBO entries of the reference dict (Network.py:221-232) — 'kls' and 'all_logqz', lists of n_layers tensors in
+        top-down order shaped (B, z_dim, tokens) like upstream's (channels-first views of token-major buffers), plus 'kl_sample_sum'
+        (B, n_layers), each sample's KL summed per level; the posterior draw then runs as ldt_reparam_kl, whose latents are
+        bit-identical to ldt_reparam's.  Off (default): both entries are None and nothing else changes."""
         self._no_training_dropout("forward")
         dev = self._device()
         if dev.type != "cuda":
@@ -466,7 +469,7 @@ class Compressor(nn.Module):
         # ---- top_down: posterior per level + decoder block
         o = self._initial_set(P, B, npts, keep_mask, seed_eps)
         all_eps = torch.empty((B * T, L * z), dtype=torch.float32, device=dev)
-        stats = []
+        stats, kls, logqz, kl_sums = [], [], [], []
         q_dec = None                                                                # next decoder level's query projection (fused)
         # bf16 image of o for the next level's att(x, o): written by the decoder block's last kernel, not by a pass of its own
         o_bf = torch.empty((B * npts, D), dtype=torch.bfloat16, device=dev) if (L > 1 and D % 64 == 0) else None
@@ -481,7 +484,12 @@ class Compressor(nn.Module):
             post = ops.sgemm(xj, Pd["w_prior"], Pd["b_prior"], act_in=ACT_SILU)      # SiLU -> Conv1d D -> 2z
             nz = post_noise[j].to(dev, torch.float32).contiguous().view(B * T, z)
             ej = all_eps[:, z * j: z * (j + 1)]
-            stats.append(ops.reparam(post, nz, ej, self.min_sigma, 10., want_stats))
+            if want_kl:                                                             # :221-224: log q(z), log p(z) and their difference
+                mu, lv, kl, lq, ks = ops.reparam_kl(post, nz, ej, self.min_sigma, 10., T, want_stats)
+                stats.append((mu, lv))
+                kls.append(kl.view(B, T, z).transpose(1, 2)); logqz.append(lq.view(B, T, z).transpose(1, 2)); kl_sums.append(ks)
+            else:
+                stats.append(ops.reparam(post, nz, ej, self.min_sigma, 10., want_stats))
             nxt = P["dec"][L - 2 - j]["att1"] if (j + 1 < L and l_emb is None) else None
             r = self._decoder_level(Pd, o, ej, B, npts, T, c=l_emb, o_bf16=o_bf if j + 1 < L else None, q_pre=q_dec, next_P=nxt)
             q_dec = r[1] if nxt is not None else None
@@ -491,4 +499,6 @@ class Compressor(nn.Module):
                    None if t is None else t.view(B, T, z) for t in stats[j]) for j in range(L)],
                "kls": None, "all_logqz": None,
                "fps_idx": fps_idx, "knn_idx": knn_idx, "centers": centers, "tokens": tok_pre}
+        if want_kl:
+            res.update({"kls": kls, "all_logqz": logqz, "kl_sample_sum": torch.stack(kl_sums, 1)})
         return res

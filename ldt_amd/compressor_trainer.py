@@ -1,0 +1,192 @@
+"""`CompressorTrainer` / `CompletionCompressorTrainer` — the evaluation half of the reference's stage-1 trainers
+(trainer/Compressor_Trainer.py, completion_trainer/Compressor_Trainer.py), MI355X path: what the `--test` branches of
+train_Compressor.py (:72,99) and train_Completion_Compressor.py (:81,108) call.
+
+Kept, with the reference's names, signatures and return values: `Trainer(cfg, model, device)`, `sample` (:54-59), `valsample`
+(:61-100), `reconstrustion` (:102-161; completion :66-95 — upstream's spelling), `resume` (:163-186).  New: `eval_losses`, the two
+ELBO terms of `compute_loss` that need no absent extension.  Training is out of scope: there is no optimizer and no scheduler, and
+`update` / `compute_loss` raise — `compute_loss` adds `EMD_loss`, which goes through the auction-EMD CUDA extension of
+evaluation/emd.py that this package does not have (and does not imitate).
+
+The encode, the decode, Chamfer / EMD and the KL terms run in HIP kernels (Compressor.forward, ldt_amd.metrics); what is plain torch
+here is bookkeeping on finished clouds: concatenation, the loaders' shift / scale de-normalisation and the category filter.
+"""
+import math
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import ops
+from .metrics import F1Score, L2_ChamferEval_1000, compute_all_metrics
+
+
+class CompressorTrainer:
+    def __init__(self, cfg, model, device):
+        self.cfg = cfg
+        self.device = device
+        self.itr, self.epoch, self.time = 0, 1, 0                    # trainer/base.py:20-26
+        self.num_points = cfg.data.tr_max_sample_points
+        self.kl_weight = getattr(cfg.opt, "kl_weight", None)
+        self.model = model.to(device)
+
+    # ---- training: refused -------------------------------------------------------------------------------
+    def update(self, data):
+        raise NotImplementedError("CompressorTrainer.update: training (optimizer step, backward) is not on this path — it is the "
+                                  "inference / evaluation path; see eval_losses for the held-out KL and Chamfer terms")
+
+    def compute_loss(self, target_set, label):
+        raise NotImplementedError("CompressorTrainer.compute_loss: its EMD_loss term needs the auction-EMD CUDA extension "
+                                  "(evaluation/emd.py), which is not on this path; eval_losses returns the KL and Chamfer terms")
+
+    @torch.no_grad()
+    def eval_losses(self, target_set, label=None):
+        """The two terms of `compute_loss` (:42-52) that stand on kernels of this package, for a held-out batch (B, N, 3):
+        'kl_loss' = `torch.cat(kls, dim=1).mean()` and 'cd_loss' = `CD_loss(output_set, target_set)` of evaluation/loss.py:72-79
+        (type 'l1': mean sqrt(dist1) + mean sqrt(dist2), on ldt_chamfer).  0-dim device tensors."""
+        self.model.eval()
+        target = target_set.to(self.device).float().contiguous()
+        out = self.model(target, label=label, want_kl=True)
+        n_kl = sum(k.numel() for k in out["kls"])
+        kl_loss = out["kl_sample_sum"].sum() / n_kl                  # the per-sample, per-level sums are the kernel's; every level is equally long
+        d_rec, d_tgt = ops.chamfer(target, out["set"].contiguous())  # squared distances: reconstruction -> target, target -> reconstruction
+        cd_loss = torch.sqrt(d_rec.clamp_min(0)).mean() + torch.sqrt(d_tgt.clamp_min(0)).mean()
+        return {"kl_loss": kl_loss, "cd_loss": cd_loss}
+
+    # ---- generation ------------------------------------------------------------------------------------------
+    def sample(self, num_samples, num_points, given_eps=None):
+        self.model.eval()
+        with torch.no_grad():
+            return self.model.sample((num_samples, num_points), given_eps=given_eps)
+
+    @torch.no_grad()
+    def valsample(self, test_loader, sample_points, vis=False):
+        """:61-100 — one prior sample per test shape (latents ~ N(0, 1)), the "Sample rate" print, `smp_ep<epoch>.npy` into
+        cfg.log.save_path (when one is set), `compute_all_metrics(smp, ref)` and the `{"val/gen/<key>": float}` dict."""
+        if vis:
+            raise NotImplementedError("valsample(vis=True): mitsuba rendering (tools/vis_utils.py) is not on this path")
+        self.model.eval()
+        all_ref, all_smp, use_time = [], [], 0.
+        for data in test_loader:
+            ref_pts = data["te_points"].to(self.device)
+            torch.cuda.synchronize()
+            t0 = time.time()
+            smp = self.sample(num_samples=data["tr_points"].size(0), num_points=sample_points)
+            torch.cuda.synchronize()
+            use_time += time.time() - t0
+            all_smp.append(smp)
+            all_ref.append(ref_pts)
+        smp, ref = torch.cat(all_smp, dim=0), torch.cat(all_ref, dim=0).float()
+        print("Sample rate: %.8f " % (smp.shape[0] / max(use_time, 1e-9)))
+        self._save("smp", smp)
+        return self._report(compute_all_metrics(smp, ref, batch_size=128))
+
+    # ---- reconstruction ----------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def reconstrustion(self, test_loader, val_cate=0):
+        """:102-161 — encode and reconstruct the test shapes, de-normalise references and reconstructions by the loader's `shift` /
+        `scale`, write `rec_ep<epoch>.npy`, score with `compute_all_metrics`.  cfg.data.num_categorys == 1: batch by batch as the
+        loader yields them.  Otherwise: the shapes with `cate_idx == val_cate`, re-batched by cfg.data.test_batch_size and encoded with
+        the label `val_cate`.  Nothing synchronises until the dump and the metrics at the end."""
+        self.model.eval()
+        dev = self.device
+        all_ref, all_rec = [], []
+        if self.cfg.data.num_categorys == 1:
+            for data in test_loader:
+                ref_pts = data["te_points"].to(dev).float()
+                rec_pts = self.model(ref_pts)["set"]
+                shift, scale = data["shift"].float().to(dev), data["scale"].float().to(dev)
+                all_ref.append(ref_pts * scale + shift)
+                all_rec.append(rec_pts * scale + shift)
+            rec, ref = torch.cat(all_rec, dim=0), torch.cat(all_ref, dim=0)
+        else:
+            shift, scale = [], []
+            for data in test_loader:
+                idx = data["cate_idx"] == val_cate
+                shift.append(data["shift"][idx].float())
+                scale.append(data["scale"][idx].float())
+                all_ref.append(data["te_points"][idx])
+            ref = torch.cat(all_ref, dim=0).to(dev).float()
+            if ref.shape[0] == 0:
+                raise ValueError("reconstrustion: no test shape has cate_idx == %r" % (val_cate,))
+            bsize = self.cfg.data.test_batch_size
+            for i in range(math.ceil(ref.shape[0] / bsize)):
+                pts = ref[i * bsize:(i + 1) * bsize]
+                cates = (torch.ones(pts.shape[0]) * val_cate).int().to(dev)
+                all_rec.append(self.model(pts, label=cates)["set"])
+            shift, scale = torch.cat(shift, dim=0).to(dev), torch.cat(scale, dim=0).to(dev)
+            rec = torch.cat(all_rec, dim=0) * scale + shift
+            ref = ref * scale + shift
+        self._save("rec", rec)
+        self.last_reconstruction = {"rec": rec, "ref": ref}
+        return self._report(compute_all_metrics(rec, ref, batch_size=128))
+
+    def _save(self, tag, clouds):
+        path = getattr(getattr(self.cfg, "log", None), "save_path", "") or ""
+        if path:
+            np.save(os.path.join(path, "%s_ep%d.npy" % (tag, self.epoch)), clouds.detach().cpu().numpy())
+
+    def _report(self, gen_res):
+        all_res = {("val/gen/%s" % k): (v if isinstance(v, float) else v.item()) for k, v in gen_res.items()}
+        print("Validation Sample (unit) Epoch:%d " % self.epoch, gen_res)
+        return all_res
+
+    # ---- checkpoints: the layout trainer/base.py:51-61 `save` writes ---------------------------------------------
+    def resume(self, epoch=None, finetune=False, strict=False, load_optim=True):
+        """:163-186 — `<cfg.log.save_path>/checkpt_<epoch>.pth` (`epoch` defaults to the last row of `training.csv`): the weights from
+        `state_dict`; unless `finetune`, also `epoch` (+ 1), `itr` and `time`.  The optimizer and scheduler entries are ignored
+        (`load_optim` is accepted for signature parity): there is no optimizer here.  Ends with `model.init()` like upstream."""
+        if epoch is None:
+            import csv
+            with open(os.path.join(self.cfg.log.save_path, "training.csv")) as f:
+                epoch = int(float(list(csv.DictReader(f))[-1]["epoch"]))
+        path = os.path.join(self.cfg.log.save_path, "checkpt_{:}.pth".format(epoch))
+        checkpt = torch.load(path, map_location="cpu", weights_only=False)      # holds cfg as argparse.Namespace
+        if not finetune:
+            self.model.load_state_dict(checkpt["state_dict"], strict=strict)
+            self.epoch = checkpt["epoch"] + 1
+            self.itr = checkpt["itr"]
+            self.time = checkpt["time"]
+        else:
+            self.model.load_state_dict(checkpt["state_dict"], strict=False)
+        self.model.init()
+
+
+class CompletionCompressorTrainer(CompressorTrainer):
+    """completion_trainer/Compressor_Trainer.py (ShapeNet-ViPC): same constructor, `sample` and `resume`; `reconstrustion` takes the
+    ViPC loader's (views, pc, pc_part) batches and reports Chamfer / F1 instead of the generation metrics."""
+
+    def update(self, data):
+        raise NotImplementedError("CompletionCompressorTrainer.update: training (optimizer step, backward) is not on this path — it is "
+                                  "the inference / evaluation path; see eval_losses for the held-out KL and Chamfer terms")
+
+    def compute_loss(self, target_set):
+        raise NotImplementedError("CompletionCompressorTrainer.compute_loss: its EMD_loss term needs the auction-EMD CUDA extension "
+                                  "(evaluation/emd.py), which is not on this path; eval_losses returns the KL and Chamfer terms")
+
+    @torch.no_grad()
+    def reconstrustion(self, test_loader):
+        """:66-95 — every complete cloud reduced to 2048 points by farthest point sampling, encoded and reconstructed;
+        `rec_ep<epoch>.npy`; returns {'cd': L2_ChamferEval_1000(rec, ref), 'f1score': F1Score(rec, ref).mean()}."""
+        self.model.eval()
+        all_ref, all_rec = [], []
+        for views, pc, pc_part in test_loader:
+            pc = pc.to(self.device).float().contiguous()
+            ref_pts = ops.gather_rows(pc, ops.fps(pc, min(2048, pc.shape[1])))
+            all_rec.append(self.model(ref_pts)["set"])
+            all_ref.append(ref_pts)
+        rec, ref = torch.cat(all_rec, dim=0), torch.cat(all_ref, dim=0)
+        self._save("rec", rec)
+        self.last_reconstruction = {"rec": rec, "ref": ref}
+        cd = L2_ChamferEval_1000(rec, ref)
+        f1score, _, _ = F1Score(rec, ref)
+        all_res = {"cd": cd, "f1score": f1score.mean()}
+        print("Validation Sample (unit) Epoch:%d " % self.epoch, all_res)
+        return all_res
+
+    def load_pretrain(self):
+        """:122-126 — `cfg.model.pretrain_path`, key `state_dict`, strict."""
+        checkpt = torch.load(os.path.join(self.cfg.model.pretrain_path), map_location="cpu", weights_only=False)
+        self.model.load_state_dict(checkpt["state_dict"], strict=True)
+        self.model.init()

@@ -28,7 +28,7 @@ def namespace2dict(ns):
 _AIRPLANE = {
     "data": {"num_categorys": 1, "tr_max_sample_points": 2048, "te_max_sample_points": 2048,
              "batch_size": 64, "test_batch_size": 64},
-    "opt": {"ema_decay": 0.9999},
+    "opt": {"ema_decay": 0.9999, "loss_type": "l2"},
     "common": {"num_points": 2048, "seed": 0},
     "score": {"num_steps": 1000, "z_dim": 120, "z_scale": 32, "hidden_size": 1024, "num_heads": 16,
               "num_blocks": 24, "num_categorys": 1, "c_dim": 0.0, "t_dim": 1024, "dropout": 0.0,

@@ -109,3 +109,30 @@ __device__ __forceinline__ f32x2 gelu_erf_fast2(f32x2 x) {
     return x * 0.5f + z * r;
 }
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
+
+// ------------------------------------------------------------------------------------------------
+// Philox4x32-10 (Salmon et al. 2011) + Box-Muller: 4 N(0,1) per counter.
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+        c[1] = (uint32_t)p1; c[3] = (uint32_t)p0; c[0] = n0; c[2] = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
+    const float u1 = ((float)a + 1.0f) * 2.3283064365386963e-10f;   // (0,1]
+    const float u2 = (float)b * 2.3283064365386963e-10f;            // [0,1)
+    const float rr = sqrtf(-2.0f * logf(u1));
+    float sn, cs;
+    sincosf(6.283185307179586f * u2, &sn, &cs);
+    z0 = rr * cs; z1 = rr * sn;
+}
+
+// posterior draw (Network.py:26-29): eps = mu + exp(logvar / 2) * noise.  One definition, so that ldt_reparam (pointops.hip) and
+// ldt_reparam_kl (eval_loss.hip) round alike: the product and the sum are ONE fused multiply-add, spelled out — left to contraction, the
+// 4-wide form of a kernel gets v_pk_fma_f32 for some lanes and v_pk_mul_f32 + v_pk_add_f32 for others.
+__device__ __forceinline__ float reparam_eps(float mu, float lv, float noise) { return fmaf(noise, expf(lv / 2.f), mu); }

@@ -131,26 +131,7 @@ int ldt_ln_launch(const LnArgs* a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al. 2011) + Box-Muller: 4 N(0,1) per counter.
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[1] = (uint32_t)p1; c[3] = (uint32_t)p0; c[0] = n0; c[2] = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-    const float u1 = ((float)a + 1.0f) * 2.3283064365386963e-10f;   // (0,1]
-    const float u2 = (float)b * 2.3283064365386963e-10f;            // [0,1)
-    const float rr = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincosf(6.283185307179586f * u2, &sn, &cs);
-    z0 = rr * cs; z1 = rr * sn;
-}
+// Philox4x32-10 + Box-Muller (philox4x32_10, box_muller): common.h — shared with the held-out-loss kernels (eval_loss.hip).
 
 // Fused predictor update (one pass over the latents):
 //   mode 0 (ancestral, exact op order of diffusion_continuous.py:152-162 + Latent_SDE_Trainer.py:57-61):

@@ -477,7 +477,7 @@ __global__ void reparam_kernel(const float* __restrict__ post, const float* __re
         const long r = i / z; const int c = (int)(i % z);
         const float mu = post[r * 2 * z + c];
         const float lv = fminf(fmaxf(post[r * 2 * z + z + c], lo), hi);
-        out[r * ldo + c] = mu + expf(lv / 2.f) * noise[i];
+        out[r * ldo + c] = reparam_eps(mu, lv, noise[i]);
         if (mu_out) { mu_out[i] = mu; lv_out[i] = lv; }
     }
 }

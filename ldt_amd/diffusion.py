@@ -68,6 +68,25 @@ class DiffusionBase:
     def std(self, t):
         return torch.sqrt(self.var(t))
 
+    def inv_var(self, var):
+        """diffusion_continuous.py:73-76: the time at which var(t) equals `var` (the sub-VP SDE has no closed form, as upstream)."""
+        raise NotImplementedError
+
+    def sample_q(self, x_init, noise, var_t, m_t):
+        """diffusion_continuous.py:78-81: a draw of q(x_t | x_0) = N(m_t x_0, var_t) given the N(0,1) `noise`.  Device latents
+        (B, ...) with one (m_t, var_t) per sample — (B,) or (B, 1, ..., 1), as the trainers pass them — go through
+        ldt_diffuse_q; anything else (host tensors, a shared scalar, full-shape coefficients) is the host expression."""
+        B = x_init.shape[0] if torch.is_tensor(x_init) and x_init.dim() > 0 else 0
+        per_sample = all(torch.is_tensor(c) and c.is_cuda and c.numel() == B for c in (var_t, m_t))
+        if per_sample and x_init.is_cuda and x_init.dtype == torch.float32 and (x_init.numel() // B) % 4 == 0:
+            return ops.diffuse_q(x_init, m_t.float(), var_t.float(), noise.to(x_init))[0]
+        return m_t * x_init + torch.sqrt(var_t) * noise
+
+    def cross_entropy_const(self, ode_eps):
+        """diffusion_continuous.py:83-86: the constant term of CE(q(z_0 | x) || p(z_0)), 1/2 (1 + log(2 pi var(ode_eps))), for the
+        ODE integration cutoff `ode_eps` (a host scalar tensor; upstream builds it on the device)."""
+        return 0.5 * (1.0 + torch.log(2.0 * np.pi * self.var(t=torch.tensor(ode_eps))))
+
     # ---- per-step coefficient table for ldt_sampler_step ------------------------------------------
     def step_table(self, N, predictor, time_eps, probability_flow=False):
         """-> (timesteps [N] fp32 CPU, coef [N,4] fp32 CPU, mode).  All scalars are produced on the CPU with
@@ -440,6 +459,9 @@ class DiffusionVPSDE(DiffusionBase):
     def discrete(self, idx):
         return self.betas.index_select(0, idx), self.alpha.index_select(0, idx)
 
+    def inv_var(self, var):
+        return _inv_var_linear_beta(var, self.beta_start, self.beta_end, self.sigma2_0)
+
 
 class DiffusionSubVPSDE(DiffusionBase):
     """diffusion_continuous.py:681-729: the sub-VP SDE (same drift as the VP-SDE, g2 = beta (1 - exp(-2 int beta))).  It has
@@ -470,6 +492,15 @@ class DiffusionSubVPSDE(DiffusionBase):
     def e2int_f(self, t):
         return torch.exp(-0.5 * self.beta_start * t - 0.25 * (self.beta_end - self.beta_start) * t * t)
 
+    def var_vpsde(self, t):
+        """:718-720: the variance of the VP-SDE with the same beta(t) (importance weighting 'like the VP-SDE')."""
+        return 1.0 - (1.0 - self.sigma2_0) * torch.exp(
+            -self.beta_start * t - 0.5 * (self.beta_end - self.beta_start) * t * t)
+
+    def inv_var_vpsde(self, var):
+        """:722-729."""
+        return _inv_var_linear_beta(var, self.beta_start, self.beta_end, self.sigma2_0)
+
 
 class _GeometricVariance(DiffusionBase):
     """var(t) = sigma2_min (sigma2_max / sigma2_min)^t - sigma2_min + sigma2_0, shared by the VE and the geometric SDE."""
@@ -485,6 +516,10 @@ class _GeometricVariance(DiffusionBase):
 
     def var(self, t):
         return self.sigma2_min * ((self.sigma2_max / self.sigma2_min) ** t) - self.sigma2_min + self.sigma2_0
+
+    def inv_var(self, var):
+        """:621-623, :755-757."""
+        return torch.log((var + self.sigma2_min - self.sigma2_0) / self.sigma2_min) / np.log(self.sigma2_max / self.sigma2_min)
 
 
 class DiffusionVESDE(_GeometricVariance):
@@ -503,6 +538,14 @@ class DiffusionVESDE(_GeometricVariance):
     def e2int_f(self, t):
         return torch.ones_like(t)
 
+    def var_N(self, t):
+        """:759-760: the variance of the normalised process, 1 - sigma2_min + sigma2_min (sigma2_max / sigma2_min)^t."""
+        return 1.0 - self.sigma2_min + self.sigma2_min * ((self.sigma2_max / self.sigma2_min) ** t)
+
+    def inv_var_N(self, var):
+        """:762-763."""
+        return torch.log((var + self.sigma2_min - 1.0) / self.sigma2_min) / np.log(self.sigma2_max / self.sigma2_min)
+
 
 class DiffusionGeometric(_GeometricVariance):
     """diffusion_continuous.py:595-623: the VP drift with a geometric progression of the variance."""
@@ -518,6 +561,14 @@ class DiffusionGeometric(_GeometricVariance):
     def e2int_f(self, t):
         return torch.sqrt(
             1.0 + self.sigma2_min * (1.0 - (self.sigma2_max / self.sigma2_min) ** t) / (1.0 - self.sigma2_0))
+
+
+def _inv_var_linear_beta(var, beta_start, beta_end, sigma2_0):
+    """t with 1 - (1 - sigma2_0) exp(-beta_start t - (beta_end - beta_start) t^2 / 2) = var: the positive root of the quadratic
+    in t (diffusion_continuous.py:674-678 for the VP-SDE, :722-729 for the sub-VP SDE's VP twin), upstream's operation order."""
+    c = torch.log((1 - var) / (1 - sigma2_0))
+    a = beta_end - beta_start
+    return (-beta_start + torch.sqrt(np.square(beta_start) - 2 * a * c)) / a
 
 
 def langevin_update(x, params, z, x_mean, std_t, snr, n_total, n_valid, sharded, scratch):

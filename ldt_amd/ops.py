@@ -394,6 +394,67 @@ def reparam(post, noise, out, lo, hi, want_stats=False):
     return mu, lv
 
 
+# ----------------------------------------------------------------------------- held-out evaluation (eval_loss.hip)
+def reparam_kl(post, noise, out, lo, hi, rows_per_sample, want_stats=False):
+    """`reparam` plus the per-element log q(z) and KL of the draw (Network.py:12-19,221-224): post fp32 [rows, 2z], noise [rows, z] ->
+    out[rows, z] (strided slice ok; bit-identical to `reparam`), returns (mu, logvar, kl [rows, z], logqz [rows, z], kl_sample_sum
+    [rows / rows_per_sample]); mu / logvar None unless want_stats."""
+    _need(post, torch.float32, "post"); _need(noise, torch.float32, "noise"); _need(out, torch.float32, "out")
+    rows, z2 = post.shape
+    z = z2 // 2
+    if not (post.is_contiguous() and noise.is_contiguous() and noise.numel() == rows * z and out.shape == (rows, z) and out.stride(1) == 1):
+        raise ValueError("reparam_kl: post [rows, 2z] and noise [rows, z] contiguous, out [rows, z] with unit column stride")
+    dev = post.device
+    mu = torch.empty((rows, z), dtype=torch.float32, device=dev) if want_stats else None
+    lv = torch.empty_like(mu) if want_stats else None
+    kl = torch.empty((rows, z), dtype=torch.float32, device=dev)
+    lq = torch.empty_like(kl)
+    ks = torch.empty((rows // max(int(rows_per_sample), 1),), dtype=torch.float32, device=dev)
+    check(lib().ldt_reparam_kl(_p(post), _p(noise), _p(out), out.stride(0), _p(mu), _p(lv), _p(kl), _p(lq), _p(ks), rows,
+                               int(rows_per_sample), z, float(lo), float(hi), stream_ptr()), "ldt_reparam_kl")
+    return mu, lv, kl, lq, ks
+
+
+def diffuse_q(x0, m, var, eta=None, *, seed=0, step=0):
+    """x_t = x0 * m[b] + sqrt(var[b]) * eta (diffusion_continuous.py:78-81) with per-sample device scalars m, var [B]: x0 fp32
+    [B, ...] -> (xt, eta).  eta None: drawn in the kernel from the Philox stream (seed, step) — the tensor
+    `philox_normal(x0.shape, dev, seed, step)` would return — and handed back."""
+    _need(x0, torch.float32, "x0"); _need(m, torch.float32, "m"); _need(var, torch.float32, "var"); _need(eta, torch.float32, "eta")
+    x0 = x0.contiguous()
+    B = x0.shape[0]
+    m, var = m.reshape(-1).contiguous(), var.reshape(-1).contiguous()
+    if m.numel() != B or var.numel() != B:
+        raise ValueError("diffuse_q: m and var hold one scalar per sample (%d), got %d / %d" % (B, m.numel(), var.numel()))
+    if eta is not None:
+        if eta.shape != x0.shape:
+            raise ValueError("diffuse_q: eta %s vs x0 %s" % (tuple(eta.shape), tuple(x0.shape)))
+        eta = eta.contiguous()
+    xt = torch.empty_like(x0)
+    drawn = torch.empty_like(x0) if eta is None else None
+    check(lib().ldt_diffuse_q(_p(x0), _p(eta), _p(m), _p(var), _p(xt), _p(drawn), B, x0.numel() // B, int(seed), int(step),
+                              stream_ptr()), "ldt_diffuse_q")
+    return xt, (drawn if eta is None else eta)
+
+
+def dsm_loss(eta, params, weight=None, l1=False):
+    """Denoising score-matching loss (Latent_SDE_Trainer.py:83-87): eta, params fp32 [B, ...], weight None or [B] ->
+    (mean over everything, 0-dim; per-sample means [B]).  Both stay on the device."""
+    _need(eta, torch.float32, "eta"); _need(params, torch.float32, "params"); _need(weight, torch.float32, "weight")
+    if eta.shape != params.shape:
+        raise ValueError("dsm_loss: eta %s vs params %s" % (tuple(eta.shape), tuple(params.shape)))
+    eta, params = eta.contiguous(), params.contiguous()
+    B = eta.shape[0]
+    if weight is not None:
+        weight = weight.reshape(-1).contiguous()
+        if weight.numel() != B:
+            raise ValueError("dsm_loss: weight holds one scalar per sample (%d), got %d" % (B, weight.numel()))
+    per = torch.empty((B,), dtype=torch.float32, device=eta.device)
+    mean = torch.empty((), dtype=torch.float32, device=eta.device)
+    check(lib().ldt_dsm_loss(_p(eta), _p(params), _p(weight), B, eta.numel() // B, int(bool(l1)), _p(per), _p(mean), stream_ptr()),
+          "ldt_dsm_loss")
+    return mean, per
+
+
 def chamfer(a, b):
     """a [B,na,3], b [B,nb,3] fp32 -> (dl [B,nb], dr [B,na]) squared nearest-neighbour distances."""
     a, b = a.contiguous(), b.contiguous()

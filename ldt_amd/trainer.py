@@ -1,6 +1,7 @@
 """`Trainer` — sampling half of the reference trainer (trainer/Latent_SDE_Trainer.py), MI355X path.
 
 Kept: `Trainer(cfg, model, compressor, device)`, `score_fn(t, x, label, condition) -> (score, params)` (:57-61),
+`val_loss(data, condition) -> held-out denoising loss` (:63-92),
 `sample(num_samples, num_points, label, condition) -> (points, eps)` (:143-165), `valsample`-style "Sample rate"
 timing (:178-181,206), EMA weight swap (:146,164; tools/utils.py:80-101) and the checkpoint keys (:232-235,
 :251-256).  Training (`update*`, optimizers, schedulers) is out of scope for this path.
@@ -137,6 +138,50 @@ class Trainer:
         finally:
             self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
         return sample, eps
+
+    @torch.no_grad()
+    def val_loss(self, data, condition=None, *, t_index=None, eta=None, seed=None):
+        """The held-out denoising loss of one batch, the reference's method line for line (trainer/Latent_SDE_Trainer.py:63-92;
+        train_Latent_Diffusion.py:76 calls it per test batch): EMA weights in, `compressor(data['te_points'])['all_eps']`, the label
+        from `data['cate_idx']` when cfg.data.num_categorys > 1, `idx = np.random.choice(arange(train_N), B)` on numpy's global
+        generator (so `np.random.seed` reproduces upstream's times), `t = linspace(1, sample_time_eps, train_N)[idx]`,
+        `xt = eps * e2int_f(t) + sqrt(var(t)) * eta` (ldt_diffuse_q), `params = Score(xt, t, label=, condition=)`, |eta - params| for
+        cfg.opt.loss_type "l1" and the square otherwise, the mean over everything (ldt_dsm_loss), EMA weights out — also when
+        something in between raises.  Returns the 0-dim device tensor; nothing is synchronised.
+
+        `eta` is where upstream calls `torch.randn_like` on the CUDA generator, which no other device reproduces: here it comes
+        from the device Philox stream keyed by ONE draw of the CPU generator (the convention of `Compressor.forward`'s posterior
+        noise).  Keyword extensions (not in the reference): `t_index` (B,) replaces the numpy draw, `eta` (B, tokens, z) the
+        noise, `seed` the Philox key.  The pieces stay available as `self.last_val_loss`."""
+        import numpy as np
+        from . import ops
+        self.model.eval()
+        self.compressor.eval()
+        self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
+        try:
+            dev = self.device
+            eps = self.compressor(data["te_points"].to(dev))["all_eps"]
+            label = data["cate_idx"].to(dev) if self.cfg.data.num_categorys > 1 else None
+            size = eps.shape[0]
+            train_N = self.cfg.sde.train_N
+            if t_index is None:
+                t_index = np.random.choice(np.arange(train_N), size, replace=True)
+            idx = torch.as_tensor(np.asarray(t_index)).long().reshape(-1)
+            if idx.numel() != size:
+                raise ValueError("val_loss: t_index holds %d entries for a batch of %d" % (idx.numel(), size))
+            t = torch.linspace(1.0, self.sample_time_eps, train_N).index_select(0, idx)      # host fp32, like the schedule tables
+            e2int_f, var = self.SDE.e2int_f(t), self.SDE.var(t)
+            if eta is None and seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            t_dev = t.to(dev)
+            xt, eta = ops.diffuse_q(eps, e2int_f.float().to(dev), var.float().to(dev),
+                                    None if eta is None else eta.to(dev, torch.float32), seed=seed or 0)
+            params = self.model(xt, t_dev, condition=condition, label=label)
+            loss, per_sample = ops.dsm_loss(eta, params, None, l1=self.cfg.opt.loss_type == "l1")
+            self.last_val_loss = {"t": t_dev, "eps": eps, "eta": eta, "xt": xt, "params": params, "sample_loss": per_sample}
+        finally:
+            self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
+        return loss
 
     @torch.no_grad()
     def valsample(self, test_loader, val_cate=0, vis=False, *, batch_size=None, ref=None, save_npy=None):
