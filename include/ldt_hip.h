@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define LDT_ABI_VERSION 23
+#define LDT_ABI_VERSION 24
 #define LDT_OK 0
 #define LDT_EARG (-1)    /* null / inconsistent argument */
 #define LDT_ESHAPE (-2)  /* unsupported shape */
@@ -103,6 +103,16 @@ int ldt_attention_fwd(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride,
  * 0 = streaming (attn_fwd_kernel<head_dim>), 1 = resident (attn_fwd_resident_kernel<head_dim>), 2 = whole-head
  * (attn_fwd_head_kernel<64, ceil(Nk / 64)>).  bench.py uses it to name the rocprofv3 symbol of the kernel it timed. */
 int ldt_attention_route(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim);
+/* Which kernel ldt_gemm_bf16 (fold = 0), ldt_gemm_resid_lnstats / ldt_gemm_lnfold (fold = 256 or 32: the statistics granule; producer when
+ * epilogue == LDT_EPI_RESID_F32, consumer otherwise) runs for a problem of this shape (a query, not a launch; the return value is the route,
+ * not a status).  The launchers and this query evaluate the same decision function.  Packed:
+ *     (family << 28) | (tiles_per_workgroup << 20) | (BM << 10) | BN
+ * family 1 = 256 x 256 persistent kernel, every workgroup one tile; 2 = the same kernel, workgroups loop over up to tiles_per_workgroup
+ * tiles; 3 = mid-size tile kernel (128 x 256 / 128 x 192 / 128 x 128 / 64 x 128 / 64 x 64, loader waves); 4 = v1 kernel (128 x 128 /
+ * 128 x 64 / 64 x 64, ragged N); 0 = no kernel takes it (the launch would return LDT_ESHAPE / LDT_EALIGN).  The query assumes what
+ * ldt_gemm_bf16's common call has: the residual in place (ldr = ldo), no per-sample gate stride or skip operand that breaks 16-byte rows.
+ * max_wgs: cap on the workgroups of the launch (0 = all CUs), as ldt_score_plan.gemm_wgs.  tiles_per_workgroup saturates at 255. */
+int ldt_gemm_route(int32_t epilogue, int32_t M, int32_t N, int32_t K, int64_t ldo, int32_t fold, int32_t max_wgs);
 /* Attention + output projection + gated residual in one kernel, for narrow blocks (the Compressor: Dh = 32,
  * C = H*Dh in {64, 128}; model/layers.py:183-200 then :218 / :225):
  *     X[b] += gate[b] * (Wo . O'[b] + bo),   O' = softmax(Q K^T / sqrt(Dh)) V written as [H][Nq][Dh] and re-read as

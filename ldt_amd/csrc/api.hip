@@ -100,6 +100,13 @@ extern "C" int ldt_attention_fwd(const uint16_t* Q, int64_t ldq, int64_t q_batch
     return ldt_attn_launch(&a, head_dim, ST(stream));
 }
 extern "C" int ldt_attention_route(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim) { return ldt_attn_route(B, H, Nq, Nk, head_dim); }
+extern "C" int ldt_gemm_route(int32_t epilogue, int32_t M, int32_t N, int32_t K, int64_t ldo, int32_t fold, int32_t max_wgs) {
+    GemmArgs a{};
+    a.M = M; a.N = N; a.K = K; a.ldo = ldo; a.ldr = ldo; a.max_wgs = max_wgs;
+    if (fold != 0 && fold != 32 && fold != 256) return 0;
+    const GemmRoute r = ldt_gemm_decide(epilogue, &a, fold);
+    return (r.family << 28) | ((r.tiles_per_wg < 255 ? r.tiles_per_wg : 255) << 20) | (r.bm << 10) | r.bn;
+}
 extern "C" int ldt_attention_oproj_resid(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K,
                                          int64_t ldk, const uint16_t* V, int64_t ldv, int64_t kv_batch_stride,
                                          int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim,

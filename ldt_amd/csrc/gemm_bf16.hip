@@ -1253,7 +1253,7 @@ static bool gemm256_takes(int epi, const GemmArgs* a) {
 }
 
 template <int EPI, int FOLD = FOLD_NONE>
-static int launch_256(const GemmArgs* a_in, hipStream_t stream) {
+static int launch_256(const GemmArgs* a_in, const GemmRoute& route, hipStream_t stream) {
     // Tile order: wide outputs (QKV: 12 column tiles, MLP-up: 16) are swept in groups of row panels, so an XCD's 32 workgroups hold a
     // block of tiles (round 2-5: 8 x 4 = 8 X panels + 4 W panels in its 4 MiB L2; round 6: 4 x 8) instead of 2 x 16 — the W panel set is
     // then re-streamed from the fabric once per group of row panels, not once per 2 (profiles/: MLP-up fetched 2.5x its unique bytes in
@@ -1279,9 +1279,7 @@ static int launch_256(const GemmArgs* a_in, hipStream_t stream) {
     static const int wreg_env = getenv("LDT_GEMM_WREG") ? atoi(getenv("LDT_GEMM_WREG")) : -1;      // 0: off even when Wp is given; 1: pack on the fly (tools/dbg)
     const int wreg_dbg = g_dbg_wreg.load() >= 0 ? g_dbg_wreg.load() : wreg_env;
     const int tiles = tm * tn;
-    static const int cap = getenv("LDT_GEMM_GRID") ? atoi(getenv("LDT_GEMM_GRID")) : LDT_NUM_CUS;   // tools/dbg: > 256 = non-persistent
-    const int lim = (a->max_wgs > 0 && a->max_wgs < cap) ? a->max_wgs : cap;
-    const int grid = tiles < lim ? tiles : lim;                          // one persistent workgroup per CU (or per CU of this stream's share)
+    const int grid = route.grid;                                         // one persistent workgroup per CU (or per CU of this stream's share): ldt_gemm_decide
     if constexpr (EPI == EPI_RESID_F32) {
         if (xring && grid == tiles && a->dbg == 0) {                     // every workgroup has exactly one tile: the ring is idle in its epilogue
             if (WREG_BUILT && wreg_dbg == 1 && !a_copy.Wp) a_copy.Wp = dbg_wfrag_cached(a->W, a->ldw, a->N, a->K, stream);
@@ -1365,6 +1363,74 @@ bool ldt_gemm_lnfold_v1_route(int M, int D, int F, int max_wgs) {
            ldt_gemm_mid_lnfold_takes(EPI_BF16, M, 3 * D, D) && ldt_gemm_mid_lnfold_takes(EPI_GELU_BF16, M, F, D);
 }
 
+// The dispatch rule (kernels.h): family, tile and grid of a GEMM.  Shape-level only: pointer and alignment checks stay with the launchers.
+GemmRoute ldt_gemm_decide(int epi, const GemmArgs* a, int granule) {
+    GemmRoute r{};
+    if (!(a->M > 0 && a->N > 0 && a->K > 0) || a->K % BK != 0 || a->ldo % 4 != 0) return r;
+    const int lim = (a->max_wgs > 0 && a->max_wgs < LDT_NUM_CUS) ? a->max_wgs : LDT_NUM_CUS;
+    auto take_256 = [&]() {
+        static const int cap = getenv("LDT_GEMM_GRID") ? atoi(getenv("LDT_GEMM_GRID")) : LDT_NUM_CUS;   // tools/dbg: > 256 = non-persistent
+        const int glim = (a->max_wgs > 0 && a->max_wgs < cap) ? a->max_wgs : cap;
+        const int tiles = (a->M / 256) * (a->N / 256);
+        r.grid = tiles < glim ? tiles : glim;
+        r.family = r.grid == tiles ? GEMM_ROUTE_256_ONE : GEMM_ROUTE_256_MULTI;
+        r.bm = r.bn = 256;
+        r.tiles_per_wg = (tiles + r.grid - 1) / r.grid;
+    };
+    auto take_mid = [&](int shape) {
+        r.family = GEMM_ROUTE_MID; r.bm = shape >> 16; r.bn = shape & 0xffff; r.tiles_per_wg = 1;
+        r.grid = ((a->M + r.bm - 1) / r.bm) * (a->N / r.bn);
+    };
+    if (granule) {
+        // LN-folded forms.  Large batches: the 256-tile kernel (statistics per 256 columns).  Small batches: the mid-size tile kernel
+        // (statistics per 32 columns), when it takes the problem in a folded form.
+        const bool producer = epi == EPI_RESID_F32;
+        if (!producer && epi != EPI_BF16 && epi != EPI_GELU_BF16) return r;
+        if (granule == 32) {
+            if (a->M % 128 != 0 || a->N % 64 != 0 || a->K < 128) return r;
+            const int shape = ldt_gemm_mid_lnfold_shape(epi, a);
+            if (shape) take_mid(shape);
+        } else if (granule == 256) {
+            if (a->M % 256 != 0 || a->N % 256 != 0 || a->K < 256 || !gemm256_takes(epi, a)) return r;
+            if (!producer && (a->K % 256 != 0 || a->K > 1024)) return r;
+            take_256();
+        }
+        return r;
+    }
+    const int force = gemm_variant_env();
+    // 256^2 persistent kernel when its tiles fill at least 5/8 of the workgroups this launch may use (all CUs, or a
+    // sub-batch stream's share): at exactly half (M = 8192, N = 1024: 128 tiles on 256 CUs) the 128^2 kernel on every CU
+    // is as fast (K = 1024) or 15 % faster (K = 4096).
+    // (N <= 128 — the Compressor's 128-channel convs over millions of point rows — would leave half of every 256-wide tile
+    //  empty: the 128^2 kernel streams those 5.7 % faster end to end, tools/dbg/c4_chunks.py)
+    const int tiles256 = ((a->M + 255) / 256) * ((a->N + 255) / 256);
+    const bool big = tiles256 * 8 >= lim * 5 && a->N > 128;
+    if (force == 0 && !big) {
+        // mid-size problems (gemm_mid.hip): 128 x 256 / 128 x 192 / 128 x 128 / 64 x 128 / 64 x 64 tiles with dedicated loader waves, when
+        // the 256^2 persistent kernel would leave CUs idle — the 1-4k-row batches
+        const int shape = ldt_gemm_mid_shape(epi, a);
+        if (shape) { take_mid(shape); return r; }
+    }
+    if ((force == 256 || (force == 0 && big)) && gemm256_takes(epi, a)) { take_256(); return r; }
+    // v1 tile shape: the largest of 128x128 / 128x64 / 64x64 that still gives every CU two tiles
+    auto ntiles = [&](int bm, int bn) { return (long)((a->M + bm - 1) / bm) * ((a->N + bn - 1) / bn); };
+    static const int v1_shape = getenv("LDT_GEMM_V1_SHAPE") ? atoi(getenv("LDT_GEMM_V1_SHAPE")) : -1;   // tools/dbg
+    // this 2-phase kernel hides a stage's load latency only across co-resident workgroups: want >= 2 tiles per CU
+    // (M = 2048: QKV 25.8 -> 22.9 us with 128x64, fc_o 14.4 -> 12.0 and mlp.out 47.7 -> 40.0 us with 64x64 tiles)
+    const int shape = v1_shape >= 0 ? v1_shape : (force == 128 || ntiles(128, 128) >= 2 * LDT_NUM_CUS) ? 0 : (ntiles(128, 64) >= 2 * LDT_NUM_CUS ? 1 : 2);
+    // 3 stages only for 64x64 tiles (48 KB of LDS, still 3 workgroups per CU; M = 2048: fc_o 13.5 -> 12.3, mlp.out 38.6 ->
+    // 31.3 us; a 4th stage measured equal): at 128x64 / 128x128 the third buffer costs a co-resident workgroup and loses 20-40 %
+    static const int v1_stages_env = getenv("LDT_GEMM_V1_STAGES") ? atoi(getenv("LDT_GEMM_V1_STAGES")) : 0;   // tools/dbg
+    r.family = GEMM_ROUTE_V1;
+    r.v1_shape = shape;
+    r.v1_stages = v1_stages_env ? v1_stages_env : (shape == 2 ? 3 : 2);
+    r.bm = (shape == 3) ? 256 : (shape == 2 ? 64 : 128);
+    r.bn = (shape == 0 || shape == 3 || shape == 4) ? 128 : 64;
+    r.tiles_per_wg = 1;
+    r.grid = (int)ntiles(r.bm, r.bn);
+    return r;
+}
+
 int ldt_gemm_lnfold_launch(int epi, const GemmArgs* a, hipStream_t stream) {
     // route: stats_parts says which statistics layout the caller's buffers use — K / 256 (N / 256 for the producer) parts: the 256-tile
     // kernel; K / 32 (N / 32): the mid-size tile kernel (ldt_gemm_lnfold_v1_route)
@@ -1385,31 +1451,34 @@ int ldt_gemm_lnfold_launch(int epi, const GemmArgs* a, hipStream_t stream) {
         LDT_REQUIRE(a->xs && a->ln_scale && a->stats_out && a->ldxs % 4 == 0 && a->ldxs >= a->N && ldt_aligned16(a->xs) &&
                     ldt_aligned16(a->ln_scale) && a->ln_step_stride % 4 == 0 && ldt_aligned16(a->stats_out), LDT_EARG,
                     "gemm_lnfold: producer needs xs / ln_scale / stats_out (16-byte aligned)");
+        const GemmRoute r = ldt_gemm_decide(epi, a, v1 ? 32 : 256);
         if (v1) {
-            int st = LDT_OK;
-            if (ldt_gemm_mid_lnfold_try(EPI_RESID_F32, a, stream, &st)) return st;   // mid-size tile kernel (gemm_mid.hip)
+            if (r.family == GEMM_ROUTE_MID) return ldt_gemm_mid_lnfold_launch(epi, (r.bm << 16) | r.bn, a, stream);   // mid-size tile kernel (gemm_mid.hip)
             ldt_set_error("gemm_lnfold: statistics per 32 columns are the mid-size tile kernel's; it does not take M=%d N=%d K=%d as a producer", a->M, a->N, a->K);
             return LDT_ESHAPE;
         }
-        return launch_256<EPI_RESID_F32, FOLD_PRODUCER>(a, stream);
+        LDT_REQUIRE(r.family == GEMM_ROUTE_256_ONE || r.family == GEMM_ROUTE_256_MULTI, LDT_ESHAPE,
+                    "gemm256: M=%d N=%d must be multiples of 256, K=%d of 64 (>= 128), rows 16-byte aligned", a->M, a->N, a->K);
+        return launch_256<EPI_RESID_F32, FOLD_PRODUCER>(a, r, stream);
     }
     LDT_REQUIRE(epi == EPI_BF16 || epi == EPI_GELU_BF16, LDT_EARG, "gemm_lnfold: epilogue %d has no folded form", epi);
     LDT_REQUIRE(a->stats_in && a->fold_S && a->fold_C && ldt_aligned16(a->stats_in) && ldt_aligned16(a->fold_S) && ldt_aligned16(a->fold_C) &&
                 a->fold_step_stride % 4 == 0, LDT_EARG, "gemm_lnfold: consumer needs stats_in, fold_S, fold_C (16-byte aligned)");
+    const GemmRoute r = ldt_gemm_decide(epi, a, v1 ? 32 : 256);
     if (v1) {
         LDT_REQUIRE(a->stats_parts <= 32, LDT_ESHAPE, "gemm_lnfold (v1 route): K=%d > 1024 input channels", a->K);
-        int st = LDT_OK;
-        if (ldt_gemm_mid_lnfold_try(epi, a, stream, &st)) return st;
+        if (r.family == GEMM_ROUTE_MID) return ldt_gemm_mid_lnfold_launch(epi, (r.bm << 16) | r.bn, a, stream);
         ldt_set_error("gemm_lnfold: statistics per 32 columns are the mid-size tile kernel's; it does not take M=%d N=%d K=%d as a consumer", a->M, a->N, a->K);
         return LDT_ESHAPE;
     }
     LDT_REQUIRE(a->stats_parts >= 1 && a->stats_parts <= 4 && a->stats_parts * 256 == a->K, LDT_EARG,
                 "gemm_lnfold: consumer needs stats_in[K/256 <= 4][M][2] (or [K/32][M][2] for the small-batch kernels); K=%d parts=%d", a->K, a->stats_parts);
-    return epi == EPI_BF16 ? launch_256<EPI_BF16, FOLD_CONSUMER>(a, stream) : launch_256<EPI_GELU_BF16, FOLD_CONSUMER>(a, stream);
+    LDT_REQUIRE(r.family == GEMM_ROUTE_256_ONE || r.family == GEMM_ROUTE_256_MULTI, LDT_ESHAPE,
+                "gemm256: M=%d N=%d must be multiples of 256, K=%d of 64 (>= 128), rows 16-byte aligned", a->M, a->N, a->K);
+    return epi == EPI_BF16 ? launch_256<EPI_BF16, FOLD_CONSUMER>(a, r, stream) : launch_256<EPI_GELU_BF16, FOLD_CONSUMER>(a, r, stream);
 }
 
-// LDT_GEMM_FORCE=128|256 pins the variant (A/B runs); default: see ldt_gemm_launch.
-static int gemm_variant() { return gemm_variant_env(); }
+// LDT_GEMM_FORCE=128|256 pins the variant (A/B runs); default: see ldt_gemm_decide.
 
 int ldt_gemm_launch(int epi, const GemmArgs* a, hipStream_t stream) {
     LDT_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0, LDT_ESHAPE, "gemm: empty problem M=%d N=%d K=%d", a->M, a->N, a->K);
@@ -1424,51 +1493,26 @@ int ldt_gemm_launch(int epi, const GemmArgs* a, hipStream_t stream) {
                     LDT_EARG, "gemm: gate needs rows_per_sample>0 and 16-byte aligned strides");
     }
     LDT_REQUIRE(!a->bias || ldt_aligned16(a->bias), LDT_EALIGN, "gemm: bias must be 16-byte aligned");
-    if (gemm_variant() == 0) {
-        // mid-size problems (gemm_mid.hip): 128 x 256 / 128 x 192 / 128 x 128 / 64 x 128 tiles with dedicated loader waves, when the 256^2
-        // persistent kernel would leave CUs idle (its 5/8 rule below) — the 1-4k-row batches
-        const int t256 = ((a->M + 255) / 256) * ((a->N + 255) / 256);
-        const int lim = (a->max_wgs > 0 && a->max_wgs < LDT_NUM_CUS) ? a->max_wgs : LDT_NUM_CUS;
-        const bool big = t256 * 8 >= lim * 5 && a->N > 128;
-        if (!big) {
-            const int shape = ldt_gemm_mid_shape(epi, a);
-            if (shape) return ldt_gemm_mid_launch(epi, shape, a, stream);
-        }
-    }
-    const int tiles256 = ((a->M + 255) / 256) * ((a->N + 255) / 256);
-    const int force = gemm_variant();
-    // 256^2 persistent kernel when its tiles fill at least 5/8 of the workgroups this launch may use (all CUs, or a
-    // sub-batch stream's share): at exactly half (M = 8192, N = 1024: 128 tiles on 256 CUs) the 128^2 kernel on every CU
-    // is as fast (K = 1024) or 15 % faster (K = 4096).
-    const int lim256 = (a->max_wgs > 0 && a->max_wgs < LDT_NUM_CUS) ? a->max_wgs : LDT_NUM_CUS;
-    // (N <= 128 — the Compressor's 128-channel convs over millions of point rows — would leave half of every 256-wide tile
-    //  empty: the 128^2 kernel streams those 5.7 % faster end to end, tools/dbg/c4_chunks.py)
-    if ((force == 256 || (force == 0 && tiles256 * 8 >= lim256 * 5 && a->N > 128)) && gemm256_takes(epi, a)) {
+    const GemmRoute r = ldt_gemm_decide(epi, a, 0);
+    if (r.family == GEMM_ROUTE_MID) return ldt_gemm_mid_launch(epi, (r.bm << 16) | r.bn, a, stream);
+    if (r.family == GEMM_ROUTE_256_ONE || r.family == GEMM_ROUTE_256_MULTI) {
         switch (epi) {
-            case EPI_F32: return launch_256<EPI_F32>(a, stream);
-            case EPI_BF16: return launch_256<EPI_BF16>(a, stream);
-            case EPI_GELU_BF16: return launch_256<EPI_GELU_BF16>(a, stream);
-            case EPI_RELU_BF16: return launch_256<EPI_RELU_BF16>(a, stream);
-            case EPI_RESID_F32: return launch_256<EPI_RESID_F32>(a, stream);
+            case EPI_F32: return launch_256<EPI_F32>(a, r, stream);
+            case EPI_BF16: return launch_256<EPI_BF16>(a, r, stream);
+            case EPI_GELU_BF16: return launch_256<EPI_GELU_BF16>(a, r, stream);
+            case EPI_RELU_BF16: return launch_256<EPI_RELU_BF16>(a, r, stream);
+            case EPI_RESID_F32: return launch_256<EPI_RESID_F32>(a, r, stream);
             default: ldt_set_error("gemm: unknown epilogue %d", epi); return LDT_EARG;
         }
     }
-    // v1 tile shape: the largest of 128x128 / 128x64 / 64x64 that still gives every CU two tiles
+    LDT_REQUIRE(r.family == GEMM_ROUTE_V1, LDT_ESHAPE, "gemm: no kernel takes M=%d N=%d K=%d", a->M, a->N, a->K);
+    const int shape = r.v1_shape, v1_stages = r.v1_stages;
     auto ntiles = [&](int bm, int bn) { return (long)((a->M + bm - 1) / bm) * ((a->N + bn - 1) / bn); };
-    static const int v1_shape = getenv("LDT_GEMM_V1_SHAPE") ? atoi(getenv("LDT_GEMM_V1_SHAPE")) : -1;   // tools/dbg
-    // this 2-phase kernel hides a stage's load latency only across co-resident workgroups: want >= 2 tiles per CU
-    // (M = 2048: QKV 25.8 -> 22.9 us with 128x64, fc_o 14.4 -> 12.0 and mlp.out 47.7 -> 40.0 us with 64x64 tiles)
-    const int shape = v1_shape >= 0 ? v1_shape : (force == 128 || ntiles(128, 128) >= 2 * LDT_NUM_CUS) ? 0 : (ntiles(128, 64) >= 2 * LDT_NUM_CUS ? 1 : 2);
     dim3 block(256);
-    // 3 stages only for 64x64 tiles (48 KB of LDS, still 3 workgroups per CU; M = 2048: fc_o 13.5 -> 12.3, mlp.out 38.6 ->
-    // 31.3 us; a 4th stage measured equal): at 128x64 / 128x128 the third buffer costs a co-resident workgroup and loses 20-40 %
-    static const int v1_stages_env = getenv("LDT_GEMM_V1_STAGES") ? atoi(getenv("LDT_GEMM_V1_STAGES")) : 0;   // tools/dbg
-    const int v1_stages = v1_stages_env ? v1_stages_env : (shape == 2 ? 3 : 2);
     static const int v1_map_env = getenv("LDT_GEMM_V1_MAP") ? atoi(getenv("LDT_GEMM_V1_MAP")) : -1;         // tools/dbg: 0 / 1 force
     GemmArgs a_v1 = *a;
     {
-        const int bm = (shape == 3) ? 256 : (shape == 2 ? 64 : 128), bn = (shape == 0 || shape == 3 || shape == 4) ? 128 : 64;
-        const long tm = (a->M + bm - 1) / bm, tn = (a->N + bn - 1) / bn;
+        const long tm = (a->M + r.bm - 1) / r.bm, tn = (a->N + r.bn - 1) / r.bn;
         a_v1.col_major = v1_map_env >= 0 ? v1_map_env : (tn >= 3 * tm ? 1 : 0);
     }
     a = &a_v1;

@@ -904,43 +904,45 @@ static int mid_fold_launch_t(const GemmArgs& a, hipStream_t stream) {
     return ldt_check_launch("gemm_bf16_nt_mid(fold)");
 }
 
-// would the folded form of this GEMM (M x N x K, statistics per 32 columns) be taken?  (Score.can_fold / ldt_gemm_lnfold_v1_route)
-bool ldt_gemm_mid_lnfold_takes(int epi, int M, int N, int K) {
-    if (!mid_env()) return false;
-    GemmArgs g{};
-    g.M = M; g.N = N; g.K = K; g.ldo = N; g.ldr = N;
-    const int shape = mid_shape_for(epi, &g, epi == EPI_RESID_F32 ? 1 : 2);
-    if (!shape) return false;
-    if (epi == EPI_RESID_F32) return N % 32 == 0;
-    return K % 32 == 0 && K / 32 <= 32 && K / MID_BK >= MidCfg<128, 256>::NS + 2;
+// Tile of the folded form of this GEMM (statistics per 32 columns), 0 = not taken: the producer's statistics granule is a wave's 32 columns
+// of a 128-column tile; the consumer's loader waves assume the whole ring is in flight and <= 32 partials per row.  (ldt_gemm_decide)
+int ldt_gemm_mid_lnfold_shape(int epi, const GemmArgs* a) {
+    if (!mid_env() || !(epi == EPI_RESID_F32 || epi == EPI_BF16 || epi == EPI_GELU_BF16)) return 0;
+    const int shape = mid_shape_for(epi, a, epi == EPI_RESID_F32 ? 1 : 2);
+    if (!shape) return 0;
+    const int bm = shape >> 16, bn = shape & 0xffff;
+    if (epi == EPI_RESID_F32) return (bn == 128 && a->N % 32 == 0) ? shape : 0;
+    return (bm == 128 && a->K % 32 == 0 && a->K / 32 <= 32 && a->K / MID_BK >= MidCfg<128, 256>::NS + 2) ? shape : 0;
 }
 
-bool ldt_gemm_mid_lnfold_try(int epi, const GemmArgs* a_in, hipStream_t stream, int* status) {
-    if (!mid_env()) return false;
-    const int shape = mid_shape_for(epi, a_in, epi == EPI_RESID_F32 ? 1 : 2);
-    if (!shape) return false;
+// would the folded form of this GEMM (M x N x K, statistics per 32 columns) be taken?  (Score.can_fold / ldt_gemm_lnfold_v1_route)
+bool ldt_gemm_mid_lnfold_takes(int epi, int M, int N, int K) {
+    GemmArgs g{};
+    g.M = M; g.N = N; g.K = K; g.ldo = N; g.ldr = N;
+    return ldt_gemm_mid_lnfold_shape(epi, &g) != 0;
+}
+
+int ldt_gemm_mid_lnfold_launch(int epi, int shape, const GemmArgs* a_in, hipStream_t stream) {
     const int bm = shape >> 16, bn = shape & 0xffff;
     GemmArgs a = *a_in;
     static const int map_env = getenv("LDT_GEMM_MID_MAP") ? atoi(getenv("LDT_GEMM_MID_MAP")) : -1;
     a.col_major = map_env >= 0 ? map_env : 1;
-    if (epi == EPI_RESID_F32) {                          // producer: a wave's 32 columns are the statistics granule
-        if (bn != 128 || a.stats_parts * 32 != a.N) return false;
-        *status = bm == 64 ? mid_fold_launch_t<EPI_RESID_F32, 64, 128, MID_FOLD_PRODUCER>(a, stream)
-                           : mid_fold_launch_t<EPI_RESID_F32, 128, 128, MID_FOLD_PRODUCER>(a, stream);
-        return true;
+    if (epi == EPI_RESID_F32) {                          // producer
+        LDT_REQUIRE(bn == 128 && a.stats_parts * 32 == a.N, LDT_ESHAPE, "gemm_mid(fold): producer needs 128-column tiles and stats[N/32][M][2]");
+        return bm == 64 ? mid_fold_launch_t<EPI_RESID_F32, 64, 128, MID_FOLD_PRODUCER>(a, stream)
+                        : mid_fold_launch_t<EPI_RESID_F32, 128, 128, MID_FOLD_PRODUCER>(a, stream);
     }
-    // consumer: the loader waves' statistics pass assumes the whole ring is in flight and <= 32 partials per row
-    if (bm != 128 || a.stats_parts > 32 || a.stats_parts * 32 != a.K || a.K / MID_BK < MidCfg<128, 256>::NS + 2) return false;
+    LDT_REQUIRE(bm == 128 && a.stats_parts <= 32 && a.stats_parts * 32 == a.K, LDT_ESHAPE, "gemm_mid(fold): consumer needs 128-row tiles and stats[K/32 <= 32][M][2]");
     if (epi == EPI_BF16)
-        *status = bn == 256 ? mid_fold_launch_t<EPI_BF16, 128, 256, MID_FOLD_CONSUMER>(a, stream)
-                : bn == 192 ? mid_fold_launch_t<EPI_BF16, 128, 192, MID_FOLD_CONSUMER>(a, stream)
-                            : mid_fold_launch_t<EPI_BF16, 128, 128, MID_FOLD_CONSUMER>(a, stream);
-    else if (epi == EPI_GELU_BF16)
-        *status = bn == 256 ? mid_fold_launch_t<EPI_GELU_BF16, 128, 256, MID_FOLD_CONSUMER>(a, stream)
-                : bn == 192 ? mid_fold_launch_t<EPI_GELU_BF16, 128, 192, MID_FOLD_CONSUMER>(a, stream)
-                            : mid_fold_launch_t<EPI_GELU_BF16, 128, 128, MID_FOLD_CONSUMER>(a, stream);
-    else return false;
-    return true;
+        return bn == 256 ? mid_fold_launch_t<EPI_BF16, 128, 256, MID_FOLD_CONSUMER>(a, stream)
+             : bn == 192 ? mid_fold_launch_t<EPI_BF16, 128, 192, MID_FOLD_CONSUMER>(a, stream)
+                         : mid_fold_launch_t<EPI_BF16, 128, 128, MID_FOLD_CONSUMER>(a, stream);
+    if (epi == EPI_GELU_BF16)
+        return bn == 256 ? mid_fold_launch_t<EPI_GELU_BF16, 128, 256, MID_FOLD_CONSUMER>(a, stream)
+             : bn == 192 ? mid_fold_launch_t<EPI_GELU_BF16, 128, 192, MID_FOLD_CONSUMER>(a, stream)
+                         : mid_fold_launch_t<EPI_GELU_BF16, 128, 128, MID_FOLD_CONSUMER>(a, stream);
+    ldt_set_error("gemm_mid(fold): epilogue %d has no folded form", epi);
+    return LDT_EARG;
 }
 
 // QKV projection + self-attention in one launch (mid_epilogue_attn): 32-token samples, head dim 64, N = 3 * hidden with hidden % 64 == 0,

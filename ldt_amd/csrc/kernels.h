@@ -77,10 +77,23 @@ struct SgemmArgs {
 };
 
 int ldt_gemm_launch(int epi, const GemmArgs* a, hipStream_t stream);
+// Which kernel a GEMM runs on: THE dispatch rule.  ldt_gemm_launch, ldt_gemm_lnfold_launch and the ldt_gemm_route query (include/ldt_hip.h)
+// all call ldt_gemm_decide and nothing else chooses a family, a tile or a grid.  granule: 0 = plain GEMM; 256 / 32 = LN-folded form with
+// statistics per that many columns (producer when epi == EPI_RESID_F32, consumer otherwise).  Reads M, N, K, ldo, ldr, skip / lds_, gate /
+// gate_sample_stride and max_wgs of `a`, no pointer's target.  family GEMM_ROUTE_NONE: no kernel takes the problem (the launchers report why).
+enum { GEMM_ROUTE_NONE = 0, GEMM_ROUTE_256_ONE = 1, GEMM_ROUTE_256_MULTI = 2, GEMM_ROUTE_MID = 3, GEMM_ROUTE_V1 = 4 };
+struct GemmRoute {
+    int family, bm, bn;
+    int tiles_per_wg;                   // most tiles one workgroup computes (> 1: the persistent 256-tile kernel only)
+    int grid;                           // workgroups launched
+    int v1_shape, v1_stages;            // GEMM_ROUTE_V1: index of the instantiation (0 128x128, 1 128x64, 2 64x64; tools/dbg: 3, 4) and its stages
+};
+GemmRoute ldt_gemm_decide(int epi, const GemmArgs* a, int granule);
 int ldt_gemm_mid_shape(int epi, const GemmArgs* a);                // gemm_mid.hip: (BM << 16) | BN of the mid-size tile kernel for this problem, 0 = not taken
 int ldt_gemm_mid_launch(int epi, int shape, const GemmArgs* a, hipStream_t stream);
+int ldt_gemm_mid_lnfold_shape(int epi, const GemmArgs* a);          // (BM << 16) | BN of the LN-folded form (statistics per 32 columns) of this GEMM, 0 = not taken
 bool ldt_gemm_mid_lnfold_takes(int epi, int M, int N, int K);       // would the LN-folded form (statistics per 32 columns) of this GEMM be taken?
-bool ldt_gemm_mid_lnfold_try(int epi, const GemmArgs* a, hipStream_t stream, int* status);
+int ldt_gemm_mid_lnfold_launch(int epi, int shape, const GemmArgs* a, hipStream_t stream);   // shape: ldt_gemm_mid_lnfold_shape's
 bool ldt_gemm_mid_qkv_attn_try(const GemmArgs* a, int tokens, int head_dim, bool folded, hipStream_t stream, int* status);
 bool ldt_gemm_qkv_attn256_try(const GemmArgs* a, int tokens, int head_dim, bool folded, hipStream_t stream, int* status);   // gemm_bf16.hip: fused QKV + self-attention at 256 tokens, Dh 64; false = not taken
 bool ldt_gemm_mid_q_xattn_try(const GemmArgs* a, int tokens, int cond_tokens, int head_dim, hipStream_t stream, int* status);   // fused q projection + cross-attention (32 x 32 tokens, Dh 64); false = not taken

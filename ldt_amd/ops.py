@@ -1,5 +1,7 @@
 """Tensor-level wrappers over the C-ABI (ldt_amd/_lib.py).  PyTorch is used only for device
 memory and the current HIP stream; every arithmetic op below runs in libldt_hip.so."""
+import collections
+
 import torch
 
 from . import _lib
@@ -70,6 +72,18 @@ def gemm_bf16(x, w, bias=None, epilogue=EPI_BF16, out=None, resid=None, skip=Non
                               _p(gate), gate_sample_stride, rows_per_sample, _p(step_ptr), gate_step_stride,
                               M, N, K, stream_ptr()), "ldt_gemm_bf16")
     return out
+
+
+GemmRoute = collections.namedtuple("GemmRoute", "family bm bn tiles_per_wg")
+GEMM_FAMILIES = ("none", "256-one-tile", "256-multi-tile", "mid", "v1")
+
+
+def gemm_route(epilogue, M, N, K, ldo=None, fold=0, max_wgs=0):
+    """Which kernel gemm_bf16 (fold = 0) or the LN-folded producer / consumer (fold = 256 or 32: the statistics granule; producer when
+    epilogue is EPI_RESID_F32) runs for this shape: the launcher's own decision (ldt_gemm_route), no launch.  -> GemmRoute(family in
+    GEMM_FAMILIES, bm, bn, tiles_per_wg)."""
+    r = int(lib().ldt_gemm_route(int(epilogue), int(M), int(N), int(K), int(N if ldo is None else ldo), int(fold), int(max_wgs)))
+    return GemmRoute(GEMM_FAMILIES[r >> 28], (r >> 10) & 1023, r & 1023, (r >> 20) & 255)
 
 
 def gemm_resid_lnstats(x, w, bias, out, ln_scale, gate=None, gate_sample_stride=0, rows_per_sample=0, step_ptr=None,

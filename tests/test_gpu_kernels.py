@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_checks as kc
 from conftest import rel_mse
 
 pytestmark = pytest.mark.gpu
@@ -48,6 +49,7 @@ def test_gemm_all_epilogues(M, N, K):
     assert rel_mse(out.cpu(), ref) < 1e-9
     out = ops.gemm_bf16(xd, wd, bd, EPI_BF16)
     assert rel_mse(out.float().cpu(), ref) < 1e-5
+    kc.assert_elementwise(out.cpu(), ref, kc.gemm_tol(x, w, bias, K, torch.bfloat16, ref=ref), "BF16 %dx%dx%d" % (M, N, K))
     out = ops.gemm_bf16(xd, wd, bd, EPI_GELU_BF16)
     assert rel_mse(out.float().cpu(), torch.nn.functional.gelu(ref)) < 1e-5
     skip = bf(torch.randn(M, N, generator=g))
@@ -72,14 +74,17 @@ def test_gemm_all_epilogues(M, N, K):
 @pytest.mark.parametrize("M,N,K", [(2048, 4096, 1024), (2048, 3072, 1024), (2048, 1024, 4096), (1024, 4096, 1024), (1024, 1024, 1024),
                                    (2048, 4096, 64), (2048, 4096, 128), (2048, 4096, 192), (1152, 1536, 64), (1152, 1536, 192),
                                    (1000, 2304, 320), (1960, 4096, 320), (4096, 1024, 1024),
-                                   # 64 x 128 tiles (4-stage ring, K-tile-deep register double buffering): 1..5 K-tiles, ragged rows
+                                   # 64 x 128 tiles (4-stage ring, K-tile-deep register double buffering): 1..5 K-tiles; (1000, 1024, 448): 64 x 64, ragged rows
                                    (2048, 1024, 64), (2048, 1024, 128), (2048, 1024, 192), (2048, 1024, 256), (2048, 1024, 320), (1000, 1024, 448),
-                                   # 128 x 192 tiles (bf16-output epilogues; the fp32 ones of these shapes take another form)
+                                   # 128 x 192 tiles for the bf16-output epilogues; the fp32 ones of these shapes run 128 x 256
                                    (2048, 3072, 64), (2048, 3072, 192), (1990, 3072, 320),
                                    # 64 x 64 tiles (6-stage ring): fewer K-tiles than stages, exactly as many, more; ragged rows
                                    (1024, 1024, 64), (1024, 1024, 128), (1024, 1024, 384), (1024, 1024, 448), (1000, 1024, 704)])
 def test_gemm_mid_kernel(M, N, K):
-    """The mid-size tile kernel (csrc/gemm_mid.hip: 128 x 256 / 128 x 128 / 64 x 128 tiles, loader waves, 3- / 4-stage ring) on the shapes the launcher hands
+    """The mid-size tile kernel (csrc/gemm_mid.hip: 128 x 256 / 128 x 192 / 128 x 128 / 64 x 128 / 64 x 64 tiles, loader waves, 3- / 4- / 6-stage
+    ring) on the shapes the launcher hands it.  Tile forms as ops.gemm_route reports them: first line of the list 128 x 256 (N = 4096, M = 2048),
+    128 x 256 fp32 / 128 x 192 bf16 (2048 x 3072), 64 x 128 (2048 x 1024 x 4096, 1152 x 1536), 128 x 128 (1024 x 4096, 1000 x 2304, 4096 x 1024),
+    64 x 64 (1024 x 1024); test_gpu_kernel_exact.py pins every form to a shape and asserts the route before it launches.  Here:
     it — incl. 1 / 2 / 3 / 5 K-tiles (prologue and drain paths of the ring), a ragged last row tile, a step-indexed shared gate, a per-sample
     gate — vs fp64 on the same bf16 operands."""
     from ldt_amd._lib import EPI_BF16, EPI_F32, EPI_GELU_BF16, EPI_RESID_F32
@@ -91,6 +96,7 @@ def test_gemm_mid_kernel(M, N, K):
     assert rel_mse(ops.gemm_bf16(xd, wd, bd, EPI_F32).cpu(), ref) < 1e-9
     o1 = ops.gemm_bf16(xd, wd, bd, EPI_BF16)
     assert rel_mse(o1.float().cpu(), ref) < 1e-5
+    kc.assert_elementwise(o1.cpu(), ref, kc.gemm_tol(x, w, bias, K, torch.bfloat16, ref=ref), "BF16 %dx%dx%d" % (M, N, K))
     assert torch.equal(o1, ops.gemm_bf16(xd, wd, bd, EPI_BF16))                  # no race: identical twice
     assert rel_mse(ops.gemm_bf16(xd, wd, bd, EPI_GELU_BF16).float().cpu(), torch.nn.functional.gelu(ref)) < 1e-5
     resid = torch.randn(M, N, generator=g)
@@ -155,6 +161,11 @@ def test_gemm_lnfold_pair(M, D, N2, gelu, granule):
     y0 = ops.gemm_bf16(hb, dev(w2, torch.bfloat16), dev(b2), EPI_GELU_BF16 if gelu else EPI_BF16)
     e_fold, e_ln = rel_mse(y.float().cpu(), ref), rel_mse(y0.float().cpu(), ref)
     assert e_fold < 3e-5 and e_fold < 4 * e_ln + 1e-6, (e_fold, e_ln)
+    # per element: xs was rounded to bf16 BEFORE the row mean came off, so each output carries 2^-8 |xs| through |w2| / sigma, plus its own
+    # bf16 rounding (the exact-operand bound of the consumer alone: test_gpu_kernel_exact.py)
+    rstd = 1 / torch.sqrt(xn.var(1, unbiased=False, keepdim=True) + 1e-6)
+    tol = 1.05 * kc.U8 * rstd * (xs.float().cpu().double().abs() @ w2.double().abs().T) + kc.U8 * ref.abs() + 1e-5
+    kc.assert_elementwise(y.cpu(), ref, tol * (kc.GELU_SLOPE if gelu else 1.0), "LN-fold pair %dx%dx%d granule %d" % (M, D, N2, granule))
 
 
 @pytest.mark.parametrize("ratio", [0.0, 2.0, 4.0, 8.0])
@@ -242,6 +253,10 @@ def test_attention(B, H, Nq, Nk, dh):
     assert out.shape == (B, H, Nq, dh)
     assert rel_mse(out.float().cpu(), ref) < 2e-5
     assert float((out.float().cpu() - ref).abs().max()) < 0.05
+    # per element: the bf16 output + P rounded to bf16 before P V (2^-8 of the largest |v| of the head's channel)
+    vmax = kv[..., C:].reshape(B, Nk, H, dh).permute(0, 2, 1, 3).double().abs().amax(2, keepdim=True)
+    kc.assert_elementwise(out.cpu().reshape(-1, dh), ref.reshape(-1, dh), (kc.U8 * ref.abs() + kc.U8 * vmax).reshape(-1, dh),
+                          "attention B %d H %d Nq %d Nk %d Dh %d" % (B, H, Nq, Nk, dh))
 
 
 def test_attention_softmax_spike():
@@ -605,3 +620,24 @@ torch.save(outs, sys.argv[1])
         for k in base:
             assert torch.equal(cur[k], base[k]), "LDT_RESID_RING=%s LDT_GEMM_WREG=%s LDT_GEMM_GM=%s differs from the register-epilogue path in %s" % (key + (k,))
     assert bool(torch.isfinite(base["x1"]).all()) and float(base["x1"].abs().mean()) > 0.1 and float(base["u"].float().abs().mean()) > 0.01
+    # the five-way bit-equality anchored to a reference: the baseline's q (plain bf16 projection of xs) and u (LN-folded consumer + GELU on
+    # xs and the producer's statistics) against float64 from the same operands, per element (float64 matmul on the device)
+    g = torch.Generator().manual_seed(11)
+    M, D, K = 16384, 1024, 1024
+    for shape in ((M, K), (D, K), (M, 4 * K), (D, 4 * K), (D,), (1, D)):           # the child's draws ahead of sc, in its order
+        torch.randn(*shape, generator=g)
+    torch.randn(D, generator=g)                                                   # sc (the statistics below are read from the kernel's st)
+    wu = (torch.randn(4 * D, D, generator=g) / 32).bfloat16().cuda().double(); S = torch.randn(4 * D, generator=g).cuda().double(); C = torch.randn(4 * D, generator=g).cuda().double()
+    wq = (torch.randn(3 * D, D, generator=g) / 32).bfloat16().cuda().double(); bq = torch.randn(3 * D, generator=g).cuda().double()
+    xs = base["xs"].cuda().double(); st = base["st"].cuda().double().sum(0)
+    ref = xs @ wq.T + bq
+    acc = (xs.abs() @ wq.abs().T + bq.abs()) * (kc.C_ACC * K * kc.U24)
+    kc.assert_elementwise(base["q"].cuda(), ref, acc * (1 + kc.U8) + kc.U8 * ref.abs(), "q = xs wq^T + bq (16384 x 3072 x 1024, 256-tile kernel, three tiles per workgroup)")
+    mean = st[:, 0:1] / D
+    rstd = 1 / torch.sqrt((st[:, 1:2] / D - mean * mean).clamp_min(0) + 1e-6)
+    mm = xs @ wu.T
+    t1, t2 = rstd * mm, rstd * mean * S
+    ref = torch.nn.functional.gelu(t1 - t2 + C)
+    acc = rstd * (xs.abs() @ wu.abs().T) * (kc.C_ACC * K * kc.U24) + 2.0 ** -19 * (t1.abs() + t2.abs() + C.abs())
+    kc.assert_elementwise(base["u"].cuda(), ref, (acc * kc.GELU_SLOPE + kc.GELU_FAST_ABS) * (1 + kc.U8) + kc.U8 * ref.abs(),
+                          "u = gelu(LN-folded xs wu^T) (16384 x 4096 x 1024, 256-tile kernel, four tiles per workgroup)")
