@@ -12,8 +12,11 @@ Weights are seeded random-init (no checkpoints reachable), noise is device Philo
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --config c5 [--gpus N]           # BASELINE configs[4]: ViPC-conditioned sampling, 32 shapes per GPU, 32 tokens
     python bench.py ... --dump-outputs DIR           # + DIR/points.npy, DIR/eps.npy: what the LAST timed sample() call returned
+    python bench.py ... --full                       # + every block below that takes runs of its own (minutes, mostly the CPU oracle)
 
-Rank 0 prints ONE JSON line: metric shapes/sec (whole job) and, at N=1,
+A plain run does what the headline needs and nothing else: it builds the model, makes W warm-up and K timed calls, writes the dump if asked
+to and prints the line.  Rank 0 prints ONE JSON line: metric shapes/sec (whole job), the whole-job TFLOP/s that follow from the same wall time
+and, with --full at N=1 (`full_blocks`; each block has a --no-... switch of its own),
   roofline      dominant kernel of the Score forward, HIP-event timed inside this process, with ITS OWN PMC traffic / MFMA utilisation
                 (+ every kernel class in `roofline_kernels`, each against the roofline that bounds it; `roofline_attention` = HBM GB/s);
                 also carries every secondary figure of the line as an `x_...` scalar (the driver's record keeps only the scalar members
@@ -24,6 +27,8 @@ Rank 0 prints ONE JSON line: metric shapes/sec (whole job) and, at N=1,
                 1e-4); `ill_conditioned_random_weights`: that run's decoded-cloud figures, informational
   extra         the headline workload on the LayerNorm-kernel path (the LN-fold guard's fallback), BASELINE configs[3] (Compressor
                 B=1024), configs[4]'s per-GPU share (ViPC, B=32, T=32), shipped T=32
+and in every line
+  roofline      --config c5 only: the whole-job MFMA fraction, from the wall time of the timed steps
   rccl_ranks_seen  ranks that met in a one-int RCCL all-gather before the model was built (0: no launcher / single process)
 
 --dump-outputs DIR: weights, x0 and the Philox keys all come from the CPU generator seeded in main(), so the same arguments give the
@@ -91,10 +96,13 @@ def parse(argv=None):
                     help="start the ranks through a child `torch.distributed.run` even at --gpus 1 (the path --gpus N > 1 takes "
                          "when no launcher started this process)")
     ap.add_argument("--sde-steps", type=int, default=1000)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the C1 oracle run (cpu_baseline + parity)")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the configs[3] / configs[4] / T=32 blocks")
-    ap.add_argument("--budget-s", type=float, default=540.0, help="extras are skipped once the run is older than this")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline does not need: per-kernel rooflines, the CPU-oracle baseline "
+                         "with its parity blocks, the extra workloads (minutes; the four options below choose among them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the C1 oracle run (cpu_baseline + parity)")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel roofline pass")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the configs[3] / configs[4] / T=32 blocks")
+    ap.add_argument("--budget-s", type=float, default=540.0, help="with --full: extras are skipped once the run is older than this")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one returned (decoded points, sampled latents) as DIR/<name>.npy")
     args = ap.parse_args(argv)
@@ -105,6 +113,22 @@ def parse(argv=None):
     if args.batch_per_gpu is None:
         args.batch_per_gpu = 64 if args.config == "c2" else 32
     return args
+
+
+def full_blocks(args, world, conditioned):
+    """Names of the line's blocks that take runs of their own, for these arguments: none unless --full was given.  The per-kernel
+    rooflines and the extra workloads belong to the unconditional workload (`conditioned`: --config c5 is running); whatever needs the
+    CPU oracle runs in a single-rank job only."""
+    if not args.full:
+        return set()
+    blocks = set()
+    if not args.no_roofline and not conditioned:
+        blocks.add("roofline")
+    if not args.no_cpu_baseline and world == 1:
+        blocks.add("cpu_baseline")
+    if not args.no_extras and world == 1 and not conditioned:
+        blocks.add("extra")
+    return blocks
 
 
 RENDEZVOUS_RETRY_WINDOW_S = 120.0      # self_launch repeats a launch only when the child failed this early on the store's bind
@@ -857,7 +881,7 @@ def main():
               "blocks) + decode to %d points") % (args.batch_per_gpu, args.tokens, cfg.score.z_dim, args.sde_steps, cfg.data.tr_max_sample_points)
         line = {
             "metric": "shapes/sec (2048-pt, %d-step SDE sample)" % args.sde_steps, "value": round(value, 4),
-            "unit": "shapes/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "unit": "shapes/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(1e3 * dt / args.steps, 2), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
             "config": {"workload": wl, "name": args.config,
@@ -870,7 +894,8 @@ def main():
             "achieved_tflops_whole_job": round(flops_call * args.steps / dt / 1e12, 1),
             "whole_job_mfma_frac": round(flops_call * args.steps / dt / 1e12 / PEAK_BF16_TFLOPS, 4),
         }
-        if not args.no_roofline and cond is None:
+        blocks = full_blocks(args, world, cond is not None)     # empty in a plain run: the line is complete as it stands
+        if "roofline" in blocks:
             roof, roofs, kernels = roofline_pass(trainer, cfg, args.batch_per_gpu)
             log("roofline pass done: %s" % json.dumps(kernels))
             line["roofline"] = dict(roof)                # (a copy: the flat `x_` scalars below go into this object only)
@@ -878,7 +903,7 @@ def main():
                                                                         fused_into="gemm_qkv: %s" % roofs["gemm_qkv"]["kernel"])
             line["roofline_kernels"] = roofs
             line["kernels"] = kernels
-        if world == 1 and not args.no_cpu_baseline and cond is None:
+        if "cpu_baseline" in blocks and cond is None:
             base, parity = c1_baseline_and_parity(trainer, cfg)
             line["cpu_baseline"] = base
             line["parity"] = parity
@@ -888,13 +913,13 @@ def main():
             tf = flops_call * args.steps / dt / 1e12
             line["roofline"] = {"bound": "mfma", "achieved": round(tf, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
                                 "frac": round(tf / PEAK_BF16_TFLOPS, 4), "traffic": None,
-                                "scope": "whole job (Score flops of SURVEY §8d + per-sample AdaLN rows / wall time); per-kernel rooflines: --config c2"}
-            if world == 1 and not args.no_cpu_baseline:
+                                "scope": "whole job (Score flops of SURVEY §8d + per-sample AdaLN rows / wall time); per-kernel rooflines: --config c2 --full"}
+            if "cpu_baseline" in blocks:
                 base, sd_s = bounded_cpu_baseline(score, cfg, args.tokens, args.sde_steps, cond)
                 line["cpu_baseline"] = base
                 line["parity"] = vipc_parity(score, args.tokens, B, cond, sd_s)
                 line["speedup_vs_cpu"] = round(value / base["value"], 1)
-        if world == 1 and not args.no_extras and cond is None:
+        if "extra" in blocks:
             extra = {}
             for name, fn in (("c2_layernorm_kernels", lambda: extra_ln_kernels(trainer, B, args.sde_steps)),
                              ("c4_compressor_b1024", lambda: extra_c4()),

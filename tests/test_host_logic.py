@@ -565,6 +565,28 @@ def test_bench_preflight_fails_fast_before_any_model_is_built(monkeypatch):
     assert not touched                                       # nothing selected a device, nothing was built
 
 
+def test_bench_runs_only_the_headline_unless_full():
+    """A plain `bench.py` run takes no run beyond its warm-up and timed steps: the per-kernel rooflines, the CPU-oracle baseline with
+    its parity blocks and the extra workloads are behind `--full`, where the --no-... switches, the rank count and --config c5 choose
+    among them as before."""
+    import bench
+    every = {"roofline", "cpu_baseline", "extra"}
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    for argv in ([], ["--gpus", "1", "--steps", "20", "--warmup", "5"], ["--config", "c5"], ["--dump-outputs", "d"],
+                 ["--no-roofline"], ["--budget-s", "1"]):
+        for world in (1, 2):
+            assert bench.full_blocks(bench.parse(argv), world, "c5" in argv) == set(), argv
+    full = lambda *more: bench.parse(["--full", *more])
+    assert bench.full_blocks(full(), 1, False) == every
+    assert bench.full_blocks(full("--no-roofline"), 1, False) == every - {"roofline"}
+    assert bench.full_blocks(full("--no-cpu-baseline"), 1, False) == every - {"cpu_baseline"}
+    assert bench.full_blocks(full("--no-extras"), 1, False) == every - {"extra"}
+    assert bench.full_blocks(full("--no-roofline", "--no-cpu-baseline", "--no-extras"), 1, False) == set()
+    assert bench.full_blocks(full(), 2, False) == {"roofline"}                  # the oracle legs run at one rank only
+    assert bench.full_blocks(full("--config", "c5"), 1, True) == {"cpu_baseline"} and bench.full_blocks(full("--config", "c5"), 2, True) == set()
+    assert "--full" in bench.launcher_argv(["--gpus", "2", "--full"], 2, 29555)  # the ranks a bare run starts inherit it
+
+
 def test_bench_dump_outputs_writes_float_arrays_under_the_cap(tmp_path):
     """`bench.py --dump-outputs DIR`: the last timed call's (points, eps) as DIR/<name>.npy in float32 (float64 kept), whole when they
     fit the cap; above it every array keeps the same fixed ascending subset of batch rows, identical from call to call."""
