@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define LDT_ABI_VERSION 24
+#define LDT_ABI_VERSION 25
 #define LDT_OK 0
 #define LDT_EARG (-1)    /* null / inconsistent argument */
 #define LDT_ESHAPE (-2)  /* unsupported shape */
@@ -113,6 +113,29 @@ int ldt_attention_route(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t he
  * ldt_gemm_bf16's common call has: the residual in place (ldr = ldo), no per-sample gate stride or skip operand that breaks 16-byte rows.
  * max_wgs: cap on the workgroups of the launch (0 = all CUs), as ldt_score_plan.gemm_wgs.  tiles_per_workgroup saturates at 255. */
 int ldt_gemm_route(int32_t epilogue, int32_t M, int32_t N, int32_t K, int64_t ldo, int32_t fold, int32_t max_wgs);
+/* The "q | k | v projection + attention" step of a Score block, launched exactly as ldt_score_forward launches it (the forward calls the same
+ * function), so that the fused kernels can be driven alone:
+ *     self-attention (kv_cond NULL):  [q | k | v] = bf16(X[B*tokens, K] . W[3*hidden, K]^T + bias),  O = attention(q, k, v)
+ *     cross-attention (kv_cond set):  q = bf16(X . W[hidden, K]^T + bias),  K | V = rows of kv_cond (K at column 0, V at column `hidden`, row
+ *                                     stride ldkv, sample stride kv_batch_stride, elements; cond_tokens rows per sample)
+ *     folded (stats set, self only):  X = the LN-folded producer's xs, [q | k | v] = bf16(r (X W^T) - r mu fold_S + fold_C) as ldt_gemm_lnfold
+ *                                     (stats[stats_parts][B*tokens][2], K / 256 or K / 32 parts; fold_S / fold_C at + *step_ptr *
+ *                                     fold_step_stride; bias NULL: it is part of fold_C)
+ * O is the contiguous [B][heads][tokens][head_dim] buffer of ldt_attention_fwd; the softmax weights are rounded to bf16 before P V.
+ * One launch when a fused form takes the shape (ldt_qkv_attention_route != 0): QKV is then not written.  Otherwise ldt_gemm_bf16 /
+ * ldt_gemm_lnfold into QKV[B*tokens][3*hidden] (q alone in the cross form) and ldt_attention_fwd.  head_dim 32 or 64; K % 64 == 0. */
+int ldt_qkv_attention(const uint16_t* X, int64_t ldx, const uint16_t* W, int64_t ldw, const float* bias,
+                      const float* stats, int32_t stats_parts, const float* fold_S, const float* fold_C, int64_t fold_step_stride,
+                      const uint16_t* kv_cond, int64_t ldkv, int64_t kv_batch_stride, uint16_t* O, uint16_t* QKV,
+                      int32_t B, int32_t tokens, int32_t cond_tokens, int32_t hidden, int32_t heads, int32_t K, int32_t max_wgs,
+                      const int32_t* step_ptr, void* stream);
+/* Which form ldt_qkv_attention (and the forward) runs for this shape (a query, not a launch; the return value is the route, not a status):
+ * 0 = two kernels, 1 = 32-token self-attention form (128 x 192 tiles of the mid-size tile kernel), 2 = 256-token self-attention form (256 x 192
+ * tiles of the persistent kernel), 3 = 32 x 32-token cross-attention form (64 x 64 tiles).  cond_tokens > 0: cross-attention.  fold: 0 plain,
+ * 32 / 256 = folded with statistics per that many columns.  The launchers and this query evaluate the same shape rules (and the same
+ * LDT_QKV_ATTN / LDT_QKV_ATTN256 / LDT_Q_XATTN switches); a misaligned operand still sends a launch to the two-kernel path. */
+int ldt_qkv_attention_route(int32_t B, int32_t tokens, int32_t cond_tokens, int32_t hidden, int32_t heads, int32_t K, int32_t fold,
+                            int32_t max_wgs);
 /* Attention + output projection + gated residual in one kernel, for narrow blocks (the Compressor: Dh = 32,
  * C = H*Dh in {64, 128}; model/layers.py:183-200 then :218 / :225):
  *     X[b] += gate[b] * (Wo . O'[b] + bo),   O' = softmax(Q K^T / sqrt(Dh)) V written as [H][Nq][Dh] and re-read as

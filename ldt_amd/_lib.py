@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDT_HIP_LIB", os.path.join(_HERE, "libldt_hip.so"))   # override: debug builds only
-ABI_VERSION = 24
+ABI_VERSION = 25
 MAX_BLOCKS = 64
 
 EPI_F32, EPI_BF16, EPI_GELU_BF16, EPI_RELU_BF16, EPI_RESID_F32 = range(5)
@@ -63,6 +63,9 @@ SIGNATURES = {
     "ldt_attention_fwd": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "ldt_attention_route": [_i32, _i32, _i32, _i32, _i32],
     "ldt_gemm_route": [_i32, _i32, _i32, _i32, _i64, _i32, _i32],
+    "ldt_qkv_attention": [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp,
+                          _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
+    "ldt_qkv_attention_route": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32],
     "ldt_attention_oproj_resid": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp],
     "ldt_sgemm": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "ldt_sinusoid": [_vp, _vp, _vp, _i32, _i32, _vp],

@@ -295,6 +295,77 @@ struct Prof {
         if (_rc != LDT_OK) return _rc;    \
     } while (0)
 
+// The "q | k | v projection + attention" step of a Score block, exactly as the forward launches it (also exported: ldt_qkv_attention).
+// Self-attention (kv == nullptr): W = [q | k | v] rows (N = 3 * hidden); cross-attention: W = the q rows (N = hidden), K | V = the cached
+// condition rows kv / kv + hidden.  Folded (stats != nullptr): X = xs of the LN-folded producer, the consumer's S | C at fold_S / fold_C.
+struct QkvAttnStep {
+    const bf16_t* X; long ldx; const bf16_t* W; long ldw; const float* bias;
+    const float* stats; int stats_parts; const float* fold_S; const float* fold_C; long fold_step_stride;
+    const bf16_t* kv; long ldkv; long kv_batch_stride;
+    bf16_t* attn_o; bf16_t* QKV;
+    int B, tokens, cond_tokens, hidden, heads, K, max_wgs;
+    const int* step_ptr;
+};
+// 0 = two kernels (GEMM + attention), 1 = 32-token self form, 2 = 256-token self form, 3 = 32 x 32-token cross form: the fused forms'
+// shape rules in the order qkv_attention_step tries them
+static int qkv_attention_route(const GemmArgs* g, int tokens, int cond_tokens, int head_dim, bool cross, bool folded) {
+    if (cross) return ldt_gemm_mid_q_xattn_takes(g, tokens, cond_tokens, head_dim) ? 3 : 0;
+    if (ldt_gemm_mid_qkv_attn_takes(g, tokens, head_dim, folded)) return 1;
+    return ldt_gemm_qkv_attn256_takes(g, tokens, head_dim, folded) ? 2 : 0;
+}
+static int qkv_attention_step(const QkvAttnStep& q, hipStream_t s, Prof* prof) {
+    const int D = q.hidden, T = q.tokens, dh = D / q.heads;
+    const bool cross = q.kv != nullptr, folded = q.stats != nullptr;
+    const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
+    GemmArgs gq{q.X, q.ldx, q.W, q.ldw, q.bias, q.QKV, 3L * D, nullptr, 0, nullptr, 0, nullptr, 0, 0, folded ? q.step_ptr : nullptr, 0,
+                q.B * T, cross ? D : 3 * D, q.K};
+    if (folded) { gq.stats_in = q.stats; gq.stats_parts = q.stats_parts; gq.fold_S = q.fold_S; gq.fold_C = q.fold_C; gq.fold_step_stride = q.fold_step_stride; }
+    gq.max_wgs = q.max_wgs;
+    gq.attn_o = q.attn_o; gq.attn_scale_log2e = scale_log2e;
+    if (cross) { gq.attn_k = q.kv; gq.attn_v = q.kv + D; gq.attn_ldkv = q.ldkv; gq.attn_kv_batch_stride = q.kv_batch_stride; }
+    int fst = LDT_OK;
+    bool took = false;
+    // projection + attention in one launch, q | k | v never reach HBM: 32 x 32 tokens against the condition (gemm_mid.hip, mid_epilogue_xattn);
+    // 32-token samples (gemm_mid.hip, mid_epilogue_attn); 256-token samples (the 256 x 192-tile form of the persistent kernel)
+    if (cross) LAUNCH_TRY(LDT_PROF_GEMM_QKV, took, ldt_gemm_mid_q_xattn_try(&gq, T, q.cond_tokens, dh, s, &fst), fst);
+    else {
+        LAUNCH_TRY(LDT_PROF_GEMM_QKV, took, ldt_gemm_mid_qkv_attn_try(&gq, T, dh, folded, s, &fst), fst);
+        if (!took) LAUNCH_TRY(LDT_PROF_GEMM_QKV, took, ldt_gemm_qkv_attn256_try(&gq, T, dh, folded, s, &fst), fst);
+    }
+    if (took) return LDT_OK;
+    if (folded) LAUNCH(LDT_PROF_GEMM_QKV, ldt_gemm_lnfold_launch(LDT_EPI_BF16, &gq, s));
+    else LAUNCH(LDT_PROF_GEMM_QKV, ldt_gemm_launch(LDT_EPI_BF16, &gq, s));
+    const int S = cross ? q.cond_tokens : T;
+    AttnArgs at{q.QKV, 3L * D, (long)T * 3 * D, cross ? q.kv : q.QKV + D, cross ? q.ldkv : 3L * D, cross ? q.kv_batch_stride : (long)T * 3 * D,
+                cross ? q.kv + D : q.QKV + 2 * D, cross ? q.ldkv : 3L * D, q.attn_o, q.B, q.heads, T, S, scale_log2e};
+    LAUNCH(LDT_PROF_ATTN, ldt_attn_launch(&at, dh, s));
+    return LDT_OK;
+}
+
+extern "C" int ldt_qkv_attention_route(int32_t B, int32_t tokens, int32_t cond_tokens, int32_t hidden, int32_t heads, int32_t K, int32_t fold,
+                                       int32_t max_wgs) {
+    if (B <= 0 || tokens <= 0 || hidden <= 0 || heads <= 0 || hidden % heads != 0 || (fold != 0 && fold != 32 && fold != 256) || (fold && cond_tokens > 0)) return 0;
+    GemmArgs g{};
+    g.M = B * tokens; g.N = cond_tokens > 0 ? hidden : 3 * hidden; g.K = K; g.max_wgs = max_wgs;
+    g.stats_parts = fold ? K / fold : 0;
+    return qkv_attention_route(&g, tokens, cond_tokens, hidden / heads, cond_tokens > 0, fold != 0);
+}
+extern "C" int ldt_qkv_attention(const uint16_t* X, int64_t ldx, const uint16_t* W, int64_t ldw, const float* bias,
+                                 const float* stats, int32_t stats_parts, const float* fold_S, const float* fold_C, int64_t fold_step_stride,
+                                 const uint16_t* kv_cond, int64_t ldkv, int64_t kv_batch_stride, uint16_t* O, uint16_t* QKV,
+                                 int32_t B, int32_t tokens, int32_t cond_tokens, int32_t hidden, int32_t heads, int32_t K, int32_t max_wgs,
+                                 const int32_t* step_ptr, void* stream) {
+    LDT_REQUIRE(X && W && O && QKV, LDT_EARG, "qkv_attention: null pointer");
+    LDT_REQUIRE(B > 0 && tokens > 0 && hidden > 0 && heads > 0 && hidden % heads == 0 && hidden % 64 == 0 && K > 0, LDT_ESHAPE,
+                "qkv_attention: B=%d tokens=%d hidden=%d heads=%d K=%d", B, tokens, hidden, heads, K);
+    LDT_REQUIRE(hidden / heads == 32 || hidden / heads == 64, LDT_ESHAPE, "qkv_attention: head dim %d not built (32, 64)", hidden / heads);
+    LDT_REQUIRE(!kv_cond || (cond_tokens > 0 && !stats), LDT_EARG, "qkv_attention: cross-attention needs cond_tokens and has no folded form");
+    LDT_REQUIRE(!stats || (fold_S && fold_C && stats_parts > 0 && !bias), LDT_EARG, "qkv_attention: the folded form needs fold_S, fold_C, stats_parts and takes no bias (it is part of fold_C)");
+    QkvAttnStep q{BF(X), ldx, BF(W), ldw, bias, stats, stats_parts, fold_S, fold_C, fold_step_stride, BF(kv_cond), ldkv, kv_batch_stride,
+                  BFM(O), BFM(QKV), B, tokens, cond_tokens, hidden, heads, K, max_wgs, step_ptr};
+    return qkv_attention_step(q, ST(stream), nullptr);
+}
+
 static int score_forward_impl(const ldt_score_plan* p, const float* x, float* eps_out, const int32_t* step_ptr,
                               hipStream_t s, Prof* prof) {
     TRY(check_plan(p));
@@ -319,56 +390,22 @@ static int score_forward_impl(const ldt_score_plan* p, const float* x, float* ep
     for (int l = 0; l < p->blocks; ++l) {                       // score.py:148-149, layers.py:212-219
         const float* m = p->mod + (long)l * 6 * D;              // shift_msa|scale_msa|gate_msa|shift_mlp|scale_mlp|gate_mlp
         const float* fl = fold ? p->fold + (long)l * fblk : nullptr;
+        QkvAttnStep qa{BF(p->Hb), D, nullptr, D, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, 0, BFM(p->Ob), BFM(p->QKV),
+                       p->batch, T, p->cond_tokens, D, p->heads, D, p->gemm_wgs, step_ptr};
         if (fold && l > 0) {                                    // Hb = x (1 + scale_msa) and the row statistics came from block l-1's mlp.out
-            GemmArgs gq{BF(p->Hb), D, BF(p->w_qkv[l]), D, nullptr, p->QKV, 3L * D, nullptr, 0, nullptr, 0, nullptr, 0, 0, step_ptr, 0, M, 3 * D, D,
-                        nullptr, 0, nullptr, 0, nullptr, p->stats, sparts, fl, fl + 3L * D, fstep};
-            gq.max_wgs = p->gemm_wgs;
-            // 32-token samples: projection + attention in one launch (gemm_mid.hip, mid_epilogue_attn): q | k | v never reach HBM
-            gq.attn_o = BFM(p->Ob); gq.attn_scale_log2e = 1.4426950408889634f / sqrtf((float)(D / p->heads));
-            int fst = LDT_OK;
-            bool took = false;
-            if (fold_v1) LAUNCH_TRY(LDT_PROF_GEMM_QKV, took, ldt_gemm_mid_qkv_attn_try(&gq, T, D / p->heads, true, s, &fst), fst);
-            else LAUNCH_TRY(LDT_PROF_GEMM_QKV, took, ldt_gemm_qkv_attn256_try(&gq, T, D / p->heads, true, s, &fst), fst);   // 256-token samples: the 256 x 192-tile form of the persistent kernel
-            if (!took) {
-            LAUNCH(LDT_PROF_GEMM_QKV, ldt_gemm_lnfold_launch(LDT_EPI_BF16, &gq, s));
-            AttnArgs at{BF(p->QKV), 3L * D, (long)T * 3 * D, BF(p->QKV) + D, 3L * D, (long)T * 3 * D, BF(p->QKV) + 2 * D, 3L * D,
-                        BFM(p->Ob), p->batch, p->heads, T, T, 1.4426950408889634f / sqrtf((float)(D / p->heads))};
-            LAUNCH(LDT_PROF_ATTN, ldt_attn_launch(&at, D / p->heads, s));
-            }
+            qa.W = BF(p->w_qkv[l]);
+            qa.stats = p->stats; qa.stats_parts = sparts; qa.fold_S = fl; qa.fold_C = fl + 3L * D; qa.fold_step_stride = fstep;
         } else {
-        LnArgs n1{p->X, D, BFM(p->Hb), D, nullptr, nullptr, m, m + D, sstr, T, step_ptr, tstr, M, D};
-        LAUNCH(LDT_PROF_LN, ldt_ln_launch(&n1, s));
-        if (p->kv_cond[l]) {                                    // cross-attention: q from the modulated x, K|V from the condition
-            const int S = p->cond_tokens;
-            GemmArgs gq{BF(p->Hb), D, BF(p->w_q[l]), D, p->b_q[l], p->QKV, 3L * D, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, 0, M, D, D};
-            gq.max_wgs = p->gemm_wgs;
-            gq.attn_o = BFM(p->Ob); gq.attn_scale_log2e = 1.4426950408889634f / sqrtf((float)(D / p->heads));
-            gq.attn_k = BF(p->kv_cond[l]); gq.attn_v = BF(p->kv_cond[l]) + D; gq.attn_ldkv = 2L * D; gq.attn_kv_batch_stride = (long)S * 2 * D;
-            int fst = LDT_OK;
-            bool took = false;
-            LAUNCH_TRY(LDT_PROF_GEMM_QKV, took, ldt_gemm_mid_q_xattn_try(&gq, T, S, D / p->heads, s, &fst), fst);   // 32 x 32 tokens: projection + attention in one launch
-            if (!took) {
-            LAUNCH(LDT_PROF_GEMM_QKV, ldt_gemm_launch(LDT_EPI_BF16, &gq, s));
-            AttnArgs at{BF(p->QKV), 3L * D, (long)T * 3 * D, BF(p->kv_cond[l]), 2L * D, (long)S * 2 * D, BF(p->kv_cond[l]) + D, 2L * D,
-                        BFM(p->Ob), p->batch, p->heads, T, S, 1.4426950408889634f / sqrtf((float)(D / p->heads))};
-            LAUNCH(LDT_PROF_ATTN, ldt_attn_launch(&at, D / p->heads, s));
-            }
-        } else {                                                // self-attention: fused q|k|v projection of the modulated x
-            GemmArgs gq{BF(p->Hb), D, BF(p->w_qkv[l]), D, p->b_qkv[l], p->QKV, 3L * D, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, 0, M, 3 * D, D};
-            gq.max_wgs = p->gemm_wgs;
-            gq.attn_o = BFM(p->Ob); gq.attn_scale_log2e = 1.4426950408889634f / sqrtf((float)(D / p->heads));
-            int fst = LDT_OK;
-            bool took = false;
-            LAUNCH_TRY(LDT_PROF_GEMM_QKV, took, ldt_gemm_mid_qkv_attn_try(&gq, T, D / p->heads, false, s, &fst), fst);   // 32-token samples: projection + attention in one launch
-            if (!took) LAUNCH_TRY(LDT_PROF_GEMM_QKV, took, ldt_gemm_qkv_attn256_try(&gq, T, D / p->heads, false, s, &fst), fst);   // 256-token samples
-            if (!took) {
-            LAUNCH(LDT_PROF_GEMM_QKV, ldt_gemm_launch(LDT_EPI_BF16, &gq, s));
-            AttnArgs at{BF(p->QKV), 3L * D, (long)T * 3 * D, BF(p->QKV) + D, 3L * D, (long)T * 3 * D, BF(p->QKV) + 2 * D, 3L * D,
-                        BFM(p->Ob), p->batch, p->heads, T, T, 1.4426950408889634f / sqrtf((float)(D / p->heads))};
-            LAUNCH(LDT_PROF_ATTN, ldt_attn_launch(&at, D / p->heads, s));
+            LnArgs n1{p->X, D, BFM(p->Hb), D, nullptr, nullptr, m, m + D, sstr, T, step_ptr, tstr, M, D};
+            LAUNCH(LDT_PROF_LN, ldt_ln_launch(&n1, s));
+            if (p->kv_cond[l]) {                                // cross-attention: q from the modulated x, K|V from the condition
+                qa.W = BF(p->w_q[l]); qa.bias = p->b_q[l];
+                qa.kv = BF(p->kv_cond[l]); qa.ldkv = 2L * D; qa.kv_batch_stride = (long)p->cond_tokens * 2 * D;
+            } else {                                            // self-attention: fused q|k|v projection of the modulated x
+                qa.W = BF(p->w_qkv[l]); qa.bias = p->b_qkv[l];
             }
         }
-        }
+        TRY(qkv_attention_step(qa, s, prof));
         if (fold) {
             // fc_o + gate + residual, also emitting Hb = x (1 + scale_mlp) and the row statistics; mlp.fc consumes them
             GemmArgs go{BF(p->Ob), D, BF(p->w_o[l]), D, p->b_o[l], p->X, D, p->X, D, nullptr, 0, m + 2 * D, sstr, T, step_ptr, tstr, M, D, D,

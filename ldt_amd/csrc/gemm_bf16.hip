@@ -1310,12 +1310,21 @@ static int gemm_variant_env();
 // QKV projection + self-attention in one launch at 256 tokens (gemm_qkv_attn256_kernel): head dim 64, N = 3 * hidden (hidden % 64 == 0),
 // whole samples (M % 256 == 0), enough (sample, head) tiles to fill 5/8 of the workgroups the launch may use.  `folded`: a = the LN-folded
 // consumer's arguments (statistics per 256 columns).  -> true when this kernel took the launch.  LDT_QKV_ATTN256=0: off (A/B).
-bool ldt_gemm_qkv_attn256_try(const GemmArgs* a_in, int tokens, int head_dim, bool folded, hipStream_t stream, int* status) {
+// The shape part of that rule (also ldt_qkv_attention_route's): reads M, N, K, stats_parts and max_wgs of `g`, no pointer.
+bool ldt_gemm_qkv_attn256_takes(const GemmArgs* a_in, int tokens, int head_dim, bool folded) {
     static const bool on = !(getenv("LDT_QKV_ATTN256") && atoi(getenv("LDT_QKV_ATTN256")) == 0);
     const GemmArgs& g = *a_in;
-    if (!on || gemm_variant_env() != 0 || tokens != 256 || head_dim != 64 || !g.attn_o) return false;
-    if (g.N % 192 != 0 || (g.N / 3) % 64 != 0 || g.M % 256 != 0 || g.K % 64 != 0 || g.K < (folded ? 256 : 128)) return false;
-    if (folded && (g.stats_parts <= 0 || g.stats_parts > 4 || g.stats_parts * 256 != g.K || !g.stats_in || !g.fold_S || !g.fold_C ||
+    if (!on || gemm_variant_env() != 0 || tokens != 256 || head_dim != 64) return false;
+    if (g.M <= 0 || g.N <= 0 || g.N % 192 != 0 || (g.N / 3) % 64 != 0 || g.M % 256 != 0 || g.K % 64 != 0 || g.K < (folded ? 256 : 128)) return false;
+    if (folded && (g.stats_parts <= 0 || g.stats_parts > 4 || g.stats_parts * 256 != g.K)) return false;
+    const long tiles = (long)(g.M / 256) * ((g.N / 3) / 64);
+    const int lim = (g.max_wgs > 0 && g.max_wgs < LDT_NUM_CUS) ? g.max_wgs : LDT_NUM_CUS;
+    return tiles * 8 >= (long)lim * 5;
+}
+bool ldt_gemm_qkv_attn256_try(const GemmArgs* a_in, int tokens, int head_dim, bool folded, hipStream_t stream, int* status) {
+    const GemmArgs& g = *a_in;
+    if (!g.attn_o || !ldt_gemm_qkv_attn256_takes(a_in, tokens, head_dim, folded)) return false;
+    if (folded && (!g.stats_in || !g.fold_S || !g.fold_C ||
                    !ldt_aligned16(g.stats_in) || !ldt_aligned16(g.fold_S) || !ldt_aligned16(g.fold_C) || g.fold_step_stride % 4 != 0))
         return false;
     if (!ldt_aligned16(g.X) || !ldt_aligned16(g.W) || !ldt_aligned16(g.attn_o) || (g.bias && !ldt_aligned16(g.bias)) || g.ldx % 8 != 0 || g.ldw % 8 != 0 ||
@@ -1324,7 +1333,6 @@ bool ldt_gemm_qkv_attn256_try(const GemmArgs* a_in, int tokens, int head_dim, bo
     const int tm = g.M / 256, tn = (g.N / 3) / 64;
     const long tiles = (long)tm * tn;
     const int lim = (g.max_wgs > 0 && g.max_wgs < LDT_NUM_CUS) ? g.max_wgs : LDT_NUM_CUS;
-    if (tiles * 8 < (long)lim * 5) return false;
     GemmArgs a = g;
     static const int gm_env = getenv("LDT_QKV_GM") ? atoi(getenv("LDT_QKV_GM")) : getenv("LDT_GEMM_GM") ? atoi(getenv("LDT_GEMM_GM")) : -1;   // tools/dbg
     a.group_m = gm_env >= 0 ? gm_env : (tn >= 8 && tm >= 8) ? 4 : 1;     // (4 since round 6: see launch_256)

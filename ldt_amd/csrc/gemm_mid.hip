@@ -955,18 +955,24 @@ static int mid_qkv_attn_launch(const GemmArgs& a, hipStream_t stream) {
     return ldt_check_launch("gemm_bf16_nt_mid(qkv+attention)");
 }
 
-bool ldt_gemm_mid_qkv_attn_try(const GemmArgs* a_in, int tokens, int head_dim, bool folded, hipStream_t stream, int* status) {
+// The shape part of that rule (also ldt_qkv_attention_route's): reads M, N, K, stats_parts and max_wgs of `g`, no pointer.
+bool ldt_gemm_mid_qkv_attn_takes(const GemmArgs* a_in, int tokens, int head_dim, bool folded) {
     static const bool on = !(getenv("LDT_QKV_ATTN") && atoi(getenv("LDT_QKV_ATTN")) == 0);
-    if (!on || !mid_env() || tokens != 32 || head_dim != 64 || !a_in->attn_o) return false;
+    if (!on || !mid_env() || tokens != 32 || head_dim != 64) return false;
     const GemmArgs& g = *a_in;
-    if (g.N % 192 != 0 || (g.N / 3) % 64 != 0 || g.M % 128 != 0 || g.K % MID_BK != 0 || g.K / MID_BK < MidCfg<128, 192>::NS + 2) return false;
+    if (g.M <= 0 || g.N <= 0 || g.N % 192 != 0 || (g.N / 3) % 64 != 0 || g.M % 128 != 0 || g.K % MID_BK != 0 || g.K / MID_BK < MidCfg<128, 192>::NS + 2) return false;
     // the regime of this family (mid_shape_for): at most two rounds of workgroups — of the workgroups this launch may use when a sub-batch
     // stream caps its grids (a->max_wgs); larger batches (B >= 256 at 16 heads) stay with the persistent 256^2 GEMM + the resident
     // attention kernel.  No lower bound: a small batch saves a launch here and has nothing to lose to a bigger tile.
     const long wgs = (long)(g.M / 128) * (g.N / 192);
     const long cus = g.max_wgs > 0 && g.max_wgs < LDT_NUM_CUS ? g.max_wgs : LDT_NUM_CUS;
     if (wgs > 2 * cus) return false;
-    if (folded && (g.stats_parts > 32 || g.stats_parts * 32 != g.K || !g.stats_in || !g.fold_S || !g.fold_C)) return false;
+    return !(folded && (g.stats_parts > 32 || g.stats_parts * 32 != g.K));
+}
+bool ldt_gemm_mid_qkv_attn_try(const GemmArgs* a_in, int tokens, int head_dim, bool folded, hipStream_t stream, int* status) {
+    if (!a_in->attn_o || !ldt_gemm_mid_qkv_attn_takes(a_in, tokens, head_dim, folded)) return false;
+    const GemmArgs& g = *a_in;
+    if (folded && (!g.stats_in || !g.fold_S || !g.fold_C)) return false;
     // the argument checks of ldt_gemm_launch / ldt_gemm_lnfold_launch, which this route runs ahead of (a violation returns false:
     // the generic path then reports it)
     if (!g.X || !g.W || !ldt_aligned16(g.X) || !ldt_aligned16(g.W) || g.ldx < g.K || g.ldw < g.K || g.ldx % 8 != 0 || g.ldw % 8 != 0) return false;
@@ -981,14 +987,20 @@ bool ldt_gemm_mid_qkv_attn_try(const GemmArgs* a_in, int tokens, int head_dim, b
 // q projection + cross-attention in one launch (mid_epilogue_xattn): 32-token samples, 32 condition tokens, head dim 64, N = hidden (a multiple
 // of 64), whole 64-row tiles (two samples each), one or two rounds of workgroups.  a->attn_k / attn_v: the cached K | V rows of the condition
 // (row stride attn_ldkv, sample stride attn_kv_batch_stride, elements).  LDT_Q_XATTN=0: off (A/B).
-bool ldt_gemm_mid_q_xattn_try(const GemmArgs* a_in, int tokens, int cond_tokens, int head_dim, hipStream_t stream, int* status) {
+// The shape part of that rule (also ldt_qkv_attention_route's): reads M, N, K and max_wgs of `g`, no pointer.
+bool ldt_gemm_mid_q_xattn_takes(const GemmArgs* a_in, int tokens, int cond_tokens, int head_dim) {
     static const bool on = !(getenv("LDT_Q_XATTN") && atoi(getenv("LDT_Q_XATTN")) == 0);
     const GemmArgs& g = *a_in;
-    if (!on || !mid_env() || tokens != 32 || cond_tokens != 32 || head_dim != 64 || !g.attn_o || !g.attn_k || !g.attn_v) return false;
-    if (g.N % 64 != 0 || g.M % 64 != 0 || g.K % MID_BK != 0 || g.K / MID_BK < 2) return false;
+    if (!on || !mid_env() || tokens != 32 || cond_tokens != 32 || head_dim != 64) return false;
+    if (g.M <= 0 || g.N <= 0 || g.N % 64 != 0 || g.M % 64 != 0 || g.K % MID_BK != 0 || g.K / MID_BK < 2) return false;
     const long wgs = (long)(g.M / 64) * (g.N / 64);
     const long cus = g.max_wgs > 0 && g.max_wgs < LDT_NUM_CUS ? g.max_wgs : LDT_NUM_CUS;
-    if (wgs < 48 || wgs > 2 * cus) return false;
+    return wgs >= 48 && wgs <= 2 * cus;
+}
+bool ldt_gemm_mid_q_xattn_try(const GemmArgs* a_in, int tokens, int cond_tokens, int head_dim, hipStream_t stream, int* status) {
+    const GemmArgs& g = *a_in;
+    if (!g.attn_o || !g.attn_k || !g.attn_v || !ldt_gemm_mid_q_xattn_takes(a_in, tokens, cond_tokens, head_dim)) return false;
+    const long wgs = (long)(g.M / 64) * (g.N / 64);
     if (!g.X || !g.W || !ldt_aligned16(g.X) || !ldt_aligned16(g.W) || g.ldx < g.K || g.ldw < g.K) return false;
     if (!ldt_aligned16(g.attn_o) || !ldt_aligned16(g.attn_k) || !ldt_aligned16(g.attn_v) || g.attn_ldkv % 8 != 0 || g.attn_kv_batch_stride % 8 != 0 ||
         (g.bias && !ldt_aligned16(g.bias)) || g.ldx % 8 != 0 || g.ldw % 8 != 0)

@@ -97,7 +97,11 @@ int ldt_gemm_mid_lnfold_launch(int epi, int shape, const GemmArgs* a, hipStream_
 bool ldt_gemm_mid_qkv_attn_try(const GemmArgs* a, int tokens, int head_dim, bool folded, hipStream_t stream, int* status);
 bool ldt_gemm_qkv_attn256_try(const GemmArgs* a, int tokens, int head_dim, bool folded, hipStream_t stream, int* status);   // gemm_bf16.hip: fused QKV + self-attention at 256 tokens, Dh 64; false = not taken
 bool ldt_gemm_mid_q_xattn_try(const GemmArgs* a, int tokens, int cond_tokens, int head_dim, hipStream_t stream, int* status);   // fused q projection + cross-attention (32 x 32 tokens, Dh 64); false = not taken
-//   // fused QKV + attention (32 tokens, Dh 64); false = not taken   // LN-folded producer / consumer (statistics per 32 columns); false = not taken
+// the shape part of the three rules above (M, N, K, stats_parts and max_wgs of `a` plus the environment switches; no pointer is read): each
+// `_try` starts with its own and then checks pointers and alignment; ldt_qkv_attention_route (include/ldt_hip.h) evaluates them in the forward's order
+bool ldt_gemm_mid_qkv_attn_takes(const GemmArgs* a, int tokens, int head_dim, bool folded);
+bool ldt_gemm_qkv_attn256_takes(const GemmArgs* a, int tokens, int head_dim, bool folded);
+bool ldt_gemm_mid_q_xattn_takes(const GemmArgs* a, int tokens, int cond_tokens, int head_dim);
 bool ldt_gemm_lnfold_v1_route(int M, int D, int F, int max_wgs);   // small batch: every GEMM of a Score block folds through the mid-size tile kernel (statistics per 32 columns)
 int ldt_gemm_lnfold_launch(int epi, const GemmArgs* a, hipStream_t stream);   // producer (RESID + xs/stats) or consumer (stats_in)
 int ldt_ln_launch(const LnArgs* a, hipStream_t s);

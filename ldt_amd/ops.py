@@ -553,6 +553,53 @@ def attention_oproj_resid_(q, k, v, B, H, Nq, Nk, head_dim, wo, bo, x, gate=None
     return x
 
 
+QKV_ATTENTION_ROUTES = ("two-kernels", "mid-self-32", "persistent-self-256", "mid-cross-32")
+
+
+def qkv_attention_route(B, tokens, hidden, heads, K, cond_tokens=0, fold=0, max_wgs=0):
+    """Which form qkv_attention (and the Score forward) runs for this shape: the launchers' own shape rules (ldt_qkv_attention_route), no
+    launch.  fold: 0 plain, 32 / 256 = folded with statistics per that many columns.  -> index into QKV_ATTENTION_ROUTES."""
+    return int(lib().ldt_qkv_attention_route(int(B), int(tokens), int(cond_tokens), int(hidden), int(heads), int(K), int(fold), int(max_wgs)))
+
+
+def qkv_attention(x, w, B, tokens, heads, bias=None, stats=None, fold_s=None, fold_c=None, fold_step_stride=0, step_ptr=None,
+                  kv_cond=None, cond_tokens=0, kv_batch_stride=None, max_wgs=0, out=None, qkv=None):
+    """The q | k | v projection + attention step of a Score block as the forward launches it (ldt_qkv_attention): x [B*tokens, K] bf16 row
+    view, w [3*hidden, K] (self-attention) or [hidden, K] with kv_cond [B*cond_tokens, >= 2*hidden] = the condition's K | V rows
+    (cross-attention; kv_batch_stride: elements between samples when they are not cond_tokens rows apart); folded: x = the producer's xs, stats [K/256 or K/32, M, 2], fold_s / fold_c [(steps,) 3*hidden].
+    qkv: the [M, 3*hidden] workspace the two-kernel path writes (a fused form leaves it alone).  -> O [B, heads, tokens, head_dim] bf16."""
+    for t, nm in ((x, "x"), (w, "w"), (kv_cond, "kv_cond")):
+        _need(t, torch.bfloat16, nm)
+        if t is not None:
+            _rowmajor(t, nm)
+    for t, nm in ((bias, "bias"), (stats, "stats"), (fold_s, "fold_s"), (fold_c, "fold_c")):
+        _need(t, torch.float32, nm)
+    M, K = x.shape
+    hidden = w.shape[0] if kv_cond is not None else w.shape[0] // 3
+    if M != B * tokens or w.shape[1] != K or w.shape[0] != (hidden if kv_cond is not None else 3 * hidden) or hidden % heads:
+        raise ValueError("qkv_attention: x%s w%s do not match B=%d tokens=%d heads=%d" % (tuple(x.shape), tuple(w.shape), B, tokens, heads))
+    if kv_cond is not None:
+        if kv_batch_stride is None:
+            kv_batch_stride = kv_cond.stride(0) * cond_tokens
+        if kv_cond.shape[1] < 2 * hidden or (B - 1) * kv_batch_stride + (cond_tokens - 1) * kv_cond.stride(0) + 2 * hidden > kv_cond.shape[0] * kv_cond.stride(0):
+            raise ValueError("qkv_attention: kv_cond must hold B samples of cond_tokens rows [>= 2*hidden]")
+    if stats is not None and (stats.dim() != 3 or tuple(stats.shape[1:]) != (M, 2) or not stats.is_contiguous()):
+        raise ValueError("qkv_attention: stats must be contiguous [parts, M, 2]")
+    if out is None:
+        out = torch.empty((B, heads, tokens, hidden // heads), dtype=torch.bfloat16, device=x.device)
+    if qkv is None:
+        qkv = torch.empty((M, 3 * hidden), dtype=torch.bfloat16, device=x.device)
+    _need(out, torch.bfloat16, "out"); _need(qkv, torch.bfloat16, "qkv")
+    if not out.is_contiguous() or not qkv.is_contiguous() or qkv.numel() < M * 3 * hidden:
+        raise ValueError("qkv_attention: out and qkv must be contiguous, qkv [M, 3*hidden]")
+    check(lib().ldt_qkv_attention(_p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(stats), stats.shape[0] if stats is not None else 0,
+                                  _p(fold_s), _p(fold_c), fold_step_stride, _p(kv_cond),
+                                  kv_cond.stride(0) if kv_cond is not None else 0, kv_batch_stride or 0,
+                                  _p(out), _p(qkv), B, tokens, cond_tokens, hidden, heads, K, max_wgs, _p(step_ptr), stream_ptr()),
+          "ldt_qkv_attention")
+    return out
+
+
 def ln_linear(x, w, bias=None, ln_w=None, ln_b=None, shift=None, scale=None, mod_sample_stride=0, rows_per_sample=0):
     """bf16 [M,N] = LN(x)[affine | modulated] @ w[N,C]^T + bias for C in {64, 128} channels, N % 64 == 0 (one fused kernel)."""
     _need(x, torch.float32, "x"); _rowmajor(x, "x"); _need(w, torch.bfloat16, "w")

@@ -1,4 +1,5 @@
-"""Per-element checks and exact probes for the MFMA kernels (used by test_gpu_kernel_exact.py and test_gpu_kernels.py).
+"""Per-element checks and exact probes for the MFMA kernels (used by test_gpu_kernel_exact.py, test_gpu_fused_attention_exact.py and
+test_gpu_kernels.py).
 
 A bf16 output's rel-MSE bar has to sit above the output rounding (~1.3e-6), so it passes hundreds of entirely wrong elements in a large
 output.  The checks here are componentwise: a bound derived from the operands in float64 (gemm_tol + assert_elementwise), and operands
@@ -141,11 +142,14 @@ def attention_pi(Nq, Nk, salt=0):
     return torch.where(i % 2 == 0, e, (i * 37 + 11) % Nk)
 
 
-def attention_gather_probe(B, H, Nq, Nk, dh, seed):
+def attention_gather_probe(B, H, Nq, Nk, dh, seed, key_salt=False):
     """Q [B, Nq, H dh], K, V [B, Nk, H dh] (bf16-exact float32) such that query i of head (b, h) scores at least 40 above every other key at key
     pi(i): K[j] carries the +1 / -1 code of the bits of j in the first 11 channels of each head, Q[i] = 160 x the code of pi(i) — a one-bit
     difference costs 2 * 160 / sqrt(dh) >= 40 in score, so every other weight is below e^-40 and O[b, h, i] == V[b, pi(i), head h] to the bit
-    (V has magnitudes in [2^-6, 4]: the leftovers cannot move a last bit).  -> (q, k, v, want [B, H, Nq, dh])."""
+    (V has magnitudes in [2^-6, 4]: the leftovers cannot move a last bit).  key_salt: head (b, h) codes j ^ m(b, h) instead of j on both sides
+    (m below the largest power of two <= Nk, different for neighbouring heads): the scores are the same, but k of another head now selects
+    key pi(i) ^ m ^ m' — without it K is the same in every head and a kernel that mixes up the heads of k goes unseen.
+    -> (q, k, v, want [B, H, Nq, dh])."""
     assert Nk <= 2048 and dh >= 11 and 2 * 160 / dh ** 0.5 >= 40
     g = torch.Generator().manual_seed(seed)
     C = H * dh
@@ -158,8 +162,9 @@ def attention_gather_probe(B, H, Nq, Nk, dh, seed):
     for b in range(B):
         for h in range(H):
             pi = attention_pi(Nq, Nk, salt=13 * (b * H + h))
-            k[b, :, h * dh:h * dh + 11] = code(torch.arange(Nk))
-            q[b, :, h * dh:h * dh + 11] = 160.0 * code(pi)
+            m = (5 + 3 * (b * H + h)) % (1 << (Nk.bit_length() - 1)) if key_salt and Nk >= 4 else 0
+            k[b, :, h * dh:h * dh + 11] = code(torch.arange(Nk) ^ m)
+            q[b, :, h * dh:h * dh + 11] = 160.0 * code(pi ^ m)
             want[b, h] = v[b, pi, h * dh:(h + 1) * dh]
             # the construction's claim, checked: the gap to the runner-up in score
             s = (q[b, :, h * dh:(h + 1) * dh].double() @ k[b, :, h * dh:(h + 1) * dh].double().T) * dh ** -0.5
@@ -167,3 +172,121 @@ def attention_gather_probe(B, H, Nq, Nk, dh, seed):
             s.scatter_(1, pi[:, None], float("-inf"))
             assert Nk == 1 or float((top - s.max(1, keepdim=True).values).min()) >= 40.0
     return q, k, v, want
+
+
+# ------------------------------------------------------------------------------------------------------------- fused projection + attention
+# (test_gpu_fused_attention_exact.py; validated without a GPU, planted faults included, by test_kernel_checks_host.py)
+def bf16_round(x64):
+    """float64 -> the bf16 value (as float64) a kernel stores: fp32, then round-to-nearest-even to bf16.  (The double rounding can differ from a
+    direct one only within 2^-24 |x| of a rounding boundary, which ambiguous_ulp counts as ambiguous anyway.)"""
+    return x64.float().bfloat16().double()
+
+
+def ambiguous_ulp(pre, acc):
+    """float64 like pre: how far bf16(an fp32 accumulation within acc + 2^-24 |pre| =: b of pre) can lie from bf16_round(pre).  0 where `pre` is
+    further than b from every bf16 rounding boundary (the midpoint of two neighbouring bf16 values; just above a power of two the lower
+    neighbour sits half an ulp away, so that boundary a quarter): both round to the same value.  Elsewhere half an ulp at |pre| + half an ulp
+    at |pre| + b + b: one ulp to within 2^-10 in the ordinary case b << ulp, and still a bound where cancellation leaves |pre| below its own
+    accumulation error (there the two can differ by many ulps)."""
+    a = pre.double().abs()
+    b = acc.double() + U24 * a
+    ulp = bf16_ulp(a)
+    frac = a / ulp - torch.floor(a / ulp)
+    dist = torch.minimum((frac - 0.5).abs() * ulp, a - torch.exp2(torch.floor(torch.log2(a.clamp_min(2.0 ** -126)))) + ulp / 4)
+    return (0.5 * ulp + 0.5 * bf16_ulp(a + b) + b) * (dist <= b).double()
+
+
+def heads(z, B, n, H, dh):
+    """[B * n, H * dh] rows -> float64 [B, H, n, dh]."""
+    return z.double().reshape(B, n, H, dh).permute(0, 2, 1, 3)
+
+
+def attention_ref64(q, k, v, B, H, Nq, Nk, dh):
+    """float64 softmax(q k^T / sqrt(dh)) v -> (O [B, H, Nq, dh], max_j |v_j| [B, H, 1, dh])."""
+    p = (heads(q, B, Nq, H, dh) @ heads(k, B, Nk, H, dh).transpose(-1, -2) * dh ** -0.5).softmax(-1)
+    vv = heads(v, B, Nk, H, dh)
+    return (p @ vv).contiguous(), vv.abs().amax(2, keepdim=True)
+
+
+def attention_base_tol(ref, vmax):
+    """The bound of test_attention_bound_vs_float64 on exact bf16 inputs: 2^-8 |ref| (bf16 output) + 2^-8 max_j |v_j| (P rounded to bf16)."""
+    return U8 * ref.abs() + U8 * vmax
+
+
+def exact_projection_probe(M, N, K, seed, with_bias=True, device="cpu"):
+    """integer_probe operands with w and the bias scaled by 2^-3: every x w^T + bias is an integer <= 256 times 2^-3, exact in fp32
+    accumulation of any order and in bf16 (checked on the float64 result), of ordinary softmax sharpness (standard deviation 0.5 .. 1.3 for
+    K = 128 .. 1024).  -> (x, w, bias, y float64 on `device`): the q | k | v a kernel computes internally are `y` to the bit."""
+    x, w, bias, ref = integer_probe(M, N, K, seed, with_bias=with_bias, device=device)
+    w, y = w / 8, ref / 8
+    bias = None if bias is None else bias / 8
+    assert torch.equal(w.bfloat16().float(), w) and torch.equal(x.bfloat16().float(), x)
+    assert bool((y * 8 == (y * 8).round()).all()) and float(y.abs().max()) <= 32.0 and torch.equal(bf16_round(y), y)
+    return x, w, bias, y
+
+
+def gather_projection_probe(B, H, Nq, Nk, dh, seed, cross=False):
+    """attention_gather_probe through the projection: self form X = [Q | K | V] rows (K_gemm = 3 H dh) and W = the 3 H dh identity; cross form
+    X = Q, W = the H dh identity and kv = [K | V] rows of the condition.  x w^T reproduces Q, K, V to the bit, so O == want at tolerance 0
+    (with no bias or an all-zero one).  -> (x, w, kv or None, want [B, H, Nq, dh]) float32 on the CPU."""
+    q, k, v, want = attention_gather_probe(B, H, Nq, Nk, dh, seed, key_salt=True)
+    C = H * dh
+    if cross:
+        return q.reshape(B * Nq, C), torch.eye(C), torch.cat([k, v], -1).reshape(B * Nk, 2 * C), want
+    assert Nq == Nk
+    return torch.cat([q, k, v], -1).reshape(B * Nq, 3 * C), torch.eye(3 * C), None, want
+
+
+def consumer_pre64(xs, w, S, C, stats, K, mm=None, mm_abs=None):
+    """The LN-folded consumer's algebra in float64 from the fp32 row statistics stats [parts, M, 2] (as test_gpu_kernel_exact._consumer_bound):
+    pre = rstd (xs w^T) - rstd mean S + C and its accumulation bound: fp32 accumulation, plus mean, variance (a difference of two fp32 terms)
+    and rsqrt in fp32, 2^-19 relative on every term they scale.  mm / mm_abs: xs w^T and |xs| |w|^T when already computed.  -> (pre, acc)."""
+    s = stats.double().sum(0)
+    mean = s[:, 0:1] / K
+    rstd = 1 / torch.sqrt((s[:, 1:2] / K - mean * mean).clamp_min(0) + 1e-6)
+    mm = xs.double() @ w.double().T if mm is None else mm
+    mm_abs = xs.double().abs() @ w.double().abs().T if mm_abs is None else mm_abs
+    t1, t2, t3 = rstd * mm, rstd * mean * S.double(), C.double()
+    return t1 - t2 + t3, rstd * mm_abs * (C_ACC * K * U24) + 2.0 ** -19 * (t1.abs() + t2.abs() + t3.abs())
+
+
+def fused_attention_tol(pre, acc, B, H, Nq, dh, kv=None, Nk=None, chunk=8):
+    """Two-stage float64 reference of `projection -> bf16 -> attention` and its componentwise tolerance, all from the reference.
+    pre float64 [B Nq, 3 H dh] = the projection ([B Nq, H dh] = q alone with kv = (k, v) rows [B Nk, H dh] given exactly), acc = its
+    accumulation bound.  r = bf16_round(pre); the kernel's q | k | v can differ from r by at most e = ambiguous_ulp(pre, acc).  Per query row
+    d_i = max_j (e_q |k|^T + |q| e_k^T + e_q e_k^T)_ij / sqrt(dh) bounds the change of every score, so every softmax weight moves by at most a
+    factor e^(+-2 d_i) and
+        |O - O_ref| <= e^(2 d_i) (2^-8 |O_ref| + 2^-8 max_j |v_j|) + (e^(2 d_i) - 1) (p |v|)_i + e^(2 d_i) (p e_v)_i.
+    -> (O_ref [B, H, Nq, dh], tol, tol / base with base = the first term at d = 0, ambiguous fraction).  Samples are processed `chunk` at a time."""
+    C = H * dh
+    r, e = bf16_round(pre), ambiguous_ulp(pre, acc)
+    if kv is None:
+        Nk = Nq
+        parts = [(r[:, i * C:(i + 1) * C], e[:, i * C:(i + 1) * C]) for i in range(3)]
+    else:
+        parts = [(r, e)] + [(t.double(), torch.zeros_like(t, dtype=torch.float64)) for t in kv]
+    refs, tols, ratios = [], [], []
+    for b0 in range(0, B, chunk):
+        nb = min(chunk, B - b0)
+        (q, eq), (k, ek), (v, ev) = [(heads(t[b0 * n:(b0 + nb) * n], nb, n, H, dh), heads(u[b0 * n:(b0 + nb) * n], nb, n, H, dh))
+                                     for (t, u), n in zip(parts, (Nq, Nk, Nk))]
+        kt, ekt = k.transpose(-1, -2), ek.transpose(-1, -2)
+        d = ((eq @ kt.abs() + q.abs() @ ekt + eq @ ekt) * dh ** -0.5).amax(-1, keepdim=True)
+        p = (q @ kt * dh ** -0.5).softmax(-1)
+        ref = p @ v
+        base = attention_base_tol(ref, v.abs().amax(2, keepdim=True))
+        g = torch.exp(2 * d)
+        tol = g * base + (g - 1) * (p @ v.abs()) + g * (p @ ev)
+        refs.append(ref); tols.append(tol); ratios.append(tol / base)
+    return torch.cat(refs).contiguous(), torch.cat(tols).contiguous(), torch.cat(ratios), float((e > 0).double().mean())
+
+
+RATIO_MEDIAN_CAP, RATIO_MAX_CAP = 3.0, 8.0
+
+
+def assert_ratio_caps(ratio, what):
+    """The condition that keeps fused_attention_tol honest: the allowance for rounding flips may widen the plain attention bound by a median
+    factor of at most 3 and nowhere by more than 8; a case beyond that needs smaller inputs, not a wider cap.  -> (median, max)."""
+    med, mx = float(ratio.median()), float(ratio.max())
+    assert med <= RATIO_MEDIAN_CAP and mx <= RATIO_MAX_CAP, "%s: tol / base median %.2f (cap %g), max %.2f (cap %g)" % (what, med, RATIO_MEDIAN_CAP, mx, RATIO_MAX_CAP)
+    return med, mx

@@ -327,7 +327,9 @@ def test_fused_qkv_attention_256_matches_two_kernel_path(tmp_path):
     B = 64 with batch-shared modulation (blocks >= 1 LN-folded consumer form, block 0 the plain form with bias) and with per-sample times
     (every block the plain form behind the LayerNorm kernel), B = 16 (256 tiles = one per workgroup) — three forwards each (run-to-run
     differences would betray a race in the q | k | v hand-over or a mis-counted wait).  Same operand rounding (q, k, v to bf16) and the same
-    attention loop (attn_tile_joint) on both sides: <= 1e-6 relative MSE (identical up to where the two GEMM kernels order their sums)."""
+    attention loop (attn_tile_joint) on both sides: <= 1e-6 relative MSE (identical up to where the two GEMM kernels order their sums).
+    This is the whole-model check; the kernel alone is held per element (float64 bounds, exact probes, bit-equality with the two-kernel path
+    on exact operands, guard bands) by tests/test_gpu_fused_attention_exact.py."""
     import os
     import subprocess
     import sys
@@ -380,7 +382,8 @@ def test_fused_cross_attention_matches_two_kernel_path(tmp_path):
     64 x 64 tiles) against the q GEMM + attention kernel pair it replaces (LDT_Q_XATTN=0), same seeded conditional forward at the production
     width (hidden 1024, 16 heads; 4 blocks: two with cross-attention; B = 8 and 32 samples: 64 and 256 workgroups) in two child processes,
     three forwards each (run-to-run differences would betray a race in the K | V staging or the q tile hand-over).  q is rounded to bf16 in
-    both paths and the softmax math is the same; the two attention kernels order their sums differently: <= 1e-6 relative MSE."""
+    both paths and the softmax math is the same; the two attention kernels order their sums differently: <= 1e-6 relative MSE.
+    This is the whole-model check; the kernel alone is held per element by tests/test_gpu_fused_attention_exact.py."""
     import os
     import subprocess
     import sys
