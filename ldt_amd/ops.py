@@ -337,8 +337,9 @@ def knn(xyz, centers, k, return_dist=False):
     return (idx, dist) if return_dist else idx
 
 
-def group_normalize(feat, xyz, fps_idx, knn_idx, alpha, beta, normalize="anchor"):
-    """LocalGrouper rows ('anchor' or 'center' normalisation): -> bf16 [B*S*k, pad64(2D+3)]."""
+def group_normalize(feat, xyz, fps_idx, knn_idx, alpha, beta, normalize="anchor", return_stats=False):
+    """LocalGrouper rows ('anchor' or 'center' normalisation): -> bf16 [B*S*k, pad64(2D+3)].  return_stats: -> (U, fp64 [2B]), the per-cloud
+    sums of (g - origin) and of its square that the normalisation was computed from (the kernels keep them as 2^-20 fixed point)."""
     B, n, D = feat.shape
     S, k = knn_idx.shape[1], knn_idx.shape[2]
     ldu = pad64(2 * D + 3)
@@ -348,16 +349,18 @@ def group_normalize(feat, xyz, fps_idx, knn_idx, alpha, beta, normalize="anchor"
     gmean = torch.empty((B, S, D + 3), dtype=torch.float32, device=feat.device) if mode else None
     check(lib().ldt_group_normalize(_p(feat), _p(xyz), _p(fps_idx), _p(knn_idx), _p(alpha), _p(beta), _p(stats), B, n, S, k, D,
                                     _p(U), ldu, mode, _p(gmean), stream_ptr()), "ldt_group_normalize")
+    if return_stats:
+        return U, stats.view(torch.int64).double() * 2.0 ** -20                 # csrc/common.h: fx_load
     return U
 
 
 GROUPER_FRAGS = 132                                      # 1 KB MFMA fragments in the fused grouper's weight image
 
 
-def grouper_mlp(feat, xyz, fps_idx, knn_idx, alpha, beta, wimg, b1, b2, b3):
+def grouper_mlp(feat, xyz, fps_idx, knn_idx, alpha, beta, wimg, b1, b2, b3, out=None):
     """Grouping ('anchor' normalisation) + PreExtraction + max over the k neighbours (k = 8, 16 or a multiple of 32) in one
     kernel: feat fp32 [B,n,128], xyz [B,n,3], fps_idx [B,S], knn_idx [B,S,k] -> fp32 [B*S, 128].  wimg: bf16 fragment image
-    (include/ldt_hip.h: ldt_grouper_mlp) built by LocalGrouper.pack."""
+    (include/ldt_hip.h: ldt_grouper_mlp) built by LocalGrouper.pack.  out: a contiguous fp32 [B*S, 128] tensor (or view) to write into."""
     B, n, D = feat.shape
     S, k = knn_idx.shape[1], knn_idx.shape[2]
     for t, nm in ((feat, "feat"), (xyz, "xyz"), (alpha, "alpha"), (beta, "beta"), (b1, "b1"), (b2, "b2"), (b3, "b3")):
@@ -367,7 +370,12 @@ def grouper_mlp(feat, xyz, fps_idx, knn_idx, alpha, beta, wimg, b1, b2, b3):
         raise ValueError("grouper_mlp: operands must be contiguous")
     if wimg.numel() != GROUPER_FRAGS * 512 or alpha.numel() != D + 3 or beta.numel() != D + 3 or min(b1.numel(), b2.numel(), b3.numel()) < D:
         raise ValueError("grouper_mlp: weight image / affine vectors have the wrong size")
-    out = torch.empty((B * S, D), dtype=torch.float32, device=feat.device)
+    if out is None:
+        out = torch.empty((B * S, D), dtype=torch.float32, device=feat.device)
+    else:
+        _need(out, torch.float32, "out")
+        if tuple(out.shape) != (B * S, D) or not out.is_contiguous() or out.device != feat.device:
+            raise ValueError("grouper_mlp: out must be a contiguous fp32 [%d, %d] tensor on the operands' device" % (B * S, D))
     stats = torch.empty((2 * B,), dtype=torch.float64, device=feat.device)
     check(lib().ldt_grouper_mlp(_p(feat), _p(xyz), _p(fps_idx), _p(knn_idx), _p(alpha), _p(beta), _p(stats), B, n, S, k, D,
                                 _p(wimg), _p(b1), _p(b2), _p(b3), _p(out), stream_ptr()), "ldt_grouper_mlp")

@@ -290,3 +290,330 @@ def assert_ratio_caps(ratio, what):
     med, mx = float(ratio.median()), float(ratio.max())
     assert med <= RATIO_MEDIAN_CAP and mx <= RATIO_MAX_CAP, "%s: tol / base median %.2f (cap %g), max %.2f (cap %g)" % (what, med, RATIO_MEDIAN_CAP, mx, RATIO_MAX_CAP)
     return med, mx
+
+
+# ------------------------------------------------------------------------------------------------------------- grouped rows + the fused grouper
+# (test_gpu_grouper_exact.py; validated without a GPU, planted faults included, by test_kernel_checks_host.py)
+#
+# A worst-case componentwise bound is useless through the grouper's three bf16 stages: 2^-8 per stage through |W1|, |W2|, |W3| is ~3 |ref|.
+# What the kernels owe instead is an INTERVAL: a float64 reference that rounds where the kernel rounds (U, h1, r, out), an allowance for what
+# fp32 arithmetic can move before each rounding, and — because rounding is monotone — lo = bf16(pre - a) <= out <= bf16(pre + a) = hi.  Where
+# lo == hi (most elements) the output is pinned to the bit; elsewhere exactly the neighbouring values are allowed.
+FX_HALF_STEP = 2.0 ** -21          # csrc/common.h: every wave's fp64 partial enters the per-cloud sums rounded to 2^-20 fixed point
+EPS_STD = float(torch.tensor(1e-5, dtype=torch.float32))       # the 1e-5f the kernels add to the standard deviation
+
+
+def _take(t, idx):
+    """t [B, n, C], idx [B, ...] -> [B, ..., C]."""
+    B = t.shape[0]
+    return torch.gather(t, 1, idx.reshape(B, -1, 1).expand(-1, -1, t.shape[-1])).reshape(*idx.shape, t.shape[-1])
+
+
+def grouper_case(B, n, S, k, seed, D=128, fscale=0.7, degenerate=None, plant=True):
+    """Crafted inputs of the grouping kernels (no FPS / kNN): features N(0, fscale^2) x (1 + b / 2) (every cloud its own scale), xyz N(0, 0.4^2),
+    seeded random indices with planted cases: point 0 and point n - 1 as neighbours and as anchors, a repeated neighbour in group S // 2, the
+    anchor inside its own neighbour set in the even groups only.  degenerate = b: every neighbour of cloud b is its group's anchor (d == 0).
+    -> dict of CPU tensors (fi, ki int32)."""
+    g = torch.Generator().manual_seed(seed)
+    feat = torch.randn(B, n, D, generator=g) * fscale * (1 + torch.arange(B).float()[:, None, None] * 0.5)
+    xyz = torch.randn(B, n, 3, generator=g) * 0.4
+    fi = torch.randint(0, n, (B, S), generator=g)
+    ki = torch.randint(0, n, (B, S, k), generator=g)
+    if plant:
+        ki = torch.where(ki == fi[:, :, None], (ki + 1) % n, ki)                  # no anchor in its own set ...
+        ki[:, ::2, k // 2] = fi[:, ::2]                                           # ... except in the even groups
+        fi[0, S - 1] = n - 1; fi[B - 1, 0] = 0
+        ki[0, 0, 0] = 0; ki[0, 0, k - 1] = n - 1; ki[B - 1, S - 1, k - 1] = 0; ki[B - 1, S - 1, 0] = n - 1
+        ki[:, S // 2, 1] = ki[:, S // 2, 0]
+        if k > 4:
+            ki[:, S // 2, k - 1] = ki[:, S // 2, 0]
+    if degenerate is not None:
+        ki[degenerate] = fi[degenerate][:, None]
+    alpha = torch.rand(D + 3, generator=g) + 0.5
+    beta = torch.randn(D + 3, generator=g) * 0.2
+    return dict(feat=feat, xyz=xyz, fi=fi.int(), ki=ki.int(), alpha=alpha, beta=beta, B=B, n=n, S=S, k=k, D=D)
+
+
+def grouper_weights(seed, D=128):
+    """PreExtraction panels of ordinary scale: bf16-exact N(0, 1 / K) weights, N(0, 0.2^2) biases.  -> (w1 [D, 2D+3], b1, w2, b2, w3, b3)."""
+    g = torch.Generator().manual_seed(seed)
+    bf = lambda t: t.bfloat16().float()
+    w1 = bf(torch.randn(D, 2 * D + 3, generator=g) / (2 * D + 3) ** 0.5)
+    w2, w3 = bf(torch.randn(D, D, generator=g) / D ** 0.5), bf(torch.randn(D, D, generator=g) / D ** 0.5)
+    b1, b2, b3 = [torch.randn(D, generator=g) * 0.2 for _ in range(3)]
+    return w1, b1, w2, b2, w3, b3
+
+
+def group_reference(feat, xyz, fi, ki, alpha, beta, mode="anchor", stats_rel=None):
+    """float64 reference of ldt_group_normalize from the fp32 operands, with what the kernels' arithmetic may move (all from the reference):
+      d      = g - origin (origin: the anchor's [feature | xyz], or in 'center' mode the mean of the group's k rows);
+      s1, s2 = per-cloud sums of d and d^2, tol1 / tol2 their tolerance.  Vector statistics kernels ('anchor', D = 64 / 128): a lane forms fp32
+               partial sums over its ceil(k / rows in flight) rows x 5 terms =: m, everything after is fp64: m 2^-24 (sum |d|, sum d^2).  Scalar
+               kernel (any other D, and 'center'): only d itself is rounded to fp32, 2^-24 per element (twice that on its square); in 'center'
+               mode d also carries the fp32 mean of k terms, k 2^-24 mean_j |g_j|.  Every wave's partial enters as 2^-20 fixed point: half a
+               step per wave on top (the kernels' own format, stated in csrc/common.h);
+      inv    = 1 / (sqrt(var) + 1e-5f), rho = its relative allowance: the statistics tolerance carried through var and sqrt, plus the fp32 cast,
+               add and divide;
+      pre    = alpha (d inv) + beta and a = its allowance: the subtraction, two multiplies and the statistics on the first term, the final add
+               on the sum (an FMA contraction only removes roundings).
+    stats_rel: the caller has ASSERTED the kernel's sums of this very case to lie within stats_rel (sum |d|, sum d^2) of s1, s2 (2^-24 in part
+    (c) of the grouper tests: half a rounding on inv, so that a stays at the 8 x 2^-24 (|alpha d inv| + |beta|) the staged reference was
+    designed with); tol1 / tol2 and rho are then that instead of the worst case of the summation.
+    -> dict(pre, a [B, S, k, D + 3], anchor [B, S, D], s1, s2, tol1, tol2, inv, rho [B])."""
+    B, n, D = feat.shape
+    S, k = ki.shape[1], ki.shape[2]
+    f, x, fi, ki = feat.double(), xyz.double(), fi.long(), ki.long()
+    G = torch.cat([_take(f, ki), _take(x, ki)], -1)
+    anchor = _take(f, fi)
+    if mode == "anchor":
+        d = G - torch.cat([anchor, _take(x, fi)], -1)[:, :, None]
+        dd = U24 * d.abs()
+    else:
+        d = G - G.mean(2, keepdim=True)
+        dd = U24 * d.abs() + (k * U24) * G.abs().mean(2, keepdim=True)
+    red = lambda t: t.sum((1, 2, 3))
+    s1, s2, cnt = red(d), red(d * d), float(S * k * (D + 3))
+    if mode == "anchor" and D in (64, 128):
+        m = -(-k // (64 // (D // 4))) * 5
+        tol1, tol2 = m * U24 * red(d.abs()), m * U24 * red(d * d)
+        waves = min((S + 3) // 4, 64) * 4
+    else:
+        tol1, tol2 = red(dd), red(2 * d.abs() * dd + dd * dd)
+        waves = min((S * k + 3) // 4, 256) * 4
+    if stats_rel is not None:
+        tol1, tol2 = stats_rel * red(d.abs()), stats_rel * red(d * d)
+    tol1 = tol1 + 2.0 ** -40 * red(d.abs()) + waves * FX_HALF_STEP
+    tol2 = tol2 + 2.0 ** -40 * red(d * d) + waves * FX_HALF_STEP
+    var = ((s2 - s1 * s1 / cnt) / (cnt - 1)).clamp_min(0)
+    dvar = (tol2 + (2 * s1.abs() * tol1 + tol1 * tol1) / cnt) / (cnt - 1)
+    std = var.sqrt()
+    dstd = torch.maximum((var + dvar).sqrt() - std, std - (var - dvar).clamp_min(0).sqrt())
+    inv = 1 / (std + EPS_STD)
+    rho = dstd * inv + 3 * U24
+    iv, rh = inv[:, None, None, None], rho[:, None, None, None]
+    al, be = alpha.double(), beta.double()
+    t1 = al * (d * iv)
+    pre = t1 + be
+    a_t1 = al.abs() * iv * dd + t1.abs() * (rh + 2 * U24)
+    a = (a_t1 + U24 * (pre.abs() + a_t1)) * (1 + 2.0 ** -10)
+    return dict(pre=pre, a=a, anchor=anchor, s1=s1, s2=s2, tol1=tol1, tol2=tol2, inv=inv, rho=rho)
+
+
+def _grouper_coords(row, col, k, S, slot=None):
+    """Where an element of a grouped tensor sits in the fused grouper: cloud / group, neighbour slot -> 32-row tile, tile row, and the layer-3
+    accumulator (half, register) that holds it; channel -> 32-channel block and lane."""
+    if slot is None:                                                       # a per-neighbour row index
+        g, j = row // k, row % k
+    else:
+        g, j = row, slot
+    gpt = 1 if k >= 32 else 32 // k
+    tj = j % 32 if gpt == 1 else (g % S % gpt) * k + j
+    return "cloud %d group %d neighbour slot %d (tile %d row %d: half %d register %d), channel block %d lane %d" % (
+        g // S, g % S, j, j // 32 if gpt == 1 else (g % S) // gpt, tj, (tj >> 2) & 1, 4 * (tj >> 3) + (tj & 3), col // 32, col % 32)
+
+
+def _tile_report_groups(bad, k, S, per_neighbour):
+    """The (group, neighbour slot, 32-channel block) view of a violation mask [rows, C]: rows are neighbour rows (group k + slot) or groups."""
+    rows = torch.nonzero(bad.any(1)).flatten()
+    grp = torch.unique(rows // k if per_neighbour else rows)
+    blocks = torch.unique(torch.nonzero(bad.any(0)).flatten() // 32).tolist()
+    s = "%d group(s) %s of %d cloud(s), 32-channel blocks %s" % (grp.numel(), grp[:8].tolist(), torch.unique(grp // S).numel(), blocks)
+    if per_neighbour:
+        s += ", neighbour slots %s" % torch.unique(rows % k)[:16].tolist()
+    return s
+
+
+def assert_interval(out, lo, hi, what, k=None, S=None, slot=None):
+    """Fails unless lo <= out <= hi everywhere (NaN violates).  out / lo / hi [rows, C].  With k and S the message also gives the element's
+    coordinates in the fused grouper (rows = neighbour rows, or groups when `slot` = the reference's arg-max neighbour per element is given)."""
+    assert tuple(out.shape) == tuple(lo.shape) == tuple(hi.shape), "%s: shape %s vs reference %s" % (what, tuple(out.shape), tuple(lo.shape))
+    o = out.double()
+    lo, hi = lo.to(o.device), hi.to(o.device)
+    bad = ~((o >= lo) & (o <= hi))
+    if bool(bad.any()):
+        C = o.shape[1]
+        far = torch.where(bad, torch.nan_to_num(torch.maximum(lo - o, o - hi), nan=float("inf")), torch.full_like(o, -1.0))
+        i = int(far.argmax())
+        r, c = i // C, i % C
+        msg = "%s: %d of %d elements outside their interval.  Worst at (row %d, col %d): got %r, want [%r, %r].  Violations: %s" % (
+            what, int(bad.sum()), bad.numel(), r, c, float(o[r, c]), float(lo[r, c]), float(hi[r, c]), _tile_report(bad, r, c))
+        if k is not None:
+            msg += "; %s; worst: %s" % (_tile_report_groups(bad, k, S, slot is None), _grouper_coords(r, c, k, S, None if slot is None else int(slot[r, c])))
+        raise AssertionError(msg)
+
+
+PINNED_MIN_ROWS = 0.98
+
+
+def check_group_rows(U, stats, ref, D, what):
+    """ldt_group_normalize's U [B S k, ldu] bf16 and fp64 sums [2B] against group_reference: the sums within tol1 / tol2; the normalised columns
+    inside [bf16(pre - a), bf16(pre + a)], at least 98 % of them pinned (a condition on the reference: a case below it needs tamer inputs);
+    the anchor columns == bf16(feat[anchor]) and the padding == 0, bit for bit.  -> dict(pinned, stat = worst err / tol of the sums)."""
+    B, S, k = ref["pre"].shape[:3]
+    st = stats.double().reshape(B, 2).to(ref["s1"].device)
+    e1, e2 = (st[:, 0] - ref["s1"]).abs(), (st[:, 1] - ref["s2"]).abs()
+    assert bool((e1 <= ref["tol1"]).all()) and bool((e2 <= ref["tol2"]).all()), "%s: sums %s vs %s / %s: err %s / %s, tol %s / %s" % (
+        what, st.tolist(), ref["s1"].tolist(), ref["s2"].tolist(), e1.tolist(), e2.tolist(), ref["tol1"].tolist(), ref["tol2"].tolist())
+    lo, hi = bf16_round(ref["pre"] - ref["a"]).reshape(-1, D + 3), bf16_round(ref["pre"] + ref["a"]).reshape(-1, D + 3)
+    pinned = float((lo == hi).double().mean())
+    assert pinned >= PINNED_MIN_ROWS, "%s: only %.4f of the normalised elements are pinned by the reference (needs %.2f)" % (what, pinned, PINNED_MIN_ROWS)
+    assert_interval(U[:, :D + 3], lo, hi, what + ": normalised columns", k=k, S=S)
+    want = ref["anchor"].float().bfloat16()[:, :, None, :].expand(-1, -1, k, -1).reshape(-1, D).to(U.device)
+    assert torch.equal(U[:, D + 3:2 * D + 3], want), what + ": anchor columns differ from bf16(feat[anchor])"
+    assert bool((U[:, 2 * D + 3:].float() == 0).all()), what + ": K padding not zero"
+    return dict(pinned=pinned, stat=float(torch.maximum(e1 / ref["tol1"], e2 / ref["tol2"]).max()))
+
+
+PINNED_MIN, WIDE_MAX = 0.6, 0.15
+
+
+def grouper_staged_reference(g, w1, b1, w2, b2, w3, b3):
+    """Staged float64 reference of grouping + PreExtraction + neighbour max from g = group_reference(..., 'anchor'): bf16 where the kernels round
+    (U, h1, r, out), every stage carrying the allowance e for elements whose rounding an fp32 accumulation can flip (ambiguous_ulp; zero where
+    the pre-activation is below -acc: ReLU gives exactly 0 on both sides), propagated through |W| of the next layer together with that layer's
+    fp32 accumulation bound C_ACC K 2^-24 (|x| |W|^T + |b|) (K = 259, 128, and 160 for layer 3 with its residual k-steps).  The result keeps
+    the allowance PER NEIGHBOUR: lo = bf16(relu(max_j (p3 - a3))), hi = bf16(relu(max_j (p3 + a3))).
+    -> dict(lo, hi, ref [B S, 128], slot = arg-max neighbour of the point reference, pinned = share with lo == hi, wide = share whose interval
+    exceeds 2 bf16 ulps)."""
+    c = C_ACC
+    B, S, k = g["pre"].shape[:3]
+    dv = g["pre"].device
+    W1, W2, W3 = w1.double().to(dv), w2.double().to(dv), w3.double().to(dv)
+    B1, B2, B3 = b1.double().to(dv), b2.double().to(dv), b3.double().to(dv)
+    los, his, refs, slots = [], [], [], []
+    for b in range(B):                                                      # one cloud at a time: the per-neighbour float64 tensors are large
+        anc = g["anchor"][b][:, None, :].expand(-1, k, -1)
+        pu = torch.cat([g["pre"][b], anc], -1)
+        au = torch.cat([g["a"][b], torch.zeros_like(anc)], -1)
+        ru, eu = bf16_round(pu), ambiguous_ulp(pu, au)
+        p1 = ru @ W1.T + B1
+        a1 = eu @ W1.abs().T + c * W1.shape[1] * U24 * (ru.abs() @ W1.abs().T + B1.abs())
+        p1r = torch.relu(p1)
+        r1, e1 = bf16_round(p1r), ambiguous_ulp(p1r, a1) * (p1 > -a1)
+        p2 = r1 @ W2.T + B2
+        a2 = e1 @ W2.abs().T + c * W2.shape[1] * U24 * (r1.abs() @ W2.abs().T + B2.abs())
+        p2r = torch.relu(p2)
+        r2, e2 = bf16_round(p2r), ambiguous_ulp(p2r, a2) * (p2 > -a2)
+        p3 = r2 @ W3.T + B3 + r1
+        a3 = e2 @ W3.abs().T + e1 + c * (W3.shape[1] + 32) * U24 * (r2.abs() @ W3.abs().T + B3.abs() + r1)
+        a3 = a3 + U24 * p3.abs()
+        los.append(bf16_round(torch.relu((p3 - a3).amax(1))))
+        his.append(bf16_round(torch.relu((p3 + a3).amax(1))))
+        m, j = p3.max(1)
+        refs.append(bf16_round(torch.relu(m))); slots.append(j)
+    lo, hi, ref, slot = torch.cat(los), torch.cat(his), torch.cat(refs), torch.cat(slots)
+    wide = (hi - lo) > 2 * bf16_ulp(hi.clamp_min(2.0 ** -126))
+    return dict(lo=lo, hi=hi, ref=ref, slot=slot, pinned=float((lo == hi).double().mean()), wide=float(wide.double().mean()), k=k, S=S)
+
+
+def check_grouper(out, sr, what):
+    """The fused grouper's (or the five-kernel chain's) fp32 [B S, 128] against grouper_staged_reference: the two conditions on the reference
+    (pinned share >= 0.6, wide-interval share <= 0.15: a case outside needs tamer inputs, not wider caps), then the interval per element.
+    -> share of elements that differ from the point reference at all."""
+    assert sr["pinned"] >= PINNED_MIN and sr["wide"] <= WIDE_MAX, "%s: pinned share %.3f (needs %.2f), wide-interval share %.3f (cap %.2f)" % (
+        what, sr["pinned"], PINNED_MIN, sr["wide"], WIDE_MAX)
+    assert_interval(out, sr["lo"], sr["hi"], what, k=sr["k"], S=sr["S"], slot=sr["slot"])
+    return float((out.double() != sr["ref"].to(out.device)).double().mean())
+
+
+# probe (a): one signed unit per W1 row, everything after layer 1 switched off: out[g][c] = max_j relu(+-U[j][sel(c)])
+def grouper_selection_probe(variant, D=128):
+    """-> (w1 [D, 2D+3] with row c = sgn(c) at column sel(c) = (c + D variant) mod (2D + 3): three variants walk all 259 inputs, every layer-1
+    k-step — the three xyz slots of step 16 and the anchor steps included —, sel [D], sgn [D], alpha [D + 3] = +-2^p)."""
+    c = torch.arange(D)
+    sel = (c + D * variant) % (2 * D + 3)
+    sgn = (1 - 2 * ((c + variant) % 2)).float()
+    w1 = torch.zeros(D, 2 * D + 3)
+    w1[c, sel] = sgn
+    i = torch.arange(D + 3)
+    alpha = torch.exp2(((i % 3) - 1).float()) * torch.where(i % 5 == 0, -1.0, 1.0)
+    return w1, sel, sgn, alpha
+
+
+def plant_winners(case, sel, sgn, alpha):
+    """A copy of `case` (distinct points for every (group, slot) and every anchor: needs S (k + 1) <= n) in which neighbour slot (c + s) mod k of
+    group s decides output channel c of probe (a): its value in input column sel(c) is moved 40 cloud scales from the anchor's, towards the
+    sign that survives alpha, W1's sign and the ReLU.  Every slot 0..k-1 — each in-lane max position, both halves, every tile — then decides
+    some output of every group (asserted by the caller on the reference's arg-max)."""
+    B, n, S, k, D = case["B"], case["n"], case["S"], case["k"], case["D"]
+    assert S * (k + 1) <= n
+    g = torch.Generator().manual_seed(1000 + S * k)
+    out = dict(case)
+    feat, xyz = case["feat"].clone(), case["xyz"].clone()
+    fi, ki = torch.empty(B, S, dtype=torch.long), torch.empty(B, S, k, dtype=torch.long)
+    for b in range(B):
+        perm = torch.randperm(n, generator=g)
+        perm = torch.cat([torch.tensor([0, n - 1]), perm[(perm != 0) & (perm != n - 1)]])        # point 0 anchors group 0, point n - 1 is its slot 0
+        fi[b] = perm[torch.arange(S) * (k + 1)]
+        ki[b] = perm[(torch.arange(S)[:, None] * (k + 1) + 1 + torch.arange(k)[None, :])]
+        for c in range(D):
+            col = int(sel[c])
+            if col >= D + 3:
+                continue                                                                          # an anchor column: the same on every slot
+            s = torch.arange(S)
+            p, a = ki[b, s, (c + s) % k], fi[b]
+            push = 40.0 * (1 + b / 2) * float(torch.sign(sgn[c] * alpha[col]))
+            if col < D:
+                feat[b, p, col] = feat[b, a, col] + push
+            else:
+                xyz[b, p, col - D] = xyz[b, a, col - D] + push
+    out.update(feat=feat, xyz=xyz, fi=fi.int(), ki=ki.int())
+    return out
+
+
+def grouper_selection_expected(U, B, S, k, sel, sgn):
+    """out of probe (a) from the grouped rows U [B S k, >= 259] (ops.group_normalize on the same inputs): float64 [B S, 128] and the arg-max slot."""
+    u = U[:, :sel.numel() * 2 + 3].double().reshape(B * S, k, -1)[:, :, sel.to(U.device)] * sgn.double().to(U.device)
+    m, j = torch.relu(u).max(1)
+    return m, j
+
+
+# probe (b): integers all the way
+def grouper_integer_probe(B, n, seed, D=128, device="cpu"):
+    """alpha = 0, beta / features / weights / biases small integers (integer_probe's {-2..2}, sparse — W2 and W3 {-1, 0, 1} and denser; biases {-3..3}): U = [beta | feat[anchor]],
+    and h1, r, out are integers of magnitude <= 256 with every partial sum an integer far below 2^24 — exact in fp32 accumulation of any order
+    and after each bf16 rounding, through all three layers and the residual.  CHECKED on the float64 result over every point as a possible
+    anchor; densities lowered until it holds.  -> (feat [B, n, D], beta, (w1, b1, w2, b2, w3, b3), o float64 [B, n, D] on `device`: the output
+    of a group is o[b, anchor])."""
+    g = torch.Generator().manual_seed(seed)
+    density = 0.1                      # W2 (+-1) at 1.5 x, W3 (+-1) at 1 x: two k-slots of a 32-row fragment then differ in some row in all but ~1e-3 of the pairs
+    for _ in range(10):
+        def draw(r, c, dens, top=3):
+            v = torch.randint(1, top, (r, c), generator=g).float() * (1 - 2 * torch.randint(0, 2, (r, c), generator=g)).float()
+            return v * (torch.rand(r, c, generator=g) < dens).float()
+        feat = draw(B * n, D, 0.3).reshape(B, n, D)
+        beta = draw(1, D + 3, 0.5).reshape(-1)
+        w1, w2, w3 = draw(D, 2 * D + 3, 0.06), draw(D, D, 1.5 * density, 2), draw(D, D, density, 2)
+        b1, b2, b3 = [torch.randint(-3, 4, (D,), generator=g).float() for _ in range(3)]
+        W1, W2, W3 = w1.to(device).double(), w2.to(device).double(), w3.to(device).double()
+        u = torch.cat([beta.to(device).double().expand(B * n, -1), feat.to(device).double().reshape(B * n, D)], -1)
+        h1 = torch.relu(u @ W1.T + b1.to(device).double())
+        r = torch.relu(h1 @ W2.T + b2.to(device).double())
+        o = torch.relu(r @ W3.T + b3.to(device).double() + h1)
+        partial = max(float((u.abs() @ W1.abs().T).max()), float((h1 @ W2.abs().T).max()), float((r @ W3.abs().T + h1).max())) + 3
+        ok = all(float(t.max()) <= 256 and bool((t == t.round()).all()) and torch.equal(bf16_round(t), t) for t in (h1, r, o))
+        if ok and partial < 2 ** 24 and float((o > 0).double().mean()) > 0.2 and float((r > 0).double().mean()) > 0.2:
+            return feat, beta, (w1, b1, w2, b2, w3, b3), o.reshape(B, n, D)
+        density *= 0.9
+    raise AssertionError("grouper_integer_probe: no density keeps h1, r and out within 256")
+
+
+def guarded(rows, cols, fill, device, guard=4096):
+    """-> (big, view): a contiguous fp32 [rows, cols] view (16-byte aligned) in the middle of a buffer whose `guard` elements on either side hold a
+    sentinel, the view itself `fill`."""
+    big = torch.full((rows * cols + 2 * guard,), SENT_F32, dtype=torch.float32, device=device)
+    view = big[guard:guard + rows * cols].view(rows, cols)
+    view.fill_(fill)
+    return big, view
+
+
+SENT_F32 = -1.7014118e38                         # a bit pattern no kernel under test produces
+
+
+def assert_guard_intact(big, numel, what, guard=4096):
+    lo, hi = big[:guard], big[guard + numel:]
+    bad = int((lo != SENT_F32).sum()) + int((hi != SENT_F32).sum())
+    if bad:
+        where = torch.nonzero(torch.cat([lo, hi]) != SENT_F32).flatten()
+        raise AssertionError("%s: %d element(s) written outside `out` (first at offset %d of the surround: %s the view)" % (
+            what, bad, int(where[0]), "before" if int(where[0]) < guard else "%d after the end of" % (int(where[0]) - guard)))

@@ -405,6 +405,17 @@ def test_fused_grouper_vs_oracle_and_chain(mods, B, n, S, k):
     # same bf16 operands and roundings, another summation order: equal up to a bf16 ulp on a few elements
     assert rel_mse(fused[1], chain[1]) < 1e-5
     assert float((fused[1] != chain[1]).float().mean()) < 0.25
+    # ... and per element: both paths inside the interval of the staged float64 reference (kernel_checks.grouper_staged_reference; the
+    # instrument of test_gpu_grouper_exact.py, here on the indices FPS and kNN chose), the kernels' sums within 2^-24 of float64 first
+    import kernel_checks as kc
+    fd, pd, fid, kid = feat.cuda(), p.cuda(), fused[2], fused[3]
+    g = kc.group_reference(fd, pd, fid, kid, G["alpha"], G["beta"], stats_rel=kc.U24)
+    st = ops.group_normalize(fd, pd, fid, kid, G["alpha"], G["beta"], return_stats=True)[1].reshape(B, 2)
+    assert bool(((st[:, 0] - g["s1"]).abs() <= g["tol1"]).all()) and bool(((st[:, 1] - g["s2"]).abs() <= g["tol2"]).all())
+    sr = kc.grouper_staged_reference(g, G["w_pre1"][:, :2 * D + 3].float(), G["b_pre1"], G["w_pre2"][:, :D].float(), G["b_pre2"],
+                                     G["w_pre3"][:, :D].float(), G["b_pre3"])
+    kc.check_grouper(fused[1], sr, "fused grouper B %d n %d S %d k %d" % (B, n, S, k))
+    kc.check_grouper(chain[1], sr, "five-kernel chain B %d n %d S %d k %d" % (B, n, S, k))
 
 
 @pytest.mark.parametrize("n,S,k,levels", [(2048, 64, 16, 3), (1000, 16, 32, 2), (640, 9, 64, 5), (2048, 8, 16, 40)])

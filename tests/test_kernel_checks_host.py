@@ -215,3 +215,196 @@ def test_planted_shifted_fold_segment_fails(B, T, H, K, granule, segment):
     out = attend(*split(project_folded(xs, w, S, Cc, stats, False, shift_segment=segment).bfloat16(), H * DH), B, H, T, T)
     with pytest.raises(AssertionError, match="outside the bound"):
         check_c(out, pre, acc, B, H, T, "shifted S | C segment")
+
+
+# ============================================================================================================= grouped rows + the fused grouper
+# An emulation of csrc/grouper_mlp.hip's contract: fp32 statistics and normalisation, bf16 at U, h1, r and out, fp32 accumulation in two k
+# orders, 32-row tiles (k = 8 / 16: 4 / 2 groups per tile with a ragged last tile, k = 32 m: m tiles combined by a max onto a zeroed buffer),
+# writing into a guarded buffer like the GPU module's.  FAULTS are the ways such a kernel goes subtly wrong.
+FAULTS = ("drop_one", "stale_inv", "xyz_zero", "swap_l2", "ragged_store", "no_zero")
+bf = lambda t: t.float().bfloat16().float()
+
+
+def mm16(a, w, rev):
+    """fp32 accumulation over K in 16-steps (the MFMA k-step), forward or reversed."""
+    steps = list(range(0, a.shape[-1], 16))
+    acc = torch.zeros(*a.shape[:-1], w.shape[0])
+    for k0 in (reversed(steps) if rev else steps):
+        acc = acc + a[..., k0:k0 + 16] @ w[:, k0:k0 + 16].T
+    return acc
+
+
+def emulate_rows(c, mode="anchor", stale=False, wrong_mean=False):
+    """ldt_group_normalize in fp32 -> (U bf16-valued float [B S k, 2D+3], sums float64 [2B])."""
+    B, S, k, D = c["B"], c["S"], c["k"], c["D"]
+    fi, ki = c["fi"].long(), c["ki"].long()
+    G = torch.cat([kc._take(c["feat"], ki), kc._take(c["xyz"], ki)], -1)
+    anc = kc._take(c["feat"], fi)
+    if mode == "anchor":
+        org = torch.cat([anc, kc._take(c["xyz"], fi)], -1)[:, :, None]
+    else:
+        org = torch.zeros(B, S, 1, D + 3)
+        for j in range(k):
+            org = org + G[:, :, j:j + 1]
+        org = org / float(k)
+        if wrong_mean:
+            org = org.roll(1, 1)
+    d = G - org
+    s1, s2 = d.double().sum((1, 2, 3)), (d.double() ** 2).sum((1, 2, 3))
+    cnt = float(S * k * (D + 3))
+    var = ((s2 - cnt * (s1 / cnt) ** 2) / (cnt - 1)).clamp_min(0)
+    inv = (1.0 / (var.sqrt().float() + torch.tensor(1e-5)))[:, None, None, None]
+    if stale:
+        inv = inv[[0] * B]
+    u = torch.cat([c["alpha"] * (d * inv) + c["beta"], anc[:, :, None].expand(-1, -1, k, -1)], -1)
+    return bf(u).reshape(B * S * k, -1), torch.stack([s1, s2], 1).reshape(-1)
+
+
+def emulate_grouper(c, W, rev=False, fault=None, fill=float("nan")):
+    """-> (big, out view [B S, 128]) of kc.guarded, filled like the GPU module fills it."""
+    B, S, k = c["B"], c["S"], c["k"]
+    w1, b1, w2, b2, w3, b3 = W
+    u, _ = emulate_rows(c, stale=fault == "stale_inv")
+    u = u.reshape(B, S, k, -1).clone()
+    if fault == "xyz_zero":
+        u[..., 128:131] = 0
+    if fault == "swap_l2":                                          # two k-slots of one layer-2 fragment (k-step 3, channel block 1) exchanged
+        w2 = w2.clone()
+        w2[32:64, [50, 53]] = w2[32:64, [53, 50]]
+    h1 = bf(torch.relu(mm16(u, w1, rev) + b1))
+    r = bf(torch.relu(mm16(h1, w2, rev) + b2))
+    o = mm16(r, w3, rev) + b3 + h1                                  # [B, S, k, 128]
+    if fault == "drop_one":                                         # the neighbour that decides channel 0 of group (0, 0) never enters the max
+        o[0, 0, int(o[0, 0, :, 0].argmax())] = float("-inf")
+    big, out = kc.guarded(B * S, 128, fill, "cpu")
+    flat = big[4096:]                                               # rows addressed from the view's start, like the kernel's pointer
+    if k > 32:
+        if fault != "no_zero":
+            out.zero_()
+        for t in range(k // 32):                                    # the tiles of a group meet in memory
+            out.copy_(torch.maximum(out, bf(torch.relu(o[:, :, 32 * t:32 * t + 32].amax(2))).reshape(B * S, 128)))
+    else:
+        res = bf(torch.relu(o.amax(2)))
+        out.copy_(res.reshape(B * S, 128))
+        gpt = 32 // k
+        if fault == "ragged_store" and S % gpt:                     # the repeated last group of the ragged tile is stored after group S - 1
+            for b in range(B):
+                flat[(b * S + S) * 128:(b * S + S + 1) * 128] = res[b, S - 1]
+    return big, out
+
+
+def wimg_of(W):
+    from ldt_amd.compressor import _grouper_fragment_image
+    return _grouper_fragment_image(W[0], W[2], W[4])
+
+
+def staged(c, W):
+    g = kc.group_reference(c["feat"], c["xyz"], c["fi"], c["ki"], c["alpha"], c["beta"], stats_rel=kc.U24)
+    st = emulate_rows(c)[1].reshape(-1, 2)
+    assert bool(((st[:, 0] - g["s1"]).abs() <= g["tol1"]).all()) and bool(((st[:, 1] - g["s2"]).abs() <= g["tol2"]).all())
+    return kc.grouper_staged_reference(g, *W)
+
+
+def probe_a(c0, variant, fault=None, rev=False):
+    """-> (got, want, slot) of probe (a) on the emulation; `want` from the emulation of ldt_group_normalize (never faulty)."""
+    w1, sel, sgn, alpha = kc.grouper_selection_probe(variant)
+    c = kc.plant_winners(dict(c0, alpha=alpha, beta=torch.zeros(131)), sel, sgn, alpha)
+    z = torch.zeros(128)
+    _, got = emulate_grouper(c, (w1, z, torch.zeros(128, 128), z, torch.zeros(128, 128), z), rev=rev, fault=fault)
+    U, _ = emulate_rows(c)
+    want, slot = kc.grouper_selection_expected(U, c["B"], c["S"], c["k"], sel, sgn)
+    return got, want, slot, sel
+
+
+def probe_b(c0, fault=None, rev=False):
+    feat, beta, W, o = kc.grouper_integer_probe(c0["B"], c0["n"], 5)
+    c = dict(c0, feat=feat, alpha=torch.zeros(131), beta=beta)
+    _, got = emulate_grouper(c, W, rev=rev, fault=fault)
+    return got, kc._take(o, c["fi"].long()).reshape(-1, 128)
+
+
+GROUPER_SHAPES = [(3, 300, 7, 8), (2, 512, 5, 64)]                  # 4 groups per tile with a ragged last tile; two tiles per group
+
+
+@pytest.mark.parametrize("mode,D,k", [("anchor", 128, 16), ("anchor", 64, 5), ("anchor", 20, 8), ("center", 128, 8), ("center", 32, 5)])
+def test_group_rows_emulation_passes_and_a_stale_inv_or_wrong_mean_fails(mode, D, k):
+    # (the degenerate cloud belongs to 'anchor' mode, where d == 0 exactly; around a group MEAN a cloud without spread leaves only the mean's
+    # own fp32 rounding, multiplied by 1 / 1e-5: nothing there can be pinned)
+    c = kc.grouper_case(3, 200, 6, k, 3, D=D, degenerate=1 if mode == "anchor" else None)
+    ref = kc.group_reference(c["feat"], c["xyz"], c["fi"], c["ki"], c["alpha"], c["beta"], mode)
+    U, st = emulate_rows(c, mode)
+    res = kc.check_group_rows(U.bfloat16(), st, ref, D, "rows")
+    assert res["pinned"] >= 0.98 and res["stat"] <= 1.0
+    if mode == "anchor":
+        assert torch.equal(U.reshape(3, -1, 2 * D + 3)[1, :, :D + 3], bf(c["beta"]).expand(6 * k, -1))  # the degenerate cloud: bf16(beta)
+    with pytest.raises(AssertionError, match="outside their interval"):
+        kc.check_group_rows(emulate_rows(c, mode, stale=True)[0].bfloat16(), st, ref, D, "stale inv")
+    if mode == "center":
+        with pytest.raises(AssertionError):
+            U2, st2 = emulate_rows(c, mode, wrong_mean=True)
+            kc.check_group_rows(U2.bfloat16(), st2, ref, D, "mean of the neighbouring group")
+
+
+@pytest.mark.parametrize("B,n,S,k", GROUPER_SHAPES)
+def test_grouper_emulation_passes_a_b_c_in_both_orders(B, n, S, k):
+    c = kc.grouper_case(B, n, S, k, 1)
+    W = kc.grouper_weights(2)
+    sr = staged(c, W)
+    for rev in (False, True):
+        big, out = emulate_grouper(c, W, rev=rev)
+        mism = kc.check_grouper(out, sr, "emulation (c) rev %d" % rev)
+        kc.assert_guard_intact(big, out.numel(), "emulation")
+        assert mism < 0.01
+        slots = set()
+        for v in range(3):
+            got, want, slot, sel = probe_a(c, v, rev=rev)
+            assert torch.equal(got.double(), want)
+            slots |= set(slot[:, sel < 131].flatten().tolist())
+        assert slots == set(range(k))                               # every register position decided some output
+        got, want = probe_b(c, rev=rev)
+        assert torch.equal(got.double(), want)
+    assert wimg_of(W).numel() == 132 * 512                          # the image the GPU module builds from the same panels
+
+
+def old_test_passes(c, W, got):
+    """What test_fused_grouper_vs_oracle_and_chain asks: rel-MSE < 1e-4 against an fp32 evaluation, < 1e-5 and fewer than 25 % of the elements
+    different against the (clean) chain."""
+    w1, b1, w2, b2, w3, b3 = [t.double() for t in W]
+    g = kc.group_reference(c["feat"], c["xyz"], c["fi"], c["ki"], c["alpha"], c["beta"])
+    u = torch.cat([g["pre"], g["anchor"][:, :, None].expand(-1, -1, c["k"], -1)], -1)
+    h1 = torch.relu(u @ w1.T + b1)
+    ref = torch.relu(torch.relu(h1 @ w2.T + b2) @ w3.T + b3 + h1).amax(2).reshape(-1, 128)
+    chain = emulate_grouper(c, W, rev=True)[1].double()
+    rel = lambda a, b: float(((a.double() - b) ** 2).sum() / (b ** 2).sum())
+    return rel(got, ref) < 1e-4 and rel(got, chain) < 1e-5 and float((got.double() != chain).double().mean()) < 0.25
+
+
+@pytest.mark.parametrize("fault", FAULTS)
+def test_planted_grouper_faults_fail(fault):
+    """Each fault fails the checks named for it (at the shape where it can occur)."""
+    W = kc.grouper_weights(2)
+    shapes = {"ragged_store": GROUPER_SHAPES[:1], "no_zero": GROUPER_SHAPES[1:]}.get(fault, GROUPER_SHAPES)
+    for B, n, S, k in shapes:
+        c = kc.grouper_case(B, n, S, k, 1)
+        sr = staged(c, W)
+        big, out = emulate_grouper(c, W, fault=fault, fill=3.0e38 if k > 32 else float("nan"))
+        if fault == "ragged_store":
+            with pytest.raises(AssertionError, match="written outside"):
+                kc.assert_guard_intact(big, out.numel(), fault)
+        with pytest.raises(AssertionError, match="outside their interval"):
+            kc.check_grouper(out, sr, fault)
+        if fault in ("drop_one", "stale_inv", "xyz_zero"):
+            assert not all(torch.equal(g.double(), w) for g, w, _, _ in (probe_a(c, v, fault=fault) for v in range(3)))
+        if fault == "swap_l2":
+            got, want = probe_b(c, fault=fault)
+            assert not torch.equal(got.double(), want)
+
+
+def test_a_dropped_neighbour_passes_what_the_rel_mse_test_asks_and_fails_the_interval():
+    """The shipped main-group shape (32 groups of 128): the neighbour that decides channel 0 of ONE group left out of the max."""
+    W = kc.grouper_weights(2)
+    c = kc.grouper_case(2, 2048, 32, 128, 1)
+    _, out = emulate_grouper(c, W, fault="drop_one")
+    assert old_test_passes(c, W, out)
+    with pytest.raises(AssertionError, match="outside their interval"):
+        kc.check_grouper(out, staged(c, W), "dropped neighbour")
