@@ -516,8 +516,8 @@ def ln_mlp_resid_(x, w_up, b_up, w_dn, b_dn, ln_w=None, ln_b=None, shift=None, s
     """In place: x += gate * MLP(LN(x)[affine | modulated]) for C in {64, 128} channels (one fused kernel).
     x_bf16_out: optional bf16 [M, >=C] row-major tensor that receives a copy of the updated x in the same pass.
     next_linear: optional dict(w=bf16 [N, C], bias=fp32 [N] | None, ln_w=, ln_b= | shift=, scale=, mod_sample_stride=,
-    rows_per_sample=) — the following block's LayerNorm + first projection, computed on the updated rows by the same kernel;
-    then returns (x, out bf16 [M, N]) instead of x."""
+    rows_per_sample=, out= bf16 [M, N] row-major view to write into | None) — the following block's LayerNorm + first projection,
+    computed on the updated rows by the same kernel; then returns (x, out bf16 [M, N]) instead of x."""
     _need(x, torch.float32, "x"); _rowmajor(x, "x")
     M, Cc = x.shape
     if x_bf16_out is not None:
@@ -537,7 +537,7 @@ def ln_mlp_resid_(x, w_up, b_up, w_dn, b_dn, ln_w=None, ln_b=None, shift=None, s
     _need(wn, torch.bfloat16, "next w")
     if wn.shape[1] != Cc or not wn.is_contiguous():
         raise ValueError("ln_mlp_resid_: next_linear w must be dense bf16 [N][C]")
-    out = torch.empty((M, wn.shape[0]), dtype=torch.bfloat16, device=x.device)
+    out = _bf16_rows_out(nx.get("out"), M, wn.shape[0], x.device, "ln_mlp_resid_: next_linear out")
     check(lib().ldt_ln_mlp_resid_next(_p(x), x.stride(0), M, Cc, _p(ln_w), _p(ln_b), _p(shift), _p(scale), _p(gate), mod_sample_stride,
                                       rows_per_sample, _p(w_up), _p(b_up), _p(w_dn), _p(b_dn), _p(x_bf16_out), ldxb,
                                       _p(nx.get("ln_w")), _p(nx.get("ln_b")), _p(nx.get("shift")), _p(nx.get("scale")),
@@ -608,14 +608,25 @@ def qkv_attention(x, w, B, tokens, heads, bias=None, stats=None, fold_s=None, fo
     return out
 
 
-def ln_linear(x, w, bias=None, ln_w=None, ln_b=None, shift=None, scale=None, mod_sample_stride=0, rows_per_sample=0):
-    """bf16 [M,N] = LN(x)[affine | modulated] @ w[N,C]^T + bias for C in {64, 128} channels, N % 64 == 0 (one fused kernel)."""
+def _bf16_rows_out(out, M, N, device, name):
+    """A fresh bf16 [M, N], or the caller's: a row-major [M, N] view (row stride >= N) on `device`."""
+    if out is None:
+        return torch.empty((M, N), dtype=torch.bfloat16, device=device)
+    _need(out, torch.bfloat16, name); _rowmajor(out, name)
+    if tuple(out.shape) != (M, N) or out.device != device:
+        raise ValueError("%s must be a bf16 [%d, %d] row-major tensor (or view) on the operands' device" % (name, M, N))
+    return out
+
+
+def ln_linear(x, w, bias=None, ln_w=None, ln_b=None, shift=None, scale=None, mod_sample_stride=0, rows_per_sample=0, out=None):
+    """bf16 [M,N] = LN(x)[affine | modulated] @ w[N,C]^T + bias for C in {64, 128} channels, N % 64 == 0 (one fused kernel).
+    out: a bf16 [M, N] row-major tensor (or view, row stride >= N) to write into."""
     _need(x, torch.float32, "x"); _rowmajor(x, "x"); _need(w, torch.bfloat16, "w")
     M, Cc = x.shape
     N = w.shape[0]
     if w.shape[1] != Cc or not w.is_contiguous():
         raise ValueError("ln_linear: w must be dense bf16 [N][C]")
-    out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    out = _bf16_rows_out(out, M, N, x.device, "ln_linear: out")
     check(lib().ldt_ln_linear(_p(x), x.stride(0), M, Cc, _p(ln_w), _p(ln_b), _p(shift), _p(scale), mod_sample_stride, rows_per_sample,
-                              _p(w), _p(bias), N, _p(out), N, stream_ptr()), "ldt_ln_linear")
+                              _p(w), _p(bias), N, _p(out), out.stride(0), stream_ptr()), "ldt_ln_linear")
     return out

@@ -617,3 +617,202 @@ def assert_guard_intact(big, numel, what, guard=4096):
         where = torch.nonzero(torch.cat([lo, hi]) != SENT_F32).flatten()
         raise AssertionError("%s: %d element(s) written outside `out` (first at offset %d of the surround: %s the view)" % (
             what, bad, int(where[0]), "before" if int(where[0]) < guard else "%d after the end of" % (int(where[0]) - guard)))
+
+
+# ------------------------------------------------------------------------------------------------------------- fused LN + MLP / LN + linear
+# (csrc/fused_mlp.hip; test_gpu_fused_mlp_exact.py; validated without a GPU, planted faults included, by test_kernel_checks_host.py)
+#
+# The worst-case bound of test_ln_linear_and_ln_mlp_guard_bands_and_bounds carries 2^-8 per bf16 stage through |W_up|, GELU and |W_dn|: it is
+# several times the update itself.  As for the grouper, the reference here rounds where the kernel rounds (h, u) and allows, per element, only
+# what fp32 arithmetic can do to that rounding: nothing, except within the accumulation error of a rounding boundary, where it is one ulp.
+LN_ALLOW = 4 * 2.0 ** -20          # fp32 LayerNorm of a normalised value (test_layernorm_modulate_and_cast_pad_guard_bands)
+MLP_TOL_CAP = 0.02                 # condition on the reference: median(tol) <= this x median(|gate * update|)
+LNLIN_PINNED_MIN, LNLIN_WIDE_MAX = 0.8, 0.05
+
+
+def sample_rows(t, n, rows_per_sample, row0=0):
+    """Per-sample rows t [nS, C] -> float64 [n, C]: row r of the result is t[(row0 + r) // rows_per_sample]."""
+    return t.double()[(torch.arange(n, device=t.device) + row0) // rows_per_sample]
+
+
+def ln_stage(x, ln_w=None, ln_b=None, shift=None, scale=None, rows_per_sample=0, row0=0):
+    """Stage h of both kernels in float64: LN(x) (eps 1e-6, biased variance), then * w + b and / or * (1 + scale) + shift (in this order, as
+    the kernel; shift / scale [nS, C] per-sample rows taken by (row0 + row) // rows_per_sample).  Allowance a = 4 2^-20 (1 + |h^|) times
+    (1 + |w|) and / or (1 + |scale|): what fp32 mean / variance / rsqrt leave on h^, carried through the factors that follow.
+    -> (pre, a, r = bf16_round(pre), e = ambiguous_ulp(pre, a))."""
+    xd = x.double()
+    hhat = (xd - xd.mean(1, keepdim=True)) / torch.sqrt(xd.var(1, unbiased=False, keepdim=True) + 1e-6)
+    pre, f = hhat, torch.ones_like(hhat)
+    if ln_w is not None:
+        w = ln_w.double().to(xd.device)
+        pre, f = pre * w + ln_b.double().to(xd.device), f * (1 + w.abs())
+    if shift is not None:
+        sc = sample_rows(scale.to(xd.device), xd.shape[0], rows_per_sample, row0)
+        pre, f = pre * (1 + sc) + sample_rows(shift.to(xd.device), xd.shape[0], rows_per_sample, row0), f * (1 + sc.abs())
+    a = LN_ALLOW * (1 + hhat.abs()) * f
+    return pre, a, bf16_round(pre), ambiguous_ulp(pre, a)
+
+
+def fused_mlp_reference(x, w_up, b_up, w_dn, b_dn, ln_w=None, ln_b=None, shift=None, scale=None, gate=None, rows_per_sample=0, row_chunk=16384):
+    """Staged float64 reference of ln_mlp_resid_kernel on x [M, C] (fp32), on x's device, `row_chunk` rows at a time:
+      h:   pre_h, a_h, r_h, e_h = ln_stage(...)
+      u:   p_u = r_h W_up^T + b_up, a_u = e_h |W_up|^T + C_ACC C 2^-24 (|r_h| |W_up|^T + |b_up|); p_g = gelu(p_u), a_g = GELU_SLOPE a_u +
+           GELU_FAST_ABS; r_u = bf16_round(p_g), e_u = ambiguous_ulp(p_g, a_g)
+      out: upd = r_u W_dn^T + b_dn, ref = x + g upd (g = the gate's per-sample row, 1 without a gate), and, the output being fp32,
+           tol = |g| (e_u |W_dn|^T + C_ACC 4C 2^-24 (|r_u| |W_dn|^T + |b_dn|)) + 2 2^-24 (|x| + |g upd|) + 2^-24 |ref|.
+    -> dict(ref, tol [M, C], amb_h, amb_u = the shares of h / u elements whose rounding may flip, ratio = median(tol) / median(|g upd|))."""
+    dv, (M, C) = x.device, x.shape
+    Wu, Bu, Wd, Bd = w_up.double().to(dv), b_up.double().to(dv), w_dn.double().to(dv), b_dn.double().to(dv)
+    refs, tols, gus, nh, nu = [], [], [], 0.0, 0.0
+    for r0 in range(0, M, row_chunk):
+        xs = x[r0:r0 + row_chunk].double()
+        _, _, rh, eh = ln_stage(xs, ln_w, ln_b, shift, scale, rows_per_sample, r0)
+        ru_abs = rh.abs() @ Wu.abs().T
+        pu = rh @ Wu.T + Bu
+        au = eh @ Wu.abs().T + C_ACC * C * U24 * (ru_abs + Bu.abs())
+        pg = torch.nn.functional.gelu(pu)
+        ag = GELU_SLOPE * au + GELU_FAST_ABS
+        ru, eu = bf16_round(pg), ambiguous_ulp(pg, ag)
+        upd = ru @ Wd.T + Bd
+        g = torch.ones_like(xs) if gate is None else sample_rows(gate.to(dv), xs.shape[0], rows_per_sample, r0)
+        ref = xs + g * upd
+        tol = g.abs() * (eu @ Wd.abs().T + C_ACC * 4 * C * U24 * (ru.abs() @ Wd.abs().T + Bd.abs())) + 2 * U24 * (xs.abs() + (g * upd).abs()) + U24 * ref.abs()
+        refs.append(ref); tols.append(tol); gus.append((g * upd).abs())
+        nh += float((eh > 0).double().sum()); nu += float((eu > 0).double().sum())
+    ref, tol, gu = torch.cat(refs), torch.cat(tols), torch.cat(gus)
+    return dict(ref=ref, tol=tol, amb_h=nh / (M * C), amb_u=nu / (M * 4 * C), ratio=float(tol.median() / gu.median()))
+
+
+def check_fused_mlp(x_out, sr, what):
+    """ln_mlp_resid_'s x against fused_mlp_reference: the condition on the reference first (median(tol) <= 0.02 median(|g upd|): a case beyond
+    it needs tamer inputs, never a wider cap), then every element.  -> worst err / tol."""
+    assert sr["ratio"] <= MLP_TOL_CAP, "%s: median(tol) / median(|update|) = %.4f (cap %g)" % (what, sr["ratio"], MLP_TOL_CAP)
+    return assert_elementwise(x_out, sr["ref"], sr["tol"], what)
+
+
+def ln_linear_reference(x, w, bias=None, ln_w=None, ln_b=None, shift=None, scale=None, rows_per_sample=0, row_chunk=16384):
+    """Interval reference of ln_linear_kernel (and of the projection ln_mlp_resid_kernel chains): pre = r_h W^T + b, a = e_h |W|^T +
+    C_ACC C 2^-24 (|r_h| |W|^T + |b|), lo = bf16_round(pre - a), hi = bf16_round(pre + a) (rounding is monotone).
+    -> dict(lo, hi, ref = bf16_round(pre) [M, N], pinned = share with lo == hi, wide = share whose interval exceeds 2 bf16 ulps)."""
+    dv, (M, C) = x.device, x.shape
+    W = w.double().to(dv)
+    B = torch.zeros(W.shape[0], dtype=torch.float64, device=dv) if bias is None else bias.double().to(dv)
+    los, his, refs = [], [], []
+    for r0 in range(0, M, row_chunk):
+        _, _, rh, eh = ln_stage(x[r0:r0 + row_chunk], ln_w, ln_b, shift, scale, rows_per_sample, r0)
+        pre = rh @ W.T + B
+        a = eh @ W.abs().T + C_ACC * C * U24 * (rh.abs() @ W.abs().T + B.abs())
+        los.append(bf16_round(pre - a)); his.append(bf16_round(pre + a)); refs.append(bf16_round(pre))
+    lo, hi, ref = torch.cat(los), torch.cat(his), torch.cat(refs)
+    wide = (hi - lo) > 2 * bf16_ulp(torch.maximum(lo.abs(), hi.abs()))
+    return dict(lo=lo, hi=hi, ref=ref, pinned=float((lo == hi).double().mean()), wide=float(wide.double().mean()))
+
+
+def check_ln_linear(out, sr, what):
+    """A bf16 [M, N] output against ln_linear_reference: the two conditions on the reference (pinned share >= 0.8, wide-interval share <= 0.05: a
+    case outside needs tamer inputs, not wider caps), then the interval per element.  -> share of elements that differ from the point reference."""
+    assert sr["pinned"] >= LNLIN_PINNED_MIN and sr["wide"] <= LNLIN_WIDE_MAX, "%s: pinned share %.3f (needs %.2f), wide-interval share %.3f (cap %.2f)" % (
+        what, sr["pinned"], LNLIN_PINNED_MIN, sr["wide"], LNLIN_WIDE_MAX)
+    assert_interval(out, sr["lo"], sr["hi"], what)
+    return float((out.double() != sr["ref"].to(out.device)).double().mean())
+
+
+def mlp_randn_case(M, C, seed, n_samples=1, N=0, tame=False):
+    """The data of the randn checks: x = 2 randn + 0.3, bf16-exact W ~ randn / sqrt(K), b ~ 0.1 randn, an affine pair (w in [1, 2), b ~ 0.2 randn)
+    and per-sample modulation rows shift | scale | gate ~ 0.5 randn as one [n_samples, 3C] tensor; with N a next-block projection wn [N, C], bn
+    and its own affine pair.  The allowance of h is 4 2^-20 (1 + |h^|) (1 + |w|) (1 + |scale|) against a value that grows with |w| |1 + scale|
+    only, so small |w| and scale near -1 unpin outputs: with w in [0.5, 1.5) an affine C = 128 case sits at 79 .. 83 % pinned, astride the
+    condition.  tame (where an affine LayerNorm and a modulation meet, and for fewer than 16 rows, where one sample's modulation row decides the
+    whole case): w in [2, 3) and modulation ~ 0.25 randn.  -> dict of CPU tensors (weights float32 holding bf16 values)."""
+    g = torch.Generator().manual_seed(seed)
+    bf = lambda t: t.bfloat16().float()
+    lo, ms = (2.0, 0.25) if tame else (1.0, 0.5)
+    d = dict(x=torch.randn(M, C, generator=g) * 2 + 0.3,
+             w_up=bf(torch.randn(4 * C, C, generator=g) / C ** 0.5), b_up=torch.randn(4 * C, generator=g) * 0.1,
+             w_dn=bf(torch.randn(C, 4 * C, generator=g) / (4 * C) ** 0.5), b_dn=torch.randn(C, generator=g) * 0.1,
+             ln_w=torch.rand(C, generator=g) + lo, ln_b=torch.randn(C, generator=g) * 0.2,
+             mod=torch.randn(n_samples, 3 * C, generator=g) * ms)
+    if N:
+        d.update(wn=bf(torch.randn(N, C, generator=g) / C ** 0.5), bn=torch.randn(N, generator=g) * 0.1,
+                 nln_w=torch.rand(C, generator=g) + lo, nln_b=torch.randn(C, generator=g) * 0.2)
+    return d
+
+
+# exact probes.  Two facts carry them (both asserted on the host, test_kernel_checks_host.py): (1) the LayerNorm can be switched off from the
+# outside: with scale = -1 the kernel computes h^ * 0 + shift == shift for any finite x (per sample, or per row with rows_per_sample = 1), and with
+# ln_w = 0 h == ln_b in every row; (2) gelu_erf_fast / gelu_erf_fast2 are exactly relu at 0 and at every |v| >= 6.
+def probe_gates(n_samples, C, g):
+    """Gates from {1, -1, 2, -2, 1/2} per (sample, channel)."""
+    return torch.tensor([1.0, -1.0, 2.0, -2.0, 0.5])[torch.randint(0, 5, (n_samples, C), generator=g)]
+
+
+def _sparse_ints(g, r, c, density, top=3):
+    v = torch.randint(1, top, (r, c), generator=g).float() * (1 - 2 * torch.randint(0, 2, (r, c), generator=g)).float()
+    return v * (torch.rand(r, c, generator=g) < density).float()
+
+
+def mlp_integer_probe(M, C, rows_per_sample, seed, gated, device="cpu"):
+    """Integers through the whole MLP.  h = the shift rows = 8 x sparse {-2..2} per sample (scale = -1 switches the LayerNorm off), W_up sparse
+    {-2..2}, b_up = 8 x {-3..3}: every hidden pre-activation is a multiple of 8, i.e. 0 or at least 8 in magnitude, where the kernel's GELU is
+    exactly relu; u is then a multiple of 8 up to 2048 (bf16-exact).  W_dn sparse {-2..2}, b_dn {-3..3}, x sparse {-2..2}, gates from
+    {+-1, +-2, 1/2}: every partial sum is a multiple of 1/2 far below 2^24, exact in fp32 in any order, with or without FMA contraction.  All
+    of that is CHECKED on the float64 result, and the densities lowered until it holds.
+    -> dict(x, shift, scale, gate (None when not `gated`), w_up, b_up, w_dn, b_dn: float32 CPU tensors; ref: float64 [M, C] on `device`)."""
+    g = torch.Generator().manual_seed(seed)
+    nS = (M + rows_per_sample - 1) // rows_per_sample
+    density = 0.25
+    for _ in range(10):
+        shift = 8 * _sparse_ints(g, nS, C, 0.4)
+        w_up, b_up = _sparse_ints(g, 4 * C, C, density), 8 * torch.randint(-3, 4, (4 * C,), generator=g).float()
+        w_dn, b_dn = _sparse_ints(g, C, 4 * C, density), torch.randint(-3, 4, (C,), generator=g).float()
+        x = _sparse_ints(g, M, C, 0.5)
+        gate = probe_gates(nS, C, g) if gated else None
+        dd = lambda t: t.double().to(device)
+        h = sample_rows(dd(shift), M, rows_per_sample)
+        pu = h @ dd(w_up).T + dd(b_up)
+        u = torch.relu(pu)
+        upd = u @ dd(w_dn).T + dd(b_dn)
+        gg = sample_rows(dd(gate), M, rows_per_sample) if gated else torch.ones_like(upd)
+        ref = dd(x) + gg * upd
+        partial = float((dd(x).abs() + gg.abs() * (u @ dd(w_dn).abs().T + dd(b_dn).abs())).max())
+        partial_u = float((h.abs() @ dd(w_up).abs().T + dd(b_up).abs()).max())
+        ok = torch.equal(bf16_round(h), h) and torch.equal(bf16_round(u), u) and bool((pu == 8 * (pu / 8).round()).all()) and float(u.max()) <= 2048
+        ok = ok and bool((2 * ref == (2 * ref).round()).all()) and max(partial, partial_u) < 2 ** 22 and torch.equal(ref.float().double(), ref)
+        if ok and float((u > 0).double().mean()) > 0.2 and float((upd != 0).double().mean()) > 0.5:
+            return dict(x=x, shift=shift, scale=torch.full_like(shift, -1.0), gate=gate, w_up=w_up, b_up=b_up, w_dn=w_dn, b_dn=b_dn, ref=ref)
+        density *= 0.8
+    raise AssertionError("mlp_integer_probe: no density keeps every stage exact at M=%d C=%d" % (M, C))
+
+
+def mlp_selection_probe(M, C, rows_per_sample, seed, gated, device="cpu"):
+    """A signed gather through the MLP.  h = the shift rows = 8 (1 + (37 c + 101 s) mod 255): multiples of 8 in [8, 2040], distinct over the
+    channels of a sample and, for one channel, over any 255 consecutive samples.  W_up is a signed one-hot: hidden unit j reads channel
+    sel(j) = (37 j + j // C) mod C with sign -1 when j % 4 == 3 (every channel is read with sign +1 by some unit), b_up = 0: u[j] =
+    relu(+-h[sel(j)]).  W_dn sums a few hidden units: unit j enters output j % C with weight 1 + j // C and output (7 j + 1 + j // C) mod C
+    with weight -(5 + j % 3), so no unit's column of W_dn is zero and no two units have the same one (checked): a hidden unit read from the wrong k-slot, chunk or row
+    changes the result.  x sparse {-2..2}, b_dn {-3..3}, gates from {+-1, +-2, 1/2}; exactness checked as in mlp_integer_probe.
+    -> the same dict as mlp_integer_probe."""
+    g = torch.Generator().manual_seed(seed)
+    nS = (M + rows_per_sample - 1) // rows_per_sample
+    c, s, j = torch.arange(C), torch.arange(nS), torch.arange(4 * C)
+    shift = 8.0 * (1 + (37 * c[None, :] + 101 * s[:, None]) % 255).float()
+    sel, sgn = (37 * j + j // C) % C, torch.where(j % 4 == 3, -1.0, 1.0)
+    w_up = torch.zeros(4 * C, C)
+    w_up[j, sel] = sgn
+    w_dn = torch.zeros(C, 4 * C)
+    w_dn[j % C, j] += (1 + j // C).float()
+    w_dn[(7 * j + 1 + j // C) % C, j] -= (5 + j % 3).float()
+    assert torch.unique(w_dn.T, dim=0).shape[0] == 4 * C and bool((w_dn != 0).any(0).all())
+    assert all(bool((sgn[sel == ch] > 0).any()) for ch in range(C))
+    b_dn = torch.randint(-3, 4, (C,), generator=g).float()
+    x = _sparse_ints(g, M, C, 0.5)
+    gate = probe_gates(nS, C, g) if gated else None
+    dd = lambda t: t.double().to(device)
+    h = sample_rows(dd(shift), M, rows_per_sample)
+    u = torch.relu(h @ dd(w_up).T)
+    upd = u @ dd(w_dn).T + dd(b_dn)
+    gg = sample_rows(dd(gate), M, rows_per_sample) if gated else torch.ones_like(upd)
+    ref = dd(x) + gg * upd
+    assert torch.equal(bf16_round(h), h) and torch.equal(bf16_round(u), u) and float(h.min()) >= 8 and float(h.max()) <= 2040
+    assert float((dd(x).abs() + gg.abs() * (u @ dd(w_dn).abs().T + dd(b_dn).abs())).max()) < 2 ** 22 and torch.equal(ref.float().double(), ref)
+    return dict(x=x, shift=shift, scale=torch.full_like(shift, -1.0), gate=gate, w_up=w_up, b_up=torch.zeros(4 * C), w_dn=w_dn, b_dn=b_dn, ref=ref)

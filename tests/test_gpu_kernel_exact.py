@@ -615,6 +615,8 @@ def test_ln_linear_and_ln_mlp_guard_bands_and_bounds(C, M, N):
     # h is rounded to bf16 before the MFMA: 2^-8 |h| through |W|; fp32 accumulation over C terms; the bf16 output
     tol = (kc.U8 * 1.01) * (h.abs() @ w.double().abs().T) + C * kc.U24 * (h.abs() @ w.double().abs().T + b.double().abs()) + kc.U8 * ref.abs()
     note("ln_linear bf16 out", kc.assert_elementwise(dense, ref, tol, "ln_linear C %d M %d N %d" % (C, M, N)))
+    # beside that bound (its 2^-8 |h| |W| is as large as an output ulp): the interval of the staged reference, which pins most elements to the bit
+    kc.check_ln_linear(dense, kc.ln_linear_reference(x, w.float(), b, ln_w=lw, ln_b=lb), "ln_linear C %d M %d N %d, staged" % (C, M, N))
     # ---- ln_mlp_resid_
     w_up = dev(torch.randn(4 * C, C, generator=g) / C ** 0.5, torch.bfloat16).contiguous(); b_up = dev(torch.randn(4 * C, generator=g) * 0.1)
     w_dn = dev(torch.randn(C, 4 * C, generator=g) / (4 * C) ** 0.5, torch.bfloat16).contiguous(); b_dn = dev(torch.randn(C, generator=g) * 0.1)
@@ -636,6 +638,10 @@ def test_ln_linear_and_ln_mlp_guard_bands_and_bounds(C, M, N):
     a2 = gu.abs() @ w_dn.double().abs().T
     tol = e_g @ w_dn.double().abs().T + 4 * C * kc.U24 * (a2 + b_dn.double().abs()) + 2 * kc.U24 * (xd.abs() + upd.abs())
     note("ln_mlp_resid_ fp32 out", kc.assert_elementwise(x1, xd + upd, tol, "ln_mlp_resid_ C %d M %d" % (C, M)))
+    # beside that bound (2^-8 per bf16 stage: as large as the update itself): the staged reference, hundreds of times tighter
+    sr = kc.fused_mlp_reference(x, w_up.float(), b_up, w_dn.float(), b_dn, ln_w=lw, ln_b=lb)
+    note("ln_mlp_resid_ fp32 out, staged", kc.check_fused_mlp(x1, sr, "ln_mlp_resid_ C %d M %d, staged" % (C, M)))
+    assert float((tol / sr["tol"]).median()) > 50
 
 
 def test_zz_margins():

@@ -440,6 +440,10 @@ def test_fused_ln_mlp_resid(C, M, mode):
                       b_dn.cuda(), x_bf16_out=mirror, **kw)
     got_upd = xd.cpu() - x
     assert rel_mse(got_upd, upd) < 1e-4
+    # beside the rel-MSE: every element inside the staged float64 tolerance (kernel_checks.fused_mlp_reference: bf16 where the kernel rounds)
+    bfw = lambda t: t.to(torch.bfloat16).float().cuda()
+    rkw = {k: v for k, v in kw.items() if k != "mod_sample_stride"}
+    kc.check_fused_mlp(xd, kc.fused_mlp_reference(x.cuda(), bfw(w_up), b_up.cuda(), bfw(w_dn), b_dn.cuda(), **rkw), "ln_mlp_resid_ C %d M %d %s" % (C, M, mode))
     if mirror is not None:                      # the bf16 copy written in the same pass == a cast of the fp32 result, bit for bit
         assert torch.equal(mirror, xd.to(torch.bfloat16))
     # the follow-on LayerNorm + linear of the next block, computed by the same launch on the rows it has just written,
@@ -527,6 +531,9 @@ def test_fused_ln_linear(C, M, N, mode):
     got = ops.ln_linear(x.cuda(), wb, b.cuda(), **kw)
     assert got.dtype == torch.bfloat16 and got.shape == (M, N)
     assert rel_mse(got.float().cpu(), want) < 1e-4
+    # beside the rel-MSE: every element inside the interval of the staged float64 reference (kernel_checks.ln_linear_reference)
+    rkw = {k: v for k, v in kw.items() if k != "mod_sample_stride"}
+    kc.check_ln_linear(got, kc.ln_linear_reference(x.cuda(), wb.float(), b.cuda(), **rkw), "ln_linear C %d M %d N %d %s" % (C, M, N, mode))
     two = ops.gemm_bf16(ops.layernorm_modulate(x.cuda(), **{({"ln_w": "w", "ln_b": "b"}.get(k, k)): v for k, v in kw.items()}), wb, b.cuda())
     assert rel_mse(got.float().cpu(), two.float().cpu()) < 2e-5
 

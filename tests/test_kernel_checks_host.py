@@ -5,6 +5,7 @@ An emulation of the kernels' contract in torch on the CPU — q | k | v = bf16(f
 applies to the HIP kernels, and the same emulation with one planted fault (one key dropped for one query row; heads h and h + 1 swapped in
 k; the S | C slice of one 64-column segment taken from the next segment) must FAIL them: the proof that the derived bound is tight enough to
 tell a right kernel from a nearly right one."""
+import numpy as np
 import pytest
 import torch
 
@@ -408,3 +409,305 @@ def test_a_dropped_neighbour_passes_what_the_rel_mse_test_asks_and_fails_the_int
     assert old_test_passes(c, W, out)
     with pytest.raises(AssertionError, match="outside their interval"):
         kc.check_grouper(out, staged(c, W), "dropped neighbour")
+
+
+# ============================================================================================================= fused LN + MLP / LN + linear
+# An emulation of csrc/fused_mlp.hip's contract: fp32 LayerNorm (+ affine, + per-sample modulation), h to bf16, fp32 accumulation over k in
+# MFMA steps of 32 (two orders), the kernel's fast GELU restated in fp32, u to bf16, the down projection accumulated hidden chunk by hidden
+# chunk of 64 (onto x + b_dn without a gate, gated in the epilogue otherwise), written into a guarded buffer.  MLP_FAULTS are the ways such a
+# kernel goes subtly wrong, each confined to the 16-row tile at TILE0 (the wave of rows 96..127 for `tile1_mod`).
+GELU_C = (1.1510004997253418, 0.45959582924842834, 0.052146632224321365, -0.007198718376457691, 0.00048810214502736926)   # csrc/common.h
+MLP_FAULTS = ("skip_chunk", "stale_weights", "swap_kslots", "bup_neighbour", "neighbour_sample", "tile1_mod")
+TILE0, FCH = 96, 2                                                   # the faulty tile's first row; the faulty hidden chunk
+
+
+def fault_rows(fault, one_row=False):
+    """(first row, rows) a planted fault touches: the tile of rows 96..111 (a sample boundary inside at rows_per_sample = 100 and 7), or tile 1
+    (rows 112..127) of the wave of rows 96..127 for `tile1_mod`; one_row: only row 100 / 112 of it."""
+    if fault == "tile1_mod":
+        return TILE0 + 16, 1 if one_row else 16
+    return (TILE0 + 4, 1) if one_row else (TILE0, 16)
+
+
+def gelu_fast_np(x, fma=True):
+    """gelu_erf_fast / gelu_erf_fast2 of csrc/common.h restated in numpy float32.  fma: every a * b + c rounded once (the scalar form's fmaf, and
+    what the compiler may contract the packed form to); otherwise the product is rounded first."""
+    x = np.asarray(x, dtype=np.float32)
+    f32 = np.float32
+    if fma:
+        mad = lambda a, b, c: (a.astype(np.float64) * np.asarray(b, np.float32).astype(np.float64) + np.asarray(c, np.float32).astype(np.float64)).astype(f32)
+    else:
+        mad = lambda a, b, c: ((a * np.asarray(b, f32)).astype(f32) + np.asarray(c, f32)).astype(f32)
+    z = np.abs(x)
+    p = mad(z, f32(GELU_C[4]), f32(GELU_C[3]))
+    for c in (GELU_C[2], GELU_C[1], GELU_C[0]):
+        p = mad(p, z, f32(c))
+    e = np.exp2(-(p * z).astype(f32)).astype(f32)
+    r = mad(e, f32(-0.5), f32(0.5))
+    return mad(z, r, (x * f32(0.5)).astype(f32)), r
+
+
+def test_fast_gelu_is_exactly_relu_at_zero_and_from_six_upwards():
+    """What the exact probes rest on: 2^(-p z) <= 2^-29 at |v| >= 6, so r == 0.5 and v / 2 + |v| / 2 is exact.  Every integer in [-2048, 2048]
+    outside 0 < |v| < 6, every multiple of 8 the probes can produce, both contraction forms; and the restatement is GELU within the stated
+    8.7e-7 elsewhere."""
+    v = np.arange(-2048, 2049, dtype=np.float32)
+    v = v[(np.abs(v) >= 6) | (v == 0)]
+    for fma in (True, False):
+        out, r = gelu_fast_np(v, fma)
+        assert np.array_equal(out, np.maximum(v, 0)) and np.all((r == 0.5) | (v == 0))
+        out8, _ = gelu_fast_np(8.0 * np.arange(-4096, 4097, dtype=np.float32), fma)
+        assert np.array_equal(out8, np.maximum(8.0 * np.arange(-4096, 4097, dtype=np.float32), 0))
+        w = np.linspace(-12, 12, 200001).astype(np.float32)
+        got = torch.from_numpy(gelu_fast_np(w, fma)[0]).double()
+        assert float((got - torch.nn.functional.gelu(torch.from_numpy(w).double())).abs().max()) <= kc.GELU_FAST_ABS
+    near, _ = gelu_fast_np(np.array([-5.0, 5.0, 3.0], dtype=np.float32))
+    assert not np.array_equal(near, np.array([0.0, 5.0, 3.0], dtype=np.float32))                    # (below 6 it is NOT relu: the sweep shows something)
+
+
+def mm32(a, w, rev):
+    """fp32 accumulation over K in 32-steps (the 16x16x32 MFMA's k), forward or reversed."""
+    steps = list(range(0, a.shape[-1], 32))
+    acc = torch.zeros(a.shape[0], w.shape[0])
+    for k0 in (reversed(steps) if rev else steps):
+        acc = acc + a[:, k0:k0 + 32] @ w[:, k0:k0 + 32].T
+    return acc
+
+
+def emu_ln(x, kw, fault=None, one_row=False):
+    """fp32 LayerNorm + affine + modulation -> bf16-valued float [M, C], and the sample index of every row's gate."""
+    M, C = x.shape
+    mean = x.sum(1, keepdim=True) / C
+    d = x - mean
+    h = d * torch.rsqrt((d * d).sum(1, keepdim=True) / C + torch.tensor(1e-6))
+    if kw.get("ln_w") is not None:
+        h = h * kw["ln_w"] + kw["ln_b"]
+    rps = kw.get("rows_per_sample", 0)
+    idx = torch.arange(M) // rps if rps else torch.zeros(M, dtype=torch.long)
+    gidx = idx.clone()
+    rows = torch.arange(M)
+    r0, n = fault_rows(fault, one_row)
+    hit = (rows >= r0) & (rows < r0 + n)
+    if fault == "neighbour_sample":                                  # the rows of the tile behind a sample boundary take the sample before it
+        idx = torch.where(hit & (idx > idx[r0 - 1]), idx - 1, idx)
+        gidx = idx.clone()
+    if fault == "tile1_mod":                                         # tile 1 of the wave of rows 96..127 keeps tile 0's (shift, scale)
+        idx = torch.where(hit, idx[(rows - 16).clamp_min(0)], idx)
+    if kw.get("shift") is not None:
+        h = h * (1 + kw["scale"][idx]) + kw["shift"][idx]
+    return bf(h), gidx
+
+
+def emulate_mlp(d, kw, rev=False, fault=None, one_row=False):
+    """-> (big, x_out view [M, C]) of kc.guarded.  d: x, w_up, b_up, w_dn, b_dn (float32, weights bf16-valued); kw: ln_w, ln_b, shift, scale,
+    gate, rows_per_sample."""
+    x, w_up, b_up, w_dn, b_dn = d["x"], d["w_up"], d["b_up"], d["w_dn"], d["b_dn"]
+    M, C = x.shape
+    h, gidx = emu_ln(x, kw, fault, one_row)
+    r0, n = fault_rows(fault, one_row)
+    T = slice(r0, r0 + n)
+    gelu = lambda t: torch.from_numpy(gelu_fast_np(t.numpy(), fma=not rev)[0])
+    gated = kw.get("gate") is not None
+    acc = torch.zeros(M, C) if gated else x + b_dn
+    chunks = list(range(4 * C // 64))
+    for ch in (reversed(chunks) if rev else chunks):
+        s = slice(ch * 64, ch * 64 + 64)
+        u = bf(gelu(mm32(h, w_up[s], rev) + b_up[s]))
+        wd = w_dn[:, s]
+        contrib = mm32(u, wd, rev)
+        if ch == FCH and fault in ("skip_chunk", "stale_weights", "swap_kslots", "bup_neighbour"):
+            p = slice((ch - 1) * 64, ch * 64)
+            if fault == "skip_chunk":
+                contrib[T] = 0
+            elif fault == "stale_weights":                           # chunk ch computed with chunk ch - 1's W_up and W_dn (b_up comes from global memory)
+                contrib[T] = mm32(bf(gelu(mm32(h[T], w_up[p], rev) + b_up[s])), w_dn[:, p], rev)
+            elif fault == "swap_kslots":                             # k-slots 2 and 5 of the chunk's U exchanged
+                u2 = u[T].clone()
+                u2[:, 16:24], u2[:, 40:48] = u[T][:, 40:48], u[T][:, 16:24]
+                contrib[T] = mm32(u2, wd, rev)
+            else:
+                n = slice((ch + 1) * 64, (ch + 2) * 64)
+                contrib[T] = mm32(bf(gelu(mm32(h[T], w_up[s], rev) + b_up[n])), wd, rev)
+        acc = acc + contrib
+    out = x + kw["gate"][gidx] * (acc + b_dn) if gated else acc
+    big, view = kc.guarded(M, C, 0.0, "cpu")
+    view.copy_(out)
+    if fault == "tail_store":                                        # the first clamped tail row is stored behind row M - 1
+        big[4096 + M * C:4096 + (M + 1) * C] = out[M - 1]
+    return big, view
+
+
+def emulate_ln_linear(x, w, bias, kw, rev=False, fault=None):
+    h, _ = emu_ln(x, kw, fault)
+    out = bf(mm32(h, w, rev) + (0 if bias is None else bias))
+    if fault == "swap_out_chunks":                                   # two 16-byte pieces of the staged output rows exchanged in one tile
+        o2 = out.clone()
+        o2[TILE0:TILE0 + 16, 8:16], o2[TILE0:TILE0 + 16, 40:48] = out[TILE0:TILE0 + 16, 40:48], out[TILE0:TILE0 + 16, 8:16]
+        out = o2
+    return out
+
+
+FORMS = {"plain": (), "affine": ("ln",), "modgate": ("mod", "gate"), "mod": ("mod",), "affmod": ("ln", "mod", "gate"), "affgate": ("ln", "gate")}
+
+
+def form_kw(d, form, rps):
+    """The LayerNorm / gate arguments of one form from mlp_randn_case's tensors."""
+    C = d["x"].shape[1]
+    kw = {}
+    if "ln" in FORMS[form]:
+        kw.update(ln_w=d["ln_w"], ln_b=d["ln_b"])
+    if "mod" in FORMS[form]:
+        kw.update(shift=d["mod"][:, :C], scale=d["mod"][:, C:2 * C])
+    if "gate" in FORMS[form]:
+        kw.update(gate=d["mod"][:, 2 * C:])
+    if "mod" in FORMS[form] or "gate" in FORMS[form]:
+        kw.update(rows_per_sample=rps)
+    return kw
+
+
+def ln_kw(kw):
+    return {k: v for k, v in kw.items() if k != "gate"}
+
+
+MLP_HOST = [(128, 300, "modgate", 100), (64, 129, "modgate", 7), (128, 200, "affine", 0), (64, 1000, "mod", 1000), (128, 333, "affmod", 33), (64, 200, "plain", 0)]
+
+
+def host_case(C, M, form, rps, N=0):
+    d = kc.mlp_randn_case(M, C, C + M + rps, n_samples=(M + rps - 1) // rps if rps else 1, N=N, tame=form == "affmod" or M < 16)
+    return d, form_kw(d, form, rps)
+
+
+def weights(d):
+    return d["w_up"], d["b_up"], d["w_dn"], d["b_dn"]
+
+
+@pytest.mark.parametrize("C,M,form,rps", MLP_HOST)
+def test_mlp_emulation_passes_the_staged_tolerance_and_the_interval_in_both_orders(C, M, form, rps):
+    d, kw = host_case(C, M, form, rps, N=128)
+    sr = kc.fused_mlp_reference(d["x"], *weights(d), **kw)
+    lr = kc.ln_linear_reference(d["x"], d["wn"], d["bn"], **ln_kw(kw))
+    print("C %d M %d %-8s rps %4d: tol / update %.4f, ambiguous h %.3f u %.3f; ln_linear pinned %.3f wide %.3f" % (
+        C, M, form, rps, sr["ratio"], sr["amb_h"], sr["amb_u"], lr["pinned"], lr["wide"]))
+    for rev in (False, True):
+        big, out = emulate_mlp(d, kw, rev=rev)
+        worst = kc.check_fused_mlp(out, sr, "emulation rev %d" % rev)
+        kc.assert_guard_intact(big, out.numel(), "emulation")
+        mism = kc.check_ln_linear(emulate_ln_linear(d["x"], d["wn"], d["bn"], ln_kw(kw), rev=rev), lr, "ln_linear emulation rev %d" % rev)
+        print("    rev %d: worst err / tol %.3f, ln_linear != point reference %.4f" % (rev, worst, mism))
+        assert 0.0 < worst <= 1.0 and mism < 0.2
+    # the staged tolerance against the worst-case bound it replaces
+    old = old_mlp_bound(d, kw)[1]
+    assert float((old / sr["tol"]).median()) > 50
+
+
+def old_mlp_bound(d, kw):
+    """test_ln_linear_and_ln_mlp_guard_bands_and_bounds's reference and worst-case tolerance (2^-8 per bf16 stage through |W_up|, GELU and |W_dn|),
+    extended by the gate.  -> (ref, tol, gate * update)."""
+    x = d["x"].double()
+    C = x.shape[1]
+    w_up, b_up, w_dn, b_dn = [t.double() for t in weights(d)]
+    h = kc.ln_stage(d["x"], **ln_kw(kw))[0]
+    a1 = h.abs() @ w_up.abs().T
+    e_u = (kc.U8 * 1.01) * a1 + C * kc.U24 * (a1 + b_up.abs())
+    gu = torch.nn.functional.gelu(h @ w_up.T + b_up)
+    e_g = e_u * kc.GELU_SLOPE + kc.GELU_FAST_ABS + kc.U8 * 1.01 * gu.abs()
+    upd = gu @ w_dn.T + b_dn
+    g = kc.sample_rows(kw["gate"], x.shape[0], kw["rows_per_sample"]) if kw.get("gate") is not None else torch.ones_like(upd)
+    tol = g.abs() * (e_g @ w_dn.abs().T + 4 * C * kc.U24 * (gu.abs() @ w_dn.abs().T + b_dn.abs())) + 2 * kc.U24 * (x.abs() + (g * upd).abs())
+    return x + g * upd, tol, g * upd
+
+
+def old_instruments_pass(d, kw, out):
+    """-> (the rel-MSE 1e-4 bar of test_fused_ln_mlp_resid passes, the worst-case bound passes)."""
+    ref, tol, gu = old_mlp_bound(d, kw)
+    upd = out.double() - d["x"].double()
+    return float(((upd - gu) ** 2).sum() / (gu ** 2).sum()) < 1e-4, bool(((out.double() - ref).abs() <= tol).all())
+
+
+def probe_kw(p, rps):
+    kw = dict(shift=p["shift"], scale=p["scale"], rows_per_sample=rps)
+    if p["gate"] is not None:
+        kw["gate"] = p["gate"]
+    return kw
+
+
+@pytest.mark.parametrize("C,M,rps", [(128, 300, 100), (64, 129, 7), (128, 130, 1), (64, 5, 16)])
+def test_mlp_emulation_passes_the_exact_probes(C, M, rps):
+    for gated in (False, True):
+        for probe in (kc.mlp_integer_probe, kc.mlp_selection_probe):
+            p = probe(M, C, rps, 3, gated)
+            x = torch.randn(M, C, generator=torch.Generator().manual_seed(1)) * 50 + p["x"]
+            h, _ = emu_ln(x, probe_kw(p, rps))                       # scale = -1 switches the LayerNorm off: h == the shift rows for ANY finite x
+            assert torch.equal(h.double(), kc.sample_rows(p["shift"], M, rps))
+            hb, _ = emu_ln(x, dict(ln_w=torch.zeros(C), ln_b=p["shift"][0]))
+            assert torch.equal(hb, p["shift"][0].expand(M, C))       # and so does ln_w = 0: h == ln_b in every row
+            for rev in (False, True):
+                assert torch.equal(emulate_mlp(p, probe_kw(p, rps), rev=rev)[1].double(), p["ref"])
+    # ln_linear: the GEMM probes with x_probe as per-row shift rows
+    xs, ws, rs = kc.selection_probe(M, 128, C)
+    xi, wi, bi, ri = kc.integer_probe(M, 128, C, 2)
+    for xp, w, b, ref in ((xs, ws, None, rs.double()), (xi, wi, bi, ri)):
+        kw = dict(shift=xp, scale=torch.full_like(xp, -1.0), rows_per_sample=1)
+        assert torch.equal(kc.bf16_round(ref), ref)
+        for rev in (False, True):
+            assert torch.equal(emulate_ln_linear(torch.randn(M, C) * 30, w, b, kw, rev=rev).double(), ref)
+
+
+def test_planted_mlp_faults_fail_the_new_checks_and_what_the_old_instruments_say():
+    """Every fault fails the staged tolerance on randn data and the probes named for it; the table printed at the end says which of them the
+    rel-MSE 1e-4 bar and the worst-case bound of test_gpu_kernel_exact.py let through (DESIGN.md section 3 quotes it)."""
+    table = []
+    for C, M, form, rps, one_row in [c + (False,) for c in MLP_HOST[:2]] + [(128, 4096, "modgate", 100, True)]:
+        d, kw = host_case(C, M, form, rps)
+        sr = kc.fused_mlp_reference(d["x"], *weights(d), **kw)
+        clean = emulate_mlp(d, kw)[1]
+        kc.check_fused_mlp(clean, sr, "no fault")
+        assert old_instruments_pass(d, kw, clean) == (True, True)
+        probes = {gated: (kc.mlp_integer_probe(M, C, rps, 3, gated), kc.mlp_selection_probe(M, C, rps, 3, gated)) for gated in (False, True)}
+        for fault in MLP_FAULTS:
+            out = emulate_mlp(d, kw, fault=fault, one_row=one_row)[1]
+            rows = torch.nonzero((out != clean).any(1)).flatten()
+            assert rows.numel() and int(rows[0]) >= TILE0 and int(rows[-1]) < TILE0 + 32
+            with pytest.raises(AssertionError, match="outside the bound"):
+                kc.check_fused_mlp(out, sr, fault)
+            caught = {(gated, i): not torch.equal(emulate_mlp(p, probe_kw(p, rps), fault=fault, one_row=one_row)[1].double(), p["ref"])
+                      for gated, ps in probes.items() for i, p in enumerate(ps)}
+            if fault != "swap_kslots":
+                assert caught[(False, 0)] and caught[(True, 0)], fault + ": the integer probe does not see it"
+            if fault != "bup_neighbour":                             # (the selection probe has b_up = 0)
+                assert caught[(False, 1)] and caught[(True, 1)], fault + ": the selection probe does not see it"
+            rel_ok, bound_ok = old_instruments_pass(d, kw, out)
+            shift = float((out - clean).abs().max())
+            table.append((C, M, rps, "%s, %s" % (fault, "one row" if one_row else "16 rows"), shift, rel_ok, bound_ok, all(caught[(g, 0)] for g in (False, True)), all(caught[(g, 1)] for g in (False, True))))
+        big, out = emulate_mlp(d, kw, fault="tail_store")
+        with pytest.raises(AssertionError, match="written outside"):
+            kc.assert_guard_intact(big, out.numel(), "tail_store")
+        table.append((C, M, rps, "tail_store, one row", 0.0, True, True, False, False))
+    print("\nfault                                          largest change   rel-MSE 1e-4   worst-case bound   staged tol   integer probe   selection probe")
+    for C, M, rps, fault, shift, rel_ok, bound_ok, ci, cs in table:
+        new = "guard band" if fault.startswith("tail_store") else "FAILS"
+        print("C %3d M %4d rps %3d %-27s %8.3f   %-12s   %-16s   %-10s   %-13s   %s" % (
+            C, M, rps, fault, shift, "passes" if rel_ok else "FAILS", "passes" if bound_ok else "FAILS", new, "FAILS" if ci else "passes", "FAILS" if cs else "passes"))
+
+
+def test_planted_ln_linear_fault_fails_the_interval_and_the_probes():
+    C, M, form, rps = MLP_HOST[0]
+    d, kw = host_case(C, M, form, rps, N=128)
+    lr = kc.ln_linear_reference(d["x"], d["wn"], d["bn"], **ln_kw(kw))
+    kc.check_ln_linear(emulate_ln_linear(d["x"], d["wn"], d["bn"], ln_kw(kw)), lr, "no fault")
+    for fault in ("swap_out_chunks", "neighbour_sample", "tile1_mod"):
+        out = emulate_ln_linear(d["x"], d["wn"], d["bn"], ln_kw(kw), fault=fault)
+        with pytest.raises(AssertionError, match="outside their interval"):
+            kc.check_ln_linear(out, lr, fault)
+        h = kc.ln_stage(d["x"], **ln_kw(kw))[0]
+        ref = h @ d["wn"].double().T + d["bn"].double()             # the old instruments of test_fused_ln_linear / ..._guard_bands_and_bounds
+        a = h.abs() @ d["wn"].double().abs().T
+        tol = (kc.U8 * 1.01) * a + C * kc.U24 * (a + d["bn"].double().abs()) + kc.U8 * ref.abs()
+        print("ln_linear %-17s rel-MSE 1e-4 %s, worst-case bound %s, interval FAILS" % (
+            fault, "passes" if float(((out.double() - ref) ** 2).sum() / (ref ** 2).sum()) < 1e-4 else "FAILS",
+            "passes" if bool(((out.double() - ref).abs() <= tol).all()) else "FAILS"))
+    xp, w, ref = kc.selection_probe(M, 128, C)
+    kwp = dict(shift=xp, scale=torch.full_like(xp, -1.0), rows_per_sample=1)
+    assert torch.equal(emulate_ln_linear(d["x"], w, None, kwp), ref)
+    assert not torch.equal(emulate_ln_linear(d["x"], w, None, kwp, fault="swap_out_chunks"), ref)
+    assert not torch.equal(emulate_ln_linear(d["x"], w, None, kwp, fault="tile1_mod"), ref)
