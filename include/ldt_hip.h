@@ -207,6 +207,34 @@ int ldt_vpsde_score(const float* params, const float* t, float beta0, float beta
 int ldt_sde_score(const float* params, const float* t, int32_t kind, float c0, float c1, float c2, float* out, int32_t B,
                   int64_t per_sample, void* stream);
 int ldt_add_f32(const float* a, const float* b, float* out, int64_t n, void* stream);
+
+/* ---- probability-flow ODE sampling: the device half of RK45 (diffusion/diffusion_continuous.py:88-131) -------
+ * `sample_mode: continuous` integrates dx/dt = f(t) x - g2(t)/2 score with scipy's Dormand-Prince 5(4) pair (torchdiffeq's
+ * scipy_solver / RK45).  These three streaming kernels are what scipy's rk_step, RK45._step_impl / _estimate_error_norm and
+ * select_initial_step (scipy/integrate/_ivp/rk.py, common.py) do between two Score evaluations, on the flattened state as scipy
+ * holds it: y and the stage derivatives K[0..6] are float64 [n].  The step controller stays on the host (ldt_amd/ode.py) and reads
+ * one double back per step attempt.  fp64 / fp32 arithmetic exactly as written (no FMA contraction), fixed reduction order, no
+ * atomics.  n must be a positive multiple of 2 (two fp64 per 16-byte access); fp64 buffers 16-byte, fp32 buffers 8-byte aligned.
+ * ldt_ode_stage: y_out = y + h * (((a0 k0 + a1 k1) + a2 k2) + ...), nterms = 1..6 terms left to right (k_s beyond nterms are not
+ *   read and may be NULL), and x_out = (float)y_out, the Score's input: stages 1-5 (rows of the tableau A), y_new (the row B) and
+ *   the Euler probe of select_initial_step (a0 = 1).  y_out must not alias an input.
+ * ldt_ode_rhs: k_out = (double)(-(f x - (0.5 g2) score)), score = -p / sd (is_score = 0: p holds the Score's params, the two
+ *   steps of Trainer.score_fn and of fun() in DiffusionBase.sample_model_ode, in fp32 in their operation order) or score = p
+ *   (is_score = 1: an opaque score_fn's own score).  f, g2 and sd = sqrt(var(t)) are batch-uniform fp32 scalars the host forms
+ *   with the SDE object's f / g2 / var at the evaluation time t = -s (the ODE runs in reversed time s, hence the leading minus).
+ * ldt_ode_scaled_sumsq: *out = sum_i ((sum_j c_j v_j[i]) / (atol + rtol max(|ya[i]|, |yb[i]|)))^2 over nvec = 1..7 vectors: the
+ *   square of scipy's norm(error / scale) (c_j = E_j over K[0..6], ya = y, yb = y_new; the host applies |h|) and of the three norms of
+ *   select_initial_step (y0; f0; f1 - f0 with ya = yb = y0).  Two stages: per-workgroup partials into scratch[scratch_len]
+ *   (LDT_ODE_SUMSQ_SCRATCH doubles always suffice; fewer cap the grid), then one workgroup.  Repeats bit for bit. */
+#define LDT_ODE_SUMSQ_SCRATCH 1024
+int ldt_ode_stage(const double* y, const double* k0, const double* k1, const double* k2, const double* k3, const double* k4,
+                  const double* k5, double a0, double a1, double a2, double a3, double a4, double a5, int32_t nterms, double h,
+                  double* y_out, float* x_out, int64_t n, void* stream);
+int ldt_ode_rhs(const float* x, const float* p, int32_t is_score, float f, float g2, float sd, double* k_out, int64_t n, void* stream);
+int ldt_ode_scaled_sumsq(const double* v0, const double* v1, const double* v2, const double* v3, const double* v4, const double* v5,
+                         const double* v6, double c0, double c1, double c2, double c3, double c4, double c5, double c6, int32_t nvec,
+                         const double* ya, const double* yb, double atol, double rtol, double* scratch, int32_t scratch_len,
+                         double* out, int64_t n, void* stream);
 /* ldt_block_activation: x = act(x) in place on bf16 rows [M][C] (row stride ld, elements) — the block activation of the reference's
  *   no-condition ResidualBlock branches (`decoder_act`: model/layers.py:224-226, `self.act` from tools/utils.py:104-124), applied to the
  *   LayerNorm output that fc_q / the MLP read.  rrelu in its eval-mode form. */

@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDT_HIP_LIB", os.path.join(_HERE, "libldt_hip.so"))   # override: debug builds only
 ABI_VERSION = 25
 MAX_BLOCKS = 64
+ODE_SUMSQ_SCRATCH = 1024        # LDT_ODE_SUMSQ_SCRATCH
 
 EPI_F32, EPI_BF16, EPI_GELU_BF16, EPI_RELU_BF16, EPI_RESID_F32 = range(5)
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_GELU = range(4)
@@ -78,6 +79,9 @@ SIGNATURES = {
     "ldt_vpsde_score": [_vp, _vp, C.c_float, C.c_float, C.c_float, _vp, _i32, _i64, _vp],
     "ldt_sde_score": [_vp, _vp, _i32, C.c_float, C.c_float, C.c_float, _vp, _i32, _i64, _vp],
     "ldt_add_f32": [_vp, _vp, _vp, _i64, _vp],
+    "ldt_ode_stage": [_vp] * 7 + [C.c_double] * 6 + [_i32, C.c_double, _vp, _vp, _i64, _vp],
+    "ldt_ode_rhs": [_vp, _vp, _i32, C.c_float, C.c_float, C.c_float, _vp, _i64, _vp],
+    "ldt_ode_scaled_sumsq": [_vp] * 7 + [C.c_double] * 7 + [_i32, _vp, _vp, C.c_double, C.c_double, _vp, _i32, _vp, _i64, _vp],
     "ldt_block_activation": [_vp, _i64, _i64, _i32, _i32, _vp],
     "ldt_group_stats": [_vp, _i64, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp],
     "ldt_norm_apply": [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp],

@@ -43,7 +43,7 @@ _AIRPLANE = {
     "sde": {"beta_start": 0.1, "beta_end": 20, "sde_type": "vpsde", "sigma2_0": 0, "time_eps": 0.01,
             "ode_tol": 1e-5, "sample_time_eps": 1e-6, "sample_mode": "discrete", "predictor": "ancestral",
             "corrector": None, "train_N": 1000, "sample_N": 1000, "snr": 0.01, "corrector_steps": 1,
-            "denoise": True, "probability_flow": False, "alpha": 1.0},
+            "denoise": True, "probability_flow": False, "alpha": 1.0, "ode_solver": "scipy"},
 }
 
 

@@ -127,7 +127,7 @@ class DiffusionBase:
     # ---- probability-flow ODE sampling (sample_mode: continuous) -----------------------------------------
     @torch.no_grad()
     def sample_model_ode(self, score_fn, num_samples, shape, ode_eps, ode_solver_tol, enable_autocast=False, noise=None,
-                         condition=None, label=None, *, device="cuda"):
+                         condition=None, label=None, *, device="cuda", solver="scipy", shared_t=None):
         """diffusion_continuous.py:88-131: dx/dt = f(t) x - g2(t)/2 * score, from t = 1 to `ode_eps`, solved the way the
         reference's `torchdiffeq.odeint(method="scipy_solver", options={"solver": "RK45"})` does it: scipy's RK45 on the
         host over the flattened float64 state, time reversed to increasing s = -t, rtol = atol = `ode_solver_tol`; every
@@ -136,12 +136,21 @@ class DiffusionBase:
         draws on the CUDA generator, :107 — not reproducible across devices either way).
         NB the bf16 Score limits the smoothness the step controller sees to ~1e-3 relative: tolerances much below that
         (the shipped `ode_tol: 1e-5`) are met only by many small steps.  torchdiffeq is not vendored upstream: its wrapper's
-        behaviour is restated from its published semantics — parity unpinned."""
+        behaviour is restated from its published semantics — parity unpinned.
+
+        solver (keyword-only, not in the reference): "scipy" (default) is the host path above; "device" keeps the float64 state and
+        the seven stage derivatives on the GPU and runs the same Dormand-Prince steps there (`_sample_model_ode_device`; ldt_amd/ode.py,
+        csrc/ode_rk45.hip), reading one double back per step attempt.  `shared_t` applies to the device solver only."""
         import time
-        from scipy.integrate import solve_ivp
+        if solver not in ("scipy", "device"):
+            raise ValueError("sample_model_ode: solver=%r (\"scipy\" or \"device\")" % (solver,))
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("sample_model_ode: device %s — the HIP path has no CPU fallback" % (device,))
+        if solver == "device":
+            return self._sample_model_ode_device(score_fn, num_samples, shape, ode_eps, ode_solver_tol, noise, condition, label, dev,
+                                                 shared_t)
+        from scipy.integrate import solve_ivp
         x0 = torch.randn((num_samples,) + tuple(shape)) if noise is None else noise
         full = tuple(x0.shape)
         nfe = [0]
@@ -159,6 +168,60 @@ class DiffusionBase:
                         t_eval=[-1.0, -float(ode_eps)], method="RK45", rtol=ode_solver_tol, atol=ode_solver_tol)
         out = torch.from_numpy(sol.y[:, -1]).to(dev, torch.float32).reshape(full)
         return out, nfe[0], time.time() - t0
+
+    def _sample_model_ode_device(self, score_fn, num_samples, shape, ode_eps, ode_solver_tol, noise, condition, label, dev, shared_t):
+        """`sample_model_ode(solver="device")`: the same ODE, tolerances, reversed time and `noise` handling as the scipy path, with
+        RK45's arithmetic on the device.  The host keeps the step controller (ldt_amd/ode.py: float64 Python scalars, scipy's rules);
+        per evaluation it forms the batch-uniform fp32 scalars f(t), g2(t), sqrt(var(t)) with this SDE object's own methods — so every
+        family works — and launches: ldt_ode_stage (stage state in float64 + its fp32 cast), one Score forward, ldt_ode_rhs (the
+        stage derivative in the operation order of `Trainer.score_fn` + `fun()` above, widened to float64).  The error norm comes
+        back as one double per step attempt (ldt_ode_scaled_sumsq); nothing else crosses the bus.
+
+        Score evaluation: every sample sits at the same t, so when `score_fn` is the bound `Trainer.score_fn` of an `ldt_amd.Score`
+        and there is no label and no condition, `Score.forward_shared_t` is used (ONE AdaLN row per evaluation, LN folding where
+        `can_fold` says so; the fold monitor's contract is untouched).  Otherwise the opaque route calls the model with a (B,) time
+        vector as the scipy path does: the params of a stock `Trainer.score_fn` (`_params_fn`), or — for any other callable — the
+        score it returns, taken as is.  `shared_t` True / False forces a route (True raises where the shared route does not exist).
+
+        Under a sharded batch each rank integrates its own rows with its own step sequence, exactly as on the scipy path: the error
+        norm is over the local rows, there is no collective here, and results are therefore not world-size invariant.
+        `self.last_ode` keeps {"accepted", "rejected", "t", "route"} of the last call."""
+        import time
+        from . import ode
+        x0 = torch.randn((num_samples,) + tuple(shape)) if noise is None else noise
+        full = tuple(x0.shape)
+        B = full[0]
+        model = _fused_model(score_fn)
+        can_share = model is not None and label is None and condition is None
+        if shared_t is None:
+            shared_t = can_share
+        elif shared_t and not can_share:
+            raise ValueError("sample_model_ode: shared_t=True needs the bound Trainer.score_fn of an ldt_amd.Score and no label / condition")
+        stock = _is_stock_score_fn(score_fn) and getattr(getattr(score_fn, "__self__", None), "model", None) is not None
+        params_of = _params_fn(score_fn) if stock and not shared_t else None
+        backend = ode.HipBackend(dev)
+
+        def fun(s, x, k_out):
+            th = torch.tensor(-float(s), dtype=torch.float32)                         # the fp32 time every sample shares
+            f, g2, sd = float(self.f(th)), float(self.g2(th)), float(torch.sqrt(self.var(th)))
+            xb = x.view(full)
+            if shared_t:
+                p, is_score = model.forward_shared_t(xb, float(th)), False
+            else:
+                t = torch.full((B,), float(th), dtype=torch.float32, device=dev)
+                if params_of is not None:
+                    p, is_score = params_of(t, xb, label=label, condition=condition), False
+                else:
+                    p, is_score = score_fn(t, xb, label=label, condition=condition)[0], True
+            backend.rhs(x, p.to(torch.float32), f, g2, sd, k_out, is_score=is_score)
+
+        t0 = time.time()
+        y0 = x0.reshape(-1).double().to(dev).contiguous()
+        y, nfe, accepted, rejected, trace = ode.rk45_solve(backend, fun, y0, y0.float(), -1.0, -float(ode_eps), ode_solver_tol, ode_solver_tol)
+        out = y.to(torch.float32).reshape(full)
+        torch.cuda.synchronize(dev)
+        self.last_ode = {"accepted": accepted, "rejected": rejected, "t": trace, "route": "shared_t" if shared_t else "opaque"}
+        return out, nfe, time.time() - t0
 
     # ---- the sampler --------------------------------------------------------------------------------
     @torch.no_grad()

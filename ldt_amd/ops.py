@@ -228,6 +228,71 @@ def sde_score(params, t, kind, c0, c1, c2):
     return out
 
 
+def _ode_vec(t, dtype, name, n=None):
+    _need(t, dtype, name)
+    if t.dim() != 1 or not t.is_contiguous() or (n is not None and t.numel() != n):
+        raise ValueError("%s must be a contiguous 1-d tensor%s, got %s" % (name, "" if n is None else " of %d elements" % n, tuple(t.shape)))
+
+
+def ode_stage(y, ks, coefs, h, y_out=None, x_out=None):
+    """y_out = y + h * (((a0 k0 + a1 k1) + a2 k2) + ...) in float64, left to right over the 1..6 (`ks`, `coefs`) terms, and
+    x_out = float32(y_out), the Score's input (ldt_ode_stage).  y, ks[i], y_out float64 [n], x_out float32 [n].  -> (y_out, x_out)."""
+    n = y.numel()
+    if not 1 <= len(ks) <= 6 or len(ks) != len(coefs):
+        raise ValueError("ode_stage: 1..6 terms with one coefficient each, got %d / %d" % (len(ks), len(coefs)))
+    _ode_vec(y, torch.float64, "y")
+    for i, k in enumerate(ks):
+        _ode_vec(k, torch.float64, "ks[%d]" % i, n)
+    if y_out is None:
+        y_out = torch.empty_like(y)
+    if x_out is None:
+        x_out = torch.empty(n, dtype=torch.float32, device=y.device)
+    _ode_vec(y_out, torch.float64, "y_out", n); _ode_vec(x_out, torch.float32, "x_out", n)
+    kp = [_p(k) for k in ks] + [0] * (6 - len(ks))
+    a = [float(c) for c in coefs] + [0.0] * (6 - len(ks))
+    check(lib().ldt_ode_stage(_p(y), *kp, *a, len(ks), float(h), _p(y_out), _p(x_out), n, stream_ptr()), "ldt_ode_stage")
+    return y_out, x_out
+
+
+def ode_rhs(x, p, f, g2, sd, k_out=None, is_score=False):
+    """k_out = float64(-(f x - (0.5 g2) score)), score = -p / sd (p = the Score's params) or p itself (is_score): the reversed-time
+    right-hand side of the probability-flow ODE in fp32, in the operation order of Trainer.score_fn + sample_model_ode's fun()
+    (ldt_ode_rhs).  x, p float32 of n elements each, f / g2 / sd python floats holding fp32 values.  -> k_out float64 [n]."""
+    _need(x, torch.float32, "x"); _need(p, torch.float32, "p")
+    x, p = x.contiguous(), p.contiguous()
+    n = x.numel()
+    if p.numel() != n:
+        raise ValueError("ode_rhs: x has %d elements, p %d" % (n, p.numel()))
+    if k_out is None:
+        k_out = torch.empty(n, dtype=torch.float64, device=x.device)
+    _ode_vec(k_out, torch.float64, "k_out", n)
+    check(lib().ldt_ode_rhs(_p(x), _p(p), int(bool(is_score)), float(f), float(g2), float(sd), _p(k_out), n, stream_ptr()), "ldt_ode_rhs")
+    return k_out
+
+
+def ode_scaled_sumsq(vs, coefs, ya, yb, atol, rtol, scratch=None, out=None):
+    """out[0] = sum_i ((sum_j c_j v_j[i]) / (atol + rtol max(|ya[i]|, |yb[i]|)))^2 over 1..7 float64 vectors, reduced in a fixed
+    order (ldt_ode_scaled_sumsq): the square of scipy's norm(error / scale).  scratch: float64 [>= 1] per-workgroup partials
+    (_lib.ODE_SUMSQ_SCRATCH always suffice).  -> out, a float64 device tensor of one element (not synchronised)."""
+    if not 1 <= len(vs) <= 7 or len(vs) != len(coefs):
+        raise ValueError("ode_scaled_sumsq: 1..7 vectors with one coefficient each, got %d / %d" % (len(vs), len(coefs)))
+    _ode_vec(ya, torch.float64, "ya")
+    n = ya.numel()
+    _ode_vec(yb, torch.float64, "yb", n)
+    for i, v in enumerate(vs):
+        _ode_vec(v, torch.float64, "vs[%d]" % i, n)
+    if scratch is None:
+        scratch = torch.empty(_lib.ODE_SUMSQ_SCRATCH, dtype=torch.float64, device=ya.device)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=ya.device)
+    _ode_vec(scratch, torch.float64, "scratch"); _ode_vec(out, torch.float64, "out", 1)
+    vp = [_p(v) for v in vs] + [0] * (7 - len(vs))
+    c = [float(x) for x in coefs] + [0.0] * (7 - len(vs))
+    check(lib().ldt_ode_scaled_sumsq(*vp, *c, len(vs), _p(ya), _p(yb), float(atol), float(rtol), _p(scratch), scratch.numel(), _p(out), n,
+                                     stream_ptr()), "ldt_ode_scaled_sumsq")
+    return out
+
+
 def add_f32(a, b, out=None):
     """a + b, fp32, same shape."""
     _need(a, torch.float32, "a"); _need(b, torch.float32, "b")

@@ -10,6 +10,7 @@ Multi-GPU: when torch.distributed is initialised, `sample(B)` runs rows [lo,hi) 
 all-gathers the finished points/latents once (ldt_amd/dist.py); results do not depend on the world size when
 every rank seeds the CPU generator identically (the reference's common_init, tools/utils.py:269-276).
 """
+import os
 import time
 
 import torch
@@ -119,7 +120,8 @@ class Trainer:
             if self.sample_mode == "continuous":             # probability-flow ODE (Latent_SDE_Trainer.py:148-152)
                 eps, self.nfe_count, _ = self.SDE.sample_model_ode(
                     score_fn=self.score_fn, num_samples=per, shape=(cs.z_scale, cs.z_dim), label=label, ode_eps=self.sample_time_eps,
-                    enable_autocast=False, ode_solver_tol=self.cfg.sde.ode_tol, condition=condition, noise=x0_loc, device=self.device)
+                    enable_autocast=False, ode_solver_tol=self.cfg.sde.ode_tol, condition=condition, noise=x0_loc, device=self.device,
+                    solver=getattr(self.cfg.sde, "ode_solver", None) or os.environ.get("LDT_ODE_SOLVER", "scipy"))
             else:
                 eps = self.SDE.sample_discrete(score_fn=self.score_fn, N=self.cfg.sde.sample_N,
                                                corrector=self.cfg.sde.corrector, predictor=self.cfg.sde.predictor,
