@@ -335,6 +335,22 @@ int ldt_diffuse_q(const float* x0, const float* eta_in, const float* m, const fl
 int ldt_dsm_loss(const float* eta, const float* params, const float* weight, int64_t B, int64_t per_sample, int32_t l1,
                  float* sample_loss, float* mean_loss, void* stream);
 
+/* ---- hybrid-trainer evaluation: the latent NELBO's sums and the JSD metric's occupancy histograms (nelbo_terms.hip, occupancy_grid.hip) ----
+ * Like the block above: status codes before any launch, fixed-order or integer reductions, no floating-point atomics, bit-reproducible.
+ * ldt_nelbo_terms: the two sums of the KL term of trainer/Hybrid_Trainer.py:139-143 in one pass over eta, params, logqz (DEVICE fp32
+ *   [B][per_sample]) and weight (DEVICE fp32 [B]; NULL = 1): sample_sums[b] = {sum_i (eta - params)^2 * weight[b], sum_i logqz} (fp32 [B][2],
+ *   required: the first stage's output), batch_sums (nullable) = the two sums over the batch (fp32 [2]).  Each term is formed in fp32 with
+ *   the reference's three roundings, the partial sums are carried in float64 and rounded once.  16-byte accesses when per_sample % 4 == 0
+ *   and the buffers are 16-byte aligned, the scalar form otherwise.  kl = (batch_sums[0] + batch_sums[1]) / (B per_sample) + c.
+ * ldt_occupancy_grid: evaluation/evaluation_metrics.py:376-389.  pts fp32 [S][n][3], cells fp32 [G][3], G <= 32768.  For every point the
+ *   nearest cell under the float64 squared distance (dx^2 + dy^2) + dz^2 of the fp32 coordinates (products and sums rounded, no FMA: what
+ *   sklearn's tree evaluates), the lowest index winning a tie: counters[g] += 1 per point, bernoulli[g] += 1 once per cloud with a point in
+ *   g.  Both uint32 [G] are ADDED to (zero them for one set's histogram).  Integer adds: exact, the same bits every run. */
+int ldt_nelbo_terms(const float* eta, const float* params, const float* logqz, const float* weight, int64_t B, int64_t per_sample,
+                    float* sample_sums, float* batch_sums, void* stream);
+int ldt_occupancy_grid(const float* pts, int32_t S, int32_t n, const float* cells, int32_t G, uint32_t* counters, uint32_t* bernoulli,
+                       void* stream);
+
 /* ---- fused MLP half of a narrow ResidualBlock (the Compressor's d = 128 blocks; model/layers.py:219,226 + :110-133) ----
  * In place on x fp32 [M][ldx]:  x += gate * (W_dn . GELU(W_up . h + b_up) + b_dn),  h = LN(x) * ln_w + ln_b  (affine,
  * no-condition blocks) or LN(x) * (1 + scale) + shift (AdaLN; shift/scale/gate are per-sample vectors, sample =

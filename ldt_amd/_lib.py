@@ -100,6 +100,8 @@ SIGNATURES = {
     "ldt_reparam_kl": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, C.c_float, C.c_float, _vp],
     "ldt_diffuse_q": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _u64, _i32, _vp],
     "ldt_dsm_loss": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp],
+    "ldt_nelbo_terms": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
+    "ldt_occupancy_grid": [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp],
     "ldt_grouper_mlp": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "ldt_ln_mlp_resid": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "ldt_ln_mlp_resid_next": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64,

@@ -27,6 +27,9 @@ from . import ops
 from ._lib import check, lib
 
 PREDICTORS = ("reversediffusion", "ancestral", "eulermaruyama", "ddim")
+# iw_sample_mode names of DiffusionBase.iw_quantities (diffusion_continuous.py:362-417); the second tuple draws t uniformly
+IW_MODES = ("ll_uniform", "ll_iw", "drop_all_uniform", "drop_all_iw", "drop_sigma2t_iw", "drop_sigma2t_uniform", "rescale_iw")
+_IW_UNIFORM_T = ("ll_uniform", "drop_all_uniform", "drop_sigma2t_uniform", "rescale_iw")
 
 
 def make_diffusion(args):
@@ -86,6 +89,140 @@ class DiffusionBase:
         """diffusion_continuous.py:83-86: the constant term of CE(q(z_0 | x) || p(z_0)), 1/2 (1 + log(2 pi var(ode_eps))), for the
         ODE integration cutoff `ode_eps` (a host scalar tensor; upstream builds it on the device)."""
         return 0.5 * (1.0 + torch.log(2.0 * np.pi * self.var(t=torch.tensor(ode_eps))))
+
+    # ---- importance-weighted time sampling (:340-592) -----------------------------------------------
+    def iw_quantities(self, size, time_eps, iw_sample_mode, iw_subvp_like_vp_sde, *, rho=None, device=None):
+        """diffusion_continuous.py:340-592: `size` diffusion times drawn under the importance-sampling scheme `iw_sample_mode`, with the
+        objective weights that go with each time.  Dispatch by `sde_type` as upstream (:340-348): 'vpsde' / 'geometric_sde' the VP-like
+        form (:351-423), 'sub_vpsde' :425-512 (its IW modes are defined through the VP-SDE with the same beta(t) and need
+        `iw_subvp_like_vp_sde`, else NotImplementedError), 'vesde' :514-592.  Modes: `IW_MODES`; anything else is upstream's ValueError.
+        Returns upstream's six tensors (t (B,), var_t (B,1), m_t (B,1), obj_weight_t, obj_weight_t_ll, g2_t (B,1)); obj_weight_t is (1,1)
+        for 'drop_all_uniform', (B,1) otherwise.  obj_weight_t is the factor in front of the l2 distance under the mode, obj_weight_t_ll
+        the one that turns the mode's sampling into likelihood weighting.
+
+        Host fp32, operation for operation in upstream's order (the arrays are (B,): a kernel would add rounding differences and no
+        speed), then moved to `device` (None: they stay on the host).  Keyword extension: `rho` (B,) replaces upstream's
+        `torch.rand(size, device='cuda')`, which no other device reproduces; by default it is ONE `torch.rand(size)` on the CPU generator."""
+        if self.sde_type in ("geometric_sde", "vpsde"):
+            family = self._iw_vpsdelike
+        elif self.sde_type == "sub_vpsde":
+            family = self._iw_subvpsdelike
+        elif self.sde_type == "vesde":
+            family = self._iw_vesde
+        else:
+            raise NotImplementedError
+        if rho is None:
+            rho = torch.rand(size)
+        rho = torch.as_tensor(rho).detach().to("cpu", torch.float32).reshape(-1)
+        if rho.numel() != size:
+            raise ValueError("iw_quantities: rho holds %d draws for size %d" % (rho.numel(), size))
+        if iw_sample_mode not in IW_MODES:
+            raise ValueError("Unrecognized importance sampling type: {}".format(iw_sample_mode))
+        if iw_sample_mode in _IW_UNIFORM_T:                       # uniform t: the same lines in all three upstream functions
+            t = rho * (1. - time_eps) + time_eps
+            var_t, m_t, g2_t = self.var(t), self.e2int_f(t), self.g2(t)
+            obj_weight_t_ll = g2_t / (2.0 * var_t)
+            if iw_sample_mode == "ll_uniform":
+                obj_weight_t = obj_weight_t_ll
+            elif iw_sample_mode == "drop_all_uniform":
+                obj_weight_t = torch.ones(1)
+            elif iw_sample_mode == "drop_sigma2t_uniform":
+                obj_weight_t = g2_t / 2.0
+            else:                                                 # rescale_iw (uniform t upstream too, despite the name)
+                obj_weight_t = 0.5 / (1.0 - var_t)
+        else:
+            t, var_t, m_t, obj_weight_t, obj_weight_t_ll, g2_t = family(rho, time_eps, iw_sample_mode, iw_subvp_like_vp_sde)
+        out = (t, var_t.view(-1, 1), m_t.view(-1, 1), obj_weight_t.view(-1, 1), obj_weight_t_ll.view(-1, 1), g2_t.view(-1, 1))
+        return out if device is None else tuple(o.to(device) for o in out)
+
+    def _iw_erfinv_t(self, rho):
+        """t for the 'drop_all_iw' mode of the (sub-)VP SDE: the inverse CDF of a density ~ 1 / (1 - var_vpsde(t)) (:389-390, :472-473)."""
+        return torch.sqrt(1.0 / self.delta_beta_half) * torch.erfinv(rho * self.const_norm_2 + self.const_erf) - self.beta_frac
+
+    def _iw_vpsdelike(self, rho, time_eps, mode, _unused):
+        ones = torch.ones_like(rho)
+        if mode == "ll_iw":                                       # :368-376
+            sigma2_1, sigma2_eps = self.var(ones), self.var(time_eps * ones)
+            log_sigma2_1, log_sigma2_eps = torch.log(sigma2_1), torch.log(sigma2_eps)
+            var_t = torch.exp(rho * log_sigma2_1 + (1 - rho) * log_sigma2_eps)
+            t = self.inv_var(var_t)
+            m_t, g2_t = self.e2int_f(t), self.g2(t)
+            obj_weight_t = obj_weight_t_ll = 0.5 * (log_sigma2_1 - log_sigma2_eps) / (1.0 - var_t)
+        elif mode == "drop_all_iw":                               # :385-393
+            assert self.sde_type == "vpsde", "Importance sampling for fully unweighted objective is currently only " \
+                                             "implemented for the regular VPSDE."
+            t = self._iw_erfinv_t(rho)
+            var_t, m_t, g2_t = self.var(t), self.e2int_f(t), self.g2(t)
+            obj_weight_t = self.const_norm / (1.0 - var_t)
+            obj_weight_t_ll = obj_weight_t * g2_t / (2.0 * var_t)
+        else:                                                     # drop_sigma2t_iw :395-403
+            sigma2_1, sigma2_eps = self.var(ones), self.var(time_eps * ones)
+            var_t = rho * sigma2_1 + (1 - rho) * sigma2_eps
+            t = self.inv_var(var_t)
+            m_t, g2_t = self.e2int_f(t), self.g2(t)
+            obj_weight_t = 0.5 * (sigma2_1 - sigma2_eps) / (1.0 - var_t)
+            obj_weight_t_ll = obj_weight_t / var_t
+        return t, var_t, m_t, obj_weight_t, obj_weight_t_ll, g2_t
+
+    def _iw_subvpsdelike(self, rho, time_eps, mode, like_vp_sde):
+        if not like_vp_sde:                                       # :457-458, :477-478, :490-491
+            raise NotImplementedError("iw_sample_mode %r of the sub-VP SDE is only defined through the analogous VP-SDE "
+                                      "(iw_subvp_like_vp_sde=True)" % (mode,))
+        ones = torch.ones_like(rho)
+        if mode == "ll_iw":                                       # :445-456
+            sigma2_1, sigma2_eps = self.var_vpsde(ones), self.var_vpsde(time_eps * ones)
+            log_sigma2_1, log_sigma2_eps = torch.log(sigma2_1), torch.log(sigma2_eps)
+            var_t_vpsde = torch.exp(rho * log_sigma2_1 + (1 - rho) * log_sigma2_eps)
+            t = self.inv_var_vpsde(var_t_vpsde)
+            var_t, m_t, g2_t = self.var(t), self.e2int_f(t), self.g2(t)
+            obj_weight_t = obj_weight_t_ll = g2_t / (2.0 * var_t) * (log_sigma2_1 - log_sigma2_eps) * var_t_vpsde / (1 - var_t_vpsde) / self.beta(t)
+        elif mode == "drop_all_iw":                               # :467-476
+            assert self.sde_type == "sub_vpsde", "Importance sampling for fully unweighted objective is " \
+                                                 "currently only implemented for the Sub-VPSDE."
+            t = self._iw_erfinv_t(rho)
+            var_t, m_t, g2_t = self.var(t), self.e2int_f(t), self.g2(t)
+            obj_weight_t = self.const_norm / (1.0 - self.var_vpsde(t))
+            obj_weight_t_ll = obj_weight_t * g2_t / (2.0 * var_t)
+        else:                                                     # drop_sigma2t_iw :480-489
+            sigma2_1, sigma2_eps = self.var_vpsde(ones), self.var_vpsde(time_eps * ones)
+            var_t_vpsde = rho * sigma2_1 + (1 - rho) * sigma2_eps
+            t = self.inv_var_vpsde(var_t_vpsde)
+            var_t, m_t, g2_t = self.var(t), self.e2int_f(t), self.g2(t)
+            obj_weight_t = 0.5 * g2_t / self.beta(t) * (sigma2_1 - sigma2_eps) / (1.0 - var_t_vpsde)
+            obj_weight_t_ll = obj_weight_t / var_t
+        return t, var_t, m_t, obj_weight_t, obj_weight_t_ll, g2_t
+
+    def _iw_vesde(self, rho, time_eps, mode, _unused):
+        ones = torch.ones_like(rho)
+        if mode in ("ll_iw", "drop_all_iw"):                      # :529-541, :550-562: one sampling law, two weightings
+            nsigma2_1, nsigma2_eps, sigma2_eps = self.var_N(ones), self.var_N(time_eps * ones), self.var(time_eps * ones)
+            log_frac_sigma2_1, log_frac_sigma2_eps = torch.log(self.sigma2_max / nsigma2_1), torch.log(nsigma2_eps / sigma2_eps)
+            var_N_t = (1.0 - self.sigma2_min) / (1.0 - torch.exp(rho * (log_frac_sigma2_1 + log_frac_sigma2_eps) - log_frac_sigma2_eps))
+            t = self.inv_var_N(var_N_t)
+            var_t, m_t, g2_t = self.var(t), self.e2int_f(t), self.g2(t)
+            obj_weight_t_ll = 0.5 * (log_frac_sigma2_1 + log_frac_sigma2_eps) * self.var_N(t) / (1.0 - self.sigma2_min)
+            if mode == "ll_iw":
+                obj_weight_t = obj_weight_t_ll
+            else:
+                obj_weight_t = 2.0 * obj_weight_t_ll / np.log(self.sigma2_max / self.sigma2_min)
+        else:                                                     # drop_sigma2t_iw :564-572
+            nsigma2_1, nsigma2_eps = self.var_N(ones), self.var_N(time_eps * ones)
+            var_N_t = torch.exp(rho * torch.log(nsigma2_1) + (1 - rho) * torch.log(nsigma2_eps))
+            t = self.inv_var_N(var_N_t)
+            var_t, m_t, g2_t = self.var(t), self.e2int_f(t), self.g2(t)
+            obj_weight_t = 0.5 * torch.log(nsigma2_1 / nsigma2_eps) * self.var_N(t)
+            obj_weight_t_ll = obj_weight_t / var_t
+        return t, var_t, m_t, obj_weight_t, obj_weight_t_ll, g2_t
+
+    def _init_iw_constants(self):
+        """The auxiliary constants of the linear-beta families (:637-645, :691-699; host fp32 scalars where upstream builds CUDA ones):
+        `delta_beta_half`, `beta_frac`, `const_aq`, `const_erf`, `const_norm`, `const_norm_2` — the erf normalisation of 'drop_all_iw'."""
+        self.delta_beta_half = torch.tensor(0.5 * (self.beta_end - self.beta_start))
+        self.beta_frac = torch.tensor(self.beta_start / (self.beta_end - self.beta_start))
+        self.const_aq = (1.0 - self.sigma2_0) * torch.exp(0.5 * self.beta_frac) * torch.sqrt(0.25 * np.pi / self.delta_beta_half)
+        self.const_erf = torch.erf(torch.sqrt(self.delta_beta_half) * (self.time_eps + self.beta_frac))
+        self.const_norm = self.const_aq * (torch.erf(torch.sqrt(self.delta_beta_half) * (1.0 + self.beta_frac)) - self.const_erf)
+        self.const_norm_2 = torch.erf(torch.sqrt(self.delta_beta_half) * (1.0 + self.beta_frac)) - self.const_erf
 
     # ---- per-step coefficient table for ldt_sampler_step ------------------------------------------
     def step_table(self, N, predictor, time_eps, probability_flow=False):
@@ -494,6 +631,7 @@ class DiffusionVPSDE(DiffusionBase):
         super().__init__(args)
         self.beta_start = args.beta_start
         self.beta_end = args.beta_end
+        self._init_iw_constants()
         self.train_N = args.train_N
         if args.sample_mode == "discrete":
             self.N = args.sample_N
@@ -535,6 +673,7 @@ class DiffusionSubVPSDE(DiffusionBase):
         super().__init__(args)
         self.beta_start = args.beta_start
         self.beta_end = args.beta_end
+        self._init_iw_constants()                               # (:691-699: "assumes regular VPSDE")
 
     def score_consts(self):
         return self.beta_start, self.beta_end, self.sigma2_0

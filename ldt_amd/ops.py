@@ -542,6 +542,46 @@ def dsm_loss(eta, params, weight=None, l1=False):
     return mean, per
 
 
+def nelbo_terms(eta, params, logqz, weight=None):
+    """The sums of the latent NELBO's KL term (Hybrid_Trainer.py:139-143): eta, params, logqz fp32 [B, ...] of one shape, weight None or
+    [B] -> (batch_sums [2] = (sum (eta - params)^2 * weight[b], sum logqz) over everything; sample_sums [B, 2], the same per sample).
+    Both stay on the device."""
+    _need(eta, torch.float32, "eta"); _need(params, torch.float32, "params"); _need(logqz, torch.float32, "logqz")
+    _need(weight, torch.float32, "weight")
+    if eta.shape != params.shape or eta.shape != logqz.shape:
+        raise ValueError("nelbo_terms: eta %s vs params %s vs logqz %s" % (tuple(eta.shape), tuple(params.shape), tuple(logqz.shape)))
+    eta, params, logqz = eta.contiguous(), params.contiguous(), logqz.contiguous()
+    B = eta.shape[0]
+    if weight is not None:
+        weight = weight.reshape(-1).contiguous()
+        if weight.numel() != B:
+            raise ValueError("nelbo_terms: weight holds one scalar per sample (%d), got %d" % (B, weight.numel()))
+    per = torch.empty((B, 2), dtype=torch.float32, device=eta.device)
+    tot = torch.empty((2,), dtype=torch.float32, device=eta.device)
+    check(lib().ldt_nelbo_terms(_p(eta), _p(params), _p(logqz), _p(weight), B, eta.numel() // max(B, 1), _p(per), _p(tot), stream_ptr()),
+          "ldt_nelbo_terms")
+    return tot, per
+
+
+def occupancy_grid(pts, cells, counters=None, bernoulli=None):
+    """evaluation_metrics.py:376-389 on the device: pts fp32 [S, n, 3], cells fp32 [G, 3] -> (counters, bernoulli), int32 [G] holding
+    unsigned counts: points per nearest cell, and clouds with at least one point in the cell.  Given `counters` / `bernoulli` are added to."""
+    _need(pts, torch.float32, "pts"); _need(cells, torch.float32, "cells")
+    _need(counters, torch.int32, "counters"); _need(bernoulli, torch.int32, "bernoulli")
+    if pts.dim() != 3 or pts.shape[-1] != 3 or cells.dim() != 2 or cells.shape[-1] != 3:
+        raise ValueError("occupancy_grid: pts [S, n, 3] and cells [G, 3], got %s / %s" % (tuple(pts.shape), tuple(cells.shape)))
+    pts, cells = pts.contiguous(), cells.contiguous()
+    S, n, G = pts.shape[0], pts.shape[1], cells.shape[0]
+    if counters is None:
+        counters = torch.zeros((G,), dtype=torch.int32, device=pts.device)
+    if bernoulli is None:
+        bernoulli = torch.zeros((G,), dtype=torch.int32, device=pts.device)
+    if counters.numel() != G or bernoulli.numel() != G or not (counters.is_contiguous() and bernoulli.is_contiguous()):
+        raise ValueError("occupancy_grid: counters / bernoulli hold one contiguous count per cell (%d)" % G)
+    check(lib().ldt_occupancy_grid(_p(pts), S, n, _p(cells), G, _p(counters), _p(bernoulli), stream_ptr()), "ldt_occupancy_grid")
+    return counters, bernoulli
+
+
 def chamfer(a, b):
     """a [B,na,3], b [B,nb,3] fp32 -> (dl [B,nb], dr [B,na]) squared nearest-neighbour distances."""
     a, b = a.contiguous(), b.contiguous()
