@@ -247,7 +247,7 @@ extern "C" int ldt_emd_approx(const float* x, const float* y, int32_t S, int32_t
 extern "C" int ldt_score_lnfold_route(int32_t M, int32_t D, int32_t F, int32_t gemm_wgs) {
     if (M <= 0 || D <= 0 || F <= 0 || D % 256 != 0 || D > 1024 || F % 256 != 0) return 0;
     if (ldt_gemm_lnfold_v1_route(M, D, F, gemm_wgs)) return 2;
-    const int lim = (gemm_wgs > 0 && gemm_wgs < LDT_NUM_CUS) ? gemm_wgs : LDT_NUM_CUS;
+    const int lim = ldt_wg_limit(gemm_wgs);
     return (M % 256 == 0 && (long)(M / 256) * (D / 256) * 8 >= (long)lim * 5) ? 1 : 0;
 }
 
@@ -372,7 +372,7 @@ static int score_forward_impl(const ldt_score_plan* p, const float* x, float* ep
     LDT_REQUIRE(x && eps_out, LDT_EARG, "score: null x/out");
     const int D = p->hidden, T = p->tokens, M = p->batch * p->tokens, F = p->mlp_hidden;
     const long sstr = p->mod_sample_stride, tstr = p->mod_step_stride;
-    // LN folding (gemm_bf16.hip): with batch-shared modulation (unconditional sampling) the LayerNorm + modulate between a
+    // LN folding (gemm256_tile.h): with batch-shared modulation (unconditional sampling) the LayerNorm + modulate between a
     // residual GEMM and the next projection is folded into the two GEMMs' epilogues; the host supplies the per-step
     // S / C tables (plan->fold) when that pays (whole 256x256 tiles that fill the chip: Score.can_fold).
     // Small batches whose GEMMs all run the v1 kernels fold through those (statistics per 32 columns), the rest through the 256-tile kernel.

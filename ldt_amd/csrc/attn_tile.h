@@ -1,5 +1,5 @@
 // attn_tile.h — the per-wave attention tile step shared by the attention kernels (attention.hip) and the fused QKV + self-attention
-// kernel of the bench shape (gemm_bf16.hip): K / V tiles of 64 keys in LDS, row-major with XOR-swizzled 16-B chunks; a wave owns 32 query
+// kernel of the bench shape (gemm_256.hip): K / V tiles of 64 keys in LDS, row-major with XOR-swizzled 16-B chunks; a wave owns 32 query
 // rows; S^T = K Q^T, online softmax with deferred maximum, O^T += V^T P^T (model/layers.py:183-197).
 #pragma once
 #include "kernels.h"

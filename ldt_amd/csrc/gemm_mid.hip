@@ -12,7 +12,7 @@
 // few bytes per flop AND enough bytes in flight needs the whole LDS of a CU and a request stream nobody has to wait for:
 //
 //   * 512 threads = 4 COMPUTE waves + 4 LOADER waves (one of each per SIMD).  Loader waves do nothing but issue the operand stream
-//     (global_load_lds, 16 B per lane, pieces of 8 rows x 128 B = whole lines: gemm_bf16.hip v3's finding) into a ring of THREE
+//     (global_load_lds, 16 B per lane, pieces of 8 rows x 128 B = whole lines: the 256-tile kernels' finding, gemm256_tile.h) into a ring of THREE
 //     64-deep K-tile stages and keep TWO K-tiles (96 KB at BN = 256) in flight; compute waves never issue a VMEM instruction in the
 //     main loop, so no MFMA stream ever stalls behind a DMA issue (60-185 cycles each) and the epilogue's loads and
 //     stores share a queue with nothing.
@@ -56,7 +56,7 @@ struct MidCfg {
     static constexpr int PPW = XPW + WPW;
 };
 
-// LN folding (gemm_bf16.hip "LN folding"; statistics granule = 32 columns = a compute wave's share of a 128-wide tile, plan->stats[D / 32][M][2]):
+// LN folding (gemm256_tile.h "LN folding"; statistics granule = 32 columns = a compute wave's share of a 128-wide tile, plan->stats[D / 32][M][2]):
 //   MID_FOLD_PRODUCER (EPI_RESID_F32, BN = 128): the epilogue also stores xs = bf16(x_new (1 + ln_scale)) and the wave's per-row (sum, sum of
 //     squares) over its 32 columns -> stats_out[n / 32][M][2] (8-lane DPP row sums in a fixed order: bit-reproducible, no atomics);
 //   MID_FOLD_CONSUMER (EPI_BF16 / EPI_GELU_BF16): X = xs.  The LOADER waves — idle between issue bursts — fetch the tile's rows' K / 32 partials
@@ -823,7 +823,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_mid_kernel(const GemmArgs a)
 }
 
 // ---------------------------------------------------------------------------------------------- launcher
-// Shapes this kernel takes (everything else stays with gemm_bf16.hip): whole column tiles, 16-byte aligned rows, K a multiple of 64,
+// Shapes this kernel takes (everything else stays with gemm_bf16.hip / gemm_256.hip): whole column tiles, 16-byte aligned rows, K a multiple of 64,
 // and a problem of at most two rounds of workgroups (longer ones belong to the persistent 256^2 kernel or the streaming v1 forms).
 static int mid_env() {
     static int v = -1;
@@ -965,7 +965,7 @@ bool ldt_gemm_mid_qkv_attn_takes(const GemmArgs* a_in, int tokens, int head_dim,
     // stream caps its grids (a->max_wgs); larger batches (B >= 256 at 16 heads) stay with the persistent 256^2 GEMM + the resident
     // attention kernel.  No lower bound: a small batch saves a launch here and has nothing to lose to a bigger tile.
     const long wgs = (long)(g.M / 128) * (g.N / 192);
-    const long cus = g.max_wgs > 0 && g.max_wgs < LDT_NUM_CUS ? g.max_wgs : LDT_NUM_CUS;
+    const long cus = ldt_wg_limit(g.max_wgs);
     if (wgs > 2 * cus) return false;
     return !(folded && (g.stats_parts > 32 || g.stats_parts * 32 != g.K));
 }
@@ -994,7 +994,7 @@ bool ldt_gemm_mid_q_xattn_takes(const GemmArgs* a_in, int tokens, int cond_token
     if (!on || !mid_env() || tokens != 32 || cond_tokens != 32 || head_dim != 64) return false;
     if (g.M <= 0 || g.N <= 0 || g.N % 64 != 0 || g.M % 64 != 0 || g.K % MID_BK != 0 || g.K / MID_BK < 2) return false;
     const long wgs = (long)(g.M / 64) * (g.N / 64);
-    const long cus = g.max_wgs > 0 && g.max_wgs < LDT_NUM_CUS ? g.max_wgs : LDT_NUM_CUS;
+    const long cus = ldt_wg_limit(g.max_wgs);
     return wgs >= 48 && wgs <= 2 * cus;
 }
 bool ldt_gemm_mid_q_xattn_try(const GemmArgs* a_in, int tokens, int cond_tokens, int head_dim, hipStream_t stream, int* status) {

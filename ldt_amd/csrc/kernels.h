@@ -4,6 +4,8 @@
 
 enum { EPI_F32 = 0, EPI_BF16 = 1, EPI_GELU_BF16 = 2, EPI_RELU_BF16 = 3, EPI_RESID_F32 = 4 };
 #define LDT_NUM_CUS 256      // MI355X
+// workgroups a launch may fill: every CU, or GemmArgs::max_wgs of them (a sub-batch stream's share)
+static inline int ldt_wg_limit(int max_wgs) { return (max_wgs > 0 && max_wgs < LDT_NUM_CUS) ? max_wgs : LDT_NUM_CUS; }
 enum { ACT_NONE = 0, ACT_SILU = 1, ACT_RELU = 2, ACT_GELU = 3 };
 
 struct GemmArgs {
@@ -18,7 +20,7 @@ struct GemmArgs {
     int rows_per_sample;
     const int* step_ptr; long gate_step_stride;   // gate += *step_ptr * gate_step_stride (device-side step counter)
     int M, N, K;
-    // ---- LayerNorm folding (256-tile kernel, interior tiles only; gemm_bf16.hip "LN folding") ----
+    // ---- LayerNorm folding (256-tile kernel, interior tiles only; gemm256_tile.h "LN folding") ----
     // producer (EPI_RESID_F32): second output xs[m][n] = bf16(out[m][n] * (1 + ln_scale[n])) and per-row partial
     // (sum, sum of squares) of out over each 256-column tile: stats_out[(n/256)][M][2]
     bf16_t* xs; long ldxs; const float* ln_scale; long ln_step_stride; float* stats_out;
@@ -34,7 +36,7 @@ struct GemmArgs {
     bf16_t* attn_o; float attn_scale_log2e;
     // fused q projection + cross-attention (gemm_mid.hip, ldt_gemm_mid_q_xattn_try): the condition's cached K | V rows (elements)
     const bf16_t* attn_k; const bf16_t* attn_v; long attn_ldkv; long attn_kv_batch_stride;
-    // 256-tile kernel, WREG form: W once more in MFMA-fragment order (gemm_bf16.hip "W from registers"; ldt_gemm_pack_wfrag), nullable
+    // 256-tile kernel, WREG form: W once more in MFMA-fragment order (gemm_256.hip "W from registers"; ldt_gemm_pack_wfrag), nullable
     const bf16_t* Wp;
 };
 
@@ -84,9 +86,9 @@ int ldt_gemm_launch(int epi, const GemmArgs* a, hipStream_t stream);
 enum { GEMM_ROUTE_NONE = 0, GEMM_ROUTE_256_ONE = 1, GEMM_ROUTE_256_MULTI = 2, GEMM_ROUTE_MID = 3, GEMM_ROUTE_V1 = 4 };
 struct GemmRoute {
     int family, bm, bn;
-    int tiles_per_wg;                   // most tiles one workgroup computes (> 1: the persistent 256-tile kernel only)
+    int tiles_per_wg;                   // most tiles one workgroup computes (> 1: the persistent 256-tile kernel only; Tile256List::max_count)
     int grid;                           // workgroups launched
-    int v1_shape, v1_stages;            // GEMM_ROUTE_V1: index of the instantiation (0 128x128, 1 128x64, 2 64x64; tools/dbg: 3, 4) and its stages
+    int v1_shape, v1_stages;            // GEMM_ROUTE_V1: index of the instantiation (0 128x128, 1 128x64, 2 64x64) and its stages
 };
 GemmRoute ldt_gemm_decide(int epi, const GemmArgs* a, int granule);
 int ldt_gemm_mid_shape(int epi, const GemmArgs* a);                // gemm_mid.hip: (BM << 16) | BN of the mid-size tile kernel for this problem, 0 = not taken
@@ -95,7 +97,7 @@ int ldt_gemm_mid_lnfold_shape(int epi, const GemmArgs* a);          // (BM << 16
 bool ldt_gemm_mid_lnfold_takes(int epi, int M, int N, int K);       // would the LN-folded form (statistics per 32 columns) of this GEMM be taken?
 int ldt_gemm_mid_lnfold_launch(int epi, int shape, const GemmArgs* a, hipStream_t stream);   // shape: ldt_gemm_mid_lnfold_shape's
 bool ldt_gemm_mid_qkv_attn_try(const GemmArgs* a, int tokens, int head_dim, bool folded, hipStream_t stream, int* status);
-bool ldt_gemm_qkv_attn256_try(const GemmArgs* a, int tokens, int head_dim, bool folded, hipStream_t stream, int* status);   // gemm_bf16.hip: fused QKV + self-attention at 256 tokens, Dh 64; false = not taken
+bool ldt_gemm_qkv_attn256_try(const GemmArgs* a, int tokens, int head_dim, bool folded, hipStream_t stream, int* status);   // gemm_256.hip: fused QKV + self-attention at 256 tokens, Dh 64; false = not taken
 bool ldt_gemm_mid_q_xattn_try(const GemmArgs* a, int tokens, int cond_tokens, int head_dim, hipStream_t stream, int* status);   // fused q projection + cross-attention (32 x 32 tokens, Dh 64); false = not taken
 // the shape part of the three rules above (M, N, K, stats_parts and max_wgs of `a` plus the environment switches; no pointer is read): each
 // `_try` starts with its own and then checks pointers and alignment; ldt_qkv_attention_route (include/ldt_hip.h) evaluates them in the forward's order

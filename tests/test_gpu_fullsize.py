@@ -321,7 +321,7 @@ def test_fullsize_vipc_conditioned_vs_oracle(full):
 
 
 def test_fused_qkv_attention_256_matches_two_kernel_path(tmp_path):
-    """QKV projection + self-attention in one launch at the bench shape (csrc/gemm_bf16.hip, gemm_qkv_attn256_kernel: 256 x 192 tiles = one
+    """QKV projection + self-attention in one launch at the bench shape (csrc/gemm_256.hip, gemm_qkv_attn256_kernel: 256 x 192 tiles = one
     head of one 256-token sample, the whole-head attention loop as the epilogue) against the QKV GEMM + attention kernel pair it replaces
     (LDT_QKV_ATTN256=0): the same seeded forwards at the production width (hidden 1024, 16 heads; 4 blocks) in two child processes —
     B = 64 with batch-shared modulation (blocks >= 1 LN-folded consumer form, block 0 the plain form with bias) and with per-sample times

@@ -58,6 +58,9 @@ _rows("one", ("BF16", "RESID"), 16384, 1024, 4096, ("256-one-tile", 256, 256, 1)
 _rows("multi", ALL, 16384, 4096, 1024, ("256-multi-tile", 256, 256, 4))
 _rows("multi", ("F32", "BF16"), 16384, 3072, 1024, ("256-multi-tile", 256, 256, 3))
 _rows("multi", ("GELU", "RESID"), 66560, 256, 256, ("256-multi-tile", 256, 256, 2))       # 260 tiles: four workgroups take a second one
+# grid == tiles, yet the kernels' tile list hands one workgroup two tiles (164 tiles, no multiple of 8): the multi-tile form must run
+_rows("multi", ("RESID", "BF16"), 10496, 1024, 1024, ("256-multi-tile", 256, 256, 2))
+_rows("multi", ("RESID",), 10496, 1024, 4096, ("256-multi-tile", 256, 256, 2))
 for _K in (64, 128, 192, 256):                     # 3-stage ring: 1, 2, stages, stages + 1 K-tiles
     _rows("mid", MID, 2048, 4096, _K, ("mid", 128, 256, 1))
     _rows("mid", ("BF16", "GELU"), 2048, 3072, _K, ("mid", 128, 192, 1))
@@ -80,6 +83,7 @@ _rows("v1", ("RELU",), 2048, 4096, 128, ("v1", 128, 128, 1))
 _rows("fold", ("RESID",), 512, 1024, 512, ("256-one-tile", 256, 256, 1), 256)
 _rows("fold", ("BF16",), 512, 768, 1024, ("256-one-tile", 256, 256, 1), 256)
 _rows("fold", ("RESID", "GELU"), 66560, 256, 256, ("256-multi-tile", 256, 256, 2), 256)
+_rows("fold", ("RESID",), 768, 768, 256, ("256-multi-tile", 256, 256, 2), 256)               # 9 tiles on 9 workgroups: the smallest such launch
 _rows("fold", ("RESID",), 16384, 1024, 1024, ("256-one-tile", 256, 256, 1), 256)
 _rows("fold", ("GELU",), 16384, 4096, 1024, ("256-multi-tile", 256, 256, 4), 256)         # MLP-up + GELU: the largest share of a step
 _rows("fold", ("BF16",), 16384, 3072, 1024, ("256-multi-tile", 256, 256, 3), 256)

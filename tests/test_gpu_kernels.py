@@ -611,7 +611,7 @@ torch.save(outs, sys.argv[1])
 ''' % ROOT
     res = {}
     # third child (round 6): the one-tile residual GEMMs with the weight operand loaded straight into registers from a fragment-order copy
-    # (gemm_bf16.hip WREG: asm loads, hand-counted waits, no W in LDS; LDT_GEMM_WREG=1 packs the copy on the fly) — same MFMA order, same bits
+    # (gemm_256.hip WREG: asm loads, hand-counted waits, no W in LDS; LDT_GEMM_WREG=1 packs the copy on the fly) — same MFMA order, same bits
     # fourth / fifth child (round 6): the grouped tile order of the multi-tile kernels (groups of 4 row panels by default; 8 until round 5, 1 =
     # row-major) only permutes which workgroup computes which tile — every tile's arithmetic is the same
     for ring, wreg, gm in (("0", "0", ""), ("1", "0", ""), ("1", "1", ""), ("1", "0", "8"), ("1", "0", "1")):

@@ -1,4 +1,6 @@
-"""tools/dbg: the four GEMMs of a Score block at small M under each v1 tile shape (LDT_GEMM_V1_SHAPE; 3 / 4 = the 8-wave forms)."""
+"""tools/dbg: the four GEMMs of a Score block at small M under each v1 tile shape (0 128x128, 1 128x64, 2 64x64) and tile order.
+The shape override LDT_GEMM_V1_SHAPE last existed at commit d634eab: point LDT_HIP_LIB at a library built from it
+(tools/dbg/build_head_variant.sh d634eab); the current library picks the shape itself (the "auto" lines)."""
 import os, sys, subprocess
 sys.path.insert(0, '.')
 if len(sys.argv) > 1 and sys.argv[1] == "child":
@@ -29,7 +31,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
         print(line, flush=True)
 else:
     for mp in ("0", "1"):
-        for shape in ("-1", "0", "1", "2", "3", "4"):
+        for shape in ("-1", "0", "1", "2"):
             env = dict(os.environ, LDT_GEMM_FORCE="128", LDT_GEMM_V1_MAP=mp)
             if shape != "-1": env["LDT_GEMM_V1_SHAPE"] = shape
             subprocess.run([sys.executable, __file__, "child"], env=env, stderr=subprocess.DEVNULL)

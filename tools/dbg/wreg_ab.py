@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""W-from-registers form of the 256-tile GEMM (gemm_bf16.hip WREG) against the LDS form, one process, one box: (1) bit equality of every
+"""W-from-registers form of the 256-tile GEMM (gemm_256.hip WREG) against the LDS form, one process, one box: (1) bit equality of every
 epilogue form on the Score shapes, three launches each; (2) alternating timings (HIP events, `reps` launches per arm and round).
 usage: wreg_ab.py [rounds]"""
 import os, sys
