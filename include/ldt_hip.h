@@ -351,6 +351,67 @@ int ldt_nelbo_terms(const float* eta, const float* params, const float* logqz, c
 int ldt_occupancy_grid(const float* pts, int32_t S, int32_t n, const float* cells, int32_t G, uint32_t* counters, uint32_t* bernoulli,
                        void* stream);
 
+/* ---- Score training: the backward pieces and the optimizer (score_bwd.hip, attention_bwd.hip, optim.hip) ----
+ * What trainer/Latent_SDE_Trainer.py:137-140 (`loss.backward()`, clip_grad_norm_, EMA(Adam).step()) needs under the forward kernels above,
+ * for the AdaLN LayerNorm Score blocks the shipped YAMLs train.  The backward GEMMs are NOT here: dgrad dX = dY . W and wgrad dW = dY^T . X
+ * are ldt_gemm_bf16 (LDT_EPI_F32 / LDT_EPI_BF16) on operands ldt_transpose_cast_bf16 prepares.  Like the evaluation kernels: status codes
+ * before any launch, every reduction in a fixed order, no floating-point atomics — a step repeats bit for bit.
+ * ldt_transpose_cast_bf16: src fp32 (src_bf16 = 0) or bf16 [R][C] (row stride ld_src) -> dst bf16 [C][R_pad] (row stride ld_dst), columns R ..
+ *   R_pad - 1 zero: W^T panels for dgrad, dY^T and X^T (the contraction over the R rows, padded to the GEMM's K % 64) for wgrad.
+ * ldt_colsum: out[c] = sum_m dy[m][c] over M rows of an fp32 or bf16 matrix — the bias gradient of every 1x1 conv / Linear (model/layers.py:
+ *   121-124,159-161,239; score.py:110).  float64 partials, one rounding.
+ * ldt_layernorm_modulate_bwd: backward of ldt_layernorm_modulate without affine (tools/utils.py:127-133 + model/layers.py:136-137,218-219,
+ *   243-245): from the saved fp32 x and the fp32 gradient dy of y = LN(x) (1 + scale[s]) + shift[s]:  dx[m][:] += the LayerNorm gradient (ADDED:
+ *   dx is the residual-stream gradient), dshift[s][:] = sum over sample s's rows of dy, dscale[s][:] = sum of dy * LN(x) (written, fp32
+ *   [samples][dmod_sample_stride]; both NULL = skipped).  scale: fp32 [samples][mod_sample_stride] (stride 0 = shared; NULL = 0).  stats: fp32
+ *   workspace [M][2], receives each row's (mean, rstd).  M % rows_per_sample == 0.
+ * ldt_gelu_bwd: du bf16 = dh * d/du GELU_erf(u) on the saved bf16 pre-activation u of mlp.fc (model/layers.py:111-113,127-129); dh fp32 or bf16.
+ * ldt_gate_residual_bwd: y = x + gate[s] * a (model/layers.py:218-219): da bf16 = dy * gate[s], dgate[s][:] = sum over sample s's rows of
+ *   dy * a (a: the branch output fc_o(...) / mlp(...), fp32 or bf16; dgate NULL = skipped and a unused).  dx = dy needs no kernel.
+ * ldt_silu_bwd: dc = dy * d/dc SiLU(c), fp32 (adaLN_modulation.0, model/layers.py:171,237; TimeEmbedding.mlp, :17); act (nullable) receives
+ *   SiLU(c), the operand of the following Linear's weight gradient (the forward applies it inside ldt_sgemm and never stores it).  dc NULL: act only.
+ * ldt_dsm_loss_bwd: gradient of ldt_dsm_loss's *mean_loss with respect to params (trainer/Latent_SDE_Trainer.py:131-137):
+ *   -2 (eta - params) weight[b] / (B per_sample), or -sign(eta - params) weight[b] / (B per_sample) when l1.
+ * ldt_embedding_grad: dE[k][:] = sum over the samples with label[b] == k of dc[b][:], in the order of b (the label nn.Embedding,
+ *   model/scorenet/score.py:125-128); every row of dE[n_classes][D] is written.
+ * ldt_attention_bwd: backward of ldt_attention_fwd for self-attention with head_dim 64, Nq = Nk = N <= 512 (model/layers.py:190-197).  Q, K, V as
+ *   ldt_attention_fwd takes them; O and dO are the contiguous [B][H][N][64] buffer that IS the raw (B N, C) view (quirk Q1: nothing is
+ *   permuted); dQ, dK, dV are written as row views like Q, K, V (heads at column h * 64; dK and dV share dkv_batch_stride).  Row maximum and
+ *   sum are recomputed (the forward writes no log-sum-exp) into stats fp32 [B][H][N][2] = (max + ln sum, rowsum(dO o O)).  bf16 MFMA, fp32
+ *   accumulation; P and dS are rounded to bf16 before the second products.  dQ per query block, dK / dV per key block: no sum across workgroups.
+ * ldt_sumsq: out[0] = sum x^2 (two stages, float64 partials in scratch[scratch_len], at most LDT_ODE_SUMSQ_SCRATCH used), out[1] = its root
+ *   (clip_grad_norm_'s total_norm over the flat gradient), out[2] = min(1, max_norm / (out[1] + 1e-6)) (clip_coef_clamped; 1 when max_norm <= 0).
+ * ldt_adam_ema_step: torch.optim.Adam's update (torch/optim/adam.py _single_tensor_adam: L2 weight_decay added to the gradient, exp_avg.lerp_,
+ *   exp_avg_sq.mul_.addcmul_, denom = sqrt(v) / sqrt(1 - beta2^step) + eps, param.addcdiv_ with -lr / (1 - beta1^step)): the same formulas in
+ *   the same order, each in its fewest-roundings form (not torch's kernel sequence: not bit-equal to an fp32 torch run), over flat fp32 buffers of n elements, then the reference's EMA (tools/utils.py:34-71): ema_init != 0 (a parameter's first step):
+ *   ema = param after the update; then always ema = ema * ema_decay + (1 - ema_decay) * param, evaluated as ema + (1 - ema_decay) (param - ema)
+ *   (and v likewise as v + (1 - beta2) (g g - v)): against an exact evaluation every stored value is within its own fp32 rounding plus a few roundings of
+ *   its step's change.  ema NULL: no EMA.  clip_factor: DEVICE float
+ *   (ldt_sumsq's out + 2) the gradient is first multiplied by, in place as clip_grad_norm_ does; NULL = 1, grad untouched.  step counts from 1. */
+int ldt_transpose_cast_bf16(const void* src, int32_t src_bf16, int64_t ld_src, uint16_t* dst, int64_t ld_dst, int64_t R, int32_t C,
+                            int64_t R_pad, void* stream);
+int ldt_colsum(const void* dy, int32_t dy_bf16, int64_t ld, int64_t M, int32_t C, float* out, void* stream);
+int ldt_layernorm_modulate_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy, const float* scale, int64_t mod_sample_stride,
+                               int32_t rows_per_sample, float* dx, int64_t lddx, float* dshift, float* dscale,
+                               int64_t dmod_sample_stride, float* stats, int64_t M, int32_t C, void* stream);
+int ldt_gelu_bwd(const uint16_t* u, int64_t ldu, const void* dh, int32_t dh_bf16, int64_t lddh, uint16_t* du, int64_t lddu, int64_t M,
+                 int32_t C, void* stream);
+int ldt_gate_residual_bwd(const float* dy, int64_t lddy, const void* a, int32_t a_bf16, int64_t lda, const float* gate,
+                          int64_t gate_sample_stride, int32_t rows_per_sample, uint16_t* da, int64_t ldda, float* dgate,
+                          int64_t dgate_sample_stride, int64_t M, int32_t C, void* stream);
+int ldt_silu_bwd(const float* c, const float* dy, float* dc, float* act, int64_t n, void* stream);
+int ldt_dsm_loss_bwd(const float* eta, const float* params, const float* weight, int64_t B, int64_t per_sample, int32_t l1, float* dparams,
+                     void* stream);
+int ldt_embedding_grad(const float* dc, int64_t ld, const int32_t* label, int32_t B, int32_t D, int32_t n_classes, float* dE, void* stream);
+int ldt_attention_bwd(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk, const uint16_t* V,
+                      int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats, uint16_t* dQ,
+                      int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
+                      int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t N, int32_t head_dim, void* stream);
+int ldt_sumsq(const float* x, int64_t n, double* scratch, int32_t scratch_len, float max_norm, float* out, void* stream);
+int ldt_adam_ema_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, double lr, double beta1,
+                      double beta2, double eps, double weight_decay, int32_t step, double ema_decay, int32_t ema_init,
+                      const float* clip_factor, void* stream);
+
 /* ---- fused MLP half of a narrow ResidualBlock (the Compressor's d = 128 blocks; model/layers.py:219,226 + :110-133) ----
  * In place on x fp32 [M][ldx]:  x += gate * (W_dn . GELU(W_up . h + b_up) + b_dn),  h = LN(x) * ln_w + ln_b  (affine,
  * no-condition blocks) or LN(x) * (1 + scale) + shift (AdaLN; shift/scale/gate are per-sample vectors, sample =

@@ -15,7 +15,8 @@ from .hybrid_trainer import HybridTrainer
 from . import metrics
 from .score import Score
 from .trainer import CompletionTrainer, EMAWeights, Trainer
+from .train import AdamEMA, ScoreTrainStep
 
 __all__ = ["Score", "Compressor", "ConditionNet", "DiffusionVPSDE", "DiffusionSubVPSDE", "DiffusionVESDE", "DiffusionGeometric", "DiffusionBase", "make_diffusion", "Trainer", "CompletionTrainer", "CompressorTrainer",
-           "CompletionCompressorTrainer", "HybridTrainer", "EMAWeights", "dict2namespace",
+           "CompletionCompressorTrainer", "HybridTrainer", "EMAWeights", "AdamEMA", "ScoreTrainStep", "dict2namespace",
            "airplane_config", "load_config", "metrics"]

@@ -102,6 +102,19 @@ SIGNATURES = {
     "ldt_dsm_loss": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp],
     "ldt_nelbo_terms": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "ldt_occupancy_grid": [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp],
+    "ldt_transpose_cast_bf16": [_vp, _i32, _i64, _vp, _i64, _i64, _i32, _i64, _vp],
+    "ldt_colsum": [_vp, _i32, _i64, _i64, _i32, _vp, _vp],
+    "ldt_layernorm_modulate_bwd": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _vp],
+    "ldt_gelu_bwd": [_vp, _i64, _vp, _i32, _i64, _vp, _i64, _i64, _i32, _vp],
+    "ldt_gate_residual_bwd": [_vp, _i64, _vp, _i32, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i64, _i32, _vp],
+    "ldt_silu_bwd": [_vp, _vp, _vp, _vp, _i64, _vp],
+    "ldt_dsm_loss_bwd": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp],
+    "ldt_embedding_grad": [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp],
+    "ldt_attention_bwd": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64,
+                          _i32, _i32, _i32, _i32, _vp],
+    "ldt_sumsq": [_vp, _i64, _vp, _i32, C.c_float, _vp, _vp],
+    "ldt_adam_ema_step": [_vp, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i32, C.c_double, _i32,
+                          _vp, _vp],
     "ldt_grouper_mlp": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "ldt_ln_mlp_resid": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "ldt_ln_mlp_resid_next": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64,

@@ -735,3 +735,213 @@ def ln_linear(x, w, bias=None, ln_w=None, ln_b=None, shift=None, scale=None, mod
     check(lib().ldt_ln_linear(_p(x), x.stride(0), M, Cc, _p(ln_w), _p(ln_b), _p(shift), _p(scale), mod_sample_stride, rows_per_sample,
                               _p(w), _p(bias), N, _p(out), out.stride(0), stream_ptr()), "ldt_ln_linear")
     return out
+
+
+# ---- Score training: backward pieces and the optimizer (csrc/score_bwd.hip, attention_bwd.hip, optim.hip) -------------------------
+def _f32_or_bf16(t, name):
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("%s must be float32 or bfloat16, got %s" % (name, t.dtype))
+    _need(t, t.dtype, name); _rowmajor(t, name)
+    return int(t.dtype == torch.bfloat16)
+
+
+def transpose_cast_bf16(src, rows_pad=None, out=None):
+    """fp32 | bf16 [R, C] -> bf16 [C, rows_pad] = src^T, columns R.. zero (rows_pad defaults to pad64(R)): the operand form of W^T (dgrad)
+    and of dY^T / X^T (wgrad, contraction over the R rows) for gemm_bf16."""
+    is_bf16 = _f32_or_bf16(src, "src")
+    if src.dim() != 2:
+        raise ValueError("transpose_cast_bf16: src must be 2-D")
+    R, Cc = src.shape
+    rows_pad = pad64(R) if rows_pad is None else int(rows_pad)
+    out = _bf16_rows_out(out, Cc, rows_pad, src.device, "transpose_cast_bf16: out")
+    check(lib().ldt_transpose_cast_bf16(_p(src), is_bf16, src.stride(0), _p(out), out.stride(0), R, Cc, rows_pad, stream_ptr()),
+          "ldt_transpose_cast_bf16")
+    return out
+
+
+def colsum(dy, out=None):
+    """fp32 [C] = sum over the rows of dy fp32 | bf16 [M, C] (a bias gradient), fixed order."""
+    is_bf16 = _f32_or_bf16(dy, "dy")
+    M, Cc = dy.shape
+    if out is None:
+        out = torch.empty((Cc,), dtype=torch.float32, device=dy.device)
+    _need(out, torch.float32, "out")
+    check(lib().ldt_colsum(_p(dy), is_bf16, dy.stride(0), M, Cc, _p(out), stream_ptr()), "ldt_colsum")
+    return out
+
+
+def wgrad(dy, x, out=None):
+    """dW fp32 [N, K] = dy[M, N]^T @ x[M, K] (operands fp32 | bf16, rounded to bf16) through the NT route: two transposing casts and
+    gemm_bf16(EPI_F32) contracting over the M rows padded to a multiple of 64."""
+    if dy.shape[0] != x.shape[0]:
+        raise ValueError("wgrad: dy %s and x %s differ in rows" % (tuple(dy.shape), tuple(x.shape)))
+    return gemm_bf16(transpose_cast_bf16(dy), transpose_cast_bf16(x), None, EPI_F32, out=out)
+
+
+def dgrad(dy, w_t, epilogue=EPI_F32, out=None):
+    """dX [M, K] = dy bf16 [M, N(pad 64)] @ W, with w_t = transpose_cast_bf16(W[N, K]) the bf16 [K, pad64(N)] panel."""
+    return gemm_bf16(dy, w_t, None, epilogue, out=out)
+
+
+def layernorm_modulate_bwd(x, dy, dx, scale=None, mod_sample_stride=0, rows_per_sample=None, want_mod=True, dshift=None, dscale=None):
+    """Backward of layernorm_modulate (no affine): dx fp32 [M, C] += LayerNorm gradient; -> (dshift, dscale) fp32 [samples, C] summed
+    over each sample's rows (None, None when not want_mod).  dshift / dscale: row views of one row stride to write into (column blocks
+    of the modulation-row gradient)."""
+    _need(x, torch.float32, "x"); _need(dy, torch.float32, "dy"); _need(dx, torch.float32, "dx"); _need(scale, torch.float32, "scale")
+    for t, nm in ((x, "x"), (dy, "dy"), (dx, "dx")):
+        _rowmajor(t, nm)
+    M, Cc = x.shape
+    if tuple(dy.shape) != (M, Cc) or tuple(dx.shape) != (M, Cc):
+        raise ValueError("layernorm_modulate_bwd: x, dy, dx must share one [M, C] shape")
+    rps = M if rows_per_sample is None else int(rows_per_sample)
+    if rps <= 0 or M % rps:
+        raise ValueError("layernorm_modulate_bwd: %d rows are not whole samples of %d" % (M, rps))
+    stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
+    dsh = dsc = None
+    if want_mod:
+        dsh = torch.empty((M // rps, Cc), dtype=torch.float32, device=x.device) if dshift is None else dshift
+        dsc = torch.empty((M // rps, Cc), dtype=torch.float32, device=x.device) if dscale is None else dscale
+        for t, nm in ((dsh, "dshift"), (dsc, "dscale")):
+            _need(t, torch.float32, nm); _rowmajor(t, nm)
+            if tuple(t.shape) != (M // rps, Cc) or t.stride(0) != dsh.stride(0):
+                raise ValueError("layernorm_modulate_bwd: %s must be [%d, %d] with the row stride of dshift" % (nm, M // rps, Cc))
+    check(lib().ldt_layernorm_modulate_bwd(_p(x), x.stride(0), _p(dy), dy.stride(0), _p(scale), mod_sample_stride, rps, _p(dx), dx.stride(0),
+                                           _p(dsh), _p(dsc), dsh.stride(0) if want_mod else 0, _p(stats), M, Cc, stream_ptr()),
+          "ldt_layernorm_modulate_bwd")
+    return dsh, dsc
+
+
+def gelu_bwd(u, dh, out=None):
+    """bf16 [M, C] = dh * GELU'(u) on the saved bf16 pre-activation u; dh fp32 | bf16."""
+    _need(u, torch.bfloat16, "u"); _rowmajor(u, "u")
+    is_bf16 = _f32_or_bf16(dh, "dh")
+    M, Cc = u.shape
+    if tuple(dh.shape) != (M, Cc):
+        raise ValueError("gelu_bwd: u %s vs dh %s" % (tuple(u.shape), tuple(dh.shape)))
+    out = _bf16_rows_out(out, M, Cc, u.device, "gelu_bwd: out")
+    check(lib().ldt_gelu_bwd(_p(u), u.stride(0), _p(dh), is_bf16, dh.stride(0), _p(out), out.stride(0), M, Cc, stream_ptr()), "ldt_gelu_bwd")
+    return out
+
+
+def gate_residual_bwd(dy, gate, a=None, gate_sample_stride=None, rows_per_sample=None, out=None, dgate=None):
+    """y = x + gate[s] * a: -> (da bf16 [M, C] = dy * gate[s], dgate fp32 [samples, C] = per-sample sum of dy * a, or None without a).
+    gate: fp32 [samples, >= C] rows (a view into the modulation rows is fine)."""
+    _need(dy, torch.float32, "dy"); _rowmajor(dy, "dy"); _need(gate, torch.float32, "gate"); _rowmajor(gate, "gate")
+    M, Cc = dy.shape
+    rps = M if rows_per_sample is None else int(rows_per_sample)
+    if rps <= 0 or M % rps:
+        raise ValueError("gate_residual_bwd: %d rows are not whole samples of %d" % (M, rps))
+    gate = gate.reshape(-1, gate.shape[-1])
+    gss = (gate.stride(0) if gate.shape[0] > 1 else 0) if gate_sample_stride is None else int(gate_sample_stride)
+    if gate.shape[0] not in (1, M // rps) or gate.shape[1] < Cc:
+        raise ValueError("gate_residual_bwd: gate %s for %d samples of %d channels" % (tuple(gate.shape), M // rps, Cc))
+    a_bf16 = 0
+    if a is not None:
+        a_bf16 = _f32_or_bf16(a, "a")
+        if tuple(a.shape) != (M, Cc):
+            raise ValueError("gate_residual_bwd: a %s vs dy %s" % (tuple(a.shape), tuple(dy.shape)))
+        if dgate is None:
+            dgate = torch.empty((M // rps, Cc), dtype=torch.float32, device=dy.device)
+        _need(dgate, torch.float32, "dgate"); _rowmajor(dgate, "dgate")
+        if tuple(dgate.shape) != (M // rps, Cc):
+            raise ValueError("gate_residual_bwd: dgate must be [%d, %d]" % (M // rps, Cc))
+    elif dgate is not None:
+        raise ValueError("gate_residual_bwd: dgate needs the branch output a")
+    out = _bf16_rows_out(out, M, Cc, dy.device, "gate_residual_bwd: out")
+    check(lib().ldt_gate_residual_bwd(_p(dy), dy.stride(0), _p(a), a_bf16, a.stride(0) if a is not None else 0, _p(gate), gss, rps, _p(out),
+                                      out.stride(0), _p(dgate), dgate.stride(0) if dgate is not None else 0, M, Cc, stream_ptr()),
+          "ldt_gate_residual_bwd")
+    return out, dgate
+
+
+def silu_bwd(c, dy, want_act=False):
+    """fp32 dc = dy * SiLU'(c); with want_act -> (dc, SiLU(c)) — the operand of the next Linear's weight gradient."""
+    _need(c, torch.float32, "c"); _need(dy, torch.float32, "dy")
+    if c.shape != dy.shape:
+        raise ValueError("silu_bwd: c %s vs dy %s" % (tuple(c.shape), tuple(dy.shape)))
+    c, dy = c.contiguous(), dy.contiguous()
+    out = torch.empty_like(c)
+    act = torch.empty_like(c) if want_act else None
+    check(lib().ldt_silu_bwd(_p(c), _p(dy), _p(out), _p(act), c.numel(), stream_ptr()), "ldt_silu_bwd")
+    return (out, act) if want_act else out
+
+
+def dsm_loss_bwd(eta, params, weight=None, l1=False):
+    """Gradient of dsm_loss's mean with respect to params: fp32, the shape of params."""
+    _need(eta, torch.float32, "eta"); _need(params, torch.float32, "params"); _need(weight, torch.float32, "weight")
+    if eta.shape != params.shape:
+        raise ValueError("dsm_loss_bwd: eta %s vs params %s" % (tuple(eta.shape), tuple(params.shape)))
+    eta, params = eta.contiguous(), params.contiguous()
+    B = eta.shape[0]
+    if weight is not None:
+        weight = weight.reshape(-1).contiguous()
+        if weight.numel() != B:
+            raise ValueError("dsm_loss_bwd: weight holds one scalar per sample (%d), got %d" % (B, weight.numel()))
+    out = torch.empty_like(params)
+    check(lib().ldt_dsm_loss_bwd(_p(eta), _p(params), _p(weight), B, eta.numel() // B, int(bool(l1)), _p(out), stream_ptr()), "ldt_dsm_loss_bwd")
+    return out
+
+
+def embedding_grad(dc, label, n_classes):
+    """fp32 [n_classes, D]: row k = the sum of dc[b] over the samples with label[b] == k, in the order of b."""
+    _need(dc, torch.float32, "dc"); _rowmajor(dc, "dc")
+    if not label.is_cuda:
+        raise _lib.LdtHipError("label must be a device tensor (got %s): the HIP path has no CPU fallback" % (label.device,))
+    B, D = dc.shape
+    label = label.reshape(-1).to(torch.int32).contiguous()
+    if label.numel() != B:
+        raise ValueError("embedding_grad: %d labels for %d rows" % (label.numel(), B))
+    out = torch.empty((int(n_classes), D), dtype=torch.float32, device=dc.device)
+    check(lib().ldt_embedding_grad(_p(dc), dc.stride(0), _p(label), B, D, int(n_classes), _p(out), stream_ptr()), "ldt_embedding_grad")
+    return out
+
+
+def attention_bwd(q, k, v, o, do, B, H, N, head_dim=64, out=None):
+    """Self-attention backward: q, k, v bf16 row views [B*N, >= H*64] as attention_fwd takes them, o and do the contiguous bf16
+    [B, H, N, 64] buffers (quirk Q1: the raw (B*N, C) view).  -> (dq, dk, dv) bf16 views [B*N, H*64] of one [B*N, 3*H*64] tensor (`out`
+    when given), the dY operand of the QKV projection's backward GEMMs."""
+    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
+        _need(t, torch.bfloat16, nm); _rowmajor(t, nm)
+    if not (o.is_contiguous() and do.is_contiguous()) or o.numel() != B * H * N * head_dim or do.numel() != o.numel():
+        raise ValueError("attention_bwd: o and do must be contiguous [B, H, N, %d]" % head_dim)
+    if k.stride(0) != v.stride(0):
+        raise ValueError("attention_bwd: K and V must share the row stride")
+    Cc = H * head_dim
+    out = _bf16_rows_out(out, B * N, 3 * Cc, q.device, "attention_bwd: out")
+    dq, dk, dv = out[:, :Cc], out[:, Cc:2 * Cc], out[:, 2 * Cc:]
+    stats = torch.empty((B, H, N, 2), dtype=torch.float32, device=q.device)
+    ldo = out.stride(0)
+    check(lib().ldt_attention_bwd(_p(q), q.stride(0), q.stride(0) * N, _p(k), k.stride(0), _p(v), v.stride(0), k.stride(0) * N, _p(o), _p(do),
+                                  _p(stats), _p(dq), ldo, ldo * N, _p(dk), ldo, _p(dv), ldo, ldo * N, B, H, N, head_dim, stream_ptr()),
+          "ldt_attention_bwd")
+    return dq, dk, dv
+
+
+def sumsq(x, max_norm=0.0, scratch=None, out=None):
+    """fp32 [3] on the device = (sum x^2, its root, min(1, max_norm / (root + 1e-6))) of a flat fp32 buffer: clip_grad_norm_'s total norm
+    and factor without a host synchronisation.  Two stages, fixed order."""
+    _need(x, torch.float32, "x")
+    if not x.is_contiguous():
+        raise ValueError("sumsq: x must be contiguous")
+    if scratch is None:
+        scratch = torch.empty((_lib.ODE_SUMSQ_SCRATCH,), dtype=torch.float64, device=x.device)
+    if out is None:
+        out = torch.empty((3,), dtype=torch.float32, device=x.device)
+    _need(scratch, torch.float64, "scratch"); _need(out, torch.float32, "out")
+    check(lib().ldt_sumsq(_p(x), x.numel(), _p(scratch), scratch.numel(), float(max_norm or 0.0), _p(out), stream_ptr()), "ldt_sumsq")
+    return out
+
+
+def adam_ema_step_(param, grad, exp_avg, exp_avg_sq, ema, step, lr, beta1, beta2, eps, weight_decay, ema_decay, ema_init, clip_factor=None):
+    """One fused torch-order Adam update + reference EMA over flat fp32 buffers, in place.  step: the step being taken (from 1);
+    clip_factor: a device float (sumsq(...)[2:]) or None."""
+    for t, nm in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (ema, "ema"), (clip_factor, "clip_factor")):
+        _need(t, torch.float32, nm)
+        if t is not None and not t.is_contiguous():
+            raise ValueError("adam_ema_step_: %s must be contiguous" % nm)
+    n = param.numel()
+    if any(t is not None and t.numel() != n for t in (grad, exp_avg, exp_avg_sq, ema)):
+        raise ValueError("adam_ema_step_: the flat buffers must hold %d elements each" % n)
+    check(lib().ldt_adam_ema_step(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), _p(ema), n, float(lr), float(beta1), float(beta2), float(eps),
+                                  float(weight_decay), int(step), float(ema_decay), int(bool(ema_init)), _p(clip_factor), stream_ptr()),
+          "ldt_adam_ema_step")

@@ -135,6 +135,11 @@ class Score(nn.Module):
         self._cond_cache = {}
         return P
 
+    def invalidate_packed(self):
+        """Drop the packed panels: the optimizer step writes the parameters through raw pointers, which moves neither `data_ptr` nor
+        `_version` — the two things params_fingerprint keys on."""
+        self._pack, self._pack_key, self._cond_cache = None, None, {}
+
     def stacked_adaln(self):
         """Every adaLN Linear stacked in mod-row order ([n_mod][t_dim] fp32 + [n_mod]) for the one-launch per-step
         AdaLN of the conditional sampler (ldt_cond_args.w_ada); built on first use, dropped on repack."""

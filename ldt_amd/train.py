@@ -1,0 +1,336 @@
+"""Score training on the HIP path: the optimizer and the host-driven training forward / backward of the eps-prediction Transformer.
+
+Reference: trainer/Latent_SDE_Trainer.py:94-141 (`update`, `update_score`), tools/utils.py:25-101 (EMA around Adam),
+model/scorenet/score.py:117-151 and model/layers.py:183-229 (what is differentiated).  Scope: the configuration the shipped YAMLs
+train — LayerNorm, AdaLN, self-attention with 64-wide heads, unconditional or label-conditioned.
+
+`AdamEMA` keeps fp32 master parameters, gradients, both Adam moments and the EMA in five flat device buffers (one fused
+`ldt_adam_ema_step` launch per step; bf16 operand panels are derived from the masters, never trained).  `ScoreTrainStep` runs the same
+kernels as inference, unfused, keeps per block what the backward needs, and then walks the blocks back: every GEMM of the backward is
+`ldt_gemm_bf16` on operands prepared by `ldt_transpose_cast_bf16`; everything else is csrc/score_bwd.hip and csrc/attention_bwd.hip.
+"""
+import torch
+
+from . import ops
+from ._lib import ACT_SILU, EPI_BF16, EPI_F32, EPI_RESID_F32
+from .layers import conv_w
+from .trainer import EMAWeights
+
+
+class AdamEMA(EMAWeights, torch.optim.Optimizer):
+    """torch.optim.Adam wrapped in the reference's EMA (tools/utils.py:25-101), stepped by one HIP kernel.
+
+    It is an `EMAWeights` (the sampler's `state[p]['ema']` / `swap_parameters_with_ema` contract) and a `torch.optim.Optimizer`
+    (`param_groups`, `state_dict()` / `load_state_dict()` in torch Adam's layout with the extra 'ema' entry, usable by
+    `torch.optim.lr_scheduler`).  Nothing is allocated until the first `step()` / `zero_grad()`: a trainer built on "cpu" or used
+    for sampling only holds no optimizer memory.
+
+    At first use every parameter becomes a view of one flat fp32 buffer and gets a `.grad` view of the flat gradient;
+    `state[p]` = {'step', 'exp_avg', 'exp_avg_sq', 'ema'} are views of the other flat buffers.  The EMA swap re-points `p.data`
+    and `state[p]['ema']` as upstream does; `step()` finds out which flat buffer currently plays which role and re-adopts any
+    tensor that was replaced from outside (`load_state_dict`, a test assigning `state[p]`)."""
+
+    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0., ema_decay=0.):
+        params = list(params)
+        EMAWeights.__init__(self, params, ema_decay)
+        defaults = dict(torch.optim.Adam(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay).defaults)
+        torch.optim.Optimizer.__init__(self, params, defaults)         # state = defaultdict(dict), param_groups, hooks
+        self._flat = None                                              # {'a', 'b' (parameter-sized role buffers), 'g', 'm', 'v', offsets}
+        self._steps = 0
+        self.last_norm = None                                          # device fp32 [3]: (sum g^2, norm, clip factor) of the last step
+
+    # ---------------------------------------------------------------- flat buffers
+    def _views(self, flat):
+        return [flat[o:o + p.numel()].view(p.shape) for p, o in zip(self.params, self._flat["off"])]
+
+    def _ensure_flat(self):
+        if not self.params:
+            raise ValueError("AdamEMA: no parameters")
+        dev = self.params[0].device
+        if dev.type != "cuda":
+            raise RuntimeError("AdamEMA: parameters are on %s; the HIP path has no CPU fallback" % dev)
+        if self._flat is None:
+            off, n = [], 0
+            for p in self.params:
+                if p.dtype != torch.float32 or p.device != dev:
+                    raise TypeError("AdamEMA: fp32 parameters on one device only")
+                off.append(n)
+                n += (p.numel() + 3) // 4 * 4                           # 16-byte aligned views
+            z = lambda: torch.zeros(n, dtype=torch.float32, device=dev)
+            self._flat = {"off": off, "n": n, "a": z(), "b": z(), "g": z(), "m": z(), "v": z(), "scratch": None}
+        F = self._flat
+        ptr = lambda flat, o: flat.data_ptr() + 4 * o
+        with torch.no_grad():
+            # which role buffer holds the parameters right now (the EMA swap exchanges the two)?
+            role = None
+            for cand, other in (("a", "b"), ("b", "a")):
+                if all(p.data_ptr() == ptr(F[cand], o) for p, o in zip(self.params, F["off"])):
+                    role = (cand, other)
+                    break
+            if role is None:                                            # first use, or parameters re-pointed from outside: adopt into 'a'
+                # state entries that still live in the role buffers (an EMA in 'a' after an odd number of swaps) are copied out first:
+                # the adoption below overwrites 'a', and the loop after it moves them to where their role now is
+                for p in self.params:
+                    st = self.state[p] if p in self.state else {}
+                    if "ema" in st and st["ema"].device == dev:
+                        st["ema"] = st["ema"].clone()
+                src = [p.data.clone() for p in self.params]             # (the new values may themselves be views of 'a' / 'b')
+                for p, v, x in zip(self.params, self._views(F["a"]), src):
+                    v.copy_(x)
+                    p.data = v
+                role = ("a", "b")
+            have_ema = [("ema" in self.state[p]) if p in self.state else False for p in self.params]
+            if any(have_ema) and not all(have_ema):
+                raise RuntimeError("AdamEMA: some parameters carry an EMA and others do not; the fused step updates all of them together")
+            for key, flat in (("ema", F[role[1]]), ("exp_avg", F["m"]), ("exp_avg_sq", F["v"])):
+                for p, o, v in zip(self.params, F["off"], self._views(flat)):
+                    st = self.state[p]
+                    cur = st.get(key)
+                    if cur is None:
+                        if key != "ema":
+                            v.zero_()
+                            st[key] = v
+                    elif cur.data_ptr() != ptr(flat, o) or cur.device != dev:
+                        v.copy_(cur)
+                        st[key] = v
+            for p, v in zip(self.params, self._views(F["g"])):
+                if p.grad is None or p.grad.data_ptr() != v.data_ptr():
+                    if p.grad is not None:
+                        v.copy_(p.grad)
+                    p.grad = v
+            steps = {int(self.state[p]["step"]) for p in self.params if "step" in self.state[p]}
+            if len(steps) > 1:
+                raise RuntimeError("AdamEMA: parameters at different step counts %s" % sorted(steps))
+            self._steps = steps.pop() if steps else 0
+        return F, role, all(have_ema)
+
+    def state_dict(self):
+        """torch's layout (Optimizer.state_dict) with every tensor cloned: the entries are views of the flat buffers."""
+        sd = torch.optim.Optimizer.state_dict(self)
+        for st in sd["state"].values():
+            for k, v in st.items():
+                if torch.is_tensor(v):
+                    st[k] = v.detach().clone()
+        return sd
+
+    @property
+    def flat_grad(self):
+        return self._ensure_flat()[0]["g"]
+
+    def zero_grad(self, set_to_none=False):
+        """Zero the flat gradient; the `.grad` views stay (set_to_none is accepted and ignored: the backward writes into them)."""
+        self._ensure_flat()[0]["g"].zero_()
+
+    @torch.no_grad()
+    def step(self, closure=None, max_norm=None):
+        """clip_grad_norm_(max_norm) (None: no clipping) + Adam + EMA over every parameter, two reductions and one update launch; the clip
+        factor never leaves the device."""
+        if closure is not None:
+            raise NotImplementedError("AdamEMA.step: closures are not used by the reference trainers")
+        F, role, have_ema = self._ensure_flat()
+        if len(self.param_groups) != 1:
+            raise NotImplementedError("AdamEMA: one parameter group (the reference's Adam(model.parameters()))")
+        g = self.param_groups[0]
+        if g.get("amsgrad") or g.get("maximize") or g.get("decoupled_weight_decay"):
+            raise NotImplementedError("AdamEMA: amsgrad / maximize / decoupled weight decay are not built")
+        if F["scratch"] is None:
+            from ._lib import ODE_SUMSQ_SCRATCH
+            F["scratch"] = torch.empty(ODE_SUMSQ_SCRATCH, dtype=torch.float64, device=F["g"].device)
+        self.last_norm = ops.sumsq(F["g"], max_norm=max_norm or 0.0, scratch=F["scratch"])
+        self._steps += 1
+        ema = F[role[1]] if self.apply_ema else None
+        ops.adam_ema_step_(F[role[0]], F["g"], F["m"], F["v"], ema, self._steps, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
+                           g["weight_decay"], self.ema_decay, ema_init=not have_ema,
+                           clip_factor=self.last_norm[2:] if max_norm is not None else None)
+        step_t = torch.tensor(float(self._steps))                       # torch Adam's host-side fp32 step counter
+        for p, v in zip(self.params, self._views(F[role[1]])):
+            st = self.state[p]
+            st["step"] = step_t.clone()
+            if self.apply_ema and "ema" not in st:
+                st["ema"] = v
+
+
+def clip_factor_host(optimizer):
+    """(total gradient norm, clip factor) of the last step as Python floats (synchronises; diagnostics and tests)."""
+    n = optimizer.last_norm.cpu()
+    return float(n[1]), float(n[2])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+def refuse_untrainable(model, condition=None, world_size=1):
+    """The configurations the training step does not cover, each refused with its reason before anything is launched."""
+    if condition is not None or getattr(model, "condition", False):
+        raise NotImplementedError("training with a ViPC / point condition (cross-attention blocks, ConditionNet) is not on this path: "
+                                  "the backward covers self-attention blocks only")
+    if getattr(model, "unet", False):
+        raise NotImplementedError("training the unet Score variant is not on this path (skip concatenations and conv shortcuts have no backward)")
+    if not (isinstance(model.norm, str) and model.norm.lower() == "layer_norm"):
+        raise NotImplementedError("training with norm=%r is not on this path: only layer_norm has a backward kernel" % (model.norm,))
+    if float(getattr(model, "dropout", 0.) or 0.) > 0:
+        raise NotImplementedError("training with dropout=%g is not on this path: the kernels have no dropout mask" % model.dropout)
+    if world_size > 1:
+        raise NotImplementedError("training on %d ranks is not on this path: the gradient all-reduce is a follow-up" % world_size)
+    if model.hidden_size // model.num_heads != 64:
+        raise NotImplementedError("training needs 64-wide attention heads (ldt_attention_bwd); got %d" % (model.hidden_size // model.num_heads))
+
+
+def _t(x):
+    """fp32 transpose as a dense matrix (data movement only: ldt_sgemm takes row strides, not column strides)."""
+    return x.t().contiguous()
+
+
+def _grad2d(p):
+    return p.grad.view(p.shape[0], -1)
+
+
+class ScoreTrainStep:
+    """One forward + backward of `Score` for the denoising loss.  `forward` returns params (B, T, z) and keeps the saved activations;
+    `backward(dparams)` fills every parameter's `.grad` view (the optimizer's flat gradient must be zeroed and attached first)."""
+
+    def __init__(self, model):
+        refuse_untrainable(model)
+        self.m = model
+        self.saved = None
+
+    # ---------------------------------------------------------------- forward
+    @torch.no_grad()
+    def forward(self, x, t, label=None):
+        m = self.m
+        if not x.is_cuda:
+            raise RuntimeError("ScoreTrainStep.forward: x is on %s; the HIP path has no CPU fallback" % x.device)
+        B, T, z = x.shape
+        D, H, nb, n_mod = m.hidden_size, m.num_heads, m.num_blocks, m.n_mod
+        M = B * T
+        P = m.packed()
+        S = {"B": B, "T": T, "label": label}
+        # conditioning rows (fp32): c = TimeEmbedding(t) [+ LabelEmbedding(label)], mod = adaLN(SiLU(c)) for every block
+        te = m.TimeEmbedding.mlp
+        S["e_t"] = ops.sinusoid(t.to(x).float().contiguous(), m._frequencies())
+        S["a_t"] = ops.sgemm(S["e_t"], te[0].weight, te[0].bias)                                  # pre-SiLU, kept
+        c = ops.sgemm(S["a_t"], te[2].weight, te[2].bias, act_in=ACT_SILU)
+        if label is not None:
+            le = m.LabelEmbedding
+            S["lab"] = label.to(x.device).long()
+            S["e_l"] = le.label_emb.weight.detach()[S["lab"]].float().contiguous()                # row gather
+            S["a_l"] = ops.sgemm(S["e_l"], le.mlp[0].weight, le.mlp[0].bias)
+            c = ops.add_f32(c, ops.sgemm(S["a_l"], le.mlp[2].weight, le.mlp[2].bias, act_in=ACT_SILU))
+        S["c"] = c
+        w_ada, b_ada = m.stacked_adaln()
+        mod = S["mod"] = ops.sgemm(c, w_ada, b_ada, act_in=ACT_SILU)                               # [B, n_mod]
+        mv = lambda off: mod[:, off:off + D]
+        kw = dict(mod_sample_stride=n_mod, rows_per_sample=T)
+        gk = dict(gate_sample_stride=n_mod, rows_per_sample=T)
+        # token path
+        S["x_in"] = x.contiguous().float().view(M, z)
+        xin = ops.cast_pad_bf16(S["x_in"], ops.pad64(z))
+        X = ops.gemm_bf16(xin, P["w_in"], P["b_in"], EPI_F32)
+        S["blocks"] = []
+        for l in range(nb):
+            m0 = l * 6 * D
+            sb = {"x1": X.clone()}
+            sb["h"] = ops.layernorm_modulate(X, shift=mv(m0), scale=mv(m0 + D), **kw)
+            sb["qkv"] = ops.gemm_bf16(sb["h"], P["w_qkv"][l], P["b_qkv"][l], EPI_BF16)
+            q, k, v = sb["qkv"][:, :D], sb["qkv"][:, D:2 * D], sb["qkv"][:, 2 * D:]
+            sb["o"] = ops.attention_fwd(q, k, v, B, H, T, T, D // H)                              # [B, H, T, Dh] == (M, D) raw view (Q1)
+            o2 = sb["o"].view(M, D)
+            sb["a1"] = ops.gemm_bf16(o2, P["w_o"][l], P["b_o"][l], EPI_BF16)                      # the branch output, for dgate
+            ops.gemm_bf16(o2, P["w_o"][l], P["b_o"][l], EPI_RESID_F32, out=X, resid=X, gate=mv(m0 + 2 * D), **gk)
+            sb["x2"] = X.clone()
+            sb["h2"] = ops.layernorm_modulate(X, shift=mv(m0 + 3 * D), scale=mv(m0 + 4 * D), **kw)
+            sb["u"] = ops.gemm_bf16(sb["h2"], P["w_up"][l], P["b_up"][l], EPI_BF16)               # MLP pre-activation
+            sb["ug"] = sb["u"].clone()
+            ops.block_activation_(sb["ug"], 1)                                                    # GELU
+            sb["a2"] = ops.gemm_bf16(sb["ug"], P["w_dn"][l], P["b_dn"][l], EPI_BF16)
+            ops.gemm_bf16(sb["ug"], P["w_dn"][l], P["b_dn"][l], EPI_RESID_F32, out=X, resid=X, gate=mv(m0 + 5 * D), **gk)
+            S["blocks"].append(sb)
+        f0 = nb * 6 * D
+        S["xf"] = X
+        S["hf"] = ops.layernorm_modulate(X, shift=mv(f0), scale=mv(f0 + D), **kw)
+        out = ops.gemm_bf16(S["hf"], P["w_out"], P["b_out"], EPI_F32, n=z)
+        self.saved = S
+        return out.view(B, T, z)
+
+    # ---------------------------------------------------------------- backward
+    @torch.no_grad()
+    def backward(self, dparams):
+        m, S = self.m, self.saved
+        if S is None:
+            raise RuntimeError("ScoreTrainStep.backward before forward")
+        self.saved = None
+        B, T = S["B"], S["T"]
+        D, nb, n_mod, z = m.hidden_size, m.num_blocks, m.n_mod, m.z_dim
+        M = B * T
+        mod = S["mod"]
+        mv = lambda off: mod[:, off:off + D]
+        dmod = torch.empty_like(mod)
+        dv = lambda off: dmod[:, off:off + D]
+        wt = lambda mod_: ops.transpose_cast_bf16(conv_w(mod_).detach())                       # W[N, K] -> bf16 [K, pad64(N)], rebuilt every step
+
+        def linear_bwd(layer, dy, x_in, want_dx=True, epilogue=EPI_F32, rows=None):
+            """dW, db into the layer's .grad views; -> dX = dy @ W (dy bf16 [M, N] or fp32; x_in the forward's operand)."""
+            ops.wgrad(dy, x_in, out=_grad2d(layer.weight) if rows is None else _grad2d(layer.weight)[rows[0]:rows[1]])
+            ops.colsum(dy, out=layer.bias.grad)
+            if not want_dx:
+                return None
+            dyb = dy if dy.dtype == torch.bfloat16 and dy.shape[1] % 64 == 0 else ops.cast_pad_bf16(dy.float() if dy.dtype != torch.float32 else dy,
+                                                                                                   ops.pad64(dy.shape[1]))
+            return ops.dgrad(dyb, wt(layer), epilogue)
+
+        # FinalLayer (model/layers.py:240-246)
+        d2 = dparams.contiguous().view(M, z)
+        dhf = linear_bwd(m.ln_out.ln, d2, S["hf"])
+        dX = torch.zeros((M, D), dtype=torch.float32, device=d2.device)
+        f0 = nb * 6 * D
+        ops.layernorm_modulate_bwd(S["xf"], dhf, dX, scale=mv(f0 + D), mod_sample_stride=n_mod, rows_per_sample=T, dshift=dv(f0), dscale=dv(f0 + D))
+        for l in reversed(range(nb)):
+            blk, sb, m0 = m.Transformer[l], S["blocks"][l], l * 6 * D
+            # x = x2 + gate_mlp * mlp(mod(LN(x2)))                                                  (layers.py:219)
+            da2, _ = ops.gate_residual_bwd(dX, mv(m0 + 5 * D), sb["a2"], gate_sample_stride=n_mod, rows_per_sample=T, dgate=dv(m0 + 5 * D))
+            dug = linear_bwd(blk.mlp.out, da2, sb["ug"])
+            du = ops.gelu_bwd(sb["u"], dug)
+            dh2 = linear_bwd(blk.mlp.fc[0][0], du, sb["h2"])
+            ops.layernorm_modulate_bwd(sb["x2"], dh2, dX, scale=mv(m0 + 4 * D), mod_sample_stride=n_mod, rows_per_sample=T,
+                                       dshift=dv(m0 + 3 * D), dscale=dv(m0 + 4 * D))
+            # x2 = x1 + gate_msa * fc_o(attention(q, k, v))                                         (layers.py:218, 183-200)
+            da1, _ = ops.gate_residual_bwd(dX, mv(m0 + 2 * D), sb["a1"], gate_sample_stride=n_mod, rows_per_sample=T, dgate=dv(m0 + 2 * D))
+            do = linear_bwd(blk.fc_o, da1, sb["o"].view(M, D), epilogue=EPI_BF16)                 # [M, D] == dO [B, H, T, Dh] raw (Q1)
+            qkv = sb["qkv"]
+            dqkv = torch.empty((M, 3 * D), dtype=torch.bfloat16, device=do.device)                # [dq | dk | dv], the dY of fc_q | fc_kv
+            dq, _, _ = ops.attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], sb["o"], do, B, m.num_heads, T, out=dqkv)
+            linear_bwd(blk.fc_q, dq, sb["h"], want_dx=False)
+            linear_bwd(blk.fc_kv, dqkv[:, D:], sb["h"], want_dx=False)
+            wqkv_t = ops.transpose_cast_bf16(torch.cat([conv_w(blk.fc_q), conv_w(blk.fc_kv)], 0).detach())
+            dh = ops.dgrad(dqkv, wqkv_t, EPI_F32)
+            ops.layernorm_modulate_bwd(sb["x1"], dh, dX, scale=mv(m0 + D), mod_sample_stride=n_mod, rows_per_sample=T,
+                                       dshift=dv(m0), dscale=dv(m0 + D))
+        linear_bwd(m.ln_in, dX, S["x_in"], want_dx=False)                                        # score.py:110
+        # conditioning rows: fp32 linears on transposed operands
+        w_ada, _ = m.stacked_adaln()
+        ds = ops.sgemm(dmod, _t(w_ada))                                                          # d SiLU(c)  [B, t_dim]
+        dc, s_c = ops.silu_bwd(S["c"], ds, want_act=True)
+        dW = ops.sgemm(_t(dmod), _t(s_c))                                                        # [n_mod, t_dim]
+        db = ops.colsum(dmod)
+        lins = [blk.adaLN[1] for blk in m.Transformer] + [m.ln_out.adaLN[1]]
+        r = 0
+        for lin in lins:
+            n = lin.weight.shape[0]
+            lin.weight.grad.copy_(dW[r:r + n])
+            lin.bias.grad.copy_(db[r:r + n])
+            r += n
+
+        def mlp2_bwd(seq, a_pre, e_in):
+            """seq = Linear, SiLU, Linear on e_in with the saved pre-activation a_pre: grads into .grad, -> d e_in."""
+            d_s = ops.sgemm(dc, _t(seq[2].weight.detach()))
+            d_a, s_a = ops.silu_bwd(a_pre, d_s, want_act=True)
+            ops.sgemm(_t(dc), _t(s_a), out=seq[2].weight.grad)
+            ops.colsum(dc, out=seq[2].bias.grad)
+            ops.sgemm(_t(d_a), _t(e_in), out=seq[0].weight.grad)
+            ops.colsum(d_a, out=seq[0].bias.grad)
+            return d_a
+
+        mlp2_bwd(m.TimeEmbedding.mlp, S["a_t"], S["e_t"])
+        if S["label"] is not None:
+            le = m.LabelEmbedding
+            d_a = mlp2_bwd(le.mlp, S["a_l"], S["e_l"])
+            d_e = ops.sgemm(d_a, _t(le.mlp[0].weight.detach()))
+            le.label_emb.weight.grad.copy_(ops.embedding_grad(d_e, S["lab"], le.label_emb.weight.shape[0]))

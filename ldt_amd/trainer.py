@@ -1,10 +1,12 @@
-"""`Trainer` — sampling half of the reference trainer (trainer/Latent_SDE_Trainer.py), MI355X path.
+"""`Trainer` — the reference's stage-2 trainer (trainer/Latent_SDE_Trainer.py), MI355X path.
 
 Kept: `Trainer(cfg, model, compressor, device)`, `score_fn(t, x, label, condition) -> (score, params)` (:57-61),
-`val_loss(data, condition) -> held-out denoising loss` (:63-92),
+`val_loss(data, condition) -> held-out denoising loss` (:63-92), `update(data, condition)` / `update_score(eps, condition, cates,
+discrete)` — one Score training step: backward, clip, Adam + EMA (:94-141; ldt_amd/train.py) —
 `sample(num_samples, num_points, label, condition) -> (points, eps)` (:143-165), `valsample`-style "Sample rate"
-timing (:178-181,206), EMA weight swap (:146,164; tools/utils.py:80-101) and the checkpoint keys (:232-235,
-:251-256).  Training (`update*`, optimizers, schedulers) is out of scope for this path.
+timing (:178-181,206), EMA weight swap (:146,164; tools/utils.py:80-101), `save` / `resume` with the reference's checkpoint
+dict (:228-266).  Training covers the Score of the shipped YAMLs (LayerNorm, AdaLN, self-attention, unconditional or labelled);
+the Compressor and the hybrid objective are not trained on this path.
 
 Multi-GPU: when torch.distributed is initialised, `sample(B)` runs rows [lo,hi) of the batch on this rank and
 all-gathers the finished points/latents once (ldt_amd/dist.py); results do not depend on the world size when
@@ -67,7 +69,13 @@ class Trainer:
         self.num_categorys = cfg.data.num_categorys
         self.model = model.to(device)
         self.compressor = compressor.to(device)
-        self.optimizer = EMAWeights(self.model.parameters(), ema_decay=cfg.opt.ema_decay)
+        # Latent_SDE_Trainer.py:42-44: EMA(Adam(...)) and its cosine schedule.  AdamEMA is an EMAWeights; it allocates nothing until the
+        # first training step.  (The YAML fields a sampling-only config leaves out take torch.optim.Adam's defaults.)
+        from .train import AdamEMA
+        opt = cfg.opt
+        self.optimizer = AdamEMA(self.model.parameters(), lr=getattr(opt, "lr", 1e-3), betas=(getattr(opt, "beta1", 0.9), getattr(opt, "beta2", 0.999)),
+                                 weight_decay=getattr(opt, "weight_decay", 0.), ema_decay=opt.ema_decay)
+        self.scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.optimizer, getattr(getattr(cfg, "common", None), "epochs", 1), 0)
         self.sample_time_eps = cfg.sde.sample_time_eps
         self.sample_N = cfg.sde.sample_N
         self.sample_mode = cfg.sde.sample_mode
@@ -268,13 +276,101 @@ class Trainer:
             print("Validation Sample (unit) Epoch:%d " % self.epoch, gen_res)
         return all_res
 
+    # ---- training: one Score step (trainer/Latent_SDE_Trainer.py:94-141, trainer/base.py:32-37) -------------------
+    def warm_up(self, optimizer, itr):
+        if itr < self.cfg.opt.warmup_iters:
+            iter_frac = min(float(itr + 1) / max(self.cfg.opt.warmup_iters, 1), 1.0)
+            lr = self.cfg.opt.lr * iter_frac
+            for param_group in optimizer.param_groups:
+                param_group["lr"] = lr
+
+    def update(self, data, condition=None):
+        """The reference's `update` line for line (:94-109): labels from `data['cate_idx']` when cfg.data.num_categorys > 1, the EMA swap
+        around the step from the second iteration on, the frozen Compressor's `all_eps` of `data['tr_points']`, `update_score`, `itr += 1`.
+        Returns the 0-dim device loss."""
+        from .train import refuse_untrainable
+        refuse_untrainable(self.model, condition, ldist.world()[1])
+        if not torch.device(self.device).type == "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("Trainer.update: device %s; the HIP path has no CPU fallback" % (self.device,))
+        cates = data["cate_idx"].to(self.device) if self.cfg.data.num_categorys > 1 else None
+        if self.itr > 0:
+            self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
+        try:
+            with torch.no_grad():
+                self.compressor.eval()
+                eps = self.compressor(data["tr_points"].to(self.device))["all_eps"]
+            loss = self.update_score(eps, cates=cates, discrete=getattr(self.cfg.opt, "discrete", False), condition=condition)
+        finally:
+            if self.itr > 0:
+                self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
+        self.itr += 1
+        return loss
+
+    def update_score(self, eps, condition=None, cates=None, discrete=False, *, t_index=None, eta=None, seed=None):
+        """The reference's `update_score` (:111-141): warm-up of the learning rate, times by `np.random.choice` (discrete) or
+        `SDE.iw_quantities(size, time_eps, cfg.sde.iw_sample_p_mode, ...)` with its per-sample `weight_p`, `xt = eps * e2int_f +
+        sqrt(var) * eta` (ldt_diffuse_q), the Score in training mode with its activations kept, the l1 / l2 loss (ldt_dsm_loss), the
+        backward pass, `clip_grad_norm_(cfg.opt.grad_norm_clip_value)` and `EMA(Adam).step()` in one fused update.  Returns the 0-dim
+        device loss; nothing is synchronised.  Keyword extensions as `val_loss`: `t_index` (B,) replaces the numpy draw of the discrete
+        times, `eta` (B, tokens, z) the noise, `seed` the Philox key of the device noise.  The pieces stay available as `self.last_update`."""
+        import numpy as np
+        from . import ops
+        from .train import ScoreTrainStep, refuse_untrainable
+        refuse_untrainable(self.model, condition, ldist.world()[1])
+        if not torch.is_tensor(eps) or not eps.is_cuda:
+            raise RuntimeError("Trainer.update_score: eps is on %s; the HIP path has no CPU fallback"
+                               % (eps.device if torch.is_tensor(eps) else type(eps).__name__,))
+        dev = eps.device
+        self.warm_up(self.optimizer, self.itr)
+        eps = eps.detach().float().contiguous()
+        self.model.train()
+        self.optimizer.zero_grad()
+        size = eps.shape[0]
+        if discrete:
+            train_N = self.cfg.sde.train_N
+            if t_index is None:
+                t_index = np.random.choice(np.arange(train_N), size, replace=True)
+            idx = torch.as_tensor(np.asarray(t_index)).long().reshape(-1)
+            if idx.numel() != size:
+                raise ValueError("update_score: t_index holds %d entries for a batch of %d" % (idx.numel(), size))
+            t = torch.linspace(1.0, self.sample_time_eps, train_N).index_select(0, idx)
+            e2int_f, var, weight_p = self.SDE.e2int_f(t), self.SDE.var(t), None
+        else:
+            t, var, e2int_f, weight_p, _, _ = self.SDE.iw_quantities(size, time_eps=self.cfg.sde.time_eps,
+                                                                     iw_sample_mode=self.cfg.sde.iw_sample_p_mode,
+                                                                     iw_subvp_like_vp_sde=self.sde_type == "sub_vpsde")
+            weight_p = weight_p.reshape(-1).float().to(dev)
+        if eta is None and seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        t_dev = t.reshape(-1).float().to(dev)
+        xt, eta = ops.diffuse_q(eps, e2int_f.reshape(-1).float().to(dev), var.reshape(-1).float().to(dev),
+                                None if eta is None else eta.to(dev, torch.float32), seed=seed or 0)
+        step = ScoreTrainStep(self.model)
+        params = step.forward(xt, t_dev, label=cates)
+        l1 = self.cfg.opt.loss_type == "l1"
+        loss, per_sample = ops.dsm_loss(eta, params, weight_p, l1=l1)
+        step.backward(ops.dsm_loss_bwd(eta, params, weight_p, l1=l1))
+        self.optimizer.step(max_norm=getattr(self.cfg.opt, "grad_norm_clip_value", None))
+        self.model.invalidate_packed()                   # the update wrote the weights through raw pointers: no version counter moved
+        self.last_update = {"t": t_dev, "eta": eta, "xt": xt, "params": params, "sample_loss": per_sample, "weight_p": weight_p,
+                            "grad_norm": self.optimizer.last_norm, "lr": self.optimizer.param_groups[0]["lr"]}
+        return loss
+
+    def save(self, **kwargs):
+        """The reference's checkpoint dict (:228-239) at `<cfg.log.save_path>/checkpt_<epoch>.pth`."""
+        path = os.path.join(self.cfg.log.save_path, "checkpt_{:}.pth".format(self.epoch))
+        torch.save({"cfg": self.cfg, "score_state_dict": self.model.state_dict(), "score_optim_state_dict": self.optimizer.state_dict(),
+                    "score_scheduler": self.scheduler.state_dict(), "compressor_state_dict": self.compressor.state_dict(),
+                    "epoch": self.epoch, "itr": self.itr, "time": self.time}, path)
+        return path
+
     # ---- checkpoints: the reference's dict layout (:228-266) ------------------------------------------
     def resume(self, epoch=None, strict=False, load_optim=True, finetune=False, pretrain=None, **kwargs):
         """Same arguments as the reference (:241-266): the file is `pretrain` if given, else
         `<cfg.log.save_path>/checkpt_<epoch>.pth` with `epoch` defaulting to the last row of `training.csv`.
-        (A path string passed as `epoch` is accepted as shorthand for `pretrain=`.)  Loads both state dicts, adopts
-        the optimizer's per-parameter 'ema' tensors (unless finetune / load_optim=False) and re-runs
-        `compressor.init()`."""
+        (A path string passed as `epoch` is accepted as shorthand for `pretrain=`.)  Loads both state dicts, the
+        optimizer's state — step, moments and the per-parameter 'ema' tensors — unless finetune / load_optim=False,
+        and re-runs `compressor.init()`."""
         import os
         if finetune:
             load_optim, strict = False, False
@@ -291,7 +387,12 @@ class Trainer:
         self.compressor.load_state_dict(ckpt["compressor_state_dict"], strict=strict)
         self.compressor.init()
         if load_optim:
-            self.optimizer.load_ema(ckpt["score_optim_state_dict"])
+            osd = ckpt["score_optim_state_dict"]
+            groups = osd.get("param_groups") or []
+            if len(groups) == 1 and len(groups[0].get("params", ())) == len(self.optimizer.params):
+                self.optimizer.load_state_dict(osd)              # :259 — step, both moments and the EMA of every parameter
+            else:                                                # a state dict without Adam's groups: its 'ema' tensors only
+                self.optimizer.load_ema(osd)
         if finetune:
             self.epoch, self.itr = 1, 0
         else:
@@ -311,6 +412,10 @@ class CompletionTrainer(Trainer):
     `sample(num_samples, condition={'img': views, 'pts': partial})` runs the score model's ConditionNet once per call
     (:150-151; needs cfg.score.condition = True), samples image/partial-cloud conditioned latents and returns the decoded
     clouds only (:168); `valsample` is the evaluation loop of :170-215 without the dataset and the renderer."""
+
+    def update(self, data, condition=None):
+        raise NotImplementedError("CompletionTrainer.update: training with a ViPC / point condition (cross-attention blocks, ConditionNet) "
+                                  "is not on this path: the backward covers self-attention blocks only")
 
     @torch.no_grad()
     def sample(self, num_samples, num_points=None, label=None, condition=None, **kw):

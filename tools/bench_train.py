@@ -1,0 +1,74 @@
+"""Time of one Score training step at production width (hidden 1024, 16 heads, 24 blocks), B = 64, at T = 32 and T = 256 latent tokens:
+HIP events around the forward, the backward and the optimizer (one warm-up step, then the median of 7), and the rate against 3 x the
+forward's FLOPs (forward + dgrad + wgrad of every GEMM; the attention backward's extra recomputation is not credited).
+    python tools/bench_train.py [out.txt] [tokens ...]          # out.txt defaults to profiles/train_step.txt, the committed record
+No speed target is attached to these numbers: the step is the unfused, host-driven form; the follow-up that fuses it starts here."""
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+import ldt_amd  # noqa: E402
+from ldt_amd import ops  # noqa: E402
+from ldt_amd.train import ScoreTrainStep  # noqa: E402
+
+out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "train_step.txt")
+tokens = [int(a) for a in sys.argv[2:]] or [32, 256]
+B, CALLS = 64, 7
+lines = []
+
+
+def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+
+def forward_flops(m, T):
+    D, F, z, nb, M = m.hidden_size, m.Transformer[0].mlp.out.in_channels, m.z_dim, m.num_blocks, B * T
+    gemm = 2 * M * (z * D + nb * (3 * D * D + D * D + 2 * D * F) + D * z)
+    attn = nb * 4 * B * T * T * D
+    return gemm + attn
+
+
+for T in tokens:
+    cfg = ldt_amd.airplane_config(latent_tokens=T)
+    torch.manual_seed(0)
+    model = ldt_amd.Score(cfg.score).cuda()
+    opt = ldt_amd.AdamEMA(model.parameters(), lr=1e-4, ema_decay=0.9999)
+    g = torch.Generator().manual_seed(1)
+    x, eta = torch.randn(B, T, model.z_dim, generator=g).cuda(), torch.randn(B, T, model.z_dim, generator=g).cuda()
+    t = (torch.rand(B, generator=g) * 0.98 + 0.01).cuda()
+    ms = {"forward": [], "backward": [], "optimizer": []}
+    for it in range(CALLS + 1):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        opt.zero_grad()
+        step = ScoreTrainStep(model)
+        ev[0].record()
+        params = step.forward(x, t)
+        loss, _ = ops.dsm_loss(eta, params)
+        ev[1].record()
+        step.backward(ops.dsm_loss_bwd(eta, params))
+        ev[2].record()
+        opt.step(max_norm=1.0)
+        model.invalidate_packed()
+        ev[3].record()
+        torch.cuda.synchronize()
+        if it:                                                    # the first step is the warm-up (allocation, panel packing)
+            for k, (a, b) in zip(ms, ((0, 1), (1, 2), (2, 3))):
+                ms[k].append(ev[a].elapsed_time(ev[b]))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    total = sum(med.values())
+    fl = forward_flops(model, T)
+    say("Score training step  B %d  T %d  hidden %d  blocks %d  (%d parameters)  loss %.4f" % (B, T, model.hidden_size, model.num_blocks,
+        sum(p.numel() for p in model.parameters()), float(loss)))
+    say("  forward %8.2f ms   backward %8.2f ms   optimizer %7.2f ms   step %8.2f ms   (median of %d after one warm-up)"
+        % (med["forward"], med["backward"], med["optimizer"], total, CALLS))
+    say("  forward FLOPs %.3e;  3 x forward / step = %.1f TFLOP/s;  forward alone %.1f TFLOP/s;  peak memory %.2f GB"
+        % (fl, 3 * fl / total / 1e9, fl / med["forward"] / 1e9, torch.cuda.max_memory_allocated() / 2 ** 30))
+    del model, opt, step, params
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+if out_path:
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
