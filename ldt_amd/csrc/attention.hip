@@ -8,34 +8,97 @@
 // (B,N,C) without permuting heads back (layers.py:197, quirk Q1), so the consumer GEMM just reads it
 // as an [B*Nq, C] matrix.
 //
-// Structure: one workgroup = 4 waves = 128 query rows of one (b,h); each wave owns 32 rows.  K/V tiles
-// of 64 keys are double-buffered in LDS, both ROW-MAJOR with 16-B chunk XOR swizzles (K: conflict-free
-// ds_read_b128 rows; V: conflict-free ds_read_b64_tr_b16, the hardware transposed read that yields the
-// V^T operand fragments directly, guide T10); the next tile is fetched into registers under the MFMAs and
-// written to the other buffer before the single barrier of the iteration (T14).  QK^T is computed SWAPPED
+// Common to every kernel here: a wave owns 32 query rows.  K/V tiles of 64 keys sit in LDS, both ROW-MAJOR
+// with 16-B chunk XOR swizzles (K: conflict-free ds_read_b128 rows; V: conflict-free ds_read_b64_tr_b16, the
+// hardware transposed read that yields the V^T operand fragments directly, guide T10).  QK^T is computed SWAPPED
 // (S^T = K·Q^T, mfma_f32_32x32x16_bf16) so a query row lives on ONE lane: the online-softmax row
 // max/sum are in-register reductions plus a single cross-half (lane^32) exchange, and the S^T accumulator
 // is directly the B operand of O^T += V^T·P^T with no LDS round trip (guide §3 "accumulator tile as the
-// next MFMA's operand", k order 16s + 8(j>>2) + 4h + (j&3)).
-#include <stdlib.h>
+// next MFMA's operand", k order 16s + 8(j>>2) + 4h + (j&3)).  The tile step itself is attn_tile.h.
+//
+// Kernels (ldt_attn_route / ldt_attn_oproj_launch choose by shape; one form each, no build or environment switches):
+//   attn_fwd_kernel<DH, OPROJ>        streaming: a workgroup = 4 waves = 128 query rows, K/V tiles double-buffered through registers
+//                                     (fetched under the MFMAs, written before the one barrier of the iteration, T14).  Dh = 64: 64-key
+//                                     tiles, attn_block chain.  Dh = 32: 128-key tiles, two joint steps per barrier.  OPROJ: + output
+//                                     projection and gated residual (Wo from L2, runtime H).
+//   attn_fwd_resident_kernel<DH>      a head's K/V resident in LDS, no barrier in the loop (attn_tile at Dh = 64, attn_head_pipelined at 32)
+//   attn_fwd_head_kernel<DH, NTL>     8 waves, the whole head in flight, K/V by LDS-DMA with counted waits (attn_tile_joint)
+//   attn_oproj_resident_kernel<H>     resident K/V + Wo in registers + output projection and gated residual (attn_head_pipelined)
+// The steps they share are the functions at the top of the file.  Two steps are still written twice, because a shared function changed
+// the code of attn_oproj_resident_kernel in a way the codegen rules of this file do not allow (profiles/attention_refactor_codegen.txt):
+// the resident K/V load (attn_fwd_resident_kernel / attn_oproj_resident_kernel) and the gated residual update (attn_fwd_kernel<32, true> /
+// attn_oproj_resident_kernel).
 
 #include <type_traits>
 
 #include "kernels.h"
 #include "attn_tile.h"
 
+// ---- the steps the kernels below share, each written once ----
+
+// XOR swizzles of the 16-B chunks of a K / V row in LDS (chunk index ^ swizzle of the row): K for the row-per-lane ds_read_b128 of
+// S^T = K Q^T, V for ds_read_b64_tr_b16.  (AttnLaneOffs::init reads with the same two.)
+template <int DH> __device__ __forceinline__ int attn_swz_k(int row) { return (DH == 64) ? ((row >> 1) & 7) : ((row >> 2) & 3); }
+template <int DH> __device__ __forceinline__ int attn_swz_v(int row) { return (DH == 64) ? (((row >> 1) & 1) << 2) : 0; }
+
+// Q^T fragments of a wave's 32 query rows from q0 (B operand of S^T = K Q^T): lane (q = r, half hh) holds Q[q][16s + 8hh + j].
+// Rows past Nq re-read row Nq-1: computed, never stored.
+template <int DH>
+__device__ __forceinline__ void attn_load_q(const AttnArgs& a, const bf16_t* Qb, int q0, int r, int hh, bf16x8 (&qf)[DH / 16]) {
+    int qrow = q0 + r;
+    qrow = qrow < a.Nq ? qrow : a.Nq - 1;
+    const bf16_t* qp = Qb + (long)qrow * a.ldq + 8 * hh;
+#pragma unroll
+    for (int s = 0; s < DH / 16; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
+}
+
+// Normalise a wave's 32 x DH outputs (rows q0.. of head (b, head)), stage them through the wave's private LDS rows `ost` (32 x ROWB bytes,
+// XOR-swizzled chunks) and store whole rows, 16 B per lane: the row-per-lane fragment layout would touch 32 lines per store.
+// (Takes the lane, not r / hh: that is the form whose code keeps every caller's register counts and wait sequence.)
+template <int DH>
+__device__ __forceinline__ void attn_store_rows(const AttnArgs& a, char* ost, const f32x16 (&oacc)[DH / 32], float l_run, int b, int head, int q0, int lane) {
+    constexpr int ROWB = DH * 2, CH = ROWB / 16;
+    const int r = lane & 31, hh = lane >> 5;
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+    const float inv = 1.0f / l_tot;
+#pragma unroll
+    for (int d = 0; d < DH / 32; ++d)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int chn = d * 4 + g;                                  // 16-B chunk; hh picks its 8-B half
+            const bf16x4 pk = {(bf16_t)(oacc[d][4 * g + 0] * inv), (bf16_t)(oacc[d][4 * g + 1] * inv),
+                               (bf16_t)(oacc[d][4 * g + 2] * inv), (bf16_t)(oacc[d][4 * g + 3] * inv)};
+            *reinterpret_cast<bf16x4*>(ost + r * ROWB + ((chn ^ (r & (CH - 1))) << 4) + hh * 8) = pk;
+        }
+    bf16_t* ob = a.O + (((long)b * a.H + head) * a.Nq + q0) * DH;
+#pragma unroll
+    for (int it = 0; it < (32 * CH) / 64; ++it) {
+        const int row = it * (64 / CH) + lane / CH, ch = lane % CH;
+        const bf16x8 v = *reinterpret_cast<const bf16x8*>(ost + row * ROWB + ((ch ^ (row & (CH - 1))) << 4));
+        if (q0 + row < a.Nq) *reinterpret_cast<bf16x8*>(ob + (long)row * DH + ch * 8) = v;
+    }
+}
+
+// Fused output projection (Dh = 32, C = 32 H channels).  A workgroup's 128 x Dh outputs are one contiguous piece of the [B][H][Nq][Dh]
+// buffer = 128/H whole rows of the (B*Nq, C) matrix the reference reinterprets it as (quirk Q1): normalised and staged in LDS as those
+// rows (B operand of the projection), 16-B chunks XOR-swizzled by attn_q1_swz.
+__device__ __forceinline__ int attn_q1_swz(int row, int C) { return C == 128 ? (row & 15) : ((row >> 1) & 7); }
+__device__ __forceinline__ void attn_q1_stage(char* stage, const f32x16& o, float inv, int wave, int r, int hh, int C) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {                                       // one 32-wide d tile
+        const int flat = (wave * 32 + r) * 32 + 8 * g + 4 * hh;
+        const int orow = flat / C, ocol = flat % C;
+        const bf16x4 pk = {(bf16_t)(o[4 * g + 0] * inv), (bf16_t)(o[4 * g + 1] * inv), (bf16_t)(o[4 * g + 2] * inv), (bf16_t)(o[4 * g + 3] * inv)};
+        *reinterpret_cast<bf16x4*>(stage + orow * (C * 2) + (((ocol >> 3) ^ attn_q1_swz(orow, C)) << 4) + (ocol & 7) * 2) = pk;
+    }
+}
+
 // Round 6, Dh = 32 (the Compressor's cross-attention, BASELINE configs[3]'s microbench): LDS tiles of 128 keys = TWO joint 64-key steps per
 // barrier — both steps' S^T MFMAs are issued before the first softmax (four independent score accumulators per wave instead of
 // attn_block's one sequential chain, which, not a unit, bounded this kernel), half the barriers and staging round trips per key.
-#ifndef ATT_STREAM32_KT
-#define ATT_STREAM32_KT 128              /* tools/dbg A/B: 64 = the round-5 form (attn_block chain) */
-#endif
-#ifndef ATT_ABL
-#define ATT_ABL 0                        /* tools/dbg timing-only builds of attn_fwd_kernel (wrong results): bit 1 no K / V fetch behind tile 0, 2 no tile compute, 4 no output store */
-#endif
 template <int DH, bool OPROJ = false>
-__global__ __launch_bounds__(256, (DH == 32 && ATT_STREAM32_KT == 128) ? 3 : 4) void attn_fwd_kernel(const AttnArgs a) {   // (four score accumulators: 168 VGPRs)
-    constexpr int KT = (DH == 32) ? ATT_STREAM32_KT : 64;   // keys per LDS tile
+__global__ __launch_bounds__(256, DH == 32 ? 3 : 4) void attn_fwd_kernel(const AttnArgs a) {   // (four score accumulators: 168 VGPRs)
+    constexpr int KT = (DH == 32) ? 128 : 64;   // keys per LDS tile
     constexpr int ROWB = DH * 2;                // K / V row bytes
     constexpr int CH = ROWB / 16;               // 16-B chunks per row (8 or 4)
     constexpr int NS = DH / 16;                 // k-steps of QK^T
@@ -58,19 +121,8 @@ __global__ __launch_bounds__(256, (DH == 32 && ATT_STREAM32_KT == 128) ? 3 : 4) 
     const bf16_t* Kb = a.K + (long)b * a.kv_batch_stride + head * DH;
     const bf16_t* Vb = a.V + (long)b * a.kv_batch_stride + head * DH;
 
-    // swizzles (16-B chunk index XOR): K for the row-per-lane ds_read_b128 of S^T = K Q^T, V for ds_read_b64_tr_b16
-    auto swzK = [](int row) { return (DH == 64) ? ((row >> 1) & 7) : ((row >> 2) & 3); };
-    auto swzV = [](int row) { return (DH == 64) ? (((row >> 1) & 1) << 2) : 0; };
-
-    // Q^T fragments (B operand of S^T = K·Q^T): lane (q = r, half hh) holds Q[q][16s + 8hh + j]
     bf16x8 qf[NS];
-    {
-        int qrow = q0 + r;
-        qrow = qrow < a.Nq ? qrow : a.Nq - 1;
-        const bf16_t* qp = Qb + (long)qrow * a.ldq + 8 * hh;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
-    }
+    attn_load_q<DH>(a, Qb, q0, r, hh, qf);
 
     // register staging of one K/V tile (issue early, write to LDS late: guide T14).  Thread -> (row, chunk) pieces are
     // fixed, so the global offsets and the swizzled LDS offsets are computed once; a tile's rows are then `uniform tile
@@ -81,7 +133,7 @@ __global__ __launch_bounds__(256, (DH == 32 && ATT_STREAM32_KT == 128) ? 3 : 4) 
     constexpr int RPP = 256 / CH;
     const int prow = tid / CH, pch = tid % CH;
     const int gk_off = prow * (int)a.ldk + pch * 8, gv_off = prow * (int)a.ldv + pch * 8;
-    const int sk_off = prow * ROWB + ((pch ^ swzK(prow)) << 4), sv_off = prow * ROWB + ((pch ^ swzV(prow)) << 4);
+    const int sk_off = prow * ROWB + ((pch ^ attn_swz_k<DH>(prow)) << 4), sv_off = prow * ROWB + ((pch ^ attn_swz_v<DH>(prow)) << 4);
     auto stage_load = [&](const bf16_t* base, long ld, int goff, int kv0) {
         const bf16_t* T = base + (long)kv0 * ld;
         if (kv0 + KT <= a.Nk) {
@@ -124,26 +176,22 @@ __global__ __launch_bounds__(256, (DH == 32 && ATT_STREAM32_KT == 128) ? 3 : 4) 
         const bool more = t + 1 < ntiles;
         char* cur = smem + BUF * 2 * TILE;
         char* nxt = smem + (BUF ^ 1) * 2 * TILE;
-        const bool fetch = more && !(ATT_ABL & 1);             // (ATT_ABL: tools/dbg timing-only builds; 0 in the product)
-        if (fetch) stage_load(Kb, a.ldk, gk_off, kv0 + KT);
-        if constexpr ((ATT_ABL & 2) != 0) {                    // timing-only: the tile's traffic without its compute
-            if (fetch) { stage_store(nxt, sk_off); stage_load(Vb, a.ldv, gv_off, kv0 + KT); }
-            asm volatile("" : "+v"(oacc[0]));
-        } else if constexpr (KT == 128) {
+        if (more) stage_load(Kb, a.ldk, gk_off, kv0 + KT);
+        if constexpr (KT == 128) {
             const bool two = kv0 + 64 < a.Nk;                // (uniform) keys 64.. of the tile exist
             f32x16 sa0, sa1, sb0, sb1;
             attn_scores<DH>(cur, qf, sa0, sa1, lo);
             if (two) attn_scores<DH>(cur + 64 * ROWB, qf, sb0, sb1, lo);
             __builtin_amdgcn_sched_barrier(0);
             attn_softmax_pv<DH>(cur + TILE, sa0, sa1, oacc, m_run, l_run, kv0, a.Nk, hh, c, lo);
-            if (fetch) { stage_store(nxt, sk_off); stage_load(Vb, a.ldv, gv_off, kv0 + KT); }
+            if (more) { stage_store(nxt, sk_off); stage_load(Vb, a.ldv, gv_off, kv0 + KT); }
             if (two) attn_softmax_pv<DH>(cur + TILE + 64 * ROWB, sb0, sb1, oacc, m_run, l_run, kv0 + 64, a.Nk, hh, c, lo);
         } else {
             attn_block<DH>(cur, cur + TILE, 0, qf, oacc, m_run, l_run, kv0, a.Nk, hh, c, lo);
-            if (fetch) { stage_store(nxt, sk_off); stage_load(Vb, a.ldv, gv_off, kv0 + KT); }
+            if (more) { stage_store(nxt, sk_off); stage_load(Vb, a.ldv, gv_off, kv0 + KT); }
             attn_block<DH>(cur, cur + TILE, 1, qf, oacc, m_run, l_run, kv0, a.Nk, hh, c, lo);
         }
-        if (fetch) stage_store(nxt + TILE, sv_off);
+        if (more) stage_store(nxt + TILE, sv_off);
         __syncthreads();
     };
     for (int t = 0; t < ntiles; t += 2) {
@@ -156,21 +204,12 @@ __global__ __launch_bounds__(256, (DH == 32 && ATT_STREAM32_KT == 128) ? 3 : 4) 
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
     if (OPROJ) {
-        // ---- fused output projection + gated residual (narrow blocks).  The workgroup's 128 x DH outputs are one
-        //      contiguous piece of the [B][H][Nq][Dh] buffer = R = 128/H whole rows of the (B*Nq, C) matrix the reference
-        //      reinterprets it as (quirk Q1): stage them in LDS as those rows (B operand), Wo fragments straight from
-        //      L2 (A operand; every workgroup reads the same 2*C*C bytes), each wave takes C/4 output channels. ----
+        // ---- fused output projection + gated residual (narrow blocks): the workgroup's R = 128/H rows of O' staged in the (idle) K/V
+        //      buffers, Wo fragments straight from L2 (A operand; every workgroup reads the same 2*C*C bytes), each wave takes C/4
+        //      output channels. ----
         const int H = a.H, C = H * DH, R = 128 / H;
         const int rowb = C * 2;
-        auto swzO = [&](int row) { return C == 128 ? (row & 15) : ((row >> 1) & 7); };
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {                        // DH == 32: one 32-wide d tile
-            const int flat = (wave * 32 + r) * DH + 8 * g + 4 * hh;
-            const int orow = flat / C, ocol = flat % C;
-            const bf16x4 pk = {(bf16_t)(oacc[0][4 * g + 0] * inv), (bf16_t)(oacc[0][4 * g + 1] * inv),
-                               (bf16_t)(oacc[0][4 * g + 2] * inv), (bf16_t)(oacc[0][4 * g + 3] * inv)};
-            *reinterpret_cast<bf16x4*>(smem + orow * rowb + (((ocol >> 3) ^ swzO(orow)) << 4) + (ocol & 7) * 2) = pk;
-        }
+        attn_q1_stage(smem, oacc[0], inv, wave, r, hh, C);
         __syncthreads();
         const int lrow = lane & 15, lq = lane >> 4;
         const int NT = C / 64, RT = R / 16, n0 = wave * (C / 4);         // (NT, RT) = (2, 2) at C = 128, (1, 4) at C = 64
@@ -185,7 +224,7 @@ __global__ __launch_bounds__(256, (DH == 32 && ATT_STREAM32_KT == 128) ? 3 : 4) 
             for (int rt = 0; rt < 4; ++rt)
                 if (rt < RT) {
                     const int orow = rt * 16 + lrow;
-                    of[rt] = *reinterpret_cast<const bf16x8*>(smem + orow * rowb + (((ks * 4 + lq) ^ swzO(orow)) << 4));
+                    of[rt] = *reinterpret_cast<const bf16x8*>(smem + orow * rowb + (((ks * 4 + lq) ^ attn_q1_swz(orow, C)) << 4));
                 }
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt)
@@ -209,6 +248,7 @@ __global__ __launch_bounds__(256, (DH == 32 && ATT_STREAM32_KT == 128) ? 3 : 4) 
                 float* xp = a.X + (xrow0 + orow) * a.ldx + ch;
                 const f32x4 b4 = *reinterpret_cast<const f32x4*>(a.bo + ch);
                 f32x4 xo = *reinterpret_cast<const f32x4*>(xp);
+                // x += gate * (acc + bo)  (own text, as in attn_oproj_resident_kernel: shared, that kernel contracted the update to FMAs at H = 2)
                 if (a.gate) {
                     const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.gate + (long)b * a.gate_sample_stride + ch);
 #pragma unroll
@@ -238,11 +278,7 @@ __global__ __launch_bounds__(256, (DH == 32 && ATT_STREAM32_KT == 128) ? 3 : 4) 
     for (int it = 0; it < (32 * LPR) / 64; ++it) {
         const int row = it * (64 / LPR) + lane / LPR, ch = lane % LPR;
         const bf16x8 v = *reinterpret_cast<const bf16x8*>(ost + row * ORS + ch * 16);
-#if ATT_ABL & 4
-        if (q0 + row < a.Nq && v[0] == (bf16_t)12345.0f) *reinterpret_cast<bf16x8*>(ob + (long)row * DH + ch * 8) = v;
-#else
         if (q0 + row < a.Nq) *reinterpret_cast<bf16x8*>(ob + (long)row * DH + ch * 8) = v;
-#endif
     }
 }
 
@@ -270,15 +306,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_resident_kernel(const AttnArg
     const bf16_t* Qb = a.Q + (long)b * a.q_batch_stride + head * DH;
     const bf16_t* Kb = a.K + (long)b * a.kv_batch_stride + head * DH;
     const bf16_t* Vb = a.V + (long)b * a.kv_batch_stride + head * DH;
-    auto swzK = [](int row) { return (DH == 64) ? ((row >> 1) & 7) : ((row >> 2) & 3); };
-    auto swzV = [](int row) { return (DH == 64) ? (((row >> 1) & 1) << 2) : 0; };
 
     // ---- load every key / value row of this head: thread -> (row = tid/CH + l*(256/CH), chunk = tid%CH); the
     //      source pointers and LDS offsets advance by constants (the swizzles repeat every 256/CH rows) ----
+    // (own text, as in attn_oproj_resident_kernel: a shared function for this loop changed that kernel's SGPR count at H = 4)
     {
         constexpr int RPL = 256 / CH;                                   // rows covered per pass (32 or 64)
         const int row0 = tid / CH, ch = tid % CH;
-        const int kofs = row0 * ROWB + ((ch ^ swzK(row0)) << 4), vofs = row0 * ROWB + ((ch ^ swzV(row0)) << 4);
+        const int kofs = row0 * ROWB + ((ch ^ attn_swz_k<DH>(row0)) << 4), vofs = row0 * ROWB + ((ch ^ attn_swz_v<DH>(row0)) << 4);
         const int npass = ntl * KT / RPL;
         for (int base = 0; base < npass; base += 4) {
             bf16x8 kreg[4], vreg[4];
@@ -312,13 +347,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_resident_kernel(const AttnArg
         const int q0 = qb * 128 + wave * 32;
         if (q0 >= a.Nq) continue;                                       // wave-uniform; no barrier below
         bf16x8 qf[NS];
-        {
-            int qrow = q0 + r;
-            qrow = qrow < a.Nq ? qrow : a.Nq - 1;
-            const bf16_t* qp = Qb + (long)qrow * a.ldq + 8 * hh;
-#pragma unroll
-            for (int s = 0; s < NS; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
-        }
+        attn_load_q<DH>(a, Qb, q0, r, hh, qf);
         f32x16 oacc[ND];
 #pragma unroll
         for (int d = 0; d < ND; ++d)
@@ -329,25 +358,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_resident_kernel(const AttnArg
         else
             for (int t = 0; t < ntl; ++t)
                 attn_tile<DH>(Ks + t * TILE, Vs + t * TILE, qf, oacc, m_run, l_run, t * KT, a.Nk, hh, c, lo);
-        // ---- normalise, stage through the wave's private LDS rows (XOR-swizzled chunks), store whole rows ----
-        const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-        const float inv = 1.0f / l_tot;
-#pragma unroll
-        for (int d = 0; d < ND; ++d)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int chn = d * 4 + g;                                // 16-B chunk; hh picks its 8-B half
-                const bf16x4 pk = {(bf16_t)(oacc[d][4 * g + 0] * inv), (bf16_t)(oacc[d][4 * g + 1] * inv),
-                                   (bf16_t)(oacc[d][4 * g + 2] * inv), (bf16_t)(oacc[d][4 * g + 3] * inv)};
-                *reinterpret_cast<bf16x4*>(ost + r * ROWB + ((chn ^ (r & (CH - 1))) << 4) + hh * 8) = pk;
-            }
-        bf16_t* ob = a.O + (((long)b * a.H + head) * a.Nq + q0) * DH;
-#pragma unroll
-        for (int it = 0; it < (32 * CH) / 64; ++it) {
-            const int row = it * (64 / CH) + lane / CH, ch = lane % CH;
-            const bf16x8 v = *reinterpret_cast<const bf16x8*>(ost + row * ROWB + ((ch ^ (row & (CH - 1))) << 4));
-            if (q0 + row < a.Nq) *reinterpret_cast<bf16x8*>(ob + (long)row * DH + ch * 8) = v;
-        }
+        attn_store_rows<DH>(a, ost, oacc, l_run, b, head, q0, lane);
     }
 }
 
@@ -391,33 +402,22 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_head_kernel(const AttnArgs a)
     static_assert(DH == 64 && NTL >= 1 && NTL <= 4, "attn_fwd_head_kernel: built for head dim 64 (8 pieces per 64-key tile = one per wave), <= 256 keys");
     typedef int i32x4 __attribute__((ext_vector_type(4)));
     i32x4 qi[NS];
-    {
+    {   // (not attn_load_q: these loads are asm, bound to the counted wait below and guarded by isa_lint.py R3)
         int qrow = q0 + r;
         qrow = qrow < a.Nq ? qrow : a.Nq - 1;
         const bf16_t* qp = Qb + (long)qrow * a.ldq + 8 * hh;
 #pragma unroll
-        for (int s = 0; s < NS; ++s) {
-#ifdef ATT_DBG_NOLOAD
-            qi[s] = (i32x4){lane, 1, 1, 1};
-            (void)qp;
-#else
+        for (int s = 0; s < NS; ++s)
             asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qi[s]) : "v"(qp + 16 * s) : "memory");
-#endif
-        }
     }
     {
         const int lr = lane / CH, cd = lane % CH;
         const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)Ks;
-#ifdef ATT_DBG_NOLOAD
-        for (int t = 0; t < 0; ++t) {
-#else
         for (int t = 0; t < ntl; ++t) {
-#endif
             const int p = t * 8 + wave;
             const int row = p * RPP + lr;
             const int krow = row < a.Nk ? row : a.Nk - 1;               // rows past Nk: P is exactly 0 there
-            const int sk = (row >> 1) & 7;
-            const int sv = ((row >> 1) & 1) << 2;
+            const int sk = attn_swz_k<DH>(row), sv = attn_swz_v<DH>(row);
             const bf16_t* ks = Kb + (long)krow * a.ldk + ((cd ^ sk) << 3);
             const bf16_t* vs = Vb + (long)krow * a.ldv + ((cd ^ sv) << 3);
             // (asm, not the builtin: with LDS-DMA it knows of in flight hipcc puts vmcnt(0) in front of the first ds_read_b64_tr of V)
@@ -450,33 +450,11 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_head_kernel(const AttnArgs a)
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();                                    // raw: __syncthreads() would drain vmcnt to 0 (the later tiles' pieces)
         __builtin_amdgcn_sched_barrier(0);
-#ifdef ATT_DBG_NOCOMPUTE
-        l_run += (float)qf[t & (NS - 1)][0];
-#else
         if (active) attn_tile_joint<DH>(Ks + t * TILE, Vs + t * TILE, qf, oacc, m_run, l_run, t * KT, a.Nk, hh, c, lo);
-#endif
     }
     __syncthreads();                                                    // every wave is done with K and V: their LDS becomes the output stage
     if (!active) return;
-    char* ost = rsmem + wave * (32 * ROWB);
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
-#pragma unroll
-    for (int d = 0; d < ND; ++d)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int chn = d * 4 + g;                                  // 16-B chunk; hh picks its 8-B half
-            const bf16x4 pk = {(bf16_t)(oacc[d][4 * g + 0] * inv), (bf16_t)(oacc[d][4 * g + 1] * inv),
-                               (bf16_t)(oacc[d][4 * g + 2] * inv), (bf16_t)(oacc[d][4 * g + 3] * inv)};
-            *reinterpret_cast<bf16x4*>(ost + r * ROWB + ((chn ^ (r & (CH - 1))) << 4) + hh * 8) = pk;
-        }
-    bf16_t* ob = a.O + (((long)b * a.H + head) * a.Nq + q0) * DH;
-#pragma unroll
-    for (int it = 0; it < (32 * CH) / 64; ++it) {
-        const int row = it * (64 / CH) + lane / CH, ch = lane % CH;
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(ost + row * ROWB + ((ch ^ (row & (CH - 1))) << 4));
-        if (q0 + row < a.Nq) *reinterpret_cast<bf16x8*>(ob + (long)row * DH + ch * 8) = v;
-    }
+    attn_store_rows<DH>(a, rsmem + wave * (32 * ROWB), oacc, l_run, b, head, q0, lane);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -486,13 +464,9 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_head_kernel(const AttnArgs a)
 // from L2: 64 KB of operands for 5 MFLOP, 4.2 GB of L2 traffic per launch at 1024 clouds next to 2.5 GB of HBM data.  Here one
 // workgroup owns a (cloud, head): K/V go to LDS once, each wave keeps its C/4 output channels of Wo as register fragments, and
 // the workgroup walks the head's query blocks (no barrier inside the attention; two per block around the 8 KB output stage).
-// ATT_OPROJ_FORM (tools/dbg A/B): 0 = the sequential 32-key chain of rounds 3-5 (3 waves per SIMD), 1 = the joint 64-key step (3 waves),
-// 2 = joint + pipelined across tiles (attn_head_pipelined: four score accumulators, 2 waves per SIMD)
-#ifndef ATT_OPROJ_FORM
-#define ATT_OPROJ_FORM 2
-#endif
+// The attention is the joint step pipelined across tiles (attn_head_pipelined: four score accumulators, 2 waves per SIMD).
 template <int H>   // heads: C = 32 H channels (2 or 4)
-__global__ __launch_bounds__(256, ATT_OPROJ_FORM == 2 ? 2 : 3) void attn_oproj_resident_kernel(const AttnArgs a, int ntl) {   // (the prefetched Q / residual registers do not fit 128 VGPRs)
+__global__ __launch_bounds__(256, 2) void attn_oproj_resident_kernel(const AttnArgs a, int ntl) {   // (the prefetched Q / residual registers do not fit 128 VGPRs)
     constexpr int DH = 32, KT = 64, ROWB = DH * 2, CH = ROWB / 16, NS = DH / 16, TILE = KT * ROWB;
     constexpr int C = H * DH, R = 128 / H, NT = C / 64, RT = R / 16, rowb = C * 2;
     extern __shared__ __attribute__((aligned(16))) char rsmem[];       // [K: ntl tiles][V: ntl tiles][O stage: R rows x C bf16 = 8 KB]
@@ -506,12 +480,11 @@ __global__ __launch_bounds__(256, ATT_OPROJ_FORM == 2 ? 2 : 3) void attn_oproj_r
     const bf16_t* Qb = a.Q + (long)b * a.q_batch_stride + head * DH;
     const bf16_t* Kb = a.K + (long)b * a.kv_batch_stride + head * DH;
     const bf16_t* Vb = a.V + (long)b * a.kv_batch_stride + head * DH;
-    auto swzK = [](int row) { return (row >> 2) & 3; };
-    auto swzO = [](int row) { return C == 128 ? (row & 15) : ((row >> 1) & 7); };
     {   // every key / value row of the head (rows past Nk repeat row Nk-1: their P is exactly 0)
+        // (own text, as in attn_fwd_resident_kernel: a shared function for this loop changed this kernel's SGPR count at H = 4)
         constexpr int RPL = 256 / CH;
         const int row0 = tid / CH, ch = tid % CH;
-        const int kofs = row0 * ROWB + ((ch ^ swzK(row0)) << 4), vofs = row0 * ROWB + (ch << 4);
+        const int kofs = row0 * ROWB + ((ch ^ attn_swz_k<DH>(row0)) << 4), vofs = row0 * ROWB + ((ch ^ attn_swz_v<DH>(row0)) << 4);
         const int npass = ntl * KT / RPL;
         for (int base = 0; base < npass; base += 4) {
             bf16x8 kreg[4], vreg[4];
@@ -548,13 +521,7 @@ __global__ __launch_bounds__(256, ATT_OPROJ_FORM == 2 ? 2 : 3) void attn_oproj_r
     // qb + 1 and the fp32 residual rows of block qb (read-modify-written by the epilogue) are requested at the head of block qb and land
     // under its attention; the projection bias is loaded once.  Before, each of the up to 16 blocks of a workgroup opened on a
     // dependent Q round trip and closed on a dependent residual round trip (~1.5 us each beside ~3 us of work).
-    auto load_q = [&](int qb, bf16x8 (&q)[NS]) {
-        int qrow = qb * 128 + wave * 32 + r;
-        qrow = qrow < a.Nq ? qrow : a.Nq - 1;                               // rows past the end: computed, never stored
-        const bf16_t* qp = Qb + (long)qrow * a.ldq + 8 * hh;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) q[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
-    };
+    auto load_q = [&](int qb, bf16x8 (&q)[NS]) { attn_load_q<DH>(a, Qb, qb * 128 + wave * 32, r, hh, q); };   // this wave's rows of query block qb
     f32x4 b4[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) b4[nt] = *reinterpret_cast<const f32x4*>(a.bo + n0 + nt * 16 + lq * 4);
@@ -577,27 +544,10 @@ __global__ __launch_bounds__(256, ATT_OPROJ_FORM == 2 ? 2 : 3) void attn_oproj_r
 #pragma unroll
         for (int i = 0; i < 16; ++i) oacc[0][i] = 0.f;
         float m_run = -INFINITY, l_run = 0.f;
-#if ATT_OPROJ_FORM == 2
         attn_head_pipelined<DH>(Ks, Vs, ntl, qf, oacc, m_run, l_run, a.Nk, hh, c, lo);
-#elif ATT_OPROJ_FORM == 1
-        for (int t = 0; t < ntl; ++t)
-            attn_tile_joint<DH>(Ks + t * TILE, Vs + t * TILE, qf, oacc, m_run, l_run, t * KT, a.Nk, hh, c, lo);
-#else
-        for (int t = 0; t < ntl; ++t)
-            attn_tile<DH>(Ks + t * TILE, Vs + t * TILE, qf, oacc, m_run, l_run, t * KT, a.Nk, hh, c, lo);
-#endif
         const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
         const float inv = 1.0f / l_tot;
-        // the workgroup's 128 x Dh outputs = R whole rows of the (B*Nq, C) matrix the reference reinterprets the head-major buffer
-        // as (quirk Q1): staged as those rows (B operand of the projection)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int flat = (wave * 32 + r) * DH + 8 * g + 4 * hh;
-            const int orow = flat / C, ocol = flat % C;
-            const bf16x4 pk = {(bf16_t)(oacc[0][4 * g + 0] * inv), (bf16_t)(oacc[0][4 * g + 1] * inv),
-                               (bf16_t)(oacc[0][4 * g + 2] * inv), (bf16_t)(oacc[0][4 * g + 3] * inv)};
-            *reinterpret_cast<bf16x4*>(Ost + orow * rowb + (((ocol >> 3) ^ swzO(orow)) << 4) + (ocol & 7) * 2) = pk;
-        }
+        attn_q1_stage(Ost, oacc[0], inv, wave, r, hh, C);
         __syncthreads();
         f32x4 pacc[NT][RT];
 #pragma unroll
@@ -610,7 +560,7 @@ __global__ __launch_bounds__(256, ATT_OPROJ_FORM == 2 ? 2 : 3) void attn_oproj_r
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 const int orow = rt * 16 + lrow;
-                of[rt] = *reinterpret_cast<const bf16x8*>(Ost + orow * rowb + (((ks * 4 + lq) ^ swzO(orow)) << 4));
+                of[rt] = *reinterpret_cast<const bf16x8*>(Ost + orow * rowb + (((ks * 4 + lq) ^ attn_q1_swz(orow, C)) << 4));
             }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
@@ -625,6 +575,7 @@ __global__ __launch_bounds__(256, ATT_OPROJ_FORM == 2 ? 2 : 3) void attn_oproj_r
                 if (orow >= valid_rows) continue;
                 float* xp = a.X + (xrow0 + orow) * a.ldx + ch;
                 f32x4 xo = xpre[nt][rt];
+                // x += gate * (acc + bo)  (own text, as in attn_fwd_kernel<32, true>: shared, this kernel contracted the update to FMAs at H = 2)
                 if (a.gate) {
                     const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.gate + (long)b * a.gate_sample_stride + ch);
 #pragma unroll
@@ -647,9 +598,8 @@ static int launch_resident(const AttnArgs* a, hipStream_t s) {
     const size_t lds = (size_t)2 * ntl * 64 * DH * 2 + 4 * 32 * DH * 2;
     LDT_ENSURE_LDS(&attn_fwd_resident_kernel<DH>, 81920, "attention");
     // query blocks of a head over `qsplit` workgroups until the launch has ~4 workgroups per CU (or one block each)
-    static const int qs_env = getenv("LDT_ATTN_QSPLIT") ? atoi(getenv("LDT_ATTN_QSPLIT")) : 0;      // tools/dbg
     const long heads = (long)a->B * a->H, nqb = (a->Nq + 127) / 128;
-    long qsplit = qs_env > 0 ? qs_env : (4L * LDT_NUM_CUS + heads - 1) / heads;
+    long qsplit = (4L * LDT_NUM_CUS + heads - 1) / heads;
     qsplit = qsplit < 1 ? 1 : (qsplit > nqb ? nqb : qsplit);
     LDT_REQUIRE(heads * qsplit < (1L << 31), LDT_ESHAPE, "attention: grid too large");
     hipLaunchKernelGGL(attn_fwd_resident_kernel<DH>, dim3((unsigned)(heads * qsplit)), dim3(256), lds, s, *a, ntl, (int)qsplit);
@@ -674,22 +624,25 @@ static int launch_head(const AttnArgs* a, hipStream_t s) {
     }
 }
 
+// what both launch entries ask of Q / K / V: rows and batch strides in whole 16-byte pieces
+static bool attn_qkv_aligned(const AttnArgs* a) {
+    return a->ldq % 8 == 0 && a->ldk % 8 == 0 && a->ldv % 8 == 0 && a->q_batch_stride % 8 == 0 && a->kv_batch_stride % 8 == 0 &&
+           ldt_aligned16(a->Q) && ldt_aligned16(a->K) && ldt_aligned16(a->V);
+}
+
 int ldt_attn_oproj_launch(const AttnArgs* a, int dh, hipStream_t s) {
     LDT_REQUIRE(a->B > 0 && a->H > 0 && a->Nq > 0 && a->Nk > 0, LDT_ESHAPE, "attention_oproj: empty problem");
     LDT_REQUIRE(dh == 32 && (a->H == 2 || a->H == 4), LDT_ESHAPE,
                 "attention_oproj: the fused kernel is built for head dim 32 with 2 or 4 heads (C = 64 / 128), got Dh=%d H=%d", dh, a->H);
     LDT_REQUIRE(a->Nq % a->H == 0, LDT_ESHAPE, "attention_oproj: Nq=%d must be a multiple of H=%d (rows of the reinterpreted output)", a->Nq, a->H);
-    LDT_REQUIRE(a->ldq % 8 == 0 && a->ldk % 8 == 0 && a->ldv % 8 == 0 && a->q_batch_stride % 8 == 0 && a->kv_batch_stride % 8 == 0 &&
-                ldt_aligned16(a->Q) && ldt_aligned16(a->K) && ldt_aligned16(a->V) && ldt_aligned16(a->Wo) && ldt_aligned16(a->bo) &&
+    LDT_REQUIRE(attn_qkv_aligned(a) && ldt_aligned16(a->Wo) && ldt_aligned16(a->bo) &&
                 ldt_aligned16(a->X) && a->ldx % 4 == 0 && a->ldx >= a->H * dh && (!a->gate || (ldt_aligned16(a->gate) && a->gate_sample_stride % 4 == 0)),
                 LDT_EALIGN, "attention_oproj: operands must be 16-byte aligned");
     const long nqb = (a->Nq + 127) / 128, groups = ((long)a->B * a->H + 7) / 8;
     LDT_REQUIRE(groups * 8 * nqb < (1L << 31), LDT_ESHAPE, "attention_oproj: grid too large");
     // several query blocks per head, few keys, a (cloud, head) pair per CU or more: K/V + Wo resident, one workgroup per pair
     // (config C4, 1024 clouds: decode 16.2 -> 15.3 ms at 128 clouds per call, 16.0 -> 14.5 at 512; encode 34.8 -> 32.9 ms)
-    static const int res_env = getenv("LDT_ATTN_OPROJ_RESIDENT") ? atoi(getenv("LDT_ATTN_OPROJ_RESIDENT")) : -1;   // 0 / 1 force (tools/dbg)
-    const bool fits = a->Nk <= 512;
-    if (fits && (res_env == 1 || (res_env != 0 && nqb >= 2 && (long)a->B * a->H >= 256))) {
+    if (a->Nk <= 512 && nqb >= 2 && (long)a->B * a->H >= 256) {
         const int ntl = (a->Nk + 63) / 64;
         const size_t lds = (size_t)2 * ntl * 64 * 64 + 8192;
         if (a->H == 4) {
@@ -711,20 +664,17 @@ int ldt_attn_route(int B, int H, int Nq, int Nk, int dh) {
     // Short sequences (one 128-row query block, keys/values of a head fit 64 KiB of LDS): resident kernel — K/V
     // loaded once, no per-tile barrier (measured 9.0 vs 9.7 us at T=32).  Longer query sets run the streaming
     // kernel, which spreads (b,h,q-block) over more workgroups (35 vs 37 us at T=256, 46 vs 56 us at 2048x256).
-    static const int force = getenv("LDT_ATTN_FORCE") ? atoi(getenv("LDT_ATTN_FORCE")) : 0;   // 1 stream, 2 resident, 3 whole-head (tools/dbg)
     const bool fits = (long)Nk * dh <= 256 * 64;
-    if (fits && (force == 2 || (force == 0 && Nq <= 128))) return 1;
+    if (fits && Nq <= 128) return 1;
     // 129..256 queries of a Dh = 64 head (the Score at T = 256): the whole-head 8-wave kernel
-    if (fits && dh == 64 && Nq <= 256 && (long)B * H < (1L << 31) && (force == 3 || (force == 0 && Nq > 128))) return 2;
+    if (fits && dh == 64 && Nq <= 256 && (long)B * H < (1L << 31)) return 2;
     return 0;
 }
 
 int ldt_attn_launch(const AttnArgs* a, int dh, hipStream_t s) {
     LDT_REQUIRE(a->B > 0 && a->H > 0 && a->Nq > 0 && a->Nk > 0, LDT_ESHAPE, "attention: empty problem B=%d H=%d Nq=%d Nk=%d", a->B, a->H, a->Nq, a->Nk);
     LDT_REQUIRE(dh == 32 || dh == 64, LDT_ESHAPE, "attention: head dim %d not built (32, 64)", dh);
-    LDT_REQUIRE(a->ldq % 8 == 0 && a->ldk % 8 == 0 && a->ldv % 8 == 0 && a->q_batch_stride % 8 == 0 && a->kv_batch_stride % 8 == 0 &&
-                ldt_aligned16(a->Q) && ldt_aligned16(a->K) && ldt_aligned16(a->V) && ldt_aligned16(a->O), LDT_EALIGN,
-                "attention: Q/K/V rows must be 16-byte aligned");
+    LDT_REQUIRE(attn_qkv_aligned(a) && ldt_aligned16(a->O), LDT_EALIGN, "attention: Q/K/V rows must be 16-byte aligned");
     LDT_REQUIRE(a->H <= 65535 && a->B <= 65535, LDT_ESHAPE, "attention: grid too large");
     const int route = ldt_attn_route(a->B, a->H, a->Nq, a->Nk, dh);
     if (route == 1) return dh == 64 ? launch_resident<64>(a, s) : launch_resident<32>(a, s);

@@ -26,22 +26,51 @@ struct AttnLaneOffs {
     }
 };
 
-// One 64-key tile for a wave (32 query rows, one per lane & 31; the keys of a 32-key block split over the two
-// half-waves), processed as two 32-key blocks: S^T = K Q^T (4 or 2 MFMAs), online softmax, O^T += V^T P^T.
-//   * The running reference m_run is moved (and O, l rescaled) only when some row's block maximum exceeds it by more
-//     than 2^ATT_THR (guide T13 "defer-max"): P = 2^((s - m_run) c) then stays <= 2^ATT_THR, exact in fp32 sums and
-//     with bf16's full relative precision, and the result O / l is the same quotient.  After the first block the
-//     branch is rarely taken, which removes the per-block alpha / rescale work (16 v_pk_mul at Dh = 64).
-//   * VALU-lean: packed fp32 FMA/ADD (two scores per instruction), max3 row maxima, masking code only on ragged tiles.
+// Defer-max (guide T13), shared by attn_block and attn_softmax_pv: the running reference m_run is moved to max(m_run, mx) (and O, l
+// rescaled) only when some row's maximum mx of this step exceeds it by more than 2^ATT_THR: P = 2^((s - m_run) c) then stays <= 2^ATT_THR,
+// exact in fp32 sums and with bf16's full relative precision, and the result O / l is the same quotient.  After the first step the branch
+// is rarely taken, which removes the per-step alpha / rescale work (16 v_pk_mul at Dh = 64).
 #define ATT_THR 6.0f
-#ifndef ATT_SCALAR_SOFTMAX
-#define ATT_SCALAR_SOFTMAX 0
-#endif
+template <int DH>
+__device__ __forceinline__ void attn_defer_max(float mx, f32x16 (&oacc)[DH / 32], float& m_run, float& l_run, float c) {
+    if (__builtin_amdgcn_ballot_w64((mx - m_run) * c > ATT_THR) != 0) {   // wave-uniform; always on the first step (m_run = -inf)
+        const float m_new = fmaxf(m_run, mx);
+        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
+        l_run *= alpha;
+        m_run = m_new;
+        const f32x2 a2 = {alpha, alpha};
+#pragma unroll
+        for (int d = 0; d < DH / 32; ++d)
+#pragma unroll
+            for (int i = 0; i < 16; i += 2) {
+                f32x2 o = {oacc[d][i], oacc[d][i + 1]};
+                o *= a2;                                         // v_pk_mul_f32
+                oacc[d][i] = o[0]; oacc[d][i + 1] = o[1];
+            }
+    }
+}
+// One 16-key slice of O^T += V^T P^T, shared by the same two: the V^T fragments by transposed LDS reads of the row-major V tile (`Vs16`: the
+// slice's first row).
+template <int DH>
+__device__ __forceinline__ void attn_pv_slice(const char* Vs16, const bf16x8& pf, f32x16 (&oacc)[DH / 32], const AttnLaneOffs<DH>& lo) {
+    constexpr int ROWB = DH * 2;
+#pragma unroll
+    for (int d = 0; d < DH / 32; ++d) {
+        const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(Vs16 + lo.v[d]));
+        const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(Vs16 + 8 * ROWB + lo.v[d]));
+        const bf16x8 vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+        oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[d], 0, 0, 0);
+    }
+}
+
+// One 32-key block (kt = 0 / 1) of a 64-key tile for a wave (32 query rows, one per lane & 31; the keys of the block split over the two
+// half-waves): S^T = K Q^T (4 or 2 MFMAs), online softmax, O^T += V^T P^T.  VALU-lean: packed fp32 FMA/ADD (two scores per instruction),
+// max3 row maxima, masking code only on ragged tiles.  attn_tile = both blocks, one after the other.
 template <int DH>
 __device__ __forceinline__ void attn_block(const char* Kt, const char* Vt, const int kt, const bf16x8 (&qf)[DH / 16], f32x16 (&oacc)[DH / 32],
                                            float& m_run, float& l_run, int kv0, int Nk, int hh, float c,
                                            const AttnLaneOffs<DH>& lo) {
-    constexpr int ROWB = DH * 2, ND = DH / 32, NS = DH / 16;
+    constexpr int ROWB = DH * 2, NS = DH / 16;
     {
         f32x16 sacc;
 #pragma unroll
@@ -62,21 +91,7 @@ __device__ __forceinline__ void attn_block(const char* Kt, const char* Vt, const
 #pragma unroll
         for (int i = 2; i < 16; i += 2) mx = __builtin_fmaxf(__builtin_fmaxf(mx, sacc[i]), sacc[i + 1]);   // -> v_max3_f32
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        if (__builtin_amdgcn_ballot_w64((mx - m_run) * c > ATT_THR) != 0) {   // wave-uniform; always on the first block (m_run = -inf)
-            const float m_new = fmaxf(m_run, mx);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-            l_run *= alpha;
-            m_run = m_new;
-            const f32x2 a2 = {alpha, alpha};
-#pragma unroll
-            for (int d = 0; d < ND; ++d)
-#pragma unroll
-                for (int i = 0; i < 16; i += 2) {
-                    f32x2 o = {oacc[d][i], oacc[d][i + 1]};
-                    o *= a2;                                     // v_pk_mul_f32
-                    oacc[d][i] = o[0]; oacc[d][i + 1] = o[1];
-                }
-        }
+        attn_defer_max<DH>(mx, oacc, m_run, l_run, c);
         const f32x2 c2 = {c, c}, nmc2 = {-m_run * c, -m_run * c};
         f32x2 ps2 = {0.f, 0.f};
         bf16x8 pf[2];
@@ -92,17 +107,8 @@ __device__ __forceinline__ void attn_block(const char* Kt, const char* Vt, const
             pf[i >> 3][(i & 7) + 1] = (bf16_t)pv[1];
         }
         l_run += ps2[0] + ps2[1];
-        // O^T += V^T · P^T : V^T fragments by transposed LDS reads of the row-major V tile
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-            for (int d = 0; d < ND; ++d) {
-                const char* base = Vt + (kt * 32 + 16 * s2) * ROWB;
-                const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(base + lo.v[d]));
-                const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(base + 8 * ROWB + lo.v[d]));
-                const bf16x8 vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[s2], oacc[d], 0, 0, 0);
-            }
+        for (int s2 = 0; s2 < 2; ++s2) attn_pv_slice<DH>(Vt + (kt * 32 + 16 * s2) * ROWB, pf[s2], oacc, lo);
     }
 }
 template <int DH>
@@ -117,7 +123,7 @@ __device__ __forceinline__ void attn_tile(const char* Kt, const char* Vt, const 
 // independent accumulators: the second chain runs in the first one's MFMA latency), one row maximum / one defer-max test per
 // tile, 32 exponentials with no dependence between them, then the four 16-key slices of O^T += V^T P^T.  attn_block's
 // per-wave dependency chain (LDS read -> 4 dependent MFMAs -> max -> exp -> cvt -> MFMAs, twice per tile) is what bounds the
-// other two kernels at 4 waves per SIMD (tools/dbg/attn_ablate.sh: 26.7 us with the loads compiled out, 23.4 us with the
+// other two kernels at 4 waves per SIMD (round-4 ablation builds: 26.7 us with the loads compiled out, 23.4 us with the
 // compute compiled out, 35.9 us together); here the chain per tile is less than half as long.
 // The two halves of the joint tile step, separately callable: a caller that keeps TWO score accumulator pairs can issue the S^T MFMAs of key
 // tile t + 1 before the softmax of tile t (the matrix pipe then works under that wave's own softmax VALU: gemm_qkv_attn256_kernel).
@@ -137,7 +143,7 @@ __device__ __forceinline__ void attn_scores(const char* Kt, const bf16x8 (&qf)[D
 template <int DH>
 __device__ __forceinline__ void attn_softmax_pv(const char* Vt, f32x16& s0, f32x16& s1, f32x16 (&oacc)[DH / 32], float& m_run, float& l_run,
                                                 int kv0, int Nk, int hh, float c, const AttnLaneOffs<DH>& lo) {
-    constexpr int ROWB = DH * 2, ND = DH / 32;
+    constexpr int ROWB = DH * 2;
     if (kv0 + 64 > Nk) {                                             // ragged tile: mask keys >= Nk
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -150,39 +156,8 @@ __device__ __forceinline__ void attn_softmax_pv(const char* Vt, f32x16& s0, f32x
 #pragma unroll
     for (int i = 1; i < 16; ++i) mx = __builtin_fmaxf(__builtin_fmaxf(mx, s0[i]), s1[i]);   // -> v_max3_f32
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    if (__builtin_amdgcn_ballot_w64((mx - m_run) * c > ATT_THR) != 0) {   // wave-uniform; always on the first tile (m_run = -inf)
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
-        l_run *= alpha;
-        m_run = m_new;
-        const f32x2 a2 = {alpha, alpha};
-#pragma unroll
-        for (int d = 0; d < ND; ++d)
-#pragma unroll
-            for (int i = 0; i < 16; i += 2) {
-                f32x2 o = {oacc[d][i], oacc[d][i + 1]};
-                o *= a2;                                             // v_pk_mul_f32
-                oacc[d][i] = o[0]; oacc[d][i + 1] = o[1];
-            }
-    }
+    attn_defer_max<DH>(mx, oacc, m_run, l_run, c);
     bf16x8 pf[4];
-#if ATT_SCALAR_SOFTMAX                                               /* tools/dbg A/B: scalar v_fma / v_add instead of the packed forms */
-    const float nmc = -m_run * c;
-    float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; i += 2) {
-        float ea0 = __builtin_fmaf(s0[i], c, nmc), ea1 = __builtin_fmaf(s0[i + 1], c, nmc);
-        float eb0 = __builtin_fmaf(s1[i], c, nmc), eb1 = __builtin_fmaf(s1[i + 1], c, nmc);
-        asm volatile("" : "+v"(ea0), "+v"(ea1), "+v"(eb0), "+v"(eb1));   // (keeps hipcc's SLP pass from re-packing the four)
-        const float pa0 = __builtin_amdgcn_exp2f(ea0), pa1 = __builtin_amdgcn_exp2f(ea1);
-        const float pb0 = __builtin_amdgcn_exp2f(eb0), pb1 = __builtin_amdgcn_exp2f(eb1);
-        q0 += pa0; q1 += pa1; q2 += pb0; q3 += pb1;
-        asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3));
-        pf[i >> 3][i & 7] = (bf16_t)pa0;       pf[i >> 3][(i & 7) + 1] = (bf16_t)pa1;
-        pf[2 + (i >> 3)][i & 7] = (bf16_t)pb0; pf[2 + (i >> 3)][(i & 7) + 1] = (bf16_t)pb1;
-    }
-    l_run += (q0 + q1) + (q2 + q3);
-#else
     const f32x2 c2 = {c, c}, nmc2 = {-m_run * c, -m_run * c};
     f32x2 psa = {0.f, 0.f}, psb = {0.f, 0.f};
 #pragma unroll
@@ -197,17 +172,8 @@ __device__ __forceinline__ void attn_softmax_pv(const char* Vt, f32x16& s0, f32x
         pf[2 + (i >> 3)][i & 7] = (bf16_t)pb[0]; pf[2 + (i >> 3)][(i & 7) + 1] = (bf16_t)pb[1];
     }
     l_run += (psa[0] + psa[1]) + (psb[0] + psb[1]);
-#endif
 #pragma unroll
-    for (int s2 = 0; s2 < 4; ++s2)                                   // 16-key slices: block s2 >> 1, half s2 & 1
-#pragma unroll
-        for (int d = 0; d < ND; ++d) {
-            const char* base = Vt + 16 * s2 * ROWB;
-            const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(base + lo.v[d]));
-            const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(base + 8 * ROWB + lo.v[d]));
-            const bf16x8 vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-            oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[s2], oacc[d], 0, 0, 0);
-        }
+    for (int s2 = 0; s2 < 4; ++s2) attn_pv_slice<DH>(Vt + 16 * s2 * ROWB, pf[s2], oacc, lo);   // 16-key slices: block s2 >> 1, half s2 & 1
 }
 
 // A head's resident K / V tiles (ntl x 64 keys in LDS) for one wave's 32 query rows, software-pipelined ACROSS tiles: the S^T MFMAs of tile
