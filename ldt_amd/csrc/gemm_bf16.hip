@@ -243,10 +243,6 @@ GemmRoute ldt_gemm_decide(int epi, const GemmArgs* a, int granule) {
         r.tiles_per_wg = Tile256List::max_count(tm, tn, r.grid);        // the kernels' own tile list: the one-tile forms run only where it says so
         r.family = r.tiles_per_wg == 1 ? GEMM_ROUTE_256_ONE : GEMM_ROUTE_256_MULTI;
     };
-    auto take_mid = [&](int shape) {
-        r.family = GEMM_ROUTE_MID; r.bm = shape >> 16; r.bn = shape & 0xffff; r.tiles_per_wg = 1;
-        r.grid = ((a->M + r.bm - 1) / r.bm) * (a->N / r.bn);
-    };
     if (granule) {
         // LN-folded forms.  Large batches: the 256-tile kernel (statistics per 256 columns).  Small batches: the mid-size tile kernel
         // (statistics per 32 columns), when it takes the problem in a folded form.
@@ -254,8 +250,7 @@ GemmRoute ldt_gemm_decide(int epi, const GemmArgs* a, int granule) {
         if (!producer && epi != EPI_BF16 && epi != EPI_GELU_BF16) return r;
         if (granule == 32) {
             if (a->M % 128 != 0 || a->N % 64 != 0 || a->K < 128) return r;
-            const int shape = ldt_gemm_mid_lnfold_shape(epi, a);
-            if (shape) take_mid(shape);
+            ldt_gemm_mid_route(epi, producer ? FOLD_PRODUCER : FOLD_CONSUMER, a, &r);
         } else if (granule == 256) {
             if (a->M % 256 != 0 || a->N % 256 != 0 || a->K < 256 || !ldt_gemm256_takes(epi, a)) return r;
             if (!producer && (a->K % 256 != 0 || a->K > 1024)) return r;
@@ -274,8 +269,7 @@ GemmRoute ldt_gemm_decide(int epi, const GemmArgs* a, int granule) {
     if (force == 0 && !big) {
         // mid-size problems (gemm_mid.hip): 128 x 256 / 128 x 192 / 128 x 128 / 64 x 128 / 64 x 64 tiles with dedicated loader waves, when
         // the 256^2 persistent kernel would leave CUs idle — the 1-4k-row batches
-        const int shape = ldt_gemm_mid_shape(epi, a);
-        if (shape) { take_mid(shape); return r; }
+        if (ldt_gemm_mid_route(epi, FOLD_NONE, a, &r)) return r;
     }
     if ((force == 256 || (force == 0 && big)) && ldt_gemm256_takes(epi, a)) { take_256(); return r; }
     // v1 tile shape: the largest of 128x128 / 128x64 / 64x64 that still gives every CU two tiles
@@ -325,7 +319,7 @@ int ldt_gemm_lnfold_launch(int epi, const GemmArgs* a, hipStream_t stream) {
                     "gemm_lnfold: producer needs xs / ln_scale / stats_out (16-byte aligned)");
         const GemmRoute r = ldt_gemm_decide(epi, a, v1 ? 32 : 256);
         if (v1) {
-            if (r.family == GEMM_ROUTE_MID) return ldt_gemm_mid_lnfold_launch(epi, (r.bm << 16) | r.bn, a, stream);   // mid-size tile kernel (gemm_mid.hip)
+            if (r.family == GEMM_ROUTE_MID) return ldt_gemm_mid_launch(epi, FOLD_PRODUCER, a, r, stream);   // mid-size tile kernel (gemm_mid.hip)
             ldt_set_error("gemm_lnfold: statistics per 32 columns are the mid-size tile kernel's; it does not take M=%d N=%d K=%d as a producer", a->M, a->N, a->K);
             return LDT_ESHAPE;
         }
@@ -339,7 +333,7 @@ int ldt_gemm_lnfold_launch(int epi, const GemmArgs* a, hipStream_t stream) {
     const GemmRoute r = ldt_gemm_decide(epi, a, v1 ? 32 : 256);
     if (v1) {
         LDT_REQUIRE(a->stats_parts <= 32, LDT_ESHAPE, "gemm_lnfold (v1 route): K=%d > 1024 input channels", a->K);
-        if (r.family == GEMM_ROUTE_MID) return ldt_gemm_mid_lnfold_launch(epi, (r.bm << 16) | r.bn, a, stream);
+        if (r.family == GEMM_ROUTE_MID) return ldt_gemm_mid_launch(epi, FOLD_CONSUMER, a, r, stream);
         ldt_set_error("gemm_lnfold: statistics per 32 columns are the mid-size tile kernel's; it does not take M=%d N=%d K=%d as a consumer", a->M, a->N, a->K);
         return LDT_ESHAPE;
     }
@@ -361,7 +355,7 @@ int ldt_gemm_launch(int epi, const GemmArgs* a, hipStream_t stream) {
     LDT_REQUIRE(a->ldo % 4 == 0 && ldt_aligned16(a->out), LDT_EALIGN, "gemm: out must be 16-byte aligned, ldo%%4==0 (ldo=%ld)", a->ldo);
     if (const int rc = gemm_check_epilogue_operands("gemm", epi, a)) return rc;
     const GemmRoute r = ldt_gemm_decide(epi, a, 0);
-    if (r.family == GEMM_ROUTE_MID) return ldt_gemm_mid_launch(epi, (r.bm << 16) | r.bn, a, stream);
+    if (r.family == GEMM_ROUTE_MID) return ldt_gemm_mid_launch(epi, FOLD_NONE, a, r, stream);
     if (r.family == GEMM_ROUTE_256_ONE || r.family == GEMM_ROUTE_256_MULTI) return ldt_gemm256_launch(epi, FOLD_NONE, a, r, stream);
     LDT_REQUIRE(r.family == GEMM_ROUTE_V1, LDT_ESHAPE, "gemm: no kernel takes M=%d N=%d K=%d", a->M, a->N, a->K);
     const int shape = r.v1_shape;

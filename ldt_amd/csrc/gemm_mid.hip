@@ -30,9 +30,14 @@
 //     EPI_F32, EPI_BF16, EPI_GELU_BF16, EPI_RESID_F32 (gate per step and/or per sample), and the LN-folded producer / consumer forms.
 //   * tile order: XCD-aware bijective remap; column-major inside an XCD's chunk (an XCD reads its own slice of W — cold in HBM every
 //     step — exactly once, and shares the small X panel set through L2 / Infinity Cache).
+// Said once each: MID_FORMS (the built forms: the shape rule's candidates AND the dispatch), mid_launch (the launch sequence of all of them),
+// mid_attn_core (the attention of both fused epilogues), MidFoldFinish (the LN-folded consumer finish), one K-tile body per main loop (instantiated
+// for the loop and for the peeled last K-tile), mid_next_slot / mid_wait_tiles.  One switch: LDT_GEMM_MID=0 turns the family off; -DMID_STAMPS is the
+// timing instrument of tools/dbg/mid_stamps.py.  What a change here may and may not do to the code generation: profiles/gemm_mid_refactor_codegen.txt.
 #include <stdlib.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "kernels.h"
 
@@ -96,6 +101,17 @@ __device__ __forceinline__ void mid_interleave() {
 
 template <int N>
 __device__ __forceinline__ void mid_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// the loader's counted wait: `ahead` (0 .. NS - 2) K-tiles of PPW requests each may stay in flight -> vmcnt(ahead * PPW) as an immediate
+template <int NS, int PPW>
+__device__ __forceinline__ void mid_wait_tiles(int ahead) {
+    if (NS >= 6 && ahead >= 4) mid_wait_vmcnt<(NS >= 6 ? 4 : 0) * PPW>();
+    else if (NS >= 5 && ahead == 3) mid_wait_vmcnt<(NS >= 5 ? 3 : 0) * PPW>();
+    else if (ahead >= 2) mid_wait_vmcnt<2 * PPW>();
+    else if (ahead == 1) mid_wait_vmcnt<PPW>();
+    else mid_wait_vmcnt<0>();
+}
+template <int NS>
+__device__ __forceinline__ int mid_next_slot(int slot) { return slot + 1 == NS ? 0 : slot + 1; }   // ring-slot advance (loader and compute waves alike)
 
 // tools/dbg build (-DMID_STAMPS): wall-clock stamps (s_memrealtime, 10 ns) of wave 0 (compute) and wave 4 (loader) of every workgroup, kept in a
 // VGPR (lane i = stamp i) and stored once at the wave's end -> g_mid_stamps[workgroup][role][64]; tools/dbg/mid_stamps.py reads them
@@ -116,7 +132,7 @@ extern "C" int ldt_dbg_mid_stamps(void* p) { return (int)hipMemcpyToSymbol(HIP_S
 __device__ __forceinline__ int mid_attn_col(int c, int h, int hidden) { return (c >> 6) * hidden + h * 64 + (c & 63); }
 
 template <int BM, int BN, int FOLD, int ATTN>
-__device__ __forceinline__ void mid_loader(const GemmArgs& a, char* smem, int lw, int lane, int m0, int n0, int kbase, int nkt, int step) {
+__device__ __forceinline__ void mid_loader(const GemmArgs& a, char* smem, int lw, int lane, int m0, int n0, int nkt, int step) {
     using C = MidCfg<BM, BN>;
     // piece = 8 rows x 128 B; lane -> row (lane >> 3), LDS position lane & 7 holds global chunk (lane & 7) ^ ((row >> 1) & 7).
     // Addresses = a wave-uniform base (tile origin + K-tile, advanced by scalar adds) + per-lane 32-bit byte offsets that never change
@@ -134,8 +150,8 @@ __device__ __forceinline__ void mid_loader(const GemmArgs& a, char* smem, int lw
         const int rr = ATTN == MID_ATTN_SELF ? mid_attn_col(r, n0 / BN, a.N / 3) : (n0 + r < a.N ? r : a.N - 1 - n0);
         wo[q] = rr * (int)a.ldw * 2 + (((lane & 7) ^ ((r >> 1) & 7)) << 4);
     }
-    const char* xbase = reinterpret_cast<const char*>(a.X + (long)m0 * a.ldx + kbase);
-    const char* wbase = reinterpret_cast<const char*>(a.W + (ATTN == MID_ATTN_SELF ? 0L : (long)n0 * a.ldw) + kbase);
+    const char* xbase = reinterpret_cast<const char*>(a.X + (long)m0 * a.ldx);
+    const char* wbase = reinterpret_cast<const char*>(a.W + (ATTN == MID_ATTN_SELF ? 0L : (long)n0 * a.ldw));
     auto issue = [&](int slot) {                         // the K-tile the bases stand at -> stage `slot`; then advance one K-tile
         char* st = smem + slot * C::STAGE;
 #pragma unroll
@@ -242,16 +258,12 @@ __device__ __forceinline__ void mid_loader(const GemmArgs& a, char* smem, int lw
         // K-tile kt+1 landed: the K-tiles issued after it are kt+2 .. min(kt + NS - 1, nkt - 1) (kt + NS goes out past the barrier)
         const int last = kt + C::NS - 1 < nkt - 1 ? kt + C::NS - 1 : nkt - 1;
         const int ahead = last - (kt + 1);               // 0 .. NS - 2
-        if (C::NS >= 6 && ahead >= 4) mid_wait_vmcnt<(C::NS >= 6 ? 4 : 0) * C::PPW>();
-        else if (C::NS >= 5 && ahead == 3) mid_wait_vmcnt<(C::NS >= 5 ? 3 : 0) * C::PPW>();
-        else if (ahead >= 2) mid_wait_vmcnt<2 * C::PPW>();
-        else if (ahead == 1) mid_wait_vmcnt<C::PPW>();
-        else mid_wait_vmcnt<0>();
+        mid_wait_tiles<C::NS, C::PPW>(ahead);
         MID_STAMP(5 + 3 * kt);
         MID_BARRIER();                                   // barrier kt: compute waves are past their last read of K-tile kt
         MID_STAMP(6 + 3 * kt);
         if (kt + C::NS < nkt) issue(slot);               // K-tile kt+NS -> the stage K-tile kt has left
-        slot = slot + 1 == C::NS ? 0 : slot + 1;
+        slot = mid_next_slot<C::NS>(slot);
     }
 #ifdef MID_STAMPS
     if (lw == 0) MID_STAMP_FLUSH(1);
@@ -278,6 +290,28 @@ __device__ __forceinline__ float mid_oct_sum(float v) {
     return v;
 }
 
+// LN-folded consumer finish, y = rstd acc + (-mean rstd S + C) (the bias is inside C), from what the loader waves left in the staging tails
+// (`tails` = the staging areas' base): this wave's S | C columns — a lane's 4 consecutive columns of each of its NT 16-column tiles, wcol = the
+// wave's first column inside the tile, lchk = lane >> 4 — and a row's (rstd, -mean rstd).
+template <int NT>
+struct MidFoldFinish {
+    f32x4 s4[NT], c4[NT];
+    __device__ __forceinline__ void fetch(const char* tails, int wcol, int lchk) {
+#pragma unroll
+        for (int ni = 0; ni < NT; ++ni) {
+            const int c = wcol + ni * 16 + lchk * 4;
+            s4[ni] = *reinterpret_cast<const f32x4*>(tails + MID_S_OFF + c * 4);
+            c4[ni] = *reinterpret_cast<const f32x4*>(tails + MID_C_OFF + c * 4);
+        }
+    }
+    static __device__ __forceinline__ f32x2 row(const char* tails, int r) { return *reinterpret_cast<const f32x2*>(tails + MID_RS_OFF + r * 8); }
+    __device__ __forceinline__ f32x4 apply(f32x2 rn, int ni, f32x4 v) const {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = rn[0] * v[r] + (rn[1] * s4[ni][r] + c4[ni][r]);
+        return v;
+    }
+};
+
 template <int EPI, int BM, int BN, int FOLD>
 __device__ __forceinline__ void mid_epilogue(const GemmArgs& a, f32x4 (&acc)[MidCfg<BM, BN>::NT][MidCfg<BM, BN>::MT], int m0, int nb, int wn, int lane,
                                              char* reg, const char* stage_base, const f32x4 (&rpre)[MidCfg<BM, BN>::MT][MidCfg<BM, BN>::NT <= 2 ? MidCfg<BM, BN>::NT : 1], int step) {
@@ -292,26 +326,17 @@ __device__ __forceinline__ void mid_epilogue(const GemmArgs& a, f32x4 (&acc)[Mid
         constexpr int CHK = NT * 2;                      // 16-B chunks per row (8 | 6 | 4)
         constexpr int CPR = NT <= 2 ? 4 : 8;             // lanes per row (a power of two; NT = 3: lanes 6, 7 of each octet idle, NT = 1: lanes 2, 3 of each quad)
         constexpr int RPI = 64 / CPR;                    // rows per store instruction (8 | 16)
-        f32x4 s4[NT];
-        if constexpr (FOLD == MID_FOLD_CONSUMER) {       // this wave's columns of the S | C slices the loader waves left in the staging tails
-#pragma unroll
-            for (int ni = 0; ni < NT; ++ni) {
-                const int c = wn * (BN / 4) + ni * 16 + lchk * 4;
-                s4[ni] = *reinterpret_cast<const f32x4*>(stage_base + MID_S_OFF + c * 4);
-                bias4[ni] = *reinterpret_cast<const f32x4*>(stage_base + MID_C_OFF + c * 4);
-            }
-        }
+        MidFoldFinish<NT> fold;
+        if constexpr (FOLD == MID_FOLD_CONSUMER) fold.fetch(stage_base, wn * (BN / 4), lchk);
 #pragma unroll
         for (int mi = 0; mi < MT; ++mi) {
             f32x2 rn = {1.f, 0.f};
-            if constexpr (FOLD == MID_FOLD_CONSUMER) rn = *reinterpret_cast<const f32x2*>(stage_base + MID_RS_OFF + (mi * 16 + lrow) * 8);
+            if constexpr (FOLD == MID_FOLD_CONSUMER) rn = fold.row(stage_base, mi * 16 + lrow);
 #pragma unroll
             for (int ni = 0; ni < NT; ++ni) {
                 f32x4 v = acc[ni][mi];
-                if constexpr (FOLD == MID_FOLD_CONSUMER) {   // y = rstd acc + (-mean rstd S + C): the bias is inside C
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = rn[0] * v[r] + (rn[1] * s4[ni][r] + bias4[ni][r]);
-                } else {
+                if constexpr (FOLD == MID_FOLD_CONSUMER) v = fold.apply(rn, ni, v);
+                else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] += bias4[ni][r];
                 }
@@ -413,73 +438,36 @@ __device__ __forceinline__ void mid_epilogue(const GemmArgs& a, f32x4 (&acc)[Mid
     }
 }
 
-// ---------------------------------------------------------------------------------------------- fused self-attention epilogue
-// QKV projection + attention in one launch for the shipped 32-token regime (model/layers.py:183-200 with N = M = 32, head dim 64).  The 128 x 192
-// tile is [q | k | v] of ONE head for FOUR whole samples: the finished projections (bias or LN-folded form applied) go to LDS as bf16 rows — the
-// operand ring is idle by then — and compute wave s runs sample s: S^T = K Q^T (8 MFMAs), the softmax over the 32 keys of a query (8 values
-// in the lane + two cross-lane steps), O^T = V^T P^T (8 MFMAs; the key order inside the 32-deep contraction is the accumulator layout's, applied
-// to both operands, so P never leaves its registers), O / l -> attn_o[B][H][32][64].  The q | k | v rows are never written to HBM and the
-// attention launch of the block is gone (6.5 us + a 12.6 MB round trip per block at B = 64).
-#define MID_T_STRIDE 400             /* bytes per staged row (192 bf16 + pad): conflict-free 16-B fragment reads */
-template <int FOLD>
-__device__ __forceinline__ void mid_epilogue_attn(const GemmArgs& a, f32x4 (&acc)[3][8], int m0, int head, int wn, int lane, char* tq,
-                                                  const char* stage_base) {
+// ---------------------------------------------------------------------------------------------- attention core of the two fused epilogues
+// One wave: QT tiles of 16 queries against the 32 keys of their sample, head dim 64, everything in LDS.  S^T = K Q^T (4 QT MFMAs), the softmax over
+// the 32 keys of a query (8 values in the lane + two cross-lane steps), O^T = V^T P^T (4 QT MFMAs; the key order inside the 32-deep contraction is
+// the accumulator layout's, applied to both operands, so P never leaves its registers), O / l -> o[query][64] as bf16x4 stores.
+// The caller says where things are: qfrag(row, c8) / kfrag(row, c8) -> the 8 channels [c8, +8) of query / key `row`; velem(key, d) -> V[key][d].
+template <int QT, class QF, class KF, class VE>
+__device__ __forceinline__ void mid_attn_core(float cs, int lane, bf16_t* o, QF qfrag, KF kfrag, VE velem) {
     const int lrow = lane & 15, lchk = lane >> 4;
-    const int hidden = a.N / 3;
-    // ---- 1. finish the projection, bf16 rows into tq[128][192]
-    f32x4 add4[3], s4[3];
-#pragma unroll
-    for (int ni = 0; ni < 3; ++ni) {
-        const int c = wn * 48 + ni * 16 + lchk * 4;
-        if constexpr (FOLD == MID_FOLD_CONSUMER) {
-            s4[ni] = *reinterpret_cast<const f32x4*>(stage_base + MID_S_OFF + c * 4);
-            add4[ni] = *reinterpret_cast<const f32x4*>(stage_base + MID_C_OFF + c * 4);
-        } else {
-            s4[ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            add4[ni] = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + mid_attn_col(c, head, hidden)) : (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-    }
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi) {
-        f32x2 rn = {1.f, 0.f};
-        if constexpr (FOLD == MID_FOLD_CONSUMER) rn = *reinterpret_cast<const f32x2*>(stage_base + MID_RS_OFF + (mi * 16 + lrow) * 8);
-#pragma unroll
-        for (int ni = 0; ni < 3; ++ni) {
-            f32x4 v = acc[ni][mi];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = rn[0] * v[r] + (rn[1] * s4[ni][r] + add4[ni][r]);
-            const bf16x4 pk = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-            *reinterpret_cast<bf16x4*>(tq + (mi * 16 + lrow) * MID_T_STRIDE + (wn * 48 + ni * 16 + lchk * 4) * 2) = pk;
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    MID_BARRIER();                                       // the four compute waves (the loader waves have ended): the tile is complete
-    // ---- 2. wave wn = sample wn: rows [32 wn, +32)
-    const char* ts = tq + wn * 32 * MID_T_STRIDE;
-    f32x4 st[2][2];                                      // [key tile][query tile]: lane holds S[key = kt*16 + lchk*4 + r][query = qt*16 + lrow]
+    f32x4 st[2][QT];                                     // [key tile][query tile]: lane holds S[key = kt*16 + lchk*4 + r][query = qt*16 + lrow]
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-        for (int qt = 0; qt < 2; ++qt) st[kt][qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int qt = 0; qt < QT; ++qt) st[kt][qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 kf[2], qf[2];
+        bf16x8 kf[2], qf[QT];
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            kf[t] = *reinterpret_cast<const bf16x8*>(ts + (t * 16 + lrow) * MID_T_STRIDE + (64 + ks * 32 + lchk * 8) * 2);
-            qf[t] = *reinterpret_cast<const bf16x8*>(ts + (t * 16 + lrow) * MID_T_STRIDE + (ks * 32 + lchk * 8) * 2);
-        }
+        for (int t = 0; t < 2; ++t) kf[t] = kfrag(t * 16 + lrow, ks * 32 + lchk * 8);
+#pragma unroll
+        for (int t = 0; t < QT; ++t) qf[t] = qfrag(t * 16 + lrow, ks * 32 + lchk * 8);
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-            for (int qt = 0; qt < 2; ++qt) st[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt], qf[qt], st[kt][qt], 0, 0, 0);
+            for (int qt = 0; qt < QT; ++qt) st[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt], qf[qt], st[kt][qt], 0, 0, 0);
     }
     // softmax over the 32 keys of each query (qt, lrow): 8 values in this lane, the rest in lanes lrow + 16 j
-    const float cs = a.attn_scale_log2e;
-    float linv[2];
-    bf16x8 pf[2];                                        // P^T operand: k-slot j of lane group lchk = key (j < 4 ? lchk*4 + j : 16 + lchk*4 + j - 4)
+    float linv[QT];
+    bf16x8 pf[QT];                                       // P^T operand: k-slot j of lane group lchk = key (j < 4 ? lchk*4 + j : 16 + lchk*4 + j - 4)
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
+    for (int qt = 0; qt < QT; ++qt) {
         float mx = fmaxf(fmaxf(fmaxf(st[0][qt][0], st[0][qt][1]), fmaxf(st[0][qt][2], st[0][qt][3])),
                          fmaxf(fmaxf(st[1][qt][0], st[1][qt][1]), fmaxf(st[1][qt][2], st[1][qt][3])));
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
@@ -496,31 +484,68 @@ __device__ __forceinline__ void mid_epilogue_attn(const GemmArgs& a, f32x4 (&acc
         pf[qt] = (bf16x8){(bf16_t)p[0], (bf16_t)p[1], (bf16_t)p[2], (bf16_t)p[3], (bf16_t)p[4], (bf16_t)p[5], (bf16_t)p[6], (bf16_t)p[7]};
     }
     // O^T[d][query] = sum_key V[key][d] P[query][key]: A operand = V^T rows d = dt*16 + lrow with the same key order in its k-slots
-    bf16_t* ob = a.attn_o + (((long)(m0 / 32 + wn) * (hidden / 64) + head) * 32) * 64;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
         bf16x8 vf;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int key = (j < 4) ? lchk * 4 + j : 16 + lchk * 4 + (j - 4);
-            vf[j] = *reinterpret_cast<const bf16_t*>(ts + key * MID_T_STRIDE + (128 + dt * 16 + lrow) * 2);
-        }
+        for (int j = 0; j < 8; ++j) vf[j] = velem((j < 4) ? lchk * 4 + j : 16 + lchk * 4 + (j - 4), dt * 16 + lrow);
 #pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-            const f32x4 o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qt], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        for (int qt = 0; qt < QT; ++qt) {
+            const f32x4 ot = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qt], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
             // lane holds O[query = qt*16 + lrow][d = dt*16 + lchk*4 + r]
-            const bf16x4 pk = {(bf16_t)(o[0] * linv[qt]), (bf16_t)(o[1] * linv[qt]), (bf16_t)(o[2] * linv[qt]), (bf16_t)(o[3] * linv[qt])};
-            *reinterpret_cast<bf16x4*>(ob + (qt * 16 + lrow) * 64 + dt * 16 + lchk * 4) = pk;
+            const bf16x4 pk = {(bf16_t)(ot[0] * linv[qt]), (bf16_t)(ot[1] * linv[qt]), (bf16_t)(ot[2] * linv[qt]), (bf16_t)(ot[3] * linv[qt])};
+            *reinterpret_cast<bf16x4*>(o + (qt * 16 + lrow) * 64 + dt * 16 + lchk * 4) = pk;
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------- fused self-attention epilogue
+// QKV projection + attention in one launch for the shipped 32-token regime (model/layers.py:183-200 with N = M = 32, head dim 64).  The 128 x 192
+// tile is [q | k | v] of ONE head for FOUR whole samples: the finished projections (bias or LN-folded form applied) go to LDS as bf16 rows — the
+// operand ring is idle by then — and compute wave s runs sample s through mid_attn_core<2> -> attn_o[B][H][32][64].  The q | k | v rows are never written to HBM and the
+// attention launch of the block is gone (6.5 us + a 12.6 MB round trip per block at B = 64).
+#define MID_T_STRIDE 400             /* bytes per staged row (192 bf16 + pad): conflict-free 16-B fragment reads */
+template <int FOLD>
+__device__ __forceinline__ void mid_epilogue_attn(const GemmArgs& a, f32x4 (&acc)[3][8], int m0, int head, int wn, int lane, char* tq,
+                                                  const char* stage_base) {
+    const int lrow = lane & 15, lchk = lane >> 4;
+    const int hidden = a.N / 3;
+    // ---- 1. finish the projection, bf16 rows into tq[128][192]
+    MidFoldFinish<3> fin;                                // (plain form: the same finish with rstd = 1, S = 0, C = the bias)
+    if constexpr (FOLD == MID_FOLD_CONSUMER) fin.fetch(stage_base, wn * 48, lchk);
+    else {
+#pragma unroll
+        for (int ni = 0; ni < 3; ++ni) {
+            fin.s4[ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            fin.c4[ni] = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + mid_attn_col(wn * 48 + ni * 16 + lchk * 4, head, hidden)) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+    }
+#pragma unroll
+    for (int mi = 0; mi < 8; ++mi) {
+        f32x2 rn = {1.f, 0.f};
+        if constexpr (FOLD == MID_FOLD_CONSUMER) rn = fin.row(stage_base, mi * 16 + lrow);
+#pragma unroll
+        for (int ni = 0; ni < 3; ++ni) {
+            const f32x4 v = fin.apply(rn, ni, acc[ni][mi]);
+            const bf16x4 pk = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+            *reinterpret_cast<bf16x4*>(tq + (mi * 16 + lrow) * MID_T_STRIDE + (wn * 48 + ni * 16 + lchk * 4) * 2) = pk;
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    MID_BARRIER();                                       // the four compute waves (the loader waves have ended): the tile is complete
+    // ---- 2. wave wn = sample wn: rows [32 wn, +32) of the tile; q | k | v at columns 0 | 64 | 128 of a staged row
+    const char* ts = tq + wn * 32 * MID_T_STRIDE;
+    mid_attn_core<2>(a.attn_scale_log2e, lane, a.attn_o + (((long)(m0 / 32 + wn) * (hidden / 64) + head) * 32) * 64,
+                     [&](int row, int c8) { return *reinterpret_cast<const bf16x8*>(ts + row * MID_T_STRIDE + c8 * 2); },
+                     [&](int row, int c8) { return *reinterpret_cast<const bf16x8*>(ts + row * MID_T_STRIDE + (64 + c8) * 2); },
+                     [&](int key, int d) { return *reinterpret_cast<const bf16_t*>(ts + key * MID_T_STRIDE + (128 + d) * 2); });
 }
 
 // ---------------------------------------------------------------------------------------------- fused cross-attention epilogue
 // q projection + cross-attention in one launch (model/layers.py:183-200 with N = 32 queries, M = 32 condition tokens, head dim 64; the K | V rows
 // of the condition are step-invariant and cached by the caller).  The 64 x 64 tile is q of ONE head for TWO whole samples; the loader waves bring
 // that head's K and V rows of the two samples into LDS ahead of the operand stream (16 KB, swizzled like the operands).  Compute wave w runs
-// sample w >> 1, queries [16 (w & 1), +16): S^T = K Q^T (4 MFMAs), softmax over the 32 keys, O^T = V^T P^T (4 MFMAs) — the math and the operand
-// layouts of mid_epilogue_attn.  q never reaches HBM and the attention launch of every cross-attention block is gone.
+// sample w >> 1, queries [16 (w & 1), +16) through mid_attn_core<1>.  q never reaches HBM and the attention launch of every cross-attention block is gone.
 #define MID_XQ_STRIDE 144            /* bytes per staged q row (64 bf16 + pad): conflict-free 16-B fragment reads */
 __device__ __forceinline__ void mid_epilogue_xattn(const GemmArgs& a, f32x4 (&acc)[1][4], int m0, int head, int wn, int lane, char* tq, const char* kv) {
     const int lrow = lane & 15, lchk = lane >> 4;
@@ -534,50 +559,13 @@ __device__ __forceinline__ void mid_epilogue_xattn(const GemmArgs& a, f32x4 (&ac
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     MID_BARRIER();                                       // the four compute waves (the loader waves have ended): the q tile is complete
     const int sp = wn >> 1, qh = wn & 1;
-    const char* ks = kv + (sp * 2) * 4096;
+    const char* ks = kv + (sp * 2) * 4096;               // K | V: 32 rows x 128 B each, 16-B chunks swizzled like the operand stages
     const char* vs = ks + 4096;
-    const char* qs = tq + (sp * 32 + qh * 16 + lrow) * MID_XQ_STRIDE;
-    f32x4 st[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};   // lane holds S[key = kt*16 + lchk*4 + r][query = lrow]
-#pragma unroll
-    for (int k2 = 0; k2 < 2; ++k2) {
-        const bf16x8 qf = *reinterpret_cast<const bf16x8*>(qs + (k2 * 32 + lchk * 8) * 2);
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-            const int row = kt * 16 + lrow;
-            const bf16x8 kf = *reinterpret_cast<const bf16x8*>(ks + row * 128 + (((k2 * 4 + lchk) ^ ((row >> 1) & 7)) << 4));
-            st[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, st[kt], 0, 0, 0);
-        }
-    }
-    const float cs = a.attn_scale_log2e;
-    float mx = fmaxf(fmaxf(fmaxf(st[0][0], st[0][1]), fmaxf(st[0][2], st[0][3])), fmaxf(fmaxf(st[1][0], st[1][1]), fmaxf(st[1][2], st[1][3])));
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float mc = mx * cs;
-    float p[8], l = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { p[kt * 4 + r] = __builtin_amdgcn_exp2f(st[kt][r] * cs - mc); l += p[kt * 4 + r]; }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    const float linv = 1.0f / l;
-    // P^T operand: k-slot j of lane group lchk = key (j < 4 ? lchk*4 + j : 16 + lchk*4 + j - 4): the accumulator layout's key order, on both operands
-    const bf16x8 pf = {(bf16_t)p[0], (bf16_t)p[1], (bf16_t)p[2], (bf16_t)p[3], (bf16_t)p[4], (bf16_t)p[5], (bf16_t)p[6], (bf16_t)p[7]};
-    bf16_t* ob = a.attn_o + ((((long)(m0 / 32 + sp)) * (a.N / 64) + head) * 32 + qh * 16 + lrow) * 64;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-        bf16x8 vf;
-        const int c = dt * 2 + (lrow >> 3);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int key = (j < 4) ? lchk * 4 + j : 16 + lchk * 4 + (j - 4);
-            vf[j] = *reinterpret_cast<const bf16_t*>(vs + key * 128 + ((c ^ ((key >> 1) & 7)) << 4) + (lrow & 7) * 2);
-        }
-        const f32x4 o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        // lane holds O[query = lrow][d = dt*16 + lchk*4 + r]
-        const bf16x4 pk = {(bf16_t)(o[0] * linv), (bf16_t)(o[1] * linv), (bf16_t)(o[2] * linv), (bf16_t)(o[3] * linv)};
-        *reinterpret_cast<bf16x4*>(ob + dt * 16 + lchk * 4) = pk;
-    }
+    const char* qs = tq + (sp * 32 + qh * 16) * MID_XQ_STRIDE;
+    mid_attn_core<1>(a.attn_scale_log2e, lane, a.attn_o + ((((long)(m0 / 32 + sp)) * (a.N / 64) + head) * 32 + qh * 16) * 64,
+                     [&](int row, int c8) { return *reinterpret_cast<const bf16x8*>(qs + row * MID_XQ_STRIDE + c8 * 2); },
+                     [&](int row, int c8) { return *reinterpret_cast<const bf16x8*>(ks + row * 128 + (((c8 >> 3) ^ ((row >> 1) & 7)) << 4)); },
+                     [&](int key, int d) { return *reinterpret_cast<const bf16_t*>(vs + key * 128 + (((d >> 3) ^ ((key >> 1) & 7)) << 4) + (d & 7) * 2); });
 }
 
 // ---------------------------------------------------------------------------------------------- kernel
@@ -593,18 +581,17 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_mid_kernel(const GemmArgs a)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     // XCD-aware bijective remap of the 1-D tile index (blocks b, b+8, ... share an XCD's L2), column-major inside the chunk
-    const int tiles_m = (a.M + BM - 1) / BM, tiles_n = a.N / BN;
+    const int tiles_m = (a.M + BM - 1) / BM;
     const int nwg = gridDim.x, bid = blockIdx.x;
     const int q = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
     const int wgid = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (bid >> 3);
-    const int tile_m = a.col_major ? wgid % tiles_m : wgid / tiles_n, tile_n = a.col_major ? wgid / tiles_m : wgid % tiles_n;
+    const int tile_m = wgid % tiles_m, tile_n = wgid / tiles_m;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const int kbase = 0;
     const int nkt = a.K / MID_BK;
     const int step = a.step_ptr ? *a.step_ptr : 0;       // device-side SDE step counter (scalar load, before any request of this kernel)
 
     if (wave >= 4) {                                     // loader waves: the operand stream, nothing else
-        mid_loader<BM, BN, FOLD, ATTN>(a, smem_mid, wave - 4, lane, m0, n0, kbase, nkt, step);
+        mid_loader<BM, BN, FOLD, ATTN>(a, smem_mid, wave - 4, lane, m0, n0, nkt, step);
         return;
     }
 
@@ -629,11 +616,10 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_mid_kernel(const GemmArgs a)
     // share this W column panel (cold in HBM at every SDE step) each pull their share of its 128-B lines towards the XCD's L2 — K-tile j of the
     // panel by the workgroup with tile_m == j mod tiles_m, one line per lane, one dword-sized LDS-DMA per wave and K-tile into the (still
     // unused) staging area.
-#ifndef MID_NO_TOUCH
     {
         const int prow = wn * 64 + lane;                 // row of the panel this lane touches (BN = 128: waves 0, 1 cover it)
         if (prow < BN) {
-            const char* wl = reinterpret_cast<const char*>(a.W + (long)(ATTN == MID_ATTN_SELF ? mid_attn_col(prow, tile_n, a.N / 3) : n0 + prow) * a.ldw + kbase);
+            const char* wl = reinterpret_cast<const char*>(a.W + (long)(ATTN == MID_ATTN_SELF ? mid_attn_col(prow, tile_n, a.N / 3) : n0 + prow) * a.ldw);
             char* dst = smem_mid + C::RING + wave * 4096;
             int cnt = 0;
             for (int j = tile_m + (tile_m < 3 ? tiles_m : 0); j < nkt && cnt < 6; j += tiles_m, ++cnt)   // (K-tiles 0-2 are requested at once anyway; 6 x 256 B: the staging area's head)
@@ -641,7 +627,6 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_mid_kernel(const GemmArgs a)
                                                  (__attribute__((address_space(3))) void*)(dst + cnt * 256), 4, 0, 0);
         }
     }
-#endif
     // (Also tried here: pulling the NEXT GEMM's weights towards the Infinity Cache, 1 / 256 of them per workgroup — 2.3 % SLOWER per SDE step
     //  at the shipped 32-token config, 2.5 % at the ViPC share: the extra HBM requests compete with this kernel's own first K-tiles.)
     MID_BARRIER();                                       // prologue barrier: K-tile 0 has landed
@@ -680,10 +665,12 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_mid_kernel(const GemmArgs a)
         ld_w(wa, st, wb0); ld_x(xa, st, xb0, 0);
         MID_LGKM0();                                     // once: both ways into the loop then carry no pending reads (see the loop's tail)
         int slot = 0;
-        // (the last K-tile is peeled: with the barrier under a condition inside ONE loop body hipcc merges the two paths in front of the
-        //  fourth block and waits there for the next K-tile's first fragment reads — lgkmcnt(3..0) — before MFMAs that do not need them)
-        __builtin_amdgcn_sched_barrier(0);
-        for (int kt = 0; kt + 1 < nkt; ++kt) {
+        // One K-tile.  The LAST one is a second instantiation, called behind the loop (the peel): with the barrier under a runtime condition inside
+        // ONE loop body hipcc merges the two paths in front of the fourth block and waits there for the next K-tile's first fragment reads —
+        // lgkmcnt(3..0) — before MFMAs that do not need them.  (The register sets are PARAMETERS: captured, hipcc's scalar replacement splits the
+        // X sets another way and the VGPR counts of seven kernels move, profiles/gemm_mid_refactor_codegen.txt.)
+        auto ktile = [&](bf16x8 (&wa)[NT], bf16x8 (&wb)[NT], bf16x8 (&xa)[4], bf16x8 (&xb)[4], auto last) {
+            constexpr bool LAST = decltype(last)::value;
             ld_x(xb, st, xb0, 1);
             mm(wa, xa, 0);
             mid_interleave<4, 2, 4 * NT>();
@@ -693,25 +680,22 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_mid_kernel(const GemmArgs a)
             ld_x(xb, st, xb1, 1);                        // last read of this stage
             mm(wb, xa, 0);
             mid_interleave<4, 2, 4 * NT>();
-            MID_LGKM0();
-            MID_BARRIER();                               // barrier kt: K-tile kt+1 landed; this stage may be refilled
-            slot = slot + 1 == C::NS ? 0 : slot + 1;
-            st = smem_mid + slot * C::STAGE;
-            ld_w(wa, st, wb0); ld_x(xa, st, xb0, 0);
+            if constexpr (!LAST) {
+                MID_LGKM0();
+                MID_BARRIER();                           // barrier kt: K-tile kt+1 landed; this stage may be refilled
+                slot = mid_next_slot<C::NS>(slot);
+                st = smem_mid + slot * C::STAGE;
+                ld_w(wa, st, wb0); ld_x(xa, st, xb0, 0);
+            }
             mm(wb, xb, 1);
-            mid_interleave<NT + 4, 1, 4 * NT>();
-            MID_LGKM0();                                 // (free behind the MFMAs; lets hipcc's wait insertion open the next trip with known counters)
-        }
-        ld_x(xb, st, xb0, 1);
-        mm(wa, xa, 0);
-        mid_interleave<4, 2, 4 * NT>();
-        ld_w(wb, st, wb1); ld_x(xa, st, xb1, 0);
-        mm(wa, xb, 1);
-        mid_interleave<NT + 4, 1, 4 * NT>();
-        ld_x(xb, st, xb1, 1);
-        mm(wb, xa, 0);
-        mid_interleave<4, 2, 4 * NT>();
-        mm(wb, xb, 1);
+            if constexpr (!LAST) {
+                mid_interleave<NT + 4, 1, 4 * NT>();
+                MID_LGKM0();                             // (free behind the MFMAs; lets hipcc's wait insertion open the next trip with known counters)
+            }
+        };
+        __builtin_amdgcn_sched_barrier(0);
+        for (int kt = 0; kt + 1 < nkt; ++kt) ktile(wa, wb, xa, xb, std::false_type{});
+        ktile(wa, wb, xa, xb, std::true_type{});
     } else if constexpr (BM == 64) {
         // 64 x 128 | 64 x 64 tile: a wave owns 64 rows x 32 | 16 columns (NT x 4 accumulator tiles), a K-tile is ONE block of 16 | 8 MFMAs; the
         // whole next K-tile's fragments (2 NT W + 8 X) are read into the other register set while this one is multiplied.  The reads of K-tile kt are complete
@@ -734,30 +718,26 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_mid_kernel(const GemmArgs a)
         };
         constexpr int KT_MFMA = 8 * NT, KT_RD = (2 * NT + 8) < KT_MFMA ? (2 * NT + 8) : KT_MFMA;   // MFMAs / interleaved reads per K-tile
         int slot = 0;
-        auto next_stage = [&]() { slot = slot + 1 == C::NS ? 0 : slot + 1; return smem_mid + slot * C::STAGE; };
+        // One K-tile out of register set (w, x) while the next one is read into (wn, xn); LAST: the next one is the final K-tile and is multiplied too
+        auto ktile = [&](const bf16x8 (&w)[2][NT], const bf16x8 (&x)[2][4], bf16x8 (&wn)[2][NT], bf16x8 (&xn)[2][4], auto last) {
+            MID_BARRIER();                               // barrier kt: K-tile kt+1 landed (and K-tile kt's stage is free: its reads returned before this trip)
+            slot = mid_next_slot<C::NS>(slot);
+            ld(wn, xn, smem_mid + slot * C::STAGE);
+            mm(w, x);
+            mid_interleave<KT_RD, 1, KT_MFMA>();
+            if constexpr (decltype(last)::value) mm(wn, xn);
+            else MID_LGKM0();
+        };
         ld(wa, xa, smem_mid);
         MID_LGKM0();
         __builtin_amdgcn_sched_barrier(0);
         int kt = 0;
-        for (; kt + 2 < nkt; kt += 2) {
-            MID_BARRIER();                               // barrier kt: K-tile kt+1 landed (and K-tile kt's stage is free: its reads returned before this trip)
-            ld(wb, xb, next_stage());
-            mm(wa, xa);
-            mid_interleave<KT_RD, 1, KT_MFMA>();
-            MID_LGKM0();
-            MID_BARRIER();                               // barrier kt+1
-            ld(wa, xa, next_stage());
-            mm(wb, xb);
-            mid_interleave<KT_RD, 1, KT_MFMA>();
-            MID_LGKM0();
+        for (; kt + 2 < nkt; kt += 2) {                  // (two K-tiles per trip: the register sets swap roles)
+            ktile(wa, xa, wb, xb, std::false_type{});
+            ktile(wb, xb, wa, xa, std::false_type{});
         }
-        if (kt + 1 < nkt) {
-            MID_BARRIER();
-            ld(wb, xb, next_stage());
-            mm(wa, xa);
-            mid_interleave<KT_RD, 1, KT_MFMA>();
-            mm(wb, xb);
-        } else mm(wa, xa);
+        if (kt + 1 < nkt) ktile(wa, xa, wb, xb, std::true_type{});
+        else mm(wa, xa);
     } else {
         // 128 x 128: a wave owns 32 columns (2 accumulator tiles x 8 row tiles); K-tile = 2 blocks of 16 MFMAs (half 0, half 1)
         bf16x8 wa[2], wb[2], xa[8], xb[8];
@@ -778,24 +758,27 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_mid_kernel(const GemmArgs a)
         ld(wa, xa, st, wb0, xb0);
         MID_LGKM0();
         int slot = 0;
-        __builtin_amdgcn_sched_barrier(0);
-        for (int kt = 0; kt + 1 < nkt; ++kt) {
+        auto ktile = [&](bf16x8 (&wa)[2], bf16x8 (&wb)[2], bf16x8 (&xa)[8], bf16x8 (&xb)[8], auto last) {   // one K-tile; the LAST one peeled, the sets as parameters: as above
+            constexpr bool LAST = decltype(last)::value;
             ld(wb, xb, st, wb1, xb1);                    // last reads of this stage
             mm(wa, xa);
             mid_interleave<10, 1>();
-            MID_LGKM0();
-            MID_BARRIER();
-            slot = slot + 1 == C::NS ? 0 : slot + 1;
-            st = smem_mid + slot * C::STAGE;
-            ld(wa, xa, st, wb0, xb0);
+            if constexpr (!LAST) {
+                MID_LGKM0();
+                MID_BARRIER();
+                slot = mid_next_slot<C::NS>(slot);
+                st = smem_mid + slot * C::STAGE;
+                ld(wa, xa, st, wb0, xb0);
+            }
             mm(wb, xb);
-            mid_interleave<10, 1>();
-            MID_LGKM0();
-        }
-        ld(wb, xb, st, wb1, xb1);
-        mm(wa, xa);
-        mid_interleave<10, 1>();
-        mm(wb, xb);
+            if constexpr (!LAST) {
+                mid_interleave<10, 1>();
+                MID_LGKM0();
+            }
+        };
+        __builtin_amdgcn_sched_barrier(0);
+        for (int kt = 0; kt + 1 < nkt; ++kt) ktile(wa, wb, xa, xb, std::false_type{});
+        ktile(wa, wb, xa, xb, std::true_type{});
     }
 
     MID_STAMP(2);
@@ -825,143 +808,136 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_mid_kernel(const GemmArgs a)
 // ---------------------------------------------------------------------------------------------- launcher
 // Shapes this kernel takes (everything else stays with gemm_bf16.hip / gemm_256.hip): whole column tiles, 16-byte aligned rows, K a multiple of 64,
 // and a problem of at most two rounds of workgroups (longer ones belong to the persistent 256^2 kernel or the streaming v1 forms).
-static int mid_env() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("LDT_GEMM_MID"); v = e ? atoi(e) : 1; }
-    return v;
+static bool mid_on() {                                   // LDT_GEMM_MID=0: the whole family off (tools/dbg/mid_bench.py: the small-tile kernels instead)
+    static const bool on = !(getenv("LDT_GEMM_MID") && atoi(getenv("LDT_GEMM_MID")) == 0);
+    return on;
 }
 
-// Tile shape for (M, N): this path is bound by what a CU can take in through the L2 -> LDS DMA (~80 GB/s, profiles/r04_mid_stamps.txt), so
-// the cost of a shape is rounds x bytes per workgroup and K-tile ~ ceil(workgroups / 256) x (BM + BN).  -> (BM << 16) | BN, 0 = not taken.
-// fold: 0 = any form; 1 = LN-folded producer (a wave's 32 columns are the statistics granule: BN = 128 forms only);
-//       2 = LN-folded consumer (the loader waves' statistics pass: 128-row forms only)
-static int mid_shape_for(int epi, const GemmArgs* a, int fold);
-int ldt_gemm_mid_shape(int epi, const GemmArgs* a) { return mid_shape_for(epi, a, 0); }
+// THE list of built forms: the shape rule picks its candidates from it (in this order) and the dispatch instantiates exactly its rows, so a form the
+// rule can pick is a form that exists.  128 x 192: bf16 outputs only.  LN-folded producer (MID_FOLD_PRODUCER: a wave's 32 columns are the statistics
+// granule): BN = 128 forms of the residual epilogue; consumer (the loader waves' statistics pass): BM = 128 forms of the bf16 epilogues.  The two
+// fused projection + attention forms have shape rules of their own (ldt_gemm_mid_qkv_attn_takes / ldt_gemm_mid_q_xattn_takes).
+constexpr unsigned mid_epis(int e0, int e1 = -1, int e2 = -1, int e3 = -1) {
+    return (1u << e0) | (e1 < 0 ? 0u : 1u << e1) | (e2 < 0 ? 0u : 1u << e2) | (e3 < 0 ? 0u : 1u << e3);
+}
+constexpr unsigned MID_EPIS_ALL = mid_epis(EPI_F32, EPI_BF16, EPI_GELU_BF16, EPI_RESID_F32), MID_EPIS_BF16 = mid_epis(EPI_BF16, EPI_GELU_BF16);
+struct MidForm { unsigned epis; int bm, bn, fold, attn; };
+constexpr MidForm MID_FORMS[] = {
+    {MID_EPIS_ALL, 128, 256, MID_FOLD_NONE, MID_ATTN_NONE},
+    {MID_EPIS_BF16, 128, 192, MID_FOLD_NONE, MID_ATTN_NONE},
+    {MID_EPIS_ALL, 128, 128, MID_FOLD_NONE, MID_ATTN_NONE},
+    {MID_EPIS_ALL, 64, 128, MID_FOLD_NONE, MID_ATTN_NONE},
+    {MID_EPIS_ALL, 64, 64, MID_FOLD_NONE, MID_ATTN_NONE},
+    {mid_epis(EPI_RESID_F32), 128, 128, MID_FOLD_PRODUCER, MID_ATTN_NONE},
+    {mid_epis(EPI_RESID_F32), 64, 128, MID_FOLD_PRODUCER, MID_ATTN_NONE},
+    {MID_EPIS_BF16, 128, 256, MID_FOLD_CONSUMER, MID_ATTN_NONE},
+    {MID_EPIS_BF16, 128, 192, MID_FOLD_CONSUMER, MID_ATTN_NONE},
+    {MID_EPIS_BF16, 128, 128, MID_FOLD_CONSUMER, MID_ATTN_NONE},
+    {mid_epis(EPI_BF16), 128, 192, MID_FOLD_NONE, MID_ATTN_SELF},
+    {mid_epis(EPI_BF16), 128, 192, MID_FOLD_CONSUMER, MID_ATTN_SELF},
+    {mid_epis(EPI_BF16), 64, 64, MID_FOLD_NONE, MID_ATTN_CROSS},
+};
+constexpr int MID_NFORMS = sizeof(MID_FORMS) / sizeof(MID_FORMS[0]);
 
-static int mid_shape_for(int epi, const GemmArgs* a, int fold) {
-    const int mode = mid_env();                          // 0 off, 1 automatic; tools/dbg: 256 / 192 / 128 / 64 pin 128x256 / 128x192 / 128x128 / 64x128
-    if (!mode) return 0;
-    if (!(epi == EPI_F32 || epi == EPI_BF16 || epi == EPI_GELU_BF16 || epi == EPI_RESID_F32)) return 0;
-    if (a->K % MID_BK != 0 || a->N % 64 != 0 || a->M < 64 || a->ldo % 8 != 0) return 0;
-    if (epi == EPI_RESID_F32 && (a->ldr % 4 != 0 || (a->gate && a->gate_sample_stride % 4 != 0))) return 0;
-    struct { int bm, bn; } cand[5] = {{128, 256}, {128, 192}, {128, 128}, {64, 128}, {64, 64}};
-    const bool bf16_out = epi == EPI_BF16 || epi == EPI_GELU_BF16;
-    if (fold == 0) {
-    if (mode == 256) return a->N % 256 == 0 ? (128 << 16) | 256 : 0;
-    if (mode == 128) return (128 << 16) | 128;
-    if (mode == 64) return (64 << 16) | 128;
-    if (mode == 6464) return (64 << 16) | 64;
-    }
-    long best_cost = 0; int best = 0;
-    if (mode == 192) return (a->N % 192 == 0 && bf16_out) ? (128 << 16) | 192 : 0;
-    for (int i = 0; i < 5; ++i) {
-        if (a->N % cand[i].bn != 0 || (cand[i].bn == 192 && !bf16_out)) continue;
-        if ((fold == 1 && cand[i].bn != 128) || (fold == 2 && cand[i].bm != 128)) continue;
-        const long wgs = (long)((a->M + cand[i].bm - 1) / cand[i].bm) * (a->N / cand[i].bn);
+// Tile shape for (M, N): this path is bound by what a CU can take in through the L2 -> LDS DMA (~80 GB/s, profiles/r04_mid_stamps.txt), so
+// the cost of a shape is rounds x bytes per workgroup and K-tile ~ ceil(workgroups / 256) x (BM + BN); the first cheapest form of the list wins.
+// -> the form, or null = not taken.
+static const MidForm* mid_form_for(int epi, int fold, const GemmArgs* a) {
+    if (!mid_on() || epi < 0 || epi > EPI_RESID_F32) return nullptr;
+    if (a->K % MID_BK != 0 || a->N % 64 != 0 || a->M < 64 || a->ldo % 8 != 0) return nullptr;
+    if (epi == EPI_RESID_F32 && (a->ldr % 4 != 0 || (a->gate && a->gate_sample_stride % 4 != 0))) return nullptr;
+    // the consumer's loader waves assume the whole ring in flight with K-tile NS behind it, and <= 32 partials per row
+    if (fold == MID_FOLD_CONSUMER && (a->K / 32 > 32 || a->K / MID_BK < MidCfg<128, 256>::NS + 2)) return nullptr;
+    const MidForm* best = nullptr;
+    long best_cost = 0;
+    for (const MidForm& f : MID_FORMS) {
+        if (f.attn != MID_ATTN_NONE || f.fold != fold || !((f.epis >> epi) & 1) || a->N % f.bn != 0) continue;
+        const long wgs = (long)((a->M + f.bm - 1) / f.bm) * (a->N / f.bn);
+        // (LDT_NUM_CUS here, ldt_wg_limit(a->max_wgs) in the two fused-attention rules below: a known difference, kept — aligning them changes routes)
         if (wgs < 48 || wgs > 2 * LDT_NUM_CUS) continue;
-        const long cost = ((wgs + LDT_NUM_CUS - 1) / LDT_NUM_CUS) * (cand[i].bm + cand[i].bn);
-        if (!best || cost < best_cost) { best = (cand[i].bm << 16) | cand[i].bn; best_cost = cost; }
+        const long cost = ((wgs + LDT_NUM_CUS - 1) / LDT_NUM_CUS) * (f.bm + f.bn);
+        if (!best || cost < best_cost) { best = &f; best_cost = cost; }
     }
     return best;
 }
 
-template <int EPI, int BM, int BN>
-static int mid_launch_t(const GemmArgs* a_in, hipStream_t stream) {
-    using C = MidCfg<BM, BN>;
-    GemmArgs a = *a_in;
-    const long tm = (a.M + BM - 1) / BM, tn = a.N / BN;
-    static const int map_env = getenv("LDT_GEMM_MID_MAP") ? atoi(getenv("LDT_GEMM_MID_MAP")) : -1;   // tools/dbg: 0 row-major, 1 column-major
-    a.col_major = map_env >= 0 ? map_env : 1;
-    LDT_ENSURE_LDS((&gemm_bf16_nt_mid_kernel<EPI, BM, BN>), C::LDS, "gemm_mid");
-    hipLaunchKernelGGL((gemm_bf16_nt_mid_kernel<EPI, BM, BN>), dim3((unsigned)(tm * tn)), dim3(512), C::LDS, stream, a);
-    return ldt_check_launch("gemm_bf16_nt_mid");
-}
-
-int ldt_gemm_mid_launch(int epi, int shape, const GemmArgs* a, hipStream_t stream) {
-    const int bm = shape >> 16, bn = shape & 0xffff;
-    if (bn == 192) return epi == EPI_BF16 ? mid_launch_t<EPI_BF16, 128, 192>(a, stream) : mid_launch_t<EPI_GELU_BF16, 128, 192>(a, stream);
-#define MID_CASE(E)                                                                                            \
-    case E: return bm == 64 ? (bn == 64 ? mid_launch_t<E, 64, 64>(a, stream) : mid_launch_t<E, 64, 128>(a, stream)) : bn == 256 ? mid_launch_t<E, 128, 256>(a, stream) \
-                                                                               : mid_launch_t<E, 128, 128>(a, stream)
-    switch (epi) {
-        MID_CASE(EPI_F32);
-        MID_CASE(EPI_BF16);
-        MID_CASE(EPI_GELU_BF16);
-        MID_CASE(EPI_RESID_F32);
-        default: ldt_set_error("gemm_mid: epilogue %d not built", epi); return LDT_EARG;
-    }
-#undef MID_CASE
-}
-
-// LN-folded forms (ldt_gemm_lnfold_launch's small-batch route: statistics per 32 columns): producer = the N = hidden residual GEMMs on
-// 64 x 128 / 128 x 128 tiles, consumer = QKV / MLP-up on 128 x 256 / 128 x 128 tiles.  -> true when this kernel took the launch.
-template <int EPI, int BM, int BN, int FOLD>
-static int mid_fold_launch_t(const GemmArgs& a, hipStream_t stream) {
-    constexpr int lds = MidCfg<BM, BN>::LDS;
-    LDT_ENSURE_LDS((&gemm_bf16_nt_mid_kernel<EPI, BM, BN, FOLD>), lds, "gemm_mid(fold)");
-    const unsigned grid = (unsigned)(((a.M + BM - 1) / BM) * (a.N / BN));
-    hipLaunchKernelGGL((gemm_bf16_nt_mid_kernel<EPI, BM, BN, FOLD>), dim3(grid), dim3(512), lds, stream, a);
-    return ldt_check_launch("gemm_bf16_nt_mid(fold)");
-}
-
-// Tile of the folded form of this GEMM (statistics per 32 columns), 0 = not taken: the producer's statistics granule is a wave's 32 columns
-// of a 128-column tile; the consumer's loader waves assume the whole ring is in flight and <= 32 partials per row.  (ldt_gemm_decide)
-int ldt_gemm_mid_lnfold_shape(int epi, const GemmArgs* a) {
-    if (!mid_env() || !(epi == EPI_RESID_F32 || epi == EPI_BF16 || epi == EPI_GELU_BF16)) return 0;
-    const int shape = mid_shape_for(epi, a, epi == EPI_RESID_F32 ? 1 : 2);
-    if (!shape) return 0;
-    const int bm = shape >> 16, bn = shape & 0xffff;
-    if (epi == EPI_RESID_F32) return (bn == 128 && a->N % 32 == 0) ? shape : 0;
-    return (bm == 128 && a->K % 32 == 0 && a->K / 32 <= 32 && a->K / MID_BK >= MidCfg<128, 256>::NS + 2) ? shape : 0;
+// fold: MID_FOLD_* (= gemm256_tile.h's FOLD_*).  Fills `r` (family GEMM_ROUTE_MID, tile, grid) and returns true when a form takes the problem.  (ldt_gemm_decide)
+bool ldt_gemm_mid_route(int epi, int fold, const GemmArgs* a, GemmRoute* r) {
+    const MidForm* f = mid_form_for(epi, fold, a);
+    if (!f) return false;
+    r->family = GEMM_ROUTE_MID; r->bm = f->bm; r->bn = f->bn; r->tiles_per_wg = 1;
+    r->grid = ((a->M + f->bm - 1) / f->bm) * (a->N / f->bn);
+    return true;
 }
 
 // would the folded form of this GEMM (M x N x K, statistics per 32 columns) be taken?  (Score.can_fold / ldt_gemm_lnfold_v1_route)
 bool ldt_gemm_mid_lnfold_takes(int epi, int M, int N, int K) {
     GemmArgs g{};
     g.M = M; g.N = N; g.K = K; g.ldo = N; g.ldr = N;
-    return ldt_gemm_mid_lnfold_shape(epi, &g) != 0;
+    return (epi == EPI_RESID_F32 || epi == EPI_BF16 || epi == EPI_GELU_BF16) && mid_form_for(epi, epi == EPI_RESID_F32 ? MID_FOLD_PRODUCER : MID_FOLD_CONSUMER, &g);
 }
 
-int ldt_gemm_mid_lnfold_launch(int epi, int shape, const GemmArgs* a_in, hipStream_t stream) {
-    const int bm = shape >> 16, bn = shape & 0xffff;
-    GemmArgs a = *a_in;
-    static const int map_env = getenv("LDT_GEMM_MID_MAP") ? atoi(getenv("LDT_GEMM_MID_MAP")) : -1;
-    a.col_major = map_env >= 0 ? map_env : 1;
-    if (epi == EPI_RESID_F32) {                          // producer
-        LDT_REQUIRE(bn == 128 && a.stats_parts * 32 == a.N, LDT_ESHAPE, "gemm_mid(fold): producer needs 128-column tiles and stats[N/32][M][2]");
-        return bm == 64 ? mid_fold_launch_t<EPI_RESID_F32, 64, 128, MID_FOLD_PRODUCER>(a, stream)
-                        : mid_fold_launch_t<EPI_RESID_F32, 128, 128, MID_FOLD_PRODUCER>(a, stream);
+// The one launch sequence of the family.  xlds: LDS bytes behind the staging areas (the cross form's K | V rows); what: the name in error text.
+template <int EPI, int BM, int BN, int FOLD, int ATTN>
+static int mid_launch(const GemmArgs& a, int xlds, const char* what, hipStream_t stream) {
+    const int lds = MidCfg<BM, BN>::LDS + xlds;
+    LDT_ENSURE_LDS((&gemm_bf16_nt_mid_kernel<EPI, BM, BN, FOLD, ATTN>), lds, what);
+    const unsigned grid = (unsigned)(((a.M + BM - 1) / BM) * (a.N / BN));
+    hipLaunchKernelGGL((gemm_bf16_nt_mid_kernel<EPI, BM, BN, FOLD, ATTN>), dim3(grid), dim3(512), lds, stream, a);
+    return ldt_check_launch(what);
+}
+
+// dispatch = a walk over MID_FORMS: row I x epilogue EPI is instantiated when the row lists the epilogue.  `q`: the form asked for (epis = one bit)
+template <int I, int EPI>
+static bool mid_launch_if(const MidForm& q, const GemmArgs& a, const char* what, hipStream_t stream, int* rc) {
+    constexpr MidForm f = MID_FORMS[I];
+    if constexpr ((f.epis >> EPI) & 1) {
+        if (q.epis == 1u << EPI && q.bm == f.bm && q.bn == f.bn && q.fold == f.fold && q.attn == f.attn) {
+            *rc = mid_launch<EPI, f.bm, f.bn, f.fold, f.attn>(a, f.attn == MID_ATTN_CROSS ? MID_XKV_BYTES : 0, what, stream);
+            return true;
+        }
     }
-    LDT_REQUIRE(bm == 128 && a.stats_parts <= 32 && a.stats_parts * 32 == a.K, LDT_ESHAPE, "gemm_mid(fold): consumer needs 128-row tiles and stats[K/32 <= 32][M][2]");
-    if (epi == EPI_BF16)
-        return bn == 256 ? mid_fold_launch_t<EPI_BF16, 128, 256, MID_FOLD_CONSUMER>(a, stream)
-             : bn == 192 ? mid_fold_launch_t<EPI_BF16, 128, 192, MID_FOLD_CONSUMER>(a, stream)
-                         : mid_fold_launch_t<EPI_BF16, 128, 128, MID_FOLD_CONSUMER>(a, stream);
-    if (epi == EPI_GELU_BF16)
-        return bn == 256 ? mid_fold_launch_t<EPI_GELU_BF16, 128, 256, MID_FOLD_CONSUMER>(a, stream)
-             : bn == 192 ? mid_fold_launch_t<EPI_GELU_BF16, 128, 192, MID_FOLD_CONSUMER>(a, stream)
-                         : mid_fold_launch_t<EPI_GELU_BF16, 128, 128, MID_FOLD_CONSUMER>(a, stream);
-    ldt_set_error("gemm_mid(fold): epilogue %d has no folded form", epi);
+    return false;
+}
+template <int... I>
+static int mid_dispatch(std::integer_sequence<int, I...>, const MidForm& q, const GemmArgs& a, const char* what, hipStream_t stream) {
+    int rc = LDT_EARG;
+    if (((mid_launch_if<I, EPI_F32>(q, a, what, stream, &rc) || mid_launch_if<I, EPI_BF16>(q, a, what, stream, &rc) ||
+          mid_launch_if<I, EPI_GELU_BF16>(q, a, what, stream, &rc) || mid_launch_if<I, EPI_RESID_F32>(q, a, what, stream, &rc)) || ...))
+        return rc;
+    ldt_set_error("%s: epilogue set %#x on %d x %d tiles (fold %d) is not built", what, q.epis, q.bm, q.bn, q.fold);
     return LDT_EARG;
+}
+static int mid_dispatch(int epi, int bm, int bn, int fold, int attn, const GemmArgs& a, const char* what, hipStream_t stream) {
+    return mid_dispatch(std::make_integer_sequence<int, MID_NFORMS>{}, MidForm{epi >= 0 && epi < 32 ? 1u << epi : 0u, bm, bn, fold, attn}, a, what, stream);
+}
+
+// route: ldt_gemm_decide's (family GEMM_ROUTE_MID).  fold = MID_FOLD_PRODUCER / CONSUMER: the LN-folded forms (ldt_gemm_lnfold_launch's small-batch
+// route, statistics per 32 columns) — the N = hidden residual GEMMs as producers, QKV / MLP-up as consumers.
+int ldt_gemm_mid_launch(int epi, int fold, const GemmArgs* a, const GemmRoute& route, hipStream_t stream) {
+    if (fold == MID_FOLD_PRODUCER)
+        LDT_REQUIRE(a->stats_parts * 32 == a->N, LDT_ESHAPE, "gemm_mid(fold): producer needs stats[N/32][M][2]");
+    if (fold == MID_FOLD_CONSUMER)
+        LDT_REQUIRE(a->stats_parts <= 32 && a->stats_parts * 32 == a->K, LDT_ESHAPE, "gemm_mid(fold): consumer needs stats[K/32 <= 32][M][2]");
+    return mid_dispatch(epi, route.bm, route.bn, fold, MID_ATTN_NONE, *a, fold ? "gemm_bf16_nt_mid(fold)" : "gemm_bf16_nt_mid", stream);
+}
+
+// The argument checks of ldt_gemm_launch / ldt_gemm_lnfold_launch, which the two fused projection + attention routes run ahead of: a violation makes
+// the route return false, and the generic path then reports it.
+static bool mid_fused_operands_ok(const GemmArgs& g) {
+    return g.X && g.W && ldt_aligned16(g.X) && ldt_aligned16(g.W) && g.ldx >= g.K && g.ldw >= g.K && g.ldx % 8 == 0 && g.ldw % 8 == 0 && g.attn_o &&
+           ldt_aligned16(g.attn_o) && (!g.bias || ldt_aligned16(g.bias));
 }
 
 // QKV projection + self-attention in one launch (mid_epilogue_attn): 32-token samples, head dim 64, N = 3 * hidden with hidden % 64 == 0,
 // whole 128-row tiles (four samples each).  `folded`: a = the LN-folded consumer's arguments (stats per 32 columns).  LDT_QKV_ATTN=0: off (A/B).
-template <int FOLD>
-static int mid_qkv_attn_launch(const GemmArgs& a, hipStream_t stream) {
-    constexpr int lds = MidCfg<128, 192>::LDS;
-    LDT_ENSURE_LDS((&gemm_bf16_nt_mid_kernel<EPI_BF16, 128, 192, FOLD, MID_ATTN_SELF>), lds, "gemm_mid(qkv+attention)");
-    hipLaunchKernelGGL((gemm_bf16_nt_mid_kernel<EPI_BF16, 128, 192, FOLD, MID_ATTN_SELF>), dim3((unsigned)((a.M / 128) * (a.N / 192))), dim3(512), lds, stream, a);
-    return ldt_check_launch("gemm_bf16_nt_mid(qkv+attention)");
-}
-
 // The shape part of that rule (also ldt_qkv_attention_route's): reads M, N, K, stats_parts and max_wgs of `g`, no pointer.
 bool ldt_gemm_mid_qkv_attn_takes(const GemmArgs* a_in, int tokens, int head_dim, bool folded) {
     static const bool on = !(getenv("LDT_QKV_ATTN") && atoi(getenv("LDT_QKV_ATTN")) == 0);
-    if (!on || !mid_env() || tokens != 32 || head_dim != 64) return false;
+    if (!on || !mid_on() || tokens != 32 || head_dim != 64) return false;
     const GemmArgs& g = *a_in;
     if (g.M <= 0 || g.N <= 0 || g.N % 192 != 0 || (g.N / 3) % 64 != 0 || g.M % 128 != 0 || g.K % MID_BK != 0 || g.K / MID_BK < MidCfg<128, 192>::NS + 2) return false;
-    // the regime of this family (mid_shape_for): at most two rounds of workgroups — of the workgroups this launch may use when a sub-batch
+    // the regime of this family (mid_form_for): at most two rounds of workgroups — of the workgroups this launch may use when a sub-batch
     // stream caps its grids (a->max_wgs); larger batches (B >= 256 at 16 heads) stay with the persistent 256^2 GEMM + the resident
     // attention kernel.  No lower bound: a small batch saves a launch here and has nothing to lose to a bigger tile.
     const long wgs = (long)(g.M / 128) * (g.N / 192);
@@ -970,17 +946,11 @@ bool ldt_gemm_mid_qkv_attn_takes(const GemmArgs* a_in, int tokens, int head_dim,
     return !(folded && (g.stats_parts > 32 || g.stats_parts * 32 != g.K));
 }
 bool ldt_gemm_mid_qkv_attn_try(const GemmArgs* a_in, int tokens, int head_dim, bool folded, hipStream_t stream, int* status) {
-    if (!a_in->attn_o || !ldt_gemm_mid_qkv_attn_takes(a_in, tokens, head_dim, folded)) return false;
     const GemmArgs& g = *a_in;
-    if (folded && (!g.stats_in || !g.fold_S || !g.fold_C)) return false;
-    // the argument checks of ldt_gemm_launch / ldt_gemm_lnfold_launch, which this route runs ahead of (a violation returns false:
-    // the generic path then reports it)
-    if (!g.X || !g.W || !ldt_aligned16(g.X) || !ldt_aligned16(g.W) || g.ldx < g.K || g.ldw < g.K || g.ldx % 8 != 0 || g.ldw % 8 != 0) return false;
-    if (!ldt_aligned16(g.attn_o) || (g.bias && !ldt_aligned16(g.bias))) return false;
-    if (folded && (!ldt_aligned16(g.stats_in) || !ldt_aligned16(g.fold_S) || !ldt_aligned16(g.fold_C) || g.fold_step_stride % 4 != 0)) return false;
-    GemmArgs a = g;
-    a.col_major = 1;
-    *status = folded ? mid_qkv_attn_launch<MID_FOLD_CONSUMER>(a, stream) : mid_qkv_attn_launch<MID_FOLD_NONE>(a, stream);
+    if (!ldt_gemm_mid_qkv_attn_takes(a_in, tokens, head_dim, folded) || !mid_fused_operands_ok(g)) return false;
+    if (folded && !(g.stats_in && g.fold_S && g.fold_C && ldt_aligned16(g.stats_in) && ldt_aligned16(g.fold_S) && ldt_aligned16(g.fold_C) && g.fold_step_stride % 4 == 0))
+        return false;
+    *status = mid_dispatch(EPI_BF16, 128, 192, folded ? MID_FOLD_CONSUMER : MID_FOLD_NONE, MID_ATTN_SELF, g, "gemm_bf16_nt_mid(qkv+attention)", stream);
     return true;
 }
 
@@ -991,7 +961,7 @@ bool ldt_gemm_mid_qkv_attn_try(const GemmArgs* a_in, int tokens, int head_dim, b
 bool ldt_gemm_mid_q_xattn_takes(const GemmArgs* a_in, int tokens, int cond_tokens, int head_dim) {
     static const bool on = !(getenv("LDT_Q_XATTN") && atoi(getenv("LDT_Q_XATTN")) == 0);
     const GemmArgs& g = *a_in;
-    if (!on || !mid_env() || tokens != 32 || cond_tokens != 32 || head_dim != 64) return false;
+    if (!on || !mid_on() || tokens != 32 || cond_tokens != 32 || head_dim != 64) return false;
     if (g.M <= 0 || g.N <= 0 || g.N % 64 != 0 || g.M % 64 != 0 || g.K % MID_BK != 0 || g.K / MID_BK < 2) return false;
     const long wgs = (long)(g.M / 64) * (g.N / 64);
     const long cus = ldt_wg_limit(g.max_wgs);
@@ -999,20 +969,8 @@ bool ldt_gemm_mid_q_xattn_takes(const GemmArgs* a_in, int tokens, int cond_token
 }
 bool ldt_gemm_mid_q_xattn_try(const GemmArgs* a_in, int tokens, int cond_tokens, int head_dim, hipStream_t stream, int* status) {
     const GemmArgs& g = *a_in;
-    if (!g.attn_o || !g.attn_k || !g.attn_v || !ldt_gemm_mid_q_xattn_takes(a_in, tokens, cond_tokens, head_dim)) return false;
-    const long wgs = (long)(g.M / 64) * (g.N / 64);
-    if (!g.X || !g.W || !ldt_aligned16(g.X) || !ldt_aligned16(g.W) || g.ldx < g.K || g.ldw < g.K) return false;
-    if (!ldt_aligned16(g.attn_o) || !ldt_aligned16(g.attn_k) || !ldt_aligned16(g.attn_v) || g.attn_ldkv % 8 != 0 || g.attn_kv_batch_stride % 8 != 0 ||
-        (g.bias && !ldt_aligned16(g.bias)) || g.ldx % 8 != 0 || g.ldw % 8 != 0)
-        return false;
-    GemmArgs a = g;
-    a.col_major = 1;
-    constexpr int lds = MidCfg<64, 64>::LDS + MID_XKV_BYTES;
-    auto launch = [&]() -> int {
-        LDT_ENSURE_LDS((&gemm_bf16_nt_mid_kernel<EPI_BF16, 64, 64, MID_FOLD_NONE, MID_ATTN_CROSS>), lds, "gemm_mid(q+cross-attention)");
-        hipLaunchKernelGGL((gemm_bf16_nt_mid_kernel<EPI_BF16, 64, 64, MID_FOLD_NONE, MID_ATTN_CROSS>), dim3((unsigned)wgs), dim3(512), lds, stream, a);
-        return ldt_check_launch("gemm_bf16_nt_mid(q+cross-attention)");
-    };
-    *status = launch();
+    if (!ldt_gemm_mid_q_xattn_takes(a_in, tokens, cond_tokens, head_dim) || !mid_fused_operands_ok(g)) return false;
+    if (!(g.attn_k && g.attn_v && ldt_aligned16(g.attn_k) && ldt_aligned16(g.attn_v) && g.attn_ldkv % 8 == 0 && g.attn_kv_batch_stride % 8 == 0)) return false;
+    *status = mid_dispatch(EPI_BF16, 64, 64, MID_FOLD_NONE, MID_ATTN_CROSS, g, "gemm_bf16_nt_mid(q+cross-attention)", stream);
     return true;
 }

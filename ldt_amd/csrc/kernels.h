@@ -30,7 +30,7 @@ struct GemmArgs {
     int group_m;                        // 256-tile kernel: row panels per group of the tile order (set by the launcher)
     int dbg;                            // tools/dbg only (LDT_DBG_EPI bits: 1 no residual read, 2 no fp32 store, 4 no xs store, 8 no statistics)
     int max_wgs;                        // 256-tile kernel: cap on the persistent grid (0 = one workgroup per CU); sub-batch streams use 128
-    int col_major;                      // v1 kernel: tile order (set by the launcher; see gemm_bf16_nt_kernel)
+    int col_major;                      // v1 kernel only: tile order (set by ldt_gemm_launch; see gemm_bf16_nt_kernel)
     // ---- QKV projection + self-attention in one launch (gemm_mid.hip, 32-token samples, head dim 64): N = 3 * hidden columns [q | k | v];
     // the kernel writes O[B][H][32][64] (the reference's raw (B,N,C) buffer, model/layers.py:190-197) to attn_o and NOT the q | k | v rows
     bf16_t* attn_o; float attn_scale_log2e;
@@ -91,11 +91,10 @@ struct GemmRoute {
     int v1_shape, v1_stages;            // GEMM_ROUTE_V1: index of the instantiation (0 128x128, 1 128x64, 2 64x64) and its stages
 };
 GemmRoute ldt_gemm_decide(int epi, const GemmArgs* a, int granule);
-int ldt_gemm_mid_shape(int epi, const GemmArgs* a);                // gemm_mid.hip: (BM << 16) | BN of the mid-size tile kernel for this problem, 0 = not taken
-int ldt_gemm_mid_launch(int epi, int shape, const GemmArgs* a, hipStream_t stream);
-int ldt_gemm_mid_lnfold_shape(int epi, const GemmArgs* a);          // (BM << 16) | BN of the LN-folded form (statistics per 32 columns) of this GEMM, 0 = not taken
+// gemm_mid.hip, the mid-size tile kernels.  fold: 0 plain, 1 LN-folded producer, 2 consumer (statistics per 32 columns; gemm256_tile.h's FOLD_*)
+bool ldt_gemm_mid_route(int epi, int fold, const GemmArgs* a, GemmRoute* r);   // true + `r` filled (family GEMM_ROUTE_MID, tile, grid) when a form takes the problem
+int ldt_gemm_mid_launch(int epi, int fold, const GemmArgs* a, const GemmRoute& route, hipStream_t stream);   // route: ldt_gemm_decide's
 bool ldt_gemm_mid_lnfold_takes(int epi, int M, int N, int K);       // would the LN-folded form (statistics per 32 columns) of this GEMM be taken?
-int ldt_gemm_mid_lnfold_launch(int epi, int shape, const GemmArgs* a, hipStream_t stream);   // shape: ldt_gemm_mid_lnfold_shape's
 bool ldt_gemm_mid_qkv_attn_try(const GemmArgs* a, int tokens, int head_dim, bool folded, hipStream_t stream, int* status);
 bool ldt_gemm_qkv_attn256_try(const GemmArgs* a, int tokens, int head_dim, bool folded, hipStream_t stream, int* status);   // gemm_256.hip: fused QKV + self-attention at 256 tokens, Dh 64; false = not taken
 bool ldt_gemm_mid_q_xattn_try(const GemmArgs* a, int tokens, int cond_tokens, int head_dim, hipStream_t stream, int* status);   // fused q projection + cross-attention (32 x 32 tokens, Dh 64); false = not taken
