@@ -171,6 +171,12 @@ int ldt_sampler_step(const float* x, const float* params, const float* noise, in
                      const int32_t* step_ptr, int32_t step_host, int32_t mode,
                      int64_t n, int64_t elem_offset, uint64_t seed,
                      int32_t philox_mul, int32_t philox_add, void* stream);
+/* The same step with the sample loop's trajectory store: x after the step is also written to traj[step*n + i] (traj NULL: none). */
+int ldt_sampler_step_traj(const float* x, const float* params, const float* noise, int64_t noise_step_stride,
+                          float* x_out, float* x_mean_out, float* traj, const float* coef,
+                          const int32_t* step_ptr, int32_t step_host, int32_t mode,
+                          int64_t n, int64_t elem_offset, uint64_t seed,
+                          int32_t philox_mul, int32_t philox_add, void* stream);
 int ldt_philox_normal(float* out, int64_t n, int64_t elem_offset, int32_t step, uint64_t seed, void* stream);
 
 /* ---- LangevinCorrector (diffusion/diffusion_continuous.py:193-210) --------------------------------------

@@ -71,6 +71,7 @@ SIGNATURES = {
     "ldt_sgemm": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "ldt_sinusoid": [_vp, _vp, _vp, _i32, _i32, _vp],
     "ldt_sampler_step": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _u64, _i32, _i32, _vp],
+    "ldt_sampler_step_traj": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _u64, _i32, _i32, _vp],
     "ldt_philox_normal": [_vp, _i64, _i64, _i32, _u64, _vp],
     "ldt_batch_norm_sum": [_vp, _i32, _i64, _vp, _vp, _vp],
     "ldt_langevin_coef": [_vp, _i32, C.c_float, C.c_float, _vp, _vp],

@@ -138,6 +138,15 @@ extern "C" int ldt_sampler_step(const float* x, const float* params, const float
                (uint32_t)seed, (uint32_t)(seed >> 32), philox_mul, philox_add};
     return ldt_sampler_step_launch(&a, ST(stream));
 }
+extern "C" int ldt_sampler_step_traj(const float* x, const float* params, const float* noise, int64_t noise_step_stride,
+                                     float* x_out, float* x_mean_out, float* traj, const float* coef, const int32_t* step_ptr,
+                                     int32_t step_host, int32_t mode, int64_t n, int64_t elem_offset, uint64_t seed,
+                                     int32_t philox_mul, int32_t philox_add, void* stream) {
+    LDT_REQUIRE(!traj || ldt_aligned16(traj), LDT_EALIGN, "sampler_step_traj: traj must be 16-byte aligned");
+    StepArgs a{x, params, noise, x_out, x_mean_out, coef, step_ptr, step_host, mode, n, elem_offset, noise_step_stride,
+               (uint32_t)seed, (uint32_t)(seed >> 32), philox_mul, philox_add, traj};
+    return ldt_sampler_step_launch(&a, ST(stream));
+}
 
 extern "C" int ldt_philox_normal(float* out, int64_t n, int64_t elem_offset, int32_t step, uint64_t seed, void* stream) {
     LDT_REQUIRE(out, LDT_EARG, "philox_normal: null pointer");

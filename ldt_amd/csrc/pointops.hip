@@ -436,12 +436,14 @@ int ldt_gather_rows_launch(const float* src, const int* idx, int B, int n, int S
 }
 
 // max over the middle axis: in [G][n][C] (bf16 or fp32) -> out fp32 [G][C]   (adaptive_max_pool1d :186; MiniPointnet max :97)
+// A NaN in a column is the result, as in torch.max (fmaxf would drop it and an upstream NaN would vanish here); once m is NaN
+// every later `v > m` is false and `v != v` only replaces it by another NaN.
 template <typename TI>
 __global__ void maxpool_kernel(const TI* __restrict__ in, long ld, int n, int C, float* __restrict__ out, long G) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < G * C; i += (long)gridDim.x * blockDim.x) {
         const long g = i / C; const int c = (int)(i % C);
         float m = -INFINITY;
-        for (int j = 0; j < n; ++j) m = fmaxf(m, (float)in[(g * n + j) * ld + c]);
+        for (int j = 0; j < n; ++j) { const float v = (float)in[(g * n + j) * ld + c]; m = (v > m || v != v) ? v : m; }
         out[i] = m;
     }
 }

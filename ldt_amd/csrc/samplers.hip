@@ -218,7 +218,7 @@ __device__ __forceinline__ float block_act(float v, int kind) {
     switch (kind) {
         case LDT_BACT_GELU: return gelu_erf(v);
         case LDT_BACT_SILU: return silu(v);
-        case LDT_BACT_RELU: return fmaxf(v, 0.f);
+        case LDT_BACT_RELU: return (v > 0.f || v != v) ? v : 0.f;      // (fmaxf would turn a NaN into 0: torch.relu keeps it)
         case LDT_BACT_LEAKY_001: return v > 0.f ? v : 0.01f * v;
         case LDT_BACT_LEAKY_02: return v > 0.f ? v : 0.2f * v;
         case LDT_BACT_RRELU_EVAL: return v > 0.f ? v : v * ((1.0f / 8.0f + 1.0f / 3.0f) * 0.5f);

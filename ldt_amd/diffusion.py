@@ -578,8 +578,6 @@ class DiffusionBase:
                                              dtype=np.float64)).to(torch.float32)                    # :310-313
         alphas_cump = torch.cat((torch.ones(1), (1.0 - betas).cumprod(dim=0)))                     # :314-315 (train_N + 1)
         timesteps = torch.linspace(time_eps, 1.0, N * 2)                                             # :262
-        st = ops.stream_ptr
-
         def level(t):                                            # :264-265
             return int((train_N * (t - time_eps) + 1).long())
 
@@ -588,20 +586,11 @@ class DiffusionBase:
             d = at_next - at
             p = 1 / (at.sqrt() * (at.sqrt() + at_next.sqrt()))
             q = 1 / (at.sqrt() * (((1 - at_next) * at).sqrt() + ((1 - at) * at_next).sqrt()))
-            out = torch.empty_like(xx)
-            check(lib().ldt_pndm_transfer(xx.data_ptr(), et.data_ptr(), float(d), float(p), float(q), out.data_ptr(), xx.numel(), st()),
-                  "ldt_pndm_transfer")
-            return out
+            return ops.pndm_transfer(xx, et, float(d), float(p), float(q))
 
         def eps_at(t, xx):
             vec_t = (torch.ones((num_samples,)) * t).to(dev)
             return params_of(vec_t, xx, condition=condition, label=label).contiguous()
-
-        def lincomb(a, c, scale):
-            out = torch.empty_like(a[0])
-            check(lib().ldt_lincomb4(a[0].data_ptr(), a[1].data_ptr(), a[2].data_ptr(), a[3].data_ptr(), c[0], c[1], c[2], c[3],
-                                     scale, out.data_ptr(), out.numel(), st()), "ldt_lincomb4")
-            return out
 
         params_of = _params_fn(score_fn)
         ets = []
@@ -610,7 +599,7 @@ class DiffusionBase:
             if len(ets) > 2:                                     # :296-300 linear multistep
                 ets.append(eps_at(timesteps[idx * 2 - 1], x))
                 ets = ets[-4:]
-                noise = lincomb((ets[-1], ets[-2], ets[-3], ets[-4]), (55.0, -59.0, 37.0, -9.0), 1 / 24)
+                noise = ops.lincomb4((ets[-1], ets[-2], ets[-3], ets[-4]), (55.0, -59.0, 37.0, -9.0), 1 / 24)
             else:                                                # :276-292 Runge-Kutta warm-up
                 t1, t2, t3 = timesteps[idx * 2 - 1], timesteps[int((idx + t_next) / 2 * 2) - 1], timesteps[int(t_next * 2) - 1]
                 e1 = eps_at(t1, x)
@@ -618,7 +607,7 @@ class DiffusionBase:
                 e2 = eps_at(t2, transfer(x, t1, t2, e1))
                 e3 = eps_at(t2, transfer(x, t1, t2, e2))
                 e4 = eps_at(t3, transfer(x, t1, t3, e3))
-                noise = lincomb((e1, e2, e3, e4), (1.0, 2.0, 2.0, 1.0), 1 / 6)
+                noise = ops.lincomb4((e1, e2, e3, e4), (1.0, 2.0, 2.0, 1.0), 1 / 6)
             x = transfer(x, timesteps[idx * 2 - 1], timesteps[t_next * 2 - 1], noise)               # :304-307
         return x
 

@@ -9,7 +9,7 @@ from ._lib import (ACT_GELU, ACT_NONE, ACT_RELU, ACT_SILU, EPI_BF16, EPI_F32, EP
                    EPI_RESID_F32, check, lib)
 
 __all__ = ["cast_pad_bf16", "gemm_bf16", "layernorm_modulate", "attention_fwd", "sgemm", "sinusoid",
-           "sampler_step", "philox_normal", "pad64", "stream_ptr"]
+           "sampler_step", "pndm_transfer", "lincomb4", "philox_normal", "pad64", "stream_ptr"]
 
 
 def stream_ptr():
@@ -183,16 +183,58 @@ def sinusoid(t, freq):
 
 
 def sampler_step(x, params, coef, step, mode=0, noise=None, noise_step_stride=0, x_out=None, x_mean_out=None,
-                 step_ptr=None, elem_offset=0, seed=0, philox_mul=1, philox_add=0):
+                 step_ptr=None, elem_offset=0, seed=0, philox_mul=1, philox_add=0, traj=None):
+    """traj: optional fp32 [n_steps, x.numel()]; x after the step is also stored in row `step` (the sample loop's parity curve)."""
     _need(x, torch.float32, "x"); _need(params, torch.float32, "params"); _need(coef, torch.float32, "coef")
-    _need(noise, torch.float32, "noise")
+    _need(noise, torch.float32, "noise"); _need(traj, torch.float32, "traj")
     if x_out is None:
         x_out = torch.empty_like(x)
-    check(lib().ldt_sampler_step(_p(x), _p(params), _p(noise), noise_step_stride, _p(x_out), _p(x_mean_out), _p(coef),
-                                 _p(step_ptr), int(step), mode, x.numel(), elem_offset, seed, philox_mul, philox_add,
-                                 stream_ptr()),
-          "ldt_sampler_step")
+    if traj is None:
+        check(lib().ldt_sampler_step(_p(x), _p(params), _p(noise), noise_step_stride, _p(x_out), _p(x_mean_out), _p(coef),
+                                     _p(step_ptr), int(step), mode, x.numel(), elem_offset, seed, philox_mul, philox_add,
+                                     stream_ptr()),
+              "ldt_sampler_step")
+        return x_out
+    if traj.dim() != 2 or traj.shape[1] != x.numel() or not traj.is_contiguous():
+        raise ValueError("sampler_step: traj must be a contiguous fp32 [n_steps, %d] tensor, got %s" % (x.numel(), tuple(traj.shape)))
+    check(lib().ldt_sampler_step_traj(_p(x), _p(params), _p(noise), noise_step_stride, _p(x_out), _p(x_mean_out), _p(traj), _p(coef),
+                                      _p(step_ptr), int(step), mode, x.numel(), elem_offset, seed, philox_mul, philox_add,
+                                      stream_ptr()),
+          "ldt_sampler_step_traj")
     return x_out
+
+
+def _same_f32(ts, names, what):
+    """Every tensor fp32 on the device, contiguous, of one shape."""
+    for t, nm in zip(ts, names):
+        _need(t, torch.float32, nm)
+        if t.shape != ts[0].shape or not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous and of shape %s, got %s" % (what, nm, tuple(ts[0].shape), tuple(t.shape)))
+
+
+def pndm_transfer(x, et, d, p, q, out=None):
+    """PNDM transfer (diffusion_continuous.py:263-274): out = x + d * (p * x - q * et) in fp32, every product and sum rounded on its own
+    (the reference's operation order).  x, et fp32 of one shape; d, p, q python floats holding fp32 values."""
+    if out is None:
+        _need(x, torch.float32, "x")
+        out = torch.empty_like(x)
+    _same_f32((x, et, out), ("x", "et", "out"), "pndm_transfer")
+    check(lib().ldt_pndm_transfer(_p(x), _p(et), float(d), float(p), float(q), _p(out), x.numel(), stream_ptr()), "ldt_pndm_transfer")
+    return out
+
+
+def lincomb4(a, c, scale, out=None):
+    """out = scale * (((c0 a0 + c1 a1) + c2 a2) + c3 a3) in fp32, left to right, no contraction (PNDM's Runge-Kutta average and 4-step
+    combination, diffusion_continuous.py:291,300).  a: four fp32 tensors of one shape, c: four floats."""
+    if len(a) != 4 or len(c) != 4:
+        raise ValueError("lincomb4: four tensors with one coefficient each, got %d / %d" % (len(a), len(c)))
+    if out is None:
+        _need(a[0], torch.float32, "a[0]")
+        out = torch.empty_like(a[0])
+    _same_f32(tuple(a) + (out,), ("a[0]", "a[1]", "a[2]", "a[3]", "out"), "lincomb4")
+    check(lib().ldt_lincomb4(_p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), float(c[0]), float(c[1]), float(c[2]), float(c[3]), float(scale),
+                             _p(out), out.numel(), stream_ptr()), "ldt_lincomb4")
+    return out
 
 
 def batch_norm_sum(x, n_valid, per_sample, norms_scratch, sum_out):

@@ -816,3 +816,467 @@ def mlp_selection_probe(M, C, rows_per_sample, seed, gated, device="cpu"):
     assert torch.equal(bf16_round(h), h) and torch.equal(bf16_round(u), u) and float(h.min()) >= 8 and float(h.max()) <= 2040
     assert float((dd(x).abs() + gg.abs() * (u @ dd(w_dn).abs().T + dd(b_dn).abs())).max()) < 2 ** 22 and torch.equal(ref.float().double(), ref)
     return dict(x=x, shift=shift, scale=torch.full_like(shift, -1.0), gate=gate, w_up=w_up, b_up=torch.zeros(4 * C), w_dn=w_dn, b_dn=b_dn, ref=ref)
+
+
+# ------------------------------------------------------------------------------------------------------------- stream, encoder and metric helpers
+# (csrc/elementwise.hip, samplers.hip, metrics.hip and the lower half of pointops.hip; test_gpu_stream_kernels_exact.py; validated without a
+# GPU, planted faults included, by test_kernel_checks_host.py)
+#
+# Three kinds of check.  EXACT: kernels that promise the reference's operation order (`fp contract(off)`), copies, casts and selections are
+# held to torch.equal with the expression evaluated in fp32 by torch on the CPU.  PHILOX: the normal stream against a numpy Philox4x32-10 +
+# Box-Muller (philox_normal_ref).  BOUNDED: everything else against float64, the tolerance derived from the kernel's stated arithmetic: every
+# fp32 rounding 2^-24 relative (U24), every libm call LIBM[name] ulps of its result (one ulp <= 2^-23 relative, ULP32).
+ULP32 = 2.0 ** -23
+# No libm error bound for this device is written in the project, so none was assumed: every constant started at 1 ulp, the worst err / tol of the
+# classes that call the function was measured on the MI355X against float64, and the constant is the next power of two at or above that
+# ratio (cap 4; the measured ratios: DESIGN.md section 3 and test_gpu_stream_kernels_exact.py::test_zz_margins).  Measured at 1 ulp: expf 0.19-0.997
+# (actnorm, reparam, mixture_seed, the score kernels, silu, selu), powf 0.49 (sde_score kind 2), logf + sincosf 0.77 (the Philox stream), sinf /
+# cosf 0.61 (sinusoid), erff 0.34 (GELU): every constant stays at 1.
+LIBM = {"expf": 1.0, "logf": 1.0, "sincosf": 1.0, "powf": 1.0, "erff": 1.0}
+SLACK = 1 + 2.0 ** -10            # second-order terms of the first-order bounds below
+
+PHILOX_M0, PHILOX_M1, PHILOX_W0, PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+PHILOX_TAG = 0x4C445421           # the constant fourth counter word of csrc/elementwise.hip
+
+
+def philox4x32_10_np(ctr, k0, k1, swap_key_increments=False):
+    """Philox4x32-10 (Salmon et al. 2011) as csrc/common.h states it: ctr uint32 [n, 4], key (k0, k1) -> uint32 [n, 4].  swap_key_increments:
+    the planted fault of the host tests (the two Weyl constants exchanged)."""
+    import numpy as np
+    c = [np.asarray(ctr)[:, i].astype(np.uint64) for i in range(4)]
+    k0, k1 = int(k0) & 0xFFFFFFFF, int(k1) & 0xFFFFFFFF
+    w0, w1 = (PHILOX_W1, PHILOX_W0) if swap_key_increments else (PHILOX_W0, PHILOX_W1)
+    mask = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(PHILOX_M0) * c[0], np.uint64(PHILOX_M1) * c[2]
+        n0 = (p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0)
+        n2 = (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1)
+        c = [n0, p1 & mask, n2, p0 & mask]
+        k0, k1 = (k0 + w0) & 0xFFFFFFFF, (k1 + w1) & 0xFFFFFFFF
+    return np.stack(c, 1).astype(np.uint32)
+
+
+def box_muller_ref(a, b, swap_sin_cos=False):
+    """csrc/common.h box_muller on uint32 arrays: u1 = ((float)a + 1) 2^-32, u2 = (float)b 2^-32 and the angle 6.2831855f u2 formed in float32
+    (those roundings are defined), log / sqrt / sin / cos in float64 on the float32 values.  -> (z0 = r cos, z1 = r sin, relative tolerance):
+    logf's error is halved by the square root, which is correctly rounded like the product; sincosf's enters in full."""
+    import numpy as np
+    u1 = (a.astype(np.float32) + np.float32(1.0)) * np.float32(2.0 ** -32)
+    u2 = b.astype(np.float32) * np.float32(2.0 ** -32)
+    ang = (np.float32(6.283185307179586) * u2).astype(np.float64)
+    r = np.sqrt(-2.0 * np.log(u1.astype(np.float64)))
+    cs, sn = np.cos(ang), np.sin(ang)
+    if swap_sin_cos:
+        cs, sn = sn, cs
+    rel = ((0.5 * LIBM["logf"] + LIBM["sincosf"]) * ULP32 + 2 * U24) * SLACK
+    return r * cs, r * sn, rel
+
+
+def philox_normal_ref(seed, step, first_vec, n_vec, swap_key_increments=False, step_word=2, swap_sin_cos=False):
+    """The normal stream of ldt_philox_normal / ldt_sampler_step(noise = NULL): float64 [n_vec, 4] and its tolerance [n_vec, 4] for the 4-vectors
+    first_vec .. first_vec + n_vec - 1 (vector e = elem_offset / 4 + i holds elements 4 e .. 4 e + 3).  Counter {lo32(e), hi32(e), step,
+    0x4C445421}, key = (lo32(seed), hi32(seed)) as csrc/api.hip splits it; lanes (z0, z1) = Box-Muller(c0, c1), (z2, z3) = Box-Muller(c2, c3).
+    The keyword arguments plant faults for the host tests (step_word = 3: step and the tag word exchanged)."""
+    import numpy as np
+    e = np.uint64(int(first_vec)) + np.arange(int(n_vec), dtype=np.uint64)
+    ctr = np.zeros((int(n_vec), 4), dtype=np.uint32)
+    ctr[:, 0] = (e & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    ctr[:, 1] = (e >> np.uint64(32)).astype(np.uint32)
+    ctr[:, step_word] = np.uint32(int(step) & 0xFFFFFFFF)
+    ctr[:, 5 - step_word] = np.uint32(PHILOX_TAG)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    c = philox4x32_10_np(ctr, seed & 0xFFFFFFFF, seed >> 32, swap_key_increments)
+    z0, z1, rel = box_muller_ref(c[:, 0], c[:, 1], swap_sin_cos)
+    z2, z3, _ = box_muller_ref(c[:, 2], c[:, 3], swap_sin_cos)
+    z = torch.from_numpy(np.stack([z0, z1, z2, z3], 1))
+    return z, z.abs() * rel
+
+
+def sweep_windows(n_items, block_items, cap_blocks, width):
+    """Where a grid-stride fault shows: [(start, stop), ...] (merged, ascending, inside [0, n_items)) covering the first `width` items, `width`
+    items either side of every multiple of the sweep cap_blocks * block_items below n_items, and the last `width` items."""
+    sweep = cap_blocks * block_items
+    raw = [(0, width), (n_items - width, n_items)] + [(k - width, k + width) for k in range(sweep, n_items, sweep)]
+    out = []
+    for a, b in sorted((max(a, 0), min(b, n_items)) for a, b in raw):
+        if a >= b:
+            continue
+        if out and a <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], b))
+        else:
+            out.append((a, b))
+    return out
+
+
+def window_index(windows, device="cpu"):
+    """The windows of sweep_windows as one int64 index tensor."""
+    return torch.cat([torch.arange(a, b, device=device) for a, b in windows])
+
+
+AMBIGUOUS_CAP = 0.02
+
+
+def assert_bf16_of(out, ref64, acc, what):
+    """out (bf16 or its values) == bf16_round(ref64) bit for bit, except where ref64 lies within acc (+ 2^-24 |ref64|) of a bf16 rounding
+    boundary (ambiguous_ulp): there either neighbour is allowed.  NaN in the reference demands NaN, an infinity itself.  At most 2 % of the
+    elements may be ambiguous (a condition on the reference: otherwise the test is not testing; choose other inputs).  -> ambiguous share."""
+    assert tuple(out.shape) == tuple(ref64.shape), "%s: shape %s vs reference %s" % (what, tuple(out.shape), tuple(ref64.shape))
+    o = out.double()
+    ref64 = ref64.to(o.device).double()
+    acc = acc.to(o.device).double().expand_as(ref64) if torch.is_tensor(acc) else torch.full_like(ref64, float(acc))
+    fin = torch.isfinite(ref64)
+    want = bf16_round(ref64)
+    allow = torch.where(fin, ambiguous_ulp(torch.where(fin, ref64, torch.zeros_like(ref64)), acc), torch.zeros_like(ref64))
+    allow = torch.where((ref64 == 0) & (acc == 0), torch.zeros_like(allow), allow)            # an exact zero is 0, not `ambiguous`
+    share = float((allow > 0).double().mean()) if allow.numel() else 0.0
+    assert share <= AMBIGUOUS_CAP, "%s: %.4f of the elements are within their accumulation error of a rounding boundary (cap %.2f)" % (what, share, AMBIGUOUS_CAP)
+    nan = torch.isnan(ref64)
+    ok = torch.where(nan, torch.isnan(o), torch.where(fin, (o == want) | ((o - want).abs() <= allow), o == ref64))
+    if not bool(ok.all()):
+        bad = ~ok
+        C = ref64.shape[-1] if ref64.dim() else 1
+        i = int(torch.nonzero(bad.reshape(-1))[0])
+        raise AssertionError("%s: %d of %d elements are not bf16(reference) (nor its neighbour where that is allowed).  First at (row %d, col %d): got %r, "
+                             "want %r (reference %r, allowance %.3g)" % (what, int(bad.sum()), bad.numel(), i // C, i % C, float(o.reshape(-1)[i]),
+                                                                         float(want.reshape(-1)[i]), float(ref64.reshape(-1)[i]), float(allow.reshape(-1)[i])))
+    return share
+
+
+def resolved_by_bf16(ref64, acc):
+    """Mask: the fp32 evaluation resolves a bf16 ulp there (acc <= a quarter ulp).  Elsewhere (a cancellation tail such as GELU below -5, where
+    1 + erf is a few fp32 ulps) assert_bf16_of cannot apply and the absolute bound acc + bf16 rounding (assert_elementwise) is the check."""
+    return torch.isfinite(ref64) & (acc <= 0.25 * bf16_ulp(ref64))
+
+
+# ---- block activations (samplers.hip block_act): float64 definition and what the fp32 evaluation may move
+BLOCK_ACT_KINDS = {"gelu": 1, "silu": 2, "relu": 3, "leakyrelu": 4, "leakyrelu0.2": 5, "rrelu": 6, "hardswish": 7, "selu": 8}
+SELU_SCALE, SELU_ALPHA = 1.0507009873554804934193349852946, 1.6732632423543772848170429916717
+RRELU_EVAL_SLOPE = float((torch.tensor(1.0 / 8.0, dtype=torch.float32) + torch.tensor(1.0 / 3.0, dtype=torch.float32)) * 0.5)
+# one select and at most ONE fp32 product: a defined rounding, held bit for bit.  (rrelu too: x (11 / 48) for an 8-bit x lands on or next to a bf16
+# rounding boundary for 5 % of all inputs, so a bound that allows either neighbour there would not meet assert_bf16_of's cap.)
+EXACT_ACTS = ("relu", "leakyrelu", "leakyrelu0.2", "rrelu")
+EXPF_MAX_ARG = 88.72283905206835      # log(FLT_MAX): above it expf is +inf
+
+
+def block_act_exact(x, kind):
+    """relu, the two leaky kinds and eval-mode rrelu in fp32 by torch on the CPU: one select and at most one product, bf16 in and out.  NaN stays NaN."""
+    v = x.float()
+    if kind == "relu":
+        r = torch.where(v > 0, v, torch.where(torch.isnan(v), v, torch.zeros_like(v)))
+    else:
+        slope = {"leakyrelu": 0.01, "leakyrelu0.2": 0.2, "rrelu": RRELU_EVAL_SLOPE}[kind]
+        r = torch.where(v > 0, v, torch.tensor(slope, dtype=torch.float32) * v)
+    return r.bfloat16()
+
+
+def block_act_ref(x, kind):
+    """float64 definition of block activation `kind` on bf16-exact inputs and acc, what the kernel's fp32 evaluation may differ by (before the
+    bf16 rounding).  Infinite inputs follow the kernel's formula in IEEE arithmetic (0 x inf = NaN); NaN gives NaN.
+      gelu      0.5 x (1 + erf(x / sqrt 2)): the argument's rounding through erf', erff, the sum's rounding; all three scaled by 0.5 |x| (for x < -5
+                the sum cancels to a few ulps of 1: acc then exceeds the result, see resolved_by_bf16), two products
+      silu      x / (1 + exp(-x)): expf, the sum, the quotient; exp(-x) = inf above 88.72 gives -0 where the definition is ~1e-37: allowed in full
+      hardswish x min(max(x + 3, 0), 6) (1/6): the sum (where the clamp passes it), two products and the constant (as / 6: one fewer); x 6 = inf above 5.67e37
+      selu      scale x | scale alpha (exp(x) - 1): expf, the difference (cancelling near 0: absolute 2^-24 exp(x)), two products and constants."""
+    v = x.double()
+    if kind == "gelu":
+        a = v * 0.70710678118654752440
+        s = 1 + torch.erf(a)
+        ref = 0.5 * v * s
+        d_s = a.abs() * U24 * (2 / 3.141592653589793 ** 0.5) * torch.exp(-a * a) * 2 + LIBM["erff"] * ULP32 * torch.erf(a).abs() + U24 * s.abs()
+        acc = 0.5 * v.abs() * d_s + 2 * U24 * ref.abs()
+    elif kind == "silu":
+        e = torch.exp(-v)
+        ref = v / (1 + e)
+        acc = ref.abs() * ((LIBM["expf"] * ULP32 + U24) * e / (1 + e) + 2 * U24)
+        acc = torch.where(-v > EXPF_MAX_ARG, ref.abs(), acc)
+    elif kind == "hardswish":
+        s3 = v + 3
+        ref = v * torch.clamp(s3, 0, 6) / 6
+        ref = torch.where(v * 6 > 3.4028234663852886e38, torch.full_like(v, float("inf")), ref)      # the formula's x * 6 overflows fp32
+        acc = v.abs() * U24 * torch.where((s3 > 0) & (s3 < 6), s3, torch.zeros_like(s3)) / 6 + 3 * U24 * ref.abs()
+    elif kind == "selu":
+        e = torch.exp(v)
+        ref = torch.where(v > 0, SELU_SCALE * v, SELU_SCALE * SELU_ALPHA * torch.expm1(v))
+        neg = SELU_SCALE * SELU_ALPHA * (LIBM["expf"] * ULP32 * e + U24 * (e - 1).abs()) + 4 * U24 * ref.abs()
+        acc = torch.where(v > 0, 2 * U24 * ref.abs(), neg)
+    else:
+        raise KeyError(kind)
+    ref = torch.where(torch.isnan(v), v, ref)
+    return ref, torch.where(torch.isfinite(ref), acc * SLACK, torch.zeros_like(acc))
+
+
+# ---- LangevinCorrector (samplers.hip)
+def batch_norms_ref(x):
+    """ldt_batch_norm_sum on x [B, per]: float64 per-sample L2 norms [B], their sum, and tolerances.  A lane adds k = ceil(per / 1024) groups of
+    four squares (4 products, 3 sums inside a group) to its accumulator, then 6 shuffle and 2 LDS tree additions: all terms are positive, so
+    (k + 12) 2^-24 relative on the sum of squares (an FMA only removes roundings), halved by the correctly rounded sqrt + its own rounding.
+    The batch sum: ceil(B / 64) additions per lane + 6 shuffles on top of the norms' own tolerances."""
+    B, per = x.shape
+    k = -(-per // 1024)
+    n = x.double().pow(2).sum(1).sqrt()
+    tn = n * ((k + 12) * 0.5 + 1) * U24 * SLACK
+    s = n.sum()
+    return n, s, tn, tn.sum() + (-(-B // 64) + 6) * U24 * (s + tn.sum()) * SLACK
+
+
+def langevin_coef_ref(sums, n_total, snr, std_t):
+    """ldt_langevin_coef: float64 {1, -step / std, sqrt(2 step), 0} from the fp32 operands, and tolerances.  grad_norm, noise_norm and r take 5
+    fp32 roundings, step = 2 r r then carries 11, -step / std 12, sqrt(2 step) 11 / 2 + 1; 1 and 0 are exact."""
+    f32 = lambda v: float(torch.tensor(float(v), dtype=torch.float32))
+    s0, s1, snr, std = float(sums[0]), float(sums[1]), f32(snr), f32(std_t)
+    r = snr * (s1 / n_total) / ((s0 / n_total) / std)
+    step = 2 * r * r
+    ref = torch.tensor([1.0, -step / std, (2 * step) ** 0.5, 0.0], dtype=torch.float64)
+    return ref, ref.abs() * torch.tensor([0.0, 12.0, 6.5, 0.0], dtype=torch.float64) * U24 * SLACK
+
+
+# ---- score = -params / sqrt(var(t)) (samplers.hip vpsde_score / sde_score)
+def sde_score_ref(params, t, kind, c0, c1, c2):
+    """float64 -params / sqrt(var(t)) of SDE family `kind` from the fp32 operands (params [B, ...], t [B], constants as the kernel receives them:
+    rounded to fp32), its tolerance, and `resolved` [B]: whether fp32 resolves var at all (var > 2 dvar; at t = 1e-6 with sigma2_0 = 0 it
+    does not: var ~ 1e-7 is one ulp of e = exp(..) ~ 1, and nothing but finiteness can be asked there).
+    One libm error in e (kinds 0, 1: expf of an argument that itself carries the roundings of a = -c0 t, b = 0.5 (c1 - c0) t t and a - b) or in
+    powf (kind 2) is carried through var analytically: kind 0 var = 1 - (1 - c2) e; kind 1 var = (1 - e)^2 + c2 e, where 1 - e keeps e's absolute
+    error and cancels at small t; kind 2 var = c0 c1^t - c0 + c2.  Then sqrt (correctly rounded) and the quotient."""
+    f32 = lambda v: torch.tensor(float(v), dtype=torch.float32).double()
+    c0, c1, c2 = f32(c0), f32(c1), f32(c2)
+    tb = t.double()
+    if kind == 2:
+        P = torch.pow(c1, tb)
+        var = c0 * P - c0 + c2
+        dvar = c0 * P * (LIBM["powf"] * ULP32 + U24) + U24 * (c0 * P - c0).abs() + U24 * var.abs()
+    else:
+        a, b = -c0 * tb, 0.5 * (c1 - c0) * tb * tb
+        e = torch.exp(a - b)
+        de = e * (U24 * (a.abs() + 3 * b.abs() + (a - b).abs()) + LIBM["expf"] * ULP32)
+        if kind == 1:
+            om = 1 - e
+            dom = de + U24 * om.abs()
+            var = om * om + c2 * e
+            dvar = 2 * om.abs() * dom + dom * dom + U24 * om * om + c2 * (de + U24 * e) + U24 * var
+        else:
+            var = 1 - (1 - c2) * e
+            dvar = (1 - c2) * (de + 2 * U24 * e) + U24 * var.abs()
+    dvar = dvar * SLACK
+    resolved = var > 2 * dvar
+    sd = var.clamp_min(0).sqrt()
+    lo, hi = (var - dvar).clamp_min(0).sqrt(), (var + dvar).sqrt()
+    shape = (-1,) + (1,) * (params.dim() - 1)
+    p = params.double()
+    ref = -p / sd.reshape(shape)
+    rel = torch.where(resolved, torch.maximum(sd / lo - 1, 1 - sd / hi) + 2 * U24, torch.full_like(sd, float("inf")))
+    return ref, ref.abs() * rel.reshape(shape) * SLACK, resolved
+
+
+# ---- encoder helpers (pointops.hip)
+def actnorm_ref(x, shift, log_scale):
+    """ActNorm (eval): float64 (x - shift) exp(-log_scale) on x [B, per], parameters [per]; one difference, expf, one product."""
+    ref = (x.double() - shift.double()) * torch.exp(-log_scale.double())
+    return ref, ref.abs() * (2 * U24 + LIBM["expf"] * ULP32) * SLACK
+
+
+def reparam_ref(post, noise, lo, hi):
+    """ldt_reparam: mu, logvar = clamp(post[:, z:], lo, hi) (both selections: exact, compared bit for bit) and float64 eps = mu + exp(logvar / 2)
+    noise with its tolerance: logvar / 2 is exact, expf, then ONE fused multiply-add (common.h reparam_eps)."""
+    z = post.shape[1] // 2
+    mu, lv = post[:, :z].clone(), post[:, z:].clamp(float(torch.tensor(lo, dtype=torch.float32)), float(torch.tensor(hi, dtype=torch.float32)))
+    prod = noise.double() * torch.exp(lv.double() / 2)
+    ref = mu.double() + prod
+    return mu, lv, ref, (prod.abs() * LIBM["expf"] * ULP32 + U24 * ref.abs()) * SLACK
+
+
+def mixture_seed_ref(eps, sig, mu, logits):
+    """InitialSet mixture rows: float64 sum_m (eps[r, m] sig[m] + mu[m]) softmax(logits)[m] and its tolerance.  A weight w_m carries the rounding
+    of d_m = logit_m - max (|d_m| 2^-24 through exp), expf, the same for the largest term of the denominator + its n_mix - 1 additions, and the
+    quotient; a weight that underflows (d_m < -87) is in error by itself, at most 2^-126.  A term carries product, sum and product with w (an
+    FMA removes one), the accumulation n_mix additions."""
+    n_mix = logits.numel()
+    d = logits.double() - logits.double().max()
+    w = torch.softmax(logits.double(), 0)
+    rw = d.abs() * U24 + LIBM["expf"] * ULP32
+    rw = rw + rw.max() + n_mix * U24
+    es = eps.double() * sig.double()
+    pre = es + mu.double()                                                  # [rows, n_mix, D]
+    wv = w[None, :, None]
+    term = pre * wv
+    ref = term.sum(1)
+    tol = (wv * (es.abs() * U24 + pre.abs() * (2 * U24 + rw[None, :, None])) + 2.0 ** -126 * pre.abs()).sum(1) + n_mix * U24 * term.abs().sum(1)
+    return ref, tol * SLACK
+
+
+def norm_points_ref(xyz, unbiased=True):
+    """Compressor.norm_pts: float64 (p - mean) / std per cloud and coordinate (UNBIASED std, torch.std's default, Network.py:170-174) on xyz
+    [B, n, 3] and its tolerance.  The kernel sums in fp64 (ceil(n / 256) + 12 additions; var = (q - n mean^2) / (n - 1) cancels, so those
+    2^-53 count against q + n mean^2), then rounds mean and 1 / std to fp32 BEFORE use: 2^-24 |mean| / std absolute, 2^-24 relative; the
+    difference and the product round once each."""
+    p = xyz.double()
+    n = p.shape[1]
+    mean = p.mean(1, keepdim=True)
+    var = p.var(1, unbiased=unbiased, keepdim=True)
+    inv = 1 / var.sqrt()
+    ref = (p - mean) * inv
+    q = (p * p).sum(1, keepdim=True)
+    rel64 = 0.5 * (-(-n // 256) + 12) * 2.0 ** -53 * (q + n * mean * mean) / ((n - 1) * var)
+    return ref, (U24 * mean.abs() * inv + ref.abs() * (3 * U24 + rel64)) * SLACK
+
+
+def group_stats_ref(x, B, T, C, G, eps, unbiased=False, eps_outside=False):
+    """nn.GroupNorm's statistics (BIASED variance, eps inside the square root) on token-major rows x [B T, C]: float64 [B, G, 2] = (mean,
+    1 / sqrt(var + eps)) and its tolerance: fp64 sums (2^-53 per addition against sum |x| and sum x^2, ceil(T cg / 256) + 10 of them), then one
+    rounding to fp32 each.  unbiased / eps_outside: the planted faults of the host tests."""
+    cg = C // G
+    xd = x.double()[:, :C].reshape(B, T, G, cg).permute(0, 2, 1, 3).reshape(B, G, T * cg)
+    n = T * cg
+    mean = xd.mean(2)
+    var = xd.var(2, unbiased=unbiased) if n > 1 else torch.zeros_like(mean)
+    e = float(torch.tensor(eps, dtype=torch.float32))
+    rstd = 1 / (var.sqrt() + e) if eps_outside else 1 / torch.sqrt(var + e)
+    adds = (-(-n // 256) + 10) * 2.0 ** -53
+    dvar = adds * ((xd * xd).mean(2) + mean * mean) * 2
+    ref = torch.stack([mean, rstd], -1)
+    tol = torch.stack([U24 * mean.abs() + adds * xd.abs().mean(2), rstd * (U24 + 0.5 * dvar / (var + e))], -1)
+    return ref, tol * SLACK
+
+
+def norm_apply_ref(x, stats=None, rows_per_stat=1, w=None, b=None, shift=None, scale=None, rows_per_sample=1):
+    """ldt_norm_apply before its bf16 rounding, float64 from the fp32 operands (stats [S, G, 2] fp32 as the kernel reads them; None: identity):
+    pre = ((x - mean) rstd [w + b]) [(1 + scale) + shift] and acc, what fp32 may move: a rounding per operation (a product-sum pair may fuse:
+    never more), the rounding of 1 + scale carried through the product.  x [M, C]; shift / scale [nS, C] by row // rows_per_sample."""
+    xd = x.double()
+    M, C = xd.shape
+    if stats is not None:
+        G = stats.shape[1]
+        st = stats.double()[torch.arange(M, device=x.device) // rows_per_stat]                   # [M, G, 2]
+        mean, rstd = st[:, :, 0].repeat_interleave(C // G, 1), st[:, :, 1].repeat_interleave(C // G, 1)
+        pre = (xd - mean) * rstd
+        acc = 2 * U24 * pre.abs()
+    else:
+        pre, acc = xd, torch.zeros_like(xd)
+    if w is not None:
+        pw = pre * w.double()
+        pre = pw + b.double()
+        acc = acc * w.double().abs() + U24 * pw.abs() + U24 * pre.abs()
+    if scale is not None:
+        sc = 1 + sample_rows(scale, M, rows_per_sample)
+        ps = pre * sc
+        pre2 = ps + sample_rows(shift, M, rows_per_sample)
+        acc = acc * sc.abs() + 2 * U24 * ps.abs() + U24 * pre2.abs()
+        pre = pre2
+    return pre, acc * SLACK
+
+
+def sinusoid_ref(t, freq):
+    """float64 [n, 2 half] = [sin(a) | cos(a)] of the FLOAT32 product a = t f (the kernel's __fmul_rn: a defined rounding) and the tolerance
+    LIBM['sincosf'] ulps of each value."""
+    a = (t.float()[:, None] * freq.float()[None, :]).double()
+    ref = torch.cat([torch.sin(a), torch.cos(a)], 1)
+    return ref, ref.abs() * LIBM["sincosf"] * ULP32 * SLACK
+
+
+# ---- Chamfer (pointops.hip chamfer_min_kernel, metrics.hip chamfer_pairwise_kernel)
+CHAMFER_ROUNDINGS = 9
+
+
+def chamfer_dir_ref(q, r):
+    """min_j |q_i - r_j|^2 for q [B, nq, 3] against r [B, nr, 3]: float64 [B, nq] and its tolerance.  The kernels evaluate the reference's expanded
+    form (|q|^2 + |r|^2) - 2 q.r: three roundings in each squared norm, one in their sum, three in the dot product (|q.r| <= (|q|^2 + |r|^2) / 2,
+    doubled exactly), one in the difference (<= 2 (|q|^2 + |r|^2)): 9 2^-24 (|q|^2 + |r|^2), ABSOLUTE — it does not shrink with the distance.
+    A minimum moves by at most the largest perturbation of its candidates: 9 2^-24 (|q_i|^2 + max_j |r_j|^2)."""
+    qd, rd = q.double(), r.double()
+    ref = torch.cat([(qd[:, i:i + 256, None, :] - rd[:, None, :, :]).pow(2).sum(-1).min(2).values for i in range(0, qd.shape[1], 256)], 1)
+    tol = CHAMFER_ROUNDINGS * U24 * (qd.pow(2).sum(-1) + rd.pow(2).sum(-1).max(1, keepdim=True).values) * SLACK
+    return ref, tol
+
+
+def chamfer_ref(a, b):
+    """ops.chamfer(a [B, na, 3], b [B, nb, 3]) -> ((dl [B, nb], tol), (dr [B, na], tol)): dl = for every point of b its nearest a."""
+    return chamfer_dir_ref(b, a), chamfer_dir_ref(a, b)
+
+
+def chamfer_pairwise_ref(x, y):
+    """ops.chamfer_pairwise(x [S, n, 3], y [R, m, 3]): float64 cd [S, R] = mean_j min_i + mean_i min_j and its tolerance: the per-query bound of
+    chamfer_dir_ref through the mean, plus the summation (4 ceil(nq / 1024) additions per lane, 6 shuffles, 2 LDS, the quotient) against the mean
+    of the magnitudes, plus the final sum's rounding."""
+    S, n = x.shape[:2]
+    R, m = y.shape[:2]
+    ref, tol = torch.zeros(S, R, dtype=torch.float64, device=x.device), torch.zeros(S, R, dtype=torch.float64, device=x.device)
+    for s in range(S):
+        for r in range(R):
+            for qq, rr in ((y[r:r + 1], x[s:s + 1]), (x[s:s + 1], y[r:r + 1])):
+                d, t = chamfer_dir_ref(qq, rr)
+                nq = qq.shape[1]
+                mean = d.mean()
+                tm = t.mean() + (4 * -(-nq // 1024) + 9) * U24 * (d.abs() + t).mean()
+                ref[s, r] += mean
+                tol[s, r] += tm
+    return ref, (tol + U24 * ref.abs()) * SLACK
+
+
+# ---- the expressions the exact kernels are held to (fp32 by torch on the CPU: every product and sum rounds on its own, as `fp contract(off)`)
+def fma32(a, b, c):
+    """float32(a b + c) with ONE rounding (the product of two fp32 values is exact in float64): what a contraction to FMA would compute."""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def sampler_step_expr(x, p, z, cf, mode, fused=False):
+    """ldt_sampler_step on fp32 tensors with the coefficient row cf [4] -> (x_mean, x_next).  mode 0: score = -p / std, x_mean = (x + beta score) /
+    sqrt(1 - beta), x = x_mean + sqrt(beta) z with cf = {beta, std, sqrt(1 - beta), sqrt(beta)}; mode 1: x_mean = A x + B p, x = x_mean + C z.
+    fused: the planted fault (mode 1 with A x + B p and x_mean + C z contracted)."""
+    if mode == 0:
+        xm = (x + cf[0] * (-p / cf[1])) / cf[2]
+        return xm, xm + cf[3] * z
+    if fused:
+        xm = fma32(cf[0], x, cf[1] * p)
+        return xm, fma32(cf[2], z, xm)
+    xm = cf[0] * x + cf[1] * p
+    return xm, xm + cf[2] * z
+
+
+def pndm_transfer_expr(x, et, d, p, q, fused=False):
+    """x + d (p x - q et) with the three scalars as fp32; fused: p x - q et and x + d (..) contracted (the planted fault)."""
+    d, p, q = [torch.tensor(float(v), dtype=torch.float32) for v in (d, p, q)]
+    if fused:
+        return fma32(d, fma32(p, x, -(q * et)), x)
+    return x + d * (p * x - q * et)
+
+
+def lincomb4_expr(a, c, s, fused=False):
+    """s (((c0 a0 + c1 a1) + c2 a2) + c3 a3), left to right; fused: every sum contracted with its product (the planted fault)."""
+    c = [torch.tensor(float(v), dtype=torch.float32) for v in c]
+    s = torch.tensor(float(s), dtype=torch.float32)
+    if fused:
+        return s * fma32(c[3], a[3], fma32(c[2], a[2], fma32(c[1], a[1], c[0] * a[0])))
+    return s * (((c[0] * a[0] + c[1] * a[1]) + c[2] * a[2]) + c[3] * a[3])
+
+
+PNDM_COEF_SETS = (((55.0, -59.0, 37.0, -9.0), 1 / 24), ((1.0, 2.0, 2.0, 1.0), 1 / 6))
+
+
+def maxpool_expr(x, G, n):
+    """max over the n rows of each group of the row-major view x [G n, C] (any row stride), fp32 [G, C]; NaN propagates (torch.max)."""
+    return x.float().reshape(G, n, x.shape[1]).max(1).values
+
+
+def check_block_act(out, x, kind, what):
+    """ldt_block_activation's bf16 `out` for bf16 inputs `x` (any shape): relu and the leaky kinds == block_act_exact; the others == bf16(float64
+    definition) where fp32 resolves a bf16 ulp (assert_bf16_of) and within acc + the bf16 rounding elsewhere (assert_elementwise); NaN in ->
+    NaN out.  -> (worst err / tol over the unresolved elements, ambiguous share of the resolved ones)."""
+    if kind in EXACT_ACTS:
+        want = block_act_exact(x, kind).to(out.device)
+        same = (out == want) | (torch.isnan(out) & torch.isnan(want))
+        assert bool(same.all()), "%s: %d elements differ from the fp32 expression (first at flat index %d)" % (
+            what, int((~same).sum()), int(torch.nonzero(~same.reshape(-1))[0]))
+        return 0.0, 0.0
+    ref, acc = block_act_ref(x.to(out.device), kind)
+    res = resolved_by_bf16(ref, acc) | ~torch.isfinite(ref)
+    share = assert_bf16_of(out[res].reshape(1, -1), ref[res].reshape(1, -1), acc[res].reshape(1, -1), what)
+    ratio = 0.0
+    if bool((~res).any()):
+        r = ref[~res].reshape(1, -1)
+        ratio = assert_elementwise(out[~res].reshape(1, -1), r, acc[~res].reshape(1, -1) * (1 + U8) + U8 * r.abs() + 2.0 ** -133, what + " (cancellation tail)")
+    return ratio, share
+
+
+def all_bf16_patterns():
+    """Every bf16 bit pattern once, as a [512, 128] bf16 tensor."""
+    return torch.arange(65536, dtype=torch.int32).to(torch.int16).view(torch.bfloat16).reshape(512, 128)

@@ -711,3 +711,392 @@ def test_planted_ln_linear_fault_fails_the_interval_and_the_probes():
     assert torch.equal(emulate_ln_linear(d["x"], w, None, kwp), ref)
     assert not torch.equal(emulate_ln_linear(d["x"], w, None, kwp, fault="swap_out_chunks"), ref)
     assert not torch.equal(emulate_ln_linear(d["x"], w, None, kwp, fault="tile1_mod"), ref)
+
+
+# ------------------------------------------------------------------------------------------------------------- stream, encoder and metric helpers
+# (test_gpu_stream_kernels_exact.py's references.)  For every helper: a torch-on-the-CPU fp32 emulation of the kernel's contract passes, benign
+# variants (another summation order, / 6 for * (1 / 6)) pass, and the emulation with one planted fault fails.
+def fails(fn, *a, **k):
+    with pytest.raises(AssertionError):
+        fn(*a, **k)
+
+
+PHILOX_KAT = [((0, 0, 0, 0), (0, 0), (0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8)),
+              ((0xffffffff,) * 4, (0xffffffff,) * 2, (0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd)),
+              ((0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344), (0xa4093822, 0x299f31d0), (0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1))]
+
+
+def test_numpy_philox_known_answers():
+    """The three published Random123 known-answer vectors of Philox4x32-10."""
+    for ctr, key, want in PHILOX_KAT:
+        got = kc.philox4x32_10_np(np.array([ctr], dtype=np.uint32), *key)[0]
+        assert tuple(int(v) for v in got) == want
+        assert tuple(int(v) for v in kc.philox4x32_10_np(np.array([ctr], dtype=np.uint32), *key, swap_key_increments=True)[0]) != want
+
+
+def philox_emulation(seed, step, first_vec, n_vec, **fault):
+    """The kernel in float32: numpy Philox, Box-Muller with float32 log / sqrt / sincos.  fault: philox_normal_ref's planted-fault keywords."""
+    e = np.uint64(first_vec) + np.arange(n_vec, dtype=np.uint64)
+    sw = fault.get("step_word", 2)
+    ctr = np.zeros((n_vec, 4), dtype=np.uint32)
+    ctr[:, 0], ctr[:, 1] = (e & np.uint64(0xFFFFFFFF)).astype(np.uint32), (e >> np.uint64(32)).astype(np.uint32)
+    ctr[:, sw], ctr[:, 5 - sw] = np.uint32(step), np.uint32(kc.PHILOX_TAG)
+    c = kc.philox4x32_10_np(ctr, seed & 0xFFFFFFFF, seed >> 32, fault.get("swap_key_increments", False))
+
+    def bm(a, b):
+        u1 = (a.astype(np.float32) + np.float32(1)) * np.float32(2.0 ** -32)
+        u2 = b.astype(np.float32) * np.float32(2.0 ** -32)
+        r, ang = np.sqrt(np.float32(-2) * np.log(u1)), np.float32(6.283185307179586) * u2
+        cs, sn = np.cos(ang), np.sin(ang)
+        return (r * sn, r * cs) if fault.get("swap_sin_cos") else (r * cs, r * sn)
+    z0, z1 = bm(c[:, 0], c[:, 1])
+    z2, z3 = bm(c[:, 2], c[:, 3])
+    out = np.stack([z0, z1, z2, z3], 1)
+    assert out.dtype == np.float32
+    return torch.from_numpy(out)
+
+
+@pytest.mark.parametrize("first_vec", [0, (2 ** 34 + 8) // 4])
+def test_philox_reference_passes_emulation_and_fails_planted_faults(first_vec):
+    seed, step, n = (0x9E3779B97F4A7C15, 7, 2048)
+    ref, tol = kc.philox_normal_ref(seed, step, first_vec, n)
+    assert float(ref.mean().abs()) < 0.05 and abs(float(ref.std()) - 1) < 0.05
+    kc.assert_elementwise(philox_emulation(seed, step, first_vec, n), ref, tol, "philox emulation")
+    for fault in (dict(swap_key_increments=True), dict(step_word=3), dict(swap_sin_cos=True)):
+        fails(kc.assert_elementwise, philox_emulation(seed, step, first_vec, n, **fault), ref, tol, "philox %s" % fault)
+    fails(kc.assert_elementwise, philox_emulation(seed, step, first_vec + 1, n), ref, tol, "philox counter off by one")
+    fails(kc.assert_elementwise, philox_emulation(seed >> 32 | (seed & 0xFFFFFFFF) << 32, step, first_vec, n), ref, tol, "philox key words exchanged")
+    if first_vec >> 32:
+        fails(kc.assert_elementwise, philox_emulation(seed, step, first_vec & 0xFFFFFFFF, n), ref, tol, "philox high counter word dropped")
+
+
+def test_sweep_windows_cover_what_grid_stride_faults_touch():
+    """A grid-stride kernel emulated with 4 items per block and a cap of 8 blocks over 2 sweeps + 7 items: compared on the windows alone, the
+    right sweep passes; an unwritten last partial sweep and a second sweep that reads from the first sweep's offset fail."""
+    block, cap, width = 4, 8, 3
+    sweep, n = block * cap, 2 * block * cap + 7
+    win = kc.sweep_windows(n, block, cap, width)
+    assert win == [(0, 3), (29, 35), (61, 67), (68, n)]
+    assert kc.sweep_windows(5, block, cap, width) == [(0, 5)] and kc.sweep_windows(sweep, block, cap, width) == [(0, 3), (29, 32)]
+    idx = kc.window_index(win)
+    src = torch.randn(n, generator=torch.Generator().manual_seed(0))
+    want = src * 2 + 1
+
+    def run(fault=None):
+        out = torch.full((n,), kc.SENT_F32)
+        for s0 in range(0, n, sweep):
+            i = torch.arange(s0, min(s0 + sweep, n))
+            if fault == "tail" and s0 + sweep > n:
+                continue
+            rd = i - sweep if (fault == "stale" and s0 == sweep) else i
+            out[i] = src[rd] * 2 + 1
+        return out
+    assert torch.equal(run()[idx], want[idx])
+    assert not torch.equal(run("tail")[idx], want[idx]) and not torch.equal(run("stale")[idx], want[idx])
+
+
+def test_exact_expressions_tell_a_contraction():
+    """sampler_step mode 1, pndm_transfer and lincomb4: the fp32 expression is what it is compared with; the same with FMA contraction (float64
+    fused, rounded once) differs in well over 1 % of the elements — shown on the reference data before the assertion — so torch.equal fails it."""
+    g = torch.Generator().manual_seed(11)
+    n = 1028
+    x, p, z, e = [torch.randn(n, generator=g) for _ in range(4)]
+    cf = torch.tensor([0.9987, -0.0123, 0.0507, 0.0])
+    xm, xn = kc.sampler_step_expr(x, p, z, cf, 1)
+    fm, fn = kc.sampler_step_expr(x, p, z, cf, 1, fused=True)
+    assert float((fm != xm).float().mean()) >= 0.01 and float((fn != xn).float().mean()) >= 0.01
+    assert not torch.equal(fm, xm) and not torch.equal(fn, xn)
+    assert torch.equal(xm, cf[0] * x + cf[1] * p) and torch.equal(xn, xm + cf[2] * z)
+    d, pp, q = -0.0021, 0.5013, 7.913
+    t, tf = kc.pndm_transfer_expr(x, e, d, pp, q), kc.pndm_transfer_expr(x, e, d, pp, q, fused=True)
+    assert float((t != tf).float().mean()) >= 0.01 and not torch.equal(t, tf)
+    a = [torch.randn(n, generator=g) for _ in range(4)]
+    (c, s), (c2, s2) = kc.PNDM_COEF_SETS
+    l, lf = kc.lincomb4_expr(a, c, s), kc.lincomb4_expr(a, c, s, fused=True)
+    assert float((l != lf).float().mean()) >= 0.01 and not torch.equal(l, lf)
+    # (1, 2, 2, 1): every product is exact, so a contraction changes nothing there; that set tells the ORDER of the sums instead
+    assert torch.equal(kc.lincomb4_expr(a, c2, s2), kc.lincomb4_expr(a, c2, s2, fused=True))
+    cf32 = [torch.tensor(v, dtype=torch.float32) for v in c2]
+    other = torch.tensor(s2, dtype=torch.float32) * ((cf32[0] * a[0] + cf32[1] * a[1]) + (cf32[2] * a[2] + cf32[3] * a[3]))
+    assert float((other != kc.lincomb4_expr(a, c2, s2)).float().mean()) >= 0.01
+    # mode 0 against the reference's own lines (diffusion_continuous.py:152-162)
+    c0 = torch.tensor([0.02, 0.7, (1 - 0.02) ** 0.5, 0.02 ** 0.5])
+    xm0, xn0 = kc.sampler_step_expr(x, p, z, c0, 0)
+    assert torch.equal(xm0, (x + c0[0] * (-p / c0[1])) / c0[2]) and torch.equal(xn0, xm0 + c0[3] * z)
+
+
+def act_emulation(x, kind, variant=None):
+    """block_act in fp32 on the CPU -> bf16.  variant: 'div6' (benign), 'slope' / 'selu3' (planted)."""
+    v = x.float()
+    f = lambda c: torch.tensor(c, dtype=torch.float32)
+    if kind == "gelu":
+        r = f(0.5) * v * (1 + torch.erf(v * f(0.70710678118654752440)))
+    elif kind == "silu":
+        r = v / (1 + torch.exp(-v))
+    elif kind == "relu":
+        r = torch.where(v > 0, v, torch.where(torch.isnan(v), v, torch.zeros_like(v)))
+    elif kind in ("leakyrelu", "leakyrelu0.2"):
+        slope = 0.2 if (kind == "leakyrelu0.2") != (variant == "slope") else 0.01
+        r = torch.where(v > 0, v, f(slope) * v)
+    elif kind == "rrelu":
+        r = torch.where(v > 0, v, v * ((f(1 / 8) + f(1 / 3)) * f(0.5)))
+    elif kind == "hardswish":
+        h = v * torch.clamp(v + 3, 0, 6)
+        r = h / 6 if variant == "div6" else h * f(1 / 6)
+    else:
+        sc, al = (1.05, 1.67) if variant == "selu3" else (kc.SELU_SCALE, kc.SELU_ALPHA)
+        r = f(sc) * torch.where(v > 0, v, f(al) * (torch.exp(v) - 1))
+    return r.bfloat16()
+
+
+def test_block_activation_reference_over_every_bf16_pattern():
+    x = kc.all_bf16_patterns()
+    assert torch.unique(x.view(torch.int16)).numel() == 65536
+    for kind in kc.BLOCK_ACT_KINDS:
+        ratio, share = kc.check_block_act(act_emulation(x, kind), x, kind, kind)
+        assert ratio <= 1 and share <= kc.AMBIGUOUS_CAP
+    kc.check_block_act(act_emulation(x, "hardswish", "div6"), x, "hardswish", "hardswish as / 6")
+    fails(kc.check_block_act, act_emulation(x, "leakyrelu", "slope"), x, "leakyrelu", "slope 0.2 for 0.01")
+    fails(kc.check_block_act, act_emulation(x, "leakyrelu0.2", "slope"), x, "leakyrelu0.2", "slope 0.01 for 0.2")
+    fails(kc.check_block_act, act_emulation(x, "selu", "selu3"), x, "selu", "selu constants cut to 3 digits")
+    # the resolved share is what makes the test a test: everything finite outside GELU's tail below -5 (1 + erf cancels) and selu's negative
+    # inputs above -1e-4 (exp(x) - 1 cancels: fp32 keeps 2^-24 absolute there), a quarter of all bit patterns each
+    for kind in ("gelu", "silu", "hardswish", "selu"):
+        ref, acc = kc.block_act_ref(x, kind)
+        assert float(kc.resolved_by_bf16(ref, acc).float().mean()) > (0.70 if kind in ("gelu", "selu") else 0.95), kind
+    nan_in = torch.isnan(x.float())
+    for kind in kc.BLOCK_ACT_KINDS:
+        assert bool(torch.isnan(act_emulation(x, kind).float()[nan_in]).all())
+    dropped = act_emulation(x, "relu").clone()
+    dropped[nan_in] = 0                                                       # fmaxf(NaN, 0) = 0
+    fails(kc.check_block_act, dropped, x, "relu", "relu that drops NaN")
+
+
+def test_assert_bf16_of_cap_and_neighbours():
+    g = torch.Generator().manual_seed(2)
+    ref = torch.randn(64, 64, generator=g).double()
+    out = kc.bf16_round(ref)
+    assert kc.assert_bf16_of(out, ref, 2.0 ** -20, "plain") <= kc.AMBIGUOUS_CAP
+    bad = out.clone()
+    bad[3, 5] += kc.bf16_ulp(ref)[3, 5]
+    fails(kc.assert_bf16_of, bad, ref, 2.0 ** -20, "one ulp off")
+    fails(kc.assert_bf16_of, out, ref, 2.0 ** -9, "too loose an accumulation bound: the cap")
+    mid = torch.tensor([[1.00390625 + 1e-6]], dtype=torch.float64)            # just above the boundary between 1 and 1 + 2^-7
+    nanref = torch.tensor([[float("nan"), float("inf"), 2.0]], dtype=torch.float64)
+    kc.AMBIGUOUS_CAP, cap = 1.0, kc.AMBIGUOUS_CAP
+    try:
+        kc.assert_bf16_of(torch.tensor([[float("nan"), float("inf"), 2.0]]), nanref, 0.0, "nan / inf")
+        fails(kc.assert_bf16_of, torch.tensor([[0.0, float("inf"), 2.0]]), nanref, 0.0, "nan dropped")
+        kc.assert_bf16_of(torch.tensor([[1.0]]), mid, 1e-5, "lower neighbour allowed")
+        kc.assert_bf16_of(torch.tensor([[1.0078125]]), mid, 1e-5, "upper neighbour")
+        fails(kc.assert_bf16_of, torch.tensor([[1.0]]), mid, 0.0, "lower neighbour without an allowance")
+    finally:
+        kc.AMBIGUOUS_CAP = cap
+
+
+def test_langevin_references():
+    g = torch.Generator().manual_seed(5)
+    for B, per in ((1, 4), (3, 3092), (70, 8192)):
+        x = torch.randn(B, per, generator=g) * 3
+        n, s, tn, ts = kc.batch_norms_ref(x)
+        for order in (lambda r: r.pow(2).sum(), lambda r: r.pow(2).flip(0).reshape(-1, 4).sum(1).sum(), lambda r: r.pow(2).reshape(4, -1).sum(0).sum()):
+            em = torch.stack([order(r).sqrt() for r in x])
+            kc.assert_elementwise(em, n, tn, "batch norms")
+            assert abs(float(em.sum()) - float(s)) <= float(ts)
+        fails(kc.assert_elementwise, torch.stack([r[:-4].pow(2).sum().sqrt() for r in x]) if per > 4 else n.float() * 1.01, n, tn, "last vector dropped")
+    for snr, std in ((0.16, 0.7), (0.01, 1e-3), (0.2, 0.999)):
+        sums = torch.tensor([123.4, 250.1])
+        f = lambda v: torch.tensor(v, dtype=torch.float32)
+        gn, nn_ = (sums[0] / f(3.0)) / f(std), sums[1] / f(3.0)
+        r = f(snr) * nn_ / gn
+        step = r * r * 2
+        em = torch.stack([f(1.0), -step / f(std), torch.sqrt(step * 2), f(0.0)])
+        ref, tol = kc.langevin_coef_ref(sums, 3, snr, std)
+        kc.assert_elementwise(em, ref, tol, "langevin_coef")
+        fails(kc.assert_elementwise, torch.stack([f(1.0), -step / f(std), torch.sqrt(step), f(0.0)]), ref, tol, "sqrt(step) for sqrt(2 step)")
+
+
+def sde_emulation(p, t, kind, c0, c1, c2, unit=False):
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    c0, c1, c2 = f(c0), f(c1), f(c2)
+    if kind == 2:
+        var = c0 * torch.pow(c1, t) - c0 + c2
+    else:
+        e = torch.exp(-c0 * t - (f(0.5) * (c1 - c0)) * t * t)
+        var = (1 - e) * (1 - e) + c2 * e if kind == 1 else 1 - (1 - c2) * e
+    sd = torch.sqrt(var if not unit else var * (1 + 3e-6))
+    return -p / sd[:, None]
+
+
+def test_sde_score_reference():
+    g = torch.Generator().manual_seed(6)
+    t = torch.tensor([1.0, 0.5, 0.25, 1e-3, 1e-6])
+    p = torch.randn(5, 96, generator=g)
+    for kind, cs in ((0, (0.1, 20.0, 0.0)), (0, (0.1, 20.0, 1e-3)), (1, (0.1, 20.0, 1e-3)), (1, (0.1, 20.0, 0.0)), (2, (1e-4, 5e5, 1e-4)), (2, (0.01, 2500.0, 0.01))):
+        ref, tol, res = kc.sde_score_ref(p, t, kind, *cs)
+        assert bool(res[:3].all()), (kind, cs)                               # t >= 0.25 is always resolved
+        if cs[2] > 0:
+            assert bool(res.all()), (kind, cs)                               # with sigma2_0 > 0 every t is
+        em = sde_emulation(p, t, kind, *cs)
+        kc.assert_elementwise(em[res], ref[res], tol[res], "sde_score kind %d" % kind)
+        fails(kc.assert_elementwise, sde_emulation(p, t, kind, *cs, unit=True)[res], ref[res], tol[res], "var off by 3e-6")
+        fails(kc.assert_elementwise, sde_emulation(p, t.flip(0), kind, *cs)[res], ref[res], tol[res], "t of another sample")
+
+
+def test_encoder_helper_references():
+    g = torch.Generator().manual_seed(7)
+    # actnorm
+    x, sh, ls = torch.randn(3, 50, generator=g), torch.randn(50, generator=g), torch.randn(50, generator=g) * 0.5
+    ref, tol = kc.actnorm_ref(x, sh, ls)
+    kc.assert_elementwise((x - sh) * torch.exp(-ls), ref, tol, "actnorm")
+    fails(kc.assert_elementwise, (x - sh) * torch.exp(ls), ref, tol, "actnorm with exp(+log_scale)")
+    # reparam
+    post, nz = torch.randn(40, 12, generator=g) * 3, torch.randn(40, 6, generator=g)
+    lo, hi = -2.0, 1.5
+    post[0, 6:9] = torch.tensor([lo, hi, lo]); post[1, 6] = float(np.nextafter(np.float32(lo), np.float32(0))); post[1, 7] = float(np.nextafter(np.float32(lo), np.float32(-9)))
+    mu, lv, ref, tol = kc.reparam_ref(post, nz, lo, hi)
+    assert float(lv.min()) == lo and float(lv.max()) == hi and float(lv[1, 0]) > lo and float(lv[1, 1]) == lo
+    kc.assert_elementwise(kc.fma32(nz, torch.exp(lv / 2), mu), ref, tol, "reparam (fused)")
+    kc.assert_elementwise(mu + torch.exp(lv / 2) * nz, ref, tol * 2, "reparam (unfused, within twice)")
+    fails(kc.assert_elementwise, mu + torch.exp(post[:, 6:] / 2) * nz, ref, tol, "reparam without the clamp")
+    # mixture seed
+    for n_mix, logits in ((1, torch.zeros(1)), (3, torch.zeros(3)), (8, torch.randn(8, generator=g)), (3, torch.tensor([0.0, 160.0, -3.0]))):
+        eps, sig, mu_ = torch.randn(9, n_mix, 5, generator=g), torch.rand(n_mix, 5, generator=g) + 0.1, torch.randn(n_mix, 5, generator=g)
+        ref, tol = kc.mixture_seed_ref(eps, sig, mu_, logits)
+        w = torch.exp(logits - logits.max()); w = w / w.sum()
+        terms = (eps * sig + mu_) * w[None, :, None]
+        kc.assert_elementwise(terms.sum(1), ref, tol, "mixture_seed")
+        kc.assert_elementwise(terms.flip(1).sum(1), ref, tol, "mixture_seed, reversed order")
+        if n_mix > 1:
+            fails(kc.assert_elementwise, ((eps * sig + mu_) * w.flip(0)[None, :, None]).sum(1) + 1e-5, ref, tol, "mixture_seed, weights reversed")
+    # sinusoid
+    half = 130
+    t = torch.tensor([1.0, 0.5, 1e-3, 0.9999])
+    fr = torch.exp(torch.arange(half) * -(np.log(10000) / (half - 1))).float()
+    ref, tol = kc.sinusoid_ref(t, fr)
+    a = t[:, None] * fr[None, :]
+    kc.assert_elementwise(torch.cat([torch.sin(a), torch.cos(a)], 1), ref, tol, "sinusoid")
+    fails(kc.assert_elementwise, torch.cat([torch.cos(a), torch.sin(a)], 1), ref, tol, "sinusoid halves exchanged")
+
+
+def norm_points_emulation(xyz, unbiased=True):
+    p = xyz.double()
+    mean = p.mean(1, keepdim=True).float()
+    inv = (1 / p.var(1, unbiased=unbiased, keepdim=True).sqrt()).float()
+    return (xyz - mean) * inv
+
+
+def test_norm_points_reference():
+    g = torch.Generator().manual_seed(8)
+    for n in (2, 255, 5000):
+        xyz = torch.randn(2, n, 3, generator=g)
+        xyz[1] = xyz[1] * 0.01 + 100.0
+        ref, tol = kc.norm_points_ref(xyz)
+        kc.assert_elementwise(norm_points_emulation(xyz), ref, tol, "norm_points n=%d" % n)
+        fails(kc.assert_elementwise, norm_points_emulation(xyz, unbiased=False), ref, tol, "norm_points with the biased variance")
+        rb, tb = kc.norm_points_ref(xyz, unbiased=False)
+        fails(kc.assert_elementwise, norm_points_emulation(xyz), rb, tb, "the other way round")
+        assert float(tol[1].max()) > 50 * float(tol[0].max()) or n == 2          # the offset cloud carries u |mean| / std
+
+
+def group_norm_emulation(x, B, T, C, G, eps, w=None, b=None, shift=None, scale=None, unbiased=False, eps_outside=False):
+    cg = C // G
+    xd = x.double().reshape(B, T, G, cg).permute(0, 2, 1, 3).reshape(B, G, -1)
+    mean, var = xd.mean(2), xd.var(2, unbiased=unbiased)
+    rstd = 1 / (var.sqrt() + eps) if eps_outside else 1 / torch.sqrt(var + eps)
+    stats = torch.stack([mean, rstd], -1).float()
+    m = stats[:, :, 0].repeat_interleave(cg, 1).repeat_interleave(T, 0)
+    r = stats[:, :, 1].repeat_interleave(cg, 1).repeat_interleave(T, 0)
+    h = (x - m) * r
+    if w is not None:
+        h = h * w + b
+    if scale is not None:
+        h = h * (1 + scale.repeat_interleave(T, 0)) + shift.repeat_interleave(T, 0)
+    return stats, h.bfloat16()
+
+
+def test_group_norm_references():
+    g = torch.Generator().manual_seed(9)
+    eps = 1e-6
+    for (C, G), T in (((32, 8), 7), ((24, 6), 33), ((128, 16), 300)):
+        B = 2
+        x = torch.randn(B * T, C, generator=g) * 2 + 0.3
+        w, b = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.2
+        sh, sc = torch.randn(B, C, generator=g) * 0.3, torch.randn(B, C, generator=g) * 0.3
+        for kw in (dict(), dict(w=w, b=b), dict(w=w, b=b, shift=sh, scale=sc)):
+            stats, y = group_norm_emulation(x, B, T, C, G, eps, **kw)
+            ref, tol = kc.group_stats_ref(x, B, T, C, G, eps)
+            kc.assert_elementwise(stats, ref, tol, "group_stats")
+            pre, acc = kc.norm_apply_ref(x, stats, T, rows_per_sample=T, **kw)
+            kc.assert_bf16_of(y, pre, acc, "norm_apply")
+        bad, ybad = group_norm_emulation(x, B, T, C, G, eps, unbiased=True)
+        fails(kc.assert_elementwise, bad, ref, tol, "GroupNorm with the unbiased variance")
+        ru, tu = kc.group_stats_ref(x, B, T, C, G, eps, unbiased=True)
+        fails(kc.assert_elementwise, stats, ru, tu, "the other way round")
+        pre, acc = kc.norm_apply_ref(x, stats, T)
+        fails(kc.assert_bf16_of, ybad, pre, acc, "norm_apply on the wrong statistics")
+    # eps outside the square root: a group of variance ~1e-5, where sqrt(var + eps) and sqrt(var) + eps differ by 5 %... of eps / sqrt(var)
+    x = torch.randn(2 * 40, 8, generator=g) * (1e-5 ** 0.5)
+    eps = 1e-5
+    ref, tol = kc.group_stats_ref(x, 2, 40, 8, 2, eps)
+    assert 0.3e-5 < float(x.double().var()) < 3e-5
+    stats, _ = group_norm_emulation(x, 2, 40, 8, 2, eps)
+    kc.assert_elementwise(stats, ref, tol, "group_stats at var ~ eps")
+    bad, _ = group_norm_emulation(x, 2, 40, 8, 2, eps, eps_outside=True)
+    fails(kc.assert_elementwise, bad, ref, tol, "eps outside the square root")
+    # identity norm
+    pre, acc = kc.norm_apply_ref(x)
+    kc.assert_bf16_of(x.bfloat16(), pre, acc, "identity norm")
+
+
+def chamfer_emulation(q, r):
+    """chamfer_min_kernel in fp32 with its FMA chains."""
+    f = kc.fma32
+    n2 = lambda p: f(p[..., 2], p[..., 2], f(p[..., 1], p[..., 1], p[..., 0] * p[..., 0]))
+    qq, rr = q[:, :, None, :].expand(-1, -1, r.shape[1], -1), r[:, None, :, :].expand(-1, q.shape[1], -1, -1)
+    dot = f(qq[..., 2], rr[..., 2], f(qq[..., 1], rr[..., 1], qq[..., 0] * rr[..., 0]))
+    return ((n2(qq) + n2(rr)) - 2 * dot).min(2).values
+
+
+def test_chamfer_references():
+    g = torch.Generator().manual_seed(10)
+    for na, nb in ((30, 110), (110, 30), (1, 1), (64, 64)):
+        a, b = torch.randn(3, na, 3, generator=g) * 0.5, torch.randn(3, nb, 3, generator=g) * 0.5 + 0.1
+        (dl, tl), (dr, tr) = kc.chamfer_ref(a, b)
+        el, er = chamfer_emulation(b, a), chamfer_emulation(a, b)
+        kc.assert_elementwise(el, dl, tl, "chamfer dl"); kc.assert_elementwise(er, dr, tr, "chamfer dr")
+        if na == nb and na > 1:
+            fails(kc.assert_elementwise, er, dl, tl, "dl and dr exchanged")
+    x, y = torch.randn(2, 70, 3, generator=g) * 0.5, torch.randn(3, 45, 3, generator=g) * 0.5
+    ref, tol = kc.chamfer_pairwise_ref(x, y)
+    em = torch.stack([torch.stack([chamfer_emulation(y[r:r + 1], x[s:s + 1]).mean() + chamfer_emulation(x[s:s + 1], y[r:r + 1]).mean() for r in range(3)]) for s in range(2)])
+    kc.assert_elementwise(em, ref, tol, "chamfer_pairwise")
+    fails(kc.assert_elementwise, em.flip(1), ref, tol, "chamfer_pairwise with the reference clouds reversed")
+    drop = torch.stack([torch.stack([chamfer_emulation(y[r:r + 1], x[s:s + 1, :64]).mean() + chamfer_emulation(x[s:s + 1], y[r:r + 1]).mean() for r in range(3)]) for s in range(2)])
+    fails(kc.assert_elementwise, drop, ref, tol, "chamfer_pairwise that loses the last chunk of one cloud")
+
+
+def test_maxpool_expression_and_stride_fault():
+    g = torch.Generator().manual_seed(12)
+    G, n, C, ld = 6, 5, 8, 12
+    big = torch.randn(G * n, ld, generator=g)
+    view = big[:, :C]
+    big[7, 3] = float("nan"); big[10:15, 2] = float("-inf")
+    want = kc.maxpool_expr(view, G, n)
+    assert bool(torch.isnan(want[1, 3])) and float(want[2, 2]) == float("-inf")
+    dense = big.reshape(-1)[:G * n * C].reshape(G * n, C)                      # the planted fault: ld = C on the strided storage
+    got = kc.maxpool_expr(dense, G, n)
+    same = lambda a, b: bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
+    assert same(kc.maxpool_expr(view.contiguous(), G, n), want) and not same(got, want)
+    fmax = torch.where(torch.isnan(view), torch.full_like(view, float("-inf")), view).reshape(G, n, C).max(1).values      # fmaxf drops NaN
+    assert not same(fmax, want)
+
+
+def test_nan_fixed_kernels_are_under_no_isa_signature():
+    """maxpool_kernel and block_act_kernel changed how they select (NaN propagates): neither is one of the hand-counted kernels whose
+    disassembly csrc/isa_signatures.json pins, so there is no signature to re-audit."""
+    import json
+    import os
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ldt_amd", "csrc", "isa_signatures.json")
+    names = " ".join(json.load(open(path))["kernels"])
+    assert "maxpool" not in names and "block_act" not in names
