@@ -175,8 +175,10 @@ def refuse_untrainable(model, condition=None, world_size=1):
 
 
 def _t(x):
-    """fp32 transpose as a dense matrix (data movement only: ldt_sgemm takes row strides, not column strides)."""
-    return x.t().contiguous()
+    """fp32 transpose as a dense matrix (data movement only: ldt_sgemm takes row strides, not column strides).  Copied into a fresh
+    tensor: `.t().contiguous()` hands a one-row matrix back as it is ([1, n] -> [n, 1] with strides (1, n) counts as contiguous), and
+    ops.sgemm refuses its last-dim stride — a batch of one sample could not take a step."""
+    return x.new_empty((x.shape[1], x.shape[0])).copy_(x.t())
 
 
 def _grad2d(p):

@@ -1280,3 +1280,184 @@ def check_block_act(out, x, kind, what):
 def all_bf16_patterns():
     """Every bf16 bit pattern once, as a [512, 128] bf16 tensor."""
     return torch.arange(65536, dtype=torch.int32).to(torch.int16).view(torch.bfloat16).reshape(512, 128)
+
+
+# ------------------------------------------------------------------------------------------------------------- Score training step
+# (csrc/score_bwd.hip, attention_bwd.hip; test_gpu_train_kernels.py holds each kernel alone with these, test_gpu_train_tape.py every call of a
+# whole backward on that call's own recorded operands; validated without a GPU, planted faults included, by test_train_tape_host.py)
+#
+# Every function takes the operands the kernel read and returns (float64 reference, componentwise bound), or two dicts of them for a kernel
+# with several outputs.  The bounds are built the way gemm_tol is:
+#   * an accumulation term C_ACC * n * 2^-24 * sum |terms| for every fp32 sum of n terms (the column sums over rows are carried in float64
+#     by the kernels, which leaves the term far from attained);
+#   * 2^-8 |value| for every intermediate the kernel rounds to bf16 (P and dS in the attention backward) and for a bf16 output;
+#   * 2^-24 |value| per fp32 rounding of the element chain, and a stated absolute allowance where libm's erff / expf / logf enter.
+LIBM_ABS = 1e-6          # |erff|, |expf| on [-inf, 0], sigmoid: a few fp32 ulp of a value <= 1 (as GELU_FAST_ABS allows the forward)
+
+
+def pad64(k):
+    return (k + 63) // 64 * 64
+
+
+def transpose_cast_want(src, rows_pad=None):
+    """bf16 [C, rows_pad] the transposing cast owes for src [R, C]: bf16(src)^T, columns R.. zero.  Exact: compared with torch.equal."""
+    R, C = src.shape
+    want = torch.zeros(C, pad64(R) if rows_pad is None else rows_pad, dtype=torch.bfloat16, device=src.device)
+    want[:, :R] = src.to(torch.bfloat16).t()
+    return want
+
+
+def cast_pad_want(src, cols_pad):
+    """bf16 [rows, cols_pad] of ldt_cast_pad_bf16: bf16(src), columns cols.. zero.  Exact."""
+    want = torch.zeros(src.shape[0], cols_pad, dtype=torch.bfloat16, device=src.device)
+    want[:, :src.shape[1]] = src.to(torch.bfloat16)
+    return want
+
+
+def colsum_ref(dy):
+    """bound: one fp32 sum of M terms + the stored value's rounding"""
+    M = dy.shape[0]
+    ref = dy.double().sum(0)
+    return ref, C_ACC * M * U24 * dy.double().abs().sum(0) + U24 * ref.abs()
+
+
+def wgrad_ref(dy, x):
+    """dW = dY^T X from the operands the GEMM read (bf16(dy)^T [N, M], bf16(x)^T [K, M]).  bound: gemm_tol over the padded contraction
+    length (the pad adds exact zeros)"""
+    a, b = dy.to(torch.bfloat16).t().contiguous(), x.to(torch.bfloat16).t().contiguous()
+    return a.double() @ b.double().T, gemm_tol(a, b, None, pad64(dy.shape[0]), torch.float32)
+
+
+def dgrad_ref(dyb, wt, out_dtype=torch.float32):
+    """dX = dY W from the bf16 operands dyb [M, N] and wt = W^T [K, N] (N: the contraction as the GEMM runs it, zero padding included)."""
+    return dyb.double() @ wt.double().T, gemm_tol(dyb, wt, None, dyb.shape[1], out_dtype)
+
+
+def sgemm_ref(a, w, bias=None):
+    """ldt_sgemm (no activation) against float64.  The bound's factor on 2^-24 (|a| |w|^T + |b|): K + 1 roundings at the worst; these kernels
+    add their products one after another, so their error grows like sqrt(K) with a larger constant than the blocked bf16 kernels': hence a
+    floor of 8 under C_ACC K (test_gpu_kernel_exact.py::test_sgemm_bound_and_integer_probe).  -> (ref, tol)."""
+    K = a.shape[1]
+    ref = a.double() @ w.double().T
+    absacc = a.double().abs() @ w.double().abs().T
+    if bias is not None:
+        ref, absacc = ref + bias.double(), absacc + bias.double().abs()
+    return ref, min(K + 1, max(C_ACC * K, 8)) * U24 * absacc + U24 * ref.abs()
+
+
+def layernorm_modulate_bwd_ref(x, dy, scale, rps, dx0):
+    """x, dy, dx0 [M, C] fp32, scale [M / rps, C] -> ({'dx', 'dshift', 'dscale'} references, the same of bounds); dx = dx0 + the LayerNorm
+    gradient (dx is accumulated into), and the row statistics (mean, var) for a caller that asserts a property of its case."""
+    M, C = x.shape
+    x6, dy6 = x.double(), dy.double()
+    mean, var = x6.mean(1, keepdim=True), x6.var(1, unbiased=False, keepdim=True)
+    rstd = 1 / torch.sqrt(var + 1e-6)
+    xh = (x6 - mean) * rstd
+    s1 = 1 + scale.double().repeat_interleave(rps, 0)
+    gg = dy6 * s1
+    mg, mgx = gg.mean(1, keepdim=True), (gg * xh).mean(1, keepdim=True)
+    ref_dx = dx0.double() + rstd * (gg - mg - xh * mgx)
+    # bound.  Row statistics in fp32: mean = a C-term sum (C_ACC C 2^-24 mean|x|, + its rounding); d = x - mean inherits it, so
+    # e_xh = |error of LN(x)| = 2^-24 (4 (1 + |xh|) + (C_ACC C + 2) mean|x| / std); rstd: relative e_r = e_xh(row max) + 2^-24 (C_ACC C + 8).
+    # The two row means of g and g xh: C_ACC C 2^-24 mean|.| each (+ mean|g| e_xh).  Element chain: 2^-24 per operation on its magnitude.
+    sd = torch.sqrt(var)
+    e_xh = U24 * (4 * (1 + xh.abs()) + (C_ACC * C + 2) * x6.abs().mean(1, keepdim=True) / sd)
+    e_r = e_xh.amax(1, keepdim=True) + U24 * (C_ACC * C + 8)
+    e_mg = U24 * (C_ACC * C + 2) * gg.abs().mean(1, keepdim=True)
+    e_mgx = U24 * (C_ACC * C + 2) * (gg * xh).abs().mean(1, keepdim=True) + (gg.abs() * e_xh).mean(1, keepdim=True)
+    inner = gg - mg - xh * mgx
+    tol_dx = (rstd * (4 * U24 * (gg.abs() + mg.abs() + (xh * mgx).abs()) + e_mg + e_xh * mgx.abs() + xh.abs() * e_mgx)
+              + (e_r + 2 * U24) * (rstd * inner).abs() + U24 * ref_dx.abs())
+    S = M // rps
+    ref_sh = dy6.view(S, rps, C).sum(1)
+    ref_sc = (dy6 * xh).view(S, rps, C).sum(1)
+    # dshift: float64 sum of fp32 terms, one rounding (+ the issue's accumulation term).  dscale: each term fp32(dy * xh): |dy| e_xh + 2^-24 |dy xh|.
+    tol_sh = C_ACC * rps * U24 * dy6.abs().view(S, rps, C).sum(1) + U24 * ref_sh.abs()
+    tol_sc = ((dy6.abs() * e_xh + U24 * (dy6 * xh).abs()).view(S, rps, C).sum(1) + C_ACC * rps * U24 * (dy6 * xh).abs().view(S, rps, C).sum(1)
+              + U24 * ref_sc.abs())
+    return {"dx": ref_dx, "dshift": ref_sh, "dscale": ref_sc}, {"dx": tol_dx, "dshift": tol_sh, "dscale": tol_sc}, (mean, var)
+
+
+def gelu_bwd_ref(u, dh):
+    """bound: bf16 output 2^-8 |ref|; fp32 chain 8 x 2^-24 |ref|; erff and expf absolute accuracy times |dh| (1 + |u|)"""
+    import math
+    u6 = u.double()
+    dgelu = 0.5 * (1 + torch.erf(u6 / math.sqrt(2))) + u6 * torch.exp(-0.5 * u6 * u6) / math.sqrt(2 * math.pi)
+    ref = dh.double() * dgelu
+    return ref, U8 * ref.abs() + 8 * U24 * ref.abs() + LIBM_ABS * dh.double().abs() * (1 + u6.abs())
+
+
+def gate_residual_bwd_ref(dy, gate, a, rps):
+    """dy [M, C] fp32, gate [M / rps, C] (the column block), a [M, C] or None -> ({'da', 'dgate'} references, bounds).
+    bound: da one fp32 product then bf16; dgate float64 sum of fp32 products (2^-24 each) + the accumulation term + its rounding"""
+    M, C = dy.shape
+    S = M // rps
+    ref_da = dy.double() * gate.double().repeat_interleave(rps, 0)
+    ref, tol = {"da": ref_da}, {"da": (U8 + U24) * ref_da.abs()}
+    if a is not None:
+        terms = dy.double() * a.double()
+        ref["dgate"] = terms.view(S, rps, C).sum(1)
+        tol["dgate"] = (1 + C_ACC * rps) * U24 * terms.abs().view(S, rps, C).sum(1) + U24 * ref["dgate"].abs()
+    return ref, tol
+
+
+def silu_bwd_ref(c, dy):
+    """-> ({'dc', 'act'} references, bounds).  bound: fp32 chain 8 x 2^-24 |ref| + the sigmoid's absolute accuracy times |dy| (1 + |c|);
+    act = SiLU(c): 4 x 2^-24 |act| + the sigmoid's accuracy times |c|"""
+    c6 = c.double()
+    sg = torch.sigmoid(c6)
+    ref = dy.double() * sg * (1 + c6 * (1 - sg))
+    return ({"dc": ref, "act": c6 * sg},
+            {"dc": 8 * U24 * ref.abs() + LIBM_ABS * dy.double().abs() * (1 + c6.abs()), "act": 4 * U24 * (c6 * sg).abs() + LIBM_ABS * c6.abs()})
+
+
+def dsm_loss_bwd_ref(eta, params, w=None, l1=False):
+    """Gradient of mean(w |eta - params|^p) by float64 autograd.  bound: four fp32 roundings (d, the factor 2 is exact, the weight, 1 / n and
+    its product)"""
+    with torch.enable_grad():
+        p6 = params.detach().double().requires_grad_(True)
+        d = eta.double() - p6
+        dist = d.abs() if l1 else d * d
+        (dist * (1 if w is None else w.double()[:, None, None])).mean().backward()
+    return p6.grad, 4 * U24 * p6.grad.abs()
+
+
+def embedding_grad_ref(dc, label, K):
+    """bound: n_k - 1 sequential fp32 additions of class k's rows, worst case (n_k small: C_ACC's statistics do not apply)"""
+    D = dc.shape[1]
+    label = label.long()
+    ref = torch.zeros(K, D, dtype=torch.float64, device=dc.device).index_add_(0, label, dc.double())
+    mag = torch.zeros(K, D, dtype=torch.float64, device=dc.device).index_add_(0, label, dc.double().abs())
+    nk = torch.bincount(label, minlength=K).double()[:, None]
+    return ref, (nk - 1).clamp_min(0) * U24 * mag
+
+
+def attn_bwd_ref(qkv, o, do, B, H, N):
+    """float64 from the bf16 operands: -> dict of references and of componentwise bounds, [B, H, N, 64] each."""
+    C = H * 64
+    hd = lambda z: z.double().view(B, N, H, 64).permute(0, 2, 1, 3)
+    q, k, v = hd(qkv[:, :C]), hd(qkv[:, C:2 * C]), hd(qkv[:, 2 * C:])
+    o6, g6 = o.double(), do.double()
+    sc = 0.125
+    s = q @ k.transpose(-1, -2) * sc
+    L = torch.logsumexp(s, -1, keepdim=True)
+    P = torch.exp(s - L)
+    D = (g6 * o6).sum(-1, keepdim=True)
+    dP = g6 @ v.transpose(-1, -2)
+    dS = P * (dP - D)
+    ref = {"dq": dS @ k * sc, "dk": dS.transpose(-1, -2) @ q * sc, "dv": P.transpose(-1, -2) @ g6}
+    # bound.  s and dP: fp32 MFMA sums of 64 terms (C_ACC 64 2^-24 |.||.|); the exponent s - L carries that of s twice (L is built from the
+    # same sums) + 8 x 2^-24 (|s| + |L|) of its fp32 arithmetic + expf / logf: P's relative error e_arg.  D: a 64-term fp32 sum.
+    # dS in fp32: P e_arg |dP - D| + P (e_dP + e_D) + 2 x 2^-24 |dS|; THEN ROUNDED TO bf16: + 2^-8 |dS|.  P ROUNDED TO bf16 for dV: + 2^-8 P.
+    # Second products: C_ACC N 2^-24 |.||.| each, scaled by 1 / 8 in fp32 (dq, dk), and the bf16 output 2^-8 |ref|.
+    acc = C_ACC * 64 * U24
+    e_arg = 2 * acc * (q.abs() @ k.abs().transpose(-1, -2)) * sc + 8 * U24 * (s.abs() + L.abs()) + 4 * LIBM_ABS
+    e_dP = acc * (g6.abs() @ v.abs().transpose(-1, -2))
+    e_D = acc * (g6.abs() * o6.abs()).sum(-1, keepdim=True)
+    e_dS = P * e_arg * (dP - D).abs() + P * (e_dP + e_D) + (2 * U24 + U8) * dS.abs()
+    e_P = P * e_arg + U8 * P
+    acc2 = C_ACC * N * U24
+    tol = {"dq": sc * (e_dS @ k.abs() + acc2 * (dS.abs() @ k.abs())) + (U8 + 2 * U24) * ref["dq"].abs(),
+           "dk": sc * (e_dS.transpose(-1, -2) @ q.abs() + acc2 * (dS.abs().transpose(-1, -2) @ q.abs())) + (U8 + 2 * U24) * ref["dk"].abs(),
+           "dv": e_P.transpose(-1, -2) @ g6.abs() + acc2 * (P.transpose(-1, -2) @ g6.abs()) + (U8 + U24) * ref["dv"].abs()}
+    return ref, tol

@@ -389,9 +389,7 @@ def test_sgemm_bound_and_integer_probe(M, N, K):
     constant than the blocked bf16 kernels': measured on the MI355X up to 4.7 at K = 64 and 3.9 at K = 20, hence a floor of 8 under C_ACC K."""
     g = torch.Generator().manual_seed(K * 7 + N)
     a = dev(torch.randn(M, K, generator=g)); w = dev(torch.randn(N, K, generator=g) / K ** 0.5); b = dev(torch.randn(N, generator=g))
-    ref = a.double() @ w.double().T + b.double()
-    absacc = a.double().abs() @ w.double().abs().T + b.double().abs()
-    tol = min(K + 1, max(kc.C_ACC * K, 8)) * kc.U24 * absacc + kc.U24 * ref.abs()
+    ref, tol = kc.sgemm_ref(a, w, b)
     r = kc.assert_elementwise(ops.sgemm(a, w, b), ref, tol, "sgemm %dx%dx%d" % (M, N, K))
     tol_r = tol + kc.U24 * torch.relu(ref)
     r = max(r, kc.assert_elementwise(ops.sgemm(a, w, b, act_out=2), torch.relu(ref), tol_r, "sgemm + ReLU %dx%dx%d" % (M, N, K)))   # ACT_RELU

@@ -1,24 +1,19 @@
 """GPU (-m gpu): the backward and optimizer kernels of a Score training step (csrc/score_bwd.hip, attention_bwd.hip, optim.hip), each
 alone, per element.
 
-Every kernel is compared with float64 computed here from the very bf16 / fp32 inputs the kernel read, with kernel_checks.assert_elementwise
-and a bound built from the operands the way kernel_checks.gemm_tol is:
-  * an accumulation term C_ACC * n * 2^-24 * sum |terms| for every fp32 sum of n terms (the column sums over rows are carried in float64
-    by the kernels, which leaves the term far from attained);
-  * 2^-8 |value| for every intermediate the kernel rounds to bf16 (P and dS in the attention backward) and for a bf16 output;
-  * 2^-24 |value| per fp32 rounding of the element chain, and a stated absolute allowance where libm's erff / expf / logf enter.
-The bound is stated next to each check.  Each test prints its largest err / tol (run with -s); DESIGN.md section 4.11 records them."""
+Every kernel is compared with float64 computed from the very bf16 / fp32 inputs the kernel read, with kernel_checks.assert_elementwise
+and a bound built from the operands the way kernel_checks.gemm_tol is.  The references and bounds live in kernel_checks.py (its "Score
+training step" section states each next to its expression): tests/test_gpu_train_tape.py holds every call of a whole backward to the same
+ones.  Each test prints its largest err / tol (run with -s); DESIGN.md section 4.11 records them."""
 import math
 
 import pytest
 import torch
 
 import kernel_checks as kc
-from kernel_checks import C_ACC, U8, U24
+from kernel_checks import U24, attn_bwd_ref
 
 pytestmark = pytest.mark.gpu
-
-LIBM_ABS = 1e-6          # |erff|, |expf| on [-inf, 0], sigmoid: a few fp32 ulp of a value <= 1 (as GELU_FAST_ABS allows the forward)
 
 
 def bf(t):
@@ -39,8 +34,7 @@ def test_transpose_cast_is_exact_and_zero_pads(R, C, src_bf16):
     src = torch.randn(R, C, generator=g)
     src = bf(src) if src_bf16 else src
     Rp = ops.pad64(R)
-    want = torch.zeros(C, Rp, dtype=torch.bfloat16)
-    want[:, :R] = bf(src).t()
+    want = kc.transpose_cast_want(src, Rp)
     big = torch.full((C + 2, Rp + 64), 7.0, dtype=torch.bfloat16, device="cuda")       # guard band around the destination view
     out = ops.transpose_cast_bf16(src.cuda(), out=big[1:C + 1, :Rp])
     assert out.shape == (C, Rp) and torch.equal(out.cpu(), want)
@@ -60,9 +54,7 @@ def test_colsum(M, C, dt):
     g = torch.Generator().manual_seed(M + C)
     dy = torch.randn(M, C, generator=g).to(dt)
     out = ops.colsum(dy.cuda())
-    ref = dy.double().sum(0)
-    # bound: one fp32 sum of M terms + the stored value's rounding
-    tol = C_ACC * M * U24 * dy.double().abs().sum(0) + U24 * ref.abs()
+    ref, tol = kc.colsum_ref(dy)
     report("colsum %dx%d %s" % (M, C, dt), kc.assert_elementwise(out.cpu(), ref, tol, "colsum"))
     assert torch.equal(ops.colsum(dy.cuda()), out)
 
@@ -74,18 +66,16 @@ def test_wgrad_and_dgrad_through_the_nt_route(M, N, K):
     g = torch.Generator().manual_seed(M * N + K)
     dy, x, w = torch.randn(M, N, generator=g), torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / N ** 0.5
     dw = ops.wgrad(dy.cuda(), x.cuda())
-    a, b = bf(dy).t().contiguous(), bf(x).t().contiguous()                           # the operands the GEMM read: [N, M], [K, M]
     assert dw.shape == (N, K) and dw.dtype == torch.float32
-    # bound: gemm_tol over the padded contraction length (the pad adds exact zeros)
-    tol = kc.gemm_tol(a, b, None, ops.pad64(M), torch.float32)
-    report("wgrad M%d N%d K%d" % (M, N, K), kc.assert_elementwise(dw.cpu(), a.double() @ b.double().T, tol, "wgrad"))
+    ref, tol = kc.wgrad_ref(dy, x)
+    report("wgrad M%d N%d K%d" % (M, N, K), kc.assert_elementwise(dw.cpu(), ref, tol, "wgrad"))
     dyb = bf(dy)
     w_t = ops.transpose_cast_bf16(w.cuda())                                          # [K, pad64(N)]
     assert w_t.shape == (K, ops.pad64(N))
     dx = ops.dgrad(dyb.cuda(), w_t)
     wt = bf(w).t().contiguous()                                                      # [K, N]
-    tol = kc.gemm_tol(dyb, wt, None, N, torch.float32)
-    report("dgrad M%d N%d K%d" % (M, N, K), kc.assert_elementwise(dx.cpu(), dyb.double() @ wt.double().T, tol, "dgrad"))
+    ref, tol = kc.dgrad_ref(dyb, wt)
+    report("dgrad M%d N%d K%d" % (M, N, K), kc.assert_elementwise(dx.cpu(), ref, tol, "dgrad"))
 
 
 # ------------------------------------------------------------------------------------------------ LayerNorm + modulate backward
@@ -106,37 +96,13 @@ def test_layernorm_modulate_bwd(M, rps, offset):
     x, dy, scale, dx0 = ln_case(M, C, rps, M + rps + int(offset), offset)
     dx = dx0.clone().cuda()
     dsh, dsc = ops.layernorm_modulate_bwd(x.cuda(), dy.cuda(), dx, scale=scale.cuda(), mod_sample_stride=C, rows_per_sample=rps)
-    x6, dy6 = x.double(), dy.double()
-    mean, var = x6.mean(1, keepdim=True), x6.var(1, unbiased=False, keepdim=True)
+    ref, tol, (mean, var) = kc.layernorm_modulate_bwd_ref(x, dy, scale, rps, dx0)
     if offset:
         assert 50 < float((mean ** 2 / var).min())
-    rstd = 1 / torch.sqrt(var + 1e-6)
-    xh = (x6 - mean) * rstd
-    s1 = 1 + scale.double().repeat_interleave(rps, 0)
-    gg = dy6 * s1
-    mg, mgx = gg.mean(1, keepdim=True), (gg * xh).mean(1, keepdim=True)
-    ref_dx = dx0.double() + rstd * (gg - mg - xh * mgx)
-    # bound.  Row statistics in fp32: mean = a C-term sum (C_ACC C 2^-24 mean|x|, + its rounding); d = x - mean inherits it, so
-    # e_xh = |error of LN(x)| = 2^-24 (4 (1 + |xh|) + (C_ACC C + 2) mean|x| / std); rstd: relative e_r = e_xh(row max) + 2^-24 (C_ACC C + 8).
-    # The two row means of g and g xh: C_ACC C 2^-24 mean|.| each (+ mean|g| e_xh).  Element chain: 2^-24 per operation on its magnitude.
-    sd = torch.sqrt(var)
-    e_xh = U24 * (4 * (1 + xh.abs()) + (C_ACC * C + 2) * x6.abs().mean(1, keepdim=True) / sd)
-    e_r = e_xh.amax(1, keepdim=True) + U24 * (C_ACC * C + 8)
-    e_mg = U24 * (C_ACC * C + 2) * gg.abs().mean(1, keepdim=True)
-    e_mgx = U24 * (C_ACC * C + 2) * (gg * xh).abs().mean(1, keepdim=True) + (gg.abs() * e_xh).mean(1, keepdim=True)
-    inner = gg - mg - xh * mgx
-    tol_dx = (rstd * (4 * U24 * (gg.abs() + mg.abs() + (xh * mgx).abs()) + e_mg + e_xh * mgx.abs() + xh.abs() * e_mgx)
-              + (e_r + 2 * U24) * (rstd * inner).abs() + U24 * ref_dx.abs())
-    r = kc.assert_elementwise(dx.cpu(), ref_dx, tol_dx, "layernorm_modulate_bwd dx")
+    r = kc.assert_elementwise(dx.cpu(), ref["dx"], tol["dx"], "layernorm_modulate_bwd dx")
     S = M // rps
-    ref_sh = dy6.view(S, rps, C).sum(1)
-    ref_sc = (dy6 * xh).view(S, rps, C).sum(1)
-    # dshift: float64 sum of fp32 terms, one rounding (+ the issue's accumulation term).  dscale: each term fp32(dy * xh): |dy| e_xh + 2^-24 |dy xh|.
-    tol_sh = C_ACC * rps * U24 * dy6.abs().view(S, rps, C).sum(1) + U24 * ref_sh.abs()
-    tol_sc = ((dy6.abs() * e_xh + U24 * (dy6 * xh).abs()).view(S, rps, C).sum(1) + C_ACC * rps * U24 * (dy6 * xh).abs().view(S, rps, C).sum(1)
-              + U24 * ref_sc.abs())
-    r = max(r, kc.assert_elementwise(dsh.cpu(), ref_sh, tol_sh, "layernorm_modulate_bwd dshift"),
-            kc.assert_elementwise(dsc.cpu(), ref_sc, tol_sc, "layernorm_modulate_bwd dscale"))
+    r = max(r, kc.assert_elementwise(dsh.cpu(), ref["dshift"], tol["dshift"], "layernorm_modulate_bwd dshift"),
+            kc.assert_elementwise(dsc.cpu(), ref["dscale"], tol["dscale"], "layernorm_modulate_bwd dscale"))
     report("layernorm_modulate_bwd M%d rps%d off%g" % (M, rps, offset), r)
     wide = torch.full((S, 6 * C), 7.0, device="cuda")                               # dshift / dscale into column blocks of wider rows
     dx3 = dx0.clone().cuda()
@@ -161,11 +127,7 @@ def test_gelu_bwd(M, dh_dt):
     u[0, :8] = bf(torch.tensor([-12.0, -6.0, -3.0, -0.0, 0.0, 3.0, 6.0, 12.0]))
     dh = torch.randn(M, C, generator=g).to(dh_dt)
     out = ops.gelu_bwd(u.cuda(), dh.cuda())
-    u6 = u.double()
-    dgelu = 0.5 * (1 + torch.erf(u6 / math.sqrt(2))) + u6 * torch.exp(-0.5 * u6 * u6) / math.sqrt(2 * math.pi)
-    ref = dh.double() * dgelu
-    # bound: bf16 output 2^-8 |ref|; fp32 chain 8 x 2^-24 |ref|; erff and expf absolute accuracy times |dh| (1 + |u|)
-    tol = U8 * ref.abs() + 8 * U24 * ref.abs() + LIBM_ABS * dh.double().abs() * (1 + u6.abs())
+    ref, tol = kc.gelu_bwd_ref(u, dh)
     report("gelu_bwd M%d %s" % (M, dh_dt), kc.assert_elementwise(out.cpu(), ref, tol, "gelu_bwd"))
 
 
@@ -180,13 +142,9 @@ def test_gate_residual_bwd(M, rps, a_dt):
     gate = mod[:, 2 * C:3 * C]
     da, dg = ops.gate_residual_bwd(dy.cuda(), mod.cuda()[:, 2 * C:3 * C], a.cuda(), rows_per_sample=rps)
     S = M // rps
-    ref_da = dy.double() * gate.double().repeat_interleave(rps, 0)
-    terms = dy.double() * a.double()
-    ref_dg = terms.view(S, rps, C).sum(1)
-    # bound: da one fp32 product then bf16; dgate float64 sum of fp32 products (2^-24 each) + the accumulation term + its rounding
-    r = kc.assert_elementwise(da.cpu(), ref_da, (U8 + U24) * ref_da.abs(), "gate_residual_bwd da")
-    tol = (1 + C_ACC * rps) * U24 * terms.abs().view(S, rps, C).sum(1) + U24 * ref_dg.abs()
-    r = max(r, kc.assert_elementwise(dg.cpu(), ref_dg, tol, "gate_residual_bwd dgate"))
+    ref, tol = kc.gate_residual_bwd_ref(dy, gate, a, rps)
+    r = kc.assert_elementwise(da.cpu(), ref["da"], tol["da"], "gate_residual_bwd da")
+    r = max(r, kc.assert_elementwise(dg.cpu(), ref["dgate"], tol["dgate"], "gate_residual_bwd dgate"))
     report("gate_residual_bwd M%d rps%d %s" % (M, rps, a_dt), r)
     da2, none = ops.gate_residual_bwd(dy.cuda(), mod.cuda()[:, 2 * C:3 * C], None, rows_per_sample=rps)
     assert none is None and torch.equal(da2, da)
@@ -201,15 +159,11 @@ def test_silu_bwd():
     c, dy = torch.randn(200, 128, generator=g) * 3, torch.randn(200, 128, generator=g)
     c[0, :4] = torch.tensor([-30.0, -0.0, 0.0, 30.0])
     out = ops.silu_bwd(c.cuda(), dy.cuda())
-    c6 = c.double()
-    sg = torch.sigmoid(c6)
-    ref = dy.double() * sg * (1 + c6 * (1 - sg))
-    # bound: fp32 chain 8 x 2^-24 |ref| + the sigmoid's absolute accuracy times |dy| (1 + |c|)
-    tol = 8 * U24 * ref.abs() + LIBM_ABS * dy.double().abs() * (1 + c6.abs())
-    report("silu_bwd", kc.assert_elementwise(out.cpu(), ref, tol, "silu_bwd"))
+    ref, tol = kc.silu_bwd_ref(c, dy)
+    report("silu_bwd", kc.assert_elementwise(out.cpu(), ref["dc"], tol["dc"], "silu_bwd"))
     out2, act = ops.silu_bwd(c.cuda(), dy.cuda(), want_act=True)                      # + SiLU(c), the next Linear's wgrad operand
     assert torch.equal(out2, out)
-    kc.assert_elementwise(act.cpu(), c6 * sg, 4 * U24 * (c6 * sg).abs() + LIBM_ABS * c6.abs(), "silu_bwd act")
+    kc.assert_elementwise(act.cpu(), ref["act"], tol["act"], "silu_bwd act")
 
 
 @pytest.mark.parametrize("B,T", [(2, 8), (25, 8), (1, 200)])
@@ -223,13 +177,8 @@ def test_dsm_loss_bwd(B, T, l1, weighted):
     params[0, 0, :4] = eta[0, 0, :4]                                                  # d = 0: the l1 gradient is 0 there
     w = torch.rand(B, generator=g) + 0.5 if weighted else None
     out = ops.dsm_loss_bwd(eta.cuda(), params.cuda(), None if w is None else w.cuda(), l1=l1)
-    p6 = params.double().requires_grad_(True)
-    d = eta.double() - p6
-    dist = d.abs() if l1 else d * d
-    (dist * (1 if w is None else w.double()[:, None, None])).mean().backward()
-    # bound: four fp32 roundings (d, the factor 2 is exact, the weight, 1 / n and its product)
-    report("dsm_loss_bwd B%d T%d l1=%d w=%d" % (B, T, l1, weighted),
-           kc.assert_elementwise(out.cpu(), p6.grad, 4 * U24 * p6.grad.abs(), "dsm_loss_bwd"))
+    ref, tol = kc.dsm_loss_bwd_ref(eta, params, w, l1)
+    report("dsm_loss_bwd B%d T%d l1=%d w=%d" % (B, T, l1, weighted), kc.assert_elementwise(out.cpu(), ref, tol, "dsm_loss_bwd"))
 
 
 def test_embedding_grad():
@@ -239,11 +188,8 @@ def test_embedding_grad():
     dc = torch.randn(B, D, generator=g)
     label = torch.tensor([2, 0, 2, 1, 0, 2, 2, 0])                                    # class 3 has no sample: a zero row
     out = ops.embedding_grad(dc.cuda(), label.cuda(), K)
-    ref = torch.zeros(K, D, dtype=torch.float64).index_add_(0, label, dc.double())
-    mag = torch.zeros(K, D, dtype=torch.float64).index_add_(0, label, dc.double().abs())
-    # bound: n_k - 1 sequential fp32 additions of class k's rows, worst case (n_k <= 4 here: C_ACC's statistics do not apply)
-    nk = torch.bincount(label, minlength=K).double()[:, None]
-    report("embedding_grad", kc.assert_elementwise(out.cpu(), ref, (nk - 1).clamp_min(0) * U24 * mag, "embedding_grad"))
+    ref, tol = kc.embedding_grad_ref(dc, label, K)
+    report("embedding_grad", kc.assert_elementwise(out.cpu(), ref, tol, "embedding_grad"))
     assert float(out[3].abs().max()) == 0.0
 
 
@@ -257,37 +203,6 @@ def attn_case(B, H, N, seed, large_logit=False):
         k = qkv[:, C:2 * C].view(B, N, H, 64)
         q += 12.0 * k[:, (7 * torch.arange(N) + 3) % N]
     return bf(qkv), bf(torch.randn(B, H, N, 64, generator=g))
-
-
-def attn_bwd_ref(qkv, o, do, B, H, N):
-    """float64 from the bf16 operands: -> dict of references and of componentwise bounds, [B, H, N, 64] each."""
-    C = H * 64
-    hd = lambda z: z.double().view(B, N, H, 64).permute(0, 2, 1, 3)
-    q, k, v = hd(qkv[:, :C]), hd(qkv[:, C:2 * C]), hd(qkv[:, 2 * C:])
-    o6, g6 = o.double(), do.double()
-    sc = 0.125
-    s = q @ k.transpose(-1, -2) * sc
-    L = torch.logsumexp(s, -1, keepdim=True)
-    P = torch.exp(s - L)
-    D = (g6 * o6).sum(-1, keepdim=True)
-    dP = g6 @ v.transpose(-1, -2)
-    dS = P * (dP - D)
-    ref = {"dq": dS @ k * sc, "dk": dS.transpose(-1, -2) @ q * sc, "dv": P.transpose(-1, -2) @ g6}
-    # bound.  s and dP: fp32 MFMA sums of 64 terms (C_ACC 64 2^-24 |.||.|); the exponent s - L carries that of s twice (L is built from the
-    # same sums) + 8 x 2^-24 (|s| + |L|) of its fp32 arithmetic + expf / logf: P's relative error e_arg.  D: a 64-term fp32 sum.
-    # dS in fp32: P e_arg |dP - D| + P (e_dP + e_D) + 2 x 2^-24 |dS|; THEN ROUNDED TO bf16: + 2^-8 |dS|.  P ROUNDED TO bf16 for dV: + 2^-8 P.
-    # Second products: C_ACC N 2^-24 |.||.| each, scaled by 1 / 8 in fp32 (dq, dk), and the bf16 output 2^-8 |ref|.
-    acc = C_ACC * 64 * U24
-    e_arg = 2 * acc * (q.abs() @ k.abs().transpose(-1, -2)) * sc + 8 * U24 * (s.abs() + L.abs()) + 4 * LIBM_ABS
-    e_dP = acc * (g6.abs() @ v.abs().transpose(-1, -2))
-    e_D = acc * (g6.abs() * o6.abs()).sum(-1, keepdim=True)
-    e_dS = P * e_arg * (dP - D).abs() + P * (e_dP + e_D) + (2 * U24 + U8) * dS.abs()
-    e_P = P * e_arg + U8 * P
-    acc2 = C_ACC * N * U24
-    tol = {"dq": sc * (e_dS @ k.abs() + acc2 * (dS.abs() @ k.abs())) + (U8 + 2 * U24) * ref["dq"].abs(),
-           "dk": sc * (e_dS.transpose(-1, -2) @ q.abs() + acc2 * (dS.abs().transpose(-1, -2) @ q.abs())) + (U8 + 2 * U24) * ref["dk"].abs(),
-           "dv": e_P.transpose(-1, -2) @ g6.abs() + acc2 * (P.transpose(-1, -2) @ g6.abs()) + (U8 + U24) * ref["dv"].abs()}
-    return ref, tol
 
 
 @pytest.mark.parametrize("B,H,N,large", [(2, 2, 8, False), (1, 2, 72, False), (1, 1, 256, False), (1, 2, 72, True)])
