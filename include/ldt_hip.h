@@ -95,13 +95,13 @@ int ldt_layernorm_modulate(const float* x, int64_t ldx, uint16_t* y, int64_t ldy
 /* ---- fused multi-head attention ---------------------------------------------------------------------
  * O[b,h,n,:] = softmax(Q K^T / sqrt(Dh)) V, heads at channel offset h*Dh of each row; output is the
  * contiguous [B][H][Nq][Dh] buffer the reference reinterprets as (B,N,C) (model/layers.py:190-197, Q1).
- * head_dim 32 or 64.  K and V share kv_batch_stride. */
+ * head_dim 8, 16, 32 or 64.  K and V share kv_batch_stride. */
 int ldt_attention_fwd(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride,
                       const uint16_t* K, int64_t ldk, const uint16_t* V, int64_t ldv, int64_t kv_batch_stride,
                       uint16_t* O, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim, void* stream);
 /* Which kernel ldt_attention_fwd runs for a problem of this shape (a query, not a launch; the return value is the route, not a status):
  * 0 = streaming (attn_fwd_kernel<head_dim>), 1 = resident (attn_fwd_resident_kernel<head_dim>), 2 = whole-head
- * (attn_fwd_head_kernel<64, ceil(Nk / 64)>).  bench.py uses it to name the rocprofv3 symbol of the kernel it timed. */
+ * (attn_fwd_head_kernel<64, ceil(Nk / 64)>), 3 = narrow heads (attn_fwd_narrow_kernel<head_dim>: every shape with head_dim 8 or 16).  bench.py uses it to name the rocprofv3 symbol of the kernel it timed. */
 int ldt_attention_route(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim);
 /* Which kernel ldt_gemm_bf16 (fold = 0), ldt_gemm_resid_lnstats / ldt_gemm_lnfold (fold = 256 or 32: the statistics granule; producer when
  * epilogue == LDT_EPI_RESID_F32, consumer otherwise) runs for a problem of this shape (a query, not a launch; the return value is the route,
@@ -123,7 +123,7 @@ int ldt_gemm_route(int32_t epilogue, int32_t M, int32_t N, int32_t K, int64_t ld
  *                                     fold_step_stride; bias NULL: it is part of fold_C)
  * O is the contiguous [B][heads][tokens][head_dim] buffer of ldt_attention_fwd; the softmax weights are rounded to bf16 before P V.
  * One launch when a fused form takes the shape (ldt_qkv_attention_route != 0): QKV is then not written.  Otherwise ldt_gemm_bf16 /
- * ldt_gemm_lnfold into QKV[B*tokens][3*hidden] (q alone in the cross form) and ldt_attention_fwd.  head_dim 32 or 64; K % 64 == 0. */
+ * ldt_gemm_lnfold into QKV[B*tokens][3*hidden] (q alone in the cross form) and ldt_attention_fwd.  head_dim 8, 16, 32 or 64 (the fused forms take 64 only: narrow heads run the two kernels); K % 64 == 0. */
 int ldt_qkv_attention(const uint16_t* X, int64_t ldx, const uint16_t* W, int64_t ldw, const float* bias,
                       const float* stats, int32_t stats_parts, const float* fold_S, const float* fold_C, int64_t fold_step_stride,
                       const uint16_t* kv_cond, int64_t ldkv, int64_t kv_batch_stride, uint16_t* O, uint16_t* QKV,

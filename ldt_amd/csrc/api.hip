@@ -265,7 +265,7 @@ static int check_plan(const ldt_score_plan* p) {
     LDT_REQUIRE(p->blocks > 0 && p->blocks <= LDT_MAX_BLOCKS, LDT_ESHAPE, "score: blocks=%d out of range", p->blocks);
     LDT_REQUIRE(p->hidden > 0 && p->heads > 0 && p->hidden % p->heads == 0, LDT_ESHAPE, "score: hidden %% heads");
     const int dh = p->hidden / p->heads;
-    LDT_REQUIRE(dh == 32 || dh == 64, LDT_ESHAPE, "score: head dim %d not built (32, 64)", dh);
+    LDT_REQUIRE(dh == 8 || dh == 16 || dh == 32 || dh == 64, LDT_ESHAPE, "score: head dim %d not built (8, 16, 32, 64)", dh);
     LDT_REQUIRE(p->hidden % 64 == 0 && p->mlp_hidden % 64 == 0 && p->z_pad % 64 == 0 && p->z_pad >= p->z_dim, LDT_ESHAPE,
                 "score: hidden/mlp_hidden/z_pad must be multiples of 64");
     LDT_REQUIRE(p->z_dim % 4 == 0, LDT_ESHAPE, "score: z_dim %% 4");
@@ -367,7 +367,8 @@ extern "C" int ldt_qkv_attention(const uint16_t* X, int64_t ldx, const uint16_t*
     LDT_REQUIRE(X && W && O && QKV, LDT_EARG, "qkv_attention: null pointer");
     LDT_REQUIRE(B > 0 && tokens > 0 && hidden > 0 && heads > 0 && hidden % heads == 0 && hidden % 64 == 0 && K > 0, LDT_ESHAPE,
                 "qkv_attention: B=%d tokens=%d hidden=%d heads=%d K=%d", B, tokens, hidden, heads, K);
-    LDT_REQUIRE(hidden / heads == 32 || hidden / heads == 64, LDT_ESHAPE, "qkv_attention: head dim %d not built (32, 64)", hidden / heads);
+    const int dh = hidden / heads;
+    LDT_REQUIRE(dh == 8 || dh == 16 || dh == 32 || dh == 64, LDT_ESHAPE, "qkv_attention: head dim %d not built (8, 16, 32, 64)", dh);
     LDT_REQUIRE(!kv_cond || (cond_tokens > 0 && !stats), LDT_EARG, "qkv_attention: cross-attention needs cond_tokens and has no folded form");
     LDT_REQUIRE(!stats || (fold_S && fold_C && stats_parts > 0 && !bias), LDT_EARG, "qkv_attention: the folded form needs fold_S, fold_C, stats_parts and takes no bias (it is part of fold_C)");
     QkvAttnStep q{BF(X), ldx, BF(W), ldw, bias, stats, stats_parts, fold_S, fold_C, fold_step_stride, BF(kv_cond), ldkv, kv_batch_stride,

@@ -659,8 +659,9 @@ int ldt_attn_oproj_launch(const AttnArgs* a, int dh, hipStream_t s) {
 }
 
 // Which kernel ldt_attn_launch takes for a problem: 0 = streaming (attn_fwd_kernel), 1 = resident (attn_fwd_resident_kernel), 2 = whole-head
-// (attn_fwd_head_kernel<64, ceil(Nk / 64)>).  Also exported (ldt_attention_route) so that bench.py names the symbol it timed instead of guessing.
+// (attn_fwd_head_kernel<64, ceil(Nk / 64)>), 3 = narrow heads, Dh 8 or 16 (attn_fwd_narrow_kernel, attention_narrow.hip).  Also exported (ldt_attention_route) so that bench.py names the symbol it timed instead of guessing.
 int ldt_attn_route(int B, int H, int Nq, int Nk, int dh) {
+    if (dh == 8 || dh == 16) return 3;                      // narrow heads: one kernel for every shape (attention_narrow.hip)
     // Short sequences (one 128-row query block, keys/values of a head fit 64 KiB of LDS): resident kernel — K/V
     // loaded once, no per-tile barrier (measured 9.0 vs 9.7 us at T=32).  Longer query sets run the streaming
     // kernel, which spreads (b,h,q-block) over more workgroups (35 vs 37 us at T=256, 46 vs 56 us at 2048x256).
@@ -673,10 +674,11 @@ int ldt_attn_route(int B, int H, int Nq, int Nk, int dh) {
 
 int ldt_attn_launch(const AttnArgs* a, int dh, hipStream_t s) {
     LDT_REQUIRE(a->B > 0 && a->H > 0 && a->Nq > 0 && a->Nk > 0, LDT_ESHAPE, "attention: empty problem B=%d H=%d Nq=%d Nk=%d", a->B, a->H, a->Nq, a->Nk);
-    LDT_REQUIRE(dh == 32 || dh == 64, LDT_ESHAPE, "attention: head dim %d not built (32, 64)", dh);
+    LDT_REQUIRE(dh == 8 || dh == 16 || dh == 32 || dh == 64, LDT_ESHAPE, "attention: head dim %d not built (8, 16, 32, 64)", dh);
     LDT_REQUIRE(attn_qkv_aligned(a) && ldt_aligned16(a->O), LDT_EALIGN, "attention: Q/K/V rows must be 16-byte aligned");
     LDT_REQUIRE(a->H <= 65535 && a->B <= 65535, LDT_ESHAPE, "attention: grid too large");
     const int route = ldt_attn_route(a->B, a->H, a->Nq, a->Nk, dh);
+    if (route == 3) return ldt_attn_narrow_launch(a, dh, s);
     if (route == 1) return dh == 64 ? launch_resident<64>(a, s) : launch_resident<32>(a, s);
     if (route == 2) return launch_head<64>(a, s);
     const long nqb = (a->Nq + 127) / 128, groups = ((long)a->B * a->H + 7) / 8;
