@@ -357,7 +357,7 @@ int ldt_nelbo_terms(const float* eta, const float* params, const float* logqz, c
 int ldt_occupancy_grid(const float* pts, int32_t S, int32_t n, const float* cells, int32_t G, uint32_t* counters, uint32_t* bernoulli,
                        void* stream);
 
-/* ---- Score training: the backward pieces and the optimizer (score_bwd.hip, attention_bwd.hip, optim.hip) ----
+/* ---- Score training: the backward pieces and the optimizer (score_bwd.hip, attention_bwd.hip, attention_narrow_bwd.hip, optim.hip) ----
  * What trainer/Latent_SDE_Trainer.py:137-140 (`loss.backward()`, clip_grad_norm_, EMA(Adam).step()) needs under the forward kernels above,
  * for the AdaLN LayerNorm Score blocks the shipped YAMLs train.  The backward GEMMs are NOT here: dgrad dX = dY . W and wgrad dW = dY^T . X
  * are ldt_gemm_bf16 (LDT_EPI_F32 / LDT_EPI_BF16) on operands ldt_transpose_cast_bf16 prepares.  Like the evaluation kernels: status codes
@@ -385,6 +385,10 @@ int ldt_occupancy_grid(const float* pts, int32_t S, int32_t n, const float* cell
  *   permuted); dQ, dK, dV are written as row views like Q, K, V (heads at column h * 64; dK and dV share dkv_batch_stride).  Row maximum and
  *   sum are recomputed (the forward writes no log-sum-exp) into stats fp32 [B][H][N][2] = (max + ln sum, rowsum(dO o O)).  bf16 MFMA, fp32
  *   accumulation; P and dS are rounded to bf16 before the second products.  dQ per query block, dK / dV per key block: no sum across workgroups.
+ * ldt_attention_bwd_narrow: the same contract for head_dim 8, 16 or 32 (scale head_dim^-0.5; ldt_attention_bwd keeps taking 64 alone).  32 runs
+ *   the kernels of ldt_attention_bwd instantiated at 32.  8 and 16 (attention_narrow_bwd.hip): one wave per 16 rows, MFMA first products with
+ *   the channel extent zero-padded, second products as per-lane fp32 FMAs: P and dS stay fp32; row statistics and dQ in one launch, dK / dV in
+ *   a second.  dQ, dK, dV rows must be 8-byte aligned (row and batch strides % 4 == 0).
  * ldt_sumsq: out[0] = sum x^2 (two stages, float64 partials in scratch[scratch_len], at most LDT_ODE_SUMSQ_SCRATCH used), out[1] = its root
  *   (clip_grad_norm_'s total_norm over the flat gradient), out[2] = min(1, max_norm / (out[1] + 1e-6)) (clip_coef_clamped; 1 when max_norm <= 0).
  * ldt_adam_ema_step: torch.optim.Adam's update (torch/optim/adam.py _single_tensor_adam: L2 weight_decay added to the gradient, exp_avg.lerp_,
@@ -413,6 +417,10 @@ int ldt_attention_bwd(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, co
                       int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats, uint16_t* dQ,
                       int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
                       int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t N, int32_t head_dim, void* stream);
+int ldt_attention_bwd_narrow(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk, const uint16_t* V,
+                             int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats, uint16_t* dQ,
+                             int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
+                             int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t N, int32_t head_dim, void* stream);
 int ldt_sumsq(const float* x, int64_t n, double* scratch, int32_t scratch_len, float max_norm, float* out, void* stream);
 int ldt_adam_ema_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, double lr, double beta1,
                       double beta2, double eps, double weight_decay, int32_t step, double ema_decay, int32_t ema_init,

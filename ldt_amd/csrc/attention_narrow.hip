@@ -18,17 +18,6 @@
 // of bounds); their scores are -inf, so their weights are exactly 0.
 #include "kernels.h"
 
-template <int N, int M>
-__device__ __forceinline__ void narrow_halve(float* v, int lr) {   // lanes lr, lr ^ M: the one with bit M keeps the upper half of v[0..N)
-    const bool up = (lr & M) != 0;
-#pragma unroll
-    for (int k = 0; k < N / 2; ++k) {
-        const float keep = up ? v[k + N / 2] : v[k];
-        const float send = up ? v[k] : v[k + N / 2];
-        v[k] = keep + __shfl_xor(send, M, 64);
-    }
-}
-
 template <int DH>
 __global__ __launch_bounds__(256) void attn_fwd_narrow_kernel(const AttnArgs a, long units, int nqb) {
     constexpr int NC = DH / 8;                                          // 16-byte pieces of a head's slice of a row

@@ -110,6 +110,31 @@ int ldt_attn_launch(const AttnArgs* a, int dh, hipStream_t s);
 int ldt_attn_route(int B, int H, int Nq, int Nk, int dh);       // 0 streaming, 1 resident, 2 whole-head (attention.hip), 3 narrow heads (attention_narrow.hip)
 int ldt_attn_narrow_launch(const AttnArgs* a, int dh, hipStream_t s);   // head dim 8 or 16; ldt_attn_launch has checked the operands
 int ldt_attn_oproj_launch(const AttnArgs* a, int dh, hipStream_t s);
+// attention backward (self-attention, Nq = Nk = N <= 512): the operands of ldt_attention_bwd / ldt_attention_bwd_narrow (include/ldt_hip.h)
+struct AttnBwdArgs {
+    const bf16_t* Q; long ldq; long q_bs;
+    const bf16_t* K; long ldk; const bf16_t* V; long ldv; long kv_bs;
+    const bf16_t* O; const bf16_t* dO;        // [B][H][N][Dh]
+    float* stats;                             // [B][H][N][2] = (L, D)
+    bf16_t* dQ; long lddq; long dq_bs;
+    bf16_t* dK; long lddk; bf16_t* dV; long lddv; long dkv_bs;
+    int B, H, N;
+    float scale;                              // Dh^-0.5
+};
+int ldt_attn_bwd_launch(const AttnBwdArgs* a, int dh, hipStream_t s);          // attention_bwd.hip: head dim 64 or 32 (MFMA second products)
+int ldt_attn_bwd_narrow_launch(const AttnBwdArgs* a, int dh, hipStream_t s);   // attention_narrow_bwd.hip: head dim 8 or 16
+// Sum of v[0..N) over the lanes lr and lr ^ M, split between them: the lane with bit M keeps the upper half of v.  Four of these (M = 8, 4, 2,
+// 1) sum a per-lane array over the 16 lanes of an MFMA row group in a fixed order and leave each lane N / 16 adjacent elements (narrow heads).
+template <int N, int M>
+__device__ __forceinline__ void narrow_halve(float* v, int lr) {
+    const bool up = (lr & M) != 0;
+#pragma unroll
+    for (int k = 0; k < N / 2; ++k) {
+        const float keep = up ? v[k + N / 2] : v[k];
+        const float send = up ? v[k] : v[k + N / 2];
+        v[k] = keep + __shfl_xor(send, M, 64);
+    }
+}
 int ldt_cast_pad_launch(const float* src, long lds, bf16_t* dst, long ldd, long rows, int cols, int cols_pad, hipStream_t s);
 int ldt_sampler_step_launch(const StepArgs* a, hipStream_t s);
 int ldt_advance_step_launch(int* step_ptr, hipStream_t s);

@@ -939,9 +939,12 @@ def embedding_grad(dc, label, n_classes):
 
 
 def attention_bwd(q, k, v, o, do, B, H, N, head_dim=64, out=None):
-    """Self-attention backward: q, k, v bf16 row views [B*N, >= H*64] as attention_fwd takes them, o and do the contiguous bf16
-    [B, H, N, 64] buffers (quirk Q1: the raw (B*N, C) view).  -> (dq, dk, dv) bf16 views [B*N, H*64] of one [B*N, 3*H*64] tensor (`out`
-    when given), the dY operand of the QKV projection's backward GEMMs."""
+    """Self-attention backward: q, k, v bf16 row views [B*N, >= H*head_dim] as attention_fwd takes them, o and do the contiguous bf16
+    [B, H, N, head_dim] buffers (quirk Q1: the raw (B*N, C) view).  -> (dq, dk, dv) bf16 views [B*N, H*head_dim] of one
+    [B*N, 3*H*head_dim] tensor (`out` when given), the dY operand of the QKV projection's backward GEMMs.
+    head_dim 64: ldt_attention_bwd; 8, 16 or 32: ldt_attention_bwd_narrow; anything else is a ValueError."""
+    if head_dim not in (8, 16, 32, 64):
+        raise ValueError("attention_bwd: head_dim %r is not 8, 16, 32 or 64" % (head_dim,))
     for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
         _need(t, torch.bfloat16, nm); _rowmajor(t, nm)
     if not (o.is_contiguous() and do.is_contiguous()) or o.numel() != B * H * N * head_dim or do.numel() != o.numel():
@@ -953,9 +956,9 @@ def attention_bwd(q, k, v, o, do, B, H, N, head_dim=64, out=None):
     dq, dk, dv = out[:, :Cc], out[:, Cc:2 * Cc], out[:, 2 * Cc:]
     stats = torch.empty((B, H, N, 2), dtype=torch.float32, device=q.device)
     ldo = out.stride(0)
-    check(lib().ldt_attention_bwd(_p(q), q.stride(0), q.stride(0) * N, _p(k), k.stride(0), _p(v), v.stride(0), k.stride(0) * N, _p(o), _p(do),
-                                  _p(stats), _p(dq), ldo, ldo * N, _p(dk), ldo, _p(dv), ldo, ldo * N, B, H, N, head_dim, stream_ptr()),
-          "ldt_attention_bwd")
+    name = "ldt_attention_bwd" if head_dim == 64 else "ldt_attention_bwd_narrow"
+    check(getattr(lib(), name)(_p(q), q.stride(0), q.stride(0) * N, _p(k), k.stride(0), _p(v), v.stride(0), k.stride(0) * N, _p(o), _p(do),
+                               _p(stats), _p(dq), ldo, ldo * N, _p(dk), ldo, _p(dv), ldo, ldo * N, B, H, N, head_dim, stream_ptr()), name)
     return dq, dk, dv
 
 

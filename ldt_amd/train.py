@@ -2,12 +2,14 @@
 
 Reference: trainer/Latent_SDE_Trainer.py:94-141 (`update`, `update_score`), tools/utils.py:25-101 (EMA around Adam),
 model/scorenet/score.py:117-151 and model/layers.py:183-229 (what is differentiated).  Scope: the configuration the shipped YAMLs
-train — LayerNorm, AdaLN, self-attention with 64-wide heads, unconditional or label-conditioned.
+train — LayerNorm, AdaLN, self-attention with 8-, 16-, 32- or 64-wide heads (the hybrid config's Score: hidden 128, 16 heads),
+unconditional or label-conditioned.
 
 `AdamEMA` keeps fp32 master parameters, gradients, both Adam moments and the EMA in five flat device buffers (one fused
 `ldt_adam_ema_step` launch per step; bf16 operand panels are derived from the masters, never trained).  `ScoreTrainStep` runs the same
 kernels as inference, unfused, keeps per block what the backward needs, and then walks the blocks back: every GEMM of the backward is
-`ldt_gemm_bf16` on operands prepared by `ldt_transpose_cast_bf16`; everything else is csrc/score_bwd.hip and csrc/attention_bwd.hip.
+`ldt_gemm_bf16` on operands prepared by `ldt_transpose_cast_bf16`; everything else is csrc/score_bwd.hip, csrc/attention_bwd.hip and
+csrc/attention_narrow_bwd.hip.
 """
 import torch
 
@@ -170,8 +172,9 @@ def refuse_untrainable(model, condition=None, world_size=1):
         raise NotImplementedError("training with dropout=%g is not on this path: the kernels have no dropout mask" % model.dropout)
     if world_size > 1:
         raise NotImplementedError("training on %d ranks is not on this path: the gradient all-reduce is a follow-up" % world_size)
-    if model.hidden_size // model.num_heads != 64:
-        raise NotImplementedError("training needs 64-wide attention heads (ldt_attention_bwd); got %d" % (model.hidden_size // model.num_heads))
+    if model.hidden_size // model.num_heads not in (8, 16, 32, 64):
+        raise NotImplementedError("training needs 8-, 16-, 32- or 64-wide attention heads (ldt_attention_bwd, ldt_attention_bwd_narrow); got %d"
+                                  % (model.hidden_size // model.num_heads))
 
 
 def _t(x):
@@ -298,7 +301,7 @@ class ScoreTrainStep:
             do = linear_bwd(blk.fc_o, da1, sb["o"].view(M, D), epilogue=EPI_BF16)                 # [M, D] == dO [B, H, T, Dh] raw (Q1)
             qkv = sb["qkv"]
             dqkv = torch.empty((M, 3 * D), dtype=torch.bfloat16, device=do.device)                # [dq | dk | dv], the dY of fc_q | fc_kv
-            dq, _, _ = ops.attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], sb["o"], do, B, m.num_heads, T, out=dqkv)
+            dq, _, _ = ops.attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], sb["o"], do, B, m.num_heads, T, head_dim=D // m.num_heads, out=dqkv)
             linear_bwd(blk.fc_q, dq, sb["h"], want_dx=False)
             linear_bwd(blk.fc_kv, dqkv[:, D:], sb["h"], want_dx=False)
             wqkv_t = ops.transpose_cast_bf16(torch.cat([conv_w(blk.fc_q), conv_w(blk.fc_kv)], 0).detach())

@@ -2,6 +2,9 @@
 HIP events around the forward, the backward and the optimizer (one warm-up step, then the median of 7), and the rate against 3 x the
 forward's FLOPs (forward + dgrad + wgrad of every GEMM; the attention backward's extra recomputation is not credited).
     python tools/bench_train.py [out.txt] [tokens ...]          # out.txt defaults to profiles/train_step.txt, the committed record
+Other Score sizes: --hidden H --t-dim D and comma lists --heads a,b,.. --batch a,b,.. (every combination is timed, heads outermost), e.g. the
+hybrid config's Score next to the 2- and 8-head models of the same width (profiles/train_step_narrow.txt):
+    python tools/bench_train.py profiles/train_step_narrow.txt 32 --hidden 128 --t-dim 128 --heads 16,2,8 --batch 8,64
 No speed target is attached to these numbers: the step is the unfused, host-driven form; the follow-up that fuses it starts here."""
 import os
 import statistics
@@ -13,9 +16,18 @@ import ldt_amd  # noqa: E402
 from ldt_amd import ops  # noqa: E402
 from ldt_amd.train import ScoreTrainStep  # noqa: E402
 
-out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "train_step.txt")
-tokens = [int(a) for a in sys.argv[2:]] or [32, 256]
-B, CALLS = 64, 7
+argv, opts = [], {}
+it = iter(sys.argv[1:])
+for a in it:
+    if a in ("--hidden", "--heads", "--t-dim", "--batch"):
+        opts[a] = [int(v) for v in next(it).split(",")]
+    else:
+        argv.append(a)
+out_path = argv[0] if argv else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "train_step.txt")
+tokens = [int(a) for a in argv[1:]] or [32, 256]
+CALLS = 7
+overrides = {k: opts[o][0] for o, k in (("--hidden", "score.hidden_size"), ("--t-dim", "score.t_dim")) if o in opts}
+runs = [(h, b, T) for h in opts.get("--heads", [None]) for b in opts.get("--batch", [64]) for T in tokens]
 lines = []
 
 
@@ -31,8 +43,8 @@ def forward_flops(m, T):
     return gemm + attn
 
 
-for T in tokens:
-    cfg = ldt_amd.airplane_config(latent_tokens=T)
+for heads, B, T in runs:
+    cfg = ldt_amd.airplane_config(latent_tokens=T, **dict(overrides, **({} if heads is None else {"score.num_heads": heads})))
     torch.manual_seed(0)
     model = ldt_amd.Score(cfg.score).cuda()
     opt = ldt_amd.AdamEMA(model.parameters(), lr=1e-4, ema_decay=0.9999)
@@ -60,8 +72,9 @@ for T in tokens:
     med = {k: statistics.median(v) for k, v in ms.items()}
     total = sum(med.values())
     fl = forward_flops(model, T)
-    say("Score training step  B %d  T %d  hidden %d  blocks %d  (%d parameters)  loss %.4f" % (B, T, model.hidden_size, model.num_blocks,
-        sum(p.numel() for p in model.parameters()), float(loss)))
+    say("Score training step  B %d  T %d  hidden %d  blocks %d  (%d parameters)  loss %.4f%s" % (B, T, model.hidden_size, model.num_blocks,
+        sum(p.numel() for p in model.parameters()), float(loss),
+        "  heads %d x %d  t_dim %d" % (model.num_heads, model.hidden_size // model.num_heads, model.t_dim) if opts else ""))
     say("  forward %8.2f ms   backward %8.2f ms   optimizer %7.2f ms   step %8.2f ms   (median of %d after one warm-up)"
         % (med["forward"], med["backward"], med["optimizer"], total, CALLS))
     say("  forward FLOPs %.3e;  3 x forward / step = %.1f TFLOP/s;  forward alone %.1f TFLOP/s;  peak memory %.2f GB"
