@@ -389,6 +389,14 @@ int ldt_occupancy_grid(const float* pts, int32_t S, int32_t n, const float* cell
  *   the kernels of ldt_attention_bwd instantiated at 32.  8 and 16 (attention_narrow_bwd.hip): one wave per 16 rows, MFMA first products with
  *   the channel extent zero-padded, second products as per-lane fp32 FMAs: P and dS stay fp32; row statistics and dQ in one launch, dK / dV in
  *   a second.  dQ, dK, dV rows must be 8-byte aligned (row and batch strides % 4 == 0).
+ * ldt_attention_bwd_cross: the contract of ldt_attention_bwd with two lengths, for the cross-attention of a conditioned Score's even blocks
+ *   (model/layers.py:183-200 with y = the point condition; model/scorenet/score.py:129-149): Nq query rows (1 .. 512) and Nk key / value rows
+ *   (1 .. 512, any relation to Nq) per sample, head_dim 8, 16, 32 or 64, scale head_dim^-0.5.  Q: B Nq rows; K, V: B Nk rows sharing
+ *   kv_batch_stride; O and dO the contiguous raw [B][H][Nq][head_dim] buffer (quirk Q1); stats fp32 [B][H][Nq][2]; dQ written as rows like Q,
+ *   dK and dV as rows like K and V.  The kernels of the two entry points above with separate row and loop extents: statistics and dQ per
+ *   block of 16 queries looping over the Nk keys, dK / dV per block of 16 keys looping over the Nq queries; every sum inside one wave in a
+ *   fixed order, no atomics, no sum across workgroups.  At Nq = Nk the same bits as ldt_attention_bwd / ldt_attention_bwd_narrow.  At
+ *   head_dim 8 and 16 the alignment rule of ldt_attention_bwd_narrow on dQ, dK, dV applies.
  * ldt_sumsq: out[0] = sum x^2 (two stages, float64 partials in scratch[scratch_len], at most LDT_ODE_SUMSQ_SCRATCH used), out[1] = its root
  *   (clip_grad_norm_'s total_norm over the flat gradient), out[2] = min(1, max_norm / (out[1] + 1e-6)) (clip_coef_clamped; 1 when max_norm <= 0).
  * ldt_adam_ema_step: torch.optim.Adam's update (torch/optim/adam.py _single_tensor_adam: L2 weight_decay added to the gradient, exp_avg.lerp_,
@@ -421,6 +429,10 @@ int ldt_attention_bwd_narrow(const uint16_t* Q, int64_t ldq, int64_t q_batch_str
                              int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats, uint16_t* dQ,
                              int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
                              int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t N, int32_t head_dim, void* stream);
+int ldt_attention_bwd_cross(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk, const uint16_t* V,
+                            int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats, uint16_t* dQ,
+                            int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
+                            int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim, void* stream);
 int ldt_sumsq(const float* x, int64_t n, double* scratch, int32_t scratch_len, float max_norm, float* out, void* stream);
 int ldt_adam_ema_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, double lr, double beta1,
                       double beta2, double eps, double weight_decay, int32_t step, double ema_decay, int32_t ema_init,

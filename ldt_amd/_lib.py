@@ -115,6 +115,8 @@ SIGNATURES = {
                           _i32, _i32, _i32, _i32, _vp],
     "ldt_attention_bwd_narrow": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64,
                                  _i32, _i32, _i32, _i32, _vp],
+    "ldt_attention_bwd_cross": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64,
+                                _i32, _i32, _i32, _i32, _i32, _vp],
     "ldt_sumsq": [_vp, _i64, _vp, _i32, C.c_float, _vp, _vp],
     "ldt_adam_ema_step": [_vp, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i32, C.c_double, _i32,
                           _vp, _vp],

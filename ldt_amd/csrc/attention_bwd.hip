@@ -1,5 +1,7 @@
-// Self-attention backward of a Score block (model/layers.py:190-197), head dim 64 or 32 (heads of 8 and 16: attention_narrow_bwd.hip),
-// Nq = Nk = N <= 512, gfx950.
+// Attention backward of a Score block (model/layers.py:190-197), head dim 64 or 32 (heads of 8 and 16: attention_narrow_bwd.hip),
+// Nq, Nk <= 512, gfx950.  Self-attention (ldt_attention_bwd, ldt_attention_bwd_narrow) runs it at Nq = Nk = N; cross-attention to the
+// point condition (ldt_attention_bwd_cross, attention_narrow_bwd.hip) with Nk keys from another tensor: the query-block kernels tile Nq
+// and loop to Nk, the key-block kernel tiles Nk and loops to Nq, and every clamp and guard takes the extent of the axis it indexes.
 //   forward:   S = Q K^T / sqrt(Dh),  P = softmax(S),  O = P V          (O is the [B][H][N][Dh] buffer the reference re-reads as (B N, C): quirk Q1;
 //                                                                       its gradient dO arrives in the same raw layout — nothing is permuted)
 //   backward:  dV = P^T dO,  dP = dO V^T,  dS = P o (dP - D),  D = rowsum(dO o O),  dQ = dS K / sqrt(Dh),  dK = dS^T Q / sqrt(Dh)
@@ -40,15 +42,15 @@ __global__ __launch_bounds__(64) void attn_bwd_stats_kernel(const AttnBwdArgs a)
     const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * AB_T;
     const bf16_t* Qb = a.Q + (long)b * a.q_bs + h * DH;
     const bf16_t* Kb = a.K + (long)b * a.kv_bs + h * DH;
-    const long ob = ((long)b * a.H + h) * a.N;
+    const long ob = ((long)b * a.H + h) * a.Nq;
     bf16x8 qf[NS];
 #pragma unroll
-    for (int s = 0; s < NS; ++s) qf[s] = ld_frag(Qb, a.ldq, q0 + lr, a.N, 4 * s + lq);
+    for (int s = 0; s < NS; ++s) qf[s] = ld_frag(Qb, a.ldq, q0 + lr, a.Nq, 4 * s + lq);
     // lane holds S[query 4 lq + i][key j0 + lr]
     float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    for (int j0 = 0; j0 < a.N; j0 += 16) {
-        const f32x4 sc = tile_qk(qf, Kb, a.ldk, j0 + lr, a.N, lq);
-        if (j0 + lr < a.N) {
+    for (int j0 = 0; j0 < a.Nk; j0 += 16) {
+        const f32x4 sc = tile_qk(qf, Kb, a.ldk, j0 + lr, a.Nk, lq);
+        if (j0 + lr < a.Nk) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) mx[i] = fmaxf(mx[i], sc[i] * a.scale);
         }
@@ -58,9 +60,9 @@ __global__ __launch_bounds__(64) void attn_bwd_stats_kernel(const AttnBwdArgs a)
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) mx[i] = fmaxf(mx[i], __shfl_xor(mx[i], o, 64));
     float sm[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j0 = 0; j0 < a.N; j0 += 16) {
-        const f32x4 sc = tile_qk(qf, Kb, a.ldk, j0 + lr, a.N, lq);
-        if (j0 + lr < a.N) {
+    for (int j0 = 0; j0 < a.Nk; j0 += 16) {
+        const f32x4 sc = tile_qk(qf, Kb, a.ldk, j0 + lr, a.Nk, lq);
+        if (j0 + lr < a.Nk) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) sm[i] += expf(sc[i] * a.scale - mx[i]);
         }
@@ -73,8 +75,8 @@ __global__ __launch_bounds__(64) void attn_bwd_stats_kernel(const AttnBwdArgs a)
     float d = 0.f;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        const bf16x8 o8 = ld_frag(a.O + ob * DH, DH, q0 + lr, a.N, 4 * s + lq);
-        const bf16x8 g8 = ld_frag(a.dO + ob * DH, DH, q0 + lr, a.N, 4 * s + lq);
+        const bf16x8 o8 = ld_frag(a.O + ob * DH, DH, q0 + lr, a.Nq, 4 * s + lq);
+        const bf16x8 g8 = ld_frag(a.dO + ob * DH, DH, q0 + lr, a.Nq, 4 * s + lq);
 #pragma unroll
         for (int j = 0; j < 8; ++j) d += (float)o8[j] * (float)g8[j];
     }
@@ -84,10 +86,10 @@ __global__ __launch_bounds__(64) void attn_bwd_stats_kernel(const AttnBwdArgs a)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int q = q0 + 4 * lq + i;
-            if (q < a.N) a.stats[(ob + q) * 2] = mx[i] + logf(sm[i]);
+            if (q < a.Nq) a.stats[(ob + q) * 2] = mx[i] + logf(sm[i]);
         }
     }
-    if (lq == 0 && q0 + lr < a.N) a.stats[(ob + q0 + lr) * 2 + 1] = d;
+    if (lq == 0 && q0 + lr < a.Nq) a.stats[(ob + q0 + lr) * 2 + 1] = d;
 }
 
 // ---- the two main kernels share one body.
@@ -100,8 +102,9 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
     __shared__ __attribute__((aligned(16))) bf16_t ds_t[AB_T][AB_LDP];
     __shared__ __attribute__((aligned(16))) bf16_t p_t[AB_T][AB_LDP];
     const int lane = threadIdx.x, lr = lane & 15, lq = lane >> 4;
-    const int b = blockIdx.z, h = blockIdx.y, r0 = blockIdx.x * AB_T, N = a.N;
-    const long ob = ((long)b * a.H + h) * N;
+    const int b = blockIdx.z, h = blockIdx.y, r0 = blockIdx.x * AB_T;
+    const int NR = KV ? a.Nk : a.Nq, NC = KV ? a.Nq : a.Nk;            // extents of the block's row axis and of the loop's column axis
+    const long ob = ((long)b * a.H + h) * a.Nq;
     const bf16_t* Qb = a.Q + (long)b * a.q_bs + h * DH;
     const bf16_t* Kb = a.K + (long)b * a.kv_bs + h * DH;
     const bf16_t* Vb = a.V + (long)b * a.kv_bs + h * DH;
@@ -115,14 +118,14 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
     bf16x8 fa[NS], fb[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        fa[s] = ld_frag(rowA, ld_rowA, r0 + lr, N, 4 * s + lq);
-        fb[s] = ld_frag(rowB, ld_rowB, r0 + lr, N, 4 * s + lq);
+        fa[s] = ld_frag(rowA, ld_rowA, r0 + lr, NR, 4 * s + lq);
+        fb[s] = ld_frag(rowB, ld_rowB, r0 + lr, NR, 4 * s + lq);
     }
     float Lr[4], Dr[4];                 // KV = false: the statistics of the block's query rows 4 lq + i
     if (!KV) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int q = min(r0 + 4 * lq + i, N - 1);
+            const int q = min(r0 + 4 * lq + i, NR - 1);
             Lr[i] = st[2 * q]; Dr[i] = st[2 * q + 1];
         }
     }
@@ -130,17 +133,17 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) { acc1[t] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc2[t] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
 
-    for (int j0 = 0; j0 < N; j0 += AB_J) {
+    for (int j0 = 0; j0 < NC; j0 += AB_J) {
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int col = j0 + 16 * half + lr;                       // this lane's column of the tile: a key (KV false) or a query (KV true)
-            const f32x4 sc = tile_qk(fa, colA, ld_colA, col, N, lq);
-            const f32x4 dp = tile_qk(fb, colB, ld_colB, col, N, lq);
+            const f32x4 sc = tile_qk(fa, colA, ld_colA, col, NC, lq);
+            const f32x4 dp = tile_qk(fb, colB, ld_colB, col, NC, lq);
             float Lc = 0.f, Dc = 0.f;
-            if (KV) { const int q = min(col, N - 1); Lc = st[2 * q]; Dc = st[2 * q + 1]; }
+            if (KV) { const int q = min(col, NC - 1); Lc = st[2 * q]; Dc = st[2 * q + 1]; }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const bool live = col < N && r0 + 4 * lq + i < N;
+                const bool live = col < NC && r0 + 4 * lq + i < NR;
                 const float p = live ? expf(sc[i] * a.scale - (KV ? Lc : Lr[i])) : 0.f;
                 const float dsv = p * (dp[i] - (KV ? Dc : Dr[i]));
                 ds_t[4 * lq + i][16 * half + lr] = (bf16_t)dsv;        // P and dS are rounded to bf16 here, before the second products
@@ -157,7 +160,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
             bf16x8 y1, y2;                                              // B: [loop row j0 + 8 lq + e][channel 16 t + lr]
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const int r = min(j0 + 8 * lq + e, N - 1);
+                const int r = min(j0 + 8 * lq + e, NC - 1);
                 y1[e] = colA[(long)r * ld_colA + 16 * t + lr];
                 if (KV) y2[e] = colB[(long)r * ld_colB + 16 * t + lr];
             }
@@ -172,7 +175,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int r = r0 + 4 * lq + i;
-            if (r < N) {
+            if (r < NR) {
                 o1[(long)r * ld1 + 16 * t + lr] = (bf16_t)(acc1[t][i] * a.scale);
                 if (KV) a.dV[(long)b * a.dkv_bs + h * DH + (long)r * a.lddv + 16 * t + lr] = (bf16_t)acc2[t][i];
             }
@@ -181,14 +184,15 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
 
 template <int DH>
 static int attn_bwd_launch_dh(const AttnBwdArgs& a, hipStream_t s) {
-    const dim3 grid((unsigned)((a.N + AB_T - 1) / AB_T), (unsigned)a.H, (unsigned)a.B), block(64);
+    const dim3 grid((unsigned)((a.Nq + AB_T - 1) / AB_T), (unsigned)a.H, (unsigned)a.B), block(64);      // query blocks
+    const dim3 grid_kv((unsigned)((a.Nk + AB_T - 1) / AB_T), (unsigned)a.H, (unsigned)a.B);               // key blocks
     hipLaunchKernelGGL(attn_bwd_stats_kernel<DH>, grid, block, 0, s, a);
     int rc = ldt_check_launch("attention_bwd (row statistics)");
     if (rc != LDT_OK) return rc;
     hipLaunchKernelGGL((attn_bwd_kernel<DH, false>), grid, block, 0, s, a);
     rc = ldt_check_launch("attention_bwd (dQ)");
     if (rc != LDT_OK) return rc;
-    hipLaunchKernelGGL((attn_bwd_kernel<DH, true>), grid, block, 0, s, a);
+    hipLaunchKernelGGL((attn_bwd_kernel<DH, true>), grid_kv, block, 0, s, a);
     return ldt_check_launch("attention_bwd (dK, dV)");
 }
 
@@ -216,6 +220,6 @@ extern "C" int ldt_attention_bwd(const uint16_t* Q, int64_t ldq, int64_t q_batch
     a.O = reinterpret_cast<const bf16_t*>(O); a.dO = reinterpret_cast<const bf16_t*>(dO); a.stats = stats;
     a.dQ = reinterpret_cast<bf16_t*>(dQ); a.lddq = lddq; a.dq_bs = dq_batch_stride;
     a.dK = reinterpret_cast<bf16_t*>(dK); a.lddk = lddk; a.dV = reinterpret_cast<bf16_t*>(dV); a.lddv = lddv; a.dkv_bs = dkv_batch_stride;
-    a.B = B; a.H = H; a.N = N; a.scale = 0.125f;
+    a.B = B; a.H = H; a.Nq = N; a.Nk = N; a.scale = 0.125f;
     return ldt_attn_bwd_launch(&a, 64, reinterpret_cast<hipStream_t>(stream));
 }

@@ -110,15 +110,16 @@ int ldt_attn_launch(const AttnArgs* a, int dh, hipStream_t s);
 int ldt_attn_route(int B, int H, int Nq, int Nk, int dh);       // 0 streaming, 1 resident, 2 whole-head (attention.hip), 3 narrow heads (attention_narrow.hip)
 int ldt_attn_narrow_launch(const AttnArgs* a, int dh, hipStream_t s);   // head dim 8 or 16; ldt_attn_launch has checked the operands
 int ldt_attn_oproj_launch(const AttnArgs* a, int dh, hipStream_t s);
-// attention backward (self-attention, Nq = Nk = N <= 512): the operands of ldt_attention_bwd / ldt_attention_bwd_narrow (include/ldt_hip.h)
+// attention backward (Nq, Nk <= 512): the operands of ldt_attention_bwd / ldt_attention_bwd_narrow (self-attention: Nq = Nk = N) and of
+// ldt_attention_bwd_cross (include/ldt_hip.h)
 struct AttnBwdArgs {
     const bf16_t* Q; long ldq; long q_bs;
     const bf16_t* K; long ldk; const bf16_t* V; long ldv; long kv_bs;
-    const bf16_t* O; const bf16_t* dO;        // [B][H][N][Dh]
-    float* stats;                             // [B][H][N][2] = (L, D)
+    const bf16_t* O; const bf16_t* dO;        // [B][H][Nq][Dh]
+    float* stats;                             // [B][H][Nq][2] = (L, D)
     bf16_t* dQ; long lddq; long dq_bs;
     bf16_t* dK; long lddk; bf16_t* dV; long lddv; long dkv_bs;
-    int B, H, N;
+    int B, H, Nq, Nk;                         // queries (rows of Q, O, dO, dQ, stats) and keys (rows of K, V, dK, dV) per sample
     float scale;                              // Dh^-0.5
 };
 int ldt_attn_bwd_launch(const AttnBwdArgs* a, int dh, hipStream_t s);          // attention_bwd.hip: head dim 64 or 32 (MFMA second products)

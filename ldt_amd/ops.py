@@ -962,6 +962,34 @@ def attention_bwd(q, k, v, o, do, B, H, N, head_dim=64, out=None):
     return dq, dk, dv
 
 
+def attention_bwd_cross(q, k, v, o, do, B, H, Nq, Nk, head_dim, dq_out=None, dkv_out=None):
+    """Cross-attention backward (ldt_attention_bwd_cross): q bf16 row view [B*Nq, >= H*head_dim], k and v bf16 row views [B*Nk, ...] of one
+    row stride, o and do the contiguous bf16 [B, H, Nq, head_dim] buffers (quirk Q1).  -> (dq, dk, dv): dq bf16 [B*Nq, H*head_dim] (`dq_out`
+    when given), dk | dv the two halves of one bf16 [B*Nk, 2*H*head_dim] tensor (`dkv_out` when given), the dY operand of fc_kv's backward
+    GEMMs.  head_dim 8, 16, 32 or 64; Nq != Nk allowed."""
+    if head_dim not in (8, 16, 32, 64):
+        raise ValueError("attention_bwd_cross: head_dim %r is not 8, 16, 32 or 64" % (head_dim,))
+    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
+        _need(t, torch.bfloat16, nm); _rowmajor(t, nm)
+    if not (o.is_contiguous() and do.is_contiguous()) or o.numel() != B * H * Nq * head_dim or do.numel() != o.numel():
+        raise ValueError("attention_bwd_cross: o and do must be contiguous [B, H, Nq, %d]" % head_dim)
+    if k.stride(0) != v.stride(0):
+        raise ValueError("attention_bwd_cross: K and V must share the row stride")
+    Cc = H * head_dim
+    if q.shape[0] != B * Nq or k.shape[0] != B * Nk or v.shape[0] != B * Nk or min(q.shape[1], k.shape[1], v.shape[1]) < Cc:
+        raise ValueError("attention_bwd_cross: q %s, k %s, v %s for B %d, Nq %d, Nk %d, %d channels"
+                         % (tuple(q.shape), tuple(k.shape), tuple(v.shape), B, Nq, Nk, Cc))
+    dq = _bf16_rows_out(dq_out, B * Nq, Cc, q.device, "attention_bwd_cross: dq_out")
+    dkv = _bf16_rows_out(dkv_out, B * Nk, 2 * Cc, q.device, "attention_bwd_cross: dkv_out")
+    dk, dv = dkv[:, :Cc], dkv[:, Cc:]
+    stats = torch.empty((B, H, Nq, 2), dtype=torch.float32, device=q.device)
+    ldq, ldkv = dq.stride(0), dkv.stride(0)
+    check(lib().ldt_attention_bwd_cross(_p(q), q.stride(0), q.stride(0) * Nq, _p(k), k.stride(0), _p(v), v.stride(0), k.stride(0) * Nk, _p(o),
+                                        _p(do), _p(stats), _p(dq), ldq, ldq * Nq, _p(dk), ldkv, _p(dv), ldkv, ldkv * Nk, B, H, Nq, Nk,
+                                        head_dim, stream_ptr()), "ldt_attention_bwd_cross")
+    return dq, dk, dv
+
+
 def sumsq(x, max_norm=0.0, scratch=None, out=None):
     """fp32 [3] on the device = (sum x^2, its root, min(1, max_norm / (root + 1e-6))) of a flat fp32 buffer: clip_grad_norm_'s total norm
     and factor without a host synchronisation.  Two stages, fixed order."""

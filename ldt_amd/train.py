@@ -2,14 +2,16 @@
 
 Reference: trainer/Latent_SDE_Trainer.py:94-141 (`update`, `update_score`), tools/utils.py:25-101 (EMA around Adam),
 model/scorenet/score.py:117-151 and model/layers.py:183-229 (what is differentiated).  Scope: the configuration the shipped YAMLs
-train — LayerNorm, AdaLN, self-attention with 8-, 16-, 32- or 64-wide heads (the hybrid config's Score: hidden 128, 16 heads),
-unconditional or label-conditioned.
+train — LayerNorm, AdaLN, attention with 8-, 16-, 32- or 64-wide heads (the hybrid config's Score: hidden 128, 16 heads),
+unconditional, label-conditioned, or conditioned on the embedded ViPC pair (pts_condition, img_condition): the even blocks then
+cross-attend to the condition tokens (completion_trainer/Latent_SDE_Trainer.py:99-145; `CompletionTrainer`), and the step hands the
+gradient with respect to that pair back.  ConditionNet itself is not differentiated.
 
 `AdamEMA` keeps fp32 master parameters, gradients, both Adam moments and the EMA in five flat device buffers (one fused
 `ldt_adam_ema_step` launch per step; bf16 operand panels are derived from the masters, never trained).  `ScoreTrainStep` runs the same
 kernels as inference, unfused, keeps per block what the backward needs, and then walks the blocks back: every GEMM of the backward is
 `ldt_gemm_bf16` on operands prepared by `ldt_transpose_cast_bf16`; everything else is csrc/score_bwd.hip, csrc/attention_bwd.hip and
-csrc/attention_narrow_bwd.hip.
+csrc/attention_narrow_bwd.hip (self-attention: ldt_attention_bwd / _narrow; cross-attention: ldt_attention_bwd_cross).
 """
 import torch
 
@@ -159,11 +161,17 @@ def clip_factor_host(optimizer):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-def refuse_untrainable(model, condition=None, world_size=1):
-    """The configurations the training step does not cover, each refused with its reason before anything is launched."""
-    if condition is not None or getattr(model, "condition", False):
+def refuse_untrainable(model, condition=None, world_size=1, *, allow_condition=False):
+    """The configurations the training step does not cover, each refused with its reason before anything is launched.
+    allow_condition: the caller trains on the embedded (pts_condition, img_condition) pair (`CompletionTrainer`); a raw condition dict —
+    ConditionNet's inputs — is refused there too."""
+    if not allow_condition and (condition is not None or getattr(model, "condition", False)):
         raise NotImplementedError("training with a ViPC / point condition (cross-attention blocks, ConditionNet) is not on this path: "
                                   "the backward covers self-attention blocks only")
+    if isinstance(condition, dict):
+        raise NotImplementedError("training on a raw ViPC / point condition dict {'img', 'pts'} is not on this path: ConditionNet's backward "
+                                  "is missing.  Run model.c_net(condition) and pass the (pts_condition, img_condition) pair it returns, "
+                                  "which freezes ConditionNet")
     if getattr(model, "unet", False):
         raise NotImplementedError("training the unet Score variant is not on this path (skip concatenations and conv shortcuts have no backward)")
     if not (isinstance(model.norm, str) and model.norm.lower() == "layer_norm"):
@@ -190,24 +198,54 @@ def _grad2d(p):
 
 class ScoreTrainStep:
     """One forward + backward of `Score` for the denoising loss.  `forward` returns params (B, T, z) and keeps the saved activations;
-    `backward(dparams)` fills every parameter's `.grad` view (the optimizer's flat gradient must be zeroed and attached first)."""
+    `backward(dparams)` fills every parameter's `.grad` view (the optimizer's flat gradient must be zeroed and attached first).
 
-    def __init__(self, model):
-        refuse_untrainable(model)
+    With `condition=(pts_condition (B, hidden, S), img_condition (B, t_dim) or 0.)` (needs allow_condition=True) the even blocks
+    cross-attend to the S condition tokens (score.py:149) and, without a label, c = TimeEmbedding(t) + img_condition (score.py:135).
+    `backward` then returns, and keeps as `self.dcondition`, (d_pts_condition (B, hidden, S) fp32, d_img_condition (B, t_dim) fp32 or
+    None when a label displaced the image condition or it was 0.): what ConditionNet's own backward would start from."""
+
+    MAX_TOKENS = 512                                                   # ldt_attention_bwd_cross: 1 <= Nq, Nk <= 512
+
+    def __init__(self, model, allow_condition=False):
+        refuse_untrainable(model, allow_condition=allow_condition)
         self.m = model
+        self.allow_condition = allow_condition
         self.saved = None
+        self.dcondition = None
 
     # ---------------------------------------------------------------- forward
     @torch.no_grad()
-    def forward(self, x, t, label=None):
+    def forward(self, x, t, label=None, condition=None):
         m = self.m
         if not x.is_cuda:
             raise RuntimeError("ScoreTrainStep.forward: x is on %s; the HIP path has no CPU fallback" % x.device)
         B, T, z = x.shape
         D, H, nb, n_mod = m.hidden_size, m.num_heads, m.num_blocks, m.n_mod
         M = B * T
+        pts_cond = img_cond = None
+        if condition is not None:                                      # every refusal before anything is launched or kept
+            self.saved = None
+            refuse_untrainable(m, condition, allow_condition=self.allow_condition)
+            if not isinstance(condition, (tuple, list)) or len(condition) != 2:
+                raise TypeError("ScoreTrainStep.forward: condition is the pair (pts_condition, img_condition), got %s" % type(condition).__name__)
+            pts_cond, img_cond = condition
+            if torch.is_tensor(pts_cond):
+                if pts_cond.dim() != 3 or pts_cond.shape[0] != B or pts_cond.shape[1] != D:
+                    raise ValueError("ScoreTrainStep.forward: pts_condition %s is not (B = %d, hidden = %d, S) channels-first"
+                                     % (tuple(pts_cond.shape), B, D))
+                Sn = pts_cond.shape[2]
+                if not (1 <= T <= self.MAX_TOKENS and 1 <= Sn <= self.MAX_TOKENS):
+                    raise NotImplementedError("training with %d query and %d condition tokens is not on this path: ldt_attention_bwd_cross takes "
+                                              "1 <= Nq, Nk <= %d" % (T, Sn, self.MAX_TOKENS))
+            else:
+                pts_cond = None
+            if not torch.is_tensor(img_cond) or label is not None:     # 0. (score.py:133), or displaced by the label (score.py:135)
+                img_cond = None
+            elif tuple(img_cond.shape) != (B, m.t_dim):
+                raise ValueError("ScoreTrainStep.forward: img_condition %s is not (B = %d, t_dim = %d)" % (tuple(img_cond.shape), B, m.t_dim))
         P = m.packed()
-        S = {"B": B, "T": T, "label": label}
+        S = {"B": B, "T": T, "label": label, "img": img_cond is not None, "S": 0}
         # conditioning rows (fp32): c = TimeEmbedding(t) [+ LabelEmbedding(label)], mod = adaLN(SiLU(c)) for every block
         te = m.TimeEmbedding.mlp
         S["e_t"] = ops.sinusoid(t.to(x).float().contiguous(), m._frequencies())
@@ -219,7 +257,13 @@ class ScoreTrainStep:
             S["e_l"] = le.label_emb.weight.detach()[S["lab"]].float().contiguous()                # row gather
             S["a_l"] = ops.sgemm(S["e_l"], le.mlp[0].weight, le.mlp[0].bias)
             c = ops.add_f32(c, ops.sgemm(S["a_l"], le.mlp[2].weight, le.mlp[2].bias, act_in=ACT_SILU))
+        if img_cond is not None:
+            c = ops.add_f32(c, img_cond.to(x.device, torch.float32).contiguous())
         S["c"] = c
+        cond = None
+        if pts_cond is not None:                                       # (B, hidden, S) channels-first -> token-major rows, bf16, once
+            S["S"] = Sn
+            cond = S["cond"] = ops.cast_pad_bf16(pts_cond.to(x.device, torch.float32).transpose(1, 2).contiguous().view(B * Sn, D), D)
         w_ada, b_ada = m.stacked_adaln()
         mod = S["mod"] = ops.sgemm(c, w_ada, b_ada, act_in=ACT_SILU)                               # [B, n_mod]
         mv = lambda off: mod[:, off:off + D]
@@ -234,9 +278,15 @@ class ScoreTrainStep:
             m0 = l * 6 * D
             sb = {"x1": X.clone()}
             sb["h"] = ops.layernorm_modulate(X, shift=mv(m0), scale=mv(m0 + D), **kw)
-            sb["qkv"] = ops.gemm_bf16(sb["h"], P["w_qkv"][l], P["b_qkv"][l], EPI_BF16)
-            q, k, v = sb["qkv"][:, :D], sb["qkv"][:, D:2 * D], sb["qkv"][:, 2 * D:]
-            sb["o"] = ops.attention_fwd(q, k, v, B, H, T, T, D // H)                              # [B, H, T, Dh] == (M, D) raw view (Q1)
+            if cond is not None and l % 2 == 0:                                                   # score.py:149; layers.py:184-189 with y
+                wq, bq, wkv, bkv = m._cross_panels(l)
+                sb["q"] = ops.gemm_bf16(sb["h"], wq, bq, EPI_BF16)
+                sb["kv"] = ops.gemm_bf16(cond, wkv, bkv, EPI_BF16)                                # [B S, 2 D] = K | V
+                sb["o"] = ops.attention_fwd(sb["q"], sb["kv"][:, :D], sb["kv"][:, D:], B, H, T, Sn, D // H)
+            else:
+                sb["qkv"] = ops.gemm_bf16(sb["h"], P["w_qkv"][l], P["b_qkv"][l], EPI_BF16)
+                q, k, v = sb["qkv"][:, :D], sb["qkv"][:, D:2 * D], sb["qkv"][:, 2 * D:]
+                sb["o"] = ops.attention_fwd(q, k, v, B, H, T, T, D // H)                          # [B, H, T, Dh] == (M, D) raw view (Q1)
             o2 = sb["o"].view(M, D)
             sb["a1"] = ops.gemm_bf16(o2, P["w_o"][l], P["b_o"][l], EPI_BF16)                      # the branch output, for dgate
             ops.gemm_bf16(o2, P["w_o"][l], P["b_o"][l], EPI_RESID_F32, out=X, resid=X, gate=mv(m0 + 2 * D), **gk)
@@ -262,7 +312,9 @@ class ScoreTrainStep:
         if S is None:
             raise RuntimeError("ScoreTrainStep.backward before forward")
         self.saved = None
-        B, T = S["B"], S["T"]
+        self.dcondition = None
+        B, T, Sn = S["B"], S["T"], S.get("S", 0)
+        d_cond = None                                                   # fp32 [B S, D]: the sum over the cross blocks, in the loop's order
         D, nb, n_mod, z = m.hidden_size, m.num_blocks, m.n_mod, m.z_dim
         M = B * T
         mod = S["mod"]
@@ -299,13 +351,21 @@ class ScoreTrainStep:
             # x2 = x1 + gate_msa * fc_o(attention(q, k, v))                                         (layers.py:218, 183-200)
             da1, _ = ops.gate_residual_bwd(dX, mv(m0 + 2 * D), sb["a1"], gate_sample_stride=n_mod, rows_per_sample=T, dgate=dv(m0 + 2 * D))
             do = linear_bwd(blk.fc_o, da1, sb["o"].view(M, D), epilogue=EPI_BF16)                 # [M, D] == dO [B, H, T, Dh] raw (Q1)
-            qkv = sb["qkv"]
-            dqkv = torch.empty((M, 3 * D), dtype=torch.bfloat16, device=do.device)                # [dq | dk | dv], the dY of fc_q | fc_kv
-            dq, _, _ = ops.attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], sb["o"], do, B, m.num_heads, T, head_dim=D // m.num_heads, out=dqkv)
-            linear_bwd(blk.fc_q, dq, sb["h"], want_dx=False)
-            linear_bwd(blk.fc_kv, dqkv[:, D:], sb["h"], want_dx=False)
-            wqkv_t = ops.transpose_cast_bf16(torch.cat([conv_w(blk.fc_q), conv_w(blk.fc_kv)], 0).detach())
-            dh = ops.dgrad(dqkv, wqkv_t, EPI_F32)
+            if "kv" in sb:                                                                        # cross-attention to the condition tokens
+                kv = sb["kv"]
+                dkv = torch.empty((B * Sn, 2 * D), dtype=torch.bfloat16, device=do.device)        # [dk | dv], the dY of fc_kv
+                dq, _, _ = ops.attention_bwd_cross(sb["q"], kv[:, :D], kv[:, D:], sb["o"], do, B, m.num_heads, T, Sn, D // m.num_heads, dkv_out=dkv)
+                dh = linear_bwd(blk.fc_q, dq, sb["h"])
+                d_c = linear_bwd(blk.fc_kv, dkv, S["cond"])                                       # [B S, D] fp32
+                d_cond = d_c if d_cond is None else ops.add_f32(d_cond, d_c)
+            else:
+                qkv = sb["qkv"]
+                dqkv = torch.empty((M, 3 * D), dtype=torch.bfloat16, device=do.device)            # [dq | dk | dv], the dY of fc_q | fc_kv
+                dq, _, _ = ops.attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], sb["o"], do, B, m.num_heads, T, head_dim=D // m.num_heads, out=dqkv)
+                linear_bwd(blk.fc_q, dq, sb["h"], want_dx=False)
+                linear_bwd(blk.fc_kv, dqkv[:, D:], sb["h"], want_dx=False)
+                wqkv_t = ops.transpose_cast_bf16(torch.cat([conv_w(blk.fc_q), conv_w(blk.fc_kv)], 0).detach())
+                dh = ops.dgrad(dqkv, wqkv_t, EPI_F32)
             ops.layernorm_modulate_bwd(sb["x1"], dh, dX, scale=mv(m0 + D), mod_sample_stride=n_mod, rows_per_sample=T,
                                        dshift=dv(m0), dscale=dv(m0 + D))
         linear_bwd(m.ln_in, dX, S["x_in"], want_dx=False)                                        # score.py:110
@@ -339,3 +399,7 @@ class ScoreTrainStep:
             d_a = mlp2_bwd(le.mlp, S["a_l"], S["e_l"])
             d_e = ops.sgemm(d_a, _t(le.mlp[0].weight.detach()))
             le.label_emb.weight.grad.copy_(ops.embedding_grad(d_e, S["lab"], le.label_emb.weight.shape[0]))
+        if Sn or S.get("img"):                                                                       # the gradient of the condition pair
+            d_pts = None if d_cond is None else d_cond.view(B, Sn, D).transpose(1, 2).contiguous()   # (B, hidden, S), as ConditionNet returns it
+            self.dcondition = (d_pts, dc if S.get("img") else None)
+        return self.dcondition

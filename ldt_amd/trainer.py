@@ -313,10 +313,16 @@ class Trainer:
         backward pass, `clip_grad_norm_(cfg.opt.grad_norm_clip_value)` and `EMA(Adam).step()` in one fused update.  Returns the 0-dim
         device loss; nothing is synchronised.  Keyword extensions as `val_loss`: `t_index` (B,) replaces the numpy draw of the discrete
         times, `eta` (B, tokens, z) the noise, `seed` the Philox key of the device noise.  The pieces stay available as `self.last_update`."""
+        from .train import refuse_untrainable
+        refuse_untrainable(self.model, condition, ldist.world()[1])
+        return self._score_step(eps, None, cates, discrete, t_index, eta, seed)
+
+    def _score_step(self, eps, condition, cates, discrete, t_index, eta, seed):
+        """The body of `update_score` after the refusals.  condition: None, or the embedded (pts_condition, img_condition) pair
+        (`CompletionTrainer`): the step then keeps the gradient with respect to that pair as `self.last_condition_grad`."""
         import numpy as np
         from . import ops
-        from .train import ScoreTrainStep, refuse_untrainable
-        refuse_untrainable(self.model, condition, ldist.world()[1])
+        from .train import ScoreTrainStep
         if not torch.is_tensor(eps) or not eps.is_cuda:
             raise RuntimeError("Trainer.update_score: eps is on %s; the HIP path has no CPU fallback"
                                % (eps.device if torch.is_tensor(eps) else type(eps).__name__,))
@@ -345,11 +351,17 @@ class Trainer:
         t_dev = t.reshape(-1).float().to(dev)
         xt, eta = ops.diffuse_q(eps, e2int_f.reshape(-1).float().to(dev), var.reshape(-1).float().to(dev),
                                 None if eta is None else eta.to(dev, torch.float32), seed=seed or 0)
-        step = ScoreTrainStep(self.model)
-        params = step.forward(xt, t_dev, label=cates)
+        if condition is None:
+            step = ScoreTrainStep(self.model)
+            params = step.forward(xt, t_dev, label=cates)
+        else:
+            step = ScoreTrainStep(self.model, allow_condition=True)
+            params = step.forward(xt, t_dev, label=cates, condition=condition)
         l1 = self.cfg.opt.loss_type == "l1"
         loss, per_sample = ops.dsm_loss(eta, params, weight_p, l1=l1)
-        step.backward(ops.dsm_loss_bwd(eta, params, weight_p, l1=l1))
+        dcondition = step.backward(ops.dsm_loss_bwd(eta, params, weight_p, l1=l1))
+        if condition is not None:
+            self.last_condition_grad = dcondition
         self.optimizer.step(max_norm=getattr(self.cfg.opt, "grad_norm_clip_value", None))
         self.model.invalidate_packed()                   # the update wrote the weights through raw pointers: no version counter moved
         self.last_update = {"t": t_dev, "eta": eta, "xt": xt, "params": params, "sample_loss": per_sample, "weight_p": weight_p,
@@ -408,14 +420,61 @@ class Trainer:
 
 
 class CompletionTrainer(Trainer):
-    """The sampling half of completion_trainer/Latent_SDE_Trainer.py (ShapeNet-ViPC completion, BASELINE configs[4]):
+    """completion_trainer/Latent_SDE_Trainer.py (ShapeNet-ViPC completion, BASELINE configs[4]):
     `sample(num_samples, condition={'img': views, 'pts': partial})` runs the score model's ConditionNet once per call
     (:150-151; needs cfg.score.condition = True), samples image/partial-cloud conditioned latents and returns the decoded
-    clouds only (:168); `valsample` is the evaluation loop of :170-215 without the dataset and the renderer."""
+    clouds only (:168); `valsample` is the evaluation loop of :170-215 without the dataset and the renderer.
+
+    Training (:99-145): `update(data, condition)` / `update_score(eps, condition, ...)` take the EMBEDDED pair
+    `(pts_condition (B, hidden, S), img_condition (B, t_dim) or 0.)` — what `model.c_net(...)` returns — and train the Score on it: the
+    even blocks cross-attend to the condition tokens (ldt_attention_bwd_cross).  ConditionNet's own backward is not on this path: the
+    gradient with respect to the pair is kept as `self.last_condition_grad = (d_pts_condition (B, hidden, S), d_img_condition (B, t_dim) or
+    None)`, where that backward would start, and the `c_net` parameters of a `cfg.score.condition=True` model receive a zero gradient."""
+
+    last_condition_grad = None
+
+    def _refuse_condition(self, condition, who):
+        """Everything this trainer's step does not take, each with its reason, before anything is launched or allocated."""
+        from .train import refuse_untrainable
+        if condition is None:
+            raise NotImplementedError("CompletionTrainer.%s: this trainer's step trains on a ViPC / point condition and takes the embedded "
+                                      "(pts_condition, img_condition) pair as `condition`; an unconditional step is Trainer.%s" % (who, who))
+        refuse_untrainable(self.model, condition, ldist.world()[1], allow_condition=True)
+        if not isinstance(condition, (tuple, list)) or len(condition) != 2:
+            raise TypeError("CompletionTrainer.%s: condition is the pair (pts_condition, img_condition), got %s" % (who, type(condition).__name__))
+        wd = max(float(g.get("weight_decay", 0.) or 0.) for g in self.optimizer.param_groups)
+        if hasattr(self.model, "c_net") and wd != 0:
+            raise NotImplementedError("CompletionTrainer.%s: weight_decay=%g with a ConditionNet in the model (cfg.score.condition=True) is not on "
+                                      "this path: ConditionNet's backward is missing, its parameters receive a zero gradient, and a frozen "
+                                      "net would silently decay" % (who, wd))
 
     def update(self, data, condition=None):
-        raise NotImplementedError("CompletionTrainer.update: training with a ViPC / point condition (cross-attention blocks, ConditionNet) "
-                                  "is not on this path: the backward covers self-attention blocks only")
+        """The reference's `update` (:99-111): the EMA swap around the step from the second iteration on, the frozen Compressor's `all_eps`
+        of `data` (a tensor as upstream; a dict with `tr_points` is accepted too), `update_score` with cfg.opt.discrete, `itr += 1`.
+        Returns the 0-dim device loss."""
+        self._refuse_condition(condition, "update")
+        if not torch.device(self.device).type == "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("CompletionTrainer.update: device %s; the HIP path has no CPU fallback" % (self.device,))
+        point = data["tr_points"] if isinstance(data, dict) else data
+        if self.itr > 0:
+            self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
+        try:
+            with torch.no_grad():
+                self.compressor.eval()
+                eps = self.compressor(point.to(self.device))["all_eps"]
+            loss = self.update_score(eps, cates=None, discrete=getattr(self.cfg.opt, "discrete", True), condition=condition)
+        finally:
+            if self.itr > 0:
+                self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
+        self.itr += 1
+        return loss
+
+    def update_score(self, eps, condition=None, cates=None, discrete=True, *, t_index=None, eta=None, seed=None):
+        """The reference's `update_score` (:113-145) with a condition pair: `Trainer.update_score`'s step (warm-up, times, `xt`, the loss,
+        clip, EMA(Adam).step(); the keyword extensions mean the same) with the Score run as `model(xt, t, condition=condition,
+        label=cates)`: with both a label and a condition the image condition is dropped (score.py:135)."""
+        self._refuse_condition(condition, "update_score")
+        return self._score_step(eps, tuple(condition), cates, discrete, t_index, eta, seed)
 
     @torch.no_grad()
     def sample(self, num_samples, num_points=None, label=None, condition=None, **kw):
