@@ -357,7 +357,7 @@ int ldt_nelbo_terms(const float* eta, const float* params, const float* logqz, c
 int ldt_occupancy_grid(const float* pts, int32_t S, int32_t n, const float* cells, int32_t G, uint32_t* counters, uint32_t* bernoulli,
                        void* stream);
 
-/* ---- Score training: the backward pieces and the optimizer (score_bwd.hip, attention_bwd.hip, attention_narrow_bwd.hip, optim.hip) ----
+/* ---- Score training: the backward pieces and the optimizer (score_bwd.hip, attention_bwd.hip, optim.hip) ----
  * What trainer/Latent_SDE_Trainer.py:137-140 (`loss.backward()`, clip_grad_norm_, EMA(Adam).step()) needs under the forward kernels above,
  * for the AdaLN LayerNorm Score blocks the shipped YAMLs train.  The backward GEMMs are NOT here: dgrad dX = dY . W and wgrad dW = dY^T . X
  * are ldt_gemm_bf16 (LDT_EPI_F32 / LDT_EPI_BF16) on operands ldt_transpose_cast_bf16 prepares.  Like the evaluation kernels: status codes
@@ -386,7 +386,7 @@ int ldt_occupancy_grid(const float* pts, int32_t S, int32_t n, const float* cell
  *   sum are recomputed (the forward writes no log-sum-exp) into stats fp32 [B][H][N][2] = (max + ln sum, rowsum(dO o O)).  bf16 MFMA, fp32
  *   accumulation; P and dS are rounded to bf16 before the second products.  dQ per query block, dK / dV per key block: no sum across workgroups.
  * ldt_attention_bwd_narrow: the same contract for head_dim 8, 16 or 32 (scale head_dim^-0.5; ldt_attention_bwd keeps taking 64 alone).  32 runs
- *   the kernels of ldt_attention_bwd instantiated at 32.  8 and 16 (attention_narrow_bwd.hip): one wave per 16 rows, MFMA first products with
+ *   the kernels of ldt_attention_bwd instantiated at 32.  8 and 16 (the narrow form of attention_bwd.hip): one wave per 16 rows, MFMA first products with
  *   the channel extent zero-padded, second products as per-lane fp32 FMAs: P and dS stay fp32; row statistics and dQ in one launch, dK / dV in
  *   a second.  dQ, dK, dV rows must be 8-byte aligned (row and batch strides % 4 == 0).
  * ldt_attention_bwd_cross: the contract of ldt_attention_bwd with two lengths, for the cross-attention of a conditioned Score's even blocks

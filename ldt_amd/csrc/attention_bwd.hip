@@ -1,58 +1,108 @@
-// Attention backward of a Score block (model/layers.py:190-197), head dim 64 or 32 (heads of 8 and 16: attention_narrow_bwd.hip),
-// Nq, Nk <= 512, gfx950.  Self-attention (ldt_attention_bwd, ldt_attention_bwd_narrow) runs it at Nq = Nk = N; cross-attention to the
-// point condition (ldt_attention_bwd_cross, attention_narrow_bwd.hip) with Nk keys from another tensor: the query-block kernels tile Nq
-// and loop to Nk, the key-block kernel tiles Nk and loops to Nq, and every clamp and guard takes the extent of the axis it indexes.
+// Attention backward of a Score block (model/layers.py:183-200), head dim 8, 16, 32 or 64, Nq, Nk <= 512, gfx950: the whole of it — both
+// kernel forms, their launchers and the three entry points.  Self-attention (ldt_attention_bwd at 64, ldt_attention_bwd_narrow at 8, 16 and
+// 32) runs it at Nq = Nk = N; cross-attention to the point condition (ldt_attention_bwd_cross, every width; model/scorenet/score.py:129-149:
+// the even blocks of a conditioned Score) with Nk keys from another tensor: query blocks tile Nq and loop to Nk, key blocks tile Nk and loop
+// to Nq, and every clamp and guard takes the extent of the axis it indexes.
 //   forward:   S = Q K^T / sqrt(Dh),  P = softmax(S),  O = P V          (O is the [B][H][N][Dh] buffer the reference re-reads as (B N, C): quirk Q1;
 //                                                                       its gradient dO arrives in the same raw layout — nothing is permuted)
 //   backward:  dV = P^T dO,  dP = dO V^T,  dS = P o (dP - D),  D = rowsum(dO o O),  dQ = dS K / sqrt(Dh),  dK = dS^T Q / sqrt(Dh)
-// The forward kernels write no log-sum-exp, so a first kernel recomputes each query row's maximum and sum (kept as L = max + ln(sum), so that
-// P = exp(S - L)) together with D.  Then dQ is produced per block of 16 query rows looping over the keys, and dK / dV per block of 16 keys
-// looping over the queries: every output element is summed inside one wave in a fixed order — no atomics, no sum across workgroups, the same
-// bits on every run.
-// Products: v_mfma_f32_16x16x32_bf16 with fp32 accumulation.  S and dP (and their transposes in the key-block kernel) take their operand
-// fragments straight from global rows (lane l: row l & 15, 8 contiguous head channels at 8 (l >> 4)); P and dS are rounded to bf16 and cross
-// one LDS tile to become the A operand of the second products.  One wave per workgroup: this is the correct, unfused form of the step.
-// The three kernels are templates on the head dim DH: DH / 32 operand chunks of the first products, DH / 16 accumulator tiles of the second.
-// ldt_attention_bwd runs the 64 instantiation; the 32 one is reached from ldt_attention_bwd_narrow (attention_narrow_bwd.hip).
+// The forward kernels write no log-sum-exp, so each query row's maximum and sum are recomputed (kept as L = max + ln(sum), so that
+// P = exp(S - L)) together with D, and go to `stats`.  Then dQ is produced per block of 16 query rows looping over the keys, and dK / dV per
+// block of 16 keys looping over the queries: every output element is summed inside one wave in a fixed order — no atomics, no sum across
+// workgroups, the same bits on every run.  Rows and columns past the end re-read the last row (never out of bounds) and get weight exactly 0.
+//
+// Both forms take the same steps up to dS, each written once below: the role table, the clamped fragment load, the first product of one
+// 16-column tile (S and dP, or their transposes in a key block: one v_mfma_f32_16x16x32_bf16 per 32 channels, fp32 accumulation, operand
+// fragments straight from global rows — lane l: row l & 15, 8 contiguous head channels at 8 (l >> 4), a zero fragment past Dh below 32), the
+// row-statistics sweep, D, and the P / dS element step.  They differ in the second products, which stay two bodies because they are two
+// algorithms:
+//   MFMA form (32, 64)   one wave per workgroup, three launches (statistics; dQ; dK and dV).  P and dS are rounded to bf16 and cross one LDS
+//                        tile to become the A operand of DH / 16 MFMAs per 32 columns.
+//   narrow form (8, 16)  as the forward's (attention_narrow.hip): one wave per (sample, head, block of 16 rows), four such waves per
+//                        workgroup, nothing shared between them: no LDS, no barrier; two launches (statistics with dQ; dK and dV).  The
+//                        lane holds P and dS of ONE column for four rows, and that column's K (Q, dO) slice is one or two 16-byte loads
+//                        in its natural layout: 4 x Dh fused multiply-adds per product into per-lane partial sums, so P and dS STAY fp32
+//                        (they never become MFMA operands: the 2^-8 terms of the 32 / 64-wide bound are absent).  narrow_halve x 4 then
+//                        sums the partials over the 16 lanes of an lq in a fixed order and leaves each lane Dh / 4 adjacent channels of one
+//                        row: times the scale (dQ, dK), one 4- or 8-byte store.
+// Also left in its two places: where a query block's own L and D come from (the MFMA form reads them from `stats`, the narrow form has just
+// computed them in registers) — one line each, and sharing it would need a switch that says which form is calling.
 #include "../../include/ldt_hip.h"
 #include "kernels.h"
 
-#define AB_T 16                      // rows (dQ kernel: queries, dK/dV kernel: keys) per workgroup
-#define AB_J 32                      // columns per loop iteration: the K extent of one 16x16x32 product
-#define AB_LDP (AB_J + 8)            // LDS row pitch of the P / dS tiles, bf16 elements (80 B: 16-B aligned rows, staggered banks)
+#define AB_T 16                      // rows (query blocks: queries, key blocks: keys) per wave
+#define AB_J 32                      // MFMA form: columns per loop iteration, the K extent of one 16x16x32 product
+#define AB_LDP (AB_J + 8)            // MFMA form: LDS row pitch of the P / dS tiles, bf16 elements (80 B: 16-B aligned rows, staggered banks)
 
-__device__ __forceinline__ bf16x8 ld_frag(const bf16_t* base, long ld, int row, int nrows, int chunk) {
-    const int r = row < nrows ? row : nrows - 1;          // rows past the end repeat the last one: finite values that a zero weight removes
-    return *reinterpret_cast<const bf16x8*>(base + (long)r * ld + chunk * 8);
+// the operands of the three entry points (include/ldt_hip.h); self-attention: Nq = Nk = N
+struct AttnBwdArgs {
+    const bf16_t* Q; long ldq; long q_bs;
+    const bf16_t* K; long ldk; const bf16_t* V; long ldv; long kv_bs;
+    const bf16_t* O; const bf16_t* dO;        // [B][H][Nq][Dh]
+    float* stats;                             // [B][H][Nq][2] = (L, D)
+    bf16_t* dQ; long lddq; long dq_bs;
+    bf16_t* dK; long lddk; bf16_t* dV; long lddv; long dkv_bs;
+    int B, H, Nq, Nk;                         // queries (rows of Q, O, dO, dQ, stats) and keys (rows of K, V, dK, dV) per sample
+    float scale;                              // Dh^-0.5
+};
+
+// ---- the steps both forms take
+constexpr int ab_steps(int dh) { return dh >= 32 ? dh / 32 : 1; }       // MFMAs (32 channels each) of one first product
+
+// One (sample, head) in the roles of a block.
+// KV = false: the block's 16 rows are queries, the loop runs over keys:    S = Q K^T,   dP = dO V^T,   dQ  = scale dS K
+// KV = true:  the block's 16 rows are keys,    the loop runs over queries: S^T = K Q^T, dP^T = V dO^T, dK = scale dS^T Q,  dV = P^T dO
+// In both the accumulator tile of a first product puts the block's rows at 4 (l >> 4) + i and the loop's column at l & 15.
+struct AttnBwdRoles {
+    const bf16_t *rowA, *rowB, *colA, *colB;                            // the block's rows (A operands of the first products), the loop's columns
+    long ld_rowA, ld_rowB, ld_colA, ld_colB;
+    int NR, NC;                                                         // extents of the block's row axis and of the loop's column axis
+    long ob;                                                            // first row of this head in O, dO and stats
+    float* st;                                                          // (L, D) of this head's query rows
+};
+template <int DH, bool KV>
+__device__ __forceinline__ AttnBwdRoles attn_bwd_roles(const AttnBwdArgs& a, int b, int h) {
+    const long ob = ((long)b * a.H + h) * a.Nq;
+    const bf16_t* Qb = a.Q + (long)b * a.q_bs + h * DH;
+    const bf16_t* Kb = a.K + (long)b * a.kv_bs + h * DH;
+    const bf16_t* Vb = a.V + (long)b * a.kv_bs + h * DH;
+    const bf16_t* Gb = a.dO + ob * DH;
+    return {KV ? Kb : Qb, KV ? Vb : Gb, KV ? Qb : Kb, KV ? Gb : Vb, KV ? a.ldk : a.ldq, KV ? a.ldv : (long)DH, KV ? a.ldq : a.ldk,
+            KV ? (long)DH : a.ldv, KV ? a.Nk : a.Nq, KV ? a.Nq : a.Nk, ob, a.stats + ob * 2};
 }
 
-template <int NS>
-__device__ __forceinline__ f32x4 tile_qk(const bf16x8 (&a)[NS], const bf16_t* base, long ld, int row, int nrows, int lq) {
+// This lane's fragment of step s of a row's first product: channels 32 s + 8 lq .. + 7, a zero fragment past Dh (Dh 8, 16).  Rows past the
+// end repeat the last one: finite values that a zero weight removes.
+template <int DH>
+__device__ __forceinline__ bf16x8 ld_frag(const bf16_t* base, long ld, int row, int nrows, int s, int lq) {
+    const bf16_t* p = base + (long)(row < nrows ? row : nrows - 1) * ld;
+    if constexpr (DH >= 32) {
+        return *reinterpret_cast<const bf16x8*>(p + (4 * s + lq) * 8);
+    } else {
+        const bf16x8 t = *reinterpret_cast<const bf16x8*>(p + 8 * (lq & (DH / 8 - 1))), zero = {0, 0, 0, 0, 0, 0, 0, 0};
+        return lq < DH / 8 ? t : zero;
+    }
+}
+
+// First product of one 16-column tile: [the 16 rows whose fragments are `a`] x [row `row` of base]^T -> element [4 lq + i][this lane's column]
+template <int DH>
+__device__ __forceinline__ f32x4 tile_qk(const bf16x8 (&a)[ab_steps(DH)], const bf16_t* base, long ld, int row, int nrows, int lq) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int s = 0; s < NS; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s], ld_frag(base, ld, row, nrows, 4 * s + lq), acc, 0, 0, 0);
+    for (int s = 0; s < ab_steps(DH); ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s], ld_frag<DH>(base, ld, row, nrows, s, lq), acc, 0, 0, 0);
     return acc;
 }
 
-// ---- per query row: L = max_j s_j + ln sum_j exp(s_j - max), s = scale * q . k_j;  D = sum_d dO o O
+// L = max_j s_j + ln sum_j exp(s_j - max), s = scale * q . k_j, of the query rows 4 lq + i whose fragments are `qf`: two sweeps over the keys
+// (the maximum, then the sum), each reduced over the 16 lanes of an lq.  Every lane of an lq ends with the same four values.
 template <int DH>
-__global__ __launch_bounds__(64) void attn_bwd_stats_kernel(const AttnBwdArgs a) {
-    constexpr int NS = DH / 32;                                         // 32-channel steps of the first products
-    const int lane = threadIdx.x, lr = lane & 15, lq = lane >> 4;
-    const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * AB_T;
-    const bf16_t* Qb = a.Q + (long)b * a.q_bs + h * DH;
-    const bf16_t* Kb = a.K + (long)b * a.kv_bs + h * DH;
-    const long ob = ((long)b * a.H + h) * a.Nq;
-    bf16x8 qf[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) qf[s] = ld_frag(Qb, a.ldq, q0 + lr, a.Nq, 4 * s + lq);
-    // lane holds S[query 4 lq + i][key j0 + lr]
+__device__ __forceinline__ void row_lse(const bf16x8 (&qf)[ab_steps(DH)], const bf16_t* Kb, long ldk, int Nk, float scale, int lr, int lq, float (&L)[4]) {
     float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    for (int j0 = 0; j0 < a.Nk; j0 += 16) {
-        const f32x4 sc = tile_qk(qf, Kb, a.ldk, j0 + lr, a.Nk, lq);
-        if (j0 + lr < a.Nk) {
+    for (int j0 = 0; j0 < Nk; j0 += 16) {
+        const f32x4 sc = tile_qk<DH>(qf, Kb, ldk, j0 + lr, Nk, lq);
+        if (j0 + lr < Nk) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) mx[i] = fmaxf(mx[i], sc[i] * a.scale);
+            for (int i = 0; i < 4; ++i) mx[i] = fmaxf(mx[i], sc[i] * scale);
         }
     }
 #pragma unroll
@@ -60,94 +110,114 @@ __global__ __launch_bounds__(64) void attn_bwd_stats_kernel(const AttnBwdArgs a)
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) mx[i] = fmaxf(mx[i], __shfl_xor(mx[i], o, 64));
     float sm[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j0 = 0; j0 < a.Nk; j0 += 16) {
-        const f32x4 sc = tile_qk(qf, Kb, a.ldk, j0 + lr, a.Nk, lq);
-        if (j0 + lr < a.Nk) {
+    for (int j0 = 0; j0 < Nk; j0 += 16) {
+        const f32x4 sc = tile_qk<DH>(qf, Kb, ldk, j0 + lr, Nk, lq);
+        if (j0 + lr < Nk) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) sm[i] += expf(sc[i] * a.scale - mx[i]);
+            for (int i = 0; i < 4; ++i) sm[i] += expf(sc[i] * scale - mx[i]);
         }
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 4; ++i) {
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) sm[i] += __shfl_xor(sm[i], o, 64);
-    // D: lane (lr, lq) sums channels 8 lq .. + 7 (and 32 + 8 lq .. + 7 at DH 64) of row q0 + lr, then the four lq
+        L[i] = mx[i] + logf(sm[i]);
+    }
+}
+
+// D = sum_d dO o O of query row `row`, whose dO fragments are `g`: lane (lr, lq) sums its channels (8 lq .. + 7 of every 32; a zero fragment
+// past Dh), then the four lq: the same bits in all four.
+template <int DH>
+__device__ __forceinline__ float row_d(const bf16_t* O, int row, int nrows, const bf16x8 (&g)[ab_steps(DH)], int lq) {
     float d = 0.f;
 #pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const bf16x8 o8 = ld_frag(a.O + ob * DH, DH, q0 + lr, a.Nq, 4 * s + lq);
-        const bf16x8 g8 = ld_frag(a.dO + ob * DH, DH, q0 + lr, a.Nq, 4 * s + lq);
+    for (int s = 0; s < ab_steps(DH); ++s) {
+        const bf16x8 o8 = ld_frag<DH>(O, DH, row, nrows, s, lq);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) d += (float)o8[j] * (float)g8[j];
+        for (int j = 0; j < 8; ++j) d += (float)o8[j] * (float)g[s][j];
     }
     d += __shfl_xor(d, 16, 64);
-    d += __shfl_xor(d, 32, 64);
+    return d + __shfl_xor(d, 32, 64);
+}
+
+// P = exp(S scale - L) and dS = P (dP - D) of this lane's four elements [row row0 + i][column col], fp32; exactly 0 past either end.  L and D
+// belong to the query: the row's (query blocks: Lr, Dr) or the column's (key blocks: read from st).
+template <bool KV>
+__device__ __forceinline__ void p_ds(const f32x4& sc, const f32x4& dp, float scale, const AttnBwdRoles& r, int row0, int col, const float (&Lr)[4],
+                                     const float (&Dr)[4], float (&p)[4], float (&ds)[4]) {
+    float Lc = 0.f, Dc = 0.f;
+    if (KV) { const int q = min(col, r.NC - 1); Lc = r.st[2 * q]; Dc = r.st[2 * q + 1]; }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const bool live = col < r.NC && row0 + i < r.NR;
+        p[i] = live ? expf(sc[i] * scale - (KV ? Lc : Lr[i])) : 0.f;
+        ds[i] = p[i] * (dp[i] - (KV ? Dc : Dr[i]));
+    }
+}
+
+// ---- MFMA form, head dim 32 or 64.  Per query row: L and D to `stats`
+template <int DH>
+__global__ __launch_bounds__(64) void attn_bwd_stats_kernel(const AttnBwdArgs a) {
+    constexpr int NS = ab_steps(DH);
+    const int lane = threadIdx.x, lr = lane & 15, lq = lane >> 4, q0 = blockIdx.x * AB_T;
+    const AttnBwdRoles r = attn_bwd_roles<DH, false>(a, blockIdx.z, blockIdx.y);
+    bf16x8 qf[NS], gf[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) qf[s] = ld_frag<DH>(r.rowA, r.ld_rowA, q0 + lr, r.NR, s, lq);
+    float L[4];                                                         // of query rows q0 + 4 lq + i
+    row_lse<DH>(qf, r.colA, r.ld_colA, r.NC, a.scale, lr, lq, L);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) gf[s] = ld_frag<DH>(r.rowB, r.ld_rowB, q0 + lr, r.NR, s, lq);
+    const float d = row_d<DH>(a.O + r.ob * DH, q0 + lr, r.NR, gf, lq);  // of query row q0 + lr
     if (lr == 0) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int q = q0 + 4 * lq + i;
-            if (q < a.Nq) a.stats[(ob + q) * 2] = mx[i] + logf(sm[i]);
+            if (q < r.NR) r.st[2 * q] = L[i];
         }
     }
-    if (lq == 0 && q0 + lr < a.Nq) a.stats[(ob + q0 + lr) * 2 + 1] = d;
+    if (lq == 0 && q0 + lr < r.NR) r.st[2 * (q0 + lr) + 1] = d;
 }
 
-// ---- the two main kernels share one body.
-// KV = false: the block's 16 rows are queries, the loop runs over keys:    S = Q K^T,   dP = dO V^T,   dQ  = scale dS K
-// KV = true:  the block's 16 rows are keys,    the loop runs over queries: S^T = K Q^T, dP^T = V dO^T, dK = scale dS^T Q,  dV = P^T dO
-// In both the accumulator tile puts the block's rows at 4 (l >> 4) + i and the loop's column at l & 15.
+// the two main kernels of the MFMA form share one body
 template <int DH, bool KV>
 __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
-    constexpr int NS = DH / 32, NT = DH / 16;                           // operand chunks of 32 channels, accumulator tiles of 16
+    constexpr int NS = ab_steps(DH), NT = DH / 16;                      // operand chunks of 32 channels, accumulator tiles of 16
     __shared__ __attribute__((aligned(16))) bf16_t ds_t[AB_T][AB_LDP];
     __shared__ __attribute__((aligned(16))) bf16_t p_t[AB_T][AB_LDP];
     const int lane = threadIdx.x, lr = lane & 15, lq = lane >> 4;
     const int b = blockIdx.z, h = blockIdx.y, r0 = blockIdx.x * AB_T;
-    const int NR = KV ? a.Nk : a.Nq, NC = KV ? a.Nq : a.Nk;            // extents of the block's row axis and of the loop's column axis
-    const long ob = ((long)b * a.H + h) * a.Nq;
-    const bf16_t* Qb = a.Q + (long)b * a.q_bs + h * DH;
-    const bf16_t* Kb = a.K + (long)b * a.kv_bs + h * DH;
-    const bf16_t* Vb = a.V + (long)b * a.kv_bs + h * DH;
-    const bf16_t* Gb = a.dO + ob * DH;
-    const float* st = a.stats + ob * 2;
-    // rows of the block (A operands of the first products) and the loop's operands
-    const bf16_t* rowA = KV ? Kb : Qb; const long ld_rowA = KV ? a.ldk : a.ldq;
-    const bf16_t* rowB = KV ? Vb : Gb; const long ld_rowB = KV ? a.ldv : DH;
-    const bf16_t* colA = KV ? Qb : Kb; const long ld_colA = KV ? a.ldq : a.ldk;
-    const bf16_t* colB = KV ? Gb : Vb; const long ld_colB = KV ? DH : a.ldv;
+    const AttnBwdRoles r = attn_bwd_roles<DH, KV>(a, b, h);
     bf16x8 fa[NS], fb[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        fa[s] = ld_frag(rowA, ld_rowA, r0 + lr, NR, 4 * s + lq);
-        fb[s] = ld_frag(rowB, ld_rowB, r0 + lr, NR, 4 * s + lq);
+        fa[s] = ld_frag<DH>(r.rowA, r.ld_rowA, r0 + lr, r.NR, s, lq);
+        fb[s] = ld_frag<DH>(r.rowB, r.ld_rowB, r0 + lr, r.NR, s, lq);
     }
-    float Lr[4], Dr[4];                 // KV = false: the statistics of the block's query rows 4 lq + i
+    float Lr[4] = {0.f, 0.f, 0.f, 0.f}, Dr[4] = {0.f, 0.f, 0.f, 0.f};   // query blocks: the statistics of rows 4 lq + i
     if (!KV) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int q = min(r0 + 4 * lq + i, NR - 1);
-            Lr[i] = st[2 * q]; Dr[i] = st[2 * q + 1];
+            const int q = min(r0 + 4 * lq + i, r.NR - 1);
+            Lr[i] = r.st[2 * q]; Dr[i] = r.st[2 * q + 1];
         }
     }
     f32x4 acc1[NT], acc2[NT];           // [16 rows][DH channels] as 16-column tiles: dQ | dK, and dV
 #pragma unroll
     for (int t = 0; t < NT; ++t) { acc1[t] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc2[t] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
 
-    for (int j0 = 0; j0 < NC; j0 += AB_J) {
+    for (int j0 = 0; j0 < r.NC; j0 += AB_J) {
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int col = j0 + 16 * half + lr;                       // this lane's column of the tile: a key (KV false) or a query (KV true)
-            const f32x4 sc = tile_qk(fa, colA, ld_colA, col, NC, lq);
-            const f32x4 dp = tile_qk(fb, colB, ld_colB, col, NC, lq);
-            float Lc = 0.f, Dc = 0.f;
-            if (KV) { const int q = min(col, NC - 1); Lc = st[2 * q]; Dc = st[2 * q + 1]; }
+            const f32x4 sc = tile_qk<DH>(fa, r.colA, r.ld_colA, col, r.NC, lq);
+            const f32x4 dp = tile_qk<DH>(fb, r.colB, r.ld_colB, col, r.NC, lq);
+            float p[4], ds[4];
+            p_ds<KV>(sc, dp, a.scale, r, r0 + 4 * lq, col, Lr, Dr, p, ds);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const bool live = col < NC && r0 + 4 * lq + i < NR;
-                const float p = live ? expf(sc[i] * a.scale - (KV ? Lc : Lr[i])) : 0.f;
-                const float dsv = p * (dp[i] - (KV ? Dc : Dr[i]));
-                ds_t[4 * lq + i][16 * half + lr] = (bf16_t)dsv;        // P and dS are rounded to bf16 here, before the second products
-                if (KV) p_t[4 * lq + i][16 * half + lr] = (bf16_t)p;
+                ds_t[4 * lq + i][16 * half + lr] = (bf16_t)ds[i];      // P and dS are rounded to bf16 here, before the second products
+                if (KV) p_t[4 * lq + i][16 * half + lr] = (bf16_t)p[i];
             }
         }
         __syncthreads();
@@ -160,9 +230,9 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
             bf16x8 y1, y2;                                              // B: [loop row j0 + 8 lq + e][channel 16 t + lr]
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const int r = min(j0 + 8 * lq + e, NC - 1);
-                y1[e] = colA[(long)r * ld_colA + 16 * t + lr];
-                if (KV) y2[e] = colB[(long)r * ld_colB + 16 * t + lr];
+                const int c = min(j0 + 8 * lq + e, r.NC - 1);
+                y1[e] = r.colA[(long)c * r.ld_colA + 16 * t + lr];
+                if (KV) y2[e] = r.colB[(long)c * r.ld_colB + 16 * t + lr];
             }
             acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsf, y1, acc1[t], 0, 0, 0);
             if (KV) acc2[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, y2, acc2[t], 0, 0, 0);
@@ -174,16 +244,16 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int r = r0 + 4 * lq + i;
-            if (r < NR) {
-                o1[(long)r * ld1 + 16 * t + lr] = (bf16_t)(acc1[t][i] * a.scale);
-                if (KV) a.dV[(long)b * a.dkv_bs + h * DH + (long)r * a.lddv + 16 * t + lr] = (bf16_t)acc2[t][i];
+            const int row = r0 + 4 * lq + i;
+            if (row < r.NR) {
+                o1[(long)row * ld1 + 16 * t + lr] = (bf16_t)(acc1[t][i] * a.scale);
+                if (KV) a.dV[(long)b * a.dkv_bs + h * DH + (long)row * a.lddv + 16 * t + lr] = (bf16_t)acc2[t][i];
             }
         }
 }
 
 template <int DH>
-static int attn_bwd_launch_dh(const AttnBwdArgs& a, hipStream_t s) {
+static int attn_bwd_launch(const AttnBwdArgs& a, hipStream_t s) {
     const dim3 grid((unsigned)((a.Nq + AB_T - 1) / AB_T), (unsigned)a.H, (unsigned)a.B), block(64);      // query blocks
     const dim3 grid_kv((unsigned)((a.Nk + AB_T - 1) / AB_T), (unsigned)a.H, (unsigned)a.B);               // key blocks
     hipLaunchKernelGGL(attn_bwd_stats_kernel<DH>, grid, block, 0, s, a);
@@ -196,30 +266,188 @@ static int attn_bwd_launch_dh(const AttnBwdArgs& a, hipStream_t s) {
     return ldt_check_launch("attention_bwd (dK, dV)");
 }
 
-int ldt_attn_bwd_launch(const AttnBwdArgs* a, int dh, hipStream_t s) {   // the entry points have checked the operands
-    LDT_REQUIRE(dh == 64 || dh == 32, LDT_ESHAPE, "attention_bwd (MFMA form): head dim %d is not 32 or 64", dh);
-    return dh == 64 ? attn_bwd_launch_dh<64>(*a, s) : attn_bwd_launch_dh<32>(*a, s);
+// ---- narrow form, head dim 8 or 16.  Query blocks: first the statistics of the block's 16 query rows, which go to `stats` for the key blocks
+// (the launch after it, in stream order) and stay in registers here; then the dQ sweep.  Key blocks: dK and dV.
+template <int DH, bool KV>
+__global__ __launch_bounds__(256) void attn_bwd_narrow_kernel(const AttnBwdArgs a, long units, int nrb) {
+    constexpr int NP = DH / 8;                                          // 16-byte pieces of a head's slice of a row
+    constexpr int NV = 4 * DH;                                          // partial sums per lane and output: [4 rows][DH channels]
+    const int lane = threadIdx.x & 63, lr = lane & 15, lq = lane >> 4;
+    const long unit = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (unit >= units) return;                                          // whole wave; the waves of a workgroup share nothing
+    const int r0 = (int)(unit % nrb) * AB_T;
+    const long bh = unit / nrb;
+    const int b = (int)(bh / a.H), head = (int)(bh % a.H);
+    const AttnBwdRoles r = attn_bwd_roles<DH, KV>(a, b, head);
+    // a row's whole head slice; rows past the end n repeat the last.  (The MFMA fragment, ld_frag, is loaded on its own: a select between
+    // the pieces of this array would turn the array into an indexed one.)
+    auto row_of = [&](const bf16_t* base, long ld, int row, int n, bf16x8 (&y)[NP]) {
+        const bf16_t* p = base + (long)min(row, n - 1) * ld;
+#pragma unroll
+        for (int c = 0; c < NP; ++c) y[c] = *reinterpret_cast<const bf16x8*>(p + 8 * c);
+    };
+    const bf16x8 fa[1] = {ld_frag<DH>(r.rowA, r.ld_rowA, r0 + lr, r.NR, 0, lq)}, fb[1] = {ld_frag<DH>(r.rowB, r.ld_rowB, r0 + lr, r.NR, 0, lq)};
+
+    float Lr[4] = {0.f, 0.f, 0.f, 0.f}, Dr[4] = {0.f, 0.f, 0.f, 0.f};   // query blocks: the statistics of rows 4 lq + i
+    if constexpr (!KV) {
+        row_lse<DH>(fa, r.colA, r.ld_colA, r.NC, a.scale, lr, lq, Lr);
+        const float d = row_d<DH>(a.O + r.ob * DH, r0 + lr, r.NR, fb, lq);      // of row r0 + lr
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            Dr[i] = __shfl(d, 4 * lq + i, 64);                          // from the lane whose lr is this row
+            const int q = r0 + 4 * lq + i;
+            if (lr == 0 && q < r.NR) r.st[2 * q] = Lr[i];
+        }
+        if (lq == 0 && r0 + lr < r.NR) r.st[2 * (r0 + lr) + 1] = d;
+    }
+
+    float acc1[NV], acc2[KV ? NV : 1];                                  // dQ | dK, and dV: [row 4 lq + i][channel], this lane's columns only
+#pragma unroll
+    for (int n = 0; n < NV; ++n) acc1[n] = 0.f;
+#pragma unroll
+    for (int n = 0; n < (KV ? NV : 1); ++n) acc2[n] = 0.f;
+    for (int j0 = 0; j0 < r.NC; j0 += 16) {
+        const int col = j0 + lr;                                        // this lane's column: a key (query blocks) or a query (key blocks)
+        bf16x8 ya[NP], yb[NP];
+        row_of(r.colA, r.ld_colA, col, r.NC, ya);
+        row_of(r.colB, r.ld_colB, col, r.NC, yb);
+        const f32x4 sc = tile_qk<DH>(fa, r.colA, r.ld_colA, col, r.NC, lq);
+        const f32x4 dp = tile_qk<DH>(fb, r.colB, r.ld_colB, col, r.NC, lq);
+        float p[4], ds[4];                                              // fp32: never an MFMA operand
+        p_ds<KV>(sc, dp, a.scale, r, r0 + 4 * lq, col, Lr, Dr, p, ds);
+#pragma unroll
+        for (int cc = 0; cc < DH; ++cc) {
+            const float y1 = (float)ya[cc >> 3][cc & 7];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc1[i * DH + cc] = fmaf(ds[i], y1, acc1[i * DH + cc]);
+            if constexpr (KV) {
+                const float y2 = (float)yb[cc >> 3][cc & 7];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc2[i * DH + cc] = fmaf(p[i], y2, acc2[i * DH + cc]);
+            }
+        }
+    }
+
+    // over the 16 lanes of an lq: after the four halvings this lane holds row 4 lq + (lr >> 2), channels c0 .. c0 + DH / 4 - 1
+    narrow_halve<NV, 8>(acc1, lr);
+    narrow_halve<NV / 2, 4>(acc1, lr);
+    narrow_halve<NV / 4, 2>(acc1, lr);
+    narrow_halve<NV / 8, 1>(acc1, lr);
+    if constexpr (KV) {
+        narrow_halve<NV, 8>(acc2, lr);
+        narrow_halve<NV / 2, 4>(acc2, lr);
+        narrow_halve<NV / 4, 2>(acc2, lr);
+        narrow_halve<NV / 8, 1>(acc2, lr);
+    }
+    const int row = r0 + 4 * lq + (lr >> 2), c0 = ((lr >> 1) & 1) * (DH / 2) + (lr & 1) * (DH / 4);
+    if (row >= r.NR) return;
+    auto store = [&](bf16_t* dst, const float* v, float f) {
+        if constexpr (DH == 8) {
+            typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+            *reinterpret_cast<bf16x2*>(dst) = (bf16x2){(bf16_t)(v[0] * f), (bf16_t)(v[1] * f)};
+        } else {
+            *reinterpret_cast<bf16x4*>(dst) = (bf16x4){(bf16_t)(v[0] * f), (bf16_t)(v[1] * f), (bf16_t)(v[2] * f), (bf16_t)(v[3] * f)};
+        }
+    };
+    if constexpr (KV) {
+        store(a.dK + (long)b * a.dkv_bs + (long)row * a.lddk + head * DH + c0, acc1, a.scale);
+        store(a.dV + (long)b * a.dkv_bs + (long)row * a.lddv + head * DH + c0, acc2, 1.0f);
+    } else {
+        store(a.dQ + (long)b * a.dq_bs + (long)row * a.lddq + head * DH + c0, acc1, a.scale);
+    }
 }
 
-extern "C" int ldt_attention_bwd(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk, const uint16_t* V,
-                                 int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats, uint16_t* dQ,
-                                 int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
-                                 int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t N, int32_t head_dim, void* stream) {
-    LDT_REQUIRE(Q && K && V && O && dO && stats && dQ && dK && dV, LDT_EARG, "attention_bwd: null pointer");
-    LDT_REQUIRE(head_dim == 64 && B > 0 && B <= 65535 && H > 0 && H <= 65535 && N > 0 && N <= 512, LDT_ESHAPE,
-                "attention_bwd: head_dim %d (64 only), B %d, H %d, N %d (self-attention, N <= 512)", head_dim, B, H, N);
-    const long need = (long)H * 64;
+template <int DH>
+static int attn_bwd_narrow_launch(const AttnBwdArgs& a, hipStream_t s) {
+    const int nqb = (a.Nq + AB_T - 1) / AB_T, nkb = (a.Nk + AB_T - 1) / AB_T;                  // query blocks, key blocks
+    const long uq = (long)a.B * a.H * nqb, uk = (long)a.B * a.H * nkb, gq = (uq + 3) / 4, gk = (uk + 3) / 4;
+    LDT_REQUIRE(gq < (1L << 31) && gk < (1L << 31), LDT_ESHAPE, "attention_bwd_narrow: grid too large");
+    hipLaunchKernelGGL((attn_bwd_narrow_kernel<DH, false>), dim3((unsigned)gq), dim3(256), 0, s, a, uq, nqb);
+    const int rc = ldt_check_launch("attention_bwd_narrow (row statistics, dQ)");
+    if (rc != LDT_OK) return rc;
+    hipLaunchKernelGGL((attn_bwd_narrow_kernel<DH, true>), dim3((unsigned)gk), dim3(256), 0, s, a, uk, nkb);
+    return ldt_check_launch("attention_bwd_narrow (dK, dV)");
+}
+
+// ---- the entry points (include/ldt_hip.h).  Each says which head widths and lengths it admits (`admit`: LDT_OK, or the status with the message
+// set) and whether the narrow form's store rule holds for it; the rest is one body.  Order of the refusals: null, shape, stride, alignment.
+template <class Admit>
+static int attn_bwd_run(const char* name, Admit admit, const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk,
+                        const uint16_t* V, int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats,
+                        uint16_t* dQ, int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
+                        int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim, bool store8, void* stream) {
+    LDT_REQUIRE(Q && K && V && O && dO && stats && dQ && dK && dV, LDT_EARG, "%s: null pointer", name);
+    const int rc = admit();
+    if (rc != LDT_OK) return rc;
+    LDT_REQUIRE(B > 0 && B <= 65535 && H > 0 && H <= 65535, LDT_ESHAPE, "%s: B %d, H %d (1 .. 65535 each)", name, B, H);
+    const long need = (long)H * head_dim;
     LDT_REQUIRE(ldq >= need && ldk >= need && ldv >= need && lddq >= need && lddk >= need && lddv >= need, LDT_ESHAPE,
-                "attention_bwd: a row stride is shorter than heads * 64 = %ld", need);
+                "%s: a row stride is shorter than heads * head_dim = %ld", name, need);
     LDT_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && q_batch_stride % 8 == 0 && kv_batch_stride % 8 == 0 && ldt_aligned16(Q) &&
                 ldt_aligned16(K) && ldt_aligned16(V) && ldt_aligned16(O) && ldt_aligned16(dO), LDT_EALIGN,
-                "attention_bwd: Q, K, V, O, dO rows must be 16-byte aligned");
+                "%s: Q, K, V, O, dO rows must be 16-byte aligned", name);
+    if (store8)                                                         // the narrow kernels store Dh / 4 adjacent channels at once (4 or 8 bytes)
+        LDT_REQUIRE(lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0 && dq_batch_stride % 4 == 0 && dkv_batch_stride % 4 == 0 &&
+                    ((reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dK) | reinterpret_cast<uintptr_t>(dV)) & 7u) == 0, LDT_EALIGN,
+                    "%s: dQ, dK, dV rows must be 8-byte aligned", name);
     AttnBwdArgs a;
     a.Q = reinterpret_cast<const bf16_t*>(Q); a.ldq = ldq; a.q_bs = q_batch_stride;
     a.K = reinterpret_cast<const bf16_t*>(K); a.ldk = ldk; a.V = reinterpret_cast<const bf16_t*>(V); a.ldv = ldv; a.kv_bs = kv_batch_stride;
     a.O = reinterpret_cast<const bf16_t*>(O); a.dO = reinterpret_cast<const bf16_t*>(dO); a.stats = stats;
     a.dQ = reinterpret_cast<bf16_t*>(dQ); a.lddq = lddq; a.dq_bs = dq_batch_stride;
     a.dK = reinterpret_cast<bf16_t*>(dK); a.lddk = lddk; a.dV = reinterpret_cast<bf16_t*>(dV); a.lddv = lddv; a.dkv_bs = dkv_batch_stride;
-    a.B = B; a.H = H; a.Nq = N; a.Nk = N; a.scale = 0.125f;
-    return ldt_attn_bwd_launch(&a, 64, reinterpret_cast<hipStream_t>(stream));
+    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.scale = 1.0f / sqrtf((float)head_dim);      // exactly 0.125 at 64
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    switch (head_dim) {
+        case 64: return attn_bwd_launch<64>(a, s);
+        case 32: return attn_bwd_launch<32>(a, s);
+        case 16: return attn_bwd_narrow_launch<16>(a, s);
+        case 8: return attn_bwd_narrow_launch<8>(a, s);
+    }
+    LDT_REQUIRE(false, LDT_ESHAPE, "%s: no kernel for head_dim %d", name, head_dim);
+}
+
+extern "C" int ldt_attention_bwd(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk, const uint16_t* V,
+                                 int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats, uint16_t* dQ,
+                                 int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
+                                 int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t N, int32_t head_dim, void* stream) {
+    auto admit = [&]() -> int {
+        LDT_REQUIRE(head_dim == 64 && N > 0 && N <= 512, LDT_ESHAPE, "attention_bwd: head_dim %d (64 only), N %d (self-attention, N <= 512)",
+                    head_dim, N);
+        return LDT_OK;
+    };
+    return attn_bwd_run("attention_bwd", admit, Q, ldq, q_batch_stride, K, ldk, V, ldv, kv_batch_stride, O, dO, stats, dQ, lddq,
+                        dq_batch_stride, dK, lddk, dV, lddv, dkv_batch_stride, B, H, N, N, head_dim, false, stream);
+}
+
+// head dim 32 runs the MFMA form but keeps the store rule of the entry point it is reached through (include/ldt_hip.h)
+extern "C" int ldt_attention_bwd_narrow(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk,
+                                        const uint16_t* V, int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO,
+                                        float* stats, uint16_t* dQ, int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk,
+                                        uint16_t* dV, int64_t lddv, int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t N,
+                                        int32_t head_dim, void* stream) {
+    auto admit = [&]() -> int {
+        LDT_REQUIRE(head_dim == 8 || head_dim == 16 || head_dim == 32, LDT_ESHAPE,
+                    "attention_bwd_narrow: head_dim %d is not 8, 16 or 32 (64: ldt_attention_bwd)", head_dim);
+        LDT_REQUIRE(N > 0 && N <= 512, LDT_ESHAPE, "attention_bwd_narrow: N %d (self-attention, N <= 512)", N);
+        return LDT_OK;
+    };
+    return attn_bwd_run("attention_bwd_narrow", admit, Q, ldq, q_batch_stride, K, ldk, V, ldv, kv_batch_stride, O, dO, stats, dQ, lddq,
+                        dq_batch_stride, dK, lddk, dV, lddv, dkv_batch_stride, B, H, N, N, head_dim, true, stream);
+}
+
+// At Nq = Nk the result equals the self-attention entry points' bit for bit.
+extern "C" int ldt_attention_bwd_cross(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk,
+                                       const uint16_t* V, int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO,
+                                       float* stats, uint16_t* dQ, int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk,
+                                       uint16_t* dV, int64_t lddv, int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t Nq, int32_t Nk,
+                                       int32_t head_dim, void* stream) {
+    auto admit = [&]() -> int {
+        LDT_REQUIRE(head_dim == 8 || head_dim == 16 || head_dim == 32 || head_dim == 64, LDT_ESHAPE,
+                    "attention_bwd_cross: head_dim %d is not 8, 16, 32 or 64", head_dim);
+        LDT_REQUIRE(Nq > 0 && Nq <= 512 && Nk > 0 && Nk <= 512, LDT_ESHAPE, "attention_bwd_cross: Nq %d, Nk %d (1 <= Nq, Nk <= 512)", Nq, Nk);
+        return LDT_OK;
+    };
+    return attn_bwd_run("attention_bwd_cross", admit, Q, ldq, q_batch_stride, K, ldk, V, ldv, kv_batch_stride, O, dO, stats, dQ, lddq,
+                        dq_batch_stride, dK, lddk, dV, lddv, dkv_batch_stride, B, H, Nq, Nk, head_dim, head_dim <= 16, stream);
 }

@@ -110,20 +110,6 @@ int ldt_attn_launch(const AttnArgs* a, int dh, hipStream_t s);
 int ldt_attn_route(int B, int H, int Nq, int Nk, int dh);       // 0 streaming, 1 resident, 2 whole-head (attention.hip), 3 narrow heads (attention_narrow.hip)
 int ldt_attn_narrow_launch(const AttnArgs* a, int dh, hipStream_t s);   // head dim 8 or 16; ldt_attn_launch has checked the operands
 int ldt_attn_oproj_launch(const AttnArgs* a, int dh, hipStream_t s);
-// attention backward (Nq, Nk <= 512): the operands of ldt_attention_bwd / ldt_attention_bwd_narrow (self-attention: Nq = Nk = N) and of
-// ldt_attention_bwd_cross (include/ldt_hip.h)
-struct AttnBwdArgs {
-    const bf16_t* Q; long ldq; long q_bs;
-    const bf16_t* K; long ldk; const bf16_t* V; long ldv; long kv_bs;
-    const bf16_t* O; const bf16_t* dO;        // [B][H][Nq][Dh]
-    float* stats;                             // [B][H][Nq][2] = (L, D)
-    bf16_t* dQ; long lddq; long dq_bs;
-    bf16_t* dK; long lddk; bf16_t* dV; long lddv; long dkv_bs;
-    int B, H, Nq, Nk;                         // queries (rows of Q, O, dO, dQ, stats) and keys (rows of K, V, dK, dV) per sample
-    float scale;                              // Dh^-0.5
-};
-int ldt_attn_bwd_launch(const AttnBwdArgs* a, int dh, hipStream_t s);          // attention_bwd.hip: head dim 64 or 32 (MFMA second products)
-int ldt_attn_bwd_narrow_launch(const AttnBwdArgs* a, int dh, hipStream_t s);   // attention_narrow_bwd.hip: head dim 8 or 16
 // Sum of v[0..N) over the lanes lr and lr ^ M, split between them: the lane with bit M keeps the upper half of v.  Four of these (M = 8, 4, 2,
 // 1) sum a per-lane array over the 16 lanes of an MFMA row group in a fixed order and leave each lane N / 16 adjacent elements (narrow heads).
 template <int N, int M>

@@ -938,28 +938,37 @@ def embedding_grad(dc, label, n_classes):
     return out
 
 
+def _attention_bwd(fn, entry, q, k, v, o, do, B, H, lengths, head_dim, outs):
+    """attention_bwd (lengths = (N,)) and attention_bwd_cross ((Nq, Nk)): the operand checks, outs(H*head_dim) -> (dq, dk, dv) bf16 row
+    views, the statistics buffer and the call of `entry`, which takes the lengths as given."""
+    Nq, Nk, cross = lengths[0], lengths[-1], len(lengths) == 2
+    if head_dim not in (8, 16, 32, 64):
+        raise ValueError("%s: head_dim %r is not 8, 16, 32 or 64" % (fn, head_dim))
+    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
+        _need(t, torch.bfloat16, nm); _rowmajor(t, nm)
+    if not (o.is_contiguous() and do.is_contiguous()) or o.numel() != B * H * Nq * head_dim or do.numel() != o.numel():
+        raise ValueError("%s: o and do must be contiguous [B, H, %s, %d]" % (fn, "Nq" if cross else "N", head_dim))
+    if k.stride(0) != v.stride(0):
+        raise ValueError("%s: K and V must share the row stride" % fn)
+    Cc = H * head_dim
+    if cross and (q.shape[0] != B * Nq or k.shape[0] != B * Nk or v.shape[0] != B * Nk or min(q.shape[1], k.shape[1], v.shape[1]) < Cc):
+        raise ValueError("%s: q %s, k %s, v %s for B %d, Nq %d, Nk %d, %d channels"
+                         % (fn, tuple(q.shape), tuple(k.shape), tuple(v.shape), B, Nq, Nk, Cc))
+    dq, dk, dv = outs(Cc)
+    stats = torch.empty((B, H, Nq, 2), dtype=torch.float32, device=q.device)
+    ldq, ldkv = dq.stride(0), dk.stride(0)
+    check(getattr(lib(), entry)(_p(q), q.stride(0), q.stride(0) * Nq, _p(k), k.stride(0), _p(v), v.stride(0), k.stride(0) * Nk, _p(o), _p(do),
+                                _p(stats), _p(dq), ldq, ldq * Nq, _p(dk), ldkv, _p(dv), ldkv, ldkv * Nk, B, H, *lengths, head_dim, stream_ptr()), entry)
+    return dq, dk, dv
+
+
 def attention_bwd(q, k, v, o, do, B, H, N, head_dim=64, out=None):
     """Self-attention backward: q, k, v bf16 row views [B*N, >= H*head_dim] as attention_fwd takes them, o and do the contiguous bf16
     [B, H, N, head_dim] buffers (quirk Q1: the raw (B*N, C) view).  -> (dq, dk, dv) bf16 views [B*N, H*head_dim] of one
     [B*N, 3*H*head_dim] tensor (`out` when given), the dY operand of the QKV projection's backward GEMMs.
     head_dim 64: ldt_attention_bwd; 8, 16 or 32: ldt_attention_bwd_narrow; anything else is a ValueError."""
-    if head_dim not in (8, 16, 32, 64):
-        raise ValueError("attention_bwd: head_dim %r is not 8, 16, 32 or 64" % (head_dim,))
-    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
-        _need(t, torch.bfloat16, nm); _rowmajor(t, nm)
-    if not (o.is_contiguous() and do.is_contiguous()) or o.numel() != B * H * N * head_dim or do.numel() != o.numel():
-        raise ValueError("attention_bwd: o and do must be contiguous [B, H, N, %d]" % head_dim)
-    if k.stride(0) != v.stride(0):
-        raise ValueError("attention_bwd: K and V must share the row stride")
-    Cc = H * head_dim
-    out = _bf16_rows_out(out, B * N, 3 * Cc, q.device, "attention_bwd: out")
-    dq, dk, dv = out[:, :Cc], out[:, Cc:2 * Cc], out[:, 2 * Cc:]
-    stats = torch.empty((B, H, N, 2), dtype=torch.float32, device=q.device)
-    ldo = out.stride(0)
-    name = "ldt_attention_bwd" if head_dim == 64 else "ldt_attention_bwd_narrow"
-    check(getattr(lib(), name)(_p(q), q.stride(0), q.stride(0) * N, _p(k), k.stride(0), _p(v), v.stride(0), k.stride(0) * N, _p(o), _p(do),
-                               _p(stats), _p(dq), ldo, ldo * N, _p(dk), ldo, _p(dv), ldo, ldo * N, B, H, N, head_dim, stream_ptr()), name)
-    return dq, dk, dv
+    return _attention_bwd("attention_bwd", "ldt_attention_bwd" if head_dim == 64 else "ldt_attention_bwd_narrow", q, k, v, o, do, B, H, (N,),
+                          head_dim, lambda Cc: _bf16_rows_out(out, B * N, 3 * Cc, q.device, "attention_bwd: out").split(Cc, 1))
 
 
 def attention_bwd_cross(q, k, v, o, do, B, H, Nq, Nk, head_dim, dq_out=None, dkv_out=None):
@@ -967,27 +976,9 @@ def attention_bwd_cross(q, k, v, o, do, B, H, Nq, Nk, head_dim, dq_out=None, dkv
     row stride, o and do the contiguous bf16 [B, H, Nq, head_dim] buffers (quirk Q1).  -> (dq, dk, dv): dq bf16 [B*Nq, H*head_dim] (`dq_out`
     when given), dk | dv the two halves of one bf16 [B*Nk, 2*H*head_dim] tensor (`dkv_out` when given), the dY operand of fc_kv's backward
     GEMMs.  head_dim 8, 16, 32 or 64; Nq != Nk allowed."""
-    if head_dim not in (8, 16, 32, 64):
-        raise ValueError("attention_bwd_cross: head_dim %r is not 8, 16, 32 or 64" % (head_dim,))
-    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do")):
-        _need(t, torch.bfloat16, nm); _rowmajor(t, nm)
-    if not (o.is_contiguous() and do.is_contiguous()) or o.numel() != B * H * Nq * head_dim or do.numel() != o.numel():
-        raise ValueError("attention_bwd_cross: o and do must be contiguous [B, H, Nq, %d]" % head_dim)
-    if k.stride(0) != v.stride(0):
-        raise ValueError("attention_bwd_cross: K and V must share the row stride")
-    Cc = H * head_dim
-    if q.shape[0] != B * Nq or k.shape[0] != B * Nk or v.shape[0] != B * Nk or min(q.shape[1], k.shape[1], v.shape[1]) < Cc:
-        raise ValueError("attention_bwd_cross: q %s, k %s, v %s for B %d, Nq %d, Nk %d, %d channels"
-                         % (tuple(q.shape), tuple(k.shape), tuple(v.shape), B, Nq, Nk, Cc))
-    dq = _bf16_rows_out(dq_out, B * Nq, Cc, q.device, "attention_bwd_cross: dq_out")
-    dkv = _bf16_rows_out(dkv_out, B * Nk, 2 * Cc, q.device, "attention_bwd_cross: dkv_out")
-    dk, dv = dkv[:, :Cc], dkv[:, Cc:]
-    stats = torch.empty((B, H, Nq, 2), dtype=torch.float32, device=q.device)
-    ldq, ldkv = dq.stride(0), dkv.stride(0)
-    check(lib().ldt_attention_bwd_cross(_p(q), q.stride(0), q.stride(0) * Nq, _p(k), k.stride(0), _p(v), v.stride(0), k.stride(0) * Nk, _p(o),
-                                        _p(do), _p(stats), _p(dq), ldq, ldq * Nq, _p(dk), ldkv, _p(dv), ldkv, ldkv * Nk, B, H, Nq, Nk,
-                                        head_dim, stream_ptr()), "ldt_attention_bwd_cross")
-    return dq, dk, dv
+    return _attention_bwd("attention_bwd_cross", "ldt_attention_bwd_cross", q, k, v, o, do, B, H, (Nq, Nk), head_dim,
+                          lambda Cc: (_bf16_rows_out(dq_out, B * Nq, Cc, q.device, "attention_bwd_cross: dq_out"),)
+                          + _bf16_rows_out(dkv_out, B * Nk, 2 * Cc, q.device, "attention_bwd_cross: dkv_out").split(Cc, 1))
 
 
 def sumsq(x, max_norm=0.0, scratch=None, out=None):

@@ -10,8 +10,8 @@ gradient with respect to that pair back.  ConditionNet itself is not differentia
 `AdamEMA` keeps fp32 master parameters, gradients, both Adam moments and the EMA in five flat device buffers (one fused
 `ldt_adam_ema_step` launch per step; bf16 operand panels are derived from the masters, never trained).  `ScoreTrainStep` runs the same
 kernels as inference, unfused, keeps per block what the backward needs, and then walks the blocks back: every GEMM of the backward is
-`ldt_gemm_bf16` on operands prepared by `ldt_transpose_cast_bf16`; everything else is csrc/score_bwd.hip, csrc/attention_bwd.hip and
-csrc/attention_narrow_bwd.hip (self-attention: ldt_attention_bwd / _narrow; cross-attention: ldt_attention_bwd_cross).
+`ldt_gemm_bf16` on operands prepared by `ldt_transpose_cast_bf16`; everything else is csrc/score_bwd.hip and
+csrc/attention_bwd.hip (self-attention: ldt_attention_bwd / _narrow; cross-attention: ldt_attention_bwd_cross).
 """
 import torch
 

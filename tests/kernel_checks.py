@@ -1432,13 +1432,15 @@ def embedding_grad_ref(dc, label, K):
     return ref, (nk - 1).clamp_min(0) * U24 * mag
 
 
-def attn_bwd_ref(qkv, o, do, B, H, N):
-    """float64 from the bf16 operands: -> dict of references and of componentwise bounds, [B, H, N, 64] each."""
-    C = H * 64
-    hd = lambda z: z.double().view(B, N, H, 64).permute(0, 2, 1, 3)
-    q, k, v = hd(qkv[:, :C]), hd(qkv[:, C:2 * C]), hd(qkv[:, 2 * C:])
+def attn_bwd_ref(q, k, v, o, do, B, H, Nq, Nk, Dh=64, rounded=True):
+    """The attention backward in float64 from the bf16 operands: q rows [B Nq, H Dh], k and v rows [B Nk, H Dh], o and do [B, H, Nq, Dh]
+    -> (references, componentwise bounds): dq [B, H, Nq, Dh]; dk, dv [B, H, Nk, Dh].  Self-attention: Nq = Nk.
+    rounded=True    P and dS are rounded to bf16 before the second products (MFMA operands): the 2^-8 terms on P and dS are present.
+                    The kernels for head widths 32 and 64.
+    rounded=False   P and dS stay fp32 (per-lane FMAs): the 2^-8 terms are absent.  The kernels for 8 and 16."""
+    q, k, v = heads(q, B, Nq, H, Dh), heads(k, B, Nk, H, Dh), heads(v, B, Nk, H, Dh)
     o6, g6 = o.double(), do.double()
-    sc = 0.125
+    sc = Dh ** -0.5
     s = q @ k.transpose(-1, -2) * sc
     L = torch.logsumexp(s, -1, keepdim=True)
     P = torch.exp(s - L)
@@ -1446,18 +1448,20 @@ def attn_bwd_ref(qkv, o, do, B, H, N):
     dP = g6 @ v.transpose(-1, -2)
     dS = P * (dP - D)
     ref = {"dq": dS @ k * sc, "dk": dS.transpose(-1, -2) @ q * sc, "dv": P.transpose(-1, -2) @ g6}
-    # bound.  s and dP: fp32 MFMA sums of 64 terms (C_ACC 64 2^-24 |.||.|); the exponent s - L carries that of s twice (L is built from the
-    # same sums) + 8 x 2^-24 (|s| + |L|) of its fp32 arithmetic + expf / logf: P's relative error e_arg.  D: a 64-term fp32 sum.
-    # dS in fp32: P e_arg |dP - D| + P (e_dP + e_D) + 2 x 2^-24 |dS|; THEN ROUNDED TO bf16: + 2^-8 |dS|.  P ROUNDED TO bf16 for dV: + 2^-8 P.
-    # Second products: C_ACC N 2^-24 |.||.| each, scaled by 1 / 8 in fp32 (dq, dk), and the bf16 output 2^-8 |ref|.
-    acc = C_ACC * 64 * U24
+    # bound.  s and dP: fp32 MFMA sums of Dh terms (C_ACC Dh 2^-24 |.||.|); the exponent s - L carries that of s twice (L is built from the
+    # same sums) + 8 x 2^-24 (|s| + |L|) of its fp32 arithmetic + expf / logf: P's relative error e_arg.  D: a Dh-term fp32 sum.
+    # dS in fp32: P e_arg |dP - D| + P (e_dP + e_D) + 2 x 2^-24 |dS|; then rounded to bf16 (u8 = 2^-8) or kept (u8 = 0), and P likewise for
+    # dV.  Second products: C_ACC n 2^-24 |.||.| each — dq sums over the Nk keys, dk and dv over the Nq queries — the scale in fp32 (dq, dk),
+    # and the bf16 output 2^-8 |ref|.
+    u8 = U8 if rounded else 0.0
+    acc = C_ACC * Dh * U24
     e_arg = 2 * acc * (q.abs() @ k.abs().transpose(-1, -2)) * sc + 8 * U24 * (s.abs() + L.abs()) + 4 * LIBM_ABS
     e_dP = acc * (g6.abs() @ v.abs().transpose(-1, -2))
     e_D = acc * (g6.abs() * o6.abs()).sum(-1, keepdim=True)
-    e_dS = P * e_arg * (dP - D).abs() + P * (e_dP + e_D) + (2 * U24 + U8) * dS.abs()
-    e_P = P * e_arg + U8 * P
-    acc2 = C_ACC * N * U24
-    tol = {"dq": sc * (e_dS @ k.abs() + acc2 * (dS.abs() @ k.abs())) + (U8 + 2 * U24) * ref["dq"].abs(),
-           "dk": sc * (e_dS.transpose(-1, -2) @ q.abs() + acc2 * (dS.abs().transpose(-1, -2) @ q.abs())) + (U8 + 2 * U24) * ref["dk"].abs(),
-           "dv": e_P.transpose(-1, -2) @ g6.abs() + acc2 * (P.transpose(-1, -2) @ g6.abs()) + (U8 + U24) * ref["dv"].abs()}
+    e_dS = P * e_arg * (dP - D).abs() + P * (e_dP + e_D) + (2 * U24 + u8) * dS.abs()
+    e_P = P * e_arg + u8 * P
+    acc_k, acc_q = C_ACC * Nk * U24, C_ACC * Nq * U24
+    tol = {"dq": sc * (e_dS @ k.abs() + acc_k * (dS.abs() @ k.abs())) + (U8 + 2 * U24) * ref["dq"].abs(),
+           "dk": sc * (e_dS.transpose(-1, -2) @ q.abs() + acc_q * (dS.abs().transpose(-1, -2) @ q.abs())) + (U8 + 2 * U24) * ref["dk"].abs(),
+           "dv": e_P.transpose(-1, -2) @ g6.abs() + acc_q * (P.transpose(-1, -2) @ g6.abs()) + (U8 + U24) * ref["dv"].abs()}
     return ref, tol

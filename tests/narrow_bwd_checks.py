@@ -1,16 +1,12 @@
-"""Helpers of test_train_narrow_host.py, test_gpu_train_narrow_kernels.py and test_gpu_train_narrow_tape.py: the attention backward at head
-widths 8, 16 and 32 (ldt_attention_bwd_narrow: csrc/attention_narrow_bwd.hip, and csrc/attention_bwd.hip instantiated at 32).
+"""Helpers of the attention-backward tests (ldt_attention_bwd, _narrow and _cross: csrc/attention_bwd.hip): the self-attention cases at
+head widths 8, 16 and 32 of test_train_narrow_host.py, test_gpu_train_narrow_kernels.py and test_gpu_train_narrow_tape.py, and what every
+case, one length or two (tests/cross_bwd_checks.py), is prepared and emulated with.
 
-`attn_bwd_ref` is kernel_checks.attn_bwd_ref with Dh in place of 64: the same float64 reference and the same componentwise bound — the
-first-product accumulation term C_ACC Dh 2^-24, the scale Dh^-0.5 — and a switch for the two forms of the second products:
-    rounded=True    P and dS are rounded to bf16 before the second products (MFMA operands): the 2^-8 terms on P and dS are present.
-                    The 64-wide kernel and its instantiation at 32.  At Dh = 64 this IS kernel_checks.attn_bwd_ref, bit for bit.
-    rounded=False   P and dS stay fp32 (per-lane FMAs): the 2^-8 terms are absent.  The kernels for 8 and 16.
-`emulate` is the kernel's arithmetic in fp32 on the CPU, with the faults the host test plants."""
+The float64 reference and its componentwise bound are kernel_checks.attn_bwd_ref; `rounds` says which of its two forms holds the kernel of
+a head width.  `emulate` is the kernels' arithmetic in fp32 on the CPU, with the faults the host tests plant."""
 import torch
 
 import kernel_checks as kc
-from kernel_checks import C_ACC, LIBM_ABS, U8, U24
 
 # (B, H, N, Dh): the smallest shapes at which the kernels can go wrong (one wave per 16 rows, 16 columns per step, 32 in the 32-wide form)
 SHAPES = [
@@ -53,92 +49,68 @@ def attn_case(B, H, N, Dh, large=False, seed=None):
     return bf(qkv), bf(torch.randn(B, H, N, Dh, generator=g))
 
 
+def split(qkv):
+    """rows [B N, 3 C] = Q | K | V -> (q [B N, C], kv [B N, 2 C])"""
+    C = qkv.shape[1] // 3
+    return qkv[:, :C], qkv[:, C:]
+
+
 def heads(z, B, H, N, Dh):
     """rows [B N, H Dh] -> [B, H, N, Dh]"""
     return z.reshape(B, N, H, Dh).permute(0, 2, 1, 3)
 
 
-def scores64(qkv, B, H, N, Dh):
+def scores64(q, kv, B, H, Nq, Nk, Dh):
+    """q rows [B Nq, H Dh], kv rows [B Nk, 2 H Dh] = K | V -> float64 logits [B, H, Nq, Nk]"""
     C = H * Dh
-    return heads(qkv[:, :C].double(), B, H, N, Dh) @ heads(qkv[:, C:2 * C].double(), B, H, N, Dh).transpose(-1, -2) * Dh ** -0.5
+    return heads(q.double(), B, H, Nq, Dh) @ heads(kv[:, :C].double(), B, H, Nk, Dh).transpose(-1, -2) * Dh ** -0.5
 
 
-def forward_o(qkv, B, H, N, Dh):
-    """The saved forward output as the kernels form it, on the CPU: bf16(bf16(P) V) -> bf16 [B, H, N, Dh]."""
+def forward_o(q, kv, B, H, Nq, Nk, Dh):
+    """The saved forward output as the kernels form it, on the CPU: bf16(bf16(P) V) -> bf16 [B, H, Nq, Dh]."""
     C = H * Dh
-    P = torch.softmax(scores64(qkv, B, H, N, Dh), -1)
-    return bf(bf(P).double() @ heads(qkv[:, 2 * C:].double(), B, H, N, Dh))
+    P = torch.softmax(scores64(q, kv, B, H, Nq, Nk, Dh), -1)
+    return bf(bf(P).double() @ heads(kv[:, C:].double(), B, H, Nk, Dh))
 
 
-def attn_bwd_ref(qkv, o, do, B, H, N, Dh=64, rounded=True):
-    """float64 from the bf16 operands: -> dict of references and of componentwise bounds, [B, H, N, Dh] each."""
+def check(got, q, kv, o, do, B, H, Nq, Nk, Dh, what, rounded=None):
+    """got: {'dq' rows [B Nq, H Dh], 'dk', 'dv' rows [B Nk, H Dh]} (any device) -> worst err / tol; fails naming the output."""
     C = H * Dh
-    hd = lambda z: z.double().view(B, N, H, Dh).permute(0, 2, 1, 3)
-    q, k, v = hd(qkv[:, :C]), hd(qkv[:, C:2 * C]), hd(qkv[:, 2 * C:])
-    o6, g6 = o.double(), do.double()
-    sc = Dh ** -0.5
-    s = q @ k.transpose(-1, -2) * sc
-    L = torch.logsumexp(s, -1, keepdim=True)
-    P = torch.exp(s - L)
-    D = (g6 * o6).sum(-1, keepdim=True)
-    dP = g6 @ v.transpose(-1, -2)
-    dS = P * (dP - D)
-    ref = {"dq": dS @ k * sc, "dk": dS.transpose(-1, -2) @ q * sc, "dv": P.transpose(-1, -2) @ g6}
-    # bound: kernel_checks.attn_bwd_ref's, term by term, with Dh for 64.  s and dP: fp32 MFMA sums of Dh terms; the exponent s - L carries
-    # that of s twice + 8 x 2^-24 (|s| + |L|) + expf / logf; D: a Dh-term fp32 sum.  dS in fp32: P e_arg |dP - D| + P (e_dP + e_D) +
-    # 2 x 2^-24 |dS|; rounded to bf16 (u8 = 2^-8) or kept (u8 = 0), and P likewise for dV.  Second products: C_ACC N 2^-24 |.||.| each,
-    # the scale in fp32 (dq, dk), and the bf16 output 2^-8 |ref|.
-    u8 = U8 if rounded else 0.0
-    acc = C_ACC * Dh * U24
-    e_arg = 2 * acc * (q.abs() @ k.abs().transpose(-1, -2)) * sc + 8 * U24 * (s.abs() + L.abs()) + 4 * LIBM_ABS
-    e_dP = acc * (g6.abs() @ v.abs().transpose(-1, -2))
-    e_D = acc * (g6.abs() * o6.abs()).sum(-1, keepdim=True)
-    e_dS = P * e_arg * (dP - D).abs() + P * (e_dP + e_D) + (2 * U24 + u8) * dS.abs()
-    e_P = P * e_arg + u8 * P
-    acc2 = C_ACC * N * U24
-    tol = {"dq": sc * (e_dS @ k.abs() + acc2 * (dS.abs() @ k.abs())) + (U8 + 2 * U24) * ref["dq"].abs(),
-           "dk": sc * (e_dS.transpose(-1, -2) @ q.abs() + acc2 * (dS.abs().transpose(-1, -2) @ q.abs())) + (U8 + 2 * U24) * ref["dk"].abs(),
-           "dv": e_P.transpose(-1, -2) @ g6.abs() + acc2 * (P.transpose(-1, -2) @ g6.abs()) + (U8 + U24) * ref["dv"].abs()}
-    return ref, tol
-
-
-def check(got, qkv, o, do, B, H, N, Dh, what, rounded=None):
-    """got: {'dq', 'dk', 'dv'} as rows [B N, H Dh] (any device) -> worst err / tol; fails naming the output."""
-    ref, tol = attn_bwd_ref(qkv.cpu(), o.cpu(), do.cpu(), B, H, N, Dh, rounds(Dh) if rounded is None else rounded)
-    return max(kc.assert_elementwise(heads(got[nm].cpu(), B, H, N, Dh), ref[nm], tol[nm], "%s %s" % (what, nm)) for nm in ("dq", "dk", "dv"))
+    kv = kv.cpu()
+    ref, tol = kc.attn_bwd_ref(q.cpu(), kv[:, :C], kv[:, C:], o.cpu(), do.cpu(), B, H, Nq, Nk, Dh, rounds(Dh) if rounded is None else rounded)
+    n = {"dq": Nq, "dk": Nk, "dv": Nk}
+    return max(kc.assert_elementwise(heads(got[nm].cpu(), B, H, n[nm], Dh), ref[nm], tol[nm], "%s %s" % (what, nm)) for nm in ("dq", "dk", "dv"))
 
 
 FAULTS = ("last key dropped from dq", "last query dropped from dk dv", "scale 1/8", "D not subtracted", "dO permuted", "L of the next head",
-          "rows past N not masked")
+          "rows past N not masked", "stats of Nk rows")
 
 
-def emulate(qkv, o, do, B, H, N, Dh, rounded, fault=None):
+def emulate(q, kv, o, do, B, H, Nq, Nk, Dh, rounded, fault=None):
     """The kernels' arithmetic in fp32: fp32 products, fp32 L and D, P and dS rounded to bf16 or not, bf16 outputs.
-    -> {'dq', 'dk', 'dv'} bf16 rows [B N, H Dh].  fault: one of FAULTS."""
+    -> {'dq' rows [B Nq, H Dh], 'dk', 'dv' rows [B Nk, H Dh]} bf16.  fault: one of FAULTS; "stats of Nk rows": L and D looked up as if the
+    statistics buffer held Nk rows per head (the self-attention indexing)."""
     assert fault is None or fault in FAULTS
     C = H * Dh
-    hd = lambda z: z.float().view(B, N, H, Dh).permute(0, 2, 1, 3)
-    q, k, v = hd(qkv[:, :C]), hd(qkv[:, C:2 * C]), hd(qkv[:, 2 * C:])
+    q4, k, v = heads(q.float(), B, H, Nq, Dh), heads(kv[:, :C].float(), B, H, Nk, Dh), heads(kv[:, C:].float(), B, H, Nk, Dh)
     o32 = o.float()
-    g32 = do.float().reshape(B, N, H, Dh).permute(0, 2, 1, 3) if fault == "dO permuted" else do.float()
+    g32 = do.float().reshape(B, Nq, H, Dh).permute(0, 2, 1, 3) if fault == "dO permuted" else do.float()
     sc = 0.125 if fault == "scale 1/8" else float(torch.tensor(float(Dh)).rsqrt())
-    if fault == "rows past N not masked":                   # a block of 16 rows whose rows >= N re-read the last one and are NOT given weight 0
-        pad = lambda z: torch.cat([z, z[:, :, -1:].expand(-1, -1, 16 - N % 16, -1)], 2) if N % 16 else z
-        L = torch.logsumexp(q @ k.transpose(-1, -2) * sc, -1, keepdim=True)
-        D = (g32 * o32).sum(-1, keepdim=True)
-        q, k, v, g32, L, D = pad(q), pad(k), pad(v), pad(g32), pad(L), pad(D)
-        s = q @ k.transpose(-1, -2) * sc
-    else:
-        s = q @ k.transpose(-1, -2) * sc
-        L = torch.logsumexp(s, -1, keepdim=True)
-        D = (g32 * o32).sum(-1, keepdim=True)
+    L = torch.logsumexp(q4 @ k.transpose(-1, -2) * sc, -1, keepdim=True)
+    D = (g32 * o32).sum(-1, keepdim=True)
+    if fault == "rows past N not masked":                   # a block of 16 rows whose rows past the end re-read the last one and are NOT given weight 0
+        pad = lambda z, n: torch.cat([z, z[:, :, -1:].expand(-1, -1, 16 - n % 16, -1)], 2) if n % 16 else z
+        q4, g32, L, D, k, v = pad(q4, Nq), pad(g32, Nq), pad(L, Nq), pad(D, Nq), pad(k, Nk), pad(v, Nk)
+    if fault == "stats of Nk rows":
+        flat = lambda z: z.reshape(-1)[(torch.arange(B * H)[:, None] * Nk + torch.arange(Nq)[None]).reshape(-1) % (B * H * Nq)].view(B, H, Nq, 1)
+        L, D = flat(L), flat(D)
     if fault == "L of the next head":
         L = L.roll(1, 1)
-    P = torch.exp(s - L)
+    P = torch.exp(q4 @ k.transpose(-1, -2) * sc - L)
     dS = P * (g32 @ v.transpose(-1, -2) - (0 if fault == "D not subtracted" else D))
     if rounded:
         P, dS = bf(P).float(), bf(dS).float()
     dSq, kq = (dS[..., :-1], k[:, :, :-1]) if fault == "last key dropped from dq" else (dS, k)
-    Pk, dSk, qk, gk = (P[:, :, :-1], dS[:, :, :-1], q[:, :, :-1], g32[:, :, :-1]) if fault == "last query dropped from dk dv" else (P, dS, q, g32)
-    out = {"dq": dSq @ kq * sc, "dk": dSk.transpose(-1, -2) @ qk * sc, "dv": Pk.transpose(-1, -2) @ gk}
-    return {nm: bf(z[:, :, :N]).permute(0, 2, 1, 3).reshape(B * N, C) for nm, z in out.items()}
+    Pk, dSk, qk, gk = (P[:, :, :-1], dS[:, :, :-1], q4[:, :, :-1], g32[:, :, :-1]) if fault == "last query dropped from dk dv" else (P, dS, q4, g32)
+    out = {"dq": (dSq @ kq * sc)[:, :, :Nq], "dk": (dSk.transpose(-1, -2) @ qk * sc)[:, :, :Nk], "dv": (Pk.transpose(-1, -2) @ gk)[:, :, :Nk]}
+    return {nm: bf(z).permute(0, 2, 1, 3).reshape(-1, C) for nm, z in out.items()}

@@ -1,6 +1,6 @@
-"""GPU (-m gpu): the cross-attention backward alone, per element (ldt_attention_bwd_cross: csrc/attention_bwd.hip at head widths 32 and 64,
-csrc/attention_narrow_bwd.hip at 8 and 16, with Nq query rows and Nk key rows).  Helpers, shapes and the bound: tests/cross_bwd_checks.py
-(kernel_checks.attn_bwd_ref's bound with the two lengths apart; test_train_cond_host.py ties it to kernel_checks without a GPU).
+"""GPU (-m gpu): the cross-attention backward alone, per element (ldt_attention_bwd_cross: csrc/attention_bwd.hip, the MFMA form at
+head widths 32 and 64, the narrow form at 8 and 16, with Nq query rows and Nk key rows).  Shapes and operands: tests/cross_bwd_checks.py;
+the bound: kernel_checks.attn_bwd_ref with the two lengths apart (test_train_cond_host.py holds it without a GPU, planted faults included).
 
   * every output element against float64 from the very bf16 operands, inside the componentwise bound; two launches bit-equal
   * at Nq = Nk the same bits as ops.attention_bwd, at all four head widths
@@ -34,12 +34,12 @@ def test_attention_bwd_cross_per_element(B, H, Nq, Nk, Dh, large):
     from ldt_amd import ops
     q, kv, do, q_d, k, v, o, do_d = operands(B, H, Nq, Nk, Dh, large)
     if large:
-        s = cb.scores64(q, kv, B, H, Nq, Nk, Dh)
+        s = nb.scores64(q, kv, B, H, Nq, Nk, Dh)
         assert float(s.amax(-1).min()) > 25 and float(s.amax(-1).max()) > 89       # past fp32 exp's range
     dq, dk, dv = ops.attention_bwd_cross(q_d, k, v, o, do_d, B, H, Nq, Nk, Dh)
     assert tuple(dq.shape) == (B * Nq, H * Dh) and tuple(dk.shape) == tuple(dv.shape) == (B * Nk, H * Dh)
     assert dk.data_ptr() + 2 * H * Dh == dv.data_ptr() and dk.stride(0) == dv.stride(0) == 2 * H * Dh       # the halves of one [B Nk, 2 C] tensor
-    r = cb.check({"dq": dq, "dk": dk, "dv": dv}, q, kv, o, do, B, H, Nq, Nk, Dh,
+    r = nb.check({"dq": dq, "dk": dk, "dv": dv}, q, kv, o, do, B, H, Nq, Nk, Dh,
                  "attention_bwd_cross B%d H%d Nq%d Nk%d Dh%d large=%d" % (B, H, Nq, Nk, Dh, large))
     print("train-kernel attention_bwd_cross B%d H%d Nq%d Nk%d Dh%d large=%d (P, dS %s)  max err/tol %.3f"
           % (B, H, Nq, Nk, Dh, large, "bf16" if nb.rounds(Dh) else "fp32", r))
@@ -69,7 +69,7 @@ def test_exact_selection_probe_on_dv(B, H, Nq, Nk, Dh):
     from ldt_amd import ops
     C = H * Dh
     q, kv, do, pi, lead = cb.selection_probe(B, H, Nq, Nk, Dh, seed=31 + Nq + Nk + Dh)
-    s = cb.scores64(q, kv, B, H, Nq, Nk, Dh)
+    s = nb.scores64(q, kv, B, H, Nq, Nk, Dh)
     top2 = s.topk(min(2, Nk), -1).values
     assert torch.equal(s.argmax(-1), pi) and (Nk == 1 or float((top2[..., 0] - top2[..., 1]).min()) >= 110)
     q_d, kv_d, do_d = q.cuda(), kv.cuda(), do.cuda()

@@ -216,7 +216,7 @@ def test_attention_bwd(B, H, N, large):
     q, k, v = qkv_d[:, :C], qkv_d[:, C:2 * C], qkv_d[:, 2 * C:]
     o = ops.attention_fwd(q, k, v, B, H, N, N, 64)                                    # the saved forward output, as training keeps it
     dq, dk, dv = ops.attention_bwd(q, k, v, o, do_d, B, H, N)
-    ref, tol = attn_bwd_ref(qkv, o.cpu(), do, B, H, N)
+    ref, tol = attn_bwd_ref(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], o.cpu(), do, B, H, N, N)
     if large:
         s = (qkv[:, :C].double().view(B, N, H, 64).permute(0, 2, 1, 3) @ qkv[:, C:2 * C].double().view(B, N, H, 64).permute(0, 2, 3, 1)) / 8
         assert float(s.amax(-1).min()) > 40 and float(s.amax(-1).max()) > 89      # past fp32 exp's range

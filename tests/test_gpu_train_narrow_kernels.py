@@ -1,6 +1,6 @@
-"""GPU (-m gpu): the attention backward at head widths 8, 16 and 32 alone, per element (ldt_attention_bwd_narrow: csrc/attention_narrow_bwd.hip
-for 8 and 16, csrc/attention_bwd.hip instantiated at 32).  Helpers, shapes and the bound: tests/narrow_bwd_checks.py (validated without a GPU,
-planted faults included, by test_train_narrow_host.py).
+"""GPU (-m gpu): the attention backward at head widths 8, 16 and 32 alone, per element (ldt_attention_bwd_narrow: csrc/attention_bwd.hip, the
+narrow form for 8 and 16, the MFMA form instantiated at 32).  Helpers and shapes: tests/narrow_bwd_checks.py; the bound:
+kernel_checks.attn_bwd_ref (validated without a GPU, planted faults included, by test_train_narrow_host.py).
 
 Every case is compared with float64 computed from the very bf16 inputs the kernel read (O from ops.attention_fwd, as training keeps it), with
 kernel_checks.assert_elementwise: err / tol <= 1 for every element of dq, dk and dv.  Then the layout: a second call gives the same bits, a
@@ -29,11 +29,11 @@ def test_attention_bwd_narrow_per_element(B, H, N, Dh, large):
     from ldt_amd import ops
     qkv, do, q, k, v, o, do_d = operands(B, H, N, Dh, large)
     if large:
-        s = nb.scores64(qkv, B, H, N, Dh)
+        s = nb.scores64(*nb.split(qkv), B, H, N, N, Dh)
         assert float(s.amax(-1).min()) > 25 and float(s.amax(-1).max()) > 89      # a backward without the recomputed maximum overflows
     dq, dk, dv = ops.attention_bwd(q, k, v, o, do_d, B, H, N, head_dim=Dh)
     assert dq.shape == dk.shape == dv.shape == (B * N, H * Dh) and dq.dtype == torch.bfloat16
-    r = nb.check({"dq": dq, "dk": dk, "dv": dv}, qkv, o, do, B, H, N, Dh, "attention_bwd B%d H%d N%d Dh%d large=%d" % (B, H, N, Dh, large))
+    r = nb.check({"dq": dq, "dk": dk, "dv": dv}, *nb.split(qkv), o, do, B, H, N, N, Dh, "attention_bwd B%d H%d N%d Dh%d large=%d" % (B, H, N, Dh, large))
     print("train-kernel attention_bwd B%d H%d N%d Dh%d large=%d (P, dS %s)  max err/tol %.3f" % (B, H, N, Dh, large, "bf16" if nb.rounds(Dh) else "fp32", r))
     dq2, dk2, dv2 = ops.attention_bwd(q, k, v, o, do_d, B, H, N, head_dim=Dh)
     assert torch.equal(dq2, dq) and torch.equal(dk2, dk) and torch.equal(dv2, dv)     # fixed order: the same bits

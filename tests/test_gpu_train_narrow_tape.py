@@ -1,5 +1,5 @@
 """GPU (-m gpu): a whole Score backward at head widths 8, 16 and 32 audited call by call (tests/train_tape.py, imported as it is; the
-attention call by tests/narrow_bwd_checks.py).
+attention call by kernel_checks.attn_bwd_ref at the call's own head width).
 
 `ScoreTrainStep` is driven under train_tape.Tape as test_gpu_train_tape.py drives it, on the hybrid config's layout (hidden 128, 16 heads,
 T = 32) and three more.  train_tape's own attention reference and its wiring table are written for 64-wide heads, so here
@@ -70,8 +70,7 @@ def run_case(tiny_cfg, name, edit=None, key=None):
 def check_attention_call(call):
     a = call.arg
     B, H, N, Dh = a("B"), a("H"), a("N"), a("head_dim")
-    qkv = torch.cat([a("q"), a("k"), a("v")], 1)
-    ref, tol = nb.attn_bwd_ref(qkv, a("o").reshape(B, H, N, Dh), a("do").reshape(B, H, N, Dh), B, H, N, Dh, nb.rounds(Dh))
+    ref, tol = kc.attn_bwd_ref(a("q"), a("k"), a("v"), a("o").reshape(B, H, N, Dh), a("do").reshape(B, H, N, Dh), B, H, N, N, Dh, nb.rounds(Dh))
     return {"attention_bwd " + k: kc.assert_elementwise(nb.heads(call.out(i), B, H, N, Dh), ref[k], tol[k], "%s, %s" % (call, k))
             for i, k in enumerate(("dq", "dk", "dv"))}
 

@@ -1,5 +1,5 @@
 """Host checks (no GPU) for Score training on a ViPC condition pair: the cross-attention backward's reference and bound
-(tests/cross_bwd_checks.py) against kernel_checks' and narrow_bwd_checks' at Nq = Nk, an fp32 emulation of the kernels with planted faults,
+(kernel_checks.attn_bwd_ref at two lengths, on the cases of tests/cross_bwd_checks.py), an fp32 emulation of the kernels with planted faults,
 the argument checks of ldt_attention_bwd_cross, the refusals of `CompletionTrainer`, and the fixture tests/golden/score_train_cond.npz
 against the oracle (tests/train_cond_checks.py)."""
 import copy
@@ -9,39 +9,21 @@ import pytest
 import torch
 
 import cross_bwd_checks as cb
-import kernel_checks as kc
 import narrow_bwd_checks as nb
 import train_cond_checks as tc
 
 
 # ------------------------------------------------------------------------------------------------ the reference and its bound
-@pytest.mark.parametrize("B,H,N,Dh", cb.SQUARE + [(1, 2, 72, 64)])
-def test_cross_reference_is_the_self_attention_one_at_equal_lengths(B, H, N, Dh):
-    """Bit for bit narrow_bwd_checks.attn_bwd_ref in both forms, and at 64 kernel_checks.attn_bwd_ref: the bound is imported, not restated."""
-    C = H * Dh
-    qkv, do = nb.attn_case(B, H, N, Dh)
-    o = nb.forward_o(qkv, B, H, N, Dh)
-    q, kv = qkv[:, :C].contiguous(), qkv[:, C:].contiguous()
-    for rounded in (True, False):
-        ref, tol = cb.attn_bwd_cross_ref(q, kv, o, do, B, H, N, N, Dh, rounded)
-        ref0, tol0 = nb.attn_bwd_ref(qkv, o, do, B, H, N, Dh, rounded)
-        assert all(torch.equal(ref[nm], ref0[nm]) and torch.equal(tol[nm], tol0[nm]) for nm in ("dq", "dk", "dv"))
-    if Dh == 64:
-        ref, tol = cb.attn_bwd_cross_ref(q, kv, o, do, B, H, N, N, 64, True)
-        ref0, tol0 = kc.attn_bwd_ref(qkv, o, do, B, H, N)
-        assert all(torch.equal(ref[nm], ref0[nm]) and torch.equal(tol[nm], tol0[nm]) for nm in ("dq", "dk", "dv"))
-
-
 @pytest.mark.parametrize("B,H,Nq,Nk,Dh,large", cb.CASES)
 def test_emulation_is_inside_the_bound(B, H, Nq, Nk, Dh, large):
     """fp32 products, fp32 L and D, bf16 outputs: inside the bound in the form the kernel of that width takes, at every shape the GPU test runs."""
     q, kv, do = cb.cross_case(B, H, Nq, Nk, Dh, large)
-    o = cb.forward_o(q, kv, B, H, Nq, Nk, Dh)
-    r = cb.check(cb.emulate(q, kv, o, do, B, H, Nq, Nk, Dh, nb.rounds(Dh)), q, kv, o, do, B, H, Nq, Nk, Dh, "emulation")
+    o = nb.forward_o(q, kv, B, H, Nq, Nk, Dh)
+    r = nb.check(nb.emulate(q, kv, o, do, B, H, Nq, Nk, Dh, nb.rounds(Dh)), q, kv, o, do, B, H, Nq, Nk, Dh, "emulation")
     print("emulation B%d H%d Nq%d Nk%d Dh%d large=%d: err / tol %.3f" % (B, H, Nq, Nk, Dh, large, r))
     assert r <= 1.0
     if large:
-        s = cb.scores64(q, kv, B, H, Nq, Nk, Dh)
+        s = nb.scores64(q, kv, B, H, Nq, Nk, Dh)
         assert float(s.amax(-1).min()) > 25 and float(s.amax(-1).max()) > 89
 
 
@@ -56,23 +38,23 @@ def test_emulation_is_inside_the_bound(B, H, Nq, Nk, Dh, large):
 ])
 def test_planted_faults_fail_naming_the_output(fault, B, H, Nq, Nk, Dh, output):
     q, kv, do = cb.cross_case(B, H, Nq, Nk, Dh)
-    o = cb.forward_o(q, kv, B, H, Nq, Nk, Dh)
+    o = nb.forward_o(q, kv, B, H, Nq, Nk, Dh)
     with pytest.raises(AssertionError, match=r"planted %s: \d+ of \d+ elements outside the bound" % output):
-        cb.check(cb.emulate(q, kv, o, do, B, H, Nq, Nk, Dh, nb.rounds(Dh), fault=fault), q, kv, o, do, B, H, Nq, Nk, Dh, "planted")
+        nb.check(nb.emulate(q, kv, o, do, B, H, Nq, Nk, Dh, nb.rounds(Dh), fault=fault), q, kv, o, do, B, H, Nq, Nk, Dh, "planted")
 
 
 @pytest.mark.parametrize("B,H,Nq,Nk,Dh", cb.PROBES)
 def test_selection_probe_is_exact_in_the_emulation(B, H, Nq, Nk, Dh):
     q, kv, do, pi, lead = cb.selection_probe(B, H, Nq, Nk, Dh, seed=31 + Nq + Nk + Dh)
-    s = cb.scores64(q, kv, B, H, Nq, Nk, Dh)
+    s = nb.scores64(q, kv, B, H, Nq, Nk, Dh)
     top2 = s.topk(2, -1).values
     assert lead >= 110 and torch.equal(s.argmax(-1), pi) and float((top2[..., 0] - top2[..., 1]).min()) >= 110
     assert all(len(set(row.tolist())) == Nq for row in pi.reshape(-1, Nq))            # every key wins at most one query
-    o = cb.forward_o(q, kv, B, H, Nq, Nk, Dh)
+    o = nb.forward_o(q, kv, B, H, Nq, Nk, Dh)
     want = cb.selection_expected_dv(do, pi, B, H, Nq, Nk, Dh)
     for rounded in (True, False):
-        assert torch.equal(cb.emulate(q, kv, o, do, B, H, Nq, Nk, Dh, rounded)["dv"], want)
-    moved = cb.emulate(q, kv, o, do, B, H, Nq, Nk, Dh, True, fault="last query dropped from dk dv")["dv"]
+        assert torch.equal(nb.emulate(q, kv, o, do, B, H, Nq, Nk, Dh, rounded)["dv"], want)
+    moved = nb.emulate(q, kv, o, do, B, H, Nq, Nk, Dh, True, fault="last query dropped from dk dv")["dv"]
     assert not torch.equal(moved, want)
 
 

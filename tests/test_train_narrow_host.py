@@ -1,5 +1,5 @@
-"""Host checks (no GPU) for Score training at head widths 8, 16 and 32: the generalised attention-backward reference and bound
-(tests/narrow_bwd_checks.py) against kernel_checks' at 64, an fp32 emulation of the kernels with planted faults, the argument checks of
+"""Host checks (no GPU) for Score training at head widths 8, 16 and 32: the two forms of the attention-backward bound
+(kernel_checks.attn_bwd_ref), an fp32 emulation of the kernels with planted faults (tests/narrow_bwd_checks.py), the argument checks of
 ldt_attention_bwd_narrow, refuse_untrainable, and the fixture tests/golden/score_train_narrow.npz against the oracle."""
 import pytest
 import torch
@@ -11,19 +11,19 @@ import train_narrow_checks as tn
 
 @pytest.mark.parametrize("B,H,N,large", [(2, 2, 8, False), (1, 2, 72, True)])
 def test_generalised_reference_is_kernel_checks_at_64(B, H, N, large):
+    """The one reference (kernel_checks.attn_bwd_ref) in its two forms: only the bound differs."""
     qkv, do = nb.attn_case(B, H, N, 64, large)
-    o = nb.forward_o(qkv, B, H, N, 64)
-    ref, tol = nb.attn_bwd_ref(qkv, o, do, B, H, N, 64, rounded=True)
-    ref0, tol0 = kc.attn_bwd_ref(qkv, o, do, B, H, N)
-    for nm in ("dq", "dk", "dv"):
-        assert torch.equal(ref[nm], ref0[nm]) and torch.equal(tol[nm], tol0[nm]), nm
-    _, tol_fp32 = nb.attn_bwd_ref(qkv, o, do, B, H, N, 64, rounded=False)          # without the 2^-8 terms the bound is smaller
+    (q, kv), C = nb.split(qkv), H * 64
+    o = nb.forward_o(q, kv, B, H, N, N, 64)
+    ref, tol = kc.attn_bwd_ref(q, kv[:, :C], kv[:, C:], o, do, B, H, N, N, 64, rounded=True)
+    ref_fp32, tol_fp32 = kc.attn_bwd_ref(q, kv[:, :C], kv[:, C:], o, do, B, H, N, N, 64, rounded=False)   # without the 2^-8 terms the bound is smaller
+    assert all(torch.equal(ref_fp32[nm], ref[nm]) for nm in ("dq", "dk", "dv"))
     assert all(bool((tol_fp32[nm] <= tol[nm]).all()) and bool((tol_fp32[nm] < tol[nm]).any()) for nm in ("dq", "dk", "dv"))
 
 
 def test_large_logit_cases_need_the_row_maximum():
     for B, H, N, Dh in nb.LARGE:
-        s = nb.scores64(nb.attn_case(B, H, N, Dh, True)[0], B, H, N, Dh)
+        s = nb.scores64(*nb.split(nb.attn_case(B, H, N, Dh, True)[0]), B, H, N, N, Dh)
         assert float(s.amax(-1).min()) > 25 and float(s.amax(-1).max()) > 89       # past fp32 exp's range
 
 
@@ -31,9 +31,10 @@ def test_large_logit_cases_need_the_row_maximum():
 def test_emulation_is_inside_the_bound(B, H, N, Dh, large):
     """fp32 products, fp32 L and D, bf16 outputs: inside the bound in both forms, at every shape the GPU test runs."""
     qkv, do = nb.attn_case(B, H, N, Dh, large)
-    o = nb.forward_o(qkv, B, H, N, Dh)
+    q, kv = nb.split(qkv)
+    o = nb.forward_o(q, kv, B, H, N, N, Dh)
     for rounded in (True, False):
-        r = nb.check(nb.emulate(qkv, o, do, B, H, N, Dh, rounded), qkv, o, do, B, H, N, Dh, "emulation", rounded=rounded)
+        r = nb.check(nb.emulate(q, kv, o, do, B, H, N, N, Dh, rounded), q, kv, o, do, B, H, N, N, Dh, "emulation", rounded=rounded)
         print("emulation B%d H%d N%d Dh%d large=%d rounded=%d: err / tol %.3f" % (B, H, N, Dh, large, rounded, r))
         assert r <= 1.0
 
@@ -51,11 +52,12 @@ def test_emulation_is_inside_the_bound(B, H, N, Dh, large):
 ])
 def test_planted_faults_fail_naming_the_output(fault, B, H, N, Dh, output):
     qkv, do = nb.attn_case(B, H, N, Dh)
-    o = nb.forward_o(qkv, B, H, N, Dh)
+    q, kv = nb.split(qkv)
+    o = nb.forward_o(q, kv, B, H, N, N, Dh)
     rounded = nb.rounds(Dh)
-    assert nb.check(nb.emulate(qkv, o, do, B, H, N, Dh, rounded), qkv, o, do, B, H, N, Dh, "sound") <= 1.0
+    assert nb.check(nb.emulate(q, kv, o, do, B, H, N, N, Dh, rounded), q, kv, o, do, B, H, N, N, Dh, "sound") <= 1.0
     with pytest.raises(AssertionError, match=r"planted %s: \d+ of \d+ elements outside the bound" % output):
-        nb.check(nb.emulate(qkv, o, do, B, H, N, Dh, rounded, fault=fault), qkv, o, do, B, H, N, Dh, "planted")
+        nb.check(nb.emulate(q, kv, o, do, B, H, N, N, Dh, rounded, fault=fault), q, kv, o, do, B, H, N, N, Dh, "planted")
 
 
 def test_narrow_entry_point_returns_argument_errors():

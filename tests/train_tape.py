@@ -227,9 +227,8 @@ def check_call(call):
         return {nm: E(call.out(), ref, tol, str(call))}
     if nm == "attention_bwd":
         B, H, N = a("B"), a("H"), a("N")
-        qkv = torch.cat([a("q"), a("k"), a("v")], 1)
         # o and do: the raw [B][H][N][64] buffers (quirk Q1), whatever shape they were handed over in
-        ref, tol = kc.attn_bwd_ref(qkv, a("o").reshape(B, H, N, 64), a("do").reshape(B, H, N, 64), B, H, N)
+        ref, tol = kc.attn_bwd_ref(a("q"), a("k"), a("v"), a("o").reshape(B, H, N, 64), a("do").reshape(B, H, N, 64), B, H, N, N)
         return {"attention_bwd " + k: E(_heads(call.out(i), B, N, H), ref[k], tol[k], "%s, %s" % (call, k)) for i, k in enumerate(("dq", "dk", "dv"))}
     raise AssertionError("%s: a call kind the audit has no reference for" % call)
 
