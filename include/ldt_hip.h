@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define LDT_ABI_VERSION 25
+#define LDT_ABI_VERSION 26
 #define LDT_OK 0
 #define LDT_EARG (-1)    /* null / inconsistent argument */
 #define LDT_ESHAPE (-2)  /* unsupported shape */
@@ -592,9 +592,6 @@ int ldt_dbg_gemm_group_m(int32_t rows_per_group);
 /* tools/dbg/epi_ablate.py: skip parts of the residual epilogue (bit 1 residual read, 2 fp32 store, 4 bf16 x(1+scale) store,
  * 8 row statistics) to attribute its time; -1 restores the product behaviour.  Process-wide; not used by the product path. */
 int ldt_dbg_gemm_epi(int32_t bits);
-/* tools/dbg + tests: 1 = every 256-tile GEMM launch without a fragment-order weight copy packs one on the fly (cached by pointer and
- * shape, never invalidated) and runs the W-from-registers form; 0 = that form off; -1 restores the product behaviour.  Process-wide. */
-int ldt_dbg_gemm_wreg(int32_t on);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDT_HIP_LIB", os.path.join(_HERE, "libldt_hip.so"))   # override: debug builds only
-ABI_VERSION = 25
+ABI_VERSION = 26
 MAX_BLOCKS = 64
 ODE_SUMSQ_SCRATCH = 1024        # LDT_ODE_SUMSQ_SCRATCH
 
@@ -131,7 +131,6 @@ SIGNATURES = {
     "ldt_score_forward_profile": [C.POINTER(ScorePlan), _vp, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), _vp],
     "ldt_dbg_gemm_group_m": [_i32],
     "ldt_dbg_gemm_epi": [_i32],
-    "ldt_dbg_gemm_wreg": [_i32],
     "ldt_sample_loop": [C.POINTER(ScorePlan), _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _u64, _vp, _i32, C.POINTER(CondArgs), _vp, _i32, _vp],
 }
 

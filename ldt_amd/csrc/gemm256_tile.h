@@ -374,15 +374,14 @@ struct KTileLanes {
 };
 
 // One K-tile out of buffer `st`: phase PH = 2 * k-half + m-half multiplies the k-half's NF W fragments with X m-tiles [4 m-half, +4).
-//   request(Phase<PH>)   before the phase's first barrier, behind its LDS reads: the caller's DMA / register-load requests and counted wait
-//   wregs(Phase<PH>, wf) W_LDS = false only, behind that barrier in p0 / p2: hands over the k-half's fragments (loaded by the caller)
+//   request(Phase<PH>)   before the phase's first barrier, behind its LDS reads: the caller's DMA requests and counted wait
 template <int PH> using Phase = std::integral_constant<int, PH>;
-template <int NF, bool W_LDS, class Req, class WRegs>
-__device__ __forceinline__ void ktile256(const char* st, const KTileLanes& ln, f32x4 (&acc)[NF][8], Req&& request, WRegs&& wregs) {
+template <int NF, class Req>
+__device__ __forceinline__ void ktile256(const char* st, const KTileLanes& ln, f32x4 (&acc)[NF][8], Req&& request) {
     bf16x8 wf[NF], xf[4];
     auto phase = [&](auto ph) {
         constexpr int PH = decltype(ph)::value, KH = PH >> 1, MH = PH & 1;
-        if constexpr (W_LDS && MH == 0) {
+        if constexpr (MH == 0) {
 #pragma unroll
             for (int i = 0; i < NF; ++i) wf[i] = *reinterpret_cast<const bf16x8*>(st + ln.wb[KH] + i * 2048);
         }
@@ -390,7 +389,6 @@ __device__ __forceinline__ void ktile256(const char* st, const KTileLanes& ln, f
         for (int i = 0; i < 4; ++i) xf[i] = *reinterpret_cast<const bf16x8*>(st + ln.xb[KH] + (MH * 4 + i) * 2048);
         request(ph);
         G256_BARRIER();
-        if constexpr (!W_LDS && MH == 0) wregs(ph, wf);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int ni = 0; ni < NF; ++ni)

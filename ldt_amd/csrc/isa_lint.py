@@ -45,7 +45,6 @@ GUARDED = [r"gemm_bf16_nt_256f_kernel<", r"gemm_qkv_attn256_kernel<", r"gemm_bf1
 MFMA_C_FAMILIES = [r"gemm_bf16_nt_mid_kernel<"]
 # register-destination loads issued by `asm volatile` (hipcc neither counts nor waits for them): (kernel regex, mnemonic, source site)
 ASM_LOADS = [(r"attn_fwd_head_kernel<", "global_load_dwordx4", "attention.hip: the Q fragments"),
-             (r"gemm_bf16_nt_256f_kernel<\d+, \d+, 1, 1, \d+>", "global_load_dwordx4", "gemm_256.hip WREG: the W fragment half-sets"),
              (r"gemm_bf16_nt_mid_kernel<\d+, \d+, \d+, 2, \d+>", "global_load_dwordx2", "gemm_mid.hip mid_loader: the row-statistics partials")]
 
 

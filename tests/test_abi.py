@@ -74,15 +74,36 @@ def _lint():
     return m
 
 
-def test_isa_lint_passes_on_the_built_library(built):
+@pytest.fixture(scope="module")
+def linted(built):
+    """One lint pass over the built library for every test that reads its result: (module, fingerprints, errors, kernel count)."""
+    L = _lint()
+    return (L,) + tuple(L.analyse(built.LIB_PATH))
+
+
+def test_isa_lint_passes_on_the_built_library(linted):
     """The hand-counted waits / asm loads / main-loop -> epilogue fence of the hot kernels are what was audited (csrc/isa_lint.py;
     build.sh runs the same check and fails the build on a violation)."""
-    L = _lint()
-    fps, errs, nk = L.analyse(built.LIB_PATH)
+    L, fps, errs, nk = linted
     assert not errs, errs[:5]
     gold = __import__("json").load(open(L.SIG_FILE))["kernels"]
     assert fps == gold and len(fps) > 50 and nk > 100
     assert L.analyse.tally.get("covered", 0) >= 100 and not L.analyse.tally.get("open") and not L.analyse.tally.get("violation")
+
+
+def test_gemm256_symbols_keep_five_arguments_with_a_reserved_zero(linted):
+    """bench.py composes the profiler's kernel filter as `gemm_bf16_nt_256f_kernel<epi, fold, xring, 0, klong>` and profiles/traffic.json /
+    mfma_util.json are keyed the same way: every such kernel, audited or built, has five integer template arguments, the fourth 0."""
+    L, fps, _, _ = linted
+    gold = __import__("json").load(open(L.SIG_FILE))["kernels"]
+    for where, keys in (("isa_signatures.json", gold), ("the built library", fps)):
+        names = [k for k in keys if "gemm_bf16_nt_256f_kernel<" in k]
+        assert names, where
+        for k in names:
+            m = re.search(r"gemm_bf16_nt_256f_kernel<([^<>]*)>", k)
+            assert m, (where, k)
+            args = m.group(1).split(", ")
+            assert len(args) == 5 and all(re.fullmatch(r"\d+", a) for a in args) and args[3] == "0", (where, k)
 
 
 def test_isa_lint_catches_what_it_is_for():

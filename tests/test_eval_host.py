@@ -175,7 +175,7 @@ def test_training_entry_points_are_refused_with_a_reason(tiny_cfg):
 def test_header_binding_and_abi_number_agree():
     from ldt_amd import _lib
     src = open(os.path.join(ROOT, "include", "ldt_hip.h")).read()
-    assert int(re.search(r"#define LDT_ABI_VERSION (\d+)", src).group(1)) == _lib.ABI_VERSION == 25
+    assert int(re.search(r"#define LDT_ABI_VERSION (\d+)", src).group(1)) == _lib.ABI_VERSION == 26
     decl = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     for name in ("ldt_reparam_kl", "ldt_diffuse_q", "ldt_dsm_loss", "ldt_gemm_route"):
         m = re.search(r"\bint %s\s*\((.*?)\)\s*;" % name, decl, flags=re.S)

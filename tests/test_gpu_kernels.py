@@ -575,7 +575,8 @@ def test_gemm256_variants_bit_equal(tmp_path):
     before it lands).  Same seeded problems in two child processes: plain RESID_F32 and the LN-fold producer (M = 16,384 x N = 1,024: exactly
     256 tiles), the LN-fold consumer with GELU on a multi-tile persistent shape (N = 4,096: four tiles per workgroup) and a plain bf16
     projection (N = 3,072), each launched three times (run-to-run differences would betray a race).  (Round 3 also held the round-2 operand
-    stream, removed in round 4, to the same bits; round 6 holds the W-from-registers form of the one-tile kernels to them.)"""
+    stream, removed in round 4, to the same bits; round 6 held the W-from-registers form of the one-tile kernels to them until that form
+    was retired.)"""
     import os
     import subprocess
     import sys
@@ -610,24 +611,22 @@ for rep in range(3):
 torch.save(outs, sys.argv[1])
 ''' % ROOT
     res = {}
-    # third child (round 6): the one-tile residual GEMMs with the weight operand loaded straight into registers from a fragment-order copy
-    # (gemm_256.hip WREG: asm loads, hand-counted waits, no W in LDS; LDT_GEMM_WREG=1 packs the copy on the fly) — same MFMA order, same bits
-    # fourth / fifth child (round 6): the grouped tile order of the multi-tile kernels (groups of 4 row panels by default; 8 until round 5, 1 =
+    # third / fourth child (round 6): the grouped tile order of the multi-tile kernels (groups of 4 row panels by default; 8 until round 5, 1 =
     # row-major) only permutes which workgroup computes which tile — every tile's arithmetic is the same
-    for ring, wreg, gm in (("0", "0", ""), ("1", "0", ""), ("1", "1", ""), ("1", "0", "8"), ("1", "0", "1")):
-        out = tmp_path / ("ring%s_wreg%s_gm%s.pt" % (ring, wreg, gm))
-        env = dict(os.environ, LDT_RESID_RING=ring, LDT_GEMM_WREG=wreg)
+    for ring, gm in (("0", ""), ("1", ""), ("1", "8"), ("1", "1")):
+        out = tmp_path / ("ring%s_gm%s.pt" % (ring, gm))
+        env = dict(os.environ, LDT_RESID_RING=ring)
         if gm:
             env["LDT_GEMM_GM"] = gm
         r = subprocess.run([sys.executable, "-c", child, str(out)], env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
-        res[(ring, wreg, gm)] = torch.load(out)
-    base = res[("0", "0", "")]
+        res[(ring, gm)] = torch.load(out)
+    base = res[("0", "")]
     for key, cur in res.items():
         for k in base:
-            assert torch.equal(cur[k], base[k]), "LDT_RESID_RING=%s LDT_GEMM_WREG=%s LDT_GEMM_GM=%s differs from the register-epilogue path in %s" % (key + (k,))
+            assert torch.equal(cur[k], base[k]), "LDT_RESID_RING=%s LDT_GEMM_GM=%s differs from the register-epilogue path in %s" % (key + (k,))
     assert bool(torch.isfinite(base["x1"]).all()) and float(base["x1"].abs().mean()) > 0.1 and float(base["u"].float().abs().mean()) > 0.01
-    # the five-way bit-equality anchored to a reference: the baseline's q (plain bf16 projection of xs) and u (LN-folded consumer + GELU on
+    # the four-way bit-equality anchored to a reference: the baseline's q (plain bf16 projection of xs) and u (LN-folded consumer + GELU on
     # xs and the producer's statistics) against float64 from the same operands, per element (float64 matmul on the device)
     g = torch.Generator().manual_seed(11)
     M, D, K = 16384, 1024, 1024

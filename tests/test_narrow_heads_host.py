@@ -73,7 +73,7 @@ def test_gather_probe_refuses_more_keys_than_codes():
 
 
 def test_abi_and_routes(lib):
-    assert lib.ldt_abi_version() == 25
+    assert lib.ldt_abi_version() == 26
     for B, H, Nq, Nk, dh in nh.NARROW:
         assert int(lib.ldt_attention_route(B, H, Nq, Nk, dh)) == nh.ROUTE_NARROW, (B, H, Nq, Nk, dh)
     for B, H, Nq, Nk, dh, route in nh.WIDE_ROUTES:

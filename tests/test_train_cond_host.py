@@ -65,7 +65,7 @@ def test_cross_entry_point_returns_argument_errors():
     g.build()
     from ldt_amd import _lib, ops
     lib = _lib.lib()
-    assert lib.ldt_abi_version() == 25 == _lib.ABI_VERSION
+    assert lib.ldt_abi_version() == 26 == _lib.ABI_VERSION
     assert "ldt_attention_bwd_cross" in _lib.SIGNATURES and len(_lib.SIGNATURES["ldt_attention_bwd_cross"]) == len(_lib.SIGNATURES["ldt_attention_bwd"]) + 1
     assert callable(ops.attention_bwd_cross)
     assert list(inspect.signature(ops.attention_bwd_cross).parameters) == ["q", "k", "v", "o", "do", "B", "H", "Nq", "Nk", "head_dim", "dq_out", "dkv_out"]

@@ -131,7 +131,7 @@ def test_new_entry_points_return_argument_errors():
     g.build()
     from ldt_amd import _lib
     lib = _lib.lib()
-    assert lib.ldt_abi_version() == 25
+    assert lib.ldt_abi_version() == 26
     assert lib.ldt_transpose_cast_bf16(None, 0, 8, None, 64, 8, 8, 64, None) == -1
     assert lib.ldt_transpose_cast_bf16(16, 0, 8, 16, 32, 8, 8, 64, None) == -2           # ld_dst < R_pad
     assert lib.ldt_colsum(None, 0, 8, 8, 8, None, None) == -1 and lib.ldt_colsum(16, 0, 4, 8, 8, 16, None) == -2

@@ -66,7 +66,7 @@ def test_narrow_entry_point_returns_argument_errors():
     g.build()
     from ldt_amd import _lib
     lib = _lib.lib()
-    assert lib.ldt_abi_version() == 25
+    assert lib.ldt_abi_version() == 26
     args = [16, 128, 1024, 16, 128, 16, 128, 1024, 16, 16, 16, 16, 128, 1024, 16, 128, 16, 128, 1024]
     f = lib.ldt_attention_bwd_narrow
     assert f(*([None] + args[1:]), 1, 2, 8, 8, None) == -1 and f(*(args[:10] + [None] + args[11:]), 1, 2, 8, 8, None) == -1

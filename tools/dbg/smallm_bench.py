@@ -1,6 +1,4 @@
-"""tools/dbg: the four GEMMs of a Score block at small M under each v1 tile shape (0 128x128, 1 128x64, 2 64x64) and tile order.
-The shape override LDT_GEMM_V1_SHAPE last existed at commit d634eab: point LDT_HIP_LIB at a library built from it
-(tools/dbg/build_head_variant.sh d634eab); the current library picks the shape itself (the "auto" lines)."""
+"""tools/dbg: the four GEMMs of a Score block at small M under the v1 kernel (the library picks the tile shape itself) and each tile order."""
 import os, sys, subprocess
 sys.path.insert(0, '.')
 if len(sys.argv) > 1 and sys.argv[1] == "child":
@@ -10,7 +8,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
     shapes = [("qkv", 3072, 1024, EPI_BF16), ("o", 1024, 1024, EPI_RESID_F32), ("up", 4096, 1024, EPI_GELU_BF16), ("dn", 1024, 4096, EPI_RESID_F32)]
     torch.manual_seed(0)
     for M in (2048, 1024):
-        line = "M=%d shape=%s map=%s:" % (M, os.environ.get("LDT_GEMM_V1_SHAPE", "auto"), os.environ.get("LDT_GEMM_V1_MAP", "0"))
+        line = "M=%d map=%s:" % (M, os.environ.get("LDT_GEMM_V1_MAP", "0"))
         for name, N, K, epi in shapes:
             x = torch.randn(M, K, device="cuda").bfloat16(); w = (torch.randn(N, K, device="cuda") / K ** 0.5).bfloat16()
             b = torch.randn(N, device="cuda"); gate = torch.randn(1, N, device="cuda")
@@ -31,7 +29,5 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
         print(line, flush=True)
 else:
     for mp in ("0", "1"):
-        for shape in ("-1", "0", "1", "2"):
-            env = dict(os.environ, LDT_GEMM_FORCE="128", LDT_GEMM_V1_MAP=mp)
-            if shape != "-1": env["LDT_GEMM_V1_SHAPE"] = shape
-            subprocess.run([sys.executable, __file__, "child"], env=env, stderr=subprocess.DEVNULL)
+        env = dict(os.environ, LDT_GEMM_FORCE="128", LDT_GEMM_V1_MAP=mp)
+        subprocess.run([sys.executable, __file__, "child"], env=env, stderr=subprocess.DEVNULL)
