@@ -10,7 +10,7 @@ optionally the next block's LayerNorm + first projection) and ln_linear_kernel â
   (2) exact probes, torch.equal: the LayerNorm switched off from outside (scale = -1: h == the shift rows; ln_w = 0: h == ln_b) and values where the
       kernel's GELU is exactly relu â€” integers through the whole MLP, a signed gather through W_up with a W_dn whose columns are all different,
       gated and ungated, and the GEMM probes through ln_linear and through the chained projection.
-  (3) the 8 waves x 16 rows form (LDT_MLP_RT=1) in one child process: the digests of its results == the default form's.
+  (3) repeated launches with mirror and chained projection: the digests of x, mirror and projection are the same every time (launch_digests).
 
 What no kernel-level test reached before, and the case that reaches it (CASES below, ids C-form-rps-M):
   rows_per_sample = 1 (per_token: every lane its own modulation row)     128-modgate-1-333, 128-modgate-1-4096, 128-mod-1-129, 64-modgate-1-127, 64-affmod-1-16
@@ -20,12 +20,11 @@ What no kernel-level test reached before, and the case that reaches it (CASES be
   an output with ldo > N, ln_linear and the chained projection           every case (test_randn_staged_and_housekeeping, the guarded launches)
   an affine LayerNorm together with a modulation                         128-affmod-7-127, 128-affmod-32-333, 64-affmod-1-16
   an affine LayerNorm with a gate only                                   128-affgate-16-128, 128-affgate-33-333, 64-affgate-100-333
-  the 8 waves x 16 rows form                                             test_rt1_form_bit_equal
+  the same digests launch after launch, mirror and chained projection   test_repeated_launches_same_digests
   the shipped pairs: C = 128 with rows_per_sample = 32 / 256 / 2048      128-modgate-32-4096, 128-modgate-256-4096, 128-modgate-2048-4096 (and rows_per_sample = 1)
 The helpers, an emulation that passes them and the planted faults that fail them are tested without a GPU in test_kernel_checks_host.py."""
 import collections
 import hashlib
-import json
 import time
 
 import pytest
@@ -272,12 +271,12 @@ def test_probes_exact(c):
         assert torch.equal(q.double(), rp[M // 2].expand(M, -1)), "ln_linear %s probe %s with ln_w = 0" % (name, _id(c))
 
 
-# ------------------------------------------------------------------------------------------------------------- (3) the 8 x 16 form
+# ------------------------------------------------------------------------------------------------------------- (3) launch digests
 def _digest(t):
     return hashlib.sha256(t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()).hexdigest()
 
 
-def rt_digests():
+def launch_digests():
     """One gated and one ungated randn case (with mirror and chained projection) and the gated integer probe -> {name: sha256}."""
     out = {}
     for c in (Case(128, "modgate", 33, 333, 128), Case(64, "affine", 0, 1000, 64)):
@@ -299,25 +298,11 @@ def rt_digests():
     return out
 
 
-def test_rt1_form_bit_equal():
-    """csrc/fused_mlp.hip states that the 8 waves x 16 rows form computes every row with the same arithmetic.  LDT_MLP_RT is read once per process:
-    one child process with LDT_MLP_RT=1 prints the digests of rt_digests(), which must equal this process's (default form: 4 waves x 32 rows)."""
-    import os
-    import subprocess
-    import sys
-    from conftest import ROOT
-    assert os.environ.get("LDT_MLP_RT", "") in ("", "0", "2"), "this process must run the default form"
-    here = rt_digests()
-    child = ("import sys, json, torch\nsys.path[:0] = [%r, %r]\nimport test_gpu_fused_mlp_exact as t\nfrom ldt_amd import ops\nt.ops = ops\n"
-             "torch.backends.cuda.matmul.allow_tf32 = False\nprint('DIGESTS ' + json.dumps(t.rt_digests()))\n") % (ROOT, os.path.join(ROOT, "tests"))
-    r = subprocess.run([sys.executable, "-c", child], env=dict(os.environ, LDT_MLP_RT="1"), capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("DIGESTS ")]
-    assert len(line) == 1, r.stdout[-2000:]
-    there = json.loads(line[0][8:])
-    assert there.keys() == here.keys()
-    for k in here:
-        assert there[k] == here[k], "LDT_MLP_RT=1 differs from the default form in: " + k
+def test_repeated_launches_same_digests():
+    """launch_digests() asserts inside: three launches with mirror and chained projection give identical digests, and the gated integer probe is
+    exact.  The digests themselves are what two builds of the library are compared by (a kernel refactor must reproduce every one)."""
+    d = launch_digests()
+    assert len(d) == 7 and all(len(v) == 64 for v in d.values())
 
 
 def test_zz_margins():
