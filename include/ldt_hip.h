@@ -438,6 +438,44 @@ int ldt_adam_ema_step(float* param, float* grad, float* exp_avg, float* exp_avg_
                       double beta2, double eps, double weight_decay, int32_t step, double ema_decay, int32_t ema_init,
                       const float* clip_factor, void* stream);
 
+/* ---- training the Compressor's decoder: reconstruction loss, attention backward on a long query axis, prior rows ----
+ * ldt_chamfer_nn: nearest neighbours both ways between x1 fp32 [B][n][3] (the estimated cloud) and x2 fp32 [B][m][3]: d1 [B][n] =
+ *   min_j |x1_i - x2_j|^2 with idx1 [B][n] the LOWEST j that attains it, d2 [B][m] / idx2 [B][m] likewise from x2 to x1 (chamfer3D.cu's forward).
+ *   Each distance is formed by the expression of ldt_chamfer: d1 and d2 equal its dr and dl bit for bit.
+ * ldt_cd_loss: CD_loss (evaluation/loss.py:71-78) of n1 + n2 such distances on the device: out[3] = (loss, term1, term2),
+ *   LDT_CD_L1: mean sqrt(max(d1, 0)) + mean sqrt(max(d2, 0)); LDT_CD_L2: mean d1 + mean d2.  Float64 partials in index order, one workgroup.
+ * ldt_cd_loss_bwd: upstream * d loss / d x1 -> dx1 fp32 [B][n][3] (chamfer3D.cu's backward through CD_loss, for the estimated cloud: the only
+ *   gradient the reference's reconstruction losses feed):  dx1[i] = 2 g1[i] (x1_i - x2_idx1[i]) + sum_{j : idx2[j] = i} 2 g2[j] (x1_i - x2_j),
+ *   g = upstream / (B n) or / (B m), times 1 / (2 |x1_i - x2_j|) under LDT_CD_L1.  The second term is gathered (point i scans idx2 of its cloud
+ *   with j ascending): no atomics, the same bits on every run.  Deviations from the reference: a pair at distance exactly 0 contributes
+ *   exactly 0 (its direction is zero; the reference's inf * 0 is NaN), and the l1 weight takes the distance from the difference vector
+ *   itself, to a few fp32 roundings, not from d1 / d2, whose expanded form is only absolutely accurate.  An index outside its cloud is skipped.
+ * ldt_attention_bwd_long: the contract of ldt_attention_bwd_cross for a long query axis: head_dim 32 only, 1 <= Nq <=
+ *   LDT_ATTN_BWD_LONG_MAX_QUERIES, 1 <= Nk <= 512 (the Compressor's decoder: Nq = 2048 set points on Nk = 32 latent tokens,
+ *   Compressor/layers.py:225 through model/layers.py:183-200).  Row statistics and dQ are ldt_attention_bwd_cross's kernels (the same bits
+ *   where both admit the shape).  dK / dV: one wave per (16 keys, LDT_ATTN_BWD_LONG_CHUNK queries) writes fp32 partials into scratch
+ *   [ceil(Nq / chunk)][B][Nk][2 H 32] (scratch_len floats, at least that many), and a second kernel adds them in chunk order, scales dK and
+ *   rounds to bf16: a fixed order set by the constant alone.
+ * ldt_rows_gather_sum: dprior fp32 [R][C] (dense) = sum over b, in the order of b, of dy[b N + src[b][r]][:] (dy fp32 [B N][ld]) where
+ *   src int32 [B][R] >= 0; -1 (or any index outside [0, N)) = sample b does not hold prior row r.  Backward of InitialSet's learned
+ *   prior (Compressor/layers.py:26-42); every row of dprior is written. */
+#define LDT_CD_L1 1
+#define LDT_CD_L2 2
+#define LDT_ATTN_BWD_LONG_MAX_QUERIES 8192
+#define LDT_ATTN_BWD_LONG_CHUNK 256
+int ldt_chamfer_nn(const float* x1, const float* x2, int32_t B, int32_t n, int32_t m, float* d1, int32_t* idx1, float* d2, int32_t* idx2,
+                   void* stream);
+int ldt_cd_loss(const float* d1, int64_t n1, const float* d2, int64_t n2, int32_t type, float* out, void* stream);
+int ldt_cd_loss_bwd(const float* x1, const float* x2, const int32_t* idx1, const int32_t* idx2, int32_t B, int32_t n, int32_t m, int32_t type,
+                    float upstream, float* dx1, void* stream);
+int ldt_attention_bwd_long(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk, const uint16_t* V,
+                           int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats, uint16_t* dQ,
+                           int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
+                           int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim, float* scratch,
+                           int64_t scratch_len, void* stream);
+int ldt_rows_gather_sum(const float* dy, int64_t ld, const int32_t* src, int32_t B, int32_t N, int32_t R, int32_t C, float* dprior,
+                        void* stream);
+
 /* ---- fused MLP half of a narrow ResidualBlock (the Compressor's d = 128 blocks; model/layers.py:219,226 + :110-133) ----
  * In place on x fp32 [M][ldx]:  x += gate * (W_dn . GELU(W_up . h + b_up) + b_dn),  h = LN(x) * ln_w + ln_b  (affine,
  * no-condition blocks) or LN(x) * (1 + scale) + shift (AdaLN; shift/scale/gate are per-sample vectors, sample =

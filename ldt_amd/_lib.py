@@ -8,9 +8,11 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDT_HIP_LIB", os.path.join(_HERE, "libldt_hip.so"))   # override: debug builds only
-ABI_VERSION = 26
+ABI_VERSION = 26                # (unchanged by the decoder-training entry points, which are additions: DESIGN.md section 4.15 says who raises it next)
 MAX_BLOCKS = 64
 ODE_SUMSQ_SCRATCH = 1024        # LDT_ODE_SUMSQ_SCRATCH
+CD_TYPES = {"l1": 1, "l2": 2}   # LDT_CD_L1, LDT_CD_L2
+ATTN_BWD_LONG_MAX_QUERIES, ATTN_BWD_LONG_MAX_KEYS, ATTN_BWD_LONG_CHUNK = 8192, 512, 256      # LDT_ATTN_BWD_LONG_*
 
 EPI_F32, EPI_BF16, EPI_GELU_BF16, EPI_RELU_BF16, EPI_RESID_F32 = range(5)
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_GELU = range(4)
@@ -117,6 +119,12 @@ SIGNATURES = {
                                  _i32, _i32, _i32, _i32, _vp],
     "ldt_attention_bwd_cross": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64,
                                 _i32, _i32, _i32, _i32, _i32, _vp],
+    "ldt_attention_bwd_long": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64,
+                               _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
+    "ldt_chamfer_nn": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "ldt_cd_loss": [_vp, _i64, _vp, _i64, _i32, _vp, _vp],
+    "ldt_cd_loss_bwd": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp],
+    "ldt_rows_gather_sum": [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
     "ldt_sumsq": [_vp, _i64, _vp, _i32, C.c_float, _vp, _vp],
     "ldt_adam_ema_step": [_vp, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i32, C.c_double, _i32,
                           _vp, _vp],

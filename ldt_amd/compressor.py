@@ -277,6 +277,11 @@ class Compressor(nn.Module):
     def _device(self):
         return self.input.weight.device
 
+    def invalidate_packed(self):
+        """Drop the packed panels: the optimizer step writes the parameters through raw pointers, which moves neither `data_ptr` nor
+        `_version` — the two things params_fingerprint keys on (as Score.invalidate_packed)."""
+        self._pack, self._pack_key = None, None
+
     def packed(self):
         key = params_fingerprint(self) + tuple((b.data_ptr(), b._version) for b in self.buffers())
         if self._pack is not None and key == self._pack_key:

@@ -4,9 +4,12 @@ train_Compressor.py (:72,99) and train_Completion_Compressor.py (:81,108) call.
 
 Kept, with the reference's names, signatures and return values: `Trainer(cfg, model, device)`, `sample` (:54-59), `valsample`
 (:61-100), `reconstrustion` (:102-161; completion :66-95 — upstream's spelling), `resume` (:163-186).  New: `eval_losses`, the two
-ELBO terms of `compute_loss` that need no absent extension.  Training is out of scope: there is no optimizer and no scheduler, and
-`update` / `compute_loss` raise — `compute_loss` adds `EMD_loss`, which goes through the auction-EMD CUDA extension of
-evaluation/emd.py that this package does not have (and does not imitate).
+ELBO terms of `compute_loss` that need no absent extension, and `update_decoder`, one training step of the DECODER with the encoder
+frozen (compressor_train.DecoderTrainStep, losses.cd_loss): the Chamfer reconstruction loss, the top-down backward,
+Adam without EMA over the decoder-side parameters, and the gradient with respect to the latents kept as `last_eps_grad`.  The whole
+Compressor step is out of scope: `update` / `compute_loss` raise — the posterior, encoder and grouper backward are not built, and
+`compute_loss` adds `EMD_loss`, which goes through the auction-EMD CUDA extension of evaluation/emd.py that this package does not have
+(and does not imitate).
 
 The encode, the decode, Chamfer / EMD and the KL terms run in HIP kernels (Compressor.forward, ldt_amd.metrics); what is plain torch
 here is bookkeeping on finished clouds: concatenation, the loaders' shift / scale de-normalisation and the category filter.
@@ -39,6 +42,56 @@ class CompressorTrainer:
     def compute_loss(self, target_set, label):
         raise NotImplementedError("CompressorTrainer.compute_loss: its EMD_loss term needs the auction-EMD CUDA extension "
                                   "(evaluation/emd.py), which is not on this path; eval_losses returns the KL and Chamfer terms")
+
+    # ---- training the decoder with the encoder frozen ---------------------------------------------------
+    optimizer = None                                                 # AdamEMA over the decoder-side parameters, created by the first update_decoder
+    last_eps_grad = None                                             # d loss / d eps of the last update_decoder
+
+    def warm_up(self, optimizer, itr):
+        """trainer/base.py's linear learning-rate warm-up, as Trainer.warm_up."""
+        if itr < self.cfg.opt.warmup_iters:
+            lr = self.cfg.opt.lr * min(float(itr + 1) / max(self.cfg.opt.warmup_iters, 1), 1.0)
+            for param_group in optimizer.param_groups:
+                param_group["lr"] = lr
+
+    def update_decoder(self, data, *, eps=None, post_noise=None):
+        """One training step of the decoder with the encoder frozen: eps = model.encode(data['tr_points']) under no_grad (or `eps` as
+        given; `post_noise` replaces the posterior draws), the learning-rate warm-up, the top-down decode with its tape
+        (compressor_train.DecoderTrainStep), the Chamfer reconstruction loss `CD_loss(set, points)` of type 'l1' with its gradient
+        (ldt_amd.losses.cd_loss), the backward, clip_grad_norm_(cfg.opt.grad_norm_clip_value) and Adam(lr, (beta1, beta2), weight_decay) —
+        the reference's stage-1 optimizer has no EMA — over the decoder-side parameters, `itr += 1`.  -> (loss, rec_loss), 0-dim device
+        tensors: with the encoder frozen the KL term has no gradient on this side, and the EMD term stays absent (compute_loss), so the
+        loss IS the Chamfer term.  `self.last_eps_grad` keeps d loss / d eps (B, tokens, n_layers * z_dim), where the posterior / encoder
+        backward would start."""
+        from .compressor_train import DecoderTrainStep, decoder_parameters, refuse_undecodable
+        from .losses import cd_loss
+        from .train import AdamEMA
+        refuse_undecodable(self.model)
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("CompressorTrainer.update_decoder: device %s; the HIP path has no CPU fallback" % (self.device,))
+        points = (data["tr_points"] if isinstance(data, dict) else data).to(self.device).float().contiguous()
+        if eps is None:
+            was_training = self.model.training
+            try:
+                with torch.no_grad():
+                    self.model.eval()                                # the frozen encoder runs as in evaluation; the caller's mode comes back
+                    eps = self.model.encode(points, post_noise=post_noise)
+            finally:
+                self.model.train(was_training)
+        if self.optimizer is None:
+            o = self.cfg.opt
+            self.optimizer = AdamEMA([p for _, p in decoder_parameters(self.model)], lr=o.lr, betas=(o.beta1, o.beta2),
+                                     weight_decay=o.weight_decay, ema_decay=0.)
+        self.warm_up(self.optimizer, self.itr)
+        self.optimizer.zero_grad()
+        step = DecoderTrainStep(self.model)
+        out = step.forward(eps.to(self.device), num_points=points.shape[1])
+        loss, d_set = cd_loss(out, points, "l1", want_grad=True)
+        self.last_eps_grad = step.backward(d_set)
+        self.optimizer.step(max_norm=getattr(self.cfg.opt, "grad_norm_clip_value", None))
+        self.model.invalidate_packed()                               # the update wrote the weights through raw pointers
+        self.itr += 1
+        return loss, loss
 
     @torch.no_grad()
     def eval_losses(self, target_set, label=None):
@@ -160,6 +213,10 @@ class CompletionCompressorTrainer(CompressorTrainer):
     def update(self, data):
         raise NotImplementedError("CompletionCompressorTrainer.update: training (optimizer step, backward) is not on this path — it is "
                                   "the inference / evaluation path; see eval_losses for the held-out KL and Chamfer terms")
+
+    def update_decoder(self, data, *, eps=None, post_noise=None):
+        raise NotImplementedError("CompletionCompressorTrainer.update_decoder: the decoder step is built and held for CompressorTrainer "
+                                  "alone; training is not on this path for the completion trainer")
 
     def compute_loss(self, target_set):
         raise NotImplementedError("CompletionCompressorTrainer.compute_loss: its EMD_loss term needs the auction-EMD CUDA extension "

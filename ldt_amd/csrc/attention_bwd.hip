@@ -1,6 +1,7 @@
 // Attention backward of a Score block (model/layers.py:183-200), head dim 8, 16, 32 or 64, Nq, Nk <= 512, gfx950: the whole of it — both
-// kernel forms, their launchers and the three entry points.  Self-attention (ldt_attention_bwd at 64, ldt_attention_bwd_narrow at 8, 16 and
-// 32) runs it at Nq = Nk = N; cross-attention to the point condition (ldt_attention_bwd_cross, every width; model/scorenet/score.py:129-149:
+// kernel forms, their launchers and the four entry points.  Self-attention (ldt_attention_bwd at 64, ldt_attention_bwd_narrow at 8, 16 and
+// 32) runs it at Nq = Nk = N; the Compressor's decoder (ldt_attention_bwd_long: head dim 32, up to 8192 queries on up to 512 keys) sums
+// dK / dV in parts, see "long query axis" below; cross-attention to the point condition (ldt_attention_bwd_cross, every width; model/scorenet/score.py:129-149:
 // the even blocks of a conditioned Score) with Nk keys from another tensor: query blocks tile Nq and loop to Nk, key blocks tile Nk and loop
 // to Nq, and every clamp and guard takes the extent of the axis it indexes.
 //   forward:   S = Q K^T / sqrt(Dh),  P = softmax(S),  O = P V          (O is the [B][H][N][Dh] buffer the reference re-reads as (B N, C): quirk Q1;
@@ -33,8 +34,12 @@
 #define AB_T 16                      // rows (query blocks: queries, key blocks: keys) per wave
 #define AB_J 32                      // MFMA form: columns per loop iteration, the K extent of one 16x16x32 product
 #define AB_LDP (AB_J + 8)            // MFMA form: LDS row pitch of the P / dS tiles, bf16 elements (80 B: 16-B aligned rows, staggered banks)
+#ifndef AB_CHUNK                     // (a measurement build of this file alone may pass another multiple of 32: tools/bench_decoder_train.py)
+#define AB_CHUNK LDT_ATTN_BWD_LONG_CHUNK   // long query axis: queries per partial sum of dK / dV.  A source constant: never a function of the grid or the device
+#endif
+static_assert(AB_CHUNK % AB_J == 0, "a 32-column step never straddles two chunks");
 
-// the operands of the three entry points (include/ldt_hip.h); self-attention: Nq = Nk = N
+// the operands of the entry points (include/ldt_hip.h); self-attention: Nq = Nk = N
 struct AttnBwdArgs {
     const bf16_t* Q; long ldq; long q_bs;
     const bf16_t* K; long ldk; const bf16_t* V; long ldv; long kv_bs;
@@ -44,6 +49,7 @@ struct AttnBwdArgs {
     bf16_t* dK; long lddk; bf16_t* dV; long lddv; long dkv_bs;
     int B, H, Nq, Nk;                         // queries (rows of Q, O, dO, dQ, stats) and keys (rows of K, V, dK, dV) per sample
     float scale;                              // Dh^-0.5
+    float* part;                              // long query axis only: fp32 partials [chunk][B][Nk][2 H Dh] = dK (unscaled) | dV
 };
 
 // ---- the steps both forms take
@@ -179,15 +185,19 @@ __global__ __launch_bounds__(64) void attn_bwd_stats_kernel(const AttnBwdArgs a)
     if (lq == 0 && q0 + lr < r.NR) r.st[2 * (q0 + lr) + 1] = d;
 }
 
-// the two main kernels of the MFMA form share one body
-template <int DH, bool KV>
+// the main kernels of the MFMA form share one body.  PART (key blocks of a long query axis): blockIdx.x = chunk * key blocks + key block; the
+// loop runs over the chunk's AB_CHUNK queries alone and the fp32 sums go to a.part unscaled, for attn_bwd_parts_kernel to add in chunk order
+template <int DH, bool KV, bool PART = false>
 __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
+    static_assert(KV || !PART, "only dK / dV are summed in parts");
     constexpr int NS = ab_steps(DH), NT = DH / 16;                      // operand chunks of 32 channels, accumulator tiles of 16
     __shared__ __attribute__((aligned(16))) bf16_t ds_t[AB_T][AB_LDP];
     __shared__ __attribute__((aligned(16))) bf16_t p_t[AB_T][AB_LDP];
     const int lane = threadIdx.x, lr = lane & 15, lq = lane >> 4;
-    const int b = blockIdx.z, h = blockIdx.y, r0 = blockIdx.x * AB_T;
+    const int nrb = PART ? (a.Nk + AB_T - 1) / AB_T : 1, chunk = PART ? blockIdx.x / nrb : 0;
+    const int b = blockIdx.z, h = blockIdx.y, r0 = (PART ? blockIdx.x % nrb : blockIdx.x) * AB_T;
     const AttnBwdRoles r = attn_bwd_roles<DH, KV>(a, b, h);
+    const int jb = chunk * AB_CHUNK, je = PART ? min(jb + AB_CHUNK, r.NC) : r.NC;      // the loop's columns
     bf16x8 fa[NS], fb[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -206,7 +216,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) { acc1[t] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc2[t] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
 
-    for (int j0 = 0; j0 < r.NC; j0 += AB_J) {
+    for (int j0 = jb; j0 < je; j0 += AB_J) {
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int col = j0 + 16 * half + lr;                       // this lane's column of the tile: a key (KV false) or a query (KV true)
@@ -238,6 +248,20 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
             if (KV) acc2[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, y2, acc2[t], 0, 0, 0);
         }
     }
+    if constexpr (PART) {
+        float* o = a.part + ((long)chunk * a.B + b) * a.Nk * (2L * a.H * DH) + h * DH;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int row = r0 + 4 * lq + i;
+                if (row < r.NR) {
+                    o[(long)row * (2 * a.H * DH) + 16 * t + lr] = acc1[t][i];
+                    o[(long)row * (2 * a.H * DH) + a.H * DH + 16 * t + lr] = acc2[t][i];
+                }
+            }
+        return;
+    }
     bf16_t* o1 = KV ? a.dK + (long)b * a.dkv_bs + h * DH : a.dQ + (long)b * a.dq_bs + h * DH;
     const long ld1 = KV ? a.lddk : a.lddq;
 #pragma unroll
@@ -264,6 +288,39 @@ static int attn_bwd_launch(const AttnBwdArgs& a, hipStream_t s) {
     if (rc != LDT_OK) return rc;
     hipLaunchKernelGGL((attn_bwd_kernel<DH, true>), grid_kv, block, 0, s, a);
     return ldt_check_launch("attention_bwd (dK, dV)");
+}
+
+// ---- long query axis (ldt_attention_bwd_long: the Compressor's decoder, 2048 queries on 32 keys), head dim 32.  Statistics and dQ are the
+// kernels above: their grids tile Nq.  dK / dV as above would be one wave per 16 keys walking every query (two waves per (sample, head), 64
+// trips each, at the decoder's shape): instead one wave takes (16 keys, AB_CHUNK queries) and leaves fp32 partials, and the kernel below adds
+// them in chunk order, scales dK and rounds to bf16.  Still no atomics, and the order is fixed by AB_CHUNK alone: the same bits on every run
+// and every device.  One thread per element of a [Nk][2 H Dh] row pair dK | dV.
+__global__ __launch_bounds__(256) void attn_bwd_parts_kernel(const AttnBwdArgs a, int dh, int chunks) {
+    const int C = a.H * dh, c = blockIdx.x * 256 + threadIdx.x, row = blockIdx.y, b = blockIdx.z;
+    if (c >= 2 * C) return;
+    const long chunk_stride = (long)a.B * a.Nk * (2L * C);
+    const float* p = a.part + ((long)b * a.Nk + row) * (2L * C) + c;
+    float s = 0.f;
+    for (int k = 0; k < chunks; ++k) s += p[k * chunk_stride];
+    if (c < C) a.dK[(long)b * a.dkv_bs + (long)row * a.lddk + c] = (bf16_t)(s * a.scale);
+    else a.dV[(long)b * a.dkv_bs + (long)row * a.lddv + (c - C)] = (bf16_t)s;
+}
+
+template <int DH>
+static int attn_bwd_long_launch(const AttnBwdArgs& a, hipStream_t s) {
+    const int chunks = (a.Nq + AB_CHUNK - 1) / AB_CHUNK, nkb = (a.Nk + AB_T - 1) / AB_T;
+    const dim3 grid((unsigned)((a.Nq + AB_T - 1) / AB_T), (unsigned)a.H, (unsigned)a.B), block(64);
+    hipLaunchKernelGGL(attn_bwd_stats_kernel<DH>, grid, block, 0, s, a);
+    int rc = ldt_check_launch("attention_bwd_long (row statistics)");
+    if (rc != LDT_OK) return rc;
+    hipLaunchKernelGGL((attn_bwd_kernel<DH, false>), grid, block, 0, s, a);
+    rc = ldt_check_launch("attention_bwd_long (dQ)");
+    if (rc != LDT_OK) return rc;
+    hipLaunchKernelGGL((attn_bwd_kernel<DH, true, true>), dim3((unsigned)(nkb * chunks), (unsigned)a.H, (unsigned)a.B), block, 0, s, a);
+    rc = ldt_check_launch("attention_bwd_long (dK, dV partials)");
+    if (rc != LDT_OK) return rc;
+    hipLaunchKernelGGL(attn_bwd_parts_kernel, dim3((unsigned)((2 * a.H * DH + 255) / 256), (unsigned)a.Nk, (unsigned)a.B), dim3(256), 0, s, a, DH, chunks);
+    return ldt_check_launch("attention_bwd_long (dK, dV)");
 }
 
 // ---- narrow form, head dim 8 or 16.  Query blocks: first the statistics of the block's 16 query rows, which go to `stats` for the key blocks
@@ -375,7 +432,8 @@ template <class Admit>
 static int attn_bwd_run(const char* name, Admit admit, const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk,
                         const uint16_t* V, int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats,
                         uint16_t* dQ, int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
-                        int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim, bool store8, void* stream) {
+                        int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim, bool store8, void* stream,
+                        float* part = nullptr) {
     LDT_REQUIRE(Q && K && V && O && dO && stats && dQ && dK && dV, LDT_EARG, "%s: null pointer", name);
     const int rc = admit();
     if (rc != LDT_OK) return rc;
@@ -397,10 +455,11 @@ static int attn_bwd_run(const char* name, Admit admit, const uint16_t* Q, int64_
     a.dQ = reinterpret_cast<bf16_t*>(dQ); a.lddq = lddq; a.dq_bs = dq_batch_stride;
     a.dK = reinterpret_cast<bf16_t*>(dK); a.lddk = lddk; a.dV = reinterpret_cast<bf16_t*>(dV); a.lddv = lddv; a.dkv_bs = dkv_batch_stride;
     a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.scale = 1.0f / sqrtf((float)head_dim);      // exactly 0.125 at 64
+    a.part = part;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (head_dim) {
         case 64: return attn_bwd_launch<64>(a, s);
-        case 32: return attn_bwd_launch<32>(a, s);
+        case 32: return part ? attn_bwd_long_launch<32>(a, s) : attn_bwd_launch<32>(a, s);
         case 16: return attn_bwd_narrow_launch<16>(a, s);
         case 8: return attn_bwd_narrow_launch<8>(a, s);
     }
@@ -450,4 +509,23 @@ extern "C" int ldt_attention_bwd_cross(const uint16_t* Q, int64_t ldq, int64_t q
     };
     return attn_bwd_run("attention_bwd_cross", admit, Q, ldq, q_batch_stride, K, ldk, V, ldv, kv_batch_stride, O, dO, stats, dQ, lddq,
                         dq_batch_stride, dK, lddk, dV, lddv, dkv_batch_stride, B, H, Nq, Nk, head_dim, head_dim <= 16, stream);
+}
+
+// The operand contract of ldt_attention_bwd_cross with a query axis of up to 8192 rows, head width 32 (the Compressor's 128 / 4) alone.
+extern "C" int ldt_attention_bwd_long(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk, const uint16_t* V,
+                                      int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats, uint16_t* dQ,
+                                      int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
+                                      int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim, float* scratch,
+                                      int64_t scratch_len, void* stream) {
+    auto admit = [&]() -> int {
+        LDT_REQUIRE(scratch, LDT_EARG, "attention_bwd_long: null pointer");
+        LDT_REQUIRE(head_dim == 32, LDT_ESHAPE, "attention_bwd_long: head_dim %d (32 only)", head_dim);
+        LDT_REQUIRE(Nq > 0 && Nq <= LDT_ATTN_BWD_LONG_MAX_QUERIES && Nk > 0 && Nk <= 512, LDT_ESHAPE,
+                    "attention_bwd_long: Nq %d, Nk %d (1 <= Nq <= %d, 1 <= Nk <= 512)", Nq, Nk, LDT_ATTN_BWD_LONG_MAX_QUERIES);
+        LDT_REQUIRE(B > 0 && H > 0 && scratch_len >= ((int64_t)(Nq + AB_CHUNK - 1) / AB_CHUNK) * B * Nk * 2 * H * head_dim, LDT_ESHAPE,
+                    "attention_bwd_long: scratch holds %ld floats, ceil(Nq / %d) * B * Nk * 2 * H * head_dim are needed", (long)scratch_len, AB_CHUNK);
+        return LDT_OK;
+    };
+    return attn_bwd_run("attention_bwd_long", admit, Q, ldq, q_batch_stride, K, ldk, V, ldv, kv_batch_stride, O, dO, stats, dQ, lddq,
+                        dq_batch_stride, dK, lddk, dV, lddv, dkv_batch_stride, B, H, Nq, Nk, head_dim, false, stream, scratch);
 }

@@ -289,3 +289,29 @@ extern "C" int ldt_embedding_grad(const float* dc, int64_t ld, const int32_t* la
                        dc, (long)ld, label, B, D, dE);
     return ldt_check_launch("embedding_grad");
 }
+
+// Backward of a set's learned prior rows (Compressor/layers.py:26-42 InitialSet: every sample starts from the same rows, all of them or, under a
+// keep_mask, its kept ones packed to the front): dprior[r] = sum over the samples that hold row r of do[b N + src[b][r]], in the order of b.
+// src[b][r] = the row of sample b that prior row r became, -1 = absent; an index outside [0, N) is taken as absent, never read.
+__global__ __launch_bounds__(256) void rows_gather_sum_kernel(const float* __restrict__ dy, long ld, const int* __restrict__ src, int B, int N, int R,
+                                                              int C, float* __restrict__ dprior) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const int r = blockIdx.y;
+    float acc = 0.f;
+    for (int b = 0; b < B; ++b) {
+        const int s = src[(long)b * R + r];
+        if (s >= 0 && s < N) acc += dy[((long)b * N + s) * ld + c];
+    }
+    dprior[(long)r * C + c] = acc;
+}
+
+extern "C" int ldt_rows_gather_sum(const float* dy, int64_t ld, const int32_t* src, int32_t B, int32_t N, int32_t R, int32_t C, float* dprior,
+                                   void* stream) {
+    LDT_REQUIRE(dy && src && dprior, LDT_EARG, "rows_gather_sum: null pointer");
+    LDT_REQUIRE(B > 0 && N > 0 && R > 0 && R <= 65535 && C > 0 && ld >= C, LDT_ESHAPE, "rows_gather_sum: B %d, N %d, R %d (1 .. 65535), C %d, ld %ld",
+                B, N, R, C, (long)ld);
+    hipLaunchKernelGGL(rows_gather_sum_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)R), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       dy, (long)ld, src, B, N, R, C, dprior);
+    return ldt_check_launch("rows_gather_sum");
+}

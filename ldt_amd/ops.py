@@ -938,9 +938,11 @@ def embedding_grad(dc, label, n_classes):
     return out
 
 
-def _attention_bwd(fn, entry, q, k, v, o, do, B, H, lengths, head_dim, outs):
+def _attention_bwd(fn, entry, q, k, v, o, do, B, H, lengths, head_dim, outs, extra=None, stats_out=None):
     """attention_bwd (lengths = (N,)) and attention_bwd_cross ((Nq, Nk)): the operand checks, outs(H*head_dim) -> (dq, dk, dv) bf16 row
-    views, the statistics buffer and the call of `entry`, which takes the lengths as given."""
+    views, the statistics buffer and the call of `entry`, which takes the lengths as given.  extra(Cc) -> arguments between head_dim and
+    the stream (attention_bwd_long's scratch).  stats_out: a contiguous fp32 [B, H, Nq, 2] tensor that receives the row statistics (L, D)
+    in place of a buffer of this call's own."""
     Nq, Nk, cross = lengths[0], lengths[-1], len(lengths) == 2
     if head_dim not in (8, 16, 32, 64):
         raise ValueError("%s: head_dim %r is not 8, 16, 32 or 64" % (fn, head_dim))
@@ -955,10 +957,13 @@ def _attention_bwd(fn, entry, q, k, v, o, do, B, H, lengths, head_dim, outs):
         raise ValueError("%s: q %s, k %s, v %s for B %d, Nq %d, Nk %d, %d channels"
                          % (fn, tuple(q.shape), tuple(k.shape), tuple(v.shape), B, Nq, Nk, Cc))
     dq, dk, dv = outs(Cc)
-    stats = torch.empty((B, H, Nq, 2), dtype=torch.float32, device=q.device)
+    stats = torch.empty((B, H, Nq, 2), dtype=torch.float32, device=q.device) if stats_out is None else stats_out
+    _need(stats, torch.float32, "stats_out")
+    if not stats.is_contiguous() or stats.numel() != B * H * Nq * 2 or stats.device != q.device:
+        raise ValueError("%s: stats_out must be a contiguous fp32 [B, H, Nq, 2] tensor on the operands' device" % fn)
     ldq, ldkv = dq.stride(0), dk.stride(0)
     check(getattr(lib(), entry)(_p(q), q.stride(0), q.stride(0) * Nq, _p(k), k.stride(0), _p(v), v.stride(0), k.stride(0) * Nk, _p(o), _p(do),
-                                _p(stats), _p(dq), ldq, ldq * Nq, _p(dk), ldkv, _p(dv), ldkv, ldkv * Nk, B, H, *lengths, head_dim, stream_ptr()), entry)
+                                _p(stats), _p(dq), ldq, ldq * Nq, _p(dk), ldkv, _p(dv), ldkv, ldkv * Nk, B, H, *lengths, head_dim, *(extra(Cc) if extra else ()), stream_ptr()), entry)
     return dq, dk, dv
 
 
@@ -979,6 +984,96 @@ def attention_bwd_cross(q, k, v, o, do, B, H, Nq, Nk, head_dim, dq_out=None, dkv
     return _attention_bwd("attention_bwd_cross", "ldt_attention_bwd_cross", q, k, v, o, do, B, H, (Nq, Nk), head_dim,
                           lambda Cc: (_bf16_rows_out(dq_out, B * Nq, Cc, q.device, "attention_bwd_cross: dq_out"),)
                           + _bf16_rows_out(dkv_out, B * Nk, 2 * Cc, q.device, "attention_bwd_cross: dkv_out").split(Cc, 1))
+
+
+def attention_bwd_long_scratch(B, H, Nq, Nk, head_dim=32):
+    """floats of fp32 scratch attention_bwd_long needs: one [B, Nk, 2 * H * head_dim] partial of dK | dV per chunk of queries."""
+    return -(-Nq // _lib.ATTN_BWD_LONG_CHUNK) * B * Nk * 2 * H * head_dim
+
+
+def attention_bwd_long(q, k, v, o, do, B, H, Nq, Nk, dq_out=None, dkv_out=None, head_dim=32, scratch=None, stats_out=None):
+    """attention_bwd_cross's contract on a long query axis (ldt_attention_bwd_long): head_dim 32 only, Nq <= ATTN_BWD_LONG_MAX_QUERIES,
+    Nk <= ATTN_BWD_LONG_MAX_KEYS.  dK / dV are summed per chunk of ATTN_BWD_LONG_CHUNK queries into `scratch` (fp32, allocated here when
+    not given: attention_bwd_long_scratch floats, laid out [chunk, B, Nk, 2 * H * 32] = dK unscaled | dV) and then added in chunk order.
+    stats_out: a contiguous fp32 [B, H, Nq, 2] tensor that receives the row statistics (max + ln sum, rowsum(dO o O)) of every query."""
+    need = attention_bwd_long_scratch(B, H, Nq, Nk, head_dim)
+    if scratch is None:
+        scratch = torch.empty((need,), dtype=torch.float32, device=q.device)
+    _need(scratch, torch.float32, "scratch")
+    if not scratch.is_contiguous():
+        raise ValueError("attention_bwd_long: scratch must be contiguous")
+    return _attention_bwd("attention_bwd_long", "ldt_attention_bwd_long", q, k, v, o, do, B, H, (Nq, Nk), head_dim,
+                          lambda Cc: (_bf16_rows_out(dq_out, B * Nq, Cc, q.device, "attention_bwd_long: dq_out"),)
+                          + _bf16_rows_out(dkv_out, B * Nk, 2 * Cc, q.device, "attention_bwd_long: dkv_out").split(Cc, 1),
+                          extra=lambda Cc: (_p(scratch), scratch.numel()), stats_out=stats_out)
+
+
+def chamfer_nn(x1, x2):
+    """x1 [B, n, 3], x2 [B, m, 3] fp32 -> (d1 [B, n], idx1 [B, n] int32, d2 [B, m], idx2 [B, m] int32): squared nearest-neighbour
+    distances both ways (bit-equal to chamfer(x1, x2)'s dr and dl) with the lowest index that attains each."""
+    _need(x1, torch.float32, "x1"); _need(x2, torch.float32, "x2")
+    if x1.dim() != 3 or x2.dim() != 3 or x1.shape[2] != 3 or x2.shape[2] != 3 or x1.shape[0] != x2.shape[0]:
+        raise ValueError("chamfer_nn: x1 %s, x2 %s are not [B, n, 3] and [B, m, 3]" % (tuple(x1.shape), tuple(x2.shape)))
+    x1, x2 = x1.contiguous(), x2.contiguous()
+    B, n, m = x1.shape[0], x1.shape[1], x2.shape[1]
+    d1, d2 = torch.empty((B, n), dtype=torch.float32, device=x1.device), torch.empty((B, m), dtype=torch.float32, device=x1.device)
+    i1, i2 = torch.empty((B, n), dtype=torch.int32, device=x1.device), torch.empty((B, m), dtype=torch.int32, device=x1.device)
+    check(lib().ldt_chamfer_nn(_p(x1), _p(x2), B, n, m, _p(d1), _p(i1), _p(d2), _p(i2), stream_ptr()), "ldt_chamfer_nn")
+    return d1, i1, d2, i2
+
+
+def _cd_type(type):
+    if type not in _lib.CD_TYPES:
+        raise ValueError("cd_loss: type %r is neither 'l1' nor 'l2'" % (type,))
+    return _lib.CD_TYPES[type]
+
+
+def cd_loss(d1, d2, type="l1", out=None):
+    """fp32 [3] on the device = (loss, term1, term2) of CD_loss over chamfer_nn's distances: 'l1' mean sqrt(d1) + mean sqrt(d2), 'l2'
+    mean d1 + mean d2.  Float64 partials in index order."""
+    t = _cd_type(type)
+    _need(d1, torch.float32, "d1"); _need(d2, torch.float32, "d2")
+    if not (d1.is_contiguous() and d2.is_contiguous()):
+        raise ValueError("cd_loss: d1 and d2 must be contiguous")
+    if out is None:
+        out = torch.empty((3,), dtype=torch.float32, device=d1.device)
+    _need(out, torch.float32, "out")
+    check(lib().ldt_cd_loss(_p(d1), d1.numel(), _p(d2), d2.numel(), t, _p(out), stream_ptr()), "ldt_cd_loss")
+    return out
+
+
+def cd_loss_bwd(x1, x2, idx1, idx2, type="l1", upstream=1.0):
+    """fp32 [B, n, 3]: upstream * d cd_loss / d x1 (the estimated cloud) from chamfer_nn's indices.  A pair at distance 0 contributes 0."""
+    _need(x1, torch.float32, "x1"); _need(x2, torch.float32, "x2"); _need(idx1, torch.int32, "idx1"); _need(idx2, torch.int32, "idx2")
+    t = _cd_type(type)
+    x1, x2 = x1.contiguous(), x2.contiguous()
+    B, n, m = x1.shape[0], x1.shape[1], x2.shape[1]
+    if tuple(idx1.shape) != (B, n) or tuple(idx2.shape) != (B, m) or x2.shape[0] != B or not (idx1.is_contiguous() and idx2.is_contiguous()):
+        raise ValueError("cd_loss_bwd: idx1 %s, idx2 %s for x1 %s, x2 %s" % (tuple(idx1.shape), tuple(idx2.shape), tuple(x1.shape), tuple(x2.shape)))
+    out = torch.empty_like(x1)
+    check(lib().ldt_cd_loss_bwd(_p(x1), _p(x2), _p(idx1), _p(idx2), B, n, m, t, float(upstream), _p(out), stream_ptr()), "ldt_cd_loss_bwd")
+    return out
+
+
+def prior_row_map(keep):
+    """The `src` of rows_gather_sum for a set that starts from the kept prior rows packed to the front (InitialSet under a keep mask,
+    Compressor/layers.py:34-37): keep bool [B, R] (True = sample b holds prior row r) -> int32 [B, R], the running count of kept rows before
+    r where kept, -1 elsewhere.  Index bookkeeping on whichever device `keep` lives on; without a mask src[b][r] = r."""
+    keep = keep.to(torch.bool)
+    pos = keep.to(torch.int32).cumsum(1, dtype=torch.int32) - 1
+    return torch.where(keep, pos, torch.full_like(pos, -1)).contiguous()
+
+
+def rows_gather_sum(dy, src, N):
+    """fp32 [R, C]: row r = the sum over the samples b with src[b, r] >= 0, in the order of b, of dy[b * N + src[b, r]].  dy fp32 [B * N, C]
+    row-major, src int32 [B, R] (-1 = sample b does not hold row r)."""
+    _need(dy, torch.float32, "dy"); _rowmajor(dy, "dy"); _need(src, torch.int32, "src")
+    B, R = src.shape
+    if dy.dim() != 2 or dy.shape[0] != B * N or not src.is_contiguous():
+        raise ValueError("rows_gather_sum: dy %s is not [B * N, C] for contiguous src %s, N %d" % (tuple(dy.shape), tuple(src.shape), N))
+    out = torch.empty((R, dy.shape[1]), dtype=torch.float32, device=dy.device)
+    check(lib().ldt_rows_gather_sum(_p(dy), dy.stride(0), _p(src), B, int(N), R, dy.shape[1], _p(out), stream_ptr()), "ldt_rows_gather_sum")
+    return out
 
 
 def sumsq(x, max_norm=0.0, scratch=None, out=None):
