@@ -476,6 +476,34 @@ int ldt_attention_bwd_long(const uint16_t* Q, int64_t ldq, int64_t q_batch_strid
 int ldt_rows_gather_sum(const float* dy, int64_t ld, const int32_t* src, int32_t B, int32_t N, int32_t R, int32_t C, float* dprior,
                         void* stream);
 
+/* ---- training the Compressor's top-down half: attention backward on a long key axis, backward of the posterior draw and the KL term ----
+ * ldt_attention_bwd_wide: the contract of ldt_attention_bwd_cross for a long KEY axis: head_dim 32 only, 1 <= Nq <= 512, 1 <= Nk <=
+ *   LDT_ATTN_BWD_WIDE_MAX_KEYS (the Compressor's posterior blocks, compute_posterior, Compressor/Network.py:61-78 through model/layers.py:
+ *   183-200: Nq = 32 latent tokens on the Nk = 2048 points of the running set).  dK / dV are ldt_attention_bwd_cross's key-block kernel.  Row
+ *   statistics and dQ run per (16 queries, LDT_ATTN_BWD_WIDE_CHUNK keys).  scratch (scratch_len floats; LDT_EARG when fewer than the two
+ *   regions need), with chunks = ceil(Nk / chunk):
+ *       [chunks][B][H][Nq][2]     each chunk's row maximum m_c and s_c = sum exp(s - m_c); a second kernel combines them in chunk order,
+ *                                 M = max_c m_c, L = M + ln sum_c s_c exp(m_c - M), and writes (L, D) to stats
+ *       [chunks][B][Nq][H 32]     unscaled fp32 partials of dQ, which a last kernel adds in chunk order, scales and rounds to bf16
+ *   A fixed order set by the constant alone: the same bits on every run.  At Nk <= LDT_ATTN_BWD_WIDE_CHUNK (one chunk) stats, dQ, dK and dV
+ *   carry the bits of ldt_attention_bwd_cross.
+ * ldt_reparam_kl_bwd: backward of ldt_reparam_kl's draw and of kl_scale x (the sum of its kl) (Compressor/Network.py:12-29, 76, 219-224), from
+ *   post fp32 [rows][2 z] = mu | logvar as stored (before the clamp), noise fp32 [rows][z] and d_eps fp32 [rows][ldd] (a column slice of a
+ *   wider buffer), into dpost fp32 [rows][2 z] = dmu | dlogvar.  Per element, lv = clamp(logvar, lo, hi), s = exp(lv / 2), eps = mu + s n as
+ *   ldt_reparam forms it:  g = d_eps + kl_scale eps,  dmu = g,  dlv = g (s n / 2) - kl_scale / 2,  dlogvar = dlv where lo <= logvar <= hi
+ *   (torch.clamp's rule: the bounds included) and exactly 0 elsewhere.  The analytic form: log q's derivatives through mu and logvar cancel
+ *   against the one through eps, log p's is eps.  16-byte accesses when z and ldd are multiples of 4 and the buffers 16-byte aligned, the
+ *   scalar form of the same kernel otherwise. */
+#define LDT_ATTN_BWD_WIDE_MAX_KEYS 8192
+#define LDT_ATTN_BWD_WIDE_CHUNK 256
+int ldt_attention_bwd_wide(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk, const uint16_t* V,
+                           int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats, uint16_t* dQ,
+                           int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
+                           int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim, float* scratch,
+                           int64_t scratch_len, void* stream);
+int ldt_reparam_kl_bwd(const float* post, const float* noise, const float* d_eps, int64_t ldd, float kl_scale, float* dpost, int64_t rows,
+                       int32_t z, float lo, float hi, void* stream);
+
 /* ---- fused MLP half of a narrow ResidualBlock (the Compressor's d = 128 blocks; model/layers.py:219,226 + :110-133) ----
  * In place on x fp32 [M][ldx]:  x += gate * (W_dn . GELU(W_up . h + b_up) + b_dn),  h = LN(x) * ln_w + ln_b  (affine,
  * no-condition blocks) or LN(x) * (1 + scale) + shift (AdaLN; shift/scale/gate are per-sample vectors, sample =

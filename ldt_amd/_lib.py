@@ -13,6 +13,7 @@ MAX_BLOCKS = 64
 ODE_SUMSQ_SCRATCH = 1024        # LDT_ODE_SUMSQ_SCRATCH
 CD_TYPES = {"l1": 1, "l2": 2}   # LDT_CD_L1, LDT_CD_L2
 ATTN_BWD_LONG_MAX_QUERIES, ATTN_BWD_LONG_MAX_KEYS, ATTN_BWD_LONG_CHUNK = 8192, 512, 256      # LDT_ATTN_BWD_LONG_*
+ATTN_BWD_WIDE_MAX_QUERIES, ATTN_BWD_WIDE_MAX_KEYS, ATTN_BWD_WIDE_CHUNK = 512, 8192, 256      # LDT_ATTN_BWD_WIDE_*
 
 EPI_F32, EPI_BF16, EPI_GELU_BF16, EPI_RELU_BF16, EPI_RESID_F32 = range(5)
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_GELU = range(4)
@@ -121,6 +122,9 @@ SIGNATURES = {
                                 _i32, _i32, _i32, _i32, _i32, _vp],
     "ldt_attention_bwd_long": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64,
                                _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
+    "ldt_attention_bwd_wide": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64,
+                               _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
+    "ldt_reparam_kl_bwd": [_vp, _vp, _vp, _i64, C.c_float, _vp, _i64, _i32, C.c_float, C.c_float, _vp],
     "ldt_chamfer_nn": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "ldt_cd_loss": [_vp, _i64, _vp, _i64, _i32, _vp, _vp],
     "ldt_cd_loss_bwd": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp],

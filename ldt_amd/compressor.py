@@ -411,37 +411,16 @@ class Compressor(nn.Module):
         return self.forward(x, **kw)["all_eps"]
 
     # ------------------------------------------------------------------ encode (Network.py:188-249)
-    @torch.no_grad()
-    def forward(self, x, num_points=None, label=None, *, post_noise=None, want_stats=False, seed_eps=None, want_kl=False):
-        """Bidirectional inference: x (B, N, 3) -> dict with 'all_eps' (B, tokens, n_layers*z_dim) and the
-        reconstruction 'set' (B, N, 3).  `post_noise`: optional list of n_layers tensors (B, tokens, z_dim) replacing
-        the N(0,1) draws of `sample(mu, logvar)` (Network.py:26-29).  'posteriors' holds token-major (mu, logvar) when want_stats.
-        `want_kl`: the ELBO entries of the reference dict (Network.py:221-232) — 'kls' and 'all_logqz', lists of n_layers tensors in
-        top-down order shaped (B, z_dim, tokens) like upstream's (channels-first views of token-major buffers), plus 'kl_sample_sum'
-        (B, n_layers), each sample's KL summed per level; the posterior draw then runs as ldt_reparam_kl, whose latents are
-        bit-identical to ldt_reparam's.  Off (default): both entries are None and nothing else changes."""
-        self._no_training_dropout("forward")
+    def _bottom_up(self, P, x, label, want_stats=False):
+        """Network.py:188-206: input conv, FPS + kNN grouping, PreExtraction, pos embedding, ActNorm, encoder stages -> (the n_layers stage
+        outputs, fresh token-major fp32 [B*T, D] buffers; the token stream; its copy before ActNorm when want_stats; the label embedding or
+        None; fps_idx, knn_idx, centers)."""
         dev = self._device()
-        if dev.type != "cuda":
-            raise RuntimeError("Compressor.forward: parameters on %s; the HIP path has no CPU fallback" % dev)
         B, N, _ = x.shape
-        T, D, z, L = self.z_scales, self.hidden_dim, self.z_dim, self.n_layers
-        npts = self.outsize if num_points is None else num_points
-        # reference order on the CPU generator: B randperms (InitialSet, :215) then one randn per level (:220)
-        keep_mask = self._presence(B, npts)
-        if self.max_outputs is None and seed_eps is None:                 # (the mixture's seed rows are drawn first, :215 before :220)
-            seed_eps = self._draw_seed_eps(B, npts)
-        if post_noise is None:
-            if self.reference_rng:
-                post_noise = [torch.randn((B, z, T)).transpose(1, 2) for _ in range(L)]
-            else:                                                    # one CPU draw keys a device-side Philox stream per level
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-                post_noise = [ops.philox_normal((B, T, z), dev, seed, step=j) for j in range(L)]
-        P = self.packed()
+        T, D = self.z_scales, self.hidden_dim
         pts = x.to(dev, torch.float32).contiguous()
         if self.norm_input:
             pts = ops.norm_points(pts)                                              # norm_pts (:170-174, :189-190)
-        # ---- bottom_up: input conv, FPS + kNN grouping, PreExtraction, pos embedding, ActNorm, encoder stages
         feat = ops.sgemm(pts.view(B * N, 3), P["w_input"], P["b_input"])            # Conv1d 3 -> D  (:192)
         n_cur = N
         if self.pre_group:                                                          # :193-194: 256 groups of 32 neighbours first
@@ -471,6 +450,50 @@ class Compressor(nn.Module):
             for Pa in Pe["atts"]:
                 residual_block(Pa, tok, B, T, y_bf16=ops.cast_pad_bf16(tok, ops.pad64(D)), Nk=T, c=pos, per_token=per_tok)
             enc_out.append(final_layer(Pe["out"], tok, B, T, pos, per_token=per_tok))
+        return enc_out, tok, tok_pre, l_emb, fps_idx, knn_idx, centers
+
+    @torch.no_grad()
+    def bottom_up(self, x, label=None):
+        """The reference's method (Network.py:188-206): x (B, N, 3) -> {'outputs': the n_layers encoder stage outputs shaped (B, hidden,
+        tokens) like upstream's (channels-first views of fresh token-major buffers, as `kls` are), 'max': the token stream's maximum,
+        'fps_idx', 'knn_idx', 'centers' as `forward` returns them}.  `forward` runs the same code."""
+        self._no_training_dropout("bottom_up")
+        dev = self._device()
+        if dev.type != "cuda":
+            raise RuntimeError("Compressor.bottom_up: parameters on %s; the HIP path has no CPU fallback" % dev)
+        enc_out, tok, _, _, fps_idx, knn_idx, centers = self._bottom_up(self.packed(), x, label)
+        B, T, D = x.shape[0], self.z_scales, self.hidden_dim
+        return {"outputs": [t.view(B, T, D).transpose(1, 2) for t in enc_out], "max": tok.max(), "fps_idx": fps_idx, "knn_idx": knn_idx,
+                "centers": centers}
+
+    @torch.no_grad()
+    def forward(self, x, num_points=None, label=None, *, post_noise=None, want_stats=False, seed_eps=None, want_kl=False):
+        """Bidirectional inference: x (B, N, 3) -> dict with 'all_eps' (B, tokens, n_layers*z_dim) and the
+        reconstruction 'set' (B, N, 3).  `post_noise`: optional list of n_layers tensors (B, tokens, z_dim) replacing
+        the N(0,1) draws of `sample(mu, logvar)` (Network.py:26-29).  'posteriors' holds token-major (mu, logvar) when want_stats.
+        `want_kl`: the ELBO entries of the reference dict (Network.py:221-232) — 'kls' and 'all_logqz', lists of n_layers tensors in
+        top-down order shaped (B, z_dim, tokens) like upstream's (channels-first views of token-major buffers), plus 'kl_sample_sum'
+        (B, n_layers), each sample's KL summed per level; the posterior draw then runs as ldt_reparam_kl, whose latents are
+        bit-identical to ldt_reparam's.  Off (default): both entries are None and nothing else changes."""
+        self._no_training_dropout("forward")
+        dev = self._device()
+        if dev.type != "cuda":
+            raise RuntimeError("Compressor.forward: parameters on %s; the HIP path has no CPU fallback" % dev)
+        B, N, _ = x.shape
+        T, D, z, L = self.z_scales, self.hidden_dim, self.z_dim, self.n_layers
+        npts = self.outsize if num_points is None else num_points
+        # reference order on the CPU generator: B randperms (InitialSet, :215) then one randn per level (:220)
+        keep_mask = self._presence(B, npts)
+        if self.max_outputs is None and seed_eps is None:                 # (the mixture's seed rows are drawn first, :215 before :220)
+            seed_eps = self._draw_seed_eps(B, npts)
+        if post_noise is None:
+            if self.reference_rng:
+                post_noise = [torch.randn((B, z, T)).transpose(1, 2) for _ in range(L)]
+            else:                                                    # one CPU draw keys a device-side Philox stream per level
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                post_noise = [ops.philox_normal((B, T, z), dev, seed, step=j) for j in range(L)]
+        P = self.packed()
+        enc_out, tok, tok_pre, l_emb, fps_idx, knn_idx, centers = self._bottom_up(P, x, label, want_stats)
         # ---- top_down: posterior per level + decoder block
         o = self._initial_set(P, B, npts, keep_mask, seed_eps)
         all_eps = torch.empty((B * T, L * z), dtype=torch.float32, device=dev)

@@ -1,4 +1,14 @@
-"""Training the Compressor's decoder on the HIP path: the host-driven top-down forward that keeps what the backward needs, and the backward
+"""Training the Compressor's top-down half on the HIP path, in two steps that share their per-level pieces.
+
+`TopDownTrainStep`: everything from the encoder's outputs upward (Network.py:208-233, `top_down`): per level the
+posterior block `decoder[l].att` (the T latent tokens attend to the N points of the running set stream; level 0 to themselves), the
+`decoder[l].prior` head, the reparameterised draw with its KL term, and the decoder block.  Its backward is ONE interleaved pass: the
+posterior of level j + 1 reads the set stream o_{j+1}, so its K/V gradient has to be in `dX` before decoder block j runs backward.
+Kernels on top of the decoder step's: `ldt_attention_bwd_wide` (T queries on N keys; level 0's T on T is `ldt_attention_bwd_cross`),
+`ldt_reparam_kl_bwd`, `ldt_silu_bwd`.  It returns the gradient with respect to the encoder outputs (`d_enc_out`), where the encoder backward
+will start; the bottom-up half (input conv, grouper, position embedding, ActNorm, encoder) stays frozen.
+
+`DecoderTrainStep` (section 4.15), the decoder alone: the host-driven top-down forward that keeps what the backward needs, and the backward
 from the gradient of the decoded set down to the decoder-side parameters and the latents.
 
 Reference: model/Compressor/Network.py:251-268 (`Compressor.sample`, what is differentiated), :80-83 (`DecoderBlock.forward` with c = None),
@@ -18,7 +28,7 @@ rows: dscale = dgamma, dshift = dbeta); the attention backward is `ldt_attention
 import torch
 
 from . import _lib, ops
-from ._lib import EPI_BF16, EPI_F32, EPI_RESID_F32
+from ._lib import ACT_SILU, EPI_BF16, EPI_F32, EPI_RESID_F32
 from .layers import conv_w
 from .train import _grad2d, _t
 
@@ -36,6 +46,129 @@ def decoder_parameters(model):
         elif parts[0] == "decoder" and (parts[2] == "ln" or (parts[2] == "att1" and parts[3] in names)):
             out.append((name, p))
     return out
+
+
+def topdown_parameters(model):
+    """The parameters a top-down step trains, in module order: decoder_parameters plus, per level, the posterior block `att` and the
+    `prior` head."""
+    names = ("fc_q", "fc_kv", "fc_o", "norm1", "norm2", "mlp")
+    dec = {n for n, _ in decoder_parameters(model)}
+    out = []
+    for name, p in model.named_parameters():
+        parts = name.split(".")
+        if name in dec or (parts[0] == "decoder" and ((parts[2] == "att" and parts[3] in names) or parts[2] == "prior")):
+            out.append((name, p))
+    return out
+
+
+# ---------------------------------------------------------------- the pieces both steps run, each written once
+def _f32(t):
+    return t.detach().float().contiguous()
+
+
+def _block_fwd(A, X, kv, B, H, Nq, Nk):
+    """The no-condition ResidualBlock (layers.py:224-226) on the fp32 rows X [B Nq, C], updated in place, with K | V = kv bf16
+    [B Nk, 2 C] given; unfused, every operand of the backward kept -> the block's tape."""
+    C, M = A["C"], B * Nq
+    sb = {"x1": X.clone()}
+    sb["h"] = ops.layernorm_modulate(X, w=A["n1"][0], b=A["n1"][1])
+    sb["q"] = ops.gemm_bf16(sb["h"], A["wq"], A["bq"], EPI_BF16)
+    sb["kv"] = kv
+    sb["o"] = ops.attention_fwd(sb["q"], kv[:, :C], kv[:, C:], B, H, Nq, Nk, HEAD_DIM)                    # [B, H, Nq, 32] == (M, C) raw view (Q1)
+    ops.gemm_bf16(sb["o"].view(M, C), A["wo"], A["bo"], EPI_RESID_F32, out=X, resid=X)
+    sb["x2"] = X.clone()
+    sb["h2"] = ops.layernorm_modulate(X, w=A["n2"][0], b=A["n2"][1])
+    sb["u"] = ops.gemm_bf16(sb["h2"], A["wup"], A["bup"], EPI_BF16)                                       # MLP pre-activation
+    sb["ug"] = sb["u"].clone()
+    ops.block_activation_(sb["ug"], 1)                                                                    # GELU
+    ops.gemm_bf16(sb["ug"], A["wdn"], A["bdn"], EPI_RESID_F32, out=X, resid=X)
+    return sb
+
+
+def _linear_bwd(layer, dy, x_in, want_dx=True, epilogue=EPI_F32):
+    """dW, db into the layer's .grad; -> dX = dy @ W (dy bf16 [M, n] or fp32; x_in the forward's operand)."""
+    ops.wgrad(dy, x_in, out=_grad2d(layer.weight))
+    ops.colsum(dy, out=layer.bias.grad)
+    if not want_dx:
+        return None
+    dyb = dy if dy.dtype == torch.bfloat16 and dy.shape[1] % 64 == 0 else ops.cast_pad_bf16(dy, ops.pad64(dy.shape[1]))
+    return ops.dgrad(dyb, ops.transpose_cast_bf16(conv_w(layer).detach()), epilogue)      # W[N, K] -> bf16 [K, pad64(N)], rebuilt every step
+
+
+def _affine_ln_bwd(norm, x, dy, dx):
+    """h = LN(x) gamma + beta: dx += the LayerNorm gradient, dgamma and dbeta into the norm's .grad."""
+    w, b = norm.affine
+    M, C = x.shape
+    ops.layernorm_modulate_bwd(x, dy, dx, scale=ops.add_f32(_f32(w), torch.full_like(w, -1.0)).view(1, C), mod_sample_stride=0,
+                               rows_per_sample=M, dshift=b.grad.view(1, C), dscale=w.grad.view(1, C))
+
+
+def _block_bwd(blk, sb, dX, B, H, Nq, Nk, attention_bwd):
+    """Backward of _block_fwd: dX fp32 [B Nq, C], the gradient of the block's result, becomes the gradient of its input; the block's
+    .grads are filled; -> dkv bf16 [B Nk, 2 C] = dK | dV, the gradient of its K | V.  attention_bwd: the ops entry for (Nq, Nk)."""
+    C, M = dX.shape[1], B * Nq
+    # x = x2 + mlp.out(GELU(mlp.fc(LN2(x2))))                                              (layers.py:226)
+    dug = _linear_bwd(blk.mlp.out, dX, sb["ug"])
+    du = ops.gelu_bwd(sb["u"], dug)
+    dh2 = _linear_bwd(blk.mlp.fc[0][0], du, sb["h2"])
+    _affine_ln_bwd(blk.norm2, sb["x2"], dh2, dX)
+    # x2 = x1 + fc_o(attention(fc_q(LN1(x1)), K | V))                                       (layers.py:225, 183-200)
+    do = _linear_bwd(blk.fc_o, dX, sb["o"].view(M, C), epilogue=EPI_BF16)                  # [M, C] == dO [B, H, Nq, 32] raw (Q1)
+    kv = sb["kv"]
+    dkv = torch.empty((B * Nk, 2 * C), dtype=torch.bfloat16, device=dX.device)            # [dk | dv]
+    dq, _, _ = attention_bwd(sb["q"], kv[:, :C], kv[:, C:], sb["o"], do, B, H, Nq, Nk, dkv_out=dkv)
+    dh = _linear_bwd(blk.fc_q, dq, sb["h"])
+    _affine_ln_bwd(blk.norm1, sb["x1"], dh, dX)
+    return dkv
+
+
+def _decoder_level_fwd(P, X, e2, j, S, B, H, N, T, L, z):
+    """Decoder block j of the top-down pass (reversed(self.decoder), Network.py:263) on the set stream X, in place -> its tape."""
+    Pd = P["dec"][L - 1 - j]
+    kv = ops.sgemm(e2[:, z * j: z * (j + 1)], Pd["w_zkv"], Pd["b_zkv"], out_bf16=True)                    # [B T, 2 C] = K | V, composed linear
+    S["w_zkv_t"][j] = _t(Pd["w_zkv"])                                                                     # [z, 2 C]: d_eps_j = dkv W_zkv
+    return _block_fwd(Pd["att1"], X, kv, B, H, N, T)
+
+
+def _decoder_level_bwd(d, sb, dX, e_j, w_zkv_t, d_eps_j, B, H, N, T):
+    """Backward of decoder block `d` = decoder[L - 1 - j]: dX becomes the gradient of the block's input, d_eps_j is written."""
+    blk = d.att1
+    dkv = _block_bwd(blk, sb, dX, B, H, N, T, ops.attention_bwd_long)
+    # kv = eps_j W_zkv^T + b_zkv with W_zkv = W_kv W_ln, b_zkv = W_kv b_ln + b_kv: the composed linear hands its gradient to both factors
+    dkv32 = ops.widen_bf16(dkv)
+    w_kv, w_ln, b_ln = _f32(conv_w(blk.fc_kv)), _f32(conv_w(d.ln)), _f32(d.ln.bias)
+    C = dX.shape[1]
+    dW_zkv = ops.sgemm(_t(dkv32), _t(e_j))                                                # [2 C, z]
+    db_zkv = ops.colsum(dkv32)                                                            # [2 C]
+    ops.sgemm(torch.cat([dW_zkv, db_zkv[:, None]], 1), torch.cat([w_ln, b_ln[:, None]], 1), out=_grad2d(blk.fc_kv.weight))   # dW_zkv W_ln^T + db_zkv (x) b_ln
+    blk.fc_kv.bias.grad.copy_(db_zkv)
+    w_kv_t = _t(w_kv)                                                                     # [C, 2 C]
+    ops.sgemm(w_kv_t, _t(dW_zkv), out=_grad2d(d.ln.weight))                               # W_kv^T dW_zkv  [C, z]
+    ops.sgemm(db_zkv.view(1, 2 * C), w_kv_t, out=d.ln.bias.grad.view(1, C))               # W_kv^T db_zkv
+    ops.sgemm(dkv32, w_zkv_t, out=d_eps_j)                                                # dkv W_zkv
+
+
+def _output_bwd(m, dset, xf, M):
+    """The output conv C -> 3 (fp32 on both sides of a 3-wide linear) -> dX fp32 [M, C], the gradient of the residual stream."""
+    d2 = dset.detach().float().contiguous().view(M, 3)
+    ops.wgrad(d2, xf, out=_grad2d(m.output.weight))
+    ops.colsum(d2, out=m.output.bias.grad)
+    return ops.sgemm(d2, _t(_f32(conv_w(m.output))))
+
+
+def _start(m, who, B, T, N, keep_mask):
+    """The checks and the first rows both forwards share -> (keep_mask, src map of rows_gather_sum, X fp32 [B N, C])."""
+    refuse_undecodable(m, N, T)
+    if keep_mask is None:
+        keep_mask = m._presence(B, N)
+    if keep_mask is not None:
+        keep_mask = keep_mask.to(torch.bool)
+        if tuple(keep_mask.shape) != (B, m.max_outputs) or not bool((keep_mask.sum(1) == N).all()):
+            raise ValueError("%s.forward: keep_mask must be (B = %d, max_outputs = %d) with %d kept rows per sample"
+                             % (who, B, m.max_outputs, N))
+    # which row of each sample every prior row became (ldt_rows_gather_sum's map), built once here where the mask is
+    src = ops.prior_row_map(torch.ones((B, N), dtype=torch.bool) if keep_mask is None else keep_mask)
+    return keep_mask, src
 
 
 def refuse_undecodable(model, num_points=None, tokens=None):
@@ -94,38 +227,13 @@ class DecoderTrainStep:
         if Z != L * z:
             raise ValueError("DecoderTrainStep.forward: eps %s is not (B, tokens, n_layers * z_dim = %d)" % (tuple(eps.shape), L * z))
         N = m.outsize if num_points is None else int(num_points)
-        refuse_undecodable(m, N, T)
-        if keep_mask is None:
-            keep_mask = m._presence(B, N)
-        if keep_mask is not None:
-            keep_mask = keep_mask.to(torch.bool)
-            if tuple(keep_mask.shape) != (B, m.max_outputs) or not bool((keep_mask.sum(1) == N).all()):
-                raise ValueError("DecoderTrainStep.forward: keep_mask must be (B = %d, max_outputs = %d) with %d kept rows per sample"
-                                 % (B, m.max_outputs, N))
+        keep_mask, src = _start(m, "DecoderTrainStep", B, T, N, keep_mask)
         P = m.packed()
-        M = B * N
         e2 = eps.detach().float().contiguous().view(B * T, Z)
-        # which row of each sample every prior row became (ldt_rows_gather_sum's map), built once here where the mask is
-        src = ops.prior_row_map(torch.ones((B, N), dtype=torch.bool) if keep_mask is None else keep_mask)
         S = {"B": B, "N": N, "T": T, "eps": e2, "src": src.to(eps.device), "w_zkv_t": [None] * L, "levels": []}
-        X = m._initial_set(P, B, N, keep_mask).clone()                  # fp32 [M, C]: the residual stream, updated in place below
-        for j in range(L):                                              # reversed(self.decoder), Network.py:263
-            Pd = P["dec"][L - 1 - j]
-            A = Pd["att1"]
-            sb = {"x1": X.clone()}
-            sb["h"] = ops.layernorm_modulate(X, w=A["n1"][0], b=A["n1"][1])
-            sb["q"] = ops.gemm_bf16(sb["h"], A["wq"], A["bq"], EPI_BF16)
-            sb["kv"] = ops.sgemm(e2[:, z * j: z * (j + 1)], Pd["w_zkv"], Pd["b_zkv"], out_bf16=True)      # [B T, 2 C] = K | V, composed linear
-            S["w_zkv_t"][j] = _t(Pd["w_zkv"])                                                             # [z, 2 C]: d_eps_j = dkv W_zkv
-            sb["o"] = ops.attention_fwd(sb["q"], sb["kv"][:, :C], sb["kv"][:, C:], B, H, N, T, HEAD_DIM)  # [B, H, N, 32] == (M, C) raw view (Q1)
-            ops.gemm_bf16(sb["o"].view(M, C), A["wo"], A["bo"], EPI_RESID_F32, out=X, resid=X)
-            sb["x2"] = X.clone()
-            sb["h2"] = ops.layernorm_modulate(X, w=A["n2"][0], b=A["n2"][1])
-            sb["u"] = ops.gemm_bf16(sb["h2"], A["wup"], A["bup"], EPI_BF16)                               # MLP pre-activation
-            sb["ug"] = sb["u"].clone()
-            ops.block_activation_(sb["ug"], 1)                                                            # GELU
-            ops.gemm_bf16(sb["ug"], A["wdn"], A["bdn"], EPI_RESID_F32, out=X, resid=X)
-            S["levels"].append(sb)
+        X = m._initial_set(P, B, N, keep_mask).clone()                  # fp32 [B N, C]: the residual stream, updated in place below
+        for j in range(L):
+            S["levels"].append(_decoder_level_fwd(P, X, e2, j, S, B, H, N, T, L, z))
         S["xf"] = X
         out = ops.sgemm(X, P["w_out"], P["b_out"])                      # Conv1d C -> 3, Network.py:266
         self.saved = S
@@ -147,58 +255,156 @@ class DecoderTrainStep:
         for _, p in decoder_parameters(m):
             if p.grad is None:
                 p.grad = torch.zeros_like(p)
-        f32 = lambda t: t.detach().float().contiguous()
-        wt = lambda mod_: ops.transpose_cast_bf16(conv_w(mod_).detach())                      # W[N, K] -> bf16 [K, pad64(N)], rebuilt every step
-
-        def linear_bwd(layer, dy, x_in, want_dx=True, epilogue=EPI_F32):
-            """dW, db into the layer's .grad; -> dX = dy @ W (dy bf16 [M, n] or fp32; x_in the forward's operand)."""
-            ops.wgrad(dy, x_in, out=_grad2d(layer.weight))
-            ops.colsum(dy, out=layer.bias.grad)
-            if not want_dx:
-                return None
-            dyb = dy if dy.dtype == torch.bfloat16 and dy.shape[1] % 64 == 0 else ops.cast_pad_bf16(dy, ops.pad64(dy.shape[1]))
-            return ops.dgrad(dyb, wt(layer), epilogue)
-
-        def affine_ln_bwd(norm, x, dy, dx):
-            """h = LN(x) gamma + beta: dx += the LayerNorm gradient, dgamma and dbeta into the norm's .grad."""
-            w, b = norm.affine
-            ops.layernorm_modulate_bwd(x, dy, dx, scale=ops.add_f32(f32(w), torch.full_like(w, -1.0)).view(1, C), mod_sample_stride=0,
-                                       rows_per_sample=M, dshift=b.grad.view(1, C), dscale=w.grad.view(1, C))
-
-        # output conv C -> 3 (fp32 on both sides of a 3-wide linear)
-        d2 = dset.detach().float().contiguous().view(M, 3)
-        ops.wgrad(d2, S["xf"], out=_grad2d(m.output.weight))
-        ops.colsum(d2, out=m.output.bias.grad)
-        dX = ops.sgemm(d2, _t(f32(conv_w(m.output))))                   # [M, C] fp32: the gradient of the residual stream
+        dX = _output_bwd(m, dset, S["xf"], M)
         d_eps = torch.empty((B * T, L * z), dtype=torch.float32, device=dX.device)
         for j in reversed(range(L)):
-            d = m.decoder[L - 1 - j]
-            blk, sb = d.att1, S["levels"][j]
-            # x = x2 + mlp.out(GELU(mlp.fc(LN2(x2))))                                              (layers.py:226)
-            dug = linear_bwd(blk.mlp.out, dX, sb["ug"])
-            du = ops.gelu_bwd(sb["u"], dug)
-            dh2 = linear_bwd(blk.mlp.fc[0][0], du, sb["h2"])
-            affine_ln_bwd(blk.norm2, sb["x2"], dh2, dX)
-            # x2 = x1 + fc_o(attention(fc_q(LN1(x1)), fc_kv(ln(eps_j))))                            (layers.py:225, 183-200)
-            do = linear_bwd(blk.fc_o, dX, sb["o"].view(M, C), epilogue=EPI_BF16)                  # [M, C] == dO [B, H, N, 32] raw (Q1)
-            kv = sb["kv"]
-            dkv = torch.empty((B * T, 2 * C), dtype=torch.bfloat16, device=dX.device)             # [dk | dv]
-            dq, _, _ = ops.attention_bwd_long(sb["q"], kv[:, :C], kv[:, C:], sb["o"], do, B, H, N, T, dkv_out=dkv)
-            dh = linear_bwd(blk.fc_q, dq, sb["h"])
-            affine_ln_bwd(blk.norm1, sb["x1"], dh, dX)
-            # kv = eps_j W_zkv^T + b_zkv with W_zkv = W_kv W_ln, b_zkv = W_kv b_ln + b_kv: the composed linear hands its gradient to both factors
-            e_j = S["eps"][:, z * j: z * (j + 1)]
-            dkv32 = ops.widen_bf16(dkv)
-            w_kv, w_ln, b_ln = f32(conv_w(blk.fc_kv)), f32(conv_w(d.ln)), f32(d.ln.bias)
-            dW_zkv = ops.sgemm(_t(dkv32), _t(e_j))                                                # [2 C, z]
-            db_zkv = ops.colsum(dkv32)                                                            # [2 C]
-            ops.sgemm(torch.cat([dW_zkv, db_zkv[:, None]], 1), torch.cat([w_ln, b_ln[:, None]], 1), out=_grad2d(blk.fc_kv.weight))   # dW_zkv W_ln^T + db_zkv (x) b_ln
-            blk.fc_kv.bias.grad.copy_(db_zkv)
-            w_kv_t = _t(w_kv)                                                                     # [C, 2 C]
-            ops.sgemm(w_kv_t, _t(dW_zkv), out=_grad2d(d.ln.weight))                               # W_kv^T dW_zkv  [C, z]
-            ops.sgemm(db_zkv.view(1, 2 * C), w_kv_t, out=d.ln.bias.grad.view(1, C))               # W_kv^T db_zkv
-            ops.sgemm(dkv32, S["w_zkv_t"][j], out=d_eps[:, z * j: z * (j + 1)])                   # dkv W_zkv
+            _decoder_level_bwd(m.decoder[L - 1 - j], S["levels"][j], dX, S["eps"][:, z * j: z * (j + 1)], S["w_zkv_t"][j],
+                               d_eps[:, z * j: z * (j + 1)], B, H, N, T)
         # the learned prior rows: every sample started from them (all, or its kept ones packed to the front)
         m.init_set.prior.grad.copy_(ops.rows_gather_sum(dX, S["src"], N))
         self.d_eps = d_eps.view(B, T, L * z)
         return self.d_eps
+
+
+def _centred_keys(A, y, kv, B, nk):
+    """K | V of a posterior block for its backward, with each sample's mean key taken off K: bf16(y W_k^T + b_k - mean_j K_j), formed from
+    the fp32 accumulators by the forward's GEMM with a per-sample bias.  Neither P (softmax is invariant under a logit shift common to a
+    row) nor dQ = scale sum_j dS_j k_j (sum_j dS_j = 0) depends on a common shift of the keys, and dK, dV do not read the key values
+    beyond P.  What does depend on it is the error: the kernel takes D = rowsum(dO o O) from the saved bf16 O, and the error of D enters
+    dQ times the P-weighted MEAN key.  The points of the set stream share a large common component (they all start from prior rows that
+    the same blocks moved), so that term dominated dQ's error (rel-MSE 1.1e-4 of dQ at the tiny fixture's last
+    level, 8.5e-6 with the mean taken off)."""
+    C = A["C"]
+    sums = torch.stack([ops.colsum(kv[b * nk:(b + 1) * nk, :C]) for b in range(B)])                       # [B, C] fp32, fixed order
+    off = torch.eye(C, dtype=torch.float32, device=kv.device) * (-1.0 / nk)
+    bias = ops.sgemm(sums, off, A["bkv"][:C].contiguous())                                                # b_k - mean key, per sample
+    kvc = kv.clone()
+    for b in range(B):
+        ops.gemm_bf16(y[b * nk:(b + 1) * nk], A["wkv"][:C], bias[b], EPI_BF16, out=kvc[b * nk:(b + 1) * nk, :C])
+    return kvc
+
+
+def _attention_bwd_self(q, k, v, o, do, B, H, Nq, Nk, dkv_out=None):
+    """Level 0's att(x, x), T on T: ldt_attention_bwd_cross at the Compressor's head width."""
+    return ops.attention_bwd_cross(q, k, v, o, do, B, H, Nq, Nk, HEAD_DIM, dkv_out=dkv_out)
+
+
+def refuse_untrainable_topdown(model, num_points=None, tokens=None):
+    """What the top-down step does not cover: the posterior's attention limits first (T queries on N keys: ldt_attention_bwd_wide; level
+    0's T on T: ldt_attention_bwd_cross), then everything refuse_undecodable refuses.  Works on CPU parameters."""
+    N = model.outsize if num_points is None else int(num_points)
+    T = model.z_scales if tokens is None else int(tokens)
+    if not (1 <= T <= TopDownTrainStep.MAX_TOKENS and 1 <= N <= TopDownTrainStep.MAX_POINTS):
+        raise NotImplementedError("training the top-down half with %d latent tokens on %d set points is not on this path: the posterior's "
+                                  "ldt_attention_bwd_wide takes 1 <= Nq <= %d, 1 <= Nk <= %d"
+                                  % (T, N, TopDownTrainStep.MAX_TOKENS, TopDownTrainStep.MAX_POINTS))
+    refuse_undecodable(model, num_points, tokens)
+
+
+class TopDownTrainStep:
+    """One forward + backward of the Compressor's top-down half (Network.py:208-233).  `forward(enc_out, post_noise)` returns the decoded
+    set (B, N, 3), all_eps (B, T, n_layers * z_dim) and kl_sample_sum (B, n_layers), and keeps the tape; `backward(dset, kl_scale)` fills
+    every `.grad` of topdown_parameters(model) for  loss = <dset, set> + kl_scale * sum(kl)  and returns d_enc_out, a list of n_layers
+    fp32 (B, T, C) tensors (index i: the gradient of enc_out[i]), kept as `self.d_enc_out`."""
+
+    MAX_TOKENS = _lib.ATTN_BWD_WIDE_MAX_QUERIES                        # ldt_attention_bwd_wide: 1 <= Nq <= 512 (and ldt_attention_bwd_cross at level 0)
+    MAX_POINTS = _lib.ATTN_BWD_WIDE_MAX_KEYS                           #                         1 <= Nk <= 8192
+
+    def __init__(self, model):
+        refuse_untrainable_topdown(model)
+        self.m = model
+        self.saved = None
+        self.d_eps = None
+        self.d_enc_out = None
+
+    # ---------------------------------------------------------------- forward
+    @torch.no_grad()
+    def forward(self, enc_out, post_noise, num_points=None, keep_mask=None):
+        m = self.m
+        L, z, C, H = m.n_layers, m.z_dim, m.hidden_dim, m.num_heads
+        enc_out, post_noise = list(enc_out), list(post_noise)
+        for t in enc_out + post_noise:
+            if not (torch.is_tensor(t) and t.is_cuda):
+                raise RuntimeError("TopDownTrainStep.forward: an operand is on %s; the HIP path has no CPU fallback"
+                                   % (t.device if torch.is_tensor(t) else type(t).__name__,))
+        self.saved = None
+        if len(enc_out) != L or len(post_noise) != L:
+            raise ValueError("TopDownTrainStep.forward: %d encoder outputs and %d posterior draws for %d levels" % (len(enc_out), len(post_noise), L))
+        B, T = enc_out[0].shape[0], enc_out[0].shape[1]
+        for t in enc_out:
+            if tuple(t.shape) != (B, T, C):
+                raise ValueError("TopDownTrainStep.forward: encoder output %s is not (B = %d, tokens = %d, hidden = %d)" % (tuple(t.shape), B, T, C))
+        for t in post_noise:
+            if tuple(t.shape) != (B, T, z):
+                raise ValueError("TopDownTrainStep.forward: posterior draw %s is not (B = %d, tokens = %d, z_dim = %d)" % (tuple(t.shape), B, T, z))
+        N = m.outsize if num_points is None else int(num_points)
+        refuse_untrainable_topdown(m, N, T)
+        keep_mask, src = _start(m, "TopDownTrainStep", B, T, N, keep_mask)
+        P = m.packed()
+        dev = enc_out[0].device
+        all_eps = torch.empty((B * T, L * z), dtype=torch.float32, device=dev)
+        S = {"B": B, "N": N, "T": T, "eps": all_eps, "src": src.to(dev), "w_zkv_t": [None] * L, "levels": [], "post": []}
+        X = m._initial_set(P, B, N, keep_mask).clone()                  # fp32 [B N, C]: the set stream o, updated in place below
+        kl_sums = []
+        for j in range(L):
+            Pd = P["dec"][L - 1 - j]
+            A = Pd["att"]
+            xj = enc_out[-j - 1].detach().float().contiguous().view(B * T, C).clone()                     # the token stream of this level, updated in place
+            # compute_posterior(x, o) (Network.py:61-78): att(x, o) with K / V from the RAW set stream (quirk Q2); level 0: att(x, x)
+            y, nk = (ops.cast_pad_bf16(xj, ops.pad64(C)), T) if j == 0 else (ops.cast_pad_bf16(X, ops.pad64(C)), N)
+            pb = _block_fwd(A, xj, ops.gemm_bf16(y, A["wkv"], A["bkv"], EPI_BF16), B, H, T, nk)
+            pb["y"], pb["x3"] = y, xj
+            pb["kv"] = _centred_keys(A, y, pb["kv"], B, nk)                                               # the backward's K | V (the forward is done with its own)
+            pb["post"] = ops.sgemm(xj, Pd["w_prior"], Pd["b_prior"], act_in=ACT_SILU)                     # SiLU -> Conv1d C -> 2 z
+            pb["noise"] = post_noise[j].detach().to(dev, torch.float32).contiguous().view(B * T, z)
+            kl_sums.append(ops.reparam_kl(pb["post"], pb["noise"], all_eps[:, z * j: z * (j + 1)], m.min_sigma, 10., T)[4])
+            S["post"].append(pb)
+            S["levels"].append(_decoder_level_fwd(P, X, all_eps, j, S, B, H, N, T, L, z))
+        S["xf"] = X
+        out = ops.sgemm(X, P["w_out"], P["b_out"])                      # Conv1d C -> 3, Network.py:233
+        self.saved = S
+        return out.view(B, N, 3), all_eps.view(B, T, L * z), torch.stack(kl_sums, 1)
+
+    # ---------------------------------------------------------------- backward
+    @torch.no_grad()
+    def backward(self, dset, kl_scale):
+        m, S = self.m, self.saved
+        if S is None:
+            raise RuntimeError("TopDownTrainStep.backward before forward")
+        self.saved = None
+        self.d_enc_out = None
+        B, N, T = S["B"], S["N"], S["T"]
+        L, z, C, H = m.n_layers, m.z_dim, m.hidden_dim, m.num_heads
+        M = B * N
+        if tuple(dset.shape) != (B, N, 3):
+            raise ValueError("TopDownTrainStep.backward: dset %s is not (%d, %d, 3)" % (tuple(dset.shape), B, N))
+        for _, p in topdown_parameters(m):
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        dX = _output_bwd(m, dset, S["xf"], M)                           # the complete gradient of o_L
+        d_eps = torch.empty((B * T, L * z), dtype=torch.float32, device=dX.device)
+        d_enc = [None] * L
+        for j in reversed(range(L)):                                    # dX: the complete gradient of o_{j+1}
+            d, pb = m.decoder[L - 1 - j], S["post"][j]
+            dej = d_eps[:, z * j: z * (j + 1)]
+            _decoder_level_bwd(d, S["levels"][j], dX, S["eps"][:, z * j: z * (j + 1)], S["w_zkv_t"][j], dej, B, H, N, T)
+            # eps_j = mu + exp(clamp(logvar) / 2) noise and kl_scale * kl (Network.py:26-29, 219-224)
+            dpost = ops.reparam_kl_bwd(pb["post"], pb["noise"], dej, kl_scale, m.min_sigma, 10.)
+            # (mu | logvar) = prior.1(SiLU(x3)), fp32 (Network.py:76)
+            lin = d.prior[1]
+            dact = ops.sgemm(dpost, _t(_f32(conv_w(lin))))
+            dXp, act = ops.silu_bwd(pb["x3"], dact, want_act=True)       # the gradient of the token stream behind the posterior block
+            ops.wgrad(dpost, act, out=_grad2d(lin.weight))
+            ops.colsum(dpost, out=lin.bias.grad)
+            nk = T if j == 0 else N
+            dkv = _block_bwd(d.att, pb, dXp, B, H, T, nk, _attention_bwd_self if j == 0 else ops.attention_bwd_wide)
+            dy = _linear_bwd(d.att.fc_kv, dkv, pb["y"])                  # [B nk, C] fp32: into the K / V source
+            if j == 0:
+                ops.add_f32(dXp, dy, out=dXp)                           # att(x, x): the block attends to its own input
+            else:
+                ops.add_f32(dX, dy, out=dX)                             # att(x, o_j): ADDED to the set stream's gradient before decoder block j - 1 runs
+            d_enc[L - 1 - j] = dXp.view(B, T, C)
+        m.init_set.prior.grad.copy_(ops.rows_gather_sum(dX, S["src"], N))
+        self.d_eps = d_eps.view(B, T, L * z)
+        self.d_enc_out = d_enc
+        return d_enc

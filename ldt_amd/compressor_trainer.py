@@ -6,8 +6,11 @@ Kept, with the reference's names, signatures and return values: `Trainer(cfg, mo
 (:61-100), `reconstrustion` (:102-161; completion :66-95 — upstream's spelling), `resume` (:163-186).  New: `eval_losses`, the two
 ELBO terms of `compute_loss` that need no absent extension, and `update_decoder`, one training step of the DECODER with the encoder
 frozen (compressor_train.DecoderTrainStep, losses.cd_loss): the Chamfer reconstruction loss, the top-down backward,
-Adam without EMA over the decoder-side parameters, and the gradient with respect to the latents kept as `last_eps_grad`.  The whole
-Compressor step is out of scope: `update` / `compute_loss` raise — the posterior, encoder and grouper backward are not built, and
+Adam without EMA over the decoder-side parameters, and the gradient with respect to the latents kept as `last_eps_grad`; and
+`update_topdown`, one step of the whole top-down half — posterior blocks, prior heads, the reparameterised draw and the KL term, then the
+decoder — with the bottom-up half frozen (compressor_train.TopDownTrainStep; section 4.16): loss = kl_weight * kl_loss + the Chamfer term,
+the gradient with respect to the encoder outputs kept as `last_enc_out_grad`.  The whole
+Compressor step is out of scope: `update` / `compute_loss` raise — the encoder and grouper backward are not built, and
 `compute_loss` adds `EMD_loss`, which goes through the auction-EMD CUDA extension of evaluation/emd.py that this package does not have
 (and does not imitate).
 
@@ -92,6 +95,69 @@ class CompressorTrainer:
         self.model.invalidate_packed()                               # the update wrote the weights through raw pointers
         self.itr += 1
         return loss, loss
+
+    # ---- training the top-down half with the bottom-up half frozen -------------------------------------------
+    topdown_optimizer = None                                         # AdamEMA over the top-down parameters, created by the first update_topdown
+    last_enc_out_grad = None                                         # d loss / d (encoder outputs) of the last update_topdown
+
+    def update_topdown(self, data, *, enc_out=None, post_noise=None):
+        """One training step of the top-down half (posterior blocks, prior heads, decoder; compressor_train.TopDownTrainStep, DESIGN.md
+        section 4.16) with the bottom-up half frozen: the encoder outputs from `model.bottom_up(data['tr_points'])` under no_grad in
+        evaluation mode (or `enc_out`, n_layers tensors (B, tokens, hidden), as given), the posterior draws as `Compressor.forward` draws
+        them (or `post_noise`), the learning-rate warm-up, the top-down pass with its tape, `CD_loss(set, points)` of type 'l1' with its
+        gradient, the interleaved backward with kl_scale = kl_weight / numel(cat(kls)), clip_grad_norm_ and Adam without EMA over the
+        top-down parameters (`self.topdown_optimizer`, apart from update_decoder's), `itr += 1`.  -> (loss, kl_loss, rec_loss), 0-dim
+        device tensors as the reference's `update` returns them: loss = kl_weight * kl_loss + rec_loss with kl_loss formed as
+        eval_losses forms it.  The reference's rec_loss also holds EMD_loss, which is absent here (compute_loss says why): rec_loss IS the
+        Chamfer term.  `self.last_enc_out_grad` keeps d loss / d enc_out, where the encoder backward would start."""
+        from .compressor_train import TopDownTrainStep, refuse_untrainable_topdown, topdown_parameters
+        from .losses import cd_loss
+        from .train import AdamEMA
+        if self.kl_weight is None:
+            raise ValueError("CompressorTrainer.update_topdown: cfg.opt.kl_weight is not set; the loss is kl_weight * kl_loss + rec_loss")
+        refuse_untrainable_topdown(self.model)
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("CompressorTrainer.update_topdown: device %s; the HIP path has no CPU fallback" % (self.device,))
+        m = self.model
+        points = (data["tr_points"] if isinstance(data, dict) else data).to(self.device).float().contiguous()
+        B, T, z, L = points.shape[0], m.z_scales, m.z_dim, m.n_layers
+        if enc_out is None:
+            was_training = m.training
+            try:
+                with torch.no_grad():
+                    m.eval()                                         # the frozen bottom-up half runs as in evaluation; the caller's mode comes back
+                    enc_out = [o.transpose(1, 2) for o in m.bottom_up(points)["outputs"]]
+            finally:
+                m.train(was_training)
+        else:
+            T = enc_out[0].shape[1]
+        # the order of Compressor.forward on the CPU generator: InitialSet's row subsets, then the posterior draws
+        keep_mask = m._presence(B, points.shape[1])
+        if keep_mask is None:                                        # (every row kept: said so, so that the step does not draw again)
+            keep_mask = torch.ones((B, m.max_outputs), dtype=torch.bool)
+        if post_noise is None:
+            if m.reference_rng:
+                post_noise = [torch.randn((B, z, T)).transpose(1, 2).to(self.device) for _ in range(L)]
+            else:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                post_noise = [ops.philox_normal((B, T, z), torch.device(self.device), seed, step=j) for j in range(L)]
+        if self.topdown_optimizer is None:
+            o = self.cfg.opt
+            self.topdown_optimizer = AdamEMA([p for _, p in topdown_parameters(m)], lr=o.lr, betas=(o.beta1, o.beta2),
+                                             weight_decay=o.weight_decay, ema_decay=0.)
+        self.warm_up(self.topdown_optimizer, self.itr)
+        self.topdown_optimizer.zero_grad()
+        step = TopDownTrainStep(m)
+        out, _, kl_sample_sum = step.forward([t.to(self.device) for t in enc_out], [t.to(self.device) for t in post_noise],
+                                             num_points=points.shape[1], keep_mask=keep_mask)
+        n_kl = L * B * z * T                                         # numel(torch.cat(kls, dim=1))
+        kl_loss = kl_sample_sum.sum() / n_kl
+        rec_loss, d_set = cd_loss(out, points, "l1", want_grad=True)
+        self.last_enc_out_grad = step.backward(d_set, self.kl_weight / n_kl)
+        self.topdown_optimizer.step(max_norm=getattr(self.cfg.opt, "grad_norm_clip_value", None))
+        m.invalidate_packed()                                        # the update wrote the weights through raw pointers
+        self.itr += 1
+        return self.kl_weight * kl_loss + rec_loss, kl_loss, rec_loss
 
     @torch.no_grad()
     def eval_losses(self, target_set, label=None):
@@ -216,6 +282,10 @@ class CompletionCompressorTrainer(CompressorTrainer):
 
     def update_decoder(self, data, *, eps=None, post_noise=None):
         raise NotImplementedError("CompletionCompressorTrainer.update_decoder: the decoder step is built and held for CompressorTrainer "
+                                  "alone; training is not on this path for the completion trainer")
+
+    def update_topdown(self, data, *, enc_out=None, post_noise=None):
+        raise NotImplementedError("CompletionCompressorTrainer.update_topdown: the top-down step is built and held for CompressorTrainer "
                                   "alone; training is not on this path for the completion trainer")
 
     def compute_loss(self, target_set):

@@ -1,7 +1,8 @@
 // Attention backward of a Score block (model/layers.py:183-200), head dim 8, 16, 32 or 64, Nq, Nk <= 512, gfx950: the whole of it — both
 // kernel forms, their launchers and the four entry points.  Self-attention (ldt_attention_bwd at 64, ldt_attention_bwd_narrow at 8, 16 and
 // 32) runs it at Nq = Nk = N; the Compressor's decoder (ldt_attention_bwd_long: head dim 32, up to 8192 queries on up to 512 keys) sums
-// dK / dV in parts, see "long query axis" below; cross-attention to the point condition (ldt_attention_bwd_cross, every width; model/scorenet/score.py:129-149:
+// dK / dV in parts, see "long query axis" below; its posterior blocks (ldt_attention_bwd_wide: up to 512 queries on up to 8192 keys) take the
+// row statistics and dQ in parts, see "long key axis"; cross-attention to the point condition (ldt_attention_bwd_cross, every width; model/scorenet/score.py:129-149:
 // the even blocks of a conditioned Score) with Nk keys from another tensor: query blocks tile Nq and loop to Nk, key blocks tile Nk and loop
 // to Nq, and every clamp and guard takes the extent of the axis it indexes.
 //   forward:   S = Q K^T / sqrt(Dh),  P = softmax(S),  O = P V          (O is the [B][H][N][Dh] buffer the reference re-reads as (B N, C): quirk Q1;
@@ -37,7 +38,10 @@
 #ifndef AB_CHUNK                     // (a measurement build of this file alone may pass another multiple of 32: tools/bench_decoder_train.py)
 #define AB_CHUNK LDT_ATTN_BWD_LONG_CHUNK   // long query axis: queries per partial sum of dK / dV.  A source constant: never a function of the grid or the device
 #endif
-static_assert(AB_CHUNK % AB_J == 0, "a 32-column step never straddles two chunks");
+#ifndef AB_WIDE_CHUNK                // (likewise: tools/bench_topdown_train.py)
+#define AB_WIDE_CHUNK LDT_ATTN_BWD_WIDE_CHUNK   // long key axis: keys per partial of the row statistics and of dQ.  A source constant, as AB_CHUNK is
+#endif
+static_assert(AB_CHUNK % AB_J == 0 && AB_WIDE_CHUNK % AB_J == 0, "a 32-column step never straddles two chunks");
 
 // the operands of the entry points (include/ldt_hip.h); self-attention: Nq = Nk = N
 struct AttnBwdArgs {
@@ -49,7 +53,8 @@ struct AttnBwdArgs {
     bf16_t* dK; long lddk; bf16_t* dV; long lddv; long dkv_bs;
     int B, H, Nq, Nk;                         // queries (rows of Q, O, dO, dQ, stats) and keys (rows of K, V, dK, dV) per sample
     float scale;                              // Dh^-0.5
-    float* part;                              // long query axis only: fp32 partials [chunk][B][Nk][2 H Dh] = dK (unscaled) | dV
+    float* part;                              // long query axis: fp32 partials [chunk][B][Nk][2 H Dh] = dK (unscaled) | dV; long key axis: [chunk][B][Nq][H Dh] = dQ (unscaled)
+    float* cstat;                             // long key axis only: [chunk][B][H][Nq][2] = each query row's maximum and sum of exp(s - maximum) over the chunk's keys
 };
 
 // ---- the steps both forms take
@@ -99,14 +104,17 @@ __device__ __forceinline__ f32x4 tile_qk(const bf16x8 (&a)[ab_steps(DH)], const 
     return acc;
 }
 
-// L = max_j s_j + ln sum_j exp(s_j - max), s = scale * q . k_j, of the query rows 4 lq + i whose fragments are `qf`: two sweeps over the keys
-// (the maximum, then the sum), each reduced over the 16 lanes of an lq.  Every lane of an lq ends with the same four values.
+// mx = max_j s_j and sm = sum_j exp(s_j - mx) over the keys jb <= j < je (je <= Nk), s = scale * q . k_j, of the query rows 4 lq + i whose
+// fragments are `qf`: two sweeps over the keys (the maximum, then the sum), each reduced over the 16 lanes of an lq.  Every lane of an lq ends
+// with the same values.  L = mx + ln sm (so that P = exp(S - L)) when the sweep took every key.
 template <int DH>
-__device__ __forceinline__ void row_lse(const bf16x8 (&qf)[ab_steps(DH)], const bf16_t* Kb, long ldk, int Nk, float scale, int lr, int lq, float (&L)[4]) {
-    float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    for (int j0 = 0; j0 < Nk; j0 += 16) {
+__device__ __forceinline__ void row_max_sum(const bf16x8 (&qf)[ab_steps(DH)], const bf16_t* Kb, long ldk, int jb, int je, int Nk, float scale, int lr,
+                                            int lq, float (&mx)[4], float (&sm)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { mx[i] = -INFINITY; sm[i] = 0.f; }
+    for (int j0 = jb; j0 < je; j0 += 16) {
         const f32x4 sc = tile_qk<DH>(qf, Kb, ldk, j0 + lr, Nk, lq);
-        if (j0 + lr < Nk) {
+        if (j0 + lr < je) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) mx[i] = fmaxf(mx[i], sc[i] * scale);
         }
@@ -115,20 +123,24 @@ __device__ __forceinline__ void row_lse(const bf16x8 (&qf)[ab_steps(DH)], const 
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) mx[i] = fmaxf(mx[i], __shfl_xor(mx[i], o, 64));
-    float sm[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j0 = 0; j0 < Nk; j0 += 16) {
+    for (int j0 = jb; j0 < je; j0 += 16) {
         const f32x4 sc = tile_qk<DH>(qf, Kb, ldk, j0 + lr, Nk, lq);
-        if (j0 + lr < Nk) {
+        if (j0 + lr < je) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) sm[i] += expf(sc[i] * scale - mx[i]);
         }
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) sm[i] += __shfl_xor(sm[i], o, 64);
-        L[i] = mx[i] + logf(sm[i]);
-    }
+}
+template <int DH>
+__device__ __forceinline__ void row_lse(const bf16x8 (&qf)[ab_steps(DH)], const bf16_t* Kb, long ldk, int Nk, float scale, int lr, int lq, float (&L)[4]) {
+    float mx[4], sm[4];
+    row_max_sum<DH>(qf, Kb, ldk, 0, Nk, Nk, scale, lr, lq, mx, sm);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) L[i] = mx[i] + logf(sm[i]);
 }
 
 // D = sum_d dO o O of query row `row`, whose dO fragments are `g`: lane (lr, lq) sums its channels (8 lq .. + 7 of every 32; a zero fragment
@@ -161,9 +173,10 @@ __device__ __forceinline__ void p_ds(const f32x4& sc, const f32x4& dp, float sca
     }
 }
 
-// ---- MFMA form, head dim 32 or 64.  Per query row: L and D to `stats`
-template <int DH>
-__global__ __launch_bounds__(64) void attn_bwd_stats_kernel(const AttnBwdArgs a) {
+// ---- MFMA form, head dim 32 or 64.  Per query row: L and D to `stats`.  WIDE (long key axis): L from the chunks' (maximum, sum) pairs that
+// attn_bwd_chunk_stats_kernel left in a.cstat, combined in chunk order: M = max_c m_c, L = M + ln sum_c s_c exp(m_c - M)
+template <int DH, bool WIDE = false>
+__global__ __launch_bounds__(64) void attn_bwd_stats_kernel(const AttnBwdArgs a, int chunks) {
     constexpr int NS = ab_steps(DH);
     const int lane = threadIdx.x, lr = lane & 15, lq = lane >> 4, q0 = blockIdx.x * AB_T;
     const AttnBwdRoles r = attn_bwd_roles<DH, false>(a, blockIdx.z, blockIdx.y);
@@ -171,7 +184,19 @@ __global__ __launch_bounds__(64) void attn_bwd_stats_kernel(const AttnBwdArgs a)
 #pragma unroll
     for (int s = 0; s < NS; ++s) qf[s] = ld_frag<DH>(r.rowA, r.ld_rowA, q0 + lr, r.NR, s, lq);
     float L[4];                                                         // of query rows q0 + 4 lq + i
-    row_lse<DH>(qf, r.colA, r.ld_colA, r.NC, a.scale, lr, lq, L);
+    if constexpr (WIDE) {
+        const long cs = (long)a.B * a.H * a.Nq * 2;                     // floats of one chunk's table
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float* c = a.cstat + (r.ob + min(q0 + 4 * lq + i, r.NR - 1)) * 2;
+            float M = -INFINITY, s = 0.f;
+            for (int k = 0; k < chunks; ++k) M = fmaxf(M, c[k * cs]);
+            for (int k = 0; k < chunks; ++k) s = fmaf(c[k * cs + 1], expf(c[k * cs] - M), s);      // one chunk: s_0 * exp(0) + 0 = s_0, the bits of row_lse
+            L[i] = M + logf(s);
+        }
+    } else {
+        row_lse<DH>(qf, r.colA, r.ld_colA, r.NC, a.scale, lr, lq, L);
+    }
 #pragma unroll
     for (int s = 0; s < NS; ++s) gf[s] = ld_frag<DH>(r.rowB, r.ld_rowB, q0 + lr, r.NR, s, lq);
     const float d = row_d<DH>(a.O + r.ob * DH, q0 + lr, r.NR, gf, lq);  // of query row q0 + lr
@@ -185,19 +210,42 @@ __global__ __launch_bounds__(64) void attn_bwd_stats_kernel(const AttnBwdArgs a)
     if (lq == 0 && q0 + lr < r.NR) r.st[2 * (q0 + lr) + 1] = d;
 }
 
-// the main kernels of the MFMA form share one body.  PART (key blocks of a long query axis): blockIdx.x = chunk * key blocks + key block; the
-// loop runs over the chunk's AB_CHUNK queries alone and the fp32 sums go to a.part unscaled, for attn_bwd_parts_kernel to add in chunk order
+// long key axis: the maximum and the sum of one chunk of AB_WIDE_CHUNK keys, per (16 queries, chunk): blockIdx.x = chunk * query blocks + query block
+template <int DH>
+__global__ __launch_bounds__(64) void attn_bwd_chunk_stats_kernel(const AttnBwdArgs a) {
+    constexpr int NS = ab_steps(DH);
+    const int lane = threadIdx.x, lr = lane & 15, lq = lane >> 4, nqb = (a.Nq + AB_T - 1) / AB_T;
+    const int chunk = blockIdx.x / nqb, q0 = (blockIdx.x % nqb) * AB_T;
+    const AttnBwdRoles r = attn_bwd_roles<DH, false>(a, blockIdx.z, blockIdx.y);
+    bf16x8 qf[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) qf[s] = ld_frag<DH>(r.rowA, r.ld_rowA, q0 + lr, r.NR, s, lq);
+    float mx[4], sm[4];
+    row_max_sum<DH>(qf, r.colA, r.ld_colA, chunk * AB_WIDE_CHUNK, min((chunk + 1) * AB_WIDE_CHUNK, r.NC), r.NC, a.scale, lr, lq, mx, sm);
+    float* o = a.cstat + ((long)chunk * a.B * a.H * a.Nq + r.ob) * 2;
+    if (lr == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int q = q0 + 4 * lq + i;
+            if (q < r.NR) { o[2 * q] = mx[i]; o[2 * q + 1] = sm[i]; }
+        }
+    }
+}
+
+// the main kernels of the MFMA form share one body.  PART: blockIdx.x = chunk * row blocks + row block; the loop runs over the chunk's columns
+// alone (key blocks of a long query axis: AB_CHUNK queries; query blocks of a long key axis: AB_WIDE_CHUNK keys) and the fp32 sums go to
+// a.part unscaled, for attn_bwd_parts_kernel to add in chunk order
 template <int DH, bool KV, bool PART = false>
 __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
-    static_assert(KV || !PART, "only dK / dV are summed in parts");
+    constexpr int CH = KV ? AB_CHUNK : AB_WIDE_CHUNK;
     constexpr int NS = ab_steps(DH), NT = DH / 16;                      // operand chunks of 32 channels, accumulator tiles of 16
     __shared__ __attribute__((aligned(16))) bf16_t ds_t[AB_T][AB_LDP];
     __shared__ __attribute__((aligned(16))) bf16_t p_t[AB_T][AB_LDP];
     const int lane = threadIdx.x, lr = lane & 15, lq = lane >> 4;
-    const int nrb = PART ? (a.Nk + AB_T - 1) / AB_T : 1, chunk = PART ? blockIdx.x / nrb : 0;
+    const int nrb = PART ? ((KV ? a.Nk : a.Nq) + AB_T - 1) / AB_T : 1, chunk = PART ? blockIdx.x / nrb : 0;
     const int b = blockIdx.z, h = blockIdx.y, r0 = (PART ? blockIdx.x % nrb : blockIdx.x) * AB_T;
     const AttnBwdRoles r = attn_bwd_roles<DH, KV>(a, b, h);
-    const int jb = chunk * AB_CHUNK, je = PART ? min(jb + AB_CHUNK, r.NC) : r.NC;      // the loop's columns
+    const int jb = chunk * CH, je = PART ? min(jb + CH, r.NC) : r.NC;                  // the loop's columns
     bf16x8 fa[NS], fb[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -249,15 +297,16 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnBwdArgs a) {
         }
     }
     if constexpr (PART) {
-        float* o = a.part + ((long)chunk * a.B + b) * a.Nk * (2L * a.H * DH) + h * DH;
+        const long W = (KV ? 2L : 1L) * a.H * DH;                      // a row of partials: dK | dV, or dQ
+        float* o = a.part + ((long)chunk * a.B + b) * r.NR * W + h * DH;
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int row = r0 + 4 * lq + i;
                 if (row < r.NR) {
-                    o[(long)row * (2 * a.H * DH) + 16 * t + lr] = acc1[t][i];
-                    o[(long)row * (2 * a.H * DH) + a.H * DH + 16 * t + lr] = acc2[t][i];
+                    o[(long)row * W + 16 * t + lr] = acc1[t][i];
+                    if (KV) o[(long)row * W + a.H * DH + 16 * t + lr] = acc2[t][i];
                 }
             }
         return;
@@ -280,7 +329,7 @@ template <int DH>
 static int attn_bwd_launch(const AttnBwdArgs& a, hipStream_t s) {
     const dim3 grid((unsigned)((a.Nq + AB_T - 1) / AB_T), (unsigned)a.H, (unsigned)a.B), block(64);      // query blocks
     const dim3 grid_kv((unsigned)((a.Nk + AB_T - 1) / AB_T), (unsigned)a.H, (unsigned)a.B);               // key blocks
-    hipLaunchKernelGGL(attn_bwd_stats_kernel<DH>, grid, block, 0, s, a);
+    hipLaunchKernelGGL(attn_bwd_stats_kernel<DH>, grid, block, 0, s, a, 1);
     int rc = ldt_check_launch("attention_bwd (row statistics)");
     if (rc != LDT_OK) return rc;
     hipLaunchKernelGGL((attn_bwd_kernel<DH, false>), grid, block, 0, s, a);
@@ -294,15 +343,17 @@ static int attn_bwd_launch(const AttnBwdArgs& a, hipStream_t s) {
 // kernels above: their grids tile Nq.  dK / dV as above would be one wave per 16 keys walking every query (two waves per (sample, head), 64
 // trips each, at the decoder's shape): instead one wave takes (16 keys, AB_CHUNK queries) and leaves fp32 partials, and the kernel below adds
 // them in chunk order, scales dK and rounds to bf16.  Still no atomics, and the order is fixed by AB_CHUNK alone: the same bits on every run
-// and every device.  One thread per element of a [Nk][2 H Dh] row pair dK | dV.
-__global__ __launch_bounds__(256) void attn_bwd_parts_kernel(const AttnBwdArgs a, int dh, int chunks) {
-    const int C = a.H * dh, c = blockIdx.x * 256 + threadIdx.x, row = blockIdx.y, b = blockIdx.z;
-    if (c >= 2 * C) return;
-    const long chunk_stride = (long)a.B * a.Nk * (2L * C);
-    const float* p = a.part + ((long)b * a.Nk + row) * (2L * C) + c;
+// and every device.  One thread per element of a [Nk][2 H Dh] row pair dK | dV (kv), or of a [Nq][H Dh] row of dQ (long key axis, below);
+// gridDim.y = the rows per sample.
+__global__ __launch_bounds__(256) void attn_bwd_parts_kernel(const AttnBwdArgs a, int dh, int chunks, bool kv) {
+    const int C = a.H * dh, W = kv ? 2 * C : C, c = blockIdx.x * 256 + threadIdx.x, row = blockIdx.y, rows = gridDim.y, b = blockIdx.z;
+    if (c >= W) return;
+    const long chunk_stride = (long)a.B * rows * W;
+    const float* p = a.part + ((long)b * rows + row) * W + c;
     float s = 0.f;
     for (int k = 0; k < chunks; ++k) s += p[k * chunk_stride];
-    if (c < C) a.dK[(long)b * a.dkv_bs + (long)row * a.lddk + c] = (bf16_t)(s * a.scale);
+    if (!kv) a.dQ[(long)b * a.dq_bs + (long)row * a.lddq + c] = (bf16_t)(s * a.scale);
+    else if (c < C) a.dK[(long)b * a.dkv_bs + (long)row * a.lddk + c] = (bf16_t)(s * a.scale);
     else a.dV[(long)b * a.dkv_bs + (long)row * a.lddv + (c - C)] = (bf16_t)s;
 }
 
@@ -310,7 +361,7 @@ template <int DH>
 static int attn_bwd_long_launch(const AttnBwdArgs& a, hipStream_t s) {
     const int chunks = (a.Nq + AB_CHUNK - 1) / AB_CHUNK, nkb = (a.Nk + AB_T - 1) / AB_T;
     const dim3 grid((unsigned)((a.Nq + AB_T - 1) / AB_T), (unsigned)a.H, (unsigned)a.B), block(64);
-    hipLaunchKernelGGL(attn_bwd_stats_kernel<DH>, grid, block, 0, s, a);
+    hipLaunchKernelGGL(attn_bwd_stats_kernel<DH>, grid, block, 0, s, a, 1);
     int rc = ldt_check_launch("attention_bwd_long (row statistics)");
     if (rc != LDT_OK) return rc;
     hipLaunchKernelGGL((attn_bwd_kernel<DH, false>), grid, block, 0, s, a);
@@ -319,8 +370,33 @@ static int attn_bwd_long_launch(const AttnBwdArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((attn_bwd_kernel<DH, true, true>), dim3((unsigned)(nkb * chunks), (unsigned)a.H, (unsigned)a.B), block, 0, s, a);
     rc = ldt_check_launch("attention_bwd_long (dK, dV partials)");
     if (rc != LDT_OK) return rc;
-    hipLaunchKernelGGL(attn_bwd_parts_kernel, dim3((unsigned)((2 * a.H * DH + 255) / 256), (unsigned)a.Nk, (unsigned)a.B), dim3(256), 0, s, a, DH, chunks);
+    hipLaunchKernelGGL(attn_bwd_parts_kernel, dim3((unsigned)((2 * a.H * DH + 255) / 256), (unsigned)a.Nk, (unsigned)a.B), dim3(256), 0, s, a, DH, chunks, true);
     return ldt_check_launch("attention_bwd_long (dK, dV)");
+}
+
+// ---- long key axis (ldt_attention_bwd_wide: the Compressor's posterior blocks, 32 latent tokens on 2048 set points), head dim 32: the mirror
+// image.  dK / dV are the key-block kernel above: its grid tiles Nk.  Row statistics and dQ as above would be one wave per 16 queries walking
+// every key (two waves per (sample, head), 2 x 128 + 64 trips each, at the posterior's shape): instead one wave takes (16 queries,
+// AB_WIDE_CHUNK keys).  The statistics: each chunk's maximum and sum, then combined in chunk order (attn_bwd_stats_kernel<DH, true>).  dQ:
+// fp32 partials that attn_bwd_parts_kernel adds in chunk order, scales and rounds to bf16.  No atomics; the order is fixed by AB_WIDE_CHUNK.
+template <int DH>
+static int attn_bwd_wide_launch(const AttnBwdArgs& a, hipStream_t s) {
+    const int chunks = (a.Nk + AB_WIDE_CHUNK - 1) / AB_WIDE_CHUNK, nqb = (a.Nq + AB_T - 1) / AB_T, nkb = (a.Nk + AB_T - 1) / AB_T;
+    const dim3 grid((unsigned)nqb, (unsigned)a.H, (unsigned)a.B), grid_c((unsigned)(nqb * chunks), (unsigned)a.H, (unsigned)a.B), block(64);
+    hipLaunchKernelGGL(attn_bwd_chunk_stats_kernel<DH>, grid_c, block, 0, s, a);
+    int rc = ldt_check_launch("attention_bwd_wide (chunk statistics)");
+    if (rc != LDT_OK) return rc;
+    hipLaunchKernelGGL((attn_bwd_stats_kernel<DH, true>), grid, block, 0, s, a, chunks);
+    rc = ldt_check_launch("attention_bwd_wide (row statistics)");
+    if (rc != LDT_OK) return rc;
+    hipLaunchKernelGGL((attn_bwd_kernel<DH, false, true>), grid_c, block, 0, s, a);
+    rc = ldt_check_launch("attention_bwd_wide (dQ partials)");
+    if (rc != LDT_OK) return rc;
+    hipLaunchKernelGGL(attn_bwd_parts_kernel, dim3((unsigned)((a.H * DH + 255) / 256), (unsigned)a.Nq, (unsigned)a.B), dim3(256), 0, s, a, DH, chunks, false);
+    rc = ldt_check_launch("attention_bwd_wide (dQ)");
+    if (rc != LDT_OK) return rc;
+    hipLaunchKernelGGL((attn_bwd_kernel<DH, true>), dim3((unsigned)nkb, (unsigned)a.H, (unsigned)a.B), block, 0, s, a);
+    return ldt_check_launch("attention_bwd_wide (dK, dV)");
 }
 
 // ---- narrow form, head dim 8 or 16.  Query blocks: first the statistics of the block's 16 query rows, which go to `stats` for the key blocks
@@ -433,7 +509,7 @@ static int attn_bwd_run(const char* name, Admit admit, const uint16_t* Q, int64_
                         const uint16_t* V, int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats,
                         uint16_t* dQ, int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
                         int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim, bool store8, void* stream,
-                        float* part = nullptr) {
+                        float* part = nullptr, bool wide = false) {
     LDT_REQUIRE(Q && K && V && O && dO && stats && dQ && dK && dV, LDT_EARG, "%s: null pointer", name);
     const int rc = admit();
     if (rc != LDT_OK) return rc;
@@ -455,11 +531,15 @@ static int attn_bwd_run(const char* name, Admit admit, const uint16_t* Q, int64_
     a.dQ = reinterpret_cast<bf16_t*>(dQ); a.lddq = lddq; a.dq_bs = dq_batch_stride;
     a.dK = reinterpret_cast<bf16_t*>(dK); a.lddk = lddk; a.dV = reinterpret_cast<bf16_t*>(dV); a.lddv = lddv; a.dkv_bs = dkv_batch_stride;
     a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.scale = 1.0f / sqrtf((float)head_dim);      // exactly 0.125 at 64
-    a.part = part;
+    a.part = part; a.cstat = nullptr;
+    if (wide) {                                                         // scratch = the chunk statistics, then the dQ partials (include/ldt_hip.h)
+        a.cstat = part;
+        a.part = part + (long)((Nk + AB_WIDE_CHUNK - 1) / AB_WIDE_CHUNK) * B * H * Nq * 2;
+    }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (head_dim) {
         case 64: return attn_bwd_launch<64>(a, s);
-        case 32: return part ? attn_bwd_long_launch<32>(a, s) : attn_bwd_launch<32>(a, s);
+        case 32: return wide ? attn_bwd_wide_launch<32>(a, s) : part ? attn_bwd_long_launch<32>(a, s) : attn_bwd_launch<32>(a, s);
         case 16: return attn_bwd_narrow_launch<16>(a, s);
         case 8: return attn_bwd_narrow_launch<8>(a, s);
     }
@@ -528,4 +608,24 @@ extern "C" int ldt_attention_bwd_long(const uint16_t* Q, int64_t ldq, int64_t q_
     };
     return attn_bwd_run("attention_bwd_long", admit, Q, ldq, q_batch_stride, K, ldk, V, ldv, kv_batch_stride, O, dO, stats, dQ, lddq,
                         dq_batch_stride, dK, lddk, dV, lddv, dkv_batch_stride, B, H, Nq, Nk, head_dim, false, stream, scratch);
+}
+
+// The operand contract of ldt_attention_bwd_cross with a key axis of up to 8192 rows, head width 32 alone: the mirror image of the above.
+extern "C" int ldt_attention_bwd_wide(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk, const uint16_t* V,
+                                      int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats, uint16_t* dQ,
+                                      int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,
+                                      int64_t dkv_batch_stride, int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim, float* scratch,
+                                      int64_t scratch_len, void* stream) {
+    auto admit = [&]() -> int {
+        LDT_REQUIRE(scratch, LDT_EARG, "attention_bwd_wide: null pointer");
+        LDT_REQUIRE(head_dim == 32, LDT_ESHAPE, "attention_bwd_wide: head_dim %d (32 only)", head_dim);
+        LDT_REQUIRE(Nq > 0 && Nq <= 512 && Nk > 0 && Nk <= LDT_ATTN_BWD_WIDE_MAX_KEYS, LDT_ESHAPE,
+                    "attention_bwd_wide: Nq %d, Nk %d (1 <= Nq <= 512, 1 <= Nk <= %d)", Nq, Nk, LDT_ATTN_BWD_WIDE_MAX_KEYS);
+        LDT_REQUIRE(B > 0 && H > 0 && scratch_len >= ((int64_t)(Nk + AB_WIDE_CHUNK - 1) / AB_WIDE_CHUNK) * B * H * Nq * (2 + head_dim), LDT_EARG,
+                    "attention_bwd_wide: scratch holds %ld floats, ceil(Nk / %d) * B * H * Nq * (2 + head_dim) are needed", (long)scratch_len,
+                    AB_WIDE_CHUNK);
+        return LDT_OK;
+    };
+    return attn_bwd_run("attention_bwd_wide", admit, Q, ldq, q_batch_stride, K, ldk, V, ldv, kv_batch_stride, O, dO, stats, dQ, lddq,
+                        dq_batch_stride, dK, lddk, dV, lddv, dkv_batch_stride, B, H, Nq, Nk, head_dim, false, stream, scratch, true);
 }

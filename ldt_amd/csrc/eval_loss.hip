@@ -1,5 +1,6 @@
 // Loss arithmetic of held-out evaluation, between kernels that already exist (encode, Score forward, Chamfer):
 //   ldt_reparam_kl   posterior draw + per-element log q(z), KL and the per-sample KL sum   (model/Compressor/Network.py:12-29,221-224)
+//   ldt_reparam_kl_bwd   its backward for training: d(draw) and d(kl_scale x sum kl) with respect to mu | logvar, in closed form
 //   ldt_diffuse_q    x_t = m_t x_0 + sqrt(var_t) eta with per-sample scalars, eta injected or drawn from the Philox stream
 //                    (diffusion/diffusion_continuous.py:78-81; trainer/Latent_SDE_Trainer.py:79-81)
 //   ldt_dsm_loss     denoising score-matching distance, per-sample and overall mean   (trainer/Latent_SDE_Trainer.py:83-87)
@@ -104,6 +105,53 @@ extern "C" int ldt_reparam_kl(const float* post, const float* noise, float* out,
         hipLaunchKernelGGL(reparam_kl_kernel<1>, dim3((unsigned)B), dim3(EVAL_WG), 0, s, post, noise, out, (long)ldo, mu_out, logvar_out, kl_out,
                            logqz_out, kl_sample_sum, (long)rows_per_sample, z, lo, hi);
     return ldt_check_launch("reparam_kl");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Backward of the draw and of kl_scale x sum(kl) (include/ldt_hip.h), one thread per V adjacent elements of a row.  log q(z) depends on mu and
+// logvar only through -logvar / 2 once eps = mu + s n is put in ((eps - mu)^2 / exp(logvar) = n^2), and -log p(z) = eps^2 / 2 + const.
+template <int V>
+__global__ __launch_bounds__(256) void reparam_kl_bwd_kernel(const float* __restrict__ post, const float* __restrict__ noise,
+                                                             const float* __restrict__ d_eps, long ldd, float kl_scale, float* __restrict__ dpost,
+                                                             long rows, int z, float lo, float hi) {
+    typedef typename Pack<V>::T vec;
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= rows * z / V) return;
+    const long e = g * V, r = e / z;
+    const int c = (int)(e % z);
+    const vec pm = ld<V>(post + r * 2 * z + c);
+    const vec pl = ld<V>(post + r * 2 * z + z + c);
+    const vec nz = ld<V>(noise + r * z + c);
+    const vec de = ld<V>(d_eps + r * ldd + c);
+    vec v_mu, v_lv;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const float raw = lane<V>(pl, j), n = lane<V>(nz, j);
+        const float lv = fminf(fmaxf(raw, lo), hi);
+        const float eps = reparam_eps(lane<V>(pm, j), lv, n);
+        const float gj = fmaf(kl_scale, eps, lane<V>(de, j));
+        const float dlv = fmaf(gj, 0.5f * (n * expf(lv / 2.f)), -0.5f * kl_scale);
+        set_lane<V>(v_mu, j, gj);
+        set_lane<V>(v_lv, j, raw >= lo && raw <= hi ? dlv : 0.f);
+    }
+    st<V>(dpost + r * 2 * z + c, v_mu);
+    st<V>(dpost + r * 2 * z + z + c, v_lv);
+}
+
+extern "C" int ldt_reparam_kl_bwd(const float* post, const float* noise, const float* d_eps, int64_t ldd, float kl_scale, float* dpost,
+                                  int64_t rows, int32_t z, float lo, float hi, void* stream) {
+    LDT_REQUIRE(post && noise && d_eps && dpost, LDT_EARG, "reparam_kl_bwd: null pointer");
+    LDT_REQUIRE(rows > 0 && z > 0 && ldd >= z && rows <= (1L << 40) / z, LDT_ESHAPE, "reparam_kl_bwd: bad shape (rows %ld, z %d, ldd %ld)", (long)rows, z,
+                (long)ldd);
+    const bool vec = z % 4 == 0 && ldd % 4 == 0 && ldt_aligned16(post) && ldt_aligned16(noise) && ldt_aligned16(d_eps) && ldt_aligned16(dpost);
+    const long threads = rows * z / (vec ? 4 : 1), wgs = (threads + 255) / 256;
+    LDT_REQUIRE(wgs <= 0x7fffffffL, LDT_ESHAPE, "reparam_kl_bwd: %ld elements", (long)rows * z);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (vec)
+        hipLaunchKernelGGL(reparam_kl_bwd_kernel<4>, dim3((unsigned)wgs), dim3(256), 0, s, post, noise, d_eps, (long)ldd, kl_scale, dpost, (long)rows, z, lo, hi);
+    else
+        hipLaunchKernelGGL(reparam_kl_bwd_kernel<1>, dim3((unsigned)wgs), dim3(256), 0, s, post, noise, d_eps, (long)ldd, kl_scale, dpost, (long)rows, z, lo, hi);
+    return ldt_check_launch("reparam_kl_bwd");
 }
 
 // ------------------------------------------------------------------------------------------------

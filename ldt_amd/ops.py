@@ -1008,6 +1008,45 @@ def attention_bwd_long(q, k, v, o, do, B, H, Nq, Nk, dq_out=None, dkv_out=None, 
                           extra=lambda Cc: (_p(scratch), scratch.numel()), stats_out=stats_out)
 
 
+def attention_bwd_wide_scratch(B, H, Nq, Nk, head_dim=32):
+    """floats of fp32 scratch attention_bwd_wide needs: per chunk of keys, each query row's (maximum, sum) [B, H, Nq, 2] and one
+    [B, Nq, H * head_dim] partial of dQ."""
+    return -(-Nk // _lib.ATTN_BWD_WIDE_CHUNK) * B * H * Nq * (2 + head_dim)
+
+
+def attention_bwd_wide(q, k, v, o, do, B, H, Nq, Nk, dq_out=None, dkv_out=None, head_dim=32, scratch=None, stats_out=None):
+    """attention_bwd_cross's contract on a long KEY axis (ldt_attention_bwd_wide): head_dim 32 only, Nq <= ATTN_BWD_WIDE_MAX_QUERIES,
+    Nk <= ATTN_BWD_WIDE_MAX_KEYS.  The row statistics and dQ are formed per chunk of ATTN_BWD_WIDE_CHUNK keys in `scratch` (fp32, allocated
+    here when not given: attention_bwd_wide_scratch floats, laid out [chunk, B, H, Nq, 2] = (maximum, sum) then [chunk, B, Nq, H * 32] =
+    dQ unscaled) and combined in chunk order.  stats_out: as attention_bwd_long's."""
+    need = attention_bwd_wide_scratch(B, H, Nq, Nk, head_dim)
+    if scratch is None:
+        scratch = torch.empty((need,), dtype=torch.float32, device=q.device)
+    _need(scratch, torch.float32, "scratch")
+    if not scratch.is_contiguous():
+        raise ValueError("attention_bwd_wide: scratch must be contiguous")
+    return _attention_bwd("attention_bwd_wide", "ldt_attention_bwd_wide", q, k, v, o, do, B, H, (Nq, Nk), head_dim,
+                          lambda Cc: (_bf16_rows_out(dq_out, B * Nq, Cc, q.device, "attention_bwd_wide: dq_out"),)
+                          + _bf16_rows_out(dkv_out, B * Nk, 2 * Cc, q.device, "attention_bwd_wide: dkv_out").split(Cc, 1),
+                          extra=lambda Cc: (_p(scratch), scratch.numel()), stats_out=stats_out)
+
+
+def reparam_kl_bwd(post, noise, d_eps, kl_scale, lo, hi):
+    """Backward of `reparam_kl`'s draw and of kl_scale * kl.sum() (ldt_reparam_kl_bwd): post fp32 [rows, 2z] = mu | logvar as stored, noise
+    [rows, z], d_eps [rows, z] (strided slice ok) -> dpost fp32 [rows, 2z] = dmu | dlogvar, exactly 0 where logvar is outside [lo, hi]."""
+    _need(post, torch.float32, "post"); _need(noise, torch.float32, "noise"); _need(d_eps, torch.float32, "d_eps")
+    if post.dim() != 2 or post.shape[1] % 2:
+        raise ValueError("reparam_kl_bwd: post %s is not [rows, 2z]" % (tuple(post.shape),))
+    rows, z = post.shape[0], post.shape[1] // 2
+    if not (post.is_contiguous() and noise.is_contiguous() and noise.numel() == rows * z and tuple(d_eps.shape) == (rows, z)
+            and d_eps.stride(1) == 1 and d_eps.stride(0) >= z):
+        raise ValueError("reparam_kl_bwd: post [rows, 2z] and noise [rows, z] contiguous, d_eps [rows, z] with unit column stride")
+    out = torch.empty_like(post)
+    check(lib().ldt_reparam_kl_bwd(_p(post), _p(noise), _p(d_eps), d_eps.stride(0), float(kl_scale), _p(out), rows, z, float(lo), float(hi),
+                                   stream_ptr()), "ldt_reparam_kl_bwd")
+    return out
+
+
 def chamfer_nn(x1, x2):
     """x1 [B, n, 3], x2 [B, m, 3] fp32 -> (d1 [B, n], idx1 [B, n] int32, d2 [B, m], idx2 [B, m] int32): squared nearest-neighbour
     distances both ways (bit-equal to chamfer(x1, x2)'s dr and dl) with the lowest index that attains each."""
