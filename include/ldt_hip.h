@@ -70,8 +70,8 @@ int ldt_gemm_bf16(int32_t epilogue, const uint16_t* X, int64_t ldx, const uint16
  *     LDT_EPI_GELU_BF16; the row statistics are those of the K = stats_parts*256 input channels (K <= 1024).
  * ln_scale / fold_S / fold_C / gate are addressed base + (*step_ptr) * their step stride (step_ptr NULL = 0).
  * stats_parts selects the statistics granule and with it the kernel family: N/256 (producer) | K/256 (consumer) partials per row — the
- *     256-tile kernels: M, N multiples of 256, K >= 256, K <= 1024 for the consumer; N/32 | K/32 — the small-batch kernels (batches
- *     of 1-2 k rows, where every GEMM of a Score block runs 64-wide tiles): M a multiple of 128, N of 64.  A producer and the consumer
+ *     256-tile kernels: M, N multiples of 256, K >= 256, K <= 1024 for the consumer; N/32 | K/32 — the mid-size tile kernels (the fold
+ *     route of batches of 1-2 k rows, whose GEMMs stay below the 256-tile kernels' fill rule): M a multiple of 128, N of 64.  A producer and the consumer
  *     of its statistics must use the same granule.  The host builds S and C in fp32 from the SAME bf16 W the GEMM reads. */
 int ldt_gemm_resid_lnstats(const uint16_t* X, int64_t ldx, const uint16_t* W, int64_t ldw, const float* bias,
                            float* out, int64_t ldo, const float* gate, int64_t gate_sample_stride,

@@ -40,6 +40,26 @@ extern "C" int ldt_abi_version(void) { return LDT_ABI_VERSION; }
         if (_rc != LDT_OK) return _rc; \
     } while (0)
 
+// GemmArgs by name: the base problem, then what an epilogue or a fused form adds (everything else stays zero)
+static GemmArgs gemm_args(const bf16_t* X, long ldx, const bf16_t* W, long ldw, const float* bias, void* out, long ldo, int M, int N, int K, int max_wgs) {
+    GemmArgs a{};
+    a.X = X; a.ldx = ldx; a.W = W; a.ldw = ldw; a.bias = bias; a.out = out; a.ldo = ldo; a.M = M; a.N = N; a.K = K; a.max_wgs = max_wgs;
+    return a;
+}
+static void gemm_add_gated_resid(GemmArgs& a, const float* resid, long ldr, const float* gate, long sample_stride, int rows_per_sample, const int* step_ptr, long step_stride) {
+    a.resid = resid; a.ldr = ldr; a.gate = gate; a.gate_sample_stride = sample_stride; a.rows_per_sample = rows_per_sample;
+    a.step_ptr = step_ptr; a.gate_step_stride = step_stride;
+}
+static void gemm_add_fold_producer(GemmArgs& a, bf16_t* xs, long ldxs, const float* ln_scale, long ln_step_stride, float* stats_out, int stats_parts) {
+    a.xs = xs; a.ldxs = ldxs; a.ln_scale = ln_scale; a.ln_step_stride = ln_step_stride; a.stats_out = stats_out; a.stats_parts = stats_parts;
+}
+static void gemm_add_fold_consumer(GemmArgs& a, const float* stats_in, int stats_parts, const float* fold_S, const float* fold_C, long step_stride, const int* step_ptr) {
+    a.stats_in = stats_in; a.stats_parts = stats_parts; a.fold_S = fold_S; a.fold_C = fold_C; a.fold_step_stride = step_stride; a.step_ptr = step_ptr;
+}
+static void gemm_add_attention(GemmArgs& a, bf16_t* attn_o, float scale_log2e, const bf16_t* k, const bf16_t* v, long ldkv, long kv_batch_stride) {
+    a.attn_o = attn_o; a.attn_scale_log2e = scale_log2e; a.attn_k = k; a.attn_v = v; a.attn_ldkv = ldkv; a.attn_kv_batch_stride = kv_batch_stride;
+}
+
 // ------------------------------------------------------------------------------ primitive ops
 extern "C" int ldt_cast_pad_bf16(const float* src, int64_t ld_src, uint16_t* dst, int64_t ld_dst, int64_t rows,
                                  int32_t cols, int32_t cols_pad, void* stream) {
@@ -53,8 +73,9 @@ extern "C" int ldt_gemm_bf16(int32_t epilogue, const uint16_t* X, int64_t ldx, c
                              int32_t rows_per_sample, const int32_t* step_ptr, int64_t gate_step_stride,
                              int32_t M, int32_t N, int32_t K, void* stream) {
     LDT_REQUIRE(X && W && out, LDT_EARG, "gemm: null pointer");
-    GemmArgs a{BF(X), ldx, BF(W), ldw, bias, out, ldo, resid, ldr, BF(skip), ldskip, gate, gate_sample_stride,
-               rows_per_sample, step_ptr, gate_step_stride, M, N, K};
+    GemmArgs a = gemm_args(BF(X), ldx, BF(W), ldw, bias, out, ldo, M, N, K, 0);
+    gemm_add_gated_resid(a, resid, ldr, gate, gate_sample_stride, rows_per_sample, step_ptr, gate_step_stride);
+    a.skip = BF(skip); a.lds_ = ldskip;
     return ldt_gemm_launch(epilogue, &a, ST(stream));
 }
 
@@ -65,9 +86,9 @@ extern "C" int ldt_gemm_resid_lnstats(const uint16_t* X, int64_t ldx, const uint
                                       int64_t ln_step_stride, int32_t M, int32_t N, int32_t K, int32_t stats_parts, void* stream) {
     LDT_REQUIRE(X && W && out && xs && ln_scale && stats_out, LDT_EARG, "gemm_resid_lnstats: null pointer");
     LDT_REQUIRE(stats_parts == N / 256 || stats_parts == N / 32, LDT_EARG, "gemm_resid_lnstats: stats_parts=%d is neither N/256 nor N/32 (N=%d)", stats_parts, N);
-    GemmArgs a{BF(X), ldx, BF(W), ldw, bias, out, ldo, out, ldo, nullptr, 0, gate, gate_sample_stride, rows_per_sample, step_ptr,
-               gate_step_stride, M, N, K, BFM(xs), ldxs, ln_scale, ln_step_stride, stats_out};
-    a.stats_parts = stats_parts;
+    GemmArgs a = gemm_args(BF(X), ldx, BF(W), ldw, bias, out, ldo, M, N, K, 0);
+    gemm_add_gated_resid(a, out, ldo, gate, gate_sample_stride, rows_per_sample, step_ptr, gate_step_stride);
+    gemm_add_fold_producer(a, BFM(xs), ldxs, ln_scale, ln_step_stride, stats_out, stats_parts);
     return ldt_gemm_lnfold_launch(EPI_RESID_F32, &a, ST(stream));
 }
 
@@ -77,8 +98,8 @@ extern "C" int ldt_gemm_lnfold(int32_t epilogue, const uint16_t* Xs, int64_t ldx
                                void* stream) {
     LDT_REQUIRE(Xs && W && out && stats_in && fold_S && fold_C, LDT_EARG, "gemm_lnfold: null pointer");
     LDT_REQUIRE(stats_parts == K / 256 || stats_parts == K / 32, LDT_EARG, "gemm_lnfold: stats_parts=%d is neither K/256 nor K/32 (K=%d)", stats_parts, K);
-    GemmArgs a{BF(Xs), ldx, BF(W), ldw, nullptr, out, ldo, nullptr, 0, nullptr, 0, nullptr, 0, 0, step_ptr, 0, M, N, K,
-               nullptr, 0, nullptr, 0, nullptr, stats_in, stats_parts, fold_S, fold_C, fold_step_stride};
+    GemmArgs a = gemm_args(BF(Xs), ldx, BF(W), ldw, nullptr, out, ldo, M, N, K, 0);
+    gemm_add_fold_consumer(a, stats_in, stats_parts, fold_S, fold_C, fold_step_stride, step_ptr);
     return ldt_gemm_lnfold_launch(epilogue, &a, ST(stream));
 }
 
@@ -258,10 +279,7 @@ extern "C" int ldt_emd_approx(const float* x, const float* y, int32_t S, int32_t
 
 // ------------------------------------------------------------------------------ Score forward
 extern "C" int ldt_score_lnfold_route(int32_t M, int32_t D, int32_t F, int32_t gemm_wgs) {
-    if (M <= 0 || D <= 0 || F <= 0 || D % 256 != 0 || D > 1024 || F % 256 != 0) return 0;
-    if (ldt_gemm_lnfold_v1_route(M, D, F, gemm_wgs)) return 2;
-    const int lim = ldt_wg_limit(gemm_wgs);
-    return (M % 256 == 0 && (long)(M / 256) * (D / 256) * 8 >= (long)lim * 5) ? 1 : 0;
+    return ldt_score_fold_decide(M, D, F, gemm_wgs).route;
 }
 
 static int check_plan(const ldt_score_plan* p) {
@@ -330,12 +348,10 @@ static int qkv_attention_step(const QkvAttnStep& q, hipStream_t s, Prof* prof) {
     const int D = q.hidden, T = q.tokens, dh = D / q.heads;
     const bool cross = q.kv != nullptr, folded = q.stats != nullptr;
     const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-    GemmArgs gq{q.X, q.ldx, q.W, q.ldw, q.bias, q.QKV, 3L * D, nullptr, 0, nullptr, 0, nullptr, 0, 0, folded ? q.step_ptr : nullptr, 0,
-                q.B * T, cross ? D : 3 * D, q.K};
-    if (folded) { gq.stats_in = q.stats; gq.stats_parts = q.stats_parts; gq.fold_S = q.fold_S; gq.fold_C = q.fold_C; gq.fold_step_stride = q.fold_step_stride; }
-    gq.max_wgs = q.max_wgs;
-    gq.attn_o = q.attn_o; gq.attn_scale_log2e = scale_log2e;
-    if (cross) { gq.attn_k = q.kv; gq.attn_v = q.kv + D; gq.attn_ldkv = q.ldkv; gq.attn_kv_batch_stride = q.kv_batch_stride; }
+    GemmArgs gq = gemm_args(q.X, q.ldx, q.W, q.ldw, q.bias, q.QKV, 3L * D, q.B * T, cross ? D : 3 * D, q.K, q.max_wgs);
+    if (folded) gemm_add_fold_consumer(gq, q.stats, q.stats_parts, q.fold_S, q.fold_C, q.fold_step_stride, q.step_ptr);
+    if (cross) gemm_add_attention(gq, q.attn_o, scale_log2e, q.kv, q.kv + D, q.ldkv, q.kv_batch_stride);
+    else gemm_add_attention(gq, q.attn_o, scale_log2e, nullptr, nullptr, 0, 0);
     int fst = LDT_OK;
     bool took = false;
     // projection + attention in one launch, q | k | v never reach HBM: 32 x 32 tokens against the condition (gemm_mid.hip, mid_epilogue_xattn);
@@ -375,8 +391,11 @@ extern "C" int ldt_qkv_attention(const uint16_t* X, int64_t ldx, const uint16_t*
     LDT_REQUIRE(dh == 8 || dh == 16 || dh == 32 || dh == 64, LDT_ESHAPE, "qkv_attention: head dim %d not built (8, 16, 32, 64)", dh);
     LDT_REQUIRE(!kv_cond || (cond_tokens > 0 && !stats), LDT_EARG, "qkv_attention: cross-attention needs cond_tokens and has no folded form");
     LDT_REQUIRE(!stats || (fold_S && fold_C && stats_parts > 0 && !bias), LDT_EARG, "qkv_attention: the folded form needs fold_S, fold_C, stats_parts and takes no bias (it is part of fold_C)");
-    QkvAttnStep q{BF(X), ldx, BF(W), ldw, bias, stats, stats_parts, fold_S, fold_C, fold_step_stride, BF(kv_cond), ldkv, kv_batch_stride,
-                  BFM(O), BFM(QKV), B, tokens, cond_tokens, hidden, heads, K, max_wgs, step_ptr};
+    QkvAttnStep q{};
+    q.X = BF(X); q.ldx = ldx; q.W = BF(W); q.ldw = ldw; q.bias = bias;
+    q.stats = stats; q.stats_parts = stats_parts; q.fold_S = fold_S; q.fold_C = fold_C; q.fold_step_stride = fold_step_stride;
+    q.kv = BF(kv_cond); q.ldkv = ldkv; q.kv_batch_stride = kv_batch_stride; q.attn_o = BFM(O); q.QKV = BFM(QKV);
+    q.B = B; q.tokens = tokens; q.cond_tokens = cond_tokens; q.hidden = hidden; q.heads = heads; q.K = K; q.max_wgs = max_wgs; q.step_ptr = step_ptr;
     return qkv_attention_step(q, ST(stream), nullptr);
 }
 
@@ -389,23 +408,22 @@ static int score_forward_impl(const ldt_score_plan* p, const float* x, float* ep
     // LN folding (gemm256_tile.h): with batch-shared modulation (unconditional sampling) the LayerNorm + modulate between a
     // residual GEMM and the next projection is folded into the two GEMMs' epilogues; the host supplies the per-step
     // S / C tables (plan->fold) when that pays (whole 256x256 tiles that fill the chip: Score.can_fold).
-    // Small batches whose GEMMs all run the v1 kernels fold through those (statistics per 32 columns), the rest through the 256-tile kernel.
-    const bool fold_v1 = ldt_gemm_lnfold_v1_route(M, D, F, p->gemm_wgs);
-    bool fold = p->fold && p->stats && sstr == 0 && (M % 256 == 0 || fold_v1) && D % 256 == 0 && D <= 1024 && F % 256 == 0;
+    // Small batches fold through the mid-size tile kernels (statistics per 32 columns), the rest through the 256-tile kernel, below its fill rule too.
+    const ScoreFold sf = ldt_score_fold_decide(M, D, F, p->gemm_wgs);
+    bool fold = p->fold && p->stats && sstr == 0 && (sf.route == SCORE_FOLD_MID || sf.shape_256);
     for (int l = 0; l < p->blocks && fold; ++l) fold = !p->kv_cond[l];
-    const int sparts = fold_v1 ? D / 32 : D / 256;              // row-statistics partials per row in plan->stats ([sparts][M][2])
+    const int sparts = D / sf.granule;                          // row-statistics partials per row in plan->stats ([sparts][M][2])
     const long fstep = p->fold_step_stride, fblk = 6L * D + 2L * F;   // per block: S_qkv[3D] | C_qkv[3D] | S_up[F] | C_up[F]
     // ln_in (score.py:136-137): latents fp32 -> bf16 (K padded) -> X fp32
     LAUNCH(LDT_PROF_OTHER, ldt_cast_pad_launch(x, p->z_dim, BFM(p->xin), p->z_pad, M, p->z_dim, p->z_pad, s));
-    {
-        GemmArgs g{BF(p->xin), p->z_pad, BF(p->w_in), p->z_pad, p->b_in, p->X, D, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, 0, M, D, p->z_pad};
-        g.max_wgs = p->gemm_wgs; LAUNCH(LDT_PROF_GEMM_IO, ldt_gemm_launch(LDT_EPI_F32, &g, s));
-    }
+    const GemmArgs g_in = gemm_args(BF(p->xin), p->z_pad, BF(p->w_in), p->z_pad, p->b_in, p->X, D, M, D, p->z_pad, p->gemm_wgs);
+    LAUNCH(LDT_PROF_GEMM_IO, ldt_gemm_launch(LDT_EPI_F32, &g_in, s));
     for (int l = 0; l < p->blocks; ++l) {                       // score.py:148-149, layers.py:212-219
         const float* m = p->mod + (long)l * 6 * D;              // shift_msa|scale_msa|gate_msa|shift_mlp|scale_mlp|gate_mlp
         const float* fl = fold ? p->fold + (long)l * fblk : nullptr;
-        QkvAttnStep qa{BF(p->Hb), D, nullptr, D, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, 0, BFM(p->Ob), BFM(p->QKV),
-                       p->batch, T, p->cond_tokens, D, p->heads, D, p->gemm_wgs, step_ptr};
+        QkvAttnStep qa{};
+        qa.X = BF(p->Hb); qa.ldx = D; qa.ldw = D; qa.attn_o = BFM(p->Ob); qa.QKV = BFM(p->QKV);
+        qa.B = p->batch; qa.tokens = T; qa.cond_tokens = p->cond_tokens; qa.hidden = D; qa.heads = p->heads; qa.K = D; qa.max_wgs = p->gemm_wgs; qa.step_ptr = step_ptr;
         if (fold && l > 0) {                                    // Hb = x (1 + scale_msa) and the row statistics came from block l-1's mlp.out
             qa.W = BF(p->w_qkv[l]);
             qa.stats = p->stats; qa.stats_parts = sparts; qa.fold_S = fl; qa.fold_C = fl + 3L * D; qa.fold_step_stride = fstep;
@@ -420,44 +438,37 @@ static int score_forward_impl(const ldt_score_plan* p, const float* x, float* ep
             }
         }
         TRY(qkv_attention_step(qa, s, prof));
+        // fc_o + gate + residual.  Folded: it also emits Hb = x (1 + scale_mlp) and the row statistics, which mlp.fc consumes
+        GemmArgs go = gemm_args(BF(p->Ob), D, BF(p->w_o[l]), D, p->b_o[l], p->X, D, M, D, D, p->gemm_wgs);
+        gemm_add_gated_resid(go, p->X, D, m + 2 * D, sstr, T, step_ptr, tstr);
         if (fold) {
-            // fc_o + gate + residual, also emitting Hb = x (1 + scale_mlp) and the row statistics; mlp.fc consumes them
-            GemmArgs go{BF(p->Ob), D, BF(p->w_o[l]), D, p->b_o[l], p->X, D, p->X, D, nullptr, 0, m + 2 * D, sstr, T, step_ptr, tstr, M, D, D,
-                        BFM(p->Hb), D, m + 4 * D, tstr, p->stats};
-            go.max_wgs = p->gemm_wgs; go.stats_parts = sparts; LAUNCH(LDT_PROF_GEMM_O, ldt_gemm_lnfold_launch(LDT_EPI_RESID_F32, &go, s));
+            gemm_add_fold_producer(go, BFM(p->Hb), D, m + 4 * D, tstr, p->stats, sparts);
+            LAUNCH(LDT_PROF_GEMM_O, ldt_gemm_lnfold_launch(LDT_EPI_RESID_F32, &go, s));
             if (p->fold_monitor) TRY(ldt_fold_monitor_launch(p->stats, sparts, M, D, p->fold_monitor, s));
-            GemmArgs gu{BF(p->Hb), D, BF(p->w_up[l]), D, nullptr, p->U, F, nullptr, 0, nullptr, 0, nullptr, 0, 0, step_ptr, 0, M, F, D,
-                        nullptr, 0, nullptr, 0, nullptr, p->stats, sparts, fl + 6L * D, fl + 6L * D + F, fstep};
-            gu.max_wgs = p->gemm_wgs; LAUNCH(LDT_PROF_GEMM_GELU, ldt_gemm_lnfold_launch(LDT_EPI_GELU_BF16, &gu, s));
-            GemmArgs gd{BF(p->U), F, BF(p->w_dn[l]), F, p->b_dn[l], p->X, D, p->X, D, nullptr, 0, m + 5 * D, sstr, T, step_ptr, tstr, M, D, F,
-                        BFM(p->Hb), D, m + 6 * D + D, tstr, p->stats};      // next block's scale_msa
-            gd.max_wgs = p->gemm_wgs; gd.stats_parts = sparts;
-            if (l + 1 < p->blocks) {
-                LAUNCH(LDT_PROF_GEMM_DN, ldt_gemm_lnfold_launch(LDT_EPI_RESID_F32, &gd, s));
-                if (p->fold_monitor) TRY(ldt_fold_monitor_launch(p->stats, sparts, M, D, p->fold_monitor, s));
-            }
-            else LAUNCH(LDT_PROF_GEMM_DN, ldt_gemm_launch(LDT_EPI_RESID_F32, &gd, s));    // FinalLayer's LN runs as a kernel
-            continue;
+        } else {
+            LnArgs n2{p->X, D, BFM(p->Hb), D, nullptr, nullptr, m + 3 * D, m + 4 * D, sstr, T, step_ptr, tstr, M, D};
+            LAUNCH(LDT_PROF_GEMM_O, ldt_gemm_launch(LDT_EPI_RESID_F32, &go, s));
+            LAUNCH(LDT_PROF_LN, ldt_ln_launch(&n2, s));
         }
-        LnArgs n2{p->X, D, BFM(p->Hb), D, nullptr, nullptr, m + 3 * D, m + 4 * D, sstr, T, step_ptr, tstr, M, D};
-        {
-            GemmArgs go{BF(p->Ob), D, BF(p->w_o[l]), D, p->b_o[l], p->X, D, p->X, D, nullptr, 0, m + 2 * D, sstr, T, step_ptr, tstr, M, D, D};
-            go.max_wgs = p->gemm_wgs; LAUNCH(LDT_PROF_GEMM_O, ldt_gemm_launch(LDT_EPI_RESID_F32, &go, s));
-        }
-        LAUNCH(LDT_PROF_LN, ldt_ln_launch(&n2, s));
-        GemmArgs gu{BF(p->Hb), D, BF(p->w_up[l]), D, p->b_up[l], p->U, F, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, 0, M, F, D};
-        gu.max_wgs = p->gemm_wgs; LAUNCH(LDT_PROF_GEMM_GELU, ldt_gemm_launch(LDT_EPI_GELU_BF16, &gu, s));
-        {
-            GemmArgs gd{BF(p->U), F, BF(p->w_dn[l]), F, p->b_dn[l], p->X, D, p->X, D, nullptr, 0, m + 5 * D, sstr, T, step_ptr, tstr, M, D, F};
-            gd.max_wgs = p->gemm_wgs; LAUNCH(LDT_PROF_GEMM_DN, ldt_gemm_launch(LDT_EPI_RESID_F32, &gd, s));
-        }
+        // mlp.fc + GELU (folded: its bias is part of fold_C)
+        GemmArgs gu = gemm_args(BF(p->Hb), D, BF(p->w_up[l]), D, fold ? nullptr : p->b_up[l], p->U, F, M, F, D, p->gemm_wgs);
+        if (fold) gemm_add_fold_consumer(gu, p->stats, sparts, fl + 6L * D, fl + 6L * D + F, fstep, step_ptr);
+        LAUNCH(LDT_PROF_GEMM_GELU, fold ? ldt_gemm_lnfold_launch(LDT_EPI_GELU_BF16, &gu, s) : ldt_gemm_launch(LDT_EPI_GELU_BF16, &gu, s));
+        // mlp.out + gate + residual.  Folded: Hb and the statistics for the next block's scale_msa; the last block's launches unfolded (FinalLayer's LN runs as a kernel)
+        GemmArgs gd = gemm_args(BF(p->U), F, BF(p->w_dn[l]), F, p->b_dn[l], p->X, D, M, D, F, p->gemm_wgs);
+        gemm_add_gated_resid(gd, p->X, D, m + 5 * D, sstr, T, step_ptr, tstr);
+        if (fold) gemm_add_fold_producer(gd, BFM(p->Hb), D, m + 6 * D + D, tstr, p->stats, sparts);
+        if (fold && l + 1 < p->blocks) {
+            LAUNCH(LDT_PROF_GEMM_DN, ldt_gemm_lnfold_launch(LDT_EPI_RESID_F32, &gd, s));
+            if (p->fold_monitor) TRY(ldt_fold_monitor_launch(p->stats, sparts, M, D, p->fold_monitor, s));
+        } else LAUNCH(LDT_PROF_GEMM_DN, ldt_gemm_launch(LDT_EPI_RESID_F32, &gd, s));
     }
     {                                                           // FinalLayer (layers.py:240-248)
         const float* m = p->mod + (long)p->blocks * 6 * D;
         LnArgs nf{p->X, D, BFM(p->Hb), D, nullptr, nullptr, m, m + D, sstr, T, step_ptr, tstr, M, D};
         LAUNCH(LDT_PROF_LN, ldt_ln_launch(&nf, s));
-        GemmArgs gf{BF(p->Hb), D, BF(p->w_out), D, p->b_out, eps_out, p->z_dim, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, 0, M, p->z_dim, D};
-        gf.max_wgs = p->gemm_wgs; LAUNCH(LDT_PROF_GEMM_IO, ldt_gemm_launch(LDT_EPI_F32, &gf, s));
+        const GemmArgs gf = gemm_args(BF(p->Hb), D, BF(p->w_out), D, p->b_out, eps_out, p->z_dim, M, p->z_dim, D, p->gemm_wgs);
+        LAUNCH(LDT_PROF_GEMM_IO, ldt_gemm_launch(LDT_EPI_F32, &gf, s));
     }
     return LDT_OK;
 }
@@ -492,12 +503,8 @@ static int enqueue_step(const ldt_score_plan* p, float* x, float* x_mean, float*
     if (cond) {                                                 // per-sample AdaLN rows of this step
         TRY(ldt_cond_rows_launch(cond->temb, cond->extra, cond->c_buf, cond->c_buf_bf16, step_counter, p->batch, cond->t_dim, 1, s));   // c_buf = silu(c)
         if (cond->w_ada_bf16 && (cond->t_dim % 64 == 0 || !cond->w_ada)) {   // bf16 weight panel: half the bytes of the HBM-bound row GEMM (fp32 accumulation + bias); a width the MFMA GEMM does not take falls back to the fp32 rows when they were given
-            GemmArgs g{};
-            g.X = BF(cond->c_buf_bf16); g.ldx = cond->t_dim;
-            g.W = BF(cond->w_ada_bf16); g.ldw = cond->t_dim;
-            g.bias = cond->b_ada; g.out = cond->mod_buf; g.ldo = cond->n_mod;
-            g.M = p->batch; g.N = cond->n_mod; g.K = cond->t_dim;
-            g.max_wgs = p->gemm_wgs;
+            const GemmArgs g = gemm_args(BF(cond->c_buf_bf16), cond->t_dim, BF(cond->w_ada_bf16), cond->t_dim, cond->b_ada, cond->mod_buf, cond->n_mod,
+                                         p->batch, cond->n_mod, cond->t_dim, p->gemm_wgs);
             TRY(ldt_gemm_launch(EPI_F32, &g, s));
         } else {
             SgemmArgs g{cond->c_buf, cond->t_dim, cond->w_ada, cond->t_dim, cond->b_ada, cond->mod_buf, cond->n_mod, 0, LDT_ACT_NONE,

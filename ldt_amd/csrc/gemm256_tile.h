@@ -85,7 +85,6 @@ struct Tile256List {
 static inline int gemm256_default_group_m(int tiles_m, int tiles_n) { return (tiles_n >= 8 && tiles_m >= 8) ? 4 : 1; }
 bool ldt_gemm256_takes(int epi, const GemmArgs* a);       // interior, aligned tiles only: everything else belongs to the mid-size / small-tile kernels
 int ldt_gemm256_launch(int epi, int fold, const GemmArgs* a, const GemmRoute& route, hipStream_t stream);   // route: ldt_gemm_decide's (a 256 family)
-int ldt_gemm_variant_env();                               // gemm_bf16.hip: LDT_GEMM_FORCE (0 = the dispatch rule decides)
 
 // sum over the 16 lanes of a DPP row (all 16 end up with the total): quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror
 __device__ __forceinline__ float row16_sum(float v) {

@@ -453,11 +453,10 @@ int ldt_gemm256_launch(int epi, int fold, const GemmArgs* a, const GemmRoute& r,
 bool ldt_gemm_qkv_attn256_takes(const GemmArgs* a_in, int tokens, int head_dim, bool folded) {
     static const bool on = !(getenv("LDT_QKV_ATTN256") && atoi(getenv("LDT_QKV_ATTN256")) == 0);
     const GemmArgs& g = *a_in;
-    if (!on || ldt_gemm_variant_env() != 0 || tokens != 256 || head_dim != 64) return false;
+    if (!on || tokens != 256 || head_dim != 64) return false;
     if (g.M <= 0 || g.N <= 0 || g.N % 192 != 0 || (g.N / 3) % 64 != 0 || g.M % 256 != 0 || g.K % 64 != 0 || g.K < (folded ? 256 : 128)) return false;
     if (folded && (g.stats_parts <= 0 || g.stats_parts > 4 || g.stats_parts * 256 != g.K)) return false;
-    const long tiles = (long)(g.M / 256) * ((g.N / 3) / 64);
-    return tiles * 8 >= (long)ldt_wg_limit(g.max_wgs) * 5;
+    return ldt_fills_workgroups((long)(g.M / 256) * ((g.N / 3) / 64), g.max_wgs);
 }
 bool ldt_gemm_qkv_attn256_try(const GemmArgs* a_in, int tokens, int head_dim, bool folded, hipStream_t stream, int* status) {
     const GemmArgs& g = *a_in;

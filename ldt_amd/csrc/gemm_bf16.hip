@@ -22,8 +22,6 @@
 //   EPI_RESID_F32  out fp32  = resid + gate[s,n] * (acc + bias)           (x + gate*(...), layers.py:218-219; gate may be null)
 // This file: that small-tile kernel (v1), the dispatch rule (ldt_gemm_decide) and the two launch entries.  The 256-row-tile kernels
 // live in gemm_256.hip (shared machinery and the tile list: gemm256_tile.h), the mid-size tile kernels in gemm_mid.hip.
-#include <stdlib.h>
-
 #include "gemm256_tile.h"
 
 #define BK 64
@@ -73,8 +71,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_bf16_nt_kernel(const GemmArgs a)
     const int q = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
     const int wgid = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (bid >> 3);
     // tile order: row-major (an XCD's chunk of workgroups = a band of output rows x every column tile: it reads its own rows of X
-    // and ALL of W) or column-major (a band of column tiles x every row tile: its own slice of W, all of X) — the launcher picks
-    // column-major for wide outputs over few row tiles (M = 1024: QKV 15.9 -> 14.5 us, MLP-up 18.2 -> 16.1 us; tools/dbg/smallm_bench.py)
+    // and ALL of W) or column-major (a band of column tiles x every row tile: its own slice of W, all of X) — ldt_gemm_decide picks
+    // column-major for wide outputs over few row tiles (M = 1024: QKV 15.9 -> 14.5 us, MLP-up 18.2 -> 16.1 us; profiles/r03_smallm_tile_sweep.txt, its script last existed at 8127e49)
     const int tiles_m = (a.M + BM - 1) / BM;
     const int tile_m = a.col_major ? wgid % tiles_m : wgid / tiles_n, tile_n = a.col_major ? wgid / tiles_m : wgid % tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
@@ -212,24 +210,32 @@ __global__ __launch_bounds__(NW * 64) void gemm_bf16_nt_kernel(const GemmArgs a)
 }
 
 // LN-folding launches.  Large batches: the 256-tile kernel (statistics per 256 columns).  Small batches — all four GEMMs of a Score block
-// (N = D, 3D, F) below ldt_gemm_launch's 5/8 rule — fold through the mid-size tile kernel (gemm_mid.hip, statistics per 32 columns:
+// (N = D, 3D, F) below the fill rule (ldt_fills_workgroups) — fold through the mid-size tile kernel (gemm_mid.hip, statistics per 32 columns:
 // stats[D / 32][M][2]) when it takes every one of them in a folded form; otherwise the LayerNorm kernels run.
-int ldt_gemm_variant_env() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("LDT_GEMM_FORCE"); v = e ? atoi(e) : 0; }
-    return v;
-}
-bool ldt_gemm_lnfold_v1_route(int M, int D, int F, int max_wgs) {
-    const int lim = ldt_wg_limit(max_wgs);
-    auto small = [&](int N) { return (long)((M + 255) / 256) * ((N + 255) / 256) * 8 < (long)lim * 5; };
-    if (!(ldt_gemm_variant_env() == 0 && M % 128 == 0 && D % 64 == 0 && F % 64 == 0 && D <= 1024 && small(D) && small(3 * D) && small(F))) return false;
+static bool ldt_gemm_lnfold_mid_route(int M, int D, int F, int max_wgs) {
+    auto small = [&](int N) { return !ldt_fills_workgroups((long)((M + 255) / 256) * ((N + 255) / 256), max_wgs); };
+    if (!(M % 128 == 0 && D % 64 == 0 && F % 64 == 0 && D <= 1024 && small(D) && small(3 * D) && small(F))) return false;
     // the folded residual producers run 64 x 128 tiles (statistics per 32 columns need whole 128-column slabs): below 5/8 of the workgroups
     // they leave the chip half empty and the LayerNorm launches they replace are cheaper — M = 1024 (B = 32 x 32 tokens): folded 1.788 ms per
     // SDE step against 1.670 with the 64 x 64 plain forms + LayerNorm kernels (profiles/r06_c5_ln_fold_decision.txt); M = 2048: 256 tiles, folded wins
-    if ((long)(M / 64) * (D / 128) * 8 < (long)lim * 5) return false;
+    if (!ldt_fills_workgroups((long)(M / 64) * (D / 128), max_wgs)) return false;
     return ldt_gemm_mid_lnfold_takes(EPI_RESID_F32, M, D, D) && ldt_gemm_mid_lnfold_takes(EPI_RESID_F32, M, D, F) &&
            ldt_gemm_mid_lnfold_takes(EPI_BF16, M, 3 * D, D) && ldt_gemm_mid_lnfold_takes(EPI_GELU_BF16, M, F, D);
 }
+// The fold decision of a Score block (kernels.h): the small-batch route first, else the 256-tile kernels when the residual GEMMs' tiles fill the workgroups
+ScoreFold ldt_score_fold_decide(int M, int D, int F, int max_wgs) {
+    ScoreFold f{SCORE_FOLD_NONE, false, 256};
+    if (M <= 0 || D <= 0 || F <= 0 || D % 256 != 0 || D > 1024 || F % 256 != 0) return f;
+    f.shape_256 = M % 256 == 0;
+    if (ldt_gemm_lnfold_mid_route(M, D, F, max_wgs)) { f.route = SCORE_FOLD_MID; f.granule = 32; }
+    else if (f.shape_256 && ldt_fills_workgroups((long)(M / 256) * (D / 256), max_wgs)) f.route = SCORE_FOLD_256;
+    return f;
+}
+
+// The v1 kernel's forms: tile and stages.  3 stages only for 64x64 tiles (48 KB of LDS, still 3 workgroups per CU; M = 2048: fc_o 13.5 -> 12.3,
+// mlp.out 38.6 -> 31.3 us; a 4th stage measured equal): at 128x64 / 128x128 the third buffer costs a co-resident workgroup and loses 20-40 %
+struct V1Form { int bm, bn, stages; };
+static constexpr V1Form V1_FORMS[3] = {{128, 128, 2}, {128, 64, 2}, {64, 64, 3}};
 
 // The dispatch rule (kernels.h): family, tile and grid of a GEMM.  Shape-level only: pointer and alignment checks stay with the launchers.
 GemmRoute ldt_gemm_decide(int epi, const GemmArgs* a, int granule) {
@@ -258,39 +264,38 @@ GemmRoute ldt_gemm_decide(int epi, const GemmArgs* a, int granule) {
         }
         return r;
     }
-    const int force = ldt_gemm_variant_env();
     // 256^2 persistent kernel when its tiles fill at least 5/8 of the workgroups this launch may use (all CUs, or a
     // sub-batch stream's share): at exactly half (M = 8192, N = 1024: 128 tiles on 256 CUs) the 128^2 kernel on every CU
     // is as fast (K = 1024) or 15 % faster (K = 4096).
     // (N <= 128 — the Compressor's 128-channel convs over millions of point rows — would leave half of every 256-wide tile
     //  empty: the 128^2 kernel streams those 5.7 % faster end to end, tools/dbg/c4_chunks.py)
-    const int tiles256 = ((a->M + 255) / 256) * ((a->N + 255) / 256);
-    const bool big = tiles256 * 8 >= lim * 5 && a->N > 128;
-    if (force == 0 && !big) {
-        // mid-size problems (gemm_mid.hip): 128 x 256 / 128 x 192 / 128 x 128 / 64 x 128 / 64 x 64 tiles with dedicated loader waves, when
-        // the 256^2 persistent kernel would leave CUs idle — the 1-4k-row batches
-        if (ldt_gemm_mid_route(epi, FOLD_NONE, a, &r)) return r;
+    const bool big = ldt_fills_workgroups(((a->M + 255) / 256) * ((a->N + 255) / 256), a->max_wgs) && a->N > 128;
+    // mid-size problems (gemm_mid.hip): 128 x 256 / 128 x 192 / 128 x 128 / 64 x 128 / 64 x 64 tiles with dedicated loader waves, when
+    // the 256^2 persistent kernel would leave CUs idle — the 1-4k-row batches
+    if (!big && ldt_gemm_mid_route(epi, FOLD_NONE, a, &r)) return r;
+    if (big && ldt_gemm256_takes(epi, a)) { take_256(); return r; }
+    // v1 form: the largest of 128x128 / 128x64 / 64x64 that still gives every CU two tiles — this 2-phase kernel hides a stage's load latency
+    // only across co-resident workgroups (M = 2048: QKV 25.8 -> 22.9 us with 128x64, fc_o 14.4 -> 12.0 and mlp.out 47.7 -> 40.0 us with 64x64 tiles)
+    long tm, tn;
+    for (r.v1_form = 0;; ++r.v1_form) {
+        r.bm = V1_FORMS[r.v1_form].bm; r.bn = V1_FORMS[r.v1_form].bn;
+        tm = (a->M + r.bm - 1) / r.bm; tn = (a->N + r.bn - 1) / r.bn;
+        if (r.v1_form == 2 || tm * tn >= 2 * LDT_NUM_CUS) break;        // the last form takes what is left
     }
-    if ((force == 256 || (force == 0 && big)) && ldt_gemm256_takes(epi, a)) { take_256(); return r; }
-    // v1 tile shape: the largest of 128x128 / 128x64 / 64x64 that still gives every CU two tiles
-    auto ntiles = [&](int bm, int bn) { return (long)((a->M + bm - 1) / bm) * ((a->N + bn - 1) / bn); };
-    // this 2-phase kernel hides a stage's load latency only across co-resident workgroups: want >= 2 tiles per CU
-    // (M = 2048: QKV 25.8 -> 22.9 us with 128x64, fc_o 14.4 -> 12.0 and mlp.out 47.7 -> 40.0 us with 64x64 tiles)
-    const int shape = (force == 128 || ntiles(128, 128) >= 2 * LDT_NUM_CUS) ? 0 : (ntiles(128, 64) >= 2 * LDT_NUM_CUS ? 1 : 2);
-    // 3 stages only for 64x64 tiles (48 KB of LDS, still 3 workgroups per CU; M = 2048: fc_o 13.5 -> 12.3, mlp.out 38.6 ->
-    // 31.3 us; a 4th stage measured equal): at 128x64 / 128x128 the third buffer costs a co-resident workgroup and loses 20-40 %
     r.family = GEMM_ROUTE_V1;
-    r.v1_shape = shape;
-    r.v1_stages = shape == 2 ? 3 : 2;
-    r.bm = shape == 2 ? 64 : 128;
-    r.bn = shape == 0 ? 128 : 64;
     r.tiles_per_wg = 1;
-    r.grid = (int)ntiles(r.bm, r.bn);
+    r.grid = (int)(tm * tn);
+    r.col_major = tn >= 3 * tm ? 1 : 0;                                 // wide outputs over few row tiles (numbers: the kernel's tile-order comment)
     return r;
 }
 
-// epilogue operand checks of both launch entries (`who` prefixes the error text)
-static int gemm_check_epilogue_operands(const char* who, int epi, const GemmArgs* a) {
+// operand checks of both launch entries (`who` prefixes the error text).  The folded forms store 16-byte bf16 rows next to the fp32 ones
+// (ldo % 8) and have always filed a leading dimension below K under alignment.
+static int gemm_check_operands(const char* who, bool folded, int epi, const GemmArgs* a) {
+    LDT_REQUIRE(a->ldx % 8 == 0 && a->ldw % 8 == 0 && ldt_aligned16(a->X) && ldt_aligned16(a->W), LDT_EALIGN,
+                "%s: X/W rows must be 16-byte aligned (ldx=%ld ldw=%ld)", who, a->ldx, a->ldw);
+    LDT_REQUIRE(a->ldx >= a->K && a->ldw >= a->K, folded ? LDT_EALIGN : LDT_ESHAPE, "%s: leading dims smaller than K", who);
+    LDT_REQUIRE(a->ldo % (folded ? 8 : 4) == 0 && ldt_aligned16(a->out), LDT_EALIGN, "%s: out rows must be 16-byte aligned (ldo=%ld)", who, a->ldo);
     if (epi == EPI_RESID_F32) {
         LDT_REQUIRE(a->resid && a->ldr % 4 == 0 && ldt_aligned16(a->resid), LDT_EALIGN, "%s: resid missing/misaligned", who);
         LDT_REQUIRE(!a->gate || (a->rows_per_sample > 0 && ldt_aligned16(a->gate) && a->gate_sample_stride % 4 == 0 && a->gate_step_stride % 4 == 0),
@@ -300,88 +305,65 @@ static int gemm_check_epilogue_operands(const char* who, int epi, const GemmArgs
     return LDT_OK;
 }
 
-int ldt_gemm_lnfold_launch(int epi, const GemmArgs* a, hipStream_t stream) {
-    // route: stats_parts says which statistics layout the caller's buffers use — K / 256 (N / 256 for the producer) parts: the 256-tile
-    // kernel; K / 32 (N / 32): the mid-size tile kernel (ldt_gemm_lnfold_v1_route)
-    const int width = epi == EPI_RESID_F32 ? a->N : a->K;
-    const bool v1 = a->stats_parts > 0 && a->stats_parts * 32 == width && a->stats_parts * 256 != width;
-    if (v1) LDT_REQUIRE(a->M > 0 && a->M % 128 == 0 && a->N % 64 == 0 && a->K >= 128 && a->K % BK == 0, LDT_ESHAPE,
-                        "gemm_lnfold (v1 route): M=%d must be a multiple of 128, N=%d of 64, K=%d >= 128, K %% 64 == 0", a->M, a->N, a->K);
-    else LDT_REQUIRE(a->M > 0 && a->N > 0 && a->K >= 256 && a->M % 256 == 0 && a->N % 256 == 0 && a->K % BK == 0, LDT_ESHAPE,
-                     "gemm_lnfold: M=%d N=%d must be multiples of 256 and K=%d >= 256, K %% 64 == 0", a->M, a->N, a->K);
-    LDT_REQUIRE(a->ldx % 8 == 0 && a->ldw % 8 == 0 && a->ldx >= a->K && a->ldw >= a->K && a->ldo % 8 == 0 && ldt_aligned16(a->X) &&
-                ldt_aligned16(a->W) && ldt_aligned16(a->out), LDT_EALIGN, "gemm_lnfold: operands must be 16-byte aligned (ldx=%ld ldw=%ld ldo=%ld)",
-                a->ldx, a->ldw, a->ldo);
-    if (epi == EPI_RESID_F32) {                                          // producer
-        if (const int rc = gemm_check_epilogue_operands("gemm_lnfold", epi, a)) return rc;
-        LDT_REQUIRE(a->xs && a->ln_scale && a->stats_out && a->ldxs % 4 == 0 && a->ldxs >= a->N && ldt_aligned16(a->xs) &&
-                    ldt_aligned16(a->ln_scale) && a->ln_step_stride % 4 == 0 && ldt_aligned16(a->stats_out), LDT_EARG,
-                    "gemm_lnfold: producer needs xs / ln_scale / stats_out (16-byte aligned)");
-        const GemmRoute r = ldt_gemm_decide(epi, a, v1 ? 32 : 256);
-        if (v1) {
-            if (r.family == GEMM_ROUTE_MID) return ldt_gemm_mid_launch(epi, FOLD_PRODUCER, a, r, stream);   // mid-size tile kernel (gemm_mid.hip)
-            ldt_set_error("gemm_lnfold: statistics per 32 columns are the mid-size tile kernel's; it does not take M=%d N=%d K=%d as a producer", a->M, a->N, a->K);
-            return LDT_ESHAPE;
-        }
-        LDT_REQUIRE(r.family == GEMM_ROUTE_256_ONE || r.family == GEMM_ROUTE_256_MULTI, LDT_ESHAPE,
-                    "gemm256: M=%d N=%d must be multiples of 256, K=%d of 64 (>= 128), rows 16-byte aligned", a->M, a->N, a->K);
-        return ldt_gemm256_launch(epi, FOLD_PRODUCER, a, r, stream);
-    }
-    LDT_REQUIRE(epi == EPI_BF16 || epi == EPI_GELU_BF16, LDT_EARG, "gemm_lnfold: epilogue %d has no folded form", epi);
-    LDT_REQUIRE(a->stats_in && a->fold_S && a->fold_C && ldt_aligned16(a->stats_in) && ldt_aligned16(a->fold_S) && ldt_aligned16(a->fold_C) &&
-                a->fold_step_stride % 4 == 0, LDT_EARG, "gemm_lnfold: consumer needs stats_in, fold_S, fold_C (16-byte aligned)");
-    const GemmRoute r = ldt_gemm_decide(epi, a, v1 ? 32 : 256);
-    if (v1) {
-        LDT_REQUIRE(a->stats_parts <= 32, LDT_ESHAPE, "gemm_lnfold (v1 route): K=%d > 1024 input channels", a->K);
-        if (r.family == GEMM_ROUTE_MID) return ldt_gemm_mid_launch(epi, FOLD_CONSUMER, a, r, stream);
-        ldt_set_error("gemm_lnfold: statistics per 32 columns are the mid-size tile kernel's; it does not take M=%d N=%d K=%d as a consumer", a->M, a->N, a->K);
-        return LDT_ESHAPE;
-    }
-    LDT_REQUIRE(a->stats_parts >= 1 && a->stats_parts <= 4 && a->stats_parts * 256 == a->K, LDT_EARG,
-                "gemm_lnfold: consumer needs stats_in[K/256 <= 4][M][2] (or [K/32][M][2] for the small-batch kernels); K=%d parts=%d", a->K, a->stats_parts);
-    LDT_REQUIRE(r.family == GEMM_ROUTE_256_ONE || r.family == GEMM_ROUTE_256_MULTI, LDT_ESHAPE,
-                "gemm256: M=%d N=%d must be multiples of 256, K=%d of 64 (>= 128), rows 16-byte aligned", a->M, a->N, a->K);
-    return ldt_gemm256_launch(epi, FOLD_CONSUMER, a, r, stream);
+// the v1 kernel on the route's form, grid and tile order
+template <int EPI>
+static int launch_v1(const GemmArgs* a, const GemmRoute& r, hipStream_t stream) {
+    static void (*const forms[3])(const GemmArgs) = {gemm_bf16_nt_kernel<EPI, V1_FORMS[0].bm, V1_FORMS[0].bn, V1_FORMS[0].stages>,
+                                                     gemm_bf16_nt_kernel<EPI, V1_FORMS[1].bm, V1_FORMS[1].bn, V1_FORMS[1].stages>,
+                                                     gemm_bf16_nt_kernel<EPI, V1_FORMS[2].bm, V1_FORMS[2].bn, V1_FORMS[2].stages>};
+    GemmArgs v = *a; v.col_major = r.col_major;
+    hipLaunchKernelGGL(forms[r.v1_form], dim3((unsigned)r.grid), dim3(256), 0, stream, v);
+    return ldt_check_launch("gemm_bf16_nt");
 }
 
-// LDT_GEMM_FORCE=128|256 pins the variant (A/B runs); default: see ldt_gemm_decide.
+// launches the route that ldt_gemm_decide chose (fold: gemm256_tile.h's FOLD_*; the v1 kernel has no folded form)
+static int gemm_launch_route(int epi, int fold, const GemmArgs* a, const GemmRoute& r, hipStream_t stream) {
+    if (r.family == GEMM_ROUTE_MID) return ldt_gemm_mid_launch(epi, fold, a, r, stream);
+    if (r.family == GEMM_ROUTE_256_ONE || r.family == GEMM_ROUTE_256_MULTI) return ldt_gemm256_launch(epi, fold, a, r, stream);
+    LDT_REQUIRE(r.family == GEMM_ROUTE_V1 && fold == FOLD_NONE, LDT_ESHAPE, "gemm: no kernel takes M=%d N=%d K=%d", a->M, a->N, a->K);
+    switch (epi) {
+        case EPI_F32: return launch_v1<EPI_F32>(a, r, stream);
+        case EPI_BF16: return launch_v1<EPI_BF16>(a, r, stream);
+        case EPI_GELU_BF16: return launch_v1<EPI_GELU_BF16>(a, r, stream);
+        case EPI_RELU_BF16: return launch_v1<EPI_RELU_BF16>(a, r, stream);
+        case EPI_RESID_F32: return launch_v1<EPI_RESID_F32>(a, r, stream);
+    }
+    ldt_set_error("gemm: unknown epilogue %d", epi);
+    return LDT_EARG;
+}
 
 int ldt_gemm_launch(int epi, const GemmArgs* a, hipStream_t stream) {
     LDT_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0, LDT_ESHAPE, "gemm: empty problem M=%d N=%d K=%d", a->M, a->N, a->K);
     LDT_REQUIRE(a->K % BK == 0, LDT_ESHAPE, "gemm: K=%d must be a multiple of %d (pad activations/weights)", a->K, BK);
-    LDT_REQUIRE(a->ldx % 8 == 0 && a->ldw % 8 == 0 && ldt_aligned16(a->X) && ldt_aligned16(a->W), LDT_EALIGN,
-                "gemm: X/W rows must be 16-byte aligned (ldx=%ld ldw=%ld)", a->ldx, a->ldw);
-    LDT_REQUIRE(a->ldx >= a->K && a->ldw >= a->K, LDT_ESHAPE, "gemm: leading dims smaller than K");
-    LDT_REQUIRE(a->ldo % 4 == 0 && ldt_aligned16(a->out), LDT_EALIGN, "gemm: out must be 16-byte aligned, ldo%%4==0 (ldo=%ld)", a->ldo);
-    if (const int rc = gemm_check_epilogue_operands("gemm", epi, a)) return rc;
-    const GemmRoute r = ldt_gemm_decide(epi, a, 0);
-    if (r.family == GEMM_ROUTE_MID) return ldt_gemm_mid_launch(epi, FOLD_NONE, a, r, stream);
-    if (r.family == GEMM_ROUTE_256_ONE || r.family == GEMM_ROUTE_256_MULTI) return ldt_gemm256_launch(epi, FOLD_NONE, a, r, stream);
-    LDT_REQUIRE(r.family == GEMM_ROUTE_V1, LDT_ESHAPE, "gemm: no kernel takes M=%d N=%d K=%d", a->M, a->N, a->K);
-    const int shape = r.v1_shape;
-    auto ntiles = [&](int bm, int bn) { return (long)((a->M + bm - 1) / bm) * ((a->N + bn - 1) / bn); };
-    dim3 block(256);
-    static const int v1_map_env = getenv("LDT_GEMM_V1_MAP") ? atoi(getenv("LDT_GEMM_V1_MAP")) : -1;         // tools/dbg: 0 / 1 force
-    GemmArgs a_v1 = *a;
-    {
-        const long tm = (a->M + r.bm - 1) / r.bm, tn = (a->N + r.bn - 1) / r.bn;
-        a_v1.col_major = v1_map_env >= 0 ? v1_map_env : (tn >= 3 * tm ? 1 : 0);
+    if (const int rc = gemm_check_operands("gemm", false, epi, a)) return rc;
+    return gemm_launch_route(epi, FOLD_NONE, a, ldt_gemm_decide(epi, a, 0), stream);
+}
+
+// The LN-folded launches: producer (EPI_RESID_F32: also writes xs and the row statistics) or consumer (EPI_BF16 / EPI_GELU_BF16: reads them).
+// stats_parts says which statistics layout the caller's buffers use: K / 32 parts (N / 32 for the producer) are the mid-size tile kernel's
+// (ldt_gemm_lnfold_mid_route), anything else means K / 256 (N / 256), the 256-tile kernel's.
+int ldt_gemm_lnfold_launch(int epi, const GemmArgs* a, hipStream_t stream) {
+    const bool producer = epi == EPI_RESID_F32;
+    const int granule = (a->stats_parts > 0 && a->stats_parts * 32 == (producer ? a->N : a->K)) ? 32 : 256;
+    if (granule == 32) LDT_REQUIRE(a->M > 0 && a->M % 128 == 0 && a->N % 64 == 0 && a->K >= 128 && a->K % BK == 0, LDT_ESHAPE,
+                                   "gemm_lnfold (mid route): M=%d must be a multiple of 128, N=%d of 64, K=%d >= 128, K %% 64 == 0", a->M, a->N, a->K);
+    else LDT_REQUIRE(a->M > 0 && a->N > 0 && a->K >= 256 && a->M % 256 == 0 && a->N % 256 == 0 && a->K % BK == 0, LDT_ESHAPE,
+                     "gemm_lnfold: M=%d N=%d must be multiples of 256 and K=%d >= 256, K %% 64 == 0", a->M, a->N, a->K);
+    if (const int rc = gemm_check_operands("gemm_lnfold", true, epi, a)) return rc;
+    if (producer) {
+        LDT_REQUIRE(a->xs && a->ln_scale && a->stats_out && a->ldxs % 4 == 0 && a->ldxs >= a->N && ldt_aligned16(a->xs) &&
+                    ldt_aligned16(a->ln_scale) && a->ln_step_stride % 4 == 0 && ldt_aligned16(a->stats_out), LDT_EARG,
+                    "gemm_lnfold: producer needs xs / ln_scale / stats_out (16-byte aligned)");
+    } else {
+        LDT_REQUIRE(epi == EPI_BF16 || epi == EPI_GELU_BF16, LDT_EARG, "gemm_lnfold: epilogue %d has no folded form", epi);
+        LDT_REQUIRE(a->stats_in && a->fold_S && a->fold_C && ldt_aligned16(a->stats_in) && ldt_aligned16(a->fold_S) && ldt_aligned16(a->fold_C) &&
+                    a->fold_step_stride % 4 == 0, LDT_EARG, "gemm_lnfold: consumer needs stats_in, fold_S, fold_C (16-byte aligned)");
+        if (granule == 32) LDT_REQUIRE(a->stats_parts <= 32, LDT_ESHAPE, "gemm_lnfold (mid route): K=%d > 1024 input channels", a->K);
+        else LDT_REQUIRE(a->stats_parts >= 1 && a->stats_parts <= 4 && a->stats_parts * 256 == a->K, LDT_EARG,
+                         "gemm_lnfold: consumer needs stats_in[K/256 <= 4][M][2] (or [K/32][M][2] for the small-batch kernels); K=%d parts=%d", a->K, a->stats_parts);
     }
-    a = &a_v1;
-#define LAUNCH_V1(E)                                                                                                     \
-    do {                                                                                                                 \
-        if (shape == 0) hipLaunchKernelGGL((gemm_bf16_nt_kernel<E, 128, 128>), dim3((unsigned)ntiles(128, 128)), block, 0, stream, *a); \
-        else if (shape == 1) hipLaunchKernelGGL((gemm_bf16_nt_kernel<E, 128, 64>), dim3((unsigned)ntiles(128, 64)), block, 0, stream, *a); \
-        else hipLaunchKernelGGL((gemm_bf16_nt_kernel<E, 64, 64, 3>), dim3((unsigned)ntiles(64, 64)), block, 0, stream, *a);  \
-    } while (0)
-    switch (epi) {
-        case EPI_F32: LAUNCH_V1(EPI_F32); break;
-        case EPI_BF16: LAUNCH_V1(EPI_BF16); break;
-        case EPI_GELU_BF16: LAUNCH_V1(EPI_GELU_BF16); break;
-        case EPI_RELU_BF16: LAUNCH_V1(EPI_RELU_BF16); break;
-        case EPI_RESID_F32: LAUNCH_V1(EPI_RESID_F32); break;
-        default: ldt_set_error("gemm: unknown epilogue %d", epi); return LDT_EARG;
-    }
-#undef LAUNCH_V1
-    return ldt_check_launch("gemm_bf16_nt");
+    const GemmRoute r = ldt_gemm_decide(epi, a, granule);
+    LDT_REQUIRE(r.family != GEMM_ROUTE_NONE, LDT_ESHAPE, "gemm_lnfold: no kernel with statistics per %d columns takes M=%d N=%d K=%d as a %s",
+                granule, a->M, a->N, a->K, producer ? "producer" : "consumer");
+    return gemm_launch_route(epi, producer ? FOLD_PRODUCER : FOLD_CONSUMER, a, r, stream);
 }

@@ -870,7 +870,7 @@ bool ldt_gemm_mid_route(int epi, int fold, const GemmArgs* a, GemmRoute* r) {
     return true;
 }
 
-// would the folded form of this GEMM (M x N x K, statistics per 32 columns) be taken?  (Score.can_fold / ldt_gemm_lnfold_v1_route)
+// would the folded form of this GEMM (M x N x K, statistics per 32 columns) be taken?  (Score.can_fold / ldt_gemm_lnfold_mid_route)
 bool ldt_gemm_mid_lnfold_takes(int epi, int M, int N, int K) {
     GemmArgs g{};
     g.M = M; g.N = N; g.K = K; g.ldo = N; g.ldr = N;

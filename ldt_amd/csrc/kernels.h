@@ -6,6 +6,8 @@ enum { EPI_F32 = 0, EPI_BF16 = 1, EPI_GELU_BF16 = 2, EPI_RELU_BF16 = 3, EPI_RESI
 #define LDT_NUM_CUS 256      // MI355X
 // workgroups a launch may fill: every CU, or GemmArgs::max_wgs of them (a sub-batch stream's share)
 static inline int ldt_wg_limit(int max_wgs) { return (max_wgs > 0 && max_wgs < LDT_NUM_CUS) ? max_wgs : LDT_NUM_CUS; }
+// THE fill rule: a persistent kernel is worth it when its tiles fill at least 5/8 of those workgroups (each caller counts its own tiles)
+static inline bool ldt_fills_workgroups(long tiles, int max_wgs) { return tiles * 8 >= (long)ldt_wg_limit(max_wgs) * 5; }
 enum { ACT_NONE = 0, ACT_SILU = 1, ACT_RELU = 2, ACT_GELU = 3 };
 
 struct GemmArgs {
@@ -30,7 +32,7 @@ struct GemmArgs {
     int group_m;                        // 256-tile kernel: row panels per group of the tile order (set by the launcher)
     int dbg;                            // tools/dbg only (LDT_DBG_EPI bits: 1 no residual read, 2 no fp32 store, 4 no xs store, 8 no statistics)
     int max_wgs;                        // 256-tile kernel: cap on the persistent grid (0 = one workgroup per CU); sub-batch streams use 128
-    int col_major;                      // v1 kernel only: tile order (set by ldt_gemm_launch; see gemm_bf16_nt_kernel)
+    int col_major;                      // v1 kernel only: tile order (GemmRoute::col_major, copied by the launcher; see gemm_bf16_nt_kernel)
     // ---- QKV projection + self-attention in one launch (gemm_mid.hip, 32-token samples, head dim 64): N = 3 * hidden columns [q | k | v];
     // the kernel writes O[B][H][32][64] (the reference's raw (B,N,C) buffer, model/layers.py:190-197) to attn_o and NOT the q | k | v rows
     bf16_t* attn_o; float attn_scale_log2e;
@@ -78,7 +80,8 @@ struct SgemmArgs {
 
 int ldt_gemm_launch(int epi, const GemmArgs* a, hipStream_t stream);
 // Which kernel a GEMM runs on: THE dispatch rule.  ldt_gemm_launch, ldt_gemm_lnfold_launch and the ldt_gemm_route query (include/ldt_hip.h)
-// all call ldt_gemm_decide and nothing else chooses a family, a tile or a grid.  granule: 0 = plain GEMM; 256 / 32 = LN-folded form with
+// all call ldt_gemm_decide and nothing else chooses a family, a tile, a grid or the v1 kernel's tile order; the launchers check the operands
+// and launch the route they are given.  granule: 0 = plain GEMM; 256 / 32 = LN-folded form with
 // statistics per that many columns (producer when epi == EPI_RESID_F32, consumer otherwise).  Reads M, N, K, ldo, ldr, skip / lds_, gate /
 // gate_sample_stride and max_wgs of `a`, no pointer's target.  family GEMM_ROUTE_NONE: no kernel takes the problem (the launchers report why).
 enum { GEMM_ROUTE_NONE = 0, GEMM_ROUTE_256_ONE = 1, GEMM_ROUTE_256_MULTI = 2, GEMM_ROUTE_MID = 3, GEMM_ROUTE_V1 = 4 };
@@ -86,7 +89,8 @@ struct GemmRoute {
     int family, bm, bn;
     int tiles_per_wg;                   // most tiles one workgroup computes (> 1: the persistent 256-tile kernel only; Tile256List::max_count)
     int grid;                           // workgroups launched
-    int v1_shape, v1_stages;            // GEMM_ROUTE_V1: index of the instantiation (0 128x128, 1 128x64, 2 64x64) and its stages
+    int v1_form;                        // GEMM_ROUTE_V1: row of the v1 kernel's table of forms (0 128 x 128 x 2 stages, 1 128 x 64 x 2, 2 64 x 64 x 3)
+    int col_major;                      // GEMM_ROUTE_V1: column-major tile order (wide outputs over few row tiles), for GemmArgs::col_major
 };
 GemmRoute ldt_gemm_decide(int epi, const GemmArgs* a, int granule);
 // gemm_mid.hip, the mid-size tile kernels.  fold: 0 plain, 1 LN-folded producer, 2 consumer (statistics per 32 columns; gemm256_tile.h's FOLD_*)
@@ -101,7 +105,12 @@ bool ldt_gemm_mid_q_xattn_try(const GemmArgs* a, int tokens, int cond_tokens, in
 bool ldt_gemm_mid_qkv_attn_takes(const GemmArgs* a, int tokens, int head_dim, bool folded);
 bool ldt_gemm_qkv_attn256_takes(const GemmArgs* a, int tokens, int head_dim, bool folded);
 bool ldt_gemm_mid_q_xattn_takes(const GemmArgs* a, int tokens, int cond_tokens, int head_dim);
-bool ldt_gemm_lnfold_v1_route(int M, int D, int F, int max_wgs);   // small batch: every GEMM of a Score block folds through the mid-size tile kernel (statistics per 32 columns)
+// Whether and how a Score block (M rows, D channels, MLP width F) folds its LayerNorms into its GEMMs: THE fold decision (gemm_bf16.hip).
+// ldt_score_lnfold_route (include/ldt_hip.h) returns `route`; the forward folds a plan that brings the fold tables when the route is the
+// mid-size one or shape_256 holds (the forced fold below the fill rule), with plan->stats laid out as [D / granule][M][2].
+enum { SCORE_FOLD_NONE = 0, SCORE_FOLD_256 = 1, SCORE_FOLD_MID = 2 };   // 256-tile kernels that fill the workgroups / small batch: every GEMM of the block runs a mid-size tile form
+struct ScoreFold { int route; bool shape_256; int granule; };           // shape_256: the 256-tile kernels take the shape, filling or not; granule: columns per statistics part (32 mid, else 256)
+ScoreFold ldt_score_fold_decide(int M, int D, int F, int max_wgs);
 int ldt_gemm_lnfold_launch(int epi, const GemmArgs* a, hipStream_t stream);   // producer (RESID + xs/stats) or consumer (stats_in)
 int ldt_ln_launch(const LnArgs* a, hipStream_t s);
 int ldt_attn_launch(const AttnArgs* a, int dh, hipStream_t s);
