@@ -1085,6 +1085,28 @@ def reparam_ref(post, noise, lo, hi):
     return mu, lv, ref, (prod.abs() * LIBM["expf"] * ULP32 + U24 * ref.abs()) * SLACK
 
 
+LOG_SQRT_2PI_F32 = float(torch.tensor(0.9189385332, dtype=torch.float32))       # the constant as csrc/eval_loss.hip holds it
+
+
+def reparam_kl_ref(eps, mu, lv):
+    """ldt_reparam_kl's log q(z) and KL per element in float64, on the kernel's own fp32 eps, mu and clamped logvar, with the tolerances of its
+    stated operation order (FMA contraction off): d = eps - mu; a = (-0.5 (d d)) / expf(lv); b = 0.5 lv; logqz = (a - b) - c;
+    logpz = (-0.5 (eps eps)) - c; kl = logqz - logpz.  With u = 2^-24: a carries d (u, twice through the square), the square (u), expf
+    (LIBM ulps = 2 LIBM u) and the division (u); the halvings are exact; each difference rounds once.
+    -> (logqz, tol_logqz, kl, tol_kl)."""
+    eps, mu, lv = eps.double(), mu.double(), lv.double()
+    d = eps - mu
+    a = (-0.5 * (d * d)) / torch.exp(lv)
+    b = 0.5 * lv
+    logqz = (a - b) - LOG_SQRT_2PI_F32
+    half_sq = 0.5 * (eps * eps)
+    logpz = -half_sq - LOG_SQRT_2PI_F32
+    kl = logqz - logpz
+    tol_q = SLACK * U24 * ((4 + 2 * LIBM["expf"]) * a.abs() + (a - b).abs() + logqz.abs())
+    tol_k = tol_q + SLACK * U24 * (2 * half_sq + logpz.abs() + kl.abs())
+    return logqz, tol_q, kl, tol_k
+
+
 def mixture_seed_ref(eps, sig, mu, logits):
     """InitialSet mixture rows: float64 sum_m (eps[r, m] sig[m] + mu[m]) softmax(logits)[m] and its tolerance.  A weight w_m carries the rounding
     of d_m = logit_m - max (|d_m| 2^-24 through exp), expf, the same for the largest term of the denominator + its n_mix - 1 additions, and the

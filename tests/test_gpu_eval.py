@@ -12,23 +12,15 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_checks as kc
 from conftest import GOLDEN, load_golden, rel_mse
 
 pytestmark = pytest.mark.gpu
-
-LOG_SQRT_2PI = 0.9189385332
 
 
 def eval_golden():
     z = np.load(os.path.join(GOLDEN, "eval_tiny.npz"))
     return {k: torch.from_numpy(np.asarray(z[k])) for k in z.files}
-
-
-def kl_terms(eps, mu, logvar):
-    """Network.py:12-19,221-224 in the dtype of the inputs: (logqz, kl)."""
-    logqz = -0.5 * torch.square(eps - mu) / torch.exp(logvar) - 0.5 * logvar - LOG_SQRT_2PI
-    logpz = -0.5 * torch.square(eps) - LOG_SQRT_2PI
-    return logqz, logqz - logpz
 
 
 def dsm_reference(eta, params, weight, l1):
@@ -74,8 +66,9 @@ def test_reparam_kl_kernel(B, T, z, L):
     assert float(fused[:, :z * j].abs().max()) == 0.0                                       # nothing outside the slice is written
     assert float(lv.max()) == hi and float(lv.min()) >= lo
     eps = fused[:, z * j: z * (j + 1)]
-    lq64, kl64 = kl_terms(eps.double(), mu.double(), lv.double())
-    assert rel_mse(lq.cpu(), lq64.cpu()) <= 1e-10 and rel_mse(kl.cpu(), kl64.cpu()) <= 1e-10
+    lq64, tol_q, kl64, tol_k = kc.reparam_kl_ref(eps.cpu(), mu.cpu(), lv.cpu())              # per element, from the kernel's operation order
+    kc.assert_elementwise(lq.cpu(), lq64, tol_q, "reparam_kl logqz")
+    kc.assert_elementwise(kl.cpu(), kl64, tol_k, "reparam_kl kl")
     assert ks.shape == (B,)
     assert relerr(ks, kl.double().view(B, -1).sum(1)) <= 1e-6                               # the fixed-order sum of the kernel's own kl
     assert relerr(ks, kl64.view(B, -1).sum(1)) <= 1e-5

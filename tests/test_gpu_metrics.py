@@ -3,12 +3,16 @@
   * pairwise Chamfer matrices, MMD-CD / COV-CD / 1-NN-CD vs the golden captured from the reference's module (fp32;
     P = |x|^2+|y|^2-2xy suffers cancellation of order 1e-7 * |p|^2, so the matrices are compared at rtol 1e-4 and the
     derived counts exactly)
-  * approximate-matching EMD vs the oracle's restatement of approxmatch.cu (parity unpinned upstream: CUDA-only):
-    relative error <= 2e-3 (v_exp_f32 vs libm expf inside a 9-level annealing)
+  * approximate-matching EMD vs the project's float64 restatement of approxmatch.cu, emd_checks.emd_ref64 (parity with the CUDA original
+    stays unpinned: it cannot be built here): every pair within emd_checks.EMD_REL.  The annealing is well conditioned on these clouds: the
+    fp32 oracle sits within 1e-6 of float64, `__expf` for `expf` moves a cost by a few 1e-7, and the bound is 4 x the worst ratio measured
+    over test_gpu_emd_exact.py's case table, rounded up to a power of two.  The derived counts (cov, 1-NN) are compared exactly:
+    test_emd_checks_host.py shows that the gaps which decide them exceed 100 EMD_REL on the golden clouds.
 """
 import pytest
 import torch
 
+import emd_checks as ec
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -47,25 +51,66 @@ def test_pairwise_cd_ragged_vs_direct(n, m):
     assert torch.allclose(got, want, rtol=1e-4, atol=1e-5)
 
 
+def within(got, want64, floor=0.0):
+    """Every element of got within EMD_REL of the float64 reference (+ an absolute floor where the reference is near 0)."""
+    got, want64 = got.detach().cpu().double(), want64.double()
+    return got.shape == want64.shape and bool(((got - want64).abs() <= ec.EMD_REL * want64.abs() + floor).all())
+
+
 def test_emd_approx_vs_oracle_and_bounds():
     from ldt_amd import metrics as Mx, ops
     from oracle import ldt_oracle as O
     a, _ = load_golden("metrics_cd")
     x, y = a["smp"][:6], a["ref"][:6]
+    want64 = ec.emd_ref64(x, y)
     want = O.emd_approxmatch_cost(x, y)
+    assert torch.allclose(want.double(), want64, rtol=1e-6, atol=0)                          # the fp32 oracle and its float64 restatement
     got = ops.emd_approx(x.cuda(), y.cuda()).cpu()
-    assert torch.allclose(got, want, rtol=2e-3), (got, want)
+    assert within(got, want64), (got, want64)
+    assert torch.allclose(got, want, rtol=ec.EMD_REL + 1e-6, atol=0), (got, want)
     emd = Mx.emd_approx(x.cuda(), y.cuda()).cpu()                  # / n, as emd_approx_cuda
-    assert torch.allclose(emd, want / x.shape[1], rtol=2e-3)
+    assert within(emd, want64 / x.shape[1])
     assert (emd > 0.97 * a["emd_exact"]).all() and (emd < 1.6 * a["emd_exact"]).all()      # vs the exact assignment
     pw = ops.emd_approx(x[:3].cuda(), y[:4].cuda(), pairwise=True).cpu()                    # all pairs, row-major
+    assert within(pw, ec.emd_ref64(x[:3], y[:4], pairwise=True))
     for i in range(3):
         for j in range(4):
-            assert abs(float(pw[i, j]) - float(O.emd_approxmatch_cost(x[i:i + 1], y[j:j + 1])[0])) < 2e-3 * float(pw[i, j])
+            assert abs(float(pw[i, j]) - float(O.emd_approxmatch_cost(x[i:i + 1], y[j:j + 1])[0])) < (ec.EMD_REL + 1e-6) * float(pw[i, j])
     # unequal sizes follow the kernel's integer mass ratios (approxmatch.cu:6-12)
     g = torch.Generator().manual_seed(5)
     u, v = torch.rand(2, 128, 3, generator=g), torch.rand(2, 64, 3, generator=g)
-    assert torch.allclose(ops.emd_approx(u.cuda(), v.cuda()).cpu(), O.emd_approxmatch_cost(u, v), rtol=2e-3)
+    got_uv = ops.emd_approx(u.cuda(), v.cuda()).cpu()
+    assert within(got_uv, ec.emd_ref64(u, v))
+    assert torch.allclose(got_uv, O.emd_approxmatch_cost(u, v), rtol=ec.EMD_REL + 1e-6, atol=0)
+
+
+def test_emd_derived_metrics_values_golden():
+    """cov-EMD, 1-NN-EMD-acc and mmd-EMD out of compute_all_metrics, and the matrices they are built from, against the float64 reference
+    matrices of the golden clouds (13 x 96 and 12 x 96 points)."""
+    from ldt_amd import metrics as Mx, ops
+    from oracle import ldt_oracle as O
+    a, _ = load_golden("metrics_cd")
+    ref, smp = a["ref"], a["smp"]
+    n = ref.shape[1]
+    M_rs, M_rr, M_ss = ec.golden_matrices(ref, smp)                                          # float64, / n
+    res = Mx.compute_all_metrics(smp.cuda(), ref.cuda(), batch_size=64)
+    want = O.lgan_mmd_cov(M_rs.t())
+    # the counts are equal exactly (the fractions are fp32 quotients formed on two devices: compared as the whole numbers they stand for)
+    count = lambda frac, total: round(float(frac) * total)
+    both = ref.shape[0] + smp.shape[0]
+    assert count(res["cov-EMD"], ref.shape[0]) == count(want["cov"], ref.shape[0])
+    assert count(res["1-NN-EMD-acc"], both) == count(O.knn_two_sample(M_rr, M_rs, M_ss, 1)["acc"], both)
+    assert abs(float(res["cov-EMD"]) - float(want["cov"])) < 1e-6
+    assert within(res["mmd-EMD"], want["mmd"])
+    # identical clouds cost (almost) nothing: on the diagonals of M_rr and M_ss the bound gets the floor EMD_REL x the cloud diameter
+    diam = lambda c: float(torch.cdist(c.double(), c.double()).amax(dim=(1, 2)).max())
+    for s_, r_, M, floor in ((ref, smp, M_rs, 0.0), (ref, ref, M_rr, diam(ref)), (smp, smp, M_ss, diam(smp))):
+        got = Mx._pairwise_EMD_CD_(s_.cuda(), r_.cuda())[1]
+        assert within(got, M, torch.eye(M.shape[0], M.shape[1], dtype=torch.float64) * (ec.EMD_REL * floor)), (got.cpu() - M).abs().max()
+    k = min(ref.shape[0], smp.shape[0])
+    each = Mx.EMD_CD(smp[:k].cuda(), ref[:k].cuda(), 64, reduced=False)["mmd-EMD"]
+    assert torch.equal(each, ops.emd_approx(smp[:k].cuda(), ref[:k].cuda()) / float(n))     # the batched kernel's values / n
+    assert within(each, ec.emd_ref64(smp[:k], ref[:k]) / n)                                 # (sample first: the matching is not symmetric)
 
 
 def test_compute_all_metrics_keys_and_full_size_smoke():
