@@ -154,6 +154,19 @@ enum ldt_act { LDT_ACT_NONE = 0, LDT_ACT_SILU = 1, LDT_ACT_RELU = 2, LDT_ACT_GEL
 int ldt_sgemm(const float* A, int64_t lda, const float* Bw, int64_t ldb, const float* bias,
               void* C, int64_t ldc, int32_t out_bf16, int32_t act_in, int32_t act_out,
               int32_t M, int32_t N, int32_t K, void* stream);
+/* Which of its seven kernel forms ldt_sgemm runs for this problem (a query, not a launch; the return value is the route, not a status; no
+ * device is touched).  The launcher and this query evaluate the same decision function.  misaligned: bit 0 A, bit 1 Bw, bit 2 C, bit 3 bias
+ * is not 16-byte aligned (a NULL bias leaves bit 3 clear).  "Rows of A and Bw load 16 bytes" below means K % 4 == 0, lda % 4 == 0,
+ * ldb % 4 == 0 and bits 0 and 1 clear.  The forms in the order they are tried, the first that takes the problem runs:
+ *   4 / 5 = linear_smalln_kernel<4> / <8> (N <= 4 / N <= 8): M >= 8192, N <= 8, rows of A and Bw load 16 bytes;
+ *   6 / 7 = linear_smallk_kernel<4> / <8> (K <= 4 / K <= 8): M >= 8192, K <= 8, N % 4 == 0 with N / 4 in 8..256 dividing 256 (N = 32, 64,
+ *           128, 256, 512, 1024), ldc % 4 == 0, bits 2 and 3 clear;
+ *   3 = sgemm_mfma_kernel<32,128,1,4,32>: M <= 48, K >= 8, M * N >= 4096, rows of A and Bw load 16 bytes;
+ *   2 = sgemm_mfma_kernel<128,128,2,2>: M > 48, otherwise as 3, and ceil(M / 128) < 65536;
+ *   1 = sgemm_nt_kernel: everything else with ceil(M / 64) < 65536 (it stages with 16-byte loads when rows of A and Bw allow, else scalar);
+ *   0 = no kernel takes it: M, N or K <= 0, or M beyond the last limit (the launch would return LDT_ESHAPE).
+ * Environment, read once per process: LDT_SGEMM_VALU set (to anything) removes the two MFMA forms, LDT_SGEMM_SKINNY=0 the four streaming ones. */
+int ldt_sgemm_route(int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t misaligned);
 
 /* sinusoidal embedding of continuous t (model/layers.py:20-36): e[n][2*half] = [sin(t f) | cos(t f)];
  * freq[half] is built by the host with the reference's fp32 expression (quirk Q5). */

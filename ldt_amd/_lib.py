@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDT_HIP_LIB", os.path.join(_HERE, "libldt_hip.so"))   # override: debug builds only
-ABI_VERSION = 26                # (unchanged by the decoder-training entry points, which are additions: DESIGN.md section 4.15 says who raises it next)
+ABI_VERSION = 26                # (unchanged by the training entry points and by ldt_sgemm_route, which are additions: DESIGN.md section 4.15 says who raises it next)
 MAX_BLOCKS = 64
 ODE_SUMSQ_SCRATCH = 1024        # LDT_ODE_SUMSQ_SCRATCH
 CD_TYPES = {"l1": 1, "l2": 2}   # LDT_CD_L1, LDT_CD_L2
@@ -72,6 +72,7 @@ SIGNATURES = {
     "ldt_qkv_attention_route": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32],
     "ldt_attention_oproj_resid": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp],
     "ldt_sgemm": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "ldt_sgemm_route": [_i32, _i32, _i32, _i64, _i64, _i64, _i32],
     "ldt_sinusoid": [_vp, _vp, _vp, _i32, _i32, _vp],
     "ldt_sampler_step": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _u64, _i32, _i32, _vp],
     "ldt_sampler_step_traj": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _u64, _i32, _i32, _vp],

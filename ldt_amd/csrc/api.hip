@@ -145,6 +145,9 @@ extern "C" int ldt_sgemm(const float* A, int64_t lda, const float* Bw, int64_t l
     SgemmArgs a{A, lda, Bw, ldb, bias, C, ldc, out_bf16, act_in, act_out, M, N, K};
     return ldt_sgemm_launch(&a, ST(stream));
 }
+extern "C" int ldt_sgemm_route(int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t misaligned) {
+    return ldt_sgemm_decide(M, N, K, lda, ldb, ldc, misaligned);
+}
 
 extern "C" int ldt_sinusoid(const float* t, const float* freq, float* e, int32_t n, int32_t half, void* stream) {
     LDT_REQUIRE(t && freq && e, LDT_EARG, "sinusoid: null pointer");

@@ -311,16 +311,42 @@ __global__ __launch_bounds__(256) void sgemm_nt_kernel(const SgemmArgs a) {
         }
     }
 }
+// The seven forms in the order they are tried (the rule is stated in include/ldt_hip.h at ldt_sgemm_route):
+//   streaming forms (skinny_linear.hip), M >= 8192 only: small N (N <= 8, K % 4 == 0, 16-byte rows of A and B), then small K (K <= 8, N / 4 in
+//   8..256 dividing 256, 16-byte rows of C and bias);  MFMA forms (sgemm_mfma.hip): K % 4 == 0, K >= 8, 16-byte rows of A and B, M N >= 4096,
+//   32 x 128 tiles when M <= 48, else 128 x 128;  the scalar-FMA kernel above for everything else its grid can hold.
+int ldt_sgemm_decide(int M, int N, int K, long lda, long ldb, long ldc, int misaligned) {
+    static const bool no_mfma = getenv("LDT_SGEMM_VALU") != nullptr;      // tools/dbg A/B: force the scalar-FMA kernel
+    static const bool no_skinny = getenv("LDT_SGEMM_SKINNY") && atoi(getenv("LDT_SGEMM_SKINNY")) == 0;
+    if (M <= 0 || N <= 0 || K <= 0) return SGEMM_ROUTE_NONE;
+    const bool rows_ab = K % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && !(misaligned & 3);      // 16-B loads of A and B rows
+    if (!no_skinny && M >= 8192) {                                        // short problems: the tiled kernels are fine
+        if (N <= 8 && rows_ab) return N <= 4 ? SGEMM_ROUTE_SMALLN_4 : SGEMM_ROUTE_SMALLN_8;
+        const int nq = N / 4;
+        if (K <= 8 && N % 4 == 0 && nq >= 8 && nq <= 256 && 256 % nq == 0 && ldc % 4 == 0 && !(misaligned & 12))   // 16-B loads of bias, 16-B / 8-B stores
+            return K <= 4 ? SGEMM_ROUTE_SMALLK_4 : SGEMM_ROUTE_SMALLK_8;
+    }
+    if (!no_mfma && rows_ab && K >= 8 && (long)M * N >= 64 * 64) {        // (tiny problems: launch-bound either way, keep the simple kernel)
+        if (M <= 48) return SGEMM_ROUTE_MFMA_32;
+        if ((M + 127) / 128 < 65536) return SGEMM_ROUTE_MFMA_128;
+    }
+    return (M + 63) / 64 < 65536 ? SGEMM_ROUTE_NT : SGEMM_ROUTE_NONE;     // grid.y limit
+}
 int ldt_sgemm_launch(const SgemmArgs* a, hipStream_t s) {
     LDT_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0, LDT_ESHAPE, "sgemm: empty problem");
     LDT_REQUIRE(a->A && a->B && a->C, LDT_EARG, "sgemm: null pointer");
-    static const bool no_mfma = getenv("LDT_SGEMM_VALU") != nullptr;      // tools/dbg A/B: force the scalar-FMA kernel
-    static const bool no_skinny = getenv("LDT_SGEMM_SKINNY") && atoi(getenv("LDT_SGEMM_SKINNY")) == 0;
-    int st = LDT_OK;
-    if (!no_skinny && ldt_skinny_linear_try(a, s, &st)) return st;      // millions of rows x (K <= 32 | N <= 8): streaming forms (skinny_linear.hip)
-    if (!no_mfma && ldt_sgemm_mfma_try(a, s, &st)) return st;            // fp32-input MFMA kernel (sgemm_mfma.hip) when rows are 16-B aligned, K % 16 == 0
+    const int misaligned = (ldt_aligned16(a->A) ? 0 : 1) | (ldt_aligned16(a->B) ? 0 : 2) | (ldt_aligned16(a->C) ? 0 : 4) |
+                           (!a->bias || ldt_aligned16(a->bias) ? 0 : 8);
+    const int route = ldt_sgemm_decide(a->M, a->N, a->K, a->lda, a->ldb, a->ldc, misaligned);
+    switch (route) {
+        case SGEMM_ROUTE_SMALLN_4: case SGEMM_ROUTE_SMALLN_8: case SGEMM_ROUTE_SMALLK_4: case SGEMM_ROUTE_SMALLK_8:
+            return ldt_skinny_linear_launch(a, route, s);
+        case SGEMM_ROUTE_MFMA_128: case SGEMM_ROUTE_MFMA_32:
+            return ldt_sgemm_mfma_launch(a, route, s);
+        case SGEMM_ROUTE_NT: break;
+        default: LDT_REQUIRE(false, LDT_ESHAPE, "sgemm: M too large for this kernel (M=%d)", a->M);
+    }
     dim3 grid((a->N + 63) / 64, (a->M + 63) / 64), block(256);
-    LDT_REQUIRE(grid.y < 65536, LDT_ESHAPE, "sgemm: M too large for this kernel (M=%d)", a->M);
     hipLaunchKernelGGL(sgemm_nt_kernel, grid, block, 0, s, *a);
     return ldt_check_launch("sgemm_nt");
 }

@@ -135,8 +135,14 @@ int ldt_advance_step_launch(int* step_ptr, hipStream_t s);
 int ldt_philox_normal_launch(float* out, long n, long elem_offset, int step, uint32_t k0, uint32_t k1, hipStream_t s);
 int ldt_sinusoid_launch(const float* t, const float* freq, float* e, int n, int half, hipStream_t s);
 int ldt_sgemm_launch(const SgemmArgs* a, hipStream_t s);
-bool ldt_sgemm_mfma_try(const SgemmArgs* a, hipStream_t s, int* status);   // sgemm_mfma.hip: false = shape not taken
-bool ldt_skinny_linear_try(const SgemmArgs* a, hipStream_t s, int* status);   // skinny_linear.hip
+// Which of its seven kernel forms the fp32 linear runs on: THE dispatch rule (elementwise.hip).  ldt_sgemm_launch and the ldt_sgemm_route
+// query (include/ldt_hip.h, which states the rule) call it and nothing else chooses a form.  misaligned: bit 0 A, 1 B, 2 C, 3 bias not
+// 16-byte aligned.  Reads the LDT_SGEMM_VALU / LDT_SGEMM_SKINNY switches once per process; touches no device and no pointer's target.
+enum { SGEMM_ROUTE_NONE = 0, SGEMM_ROUTE_NT = 1, SGEMM_ROUTE_MFMA_128 = 2, SGEMM_ROUTE_MFMA_32 = 3, SGEMM_ROUTE_SMALLN_4 = 4,
+       SGEMM_ROUTE_SMALLN_8 = 5, SGEMM_ROUTE_SMALLK_4 = 6, SGEMM_ROUTE_SMALLK_8 = 7 };
+int ldt_sgemm_decide(int M, int N, int K, long lda, long ldb, long ldc, int misaligned);
+int ldt_sgemm_mfma_launch(const SgemmArgs* a, int route, hipStream_t s);      // sgemm_mfma.hip: SGEMM_ROUTE_MFMA_128 / _32 (grid and launch)
+int ldt_skinny_linear_launch(const SgemmArgs* a, int route, hipStream_t s);   // skinny_linear.hip: SGEMM_ROUTE_SMALLN_* / SMALLK_* (grid sized to the device, launch)
 
 int ldt_fps_launch(const float* xyz, int B, int n, int m, int skip_near_origin, int* idx, hipStream_t s);
 int ldt_fps_wave_launch(const float* xyz, int B, int n, int m, int skip_near_origin, int* idx, hipStream_t s);   // fps_wave.hip

@@ -127,12 +127,9 @@ __global__ __launch_bounds__(256) void sgemm_mfma_kernel(const SgemmArgs a) {
         }
 }
 
-// -> true when the MFMA kernel took the problem (K % 4 == 0 — a ragged last slab is zero-filled —, 16-byte aligned rows);
-// otherwise the caller falls back to the scalar kernel (the 3-channel input convs, 131/259-channel grouper rows).
-bool ldt_sgemm_mfma_try(const SgemmArgs* a, hipStream_t s, int* status) {
-    if (a->K % 4 != 0 || a->K < 8 || a->lda % 4 != 0 || a->ldb % 4 != 0 || !ldt_aligned16(a->A) || !ldt_aligned16(a->B)) return false;
-    if ((long)a->M * a->N < 64 * 64) return false;       // tiny problems: launch-bound either way, keep the simple kernel
-    if (a->M <= 48) {                                     // skinny: per-step per-sample AdaLN rows (M = batch), weight streaming
+// route: ldt_sgemm_decide's (SGEMM_ROUTE_MFMA_128 or _32: K % 4 == 0 — a ragged last slab is zero-filled —, 16-byte aligned rows).
+int ldt_sgemm_mfma_launch(const SgemmArgs* a, int route, hipStream_t s) {
+    if (route == SGEMM_ROUTE_MFMA_32) {                   // skinny: per-step per-sample AdaLN rows (M = batch), weight streaming
         // 32 x 128 tiles, 32-deep slabs: M = 32, N = 149,504, K = 1024 in 161 us = 3.8 TB/s of weights with the SiLU of the AdaLN input applied
         // by the caller (176 with it in stage(); 32 x 256 tiles: 196; 16-deep slabs: 215).  Round-4 probes (tools/dbg/skinny_sgemm_bench.py,
         // profiles/r04_skinny_sgemm_probes.txt): a second slab of register prefetch is SLOWER (200 us), rows padded off the 4-KiB stride 165-173,
@@ -143,10 +140,9 @@ bool ldt_sgemm_mfma_try(const SgemmArgs* a, hipStream_t s, int* status) {
         dim3 grid((a->N + 127) / 128, (a->M + 31) / 32);
         hipLaunchKernelGGL((sgemm_mfma_kernel<32, 128, 1, 4, 32>), grid, dim3(256), 0, s, *a);
     } else {
+        LDT_REQUIRE(route == SGEMM_ROUTE_MFMA_128, LDT_EARG, "sgemm_mfma: route %d is not an MFMA form", route);
         dim3 grid((a->N + 127) / 128, (a->M + 127) / 128);
-        if (grid.y >= 65536) return false;
         hipLaunchKernelGGL((sgemm_mfma_kernel<128, 128, 2, 2>), grid, dim3(256), 0, s, *a);
     }
-    *status = ldt_check_launch("sgemm_mfma");
-    return true;
+    return ldt_check_launch("sgemm_mfma");
 }

@@ -3,7 +3,8 @@
 //     out[M][N] = act_out( act_in(A[M][K]) . W[N][K]^T + bias )
 // A 128-wide MFMA tile spends 98 % of its work on zero padding there (N = 3) or cannot be used at all (K = 3), and the generic kernels
 // ran at 0.04 – 0.3 of the HBM rate.  Two forms, both fp32 FMA chains (the fp32 parity bars of ldt_sgemm hold), both bandwidth-bound:
-//   * small K (<= 8), N a multiple of 4 dividing 1024: a thread owns 4 consecutive outputs of a row with its K x 4 weights in
+// (which problems take which form: ldt_sgemm_decide in elementwise.hip, stated at ldt_sgemm_route in include/ldt_hip.h)
+//   * small K (<= 8), N / 4 in 8..256 dividing 256 (N = 32 ... 1024): a thread owns 4 consecutive outputs of a row with its K x 4 weights in
 //     registers for the whole (grid-strided) launch; the row's K inputs are broadcast loads; 16-B (fp32) or 8-B (bf16) stores, whole rows
 //     per 32 lanes;
 //   * small N (<= 8), K a multiple of 4: 32 lanes read a row 16 B each (coalesced), N partial dot products per lane, 5 xor-shuffles.
@@ -127,31 +128,25 @@ __global__ __launch_bounds__(256) void linear_smalln_kernel(const SgemmArgs a) {
 
 }  // namespace
 
-// -> true when one of the streaming forms took the problem
-bool ldt_skinny_linear_try(const SgemmArgs* a, hipStream_t s, int* status) {
-    if (a->M < 8192) return false;                                   // short problems: the tiled kernels are fine
+// route: ldt_sgemm_decide's (one of the four streaming forms).  Grid sizing only: the kernels stride over the rows, so the grid caps at a
+// fixed number of workgroups per CU and a longer problem takes further trips.
+int ldt_skinny_linear_launch(const SgemmArgs* a, int route, hipStream_t s) {
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (a->N <= 8 && a->K % 4 == 0 && a->lda % 4 == 0 && a->ldb % 4 == 0 && ldt_aligned16(a->A) && ldt_aligned16(a->B)) {
+    if (route == SGEMM_ROUTE_SMALLN_4 || route == SGEMM_ROUTE_SMALLN_8) {
         long blocks = ((long)a->M + 31) / 32;
         if (blocks > (long)cus * 16) blocks = (long)cus * 16;
-        if (a->N <= 4) hipLaunchKernelGGL(linear_smalln_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, *a);
+        if (route == SGEMM_ROUTE_SMALLN_4) hipLaunchKernelGGL(linear_smalln_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, *a);
         else hipLaunchKernelGGL(linear_smalln_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, s, *a);
-        *status = ldt_check_launch("linear_smalln");
-        return true;
+        return ldt_check_launch("linear_smalln");
     }
-    const int nq = a->N / 4;
-    if (a->K <= 8 && a->N % 4 == 0 && nq >= 8 && nq <= 256 && 256 % nq == 0 && ldt_aligned16(a->C) &&
-        a->ldc % 4 == 0 && (!a->bias || ldt_aligned16(a->bias))) {
-        const int rpb = 256 / nq;
-        long blocks = ((long)a->M + rpb * 4 - 1) / (rpb * 4);
-        if (blocks > (long)cus * 8) blocks = (long)cus * 8;
-        const dim3 g((unsigned)blocks), b(256);
-        if (a->K <= 4) hipLaunchKernelGGL(linear_smallk_kernel<4>, g, b, 0, s, *a);
-        else hipLaunchKernelGGL(linear_smallk_kernel<8>, g, b, 0, s, *a);
-        *status = ldt_check_launch("linear_smallk");
-        return true;
-    }
-    return false;
+    LDT_REQUIRE(route == SGEMM_ROUTE_SMALLK_4 || route == SGEMM_ROUTE_SMALLK_8, LDT_EARG, "skinny_linear: route %d is not a streaming form", route);
+    const int rpb = 256 / (a->N / 4);
+    long blocks = ((long)a->M + rpb * 4 - 1) / (rpb * 4);
+    if (blocks > (long)cus * 8) blocks = (long)cus * 8;
+    const dim3 g((unsigned)blocks), b(256);
+    if (route == SGEMM_ROUTE_SMALLK_4) hipLaunchKernelGGL(linear_smallk_kernel<4>, g, b, 0, s, *a);
+    else hipLaunchKernelGGL(linear_smallk_kernel<8>, g, b, 0, s, *a);
+    return ldt_check_launch("linear_smallk");
 }

@@ -175,6 +175,27 @@ def sgemm(a, w, bias=None, act_in=ACT_NONE, act_out=ACT_NONE, out=None, out_bf16
     return out
 
 
+SGEMM_ROUTES = ("none", "sgemm_nt", "sgemm_mfma<128,128>", "sgemm_mfma<32,128>", "linear_smalln<4>", "linear_smalln<8>",
+                "linear_smallk<4>", "linear_smallk<8>")
+
+
+def sgemm_route_shape(M, N, K, lda=None, ldb=None, ldc=None, misaligned=0):
+    """Which of its seven kernel forms sgemm runs for this shape: the launcher's own decision (ldt_sgemm_route), no launch, no device, no
+    allocation.  Leading dimensions default to the dense ones; misaligned: bit 0 a, 1 w, 2 out, 3 bias not 16-byte aligned.
+    -> index into SGEMM_ROUTES (0: no kernel takes it)."""
+    return int(lib().ldt_sgemm_route(int(M), int(N), int(K), int(K if lda is None else lda), int(K if ldb is None else ldb),
+                                     int(N if ldc is None else ldc), int(misaligned)))
+
+
+def sgemm_route(a, w, bias=None, out=None):
+    """sgemm_route_shape of the call sgemm(a, w, bias, out=out): strides and alignment from the tensors themselves (a fresh output is
+    dense and aligned; the route does not depend on the activations or the output type)."""
+    M, K = a.shape
+    N = w.shape[0]
+    mis = sum(bit for bit, t in ((1, a), (2, w), (4, out), (8, bias)) if t is not None and t.data_ptr() % 16)
+    return sgemm_route_shape(M, N, K, a.stride(0), w.stride(0), N if out is None else out.stride(0), mis)
+
+
 def sinusoid(t, freq):
     _need(t, torch.float32, "t"); _need(freq, torch.float32, "freq")
     e = torch.empty((t.numel(), 2 * freq.numel()), dtype=torch.float32, device=t.device)

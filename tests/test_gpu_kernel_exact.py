@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import kernel_checks as kc
+import sgemm_checks as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -365,30 +366,36 @@ def test_gemm_exact_probes(epi, M, N, K, fold, expected):
         _exact_plain(epi, M, N, K)
 
 
-@pytest.mark.parametrize("M,N,K", [(1000, 768, 64), (130, 300, 256), (1000, 2048, 1024),        # sgemm_mfma
-                                   (19, 2085, 512), (1, 2048, 1024), (20001, 128, 3), (30003, 3, 128), (10000, 1, 512),   # skinny forms
-                                   (5, 64, 3), (65, 40, 128)])
+@pytest.mark.parametrize("M,N,K", [(1000, 768, 64), (130, 300, 256), (1000, 2048, 1024),        # 128 x 128 MFMA
+                                   (19, 2085, 512),                                             # 32 x 128 MFMA
+                                   (20001, 128, 3), (30003, 3, 128), (10000, 1, 512),           # streaming: small-K <4>, small-N <4>, small-N <4>
+                                   (1, 2048, 1024), (5, 64, 3), (65, 40, 128)])                 # scalar-FMA kernel (M N < 4096; K % 4 != 0)
 def test_sgemm_selection_probe(M, N, K):
     x, w, ref = kc.selection_probe(M, N, K)
     b = (torch.arange(N) % 7 - 3).float()
+    assert ops.sgemm_route(dev(x), dev(w), dev(b)) == sc.LEGACY_ROUTES[(M, N, K)]
     out = ops.sgemm(dev(x), dev(w), dev(b))
     kc.assert_elementwise(out, dev(ref).double() + dev(b).double(), 0.0, "selection probe, sgemm %dx%dx%d" % (M, N, K))
 
 
+# the route of every shape, by the launcher's own query: sgemm_checks.LEGACY_ROUTES (asserted on the CPU by test_sgemm_route_host.py and below)
 SGEMM = [(5, 64, 3), (300, 128, 20), (1000, 768, 64), (7, 2048, 1024), (65, 40, 128), (130, 300, 256), (32, 1000, 512), (1000, 2048, 1024),
-         (4096, 40, 128), (2048, 128, 20),                                                       # sgemm_mfma / scalar-FMA kernel
-         (19, 2085, 512), (32, 4224, 256), (1, 2048, 1024),                                      # skinny AdaLN-row form (M <= 32, N >= 2048)
-         (20001, 128, 3), (16385, 128, 20), (9000, 64, 32), (30003, 3, 128), (8193, 8, 64), (10000, 1, 512)]   # streaming forms (skinny_linear.hip)
+         (4096, 40, 128), (2048, 128, 20),                     # scalar-FMA kernel (5 x 64 x 3, 65 x 40 x 128), 32 x 128 MFMA (M = 7, 32), else 128 x 128 MFMA
+         (19, 2085, 512), (32, 4224, 256), (1, 2048, 1024),    # 32 x 128 MFMA (M <= 48); M = 1 has M N < 4096: scalar-FMA kernel
+         (20001, 128, 3), (16385, 128, 20), (9000, 64, 32),    # M >= 8192: small-K <4>, then two shapes with K > 8 and N > 8: 128 x 128 MFMA
+         (30003, 3, 128), (8193, 8, 64), (10000, 1, 512)]      # small-N <4>, <8>, <4>
 
 
 @pytest.mark.parametrize("M,N,K", SGEMM)
 def test_sgemm_bound_and_integer_probe(M, N, K):
-    """ops.sgemm on the shapes of test_gpu_kernels.py::test_sgemm (all three routes), per element: randn data against float64 within the fp32
+    """ops.sgemm on the shapes of test_gpu_kernels.py::test_sgemm (six of the seven kernel forms; all seven, with activations and views:
+    test_gpu_sgemm_exact.py), per element: randn data against float64 within the fp32
     accumulation bound, and the integer probe exactly.  The bound's factor on 2^-24 (|a| |w|^T + |b|): K + 1 roundings at the worst; these
     kernels add their products one after another (fp32 FMA chains, 32 x 32 x 2 MFMAs), so their error grows like sqrt(K) with a larger
     constant than the blocked bf16 kernels': measured on the MI355X up to 4.7 at K = 64 and 3.9 at K = 20, hence a floor of 8 under C_ACC K."""
     g = torch.Generator().manual_seed(K * 7 + N)
     a = dev(torch.randn(M, K, generator=g)); w = dev(torch.randn(N, K, generator=g) / K ** 0.5); b = dev(torch.randn(N, generator=g))
+    assert ops.sgemm_route(a, w, b) == sc.LEGACY_ROUTES[(M, N, K)]
     ref, tol = kc.sgemm_ref(a, w, b)
     r = kc.assert_elementwise(ops.sgemm(a, w, b), ref, tol, "sgemm %dx%dx%d" % (M, N, K))
     tol_r = tol + kc.U24 * torch.relu(ref)

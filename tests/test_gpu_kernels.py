@@ -317,24 +317,30 @@ def test_layernorm_modulate(M, C):
 # ------------------------------------------------------------------------------------------- fp32 linears
 @pytest.mark.parametrize("M,N,K", [(5, 64, 3), (300, 128, 20), (1000, 768, 64), (7, 2048, 1024), (65, 40, 128), (130, 300, 256),
                                    (32, 1000, 512), (1000, 2048, 1024), (4096, 40, 128), (2048, 128, 20),
-                                   # LDS-DMA streaming form of the skinny AdaLN-row GEMM (M <= 32, N >= 2048, K % 32 == 0): ragged N, M < 32
+                                   # the 32 x 128 MFMA form of the AdaLN-row GEMM (M <= 48, M N >= 4096): ragged N, M < 32; M = 1 stays on the scalar kernel
                                    (19, 2085, 512), (32, 4224, 256), (1, 2048, 1024),
-                                   # streaming forms (skinny_linear.hip): millions-of-rows convs of the Compressor, ragged tails
+                                   # M >= 8192.  Streaming forms (skinny_linear.hip) take K <= 8 or N <= 8 only: (20001, 128, 3) small-K, the last
+                                   # three small-N; (16385, 128, 20) and (9000, 64, 32) run the 128 x 128 MFMA kernel.  Ragged tails
                                    (20001, 128, 3), (16385, 128, 20), (9000, 64, 32), (30003, 3, 128), (8193, 8, 64), (10000, 1, 512)])
 def test_sgemm(M, N, K):
+    """the kernel form of every shape is the one sgemm_checks.LEGACY_ROUTES names, by the launcher's own query (per element and by route:
+    test_gpu_sgemm_exact.py)"""
     from ldt_amd._lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SILU
+    import sgemm_checks as sc
     g = torch.Generator().manual_seed(K)
     a = torch.randn(M, K, generator=g); w = torch.randn(N, K, generator=g) / K ** 0.5; b = torch.randn(N, generator=g)
     F = torch.nn.functional
+    assert ops.sgemm_route(dev(a), dev(w), dev(b)) == sc.LEGACY_ROUTES[(M, N, K)]
     out = ops.sgemm(dev(a), dev(w), dev(b))
     assert rel_mse(out.cpu(), a.double() @ w.double().T + b.double()) < 1e-12
     out = ops.sgemm(dev(a), dev(w), dev(b), act_in=ACT_SILU, act_out=ACT_RELU)
     assert rel_mse(out.cpu(), torch.relu(F.silu(a.double()) @ w.double().T + b.double())) < 1e-12
     out = ops.sgemm(dev(a), dev(w), None, act_out=ACT_GELU, out_bf16=True)
     assert rel_mse(out.float().cpu(), F.gelu(a.double() @ w.double().T)) < 1e-5
-    # strided input / output views
+    # strided input / output views: columns 3.. of K + 11 and 2.. of N + 5 break the 16-byte alignment, so every shape runs the scalar kernel here
     big = torch.randn(M, K + 11, generator=g)
     outb = torch.zeros(M, N + 5, device="cuda")
+    assert ops.sgemm_route(dev(big)[:, 3:3 + K], dev(w), dev(b), outb[:, 2:2 + N]) == sc.ROUTE_NT
     ops.sgemm(dev(big)[:, 3:3 + K], dev(w), dev(b), out=outb[:, 2:2 + N])
     assert rel_mse(outb[:, 2:2 + N].cpu(), big[:, 3:3 + K].double() @ w.double().T + b.double()) < 1e-12
     assert float(outb[:, :2].abs().sum()) == 0
