@@ -393,6 +393,14 @@ int ldt_occupancy_grid(const float* pts, int32_t S, int32_t n, const float* cell
  *   -2 (eta - params) weight[b] / (B per_sample), or -sign(eta - params) weight[b] / (B per_sample) when l1.
  * ldt_embedding_grad: dE[k][:] = sum over the samples with label[b] == k of dc[b][:], in the order of b (the label nn.Embedding,
  *   model/scorenet/score.py:125-128); every row of dE[n_classes][D] is written.
+ * ldt_actnorm_bwd: backward of ldt_actnorm (model/layers.py:103-107 `(x - shift) * exp(-log_scale)`, the parameters :66-72; the Compressor's
+ *   conv_in, Network.py:200-201) from the fp32 gradient dz and the forward's OUTPUT z [B][per_sample] (the forward runs in place: z is what is
+ *   kept): dx[b][i] = dz[b][i] exp(-log_scale[i]) (dx may alias dz), dshift[i] = -sum_b dx[b][i], dlog_scale[i] = -sum_b dz[b][i] z[b][i];
+ *   dshift / dlog_scale fp32 [per_sample], each nullable (both NULL: dx only; z is read for dlog_scale alone).  Both forms of the reference's
+ *   ActNorm: per token and channel (per_sample = T C, B samples) and 'set' (per_sample = C, B T rows).  The sums run over b in ascending order
+ *   inside contiguous runs of rows, the runs and — past 512 rows — the workgroups' partials (stream-ordered scratch of the call's own) are added
+ *   in index order: float64 throughout, one rounding, no atomics.  16-byte accesses when per_sample % 4 == 0 and dz, z, log_scale, dx are
+ *   16-byte aligned, the scalar form of the same kernel otherwise.  LDT_EARG for a null pointer, B < 1 or per_sample < 1.
  * ldt_attention_bwd: backward of ldt_attention_fwd for self-attention with head_dim 64, Nq = Nk = N <= 512 (model/layers.py:190-197).  Q, K, V as
  *   ldt_attention_fwd takes them; O and dO are the contiguous [B][H][N][64] buffer that IS the raw (B N, C) view (quirk Q1: nothing is
  *   permuted); dQ, dK, dV are written as row views like Q, K, V (heads at column h * 64; dK and dV share dkv_batch_stride).  Row maximum and
@@ -434,6 +442,8 @@ int ldt_silu_bwd(const float* c, const float* dy, float* dc, float* act, int64_t
 int ldt_dsm_loss_bwd(const float* eta, const float* params, const float* weight, int64_t B, int64_t per_sample, int32_t l1, float* dparams,
                      void* stream);
 int ldt_embedding_grad(const float* dc, int64_t ld, const int32_t* label, int32_t B, int32_t D, int32_t n_classes, float* dE, void* stream);
+int ldt_actnorm_bwd(const float* dz, const float* z, const float* log_scale, int64_t B, int64_t per_sample, float* dx, float* dshift,
+                    float* dlog_scale, void* stream);
 int ldt_attention_bwd(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K, int64_t ldk, const uint16_t* V,
                       int64_t ldv, int64_t kv_batch_stride, const uint16_t* O, const uint16_t* dO, float* stats, uint16_t* dQ,
                       int64_t lddq, int64_t dq_batch_stride, uint16_t* dK, int64_t lddk, uint16_t* dV, int64_t lddv,

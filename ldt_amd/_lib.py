@@ -100,6 +100,7 @@ SIGNATURES = {
     "ldt_gather_rows": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
     "ldt_maxpool": [_vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp],
     "ldt_actnorm": [_vp, _vp, _vp, _i64, _i64, _vp],
+    "ldt_actnorm_bwd": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
     "ldt_reparam": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, C.c_float, C.c_float, _vp],
     "ldt_chamfer": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "ldt_reparam_kl": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, C.c_float, C.c_float, _vp],

@@ -411,10 +411,10 @@ class Compressor(nn.Module):
         return self.forward(x, **kw)["all_eps"]
 
     # ------------------------------------------------------------------ encode (Network.py:188-249)
-    def _bottom_up(self, P, x, label, want_stats=False):
-        """Network.py:188-206: input conv, FPS + kNN grouping, PreExtraction, pos embedding, ActNorm, encoder stages -> (the n_layers stage
-        outputs, fresh token-major fp32 [B*T, D] buffers; the token stream; its copy before ActNorm when want_stats; the label embedding or
-        None; fps_idx, knn_idx, centers)."""
+    def _front(self, P, x, label):
+        """Network.py:189-198: input conv, FPS + kNN grouping, PreExtraction, pos embedding (+ the label embedding) -> (the grouped tokens,
+        token-major fp32 [B*T, D], BEFORE ActNorm; the position condition [B, p_dim], or [B*T, p_dim] with pos_embedding: mlp; the label
+        embedding or None; fps_idx, knn_idx, centers)."""
         dev = self._device()
         B, N, _ = x.shape
         T, D = self.z_scales, self.hidden_dim
@@ -428,9 +428,7 @@ class Compressor(nn.Module):
             n_cur = 256
         k = n_cur // T * 2                                                          # :195
         centers, tok, fps_idx, knn_idx = run_grouper(P["group"], pts, feat.view(B, n_cur, D), T, k)
-        tok_pre = tok.clone() if want_stats else None
-        per_tok = "w_pm1" in P
-        if per_tok:                                                                 # pos_embedding: mlp (:133-134): one row per token
+        if "w_pm1" in P:                                                            # pos_embedding: mlp (:133-134): one row per token
             from ._lib import ACT_GELU
             pos = ops.sgemm(ops.sgemm(centers.view(B * T, 3), P["w_pm1"], P["b_pm1"], act_out=ACT_GELU), P["w_pm2"], P["b_pm2"])
         else:
@@ -443,6 +441,31 @@ class Compressor(nn.Module):
             e = PL["emb"][label.to(dev).long()].contiguous()
             l_emb = ops.sgemm(ops.sgemm(e, PL["w1"], PL["b1"], act_out=ACT_SILU), PL["w2"], PL["b2"])
             pos = pos + l_emb
+        return tok, pos, l_emb, fps_idx, knn_idx, centers
+
+    @torch.no_grad()
+    def front(self, x, label=None):
+        """The part of the bottom-up pass below ActNorm (Network.py:189-198), which the encoder training step keeps frozen: x (B, N, 3) ->
+        {'tokens': the grouped tokens (B, tokens, hidden) fp32 BEFORE ActNorm, 'pos': the position condition (B, p_dim) (with
+        pos_embedding: mlp one row per token, (B, tokens, p_dim)), 'centers', 'fps_idx', 'knn_idx' as `forward` returns them}.
+        `forward`, `encode` and `bottom_up` run the same code."""
+        self._no_training_dropout("front")
+        dev = self._device()
+        if dev.type != "cuda":
+            raise RuntimeError("Compressor.front: parameters on %s; the HIP path has no CPU fallback" % dev)
+        tok, pos, _, fps_idx, knn_idx, centers = self._front(self.packed(), x, label)
+        B, T = x.shape[0], self.z_scales
+        return {"tokens": tok.view(B, T, self.hidden_dim), "pos": pos.view(B, -1) if pos.shape[0] == B else pos.view(B, T, -1),
+                "centers": centers, "fps_idx": fps_idx, "knn_idx": knn_idx}
+
+    def _bottom_up(self, P, x, label, want_stats=False):
+        """Network.py:188-206: input conv, FPS + kNN grouping, PreExtraction, pos embedding, ActNorm, encoder stages -> (the n_layers stage
+        outputs, fresh token-major fp32 [B*T, D] buffers; the token stream; its copy before ActNorm when want_stats; the label embedding or
+        None; fps_idx, knn_idx, centers)."""
+        B, T, D = x.shape[0], self.z_scales, self.hidden_dim
+        tok, pos, l_emb, fps_idx, knn_idx, centers = self._front(P, x, label)
+        tok_pre = tok.clone() if want_stats else None
+        per_tok = "w_pm1" in P
         if self.ActNorm is not None:
             ops.actnorm_(tok, P["an_shift"], P["an_logs"], B)
         enc_out = []

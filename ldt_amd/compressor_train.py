@@ -1,4 +1,12 @@
-"""Training the Compressor's top-down half on the HIP path, in two steps that share their per-level pieces.
+"""Training the Compressor on the HIP path from the grouped tokens up, in three steps that share their pieces.
+
+`EncoderTrainStep`: what lies between the frozen front (`Compressor.front`: input conv, grouper, position
+embedding) and the top-down half (Network.py:200-205): ActNorm, then per stage the AdaLN self-attention blocks (K / V from the RAW token
+stream, quirk Q2) and the FinalLayer `conv_out`, all modulated by rows of ONE fp32 linear on SiLU(pos).  Its backward starts from
+TopDownTrainStep's `d_enc_out`, runs the stages in reverse with the FinalLayer's gradient ADDED to the running stream gradient (the stream
+runs on into the next stage), and ends in `ldt_actnorm_bwd`; it returns (d_tokens, d_pos), where the grouper's and the position embedding's
+backward would start.  The block body is train.ScoreTrainStep's (`ldt_layernorm_modulate_bwd`, `ldt_gate_residual_bwd`, `ldt_gelu_bwd`,
+`ldt_attention_bwd_cross` at T on T, `ldt_silu_bwd`, `ldt_sgemm` for the conditioning linear).
 
 `TopDownTrainStep`: everything from the encoder's outputs upward (Network.py:208-233, `top_down`): per level the
 posterior block `decoder[l].att` (the T latent tokens attend to the N points of the running set stream; level 0 to themselves), the
@@ -6,7 +14,7 @@ posterior block `decoder[l].att` (the T latent tokens attend to the N points of 
 posterior of level j + 1 reads the set stream o_{j+1}, so its K/V gradient has to be in `dX` before decoder block j runs backward.
 Kernels on top of the decoder step's: `ldt_attention_bwd_wide` (T queries on N keys; level 0's T on T is `ldt_attention_bwd_cross`),
 `ldt_reparam_kl_bwd`, `ldt_silu_bwd`.  It returns the gradient with respect to the encoder outputs (`d_enc_out`), where the encoder backward
-will start; the bottom-up half (input conv, grouper, position embedding, ActNorm, encoder) stays frozen.
+starts; on its own it leaves the bottom-up half (input conv, grouper, position embedding, ActNorm, encoder) frozen.
 
 `DecoderTrainStep` (section 4.15), the decoder alone: the host-driven top-down forward that keeps what the backward needs, and the backward
 from the gradient of the decoded set down to the decoder-side parameters and the latents.
@@ -408,3 +416,203 @@ class TopDownTrainStep:
         self.d_eps = d_eps.view(B, T, L * z)
         self.d_enc_out = d_enc
         return d_enc
+
+
+# ---------------------------------------------------------------- the encoder: ActNorm and the AdaLN stages
+def encoder_parameters(model):
+    """The parameters an encoder step trains, in module order: conv_in's ActNorm, and per stage the AdaLN blocks and the FinalLayer
+    (`norm1` / `norm2` / `norm` have no parameters under AdaLN)."""
+    names = ("fc_q", "fc_kv", "fc_o", "adaLN", "mlp")
+    out = []
+    for name, p in model.named_parameters():
+        parts = name.split(".")
+        if parts[0] == "conv_in" and parts[1] in ("shift", "log_scale"):
+            out.append((name, p))
+        elif parts[0] == "encoder" and ((parts[2] == "atts" and parts[4] in names) or (parts[2] == "conv_out" and parts[3] in ("adaLN", "ln"))):
+            out.append((name, p))
+    return out
+
+
+def refuse_untrainable_encoder(model, tokens=None):
+    """The configurations the encoder step does not cover, each refused with its reason before anything is launched (works on CPU
+    parameters).  tokens: the token count of the call (default: cfg.z_scales).  `ActNorm: ~` is covered: the step then has no ActNorm."""
+    from .layers import MLP
+    if isinstance(model.pos_embedding, MLP):
+        raise NotImplementedError("training the encoder with pos_embedding: mlp is not on this path: a per-token position condition modulates "
+                                  "every token with its own row, and the modulation backward sums over a sample's tokens")
+    if getattr(model, "class_condition", False):
+        raise NotImplementedError("training the encoder with class_condition is not on this path: the label embedding added to the position "
+                                  "condition has no backward here")
+    if model.AdaLN is not None and not model.AdaLN:
+        raise NotImplementedError("training the encoder with AdaLN: False is not on this path: the backward covers the AdaLN blocks only")
+    if not (isinstance(model.norm, str) and model.norm.lower() == "layer_norm"):
+        raise NotImplementedError("training the encoder with norm=%r is not on this path: only layer_norm has a backward kernel" % (model.norm,))
+    if float(getattr(model, "encoder_dropout_p", 0.) or 0.) > 0:
+        raise NotImplementedError("training the encoder with encoder_dropout_p=%g is not on this path: the kernels have no dropout mask"
+                                  % model.encoder_dropout_p)
+    if model.hidden_dim % model.num_heads or model.hidden_dim // model.num_heads != HEAD_DIM:
+        raise NotImplementedError("training the encoder needs %d-wide attention heads (ldt_attention_bwd_cross as the decoder's kernels take "
+                                  "them); got hidden %d / %d heads" % (HEAD_DIM, model.hidden_dim, model.num_heads))
+    T = model.z_scales if tokens is None else int(tokens)
+    if not 1 <= T <= EncoderTrainStep.MAX_TOKENS:
+        raise NotImplementedError("training the encoder with %d tokens is not on this path: ldt_attention_bwd_cross takes 1 <= Nq, Nk <= %d"
+                                  % (T, EncoderTrainStep.MAX_TOKENS))
+
+
+class EncoderTrainStep:
+    """One forward + backward of the Compressor's encoder (Network.py:200-205: ActNorm, then per stage `encoder_layers` AdaLN blocks that
+    attend to their own RAW input (layers.py:210-219 with y = x, quirk Q2) and the FinalLayer `conv_out`, :41-45).  `forward(tokens, pos)`
+    takes the grouped tokens (B, T, hidden) BEFORE ActNorm and the position condition (B, p_dim) (`Compressor.front`) and returns the
+    n_layers stage outputs, fresh fp32 (B, T, hidden) tensors, keeping the tape; `backward(d_enc_out)` fills every `.grad` of
+    encoder_parameters(model) and returns (d_tokens (B, T, hidden), d_pos (B, p_dim)), kept as `self.d_tokens` / `self.d_pos`: where the
+    grouper's and the position embedding's backward would start."""
+
+    MAX_TOKENS = 512                                                   # ldt_attention_bwd_cross: 1 <= Nq, Nk <= 512
+
+    def __init__(self, model):
+        refuse_untrainable_encoder(model)
+        self.m = model
+        self.saved = None
+        self.d_tokens = None
+        self.d_pos = None
+
+    def _adaln(self):
+        """Every block's and FinalLayer's adaLN.1 in the order the modulation row is laid out: per stage the blocks (6 C each: shift_msa,
+        scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp), then conv_out (2 C: shift, scale)."""
+        return [lin for e in self.m.encoder for lin in [a.adaLN[1] for a in e.atts] + [e.conv_out.adaLN[1]]]
+
+    # ---------------------------------------------------------------- forward
+    @torch.no_grad()
+    def forward(self, tokens, pos):
+        m = self.m
+        for t in (tokens, pos):
+            if not (torch.is_tensor(t) and t.is_cuda):
+                raise RuntimeError("EncoderTrainStep.forward: an operand is on %s; the HIP path has no CPU fallback"
+                                   % (t.device if torch.is_tensor(t) else type(t).__name__,))
+        self.saved = None
+        C, H = m.hidden_dim, m.num_heads
+        if tokens.dim() != 3 or tokens.shape[2] != C:
+            raise ValueError("EncoderTrainStep.forward: tokens %s is not (B, tokens, hidden = %d)" % (tuple(tokens.shape), C))
+        B, T = tokens.shape[0], tokens.shape[1]
+        if tuple(pos.shape) != (B, m.p_dim):
+            raise ValueError("EncoderTrainStep.forward: pos %s is not (B = %d, p_dim = %d)" % (tuple(pos.shape), B, m.p_dim))
+        refuse_untrainable_encoder(m, T)
+        M = B * T
+        P = m.packed()
+        S = {"B": B, "T": T, "stages": []}
+        X = tokens.detach().float().contiguous().view(M, C).clone()     # the token stream x, updated in place below
+        if m.ActNorm is not None:
+            if P["an_shift"].numel() not in (C, T * C):
+                raise ValueError("EncoderTrainStep.forward: ActNorm holds %d values for %d tokens of %d channels" % (P["an_shift"].numel(), T, C))
+            ops.actnorm_(X, P["an_shift"], P["an_logs"], M * C // P["an_shift"].numel())                  # Network.py:200-201
+        S["pos"] = pos.detach().float().contiguous()
+        lins = self._adaln()
+        S["w_ada"] = torch.cat([_f32(l.weight) for l in lins], 0)
+        mod = S["mod"] = ops.sgemm(S["pos"], S["w_ada"], torch.cat([_f32(l.bias) for l in lins], 0), act_in=ACT_SILU)   # [B, n_mod]
+        n_mod = mod.shape[1]
+        mv = lambda off: mod[:, off:off + C]
+        kw = dict(mod_sample_stride=n_mod, rows_per_sample=T)
+        gk = dict(gate_sample_stride=n_mod, rows_per_sample=T)
+        outs, m0 = [], 0
+        for Pe in P["enc"]:
+            st = {"blocks": []}
+            for A in Pe["atts"]:
+                sb = {"x1": X.clone()}                                  # (the first block's x1 is ActNorm's output z)
+                sb["h"] = ops.layernorm_modulate(X, shift=mv(m0), scale=mv(m0 + C), **kw)
+                sb["y"] = ops.cast_pad_bf16(X, ops.pad64(C))            # K / V from the RAW x (Network.py:44, quirk Q2)
+                sb["q"] = ops.gemm_bf16(sb["h"], A["wq"], A["bq"], EPI_BF16)
+                sb["kv"] = ops.gemm_bf16(sb["y"], A["wkv"], A["bkv"], EPI_BF16)
+                sb["o"] = ops.attention_fwd(sb["q"], sb["kv"][:, :C], sb["kv"][:, C:], B, H, T, T, HEAD_DIM)   # [B, H, T, 32] == (M, C) raw view (Q1)
+                # the backward's K | V: the raw tokens share a large common component (mean key / rms key 0.8 - 0.9 at the tiny fixture), the
+                # case _centred_keys was written for (section 4.17: dQ rel-MSE 1e-4 - 2e-4 from D = rowsum(dO o O) of the bf16 O, 1e-7 - 4e-7 centred)
+                sb["kv"] = _centred_keys(A, sb["y"], sb["kv"], B, T)
+                o2 = sb["o"].view(M, C)
+                sb["a1"] = ops.gemm_bf16(o2, A["wo"], A["bo"], EPI_BF16)                                  # the branch output, for dgate
+                ops.gemm_bf16(o2, A["wo"], A["bo"], EPI_RESID_F32, out=X, resid=X, gate=mv(m0 + 2 * C), **gk)
+                sb["x2"] = X.clone()
+                sb["h2"] = ops.layernorm_modulate(X, shift=mv(m0 + 3 * C), scale=mv(m0 + 4 * C), **kw)
+                sb["u"] = ops.gemm_bf16(sb["h2"], A["wup"], A["bup"], EPI_BF16)                           # MLP pre-activation
+                sb["ug"] = sb["u"].clone()
+                ops.block_activation_(sb["ug"], 1)                                                        # GELU
+                sb["a2"] = ops.gemm_bf16(sb["ug"], A["wdn"], A["bdn"], EPI_BF16)
+                ops.gemm_bf16(sb["ug"], A["wdn"], A["bdn"], EPI_RESID_F32, out=X, resid=X, gate=mv(m0 + 5 * C), **gk)
+                st["blocks"].append(sb)
+                m0 += 6 * C
+            # conv_out, a FinalLayer (layers.py:240-246): the stream x itself runs on into the next stage
+            st["xf"] = X.clone()
+            st["hf"] = ops.layernorm_modulate(X, shift=mv(m0), scale=mv(m0 + C), **kw)
+            outs.append(ops.gemm_bf16(st["hf"], Pe["out"]["w"], Pe["out"]["b"], EPI_F32, n=Pe["out"]["n_out"]).view(B, T, -1))
+            m0 += 2 * C
+            S["stages"].append(st)
+        self.saved = S
+        return outs
+
+    # ---------------------------------------------------------------- backward
+    @torch.no_grad()
+    def backward(self, d_enc_out):
+        m, S = self.m, self.saved
+        if S is None:
+            raise RuntimeError("EncoderTrainStep.backward before forward")
+        self.saved = None
+        self.d_tokens = self.d_pos = None
+        B, T = S["B"], S["T"]
+        C, H, L, E = m.hidden_dim, m.num_heads, m.n_layers, m.encoder_layers
+        M = B * T
+        d_enc_out = list(d_enc_out)
+        if len(d_enc_out) != L or any(not torch.is_tensor(t) or tuple(t.shape) != (B, T, C) for t in d_enc_out):
+            raise ValueError("EncoderTrainStep.backward: d_enc_out is not %d tensors (%d, %d, %d)" % (L, B, T, C))
+        if any(not t.is_cuda for t in d_enc_out):
+            raise RuntimeError("EncoderTrainStep.backward: a gradient is on the CPU; the HIP path has no CPU fallback")
+        for _, p in encoder_parameters(m):
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        mod = S["mod"]
+        n_mod = mod.shape[1]
+        mv = lambda off: mod[:, off:off + C]
+        dmod = torch.empty_like(mod)
+        dv = lambda off: dmod[:, off:off + C]
+        kw = dict(mod_sample_stride=n_mod, rows_per_sample=T)
+        gk = dict(gate_sample_stride=n_mod, rows_per_sample=T)
+        dX = torch.zeros((M, C), dtype=torch.float32, device=mod.device)     # the gradient of the stream x: every later stage's is already in it
+        for i in reversed(range(L)):
+            enc, st = m.encoder[i], S["stages"][i]
+            f0 = i * (6 * E + 2) * C + 6 * E * C
+            # enc_out[i] = conv_out.ln(mod(LN(x)))                                                  (layers.py:240-246): ADDED to dX
+            dhf = _linear_bwd(enc.conv_out.ln, d_enc_out[i].detach().float().contiguous().view(M, C), st["hf"])
+            ops.layernorm_modulate_bwd(st["xf"], dhf, dX, scale=mv(f0 + C), dshift=dv(f0), dscale=dv(f0 + C), **kw)
+            for k in reversed(range(E)):
+                blk, sb, m0 = enc.atts[k], st["blocks"][k], i * (6 * E + 2) * C + 6 * k * C
+                # x = x2 + gate_mlp * mlp(mod(LN(x2)))                                              (layers.py:219)
+                da2, _ = ops.gate_residual_bwd(dX, mv(m0 + 5 * C), sb["a2"], dgate=dv(m0 + 5 * C), **gk)
+                dug = _linear_bwd(blk.mlp.out, da2, sb["ug"])
+                du = ops.gelu_bwd(sb["u"], dug)
+                dh2 = _linear_bwd(blk.mlp.fc[0][0], du, sb["h2"])
+                ops.layernorm_modulate_bwd(sb["x2"], dh2, dX, scale=mv(m0 + 4 * C), dshift=dv(m0 + 3 * C), dscale=dv(m0 + 4 * C), **kw)
+                # x2 = x1 + gate_msa * fc_o(attention(fc_q(mod(LN(x1))), fc_kv(x1)))                (layers.py:218, 183-200)
+                da1, _ = ops.gate_residual_bwd(dX, mv(m0 + 2 * C), sb["a1"], dgate=dv(m0 + 2 * C), **gk)
+                do = _linear_bwd(blk.fc_o, da1, sb["o"].view(M, C), epilogue=EPI_BF16)               # [M, C] == dO [B, H, T, 32] raw (Q1)
+                kv = sb["kv"]
+                dkv = torch.empty((M, 2 * C), dtype=torch.bfloat16, device=dX.device)                # [dk | dv], the dY of fc_kv
+                dq, _, _ = ops.attention_bwd_cross(sb["q"], kv[:, :C], kv[:, C:], sb["o"], do, B, H, T, T, HEAD_DIM, dkv_out=dkv)
+                dh = _linear_bwd(blk.fc_q, dq, sb["h"])
+                dy = _linear_bwd(blk.fc_kv, dkv, sb["y"])                                            # [M, C] fp32: into the raw x1
+                ops.layernorm_modulate_bwd(sb["x1"], dh, dX, scale=mv(m0 + C), dshift=dv(m0), dscale=dv(m0 + C), **kw)
+                ops.add_f32(dX, dy, out=dX)
+        # the conditioning row: mod = adaLN.1(SiLU(pos)) for every block and FinalLayer, one fp32 linear on transposed operands
+        ds = ops.sgemm(dmod, _t(S["w_ada"]))                                                         # d SiLU(pos)  [B, p_dim]
+        d_pos, s_c = ops.silu_bwd(S["pos"], ds, want_act=True)
+        dW = ops.sgemm(_t(dmod), _t(s_c))                                                            # [n_mod, p_dim]
+        db = ops.colsum(dmod)
+        r = 0
+        for lin in self._adaln():
+            n = lin.weight.shape[0]
+            lin.weight.grad.copy_(dW[r:r + n])
+            lin.bias.grad.copy_(db[r:r + n])
+            r += n
+        if m.ActNorm is not None:                                                                    # z = (x - shift) exp(-log_scale), layers.py:103-107
+            ci = m.conv_in
+            z = S["stages"][0]["blocks"][0]["x1"] if E else S["stages"][0]["xf"]
+            ops.actnorm_bwd(dX, z, _f32(ci.log_scale).view(-1), M * C // ci.shift.numel(), dx=dX, dshift=ci.shift.grad.view(-1),
+                            dlog_scale=ci.log_scale.grad.view(-1))
+        self.d_tokens, self.d_pos = dX.view(B, T, C), d_pos
+        return self.d_tokens, self.d_pos

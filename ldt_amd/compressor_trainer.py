@@ -9,8 +9,10 @@ frozen (compressor_train.DecoderTrainStep, losses.cd_loss; DESIGN.md section 4.1
 Adam without EMA over the decoder-side parameters, and the gradient with respect to the latents kept as `last_eps_grad`; and
 `update_topdown`, one step of the whole top-down half — posterior blocks, prior heads, the reparameterised draw and the KL term, then the
 decoder — with the bottom-up half frozen (compressor_train.TopDownTrainStep; section 4.16): loss = kl_weight * kl_loss + the Chamfer term,
-the gradient with respect to the encoder outputs kept as `last_enc_out_grad`.  The whole
-Compressor step is out of scope: `update` / `compute_loss` raise — the encoder and grouper backward are not built, and
+the gradient with respect to the encoder outputs kept as `last_enc_out_grad`; and `update_encoder`, that step with ActNorm and the encoder
+in the graph and only the front (input conv, grouper, position embedding) frozen (compressor_train.EncoderTrainStep; section 4.17), the
+gradients with respect to the grouped tokens and the position condition kept as `last_tokens_grad` / `last_pos_grad`.  The whole
+Compressor step is out of scope: `update` / `compute_loss` raise — the grouper backward is not built, and
 `compute_loss` adds `EMD_loss`, which goes through the auction-EMD CUDA extension of evaluation/emd.py that this package does not have
 (and does not imitate).
 
@@ -159,6 +161,83 @@ class CompressorTrainer:
         self.itr += 1
         return self.kl_weight * kl_loss + rec_loss, kl_loss, rec_loss
 
+    # ---- training the encoder and the top-down half with the grouped tokens frozen ---------------------------
+    encoder_optimizer = None                                         # AdamEMA over the encoder + top-down parameters, created by the first update_encoder
+    last_tokens_grad = None                                          # d loss / d tokens (before ActNorm) of the last update_encoder
+    last_pos_grad = None                                             # d loss / d (position condition) of the last update_encoder
+
+    def update_encoder(self, data, *, tokens=None, pos=None, post_noise=None):
+        """`update_topdown` with the encoder in the graph (compressor_train.EncoderTrainStep): the grouped tokens and
+        the position condition from `model.front(data['tr_points'])` under no_grad in evaluation mode (or `tokens` (B, T, hidden) before
+        ActNorm and `pos` (B, p_dim) as given) stay frozen; ActNorm and the encoder stages run with their tape, the top-down pass on their
+        outputs, `CD_loss` of type 'l1', the interleaved top-down backward and, from its d_enc_out, the encoder backward.  While
+        `model.conv_in.initialized` is 0 the reference's data-dependent ActNorm init runs first on these tokens (layers.py:74-79, 84-92:
+        shift = the batch mean, log_scale = log(unbiased batch std + eps); torch on the device, once).  clip_grad_norm_ and Adam without EMA
+        over the encoder + top-down parameters (`self.encoder_optimizer`, apart from the other two), `itr += 1`.  -> (loss, kl_loss,
+        rec_loss) as update_topdown.  `self.last_tokens_grad` (B, T, hidden) and `self.last_pos_grad` (B, p_dim) keep what the grouper's
+        and the position embedding's backward would start from."""
+        from .compressor_train import (EncoderTrainStep, TopDownTrainStep, encoder_parameters, refuse_untrainable_encoder,
+                                       refuse_untrainable_topdown, topdown_parameters)
+        from .losses import cd_loss
+        from .train import AdamEMA
+        if self.kl_weight is None:
+            raise ValueError("CompressorTrainer.update_encoder: cfg.opt.kl_weight is not set; the loss is kl_weight * kl_loss + rec_loss")
+        refuse_untrainable_encoder(self.model)
+        refuse_untrainable_topdown(self.model)
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("CompressorTrainer.update_encoder: device %s; the HIP path has no CPU fallback" % (self.device,))
+        m = self.model
+        points = (data["tr_points"] if isinstance(data, dict) else data).to(self.device).float().contiguous()
+        B, z, L = points.shape[0], m.z_dim, m.n_layers
+        if tokens is None or pos is None:
+            was_training = m.training
+            try:
+                with torch.no_grad():
+                    m.eval()                                         # the frozen front runs as in evaluation; the caller's mode comes back
+                    fr = m.front(points)
+            finally:
+                m.train(was_training)
+            tokens = fr["tokens"] if tokens is None else tokens
+            pos = fr["pos"] if pos is None else pos
+        tokens, pos = tokens.to(self.device).float().contiguous(), pos.to(self.device).float().contiguous()
+        T = tokens.shape[1]
+        if m.ActNorm is not None and not bool(m.conv_in.initialized):
+            with torch.no_grad():                                    # ActNorm.data_init (layers.py:74-79) on these tokens
+                ci = m.conv_in
+                x = tokens.view(-1, 1, tokens.shape[2]) if ci.feature_type == "set" else tokens
+                ci.shift.data.copy_(torch.mean(x, dim=0, keepdim=True))
+                ci.log_scale.data.copy_(torch.log(torch.std(x, dim=0, keepdim=True) + ci.eps))
+                ci.initialized += 1.
+            m.invalidate_packed()
+        # the order of Compressor.forward on the CPU generator: InitialSet's row subsets, then the posterior draws
+        keep_mask = m._presence(B, points.shape[1])
+        if keep_mask is None:                                        # (every row kept: said so, so that the step does not draw again)
+            keep_mask = torch.ones((B, m.max_outputs), dtype=torch.bool)
+        if post_noise is None:
+            if m.reference_rng:
+                post_noise = [torch.randn((B, z, T)).transpose(1, 2).to(self.device) for _ in range(L)]
+            else:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                post_noise = [ops.philox_normal((B, T, z), torch.device(self.device), seed, step=j) for j in range(L)]
+        if self.encoder_optimizer is None:
+            o = self.cfg.opt
+            self.encoder_optimizer = AdamEMA([p for _, p in encoder_parameters(m) + topdown_parameters(m)], lr=o.lr, betas=(o.beta1, o.beta2),
+                                             weight_decay=o.weight_decay, ema_decay=0.)
+        self.warm_up(self.encoder_optimizer, self.itr)
+        self.encoder_optimizer.zero_grad()
+        enc, top = EncoderTrainStep(m), TopDownTrainStep(m)
+        enc_out = enc.forward(tokens, pos)
+        out, _, kl_sample_sum = top.forward(enc_out, [t.to(self.device) for t in post_noise], num_points=points.shape[1], keep_mask=keep_mask)
+        n_kl = L * B * z * T                                         # numel(torch.cat(kls, dim=1))
+        kl_loss = kl_sample_sum.sum() / n_kl
+        rec_loss, d_set = cd_loss(out, points, "l1", want_grad=True)
+        d_enc_out = top.backward(d_set, self.kl_weight / n_kl)
+        self.last_tokens_grad, self.last_pos_grad = enc.backward(d_enc_out)
+        self.encoder_optimizer.step(max_norm=getattr(self.cfg.opt, "grad_norm_clip_value", None))
+        m.invalidate_packed()                                        # the update wrote the weights through raw pointers
+        self.itr += 1
+        return self.kl_weight * kl_loss + rec_loss, kl_loss, rec_loss
+
     @torch.no_grad()
     def eval_losses(self, target_set, label=None):
         """The two terms of `compute_loss` (:42-52) that stand on kernels of this package, for a held-out batch (B, N, 3):
@@ -286,6 +365,10 @@ class CompletionCompressorTrainer(CompressorTrainer):
 
     def update_topdown(self, data, *, enc_out=None, post_noise=None):
         raise NotImplementedError("CompletionCompressorTrainer.update_topdown: the top-down step is built and held for CompressorTrainer "
+                                  "alone; training is not on this path for the completion trainer")
+
+    def update_encoder(self, data, *, tokens=None, pos=None, post_noise=None):
+        raise NotImplementedError("CompletionCompressorTrainer.update_encoder: the encoder step is built and held for CompressorTrainer "
                                   "alone; training is not on this path for the completion trainer")
 
     def compute_loss(self, target_set):

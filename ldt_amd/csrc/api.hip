@@ -226,6 +226,12 @@ extern "C" int ldt_actnorm(float* x, const float* shift, const float* log_scale,
     LDT_REQUIRE(x && shift && log_scale, LDT_EARG, "actnorm: null pointer");
     return ldt_actnorm_launch(x, shift, log_scale, B, per_sample, ST(stream));
 }
+extern "C" int ldt_actnorm_bwd(const float* dz, const float* z, const float* log_scale, int64_t B, int64_t per_sample, float* dx, float* dshift,
+                               float* dlog_scale, void* stream) {
+    LDT_REQUIRE(dz && log_scale && dx && (z || !dlog_scale), LDT_EARG, "actnorm_bwd: null pointer (dlog_scale needs z)");
+    LDT_REQUIRE(B >= 1 && per_sample >= 1, LDT_EARG, "actnorm_bwd: B %ld, per_sample %ld", (long)B, (long)per_sample);
+    return ldt_actnorm_bwd_launch(dz, z, log_scale, B, per_sample, dx, dshift, dlog_scale, ST(stream));
+}
 extern "C" int ldt_reparam(const float* post, const float* noise, float* out, int64_t ldo, float* mu_out, float* logvar_out,
                            int64_t rows, int32_t z, float lo, float hi, void* stream) {
     LDT_REQUIRE(post && noise && out, LDT_EARG, "reparam: null pointer");

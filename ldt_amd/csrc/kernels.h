@@ -169,6 +169,8 @@ int ldt_mixture_seed_launch(const float* eps, const float* sig, const float* mu,
 int ldt_gather_rows_launch(const float* src, const int* idx, int B, int n, int S, int C, float* out, hipStream_t s);
 int ldt_maxpool_launch(const void* in, int in_bf16, long ld, long G, int n, int C, float* out, hipStream_t s);
 int ldt_actnorm_launch(float* x, const float* shift, const float* log_scale, long B, long per_sample, hipStream_t s);
+int ldt_actnorm_bwd_launch(const float* dz, const float* z, const float* log_scale, long B, long per_sample, float* dx, float* dshift,
+                           float* dlog_scale, hipStream_t s);   // actnorm_bwd.hip
 int ldt_reparam_launch(const float* post, const float* noise, float* out, long ldo, float* mu_out, float* lv_out,
                        long rows, int z, float lo, float hi, hipStream_t s);
 int ldt_chamfer_launch(const float* a, const float* b, int B, int na, int nb, float* dl, float* dr, hipStream_t s);

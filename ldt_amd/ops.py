@@ -533,6 +533,33 @@ def actnorm_(x, shift, log_scale, B):
     return x
 
 
+def actnorm_bwd(dz, z, log_scale, B, dx=None, dshift=None, dlog_scale=None, want_sums=True):
+    """Backward of actnorm_: dz, z (the forward's OUTPUT) fp32 with B samples of dz.numel() // B elements, log_scale fp32 [per_sample] ->
+    (dx, dshift, dlog_scale): dx = dz exp(-log_scale) (`dx` given: written there, dz itself allowed), dshift = -sum_b dx and
+    dlog_scale = -sum_b dz z into the buffers given or fresh ones (want_sums False: dx only, both None)."""
+    for t, nm in ((dz, "dz"), (z, "z"), (log_scale, "log_scale"), (dx, "dx"), (dshift, "dshift"), (dlog_scale, "dlog_scale")):
+        _need(t, torch.float32, nm)
+    if not dz.is_contiguous() or not z.is_contiguous() or dz.shape != z.shape:
+        raise ValueError("actnorm_bwd: dz %s and z %s must be contiguous and of one shape" % (tuple(dz.shape), tuple(z.shape)))
+    per = dz.numel() // max(int(B), 1)
+    if B < 1 or per < 1 or per * B != dz.numel() or log_scale.numel() != per or not log_scale.is_contiguous():
+        raise ValueError("actnorm_bwd: %d elements in B = %d samples with log_scale %s" % (dz.numel(), B, tuple(log_scale.shape)))
+    if dx is None:
+        dx = torch.empty_like(dz)
+    elif not dx.is_contiguous() or dx.numel() != dz.numel():
+        raise ValueError("actnorm_bwd: dx %s is not contiguous with dz's %d elements" % (tuple(dx.shape), dz.numel()))
+    if want_sums:
+        dshift = torch.empty(per, dtype=torch.float32, device=dz.device) if dshift is None else dshift
+        dlog_scale = torch.empty(per, dtype=torch.float32, device=dz.device) if dlog_scale is None else dlog_scale
+        for t in (dshift, dlog_scale):
+            if not t.is_contiguous() or t.numel() != per:
+                raise ValueError("actnorm_bwd: a sum buffer is %s, not contiguous with %d elements" % (tuple(t.shape), per))
+    else:
+        dshift = dlog_scale = None
+    check(lib().ldt_actnorm_bwd(_p(dz), _p(z), _p(log_scale), B, per, _p(dx), _p(dshift), _p(dlog_scale), stream_ptr()), "ldt_actnorm_bwd")
+    return dx, dshift, dlog_scale
+
+
 def reparam(post, noise, out, lo, hi, want_stats=False):
     """post fp32 [rows, 2z], noise [rows, z] -> out[rows, z] (strided slice ok) = mu + exp(clamp(logvar)/2)*noise."""
     rows, z2 = post.shape
