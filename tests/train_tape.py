@@ -3,8 +3,8 @@ MI355X, test_train_tape_host.py on a pure-torch emulation of the entry points, p
 
 `ldt_amd.train` reaches every kernel through its module attribute `ops`.  `Tape(ops)` forwards every attribute and records, for each call made
 through it, the function name, its operands (cloned, with their shapes, strides and dtypes) and its outputs (cloned); for operands written in
-place (`out=`, `dx`, `dshift=`, `dscale=`, `dgate=`: the `.grad` views and the column blocks of `dmod` among them) the view AND the whole
-storage under it, before and after the call.
+place (`out=`, `dx`, `dshift=`, `dscale=`, `dgate=`, and the Compressor entry points' `dq_out=`, `dkv_out=`, `dlog_scale=`, `stats_out=`:
+the `.grad` views and the column blocks of `dmod` among them) the view AND the whole storage under it, before and after the call.
 
 Two audits read the tape of a backward:
   * `audit_numeric`: every call's output against float64 computed from that call's OWN recorded operands, with the references and bounds of
@@ -22,7 +22,8 @@ import torch
 
 import kernel_checks as kc
 
-INPLACE = ("out", "dx", "dshift", "dscale", "dgate")
+INPLACE = ("out", "dx", "dshift", "dscale", "dgate",
+           "dq_out", "dkv_out", "dlog_scale", "stats_out")      # the Compressor steps' entry points (tests/compressor_tape.py)
 PLAIN = ("pad64", "stream_ptr")                      # no tensors: forwarded unrecorded
 
 
