@@ -1,44 +1,33 @@
-"""Training the Compressor on the HIP path from the grouped tokens up, in three steps that share their pieces.
+"""Training the Compressor on the HIP path from the grouped tokens up, in three steps around train_block's one block: here is what is
+particular to each — the operand checks and refusals, the conditioning row, the level / stage loops and the order in which the stream
+gradients are added — plus `_centred_keys` and the composed `w_zkv` linear's backward.
 
-`EncoderTrainStep`: what lies between the frozen front (`Compressor.front`: input conv, grouper, position
-embedding) and the top-down half (Network.py:200-205): ActNorm, then per stage the AdaLN self-attention blocks (K / V from the RAW token
-stream, quirk Q2) and the FinalLayer `conv_out`, all modulated by rows of ONE fp32 linear on SiLU(pos).  Its backward starts from
-TopDownTrainStep's `d_enc_out`, runs the stages in reverse with the FinalLayer's gradient ADDED to the running stream gradient (the stream
-runs on into the next stage), and ends in `ldt_actnorm_bwd`; it returns (d_tokens, d_pos), where the grouper's and the position embedding's
-backward would start.  The block body is train.ScoreTrainStep's (`ldt_layernorm_modulate_bwd`, `ldt_gate_residual_bwd`, `ldt_gelu_bwd`,
-`ldt_attention_bwd_cross` at T on T, `ldt_silu_bwd`, `ldt_sgemm` for the conditioning linear).
+`DecoderTrainStep`, the decoder alone with the encoder frozen (Network.py:251-268 `Compressor.sample`, :80-83
+`DecoderBlock.forward` with c = None; model/Compressor/layers.py:26-42, the learned prior rows): per level the affine-form block of the N
+set points on the T latent tokens, K | V handed in by the composed linear on eps_j (`ldt_attention_bwd_long`; the fp32 linears on the
+latent tokens: `ldt_sgemm`; the prior rows' gradient: `ldt_rows_gather_sum`).  `backward` fills the `.grad` of decoder_parameters(model)
+and returns the gradient with respect to the latents (`d_eps`).
 
-`TopDownTrainStep`: everything from the encoder's outputs upward (Network.py:208-233, `top_down`): per level the
-posterior block `decoder[l].att` (the T latent tokens attend to the N points of the running set stream; level 0 to themselves), the
-`decoder[l].prior` head, the reparameterised draw with its KL term, and the decoder block.  Its backward is ONE interleaved pass: the
-posterior of level j + 1 reads the set stream o_{j+1}, so its K/V gradient has to be in `dX` before decoder block j runs backward.
-Kernels on top of the decoder step's: `ldt_attention_bwd_wide` (T queries on N keys; level 0's T on T is `ldt_attention_bwd_cross`),
-`ldt_reparam_kl_bwd`, `ldt_silu_bwd`.  It returns the gradient with respect to the encoder outputs (`d_enc_out`), where the encoder backward
-starts; on its own it leaves the bottom-up half (input conv, grouper, position embedding, ActNorm, encoder) frozen.
+`TopDownTrainStep` (section 4.16): everything from the encoder's outputs upward (Network.py:208-233, `top_down`): per level the
+posterior block `decoder[l].att` (the affine form again: the T latent tokens attend to the N points of the running set stream, level 0 to
+themselves; K / V from the RAW stream, quirk Q2), the `decoder[l].prior` head, the reparameterised draw with its KL term, and the decoder
+block.  Its backward is ONE interleaved pass: the posterior of level j + 1 reads the set stream o_{j+1}, so its K/V gradient has to be in
+`dX` before decoder block j runs backward.  Kernels on top of the decoder step's: `ldt_attention_bwd_wide` (T queries on N keys; level 0's
+T on T is `ldt_attention_bwd_cross`), `ldt_reparam_kl_bwd`, `ldt_silu_bwd`.  It returns the gradient with respect to the encoder outputs
+(`d_enc_out`), where the encoder backward starts.
 
-`DecoderTrainStep` (section 4.15), the decoder alone: the host-driven top-down forward that keeps what the backward needs, and the backward
-from the gradient of the decoded set down to the decoder-side parameters and the latents.
-
-Reference: model/Compressor/Network.py:251-268 (`Compressor.sample`, what is differentiated), :80-83 (`DecoderBlock.forward` with c = None),
-model/layers.py:183-200, 224-226 (the no-condition ResidualBlock: affine LayerNorm, attention of the set on the latent tokens, MLP),
-model/Compressor/layers.py:26-42 (the learned prior rows).  Scope: the decoder with the encoder frozen, as train.ScoreTrainStep trains the
-Score with ConditionNet frozen: `backward` fills the `.grad` of `init_set.prior`, `output.*` and, per level, `decoder[l].ln.*` and
-`decoder[l].att1.{fc_q, fc_kv, fc_o, norm1, norm2, mlp.fc.0.0, mlp.out}.*`, and returns the gradient with respect to the latents
-(`d_eps`), which is where the posterior / encoder backward will start.  It touches no other parameter: `decoder[l].att`, `decoder[l].prior`,
-the encoder, the grouper, the position embedding and ActNorm are the posterior side.
-
-Kernels: the forward's are the inference kernels, unfused; every GEMM of the backward is `ldt_gemm_bf16` on operands prepared by
-`ldt_transpose_cast_bf16` (the fp32 linears on the T latent tokens: `ldt_sgemm`); the affine LayerNorm backward is
-`ldt_layernorm_modulate_bwd` with the affine read as a modulation shared by all rows (scale = gamma - 1, shift = beta, one "sample" of M
-rows: dscale = dgamma, dshift = dbeta); the attention backward is `ldt_attention_bwd_long` (N queries on T keys); the prior rows' gradient is
-`ldt_rows_gather_sum`.
+`EncoderTrainStep` (section 4.17): what lies between the frozen front (`Compressor.front`) and the top-down half (Network.py:200-205):
+ActNorm, then per stage the AdaLN-form blocks (K / V from the RAW token stream) and the FinalLayer `conv_out`, all modulated by rows of ONE
+fp32 linear on SiLU(pos).  Its backward starts from `d_enc_out`, runs the stages in reverse with the FinalLayer's gradient ADDED to the
+running stream gradient (the stream runs on into the next stage), and ends in `ldt_actnorm_bwd`; it returns (d_tokens, d_pos), where the
+grouper's and the position embedding's backward would start.
 """
 import torch
 
 from . import _lib, ops
-from ._lib import ACT_SILU, EPI_BF16, EPI_F32, EPI_RESID_F32
+from ._lib import ACT_SILU, EPI_BF16
 from .layers import conv_w
-from .train import _grad2d, _t
+from .train_block import ModRows, TrainBlock, _grad2d, _t, refuse_host
 
 HEAD_DIM = 32                                                          # ldt_attention_bwd_long: the Compressor's 128 / 4
 
@@ -74,74 +63,18 @@ def _f32(t):
     return t.detach().float().contiguous()
 
 
-def _block_fwd(A, X, kv, B, H, Nq, Nk):
-    """The no-condition ResidualBlock (layers.py:224-226) on the fp32 rows X [B Nq, C], updated in place, with K | V = kv bf16
-    [B Nk, 2 C] given; unfused, every operand of the backward kept -> the block's tape."""
-    C, M = A["C"], B * Nq
-    sb = {"x1": X.clone()}
-    sb["h"] = ops.layernorm_modulate(X, w=A["n1"][0], b=A["n1"][1])
-    sb["q"] = ops.gemm_bf16(sb["h"], A["wq"], A["bq"], EPI_BF16)
-    sb["kv"] = kv
-    sb["o"] = ops.attention_fwd(sb["q"], kv[:, :C], kv[:, C:], B, H, Nq, Nk, HEAD_DIM)                    # [B, H, Nq, 32] == (M, C) raw view (Q1)
-    ops.gemm_bf16(sb["o"].view(M, C), A["wo"], A["bo"], EPI_RESID_F32, out=X, resid=X)
-    sb["x2"] = X.clone()
-    sb["h2"] = ops.layernorm_modulate(X, w=A["n2"][0], b=A["n2"][1])
-    sb["u"] = ops.gemm_bf16(sb["h2"], A["wup"], A["bup"], EPI_BF16)                                       # MLP pre-activation
-    sb["ug"] = sb["u"].clone()
-    ops.block_activation_(sb["ug"], 1)                                                                    # GELU
-    ops.gemm_bf16(sb["ug"], A["wdn"], A["bdn"], EPI_RESID_F32, out=X, resid=X)
-    return sb
-
-
-def _linear_bwd(layer, dy, x_in, want_dx=True, epilogue=EPI_F32):
-    """dW, db into the layer's .grad; -> dX = dy @ W (dy bf16 [M, n] or fp32; x_in the forward's operand)."""
-    ops.wgrad(dy, x_in, out=_grad2d(layer.weight))
-    ops.colsum(dy, out=layer.bias.grad)
-    if not want_dx:
-        return None
-    dyb = dy if dy.dtype == torch.bfloat16 and dy.shape[1] % 64 == 0 else ops.cast_pad_bf16(dy, ops.pad64(dy.shape[1]))
-    return ops.dgrad(dyb, ops.transpose_cast_bf16(conv_w(layer).detach()), epilogue)      # W[N, K] -> bf16 [K, pad64(N)], rebuilt every step
-
-
-def _affine_ln_bwd(norm, x, dy, dx):
-    """h = LN(x) gamma + beta: dx += the LayerNorm gradient, dgamma and dbeta into the norm's .grad."""
-    w, b = norm.affine
-    M, C = x.shape
-    ops.layernorm_modulate_bwd(x, dy, dx, scale=ops.add_f32(_f32(w), torch.full_like(w, -1.0)).view(1, C), mod_sample_stride=0,
-                               rows_per_sample=M, dshift=b.grad.view(1, C), dscale=w.grad.view(1, C))
-
-
-def _block_bwd(blk, sb, dX, B, H, Nq, Nk, attention_bwd):
-    """Backward of _block_fwd: dX fp32 [B Nq, C], the gradient of the block's result, becomes the gradient of its input; the block's
-    .grads are filled; -> dkv bf16 [B Nk, 2 C] = dK | dV, the gradient of its K | V.  attention_bwd: the ops entry for (Nq, Nk)."""
-    C, M = dX.shape[1], B * Nq
-    # x = x2 + mlp.out(GELU(mlp.fc(LN2(x2))))                                              (layers.py:226)
-    dug = _linear_bwd(blk.mlp.out, dX, sb["ug"])
-    du = ops.gelu_bwd(sb["u"], dug)
-    dh2 = _linear_bwd(blk.mlp.fc[0][0], du, sb["h2"])
-    _affine_ln_bwd(blk.norm2, sb["x2"], dh2, dX)
-    # x2 = x1 + fc_o(attention(fc_q(LN1(x1)), K | V))                                       (layers.py:225, 183-200)
-    do = _linear_bwd(blk.fc_o, dX, sb["o"].view(M, C), epilogue=EPI_BF16)                  # [M, C] == dO [B, H, Nq, 32] raw (Q1)
-    kv = sb["kv"]
-    dkv = torch.empty((B * Nk, 2 * C), dtype=torch.bfloat16, device=dX.device)            # [dk | dv]
-    dq, _, _ = attention_bwd(sb["q"], kv[:, :C], kv[:, C:], sb["o"], do, B, H, Nq, Nk, dkv_out=dkv)
-    dh = _linear_bwd(blk.fc_q, dq, sb["h"])
-    _affine_ln_bwd(blk.norm1, sb["x1"], dh, dX)
-    return dkv
-
-
 def _decoder_level_fwd(P, X, e2, j, S, B, H, N, T, L, z):
     """Decoder block j of the top-down pass (reversed(self.decoder), Network.py:263) on the set stream X, in place -> its tape."""
     Pd = P["dec"][L - 1 - j]
     kv = ops.sgemm(e2[:, z * j: z * (j + 1)], Pd["w_zkv"], Pd["b_zkv"], out_bf16=True)                    # [B T, 2 C] = K | V, composed linear
     S["w_zkv_t"][j] = _t(Pd["w_zkv"])                                                                     # [z, 2 C]: d_eps_j = dkv W_zkv
-    return _block_fwd(Pd["att1"], X, kv, B, H, N, T)
+    return TrainBlock(ops).block_fwd(Pd["att1"], X, (B, H, N, T, HEAD_DIM), kv=kv)
 
 
 def _decoder_level_bwd(d, sb, dX, e_j, w_zkv_t, d_eps_j, B, H, N, T):
     """Backward of decoder block `d` = decoder[L - 1 - j]: dX becomes the gradient of the block's input, d_eps_j is written."""
     blk = d.att1
-    dkv = _block_bwd(blk, sb, dX, B, H, N, T, ops.attention_bwd_long)
+    dkv = TrainBlock(ops).block_bwd(blk, sb, dX, (B, H, N, T, HEAD_DIM), ops.attention_bwd_long)
     # kv = eps_j W_zkv^T + b_zkv with W_zkv = W_kv W_ln, b_zkv = W_kv b_ln + b_kv: the composed linear hands its gradient to both factors
     dkv32 = ops.widen_bf16(dkv)
     w_kv, w_ln, b_ln = _f32(conv_w(blk.fc_kv)), _f32(conv_w(d.ln)), _f32(d.ln.bias)
@@ -226,9 +159,7 @@ class DecoderTrainStep:
     @torch.no_grad()
     def forward(self, eps, num_points=None, keep_mask=None):
         m = self.m
-        if not (torch.is_tensor(eps) and eps.is_cuda):
-            raise RuntimeError("DecoderTrainStep.forward: eps is on %s; the HIP path has no CPU fallback"
-                               % (eps.device if torch.is_tensor(eps) else type(eps).__name__,))
+        refuse_host("DecoderTrainStep.forward", "eps", eps)
         self.saved = None
         B, T, Z = eps.shape
         L, z, C, H = m.n_layers, m.z_dim, m.hidden_dim, m.num_heads
@@ -292,11 +223,6 @@ def _centred_keys(A, y, kv, B, nk):
     return kvc
 
 
-def _attention_bwd_self(q, k, v, o, do, B, H, Nq, Nk, dkv_out=None):
-    """Level 0's att(x, x), T on T: ldt_attention_bwd_cross at the Compressor's head width."""
-    return ops.attention_bwd_cross(q, k, v, o, do, B, H, Nq, Nk, HEAD_DIM, dkv_out=dkv_out)
-
-
 def refuse_untrainable_topdown(model, num_points=None, tokens=None):
     """What the top-down step does not cover: the posterior's attention limits first (T queries on N keys: ldt_attention_bwd_wide; level
     0's T on T: ldt_attention_bwd_cross), then everything refuse_undecodable refuses.  Works on CPU parameters."""
@@ -331,10 +257,7 @@ class TopDownTrainStep:
         m = self.m
         L, z, C, H = m.n_layers, m.z_dim, m.hidden_dim, m.num_heads
         enc_out, post_noise = list(enc_out), list(post_noise)
-        for t in enc_out + post_noise:
-            if not (torch.is_tensor(t) and t.is_cuda):
-                raise RuntimeError("TopDownTrainStep.forward: an operand is on %s; the HIP path has no CPU fallback"
-                                   % (t.device if torch.is_tensor(t) else type(t).__name__,))
+        refuse_host("TopDownTrainStep.forward", "an operand", *enc_out, *post_noise)
         self.saved = None
         if len(enc_out) != L or len(post_noise) != L:
             raise ValueError("TopDownTrainStep.forward: %d encoder outputs and %d posterior draws for %d levels" % (len(enc_out), len(post_noise), L))
@@ -351,6 +274,7 @@ class TopDownTrainStep:
         P = m.packed()
         dev = enc_out[0].device
         all_eps = torch.empty((B * T, L * z), dtype=torch.float32, device=dev)
+        tb = TrainBlock(ops)
         S = {"B": B, "N": N, "T": T, "eps": all_eps, "src": src.to(dev), "w_zkv_t": [None] * L, "levels": [], "post": []}
         X = m._initial_set(P, B, N, keep_mask).clone()                  # fp32 [B N, C]: the set stream o, updated in place below
         kl_sums = []
@@ -360,7 +284,7 @@ class TopDownTrainStep:
             xj = enc_out[-j - 1].detach().float().contiguous().view(B * T, C).clone()                     # the token stream of this level, updated in place
             # compute_posterior(x, o) (Network.py:61-78): att(x, o) with K / V from the RAW set stream (quirk Q2); level 0: att(x, x)
             y, nk = (ops.cast_pad_bf16(xj, ops.pad64(C)), T) if j == 0 else (ops.cast_pad_bf16(X, ops.pad64(C)), N)
-            pb = _block_fwd(A, xj, ops.gemm_bf16(y, A["wkv"], A["bkv"], EPI_BF16), B, H, T, nk)
+            pb = tb.block_fwd(A, xj, (B, H, T, nk, HEAD_DIM), kv=ops.gemm_bf16(y, A["wkv"], A["bkv"], EPI_BF16))
             pb["y"], pb["x3"] = y, xj
             pb["kv"] = _centred_keys(A, y, pb["kv"], B, nk)                                               # the backward's K | V (the forward is done with its own)
             pb["post"] = ops.sgemm(xj, Pd["w_prior"], Pd["b_prior"], act_in=ACT_SILU)                     # SiLU -> Conv1d C -> 2 z
@@ -390,6 +314,7 @@ class TopDownTrainStep:
             if p.grad is None:
                 p.grad = torch.zeros_like(p)
         dX = _output_bwd(m, dset, S["xf"], M)                           # the complete gradient of o_L
+        tb = TrainBlock(ops)
         d_eps = torch.empty((B * T, L * z), dtype=torch.float32, device=dX.device)
         d_enc = [None] * L
         for j in reversed(range(L)):                                    # dX: the complete gradient of o_{j+1}
@@ -405,8 +330,8 @@ class TopDownTrainStep:
             ops.wgrad(dpost, act, out=_grad2d(lin.weight))
             ops.colsum(dpost, out=lin.bias.grad)
             nk = T if j == 0 else N
-            dkv = _block_bwd(d.att, pb, dXp, B, H, T, nk, _attention_bwd_self if j == 0 else ops.attention_bwd_wide)
-            dy = _linear_bwd(d.att.fc_kv, dkv, pb["y"])                  # [B nk, C] fp32: into the K / V source
+            dkv = tb.block_bwd(d.att, pb, dXp, (B, H, T, nk, HEAD_DIM), ops.attention_bwd_cross if j == 0 else ops.attention_bwd_wide)
+            dy = tb.linear_bwd(d.att.fc_kv, dkv, pb["y"])                   # [B nk, C] fp32: into the K / V source
             if j == 0:
                 ops.add_f32(dXp, dy, out=dXp)                           # att(x, x): the block attends to its own input
             else:
@@ -485,10 +410,7 @@ class EncoderTrainStep:
     @torch.no_grad()
     def forward(self, tokens, pos):
         m = self.m
-        for t in (tokens, pos):
-            if not (torch.is_tensor(t) and t.is_cuda):
-                raise RuntimeError("EncoderTrainStep.forward: an operand is on %s; the HIP path has no CPU fallback"
-                                   % (t.device if torch.is_tensor(t) else type(t).__name__,))
+        refuse_host("EncoderTrainStep.forward", "an operand", tokens, pos)
         self.saved = None
         C, H = m.hidden_dim, m.num_heads
         if tokens.dim() != 3 or tokens.shape[2] != C:
@@ -508,40 +430,21 @@ class EncoderTrainStep:
         S["pos"] = pos.detach().float().contiguous()
         lins = self._adaln()
         S["w_ada"] = torch.cat([_f32(l.weight) for l in lins], 0)
-        mod = S["mod"] = ops.sgemm(S["pos"], S["w_ada"], torch.cat([_f32(l.bias) for l in lins], 0), act_in=ACT_SILU)   # [B, n_mod]
-        n_mod = mod.shape[1]
-        mv = lambda off: mod[:, off:off + C]
-        kw = dict(mod_sample_stride=n_mod, rows_per_sample=T)
-        gk = dict(gate_sample_stride=n_mod, rows_per_sample=T)
+        S["mod"] = ops.sgemm(S["pos"], S["w_ada"], torch.cat([_f32(l.bias) for l in lins], 0), act_in=ACT_SILU)   # [B, n_mod]
+        mod, tb = ModRows(S["mod"], C, T), TrainBlock(ops)
+        # the backward's K | V: the raw tokens share a large common component (mean key / rms key 0.8 - 0.9 at the tiny fixture), the case
+        # _centred_keys was written for (section 4.17: dQ rel-MSE 1e-4 - 2e-4 from D = rowsum(dO o O) of the bf16 O, 1e-7 - 4e-7 centred)
+        centred = lambda A: lambda y, kv: _centred_keys(A, y, kv, B, T)
         outs, m0 = [], 0
         for Pe in P["enc"]:
             st = {"blocks": []}
-            for A in Pe["atts"]:
-                sb = {"x1": X.clone()}                                  # (the first block's x1 is ActNorm's output z)
-                sb["h"] = ops.layernorm_modulate(X, shift=mv(m0), scale=mv(m0 + C), **kw)
-                sb["y"] = ops.cast_pad_bf16(X, ops.pad64(C))            # K / V from the RAW x (Network.py:44, quirk Q2)
-                sb["q"] = ops.gemm_bf16(sb["h"], A["wq"], A["bq"], EPI_BF16)
-                sb["kv"] = ops.gemm_bf16(sb["y"], A["wkv"], A["bkv"], EPI_BF16)
-                sb["o"] = ops.attention_fwd(sb["q"], sb["kv"][:, :C], sb["kv"][:, C:], B, H, T, T, HEAD_DIM)   # [B, H, T, 32] == (M, C) raw view (Q1)
-                # the backward's K | V: the raw tokens share a large common component (mean key / rms key 0.8 - 0.9 at the tiny fixture), the
-                # case _centred_keys was written for (section 4.17: dQ rel-MSE 1e-4 - 2e-4 from D = rowsum(dO o O) of the bf16 O, 1e-7 - 4e-7 centred)
-                sb["kv"] = _centred_keys(A, sb["y"], sb["kv"], B, T)
-                o2 = sb["o"].view(M, C)
-                sb["a1"] = ops.gemm_bf16(o2, A["wo"], A["bo"], EPI_BF16)                                  # the branch output, for dgate
-                ops.gemm_bf16(o2, A["wo"], A["bo"], EPI_RESID_F32, out=X, resid=X, gate=mv(m0 + 2 * C), **gk)
-                sb["x2"] = X.clone()
-                sb["h2"] = ops.layernorm_modulate(X, shift=mv(m0 + 3 * C), scale=mv(m0 + 4 * C), **kw)
-                sb["u"] = ops.gemm_bf16(sb["h2"], A["wup"], A["bup"], EPI_BF16)                           # MLP pre-activation
-                sb["ug"] = sb["u"].clone()
-                ops.block_activation_(sb["ug"], 1)                                                        # GELU
-                sb["a2"] = ops.gemm_bf16(sb["ug"], A["wdn"], A["bdn"], EPI_BF16)
-                ops.gemm_bf16(sb["ug"], A["wdn"], A["bdn"], EPI_RESID_F32, out=X, resid=X, gate=mv(m0 + 5 * C), **gk)
-                st["blocks"].append(sb)
+            for A in Pe["atts"]:                                        # K / V from the RAW x (Network.py:44, quirk Q2); the first x1 is ActNorm's output z
+                st["blocks"].append(tb.block_fwd(A, X, (B, H, T, T, HEAD_DIM), mod, m0, y=X, kv_bwd=centred(A)))
                 m0 += 6 * C
             # conv_out, a FinalLayer (layers.py:240-246): the stream x itself runs on into the next stage
             st["xf"] = X.clone()
-            st["hf"] = ops.layernorm_modulate(X, shift=mv(m0), scale=mv(m0 + C), **kw)
-            outs.append(ops.gemm_bf16(st["hf"], Pe["out"]["w"], Pe["out"]["b"], EPI_F32, n=Pe["out"]["n_out"]).view(B, T, -1))
+            st["hf"], out = tb.final_fwd(X, Pe["out"]["w"], Pe["out"]["b"], Pe["out"]["n_out"], mod, m0)
+            outs.append(out.view(B, T, -1))
             m0 += 2 * C
             S["stages"].append(st)
         self.saved = S
@@ -566,49 +469,18 @@ class EncoderTrainStep:
         for _, p in encoder_parameters(m):
             if p.grad is None:
                 p.grad = torch.zeros_like(p)
-        mod = S["mod"]
-        n_mod = mod.shape[1]
-        mv = lambda off: mod[:, off:off + C]
-        dmod = torch.empty_like(mod)
-        dv = lambda off: dmod[:, off:off + C]
-        kw = dict(mod_sample_stride=n_mod, rows_per_sample=T)
-        gk = dict(gate_sample_stride=n_mod, rows_per_sample=T)
-        dX = torch.zeros((M, C), dtype=torch.float32, device=mod.device)     # the gradient of the stream x: every later stage's is already in it
+        dmod = torch.empty_like(S["mod"])
+        mod, tb = ModRows(S["mod"], C, T, dmod), TrainBlock(ops)
+        dX = torch.zeros((M, C), dtype=torch.float32, device=dmod.device)    # the gradient of the stream x: every later stage's is already in it
         for i in reversed(range(L)):
-            enc, st = m.encoder[i], S["stages"][i]
-            f0 = i * (6 * E + 2) * C + 6 * E * C
+            enc, st, m0 = m.encoder[i], S["stages"][i], i * (6 * E + 2) * C
             # enc_out[i] = conv_out.ln(mod(LN(x)))                                                  (layers.py:240-246): ADDED to dX
-            dhf = _linear_bwd(enc.conv_out.ln, d_enc_out[i].detach().float().contiguous().view(M, C), st["hf"])
-            ops.layernorm_modulate_bwd(st["xf"], dhf, dX, scale=mv(f0 + C), dshift=dv(f0), dscale=dv(f0 + C), **kw)
+            tb.final_bwd(enc.conv_out.ln, d_enc_out[i].detach().float().contiguous().view(M, C), st["xf"], st["hf"], dX, mod, m0 + 6 * E * C)
             for k in reversed(range(E)):
-                blk, sb, m0 = enc.atts[k], st["blocks"][k], i * (6 * E + 2) * C + 6 * k * C
-                # x = x2 + gate_mlp * mlp(mod(LN(x2)))                                              (layers.py:219)
-                da2, _ = ops.gate_residual_bwd(dX, mv(m0 + 5 * C), sb["a2"], dgate=dv(m0 + 5 * C), **gk)
-                dug = _linear_bwd(blk.mlp.out, da2, sb["ug"])
-                du = ops.gelu_bwd(sb["u"], dug)
-                dh2 = _linear_bwd(blk.mlp.fc[0][0], du, sb["h2"])
-                ops.layernorm_modulate_bwd(sb["x2"], dh2, dX, scale=mv(m0 + 4 * C), dshift=dv(m0 + 3 * C), dscale=dv(m0 + 4 * C), **kw)
-                # x2 = x1 + gate_msa * fc_o(attention(fc_q(mod(LN(x1))), fc_kv(x1)))                (layers.py:218, 183-200)
-                da1, _ = ops.gate_residual_bwd(dX, mv(m0 + 2 * C), sb["a1"], dgate=dv(m0 + 2 * C), **gk)
-                do = _linear_bwd(blk.fc_o, da1, sb["o"].view(M, C), epilogue=EPI_BF16)               # [M, C] == dO [B, H, T, 32] raw (Q1)
-                kv = sb["kv"]
-                dkv = torch.empty((M, 2 * C), dtype=torch.bfloat16, device=dX.device)                # [dk | dv], the dY of fc_kv
-                dq, _, _ = ops.attention_bwd_cross(sb["q"], kv[:, :C], kv[:, C:], sb["o"], do, B, H, T, T, HEAD_DIM, dkv_out=dkv)
-                dh = _linear_bwd(blk.fc_q, dq, sb["h"])
-                dy = _linear_bwd(blk.fc_kv, dkv, sb["y"])                                            # [M, C] fp32: into the raw x1
-                ops.layernorm_modulate_bwd(sb["x1"], dh, dX, scale=mv(m0 + C), dshift=dv(m0), dscale=dv(m0 + C), **kw)
-                ops.add_f32(dX, dy, out=dX)
-        # the conditioning row: mod = adaLN.1(SiLU(pos)) for every block and FinalLayer, one fp32 linear on transposed operands
-        ds = ops.sgemm(dmod, _t(S["w_ada"]))                                                         # d SiLU(pos)  [B, p_dim]
-        d_pos, s_c = ops.silu_bwd(S["pos"], ds, want_act=True)
-        dW = ops.sgemm(_t(dmod), _t(s_c))                                                            # [n_mod, p_dim]
-        db = ops.colsum(dmod)
-        r = 0
-        for lin in self._adaln():
-            n = lin.weight.shape[0]
-            lin.weight.grad.copy_(dW[r:r + n])
-            lin.bias.grad.copy_(db[r:r + n])
-            r += n
+                sb = st["blocks"][k]
+                dy = tb.block_bwd(enc.atts[k], sb, dX, (B, H, T, T, HEAD_DIM), ops.attention_bwd_cross, mod, m0 + 6 * k * C, y=sb["y"])
+                ops.add_f32(dX, dy, out=dX)                                                          # [M, C] fp32: into the raw x1
+        d_pos = tb.adaln_bwd(dmod, S["w_ada"], S["pos"], self._adaln())                                 # the conditioning row
         if m.ActNorm is not None:                                                                    # z = (x - shift) exp(-log_scale), layers.py:103-107
             ci = m.conv_in
             z = S["stages"][0]["blocks"][0]["x1"] if E else S["stages"][0]["xf"]

@@ -59,6 +59,69 @@ class CompressorTrainer:
             for param_group in optimizer.param_groups:
                 param_group["lr"] = lr
 
+    # ---- what the three update_* steps share ------------------------------------------------------------------
+    def _points(self, who, data):
+        """The device refusal, then data['tr_points'] (or the tensor itself) as fp32 on the device."""
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("CompressorTrainer.%s: device %s; the HIP path has no CPU fallback" % (who, self.device))
+        return (data["tr_points"] if isinstance(data, dict) else data).to(self.device).float().contiguous()
+
+    def _frozen(self, part):
+        """part() under no_grad with the model in evaluation mode: a frozen part runs as in evaluation; the caller's mode comes back."""
+        was_training = self.model.training
+        try:
+            with torch.no_grad():
+                self.model.eval()
+                return part()
+        finally:
+            self.model.train(was_training)
+
+    def _draws(self, B, N, T, post_noise):
+        """-> (keep_mask, post_noise) in the order of Compressor.forward on the CPU generator: InitialSet's row subsets, then the posterior
+        draws (unless given)."""
+        m = self.model
+        keep_mask = m._presence(B, N)
+        if keep_mask is None:                                        # (every row kept: said so, so that the step does not draw again)
+            keep_mask = torch.ones((B, m.max_outputs), dtype=torch.bool)
+        if post_noise is None:
+            if m.reference_rng:
+                post_noise = [torch.randn((B, m.z_dim, T)).transpose(1, 2).to(self.device) for _ in range(m.n_layers)]
+            else:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                post_noise = [ops.philox_normal((B, T, m.z_dim), torch.device(self.device), seed, step=j) for j in range(m.n_layers)]
+        return keep_mask, post_noise
+
+    def _begin(self, attr, parameters):
+        """The optimizer kept as `self.<attr>` (Adam without EMA over parameters(), created at its first use), warmed up and zeroed."""
+        if getattr(self, attr) is None:
+            from .train import AdamEMA
+            o = self.cfg.opt
+            setattr(self, attr, AdamEMA([p for _, p in parameters()], lr=o.lr, betas=(o.beta1, o.beta2), weight_decay=o.weight_decay, ema_decay=0.))
+        optimizer = getattr(self, attr)
+        self.warm_up(optimizer, self.itr)
+        optimizer.zero_grad()
+        return optimizer
+
+    def _finish(self, optimizer):
+        optimizer.step(max_norm=getattr(self.cfg.opt, "grad_norm_clip_value", None))
+        self.model.invalidate_packed()                               # the update wrote the weights through raw pointers
+        self.itr += 1
+
+    def _topdown_pass(self, points, enc_out, post_noise, keep_mask, T):
+        """The top-down forward with its tape, loss = kl_weight * kl_loss + `CD_loss(set, points)` of type 'l1', and the interleaved backward
+        with kl_scale = kl_weight / numel(cat(kls)) -> ((loss, kl_loss, rec_loss), d_enc_out)."""
+        from .compressor_train import TopDownTrainStep
+        from .losses import cd_loss
+        m = self.model
+        step = TopDownTrainStep(m)
+        out, _, kl_sample_sum = step.forward([t.to(self.device) for t in enc_out], [t.to(self.device) for t in post_noise],
+                                             num_points=points.shape[1], keep_mask=keep_mask)
+        n_kl = m.n_layers * points.shape[0] * m.z_dim * T            # numel(torch.cat(kls, dim=1))
+        kl_loss = kl_sample_sum.sum() / n_kl
+        rec_loss, d_set = cd_loss(out, points, "l1", want_grad=True)
+        d_enc_out = step.backward(d_set, self.kl_weight / n_kl)
+        return (self.kl_weight * kl_loss + rec_loss, kl_loss, rec_loss), d_enc_out
+
     def update_decoder(self, data, *, eps=None, post_noise=None):
         """One training step of the decoder with the encoder frozen: eps = model.encode(data['tr_points']) under no_grad (or `eps` as
         given; `post_noise` replaces the posterior draws), the learning-rate warm-up, the top-down decode with its tape
@@ -70,32 +133,16 @@ class CompressorTrainer:
         backward would start."""
         from .compressor_train import DecoderTrainStep, decoder_parameters, refuse_undecodable
         from .losses import cd_loss
-        from .train import AdamEMA
         refuse_undecodable(self.model)
-        if torch.device(self.device).type != "cuda":
-            raise RuntimeError("CompressorTrainer.update_decoder: device %s; the HIP path has no CPU fallback" % (self.device,))
-        points = (data["tr_points"] if isinstance(data, dict) else data).to(self.device).float().contiguous()
+        points = self._points("update_decoder", data)
         if eps is None:
-            was_training = self.model.training
-            try:
-                with torch.no_grad():
-                    self.model.eval()                                # the frozen encoder runs as in evaluation; the caller's mode comes back
-                    eps = self.model.encode(points, post_noise=post_noise)
-            finally:
-                self.model.train(was_training)
-        if self.optimizer is None:
-            o = self.cfg.opt
-            self.optimizer = AdamEMA([p for _, p in decoder_parameters(self.model)], lr=o.lr, betas=(o.beta1, o.beta2),
-                                     weight_decay=o.weight_decay, ema_decay=0.)
-        self.warm_up(self.optimizer, self.itr)
-        self.optimizer.zero_grad()
+            eps = self._frozen(lambda: self.model.encode(points, post_noise=post_noise))
+        optimizer = self._begin("optimizer", lambda: decoder_parameters(self.model))
         step = DecoderTrainStep(self.model)
         out = step.forward(eps.to(self.device), num_points=points.shape[1])
         loss, d_set = cd_loss(out, points, "l1", want_grad=True)
         self.last_eps_grad = step.backward(d_set)
-        self.optimizer.step(max_norm=getattr(self.cfg.opt, "grad_norm_clip_value", None))
-        self.model.invalidate_packed()                               # the update wrote the weights through raw pointers
-        self.itr += 1
+        self._finish(optimizer)
         return loss, loss
 
     # ---- training the top-down half with the bottom-up half frozen -------------------------------------------
@@ -112,54 +159,22 @@ class CompressorTrainer:
         device tensors as the reference's `update` returns them: loss = kl_weight * kl_loss + rec_loss with kl_loss formed as
         eval_losses forms it.  The reference's rec_loss also holds EMD_loss, which is absent here (compute_loss says why): rec_loss IS the
         Chamfer term.  `self.last_enc_out_grad` keeps d loss / d enc_out, where the encoder backward would start."""
-        from .compressor_train import TopDownTrainStep, refuse_untrainable_topdown, topdown_parameters
-        from .losses import cd_loss
-        from .train import AdamEMA
+        from .compressor_train import refuse_untrainable_topdown, topdown_parameters
         if self.kl_weight is None:
             raise ValueError("CompressorTrainer.update_topdown: cfg.opt.kl_weight is not set; the loss is kl_weight * kl_loss + rec_loss")
         refuse_untrainable_topdown(self.model)
-        if torch.device(self.device).type != "cuda":
-            raise RuntimeError("CompressorTrainer.update_topdown: device %s; the HIP path has no CPU fallback" % (self.device,))
         m = self.model
-        points = (data["tr_points"] if isinstance(data, dict) else data).to(self.device).float().contiguous()
-        B, T, z, L = points.shape[0], m.z_scales, m.z_dim, m.n_layers
+        points = self._points("update_topdown", data)
         if enc_out is None:
-            was_training = m.training
-            try:
-                with torch.no_grad():
-                    m.eval()                                         # the frozen bottom-up half runs as in evaluation; the caller's mode comes back
-                    enc_out = [o.transpose(1, 2) for o in m.bottom_up(points)["outputs"]]
-            finally:
-                m.train(was_training)
+            T = m.z_scales
+            enc_out = self._frozen(lambda: [o.transpose(1, 2) for o in m.bottom_up(points)["outputs"]])
         else:
             T = enc_out[0].shape[1]
-        # the order of Compressor.forward on the CPU generator: InitialSet's row subsets, then the posterior draws
-        keep_mask = m._presence(B, points.shape[1])
-        if keep_mask is None:                                        # (every row kept: said so, so that the step does not draw again)
-            keep_mask = torch.ones((B, m.max_outputs), dtype=torch.bool)
-        if post_noise is None:
-            if m.reference_rng:
-                post_noise = [torch.randn((B, z, T)).transpose(1, 2).to(self.device) for _ in range(L)]
-            else:
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-                post_noise = [ops.philox_normal((B, T, z), torch.device(self.device), seed, step=j) for j in range(L)]
-        if self.topdown_optimizer is None:
-            o = self.cfg.opt
-            self.topdown_optimizer = AdamEMA([p for _, p in topdown_parameters(m)], lr=o.lr, betas=(o.beta1, o.beta2),
-                                             weight_decay=o.weight_decay, ema_decay=0.)
-        self.warm_up(self.topdown_optimizer, self.itr)
-        self.topdown_optimizer.zero_grad()
-        step = TopDownTrainStep(m)
-        out, _, kl_sample_sum = step.forward([t.to(self.device) for t in enc_out], [t.to(self.device) for t in post_noise],
-                                             num_points=points.shape[1], keep_mask=keep_mask)
-        n_kl = L * B * z * T                                         # numel(torch.cat(kls, dim=1))
-        kl_loss = kl_sample_sum.sum() / n_kl
-        rec_loss, d_set = cd_loss(out, points, "l1", want_grad=True)
-        self.last_enc_out_grad = step.backward(d_set, self.kl_weight / n_kl)
-        self.topdown_optimizer.step(max_norm=getattr(self.cfg.opt, "grad_norm_clip_value", None))
-        m.invalidate_packed()                                        # the update wrote the weights through raw pointers
-        self.itr += 1
-        return self.kl_weight * kl_loss + rec_loss, kl_loss, rec_loss
+        keep_mask, post_noise = self._draws(points.shape[0], points.shape[1], T, post_noise)
+        optimizer = self._begin("topdown_optimizer", lambda: topdown_parameters(m))
+        losses, self.last_enc_out_grad = self._topdown_pass(points, enc_out, post_noise, keep_mask, T)
+        self._finish(optimizer)
+        return losses
 
     # ---- training the encoder and the top-down half with the grouped tokens frozen ---------------------------
     encoder_optimizer = None                                         # AdamEMA over the encoder + top-down parameters, created by the first update_encoder
@@ -176,31 +191,19 @@ class CompressorTrainer:
         over the encoder + top-down parameters (`self.encoder_optimizer`, apart from the other two), `itr += 1`.  -> (loss, kl_loss,
         rec_loss) as update_topdown.  `self.last_tokens_grad` (B, T, hidden) and `self.last_pos_grad` (B, p_dim) keep what the grouper's
         and the position embedding's backward would start from."""
-        from .compressor_train import (EncoderTrainStep, TopDownTrainStep, encoder_parameters, refuse_untrainable_encoder,
-                                       refuse_untrainable_topdown, topdown_parameters)
-        from .losses import cd_loss
-        from .train import AdamEMA
+        from .compressor_train import (EncoderTrainStep, encoder_parameters, refuse_untrainable_encoder, refuse_untrainable_topdown,
+                                       topdown_parameters)
         if self.kl_weight is None:
             raise ValueError("CompressorTrainer.update_encoder: cfg.opt.kl_weight is not set; the loss is kl_weight * kl_loss + rec_loss")
         refuse_untrainable_encoder(self.model)
         refuse_untrainable_topdown(self.model)
-        if torch.device(self.device).type != "cuda":
-            raise RuntimeError("CompressorTrainer.update_encoder: device %s; the HIP path has no CPU fallback" % (self.device,))
         m = self.model
-        points = (data["tr_points"] if isinstance(data, dict) else data).to(self.device).float().contiguous()
-        B, z, L = points.shape[0], m.z_dim, m.n_layers
+        points = self._points("update_encoder", data)
         if tokens is None or pos is None:
-            was_training = m.training
-            try:
-                with torch.no_grad():
-                    m.eval()                                         # the frozen front runs as in evaluation; the caller's mode comes back
-                    fr = m.front(points)
-            finally:
-                m.train(was_training)
+            fr = self._frozen(lambda: m.front(points))
             tokens = fr["tokens"] if tokens is None else tokens
             pos = fr["pos"] if pos is None else pos
         tokens, pos = tokens.to(self.device).float().contiguous(), pos.to(self.device).float().contiguous()
-        T = tokens.shape[1]
         if m.ActNorm is not None and not bool(m.conv_in.initialized):
             with torch.no_grad():                                    # ActNorm.data_init (layers.py:74-79) on these tokens
                 ci = m.conv_in
@@ -209,34 +212,14 @@ class CompressorTrainer:
                 ci.log_scale.data.copy_(torch.log(torch.std(x, dim=0, keepdim=True) + ci.eps))
                 ci.initialized += 1.
             m.invalidate_packed()
-        # the order of Compressor.forward on the CPU generator: InitialSet's row subsets, then the posterior draws
-        keep_mask = m._presence(B, points.shape[1])
-        if keep_mask is None:                                        # (every row kept: said so, so that the step does not draw again)
-            keep_mask = torch.ones((B, m.max_outputs), dtype=torch.bool)
-        if post_noise is None:
-            if m.reference_rng:
-                post_noise = [torch.randn((B, z, T)).transpose(1, 2).to(self.device) for _ in range(L)]
-            else:
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-                post_noise = [ops.philox_normal((B, T, z), torch.device(self.device), seed, step=j) for j in range(L)]
-        if self.encoder_optimizer is None:
-            o = self.cfg.opt
-            self.encoder_optimizer = AdamEMA([p for _, p in encoder_parameters(m) + topdown_parameters(m)], lr=o.lr, betas=(o.beta1, o.beta2),
-                                             weight_decay=o.weight_decay, ema_decay=0.)
-        self.warm_up(self.encoder_optimizer, self.itr)
-        self.encoder_optimizer.zero_grad()
-        enc, top = EncoderTrainStep(m), TopDownTrainStep(m)
+        keep_mask, post_noise = self._draws(points.shape[0], points.shape[1], tokens.shape[1], post_noise)
+        optimizer = self._begin("encoder_optimizer", lambda: encoder_parameters(m) + topdown_parameters(m))
+        enc = EncoderTrainStep(m)
         enc_out = enc.forward(tokens, pos)
-        out, _, kl_sample_sum = top.forward(enc_out, [t.to(self.device) for t in post_noise], num_points=points.shape[1], keep_mask=keep_mask)
-        n_kl = L * B * z * T                                         # numel(torch.cat(kls, dim=1))
-        kl_loss = kl_sample_sum.sum() / n_kl
-        rec_loss, d_set = cd_loss(out, points, "l1", want_grad=True)
-        d_enc_out = top.backward(d_set, self.kl_weight / n_kl)
+        losses, d_enc_out = self._topdown_pass(points, enc_out, post_noise, keep_mask, tokens.shape[1])
         self.last_tokens_grad, self.last_pos_grad = enc.backward(d_enc_out)
-        self.encoder_optimizer.step(max_norm=getattr(self.cfg.opt, "grad_norm_clip_value", None))
-        m.invalidate_packed()                                        # the update wrote the weights through raw pointers
-        self.itr += 1
-        return self.kl_weight * kl_loss + rec_loss, kl_loss, rec_loss
+        self._finish(optimizer)
+        return losses
 
     @torch.no_grad()
     def eval_losses(self, target_set, label=None):

@@ -8,16 +8,16 @@ cross-attend to the condition tokens (completion_trainer/Latent_SDE_Trainer.py:9
 gradient with respect to that pair back.  ConditionNet itself is not differentiated.
 
 `AdamEMA` keeps fp32 master parameters, gradients, both Adam moments and the EMA in five flat device buffers (one fused
-`ldt_adam_ema_step` launch per step; bf16 operand panels are derived from the masters, never trained).  `ScoreTrainStep` runs the same
-kernels as inference, unfused, keeps per block what the backward needs, and then walks the blocks back: every GEMM of the backward is
-`ldt_gemm_bf16` on operands prepared by `ldt_transpose_cast_bf16`; everything else is csrc/score_bwd.hip and
-csrc/attention_bwd.hip (self-attention: ldt_attention_bwd / _narrow; cross-attention: ldt_attention_bwd_cross).
+`ldt_adam_ema_step` launch per step; bf16 operand panels are derived from the masters, never trained).  `ScoreTrainStep` is what is
+the Score's own around train_block's block (the AdaLN form; self-attention on the fused q | k | v panel: ldt_attention_bwd / _narrow;
+cross-attention to the condition tokens: ldt_attention_bwd_cross): the operand checks, the conditioning rows c and mod with their
+fp32 backward, the block loop and the sum of the condition's gradient over the cross blocks.
 """
 import torch
 
 from . import ops
-from ._lib import ACT_SILU, EPI_BF16, EPI_F32, EPI_RESID_F32
-from .layers import conv_w
+from ._lib import ACT_SILU, EPI_F32
+from .train_block import ModRows, TrainBlock, _t, refuse_host
 from .trainer import EMAWeights
 
 
@@ -185,17 +185,6 @@ def refuse_untrainable(model, condition=None, world_size=1, *, allow_condition=F
                                   % (model.hidden_size // model.num_heads))
 
 
-def _t(x):
-    """fp32 transpose as a dense matrix (data movement only: ldt_sgemm takes row strides, not column strides).  Copied into a fresh
-    tensor: `.t().contiguous()` hands a one-row matrix back as it is ([1, n] -> [n, 1] with strides (1, n) counts as contiguous), and
-    ops.sgemm refuses its last-dim stride — a batch of one sample could not take a step."""
-    return x.new_empty((x.shape[1], x.shape[0])).copy_(x.t())
-
-
-def _grad2d(p):
-    return p.grad.view(p.shape[0], -1)
-
-
 class ScoreTrainStep:
     """One forward + backward of `Score` for the denoising loss.  `forward` returns params (B, T, z) and keeps the saved activations;
     `backward(dparams)` fills every parameter's `.grad` view (the optimizer's flat gradient must be zeroed and attached first).
@@ -214,15 +203,23 @@ class ScoreTrainStep:
         self.saved = None
         self.dcondition = None
 
+    def _panels(self, P, l, cross):
+        """Block l's operands under blocks.pack_block's names: the packed q | k | v panel, or fc_q and fc_kv apart for a cross block."""
+        A = {"wo": P["w_o"][l], "bo": P["b_o"][l], "wup": P["w_up"][l], "bup": P["b_up"][l], "wdn": P["w_dn"][l], "bdn": P["b_dn"][l]}
+        if cross:
+            A["wq"], A["bq"], A["wkv"], A["bkv"] = self.m._cross_panels(l)
+        else:
+            A["wqkv"], A["bqkv"] = P["w_qkv"][l], P["b_qkv"][l]
+        return A
+
     # ---------------------------------------------------------------- forward
     @torch.no_grad()
     def forward(self, x, t, label=None, condition=None):
         m = self.m
-        if not x.is_cuda:
-            raise RuntimeError("ScoreTrainStep.forward: x is on %s; the HIP path has no CPU fallback" % x.device)
+        refuse_host("ScoreTrainStep.forward", "x", x)
         B, T, z = x.shape
-        D, H, nb, n_mod = m.hidden_size, m.num_heads, m.num_blocks, m.n_mod
-        M = B * T
+        D, H, nb = m.hidden_size, m.num_heads, m.num_blocks
+        M, Sn = B * T, 0
         pts_cond = img_cond = None
         if condition is not None:                                      # every refusal before anything is launched or kept
             self.saved = None
@@ -265,43 +262,19 @@ class ScoreTrainStep:
             S["S"] = Sn
             cond = S["cond"] = ops.cast_pad_bf16(pts_cond.to(x.device, torch.float32).transpose(1, 2).contiguous().view(B * Sn, D), D)
         w_ada, b_ada = m.stacked_adaln()
-        mod = S["mod"] = ops.sgemm(c, w_ada, b_ada, act_in=ACT_SILU)                               # [B, n_mod]
-        mv = lambda off: mod[:, off:off + D]
-        kw = dict(mod_sample_stride=n_mod, rows_per_sample=T)
-        gk = dict(gate_sample_stride=n_mod, rows_per_sample=T)
+        S["mod"] = ops.sgemm(c, w_ada, b_ada, act_in=ACT_SILU)                                    # [B, n_mod]
+        mod, tb = ModRows(S["mod"], D, T), TrainBlock(ops)
         # token path
         S["x_in"] = x.contiguous().float().view(M, z)
         xin = ops.cast_pad_bf16(S["x_in"], ops.pad64(z))
         X = ops.gemm_bf16(xin, P["w_in"], P["b_in"], EPI_F32)
         S["blocks"] = []
         for l in range(nb):
-            m0 = l * 6 * D
-            sb = {"x1": X.clone()}
-            sb["h"] = ops.layernorm_modulate(X, shift=mv(m0), scale=mv(m0 + D), **kw)
-            if cond is not None and l % 2 == 0:                                                   # score.py:149; layers.py:184-189 with y
-                wq, bq, wkv, bkv = m._cross_panels(l)
-                sb["q"] = ops.gemm_bf16(sb["h"], wq, bq, EPI_BF16)
-                sb["kv"] = ops.gemm_bf16(cond, wkv, bkv, EPI_BF16)                                # [B S, 2 D] = K | V
-                sb["o"] = ops.attention_fwd(sb["q"], sb["kv"][:, :D], sb["kv"][:, D:], B, H, T, Sn, D // H)
-            else:
-                sb["qkv"] = ops.gemm_bf16(sb["h"], P["w_qkv"][l], P["b_qkv"][l], EPI_BF16)
-                q, k, v = sb["qkv"][:, :D], sb["qkv"][:, D:2 * D], sb["qkv"][:, 2 * D:]
-                sb["o"] = ops.attention_fwd(q, k, v, B, H, T, T, D // H)                          # [B, H, T, Dh] == (M, D) raw view (Q1)
-            o2 = sb["o"].view(M, D)
-            sb["a1"] = ops.gemm_bf16(o2, P["w_o"][l], P["b_o"][l], EPI_BF16)                      # the branch output, for dgate
-            ops.gemm_bf16(o2, P["w_o"][l], P["b_o"][l], EPI_RESID_F32, out=X, resid=X, gate=mv(m0 + 2 * D), **gk)
-            sb["x2"] = X.clone()
-            sb["h2"] = ops.layernorm_modulate(X, shift=mv(m0 + 3 * D), scale=mv(m0 + 4 * D), **kw)
-            sb["u"] = ops.gemm_bf16(sb["h2"], P["w_up"][l], P["b_up"][l], EPI_BF16)               # MLP pre-activation
-            sb["ug"] = sb["u"].clone()
-            ops.block_activation_(sb["ug"], 1)                                                    # GELU
-            sb["a2"] = ops.gemm_bf16(sb["ug"], P["w_dn"][l], P["b_dn"][l], EPI_BF16)
-            ops.gemm_bf16(sb["ug"], P["w_dn"][l], P["b_dn"][l], EPI_RESID_F32, out=X, resid=X, gate=mv(m0 + 5 * D), **gk)
-            S["blocks"].append(sb)
-        f0 = nb * 6 * D
+            cross = cond is not None and l % 2 == 0                                               # score.py:149; layers.py:184-189 with y
+            S["blocks"].append(tb.block_fwd(self._panels(P, l, cross), X, (B, H, T, Sn if cross else T, D // H), mod, l * 6 * D,
+                                         y=cond if cross else None))
         S["xf"] = X
-        S["hf"] = ops.layernorm_modulate(X, shift=mv(f0), scale=mv(f0 + D), **kw)
-        out = ops.gemm_bf16(S["hf"], P["w_out"], P["b_out"], EPI_F32, n=z)
+        S["hf"], out = tb.final_fwd(X, P["w_out"], P["b_out"], z, mod, nb * 6 * D)
         self.saved = S
         return out.view(B, T, z)
 
@@ -315,73 +288,22 @@ class ScoreTrainStep:
         self.dcondition = None
         B, T, Sn = S["B"], S["T"], S.get("S", 0)
         d_cond = None                                                   # fp32 [B S, D]: the sum over the cross blocks, in the loop's order
-        D, nb, n_mod, z = m.hidden_size, m.num_blocks, m.n_mod, m.z_dim
+        D, H, nb, z = m.hidden_size, m.num_heads, m.num_blocks, m.z_dim
         M = B * T
-        mod = S["mod"]
-        mv = lambda off: mod[:, off:off + D]
-        dmod = torch.empty_like(mod)
-        dv = lambda off: dmod[:, off:off + D]
-        wt = lambda mod_: ops.transpose_cast_bf16(conv_w(mod_).detach())                       # W[N, K] -> bf16 [K, pad64(N)], rebuilt every step
-
-        def linear_bwd(layer, dy, x_in, want_dx=True, epilogue=EPI_F32, rows=None):
-            """dW, db into the layer's .grad views; -> dX = dy @ W (dy bf16 [M, N] or fp32; x_in the forward's operand)."""
-            ops.wgrad(dy, x_in, out=_grad2d(layer.weight) if rows is None else _grad2d(layer.weight)[rows[0]:rows[1]])
-            ops.colsum(dy, out=layer.bias.grad)
-            if not want_dx:
-                return None
-            dyb = dy if dy.dtype == torch.bfloat16 and dy.shape[1] % 64 == 0 else ops.cast_pad_bf16(dy.float() if dy.dtype != torch.float32 else dy,
-                                                                                                   ops.pad64(dy.shape[1]))
-            return ops.dgrad(dyb, wt(layer), epilogue)
-
-        # FinalLayer (model/layers.py:240-246)
+        dmod = torch.empty_like(S["mod"])
+        mod, tb = ModRows(S["mod"], D, T, dmod), TrainBlock(ops)
         d2 = dparams.contiguous().view(M, z)
-        dhf = linear_bwd(m.ln_out.ln, d2, S["hf"])
         dX = torch.zeros((M, D), dtype=torch.float32, device=d2.device)
-        f0 = nb * 6 * D
-        ops.layernorm_modulate_bwd(S["xf"], dhf, dX, scale=mv(f0 + D), mod_sample_stride=n_mod, rows_per_sample=T, dshift=dv(f0), dscale=dv(f0 + D))
+        tb.final_bwd(m.ln_out.ln, d2, S["xf"], S["hf"], dX, mod, nb * 6 * D)
         for l in reversed(range(nb)):
-            blk, sb, m0 = m.Transformer[l], S["blocks"][l], l * 6 * D
-            # x = x2 + gate_mlp * mlp(mod(LN(x2)))                                                  (layers.py:219)
-            da2, _ = ops.gate_residual_bwd(dX, mv(m0 + 5 * D), sb["a2"], gate_sample_stride=n_mod, rows_per_sample=T, dgate=dv(m0 + 5 * D))
-            dug = linear_bwd(blk.mlp.out, da2, sb["ug"])
-            du = ops.gelu_bwd(sb["u"], dug)
-            dh2 = linear_bwd(blk.mlp.fc[0][0], du, sb["h2"])
-            ops.layernorm_modulate_bwd(sb["x2"], dh2, dX, scale=mv(m0 + 4 * D), mod_sample_stride=n_mod, rows_per_sample=T,
-                                       dshift=dv(m0 + 3 * D), dscale=dv(m0 + 4 * D))
-            # x2 = x1 + gate_msa * fc_o(attention(q, k, v))                                         (layers.py:218, 183-200)
-            da1, _ = ops.gate_residual_bwd(dX, mv(m0 + 2 * D), sb["a1"], gate_sample_stride=n_mod, rows_per_sample=T, dgate=dv(m0 + 2 * D))
-            do = linear_bwd(blk.fc_o, da1, sb["o"].view(M, D), epilogue=EPI_BF16)                 # [M, D] == dO [B, H, T, Dh] raw (Q1)
+            blk, sb = m.Transformer[l], S["blocks"][l]
             if "kv" in sb:                                                                        # cross-attention to the condition tokens
-                kv = sb["kv"]
-                dkv = torch.empty((B * Sn, 2 * D), dtype=torch.bfloat16, device=do.device)        # [dk | dv], the dY of fc_kv
-                dq, _, _ = ops.attention_bwd_cross(sb["q"], kv[:, :D], kv[:, D:], sb["o"], do, B, m.num_heads, T, Sn, D // m.num_heads, dkv_out=dkv)
-                dh = linear_bwd(blk.fc_q, dq, sb["h"])
-                d_c = linear_bwd(blk.fc_kv, dkv, S["cond"])                                       # [B S, D] fp32
-                d_cond = d_c if d_cond is None else ops.add_f32(d_cond, d_c)
+                d_cond = tb.block_bwd(blk, sb, dX, (B, H, T, Sn, D // H), ops.attention_bwd_cross, mod, l * 6 * D, y=S["cond"], dy_sum=d_cond)
             else:
-                qkv = sb["qkv"]
-                dqkv = torch.empty((M, 3 * D), dtype=torch.bfloat16, device=do.device)            # [dq | dk | dv], the dY of fc_q | fc_kv
-                dq, _, _ = ops.attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], sb["o"], do, B, m.num_heads, T, head_dim=D // m.num_heads, out=dqkv)
-                linear_bwd(blk.fc_q, dq, sb["h"], want_dx=False)
-                linear_bwd(blk.fc_kv, dqkv[:, D:], sb["h"], want_dx=False)
-                wqkv_t = ops.transpose_cast_bf16(torch.cat([conv_w(blk.fc_q), conv_w(blk.fc_kv)], 0).detach())
-                dh = ops.dgrad(dqkv, wqkv_t, EPI_F32)
-            ops.layernorm_modulate_bwd(sb["x1"], dh, dX, scale=mv(m0 + D), mod_sample_stride=n_mod, rows_per_sample=T,
-                                       dshift=dv(m0), dscale=dv(m0 + D))
-        linear_bwd(m.ln_in, dX, S["x_in"], want_dx=False)                                        # score.py:110
+                tb.block_bwd(blk, sb, dX, (B, H, T, T, D // H), None, mod, l * 6 * D)
+        tb.linear_bwd(m.ln_in, dX, S["x_in"], want_dx=False)                                        # score.py:110
         # conditioning rows: fp32 linears on transposed operands
-        w_ada, _ = m.stacked_adaln()
-        ds = ops.sgemm(dmod, _t(w_ada))                                                          # d SiLU(c)  [B, t_dim]
-        dc, s_c = ops.silu_bwd(S["c"], ds, want_act=True)
-        dW = ops.sgemm(_t(dmod), _t(s_c))                                                        # [n_mod, t_dim]
-        db = ops.colsum(dmod)
-        lins = [blk.adaLN[1] for blk in m.Transformer] + [m.ln_out.adaLN[1]]
-        r = 0
-        for lin in lins:
-            n = lin.weight.shape[0]
-            lin.weight.grad.copy_(dW[r:r + n])
-            lin.bias.grad.copy_(db[r:r + n])
-            r += n
+        dc = tb.adaln_bwd(dmod, m.stacked_adaln()[0], S["c"], [blk.adaLN[1] for blk in m.Transformer] + [m.ln_out.adaLN[1]])
 
         def mlp2_bwd(seq, a_pre, e_in):
             """seq = Linear, SiLU, Linear on e_in with the saved pre-activation a_pre: grads into .grad, -> d e_in."""

@@ -367,10 +367,10 @@ def drive(tiny_cfg, kind, emu=None, step_fault=None, kernel_fault=None, corrupt=
     tape = tt.Tape(emu if kernel_fault is None else Plant(emu, kernel_fault, ctx, emu))
     r = dict(case=case, model=m, tape=tape, kind=kind)
     with pytest.MonkeyPatch.context() as mp:
-        mp.setattr(ct, "ops", tape)
+        tt.install_ops(mp, tape)
         S = saved_encoder(ct, case) if kind == "encoder" else saved_topdown(ct, case)
         ctx["S"] = S
-        mp.setattr(ct, "ops", tape if step_fault is None else Plant(tape, step_fault, ctx, emu))
+        tt.install_ops(mp, tape if step_fault is None else Plant(tape, step_fault, ctx, emu))
         fed = cpt.copy_saved(S)
         if corrupt is not None:
             corrupt(fed)

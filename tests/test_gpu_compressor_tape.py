@@ -58,7 +58,7 @@ def run_decoder(tiny_cfg, name, edit=None, key=None):
     dset = case["d_set"].cuda() if edit is None else edit(case["d_set"].cuda())
     keep = case["keep"]
     with pytest.MonkeyPatch.context() as mp:
-        mp.setattr(ct, "ops", tape)
+        tt.install_ops(mp, tape)
         step = ct.DecoderTrainStep(model)
         pts = step.forward(case["eps"].cuda(), num_points=case["N"], keep_mask=keep)
         S = cpt.copy_saved(step.saved)
@@ -79,7 +79,7 @@ def run_topdown(tiny_cfg, name, edit=None, key=None, kl_scale=None, then_encoder
     dset = case["d_set"].cuda() if edit is None else edit(case["d_set"].cuda())
     ks = case["kl_scale"] if kl_scale is None else kl_scale
     with pytest.MonkeyPatch.context() as mp:
-        mp.setattr(ct, "ops", tape)
+        tt.install_ops(mp, tape)
         enc, enc_S = None, None
         if then_encoder:
             enc = ct.EncoderTrainStep(model)
@@ -116,7 +116,7 @@ def run_encoder(tiny_cfg, name, edit=None, key=None):
     if edit is not None:
         d_enc = [edit(t) for t in d_enc]
     with pytest.MonkeyPatch.context() as mp:
-        mp.setattr(ct, "ops", tape)
+        tt.install_ops(mp, tape)
         step = ct.EncoderTrainStep(model)
         outs = step.forward(case["tokens"].cuda(), case["pos"].cuda())
         S = cpt.copy_saved(step.saved)

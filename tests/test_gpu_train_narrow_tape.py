@@ -50,7 +50,7 @@ def run_case(tiny_cfg, name, edit=None, key=None):
     tt.flat_grads(model)
     tape = tt.Tape(train.ops)
     with pytest.MonkeyPatch.context() as mp:
-        mp.setattr(train, "ops", tape)
+        tt.install_ops(mp, tape)
         step = train.ScoreTrainStep(model)
         params = step.forward(x.cuda(), t.cuda(), None if label is None else label.cuda())
         S = tt.copy_saved(step.saved)

@@ -245,7 +245,7 @@ def backward_on(tiny_cfg, monkeypatch, ops, corrupt=None, step_fault=None):
     model, S = d["model"], d["S"]
     tt.flat_grads(model)
     tape = tt.Tape(ops)
-    monkeypatch.setattr(train, "ops", tape if step_fault is None else Faulty(tape, step_fault, model.hidden_size, S["B"] * S["T"]))
+    tt.install_ops(monkeypatch, tape if step_fault is None else Faulty(tape, step_fault, model.hidden_size, S["B"] * S["T"]))
     step = train.ScoreTrainStep(model)
     step.saved = tt.copy_saved(S)
     if corrupt is not None:

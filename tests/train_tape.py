@@ -1,7 +1,8 @@
 """A call tape for `ScoreTrainStep` and the audit of a whole backward read from it (a plain helper module: test_gpu_train_tape.py runs it on the
 MI355X, test_train_tape_host.py on a pure-torch emulation of the entry points, planted faults included).
 
-`ldt_amd.train` reaches every kernel through its module attribute `ops`.  `Tape(ops)` forwards every attribute and records, for each call made
+`ldt_amd.train` reaches every kernel through its module attribute `ops`, which it also hands to the block of `ldt_amd.train_block`
+(`install_ops` replaces the attribute on all the step modules at once).  `Tape(ops)` forwards every attribute and records, for each call made
 through it, the function name, its operands (cloned, with their shapes, strides and dtypes) and its outputs (cloned); for operands written in
 place (`out=`, `dx`, `dshift=`, `dscale=`, `dgate=`, and the Compressor entry points' `dq_out=`, `dkv_out=`, `dlog_scale=`, `stats_out=`:
 the `.grad` views and the column blocks of `dmod` among them) the view AND the whole storage under it, before and after the call.
@@ -119,6 +120,15 @@ class Tape:
 
 
 # ------------------------------------------------------------------------------------------------------------- driving a step
+def install_ops(mp, proxy):
+    """`proxy` as the module attribute `ops` of every module a training step reaches its kernels through, in the MonkeyPatch context `mp`:
+    ldt_amd.train, ldt_amd.compressor_train and ldt_amd.train_block, which holds the block they share.  A step hands its own module's `ops`
+    to the block (`TrainBlock(ops)`); train_block's attribute is what a TrainBlock built without one falls back to, so no path is left out."""
+    import importlib
+    for name in ("train", "compressor_train", "train_block"):
+        mp.setattr(importlib.import_module("ldt_amd." + name), "ops", proxy)
+
+
 def flat_grads(model):
     """Zeroed `.grad` views of one flat fp32 buffer for every parameter, the way AdamEMA._ensure_flat lays them out (16-byte aligned views in
     parameter order).  On the GPU this IS AdamEMA (zero_grad()); on the CPU, where AdamEMA refuses, the same layout by hand.  -> the flat buffer."""
