@@ -7,18 +7,16 @@ orchestrator (`ldt_score_forward`) because it runs 24 blocks x 1000 steps.
 
 K/V source y (quirk Q2): None -> the normalised/modulated x itself; otherwise the RAW tensor given.
 Head merge (quirk Q1): the attention kernel writes [B][H][N][Dh]; that buffer *is* the (B,N,C) raw reinterpret.
+A block is four stages (`_modulation_rows`, `_q_kv`, `_attention`, `_mlp`); each of the last three is one fused kernel or the chain of
+kernels it stands for, chosen by shape alone (the `_can_*` predicates; the routes per block form: DESIGN.md §4.4).
 """
+import collections
+
 import torch
 
 from . import ops
-from ._lib import ACT_SILU, EPI_BF16, EPI_GELU_BF16, EPI_RESID_F32, block_act_id
+from ._lib import ACT_SILU, EPI_BF16, EPI_F32, EPI_GELU_BF16, EPI_RESID_F32, block_act_id
 from .layers import conv_w
-
-
-# the fused LN+MLP kernel serves 64- and 128-channel blocks; LDT_FUSED_MLP=0 keeps the three-kernel path (A/B runs)
-import os
-FUSED_MLP = os.environ.get("LDT_FUSED_MLP", "1") != "0"
-FUSED_ATTN = os.environ.get("LDT_FUSED_ATTN", "1") != "0"
 
 
 def _bf(w):
@@ -70,104 +68,137 @@ def apply_norm(kind, x, B, N, affine=(None, None), groups=0, shift=None, scale=N
                           rows_per_sample=rows_per_sample if shift is not None else 1)
 
 
-def residual_block(P, x, B, Nq, y_bf16=None, Nk=None, c=None, per_token=False, x_bf16_out=None, q_pre=None, next_P=None, kv_pre=None):
+# What a block form hands to its stages.  n1 / n2: the keyword set of norm 1 / norm 2 as the fused LN kernels name it — the affine (ln_w, ln_b:
+# None in a conditioned LayerNorm block) and, in the two AdaLN forms, the shift / scale rows, their sample stride and the rows per sample;
+# g1 / g2: the gate rows (None: plain form), gate_stride apart per sample; act: the plain form's activation behind both norms (0: none).
+_Rows = collections.namedtuple("_Rows", "n1 n2 g1 g2 gate_stride act")
+
+
+def _modulation_rows(P, c, rps):
+    C, Co = P["C"], P["Co"]
+    n1, n2 = dict(ln_w=P["n1"][0], ln_b=P["n1"][1]), dict(ln_w=P["n2"][0], ln_b=P["n2"][1])
+    if c is None:                                                                   # plain form (layers.py:224-226)
+        return _Rows(n1, n2, None, None, 0, P.get("act", 0))
+    if C == Co:                                                                     # AdaLN, layers.py:214
+        mod = ops.sgemm(c, P["wada"], P["bada"], act_in=ACT_SILU)                  # [B, 6C]
+        sh1, sc1, g1, sh2, sc2, g2 = (mod[:, i * C:(i + 1) * C] for i in range(6))
+        s1 = s2 = 6 * C
+    else:                                                                           # U-Net down, layers.py:216-217
+        m1 = ops.sgemm(c, P["wada1"], P["bada1"], act_in=ACT_SILU)                 # [B, 2C]   shift_msa | scale_msa
+        mod = ops.sgemm(c, P["wada2"], P["bada2"], act_in=ACT_SILU)                # [B, 4Co]  gate_msa | shift_mlp | scale_mlp | gate_mlp
+        sh1, sc1, s1, s2 = m1[:, :C], m1[:, C:], 2 * C, 4 * Co
+        g1, sh2, sc2, g2 = (mod[:, i * Co:(i + 1) * Co] for i in range(4))
+    n1.update(shift=sh1, scale=sc1, mod_sample_stride=s1, rows_per_sample=rps)
+    n2.update(shift=sh2, scale=sc2, mod_sample_stride=s2, rows_per_sample=rps)
+    return _Rows(n1, n2, g1, g2, s2, 0)
+
+
+def _norm_chain(P, i, x, B, N, act, ln_w, ln_b, **mod):
+    """Norm i (0, 1) of the block by the norm kernels, then the block activation in an element-wise pass -> bf16 rows."""
+    h = apply_norm(P.get("norm", "layer_norm"), x, B, N, (ln_w, ln_b), P["groups"][i], **mod)
+    return ops.block_activation_(h, act) if act else h
+
+
+def _ln_fusable(P, R, x):
+    """Both fused LN kernels are LayerNorm kernels without an activation slot, and read the rows of x as float4."""
+    return P.get("norm", "layer_norm") == "layer_norm" and not R.act and x.stride(0) % 4 == 0
+
+
+def _can_ln_linear(P, R, x):
+    """ldt_ln_linear: C in {64, 128} (so W has no padded columns) and N % 64 == 0."""
+    return _ln_fusable(P, R, x) and P["C"] in (64, 128) and P["wq"].shape[1] == P["C"] and P["Co"] % 64 == 0
+
+
+def _q_kv(P, R, x, B, Nq, y_bf16, Nk, kv_pre, q_pre):
+    """-> (q, K | V bf16 [B*Nk, 2Co] (layers.py:189), Nk).  LN1 (+ modulate | affine) + fc_q [+ fc_kv on the same normalised input] in ONE kernel
+    (csrc/fused_mlp.hip: the normalised rows are never written), or q_pre from the previous block's MLP kernel; or norm, activation, GEMMs."""
+    ext = y_bf16 is not None or kv_pre is not None                                  # K/V come from another tensor
+    if not _can_ln_linear(P, R, x):
+        h = _norm_chain(P, 0, x, B, Nq, R.act, **R.n1)
+        q = ops.gemm_bf16(h, P["wq"], P["bq"], EPI_BF16)
+        if not ext:
+            y_bf16, Nk = h, Nq
+    elif not ext and "wqkv" in P:
+        qkv = ops.ln_linear(x, P["wqkv"], P["bqkv"], **R.n1)
+        return qkv[:, :P["Co"]], qkv[:, P["Co"]:], Nq
+    else:
+        q = q_pre if (q_pre is not None and ext) else ops.ln_linear(x, P["wq"], P["bq"], **R.n1)
+        if not ext:                                  # a U-Net down block at hidden 64 (C = 128, Co = 64, so no wqkv): LN runs twice
+            y_bf16, Nk = _norm_chain(P, 0, x, B, Nq, 0, **R.n1), Nq
+    return q, (kv_pre if kv_pre is not None else ops.gemm_bf16(y_bf16, P["wkv"], P["bkv"], EPI_BF16)), Nk
+
+
+def _can_attention_oproj(P, R, Nq, per_token):
+    """ldt_attention_oproj_resid: Dh = 32 with H in {2, 4}, Nq % H == 0 (the raw head merge, Q1), dense Wo, one gate row per SAMPLE."""
+    Co, H = P["Co"], P["H"]
+    return Co // H == 32 and H in (2, 4) and Nq % H == 0 and P["wo"].shape == (Co, Co) and not (per_token and R.g1 is not None)
+
+
+def _attention(P, R, x, q, kv, B, Nq, Nk, rps, per_token):
+    """x += g1 * fc_o(Attn(q, K, V)) -> x (a new tensor behind the conv shortcut of a U-Net down block).  Attention + out-projection + gated
+    residual in ONE kernel (csrc/attention.hip, OPROJ: the [B,H,Nq,Dh] result never goes to HBM), or attention and the residual GEMM."""
+    C, Co, H = P["C"], P["Co"], P["H"]
+    if C != Co:                                                                     # shortcut(x): Conv1d dim_in -> dim_out
+        x = ops.gemm_bf16(ops.cast_pad_bf16(x, ops.pad64(C)), P["wsc"], P["bsc"], EPI_F32)
+    if _can_attention_oproj(P, R, Nq, per_token):
+        ops.attention_oproj_resid_(q, kv[:, :Co], kv[:, Co:], B, H, Nq, Nk, 32, P["wo"], P["bo"], x, gate=R.g1, gate_sample_stride=R.gate_stride)
+    else:
+        a = ops.attention_fwd(q, kv[:, :Co], kv[:, Co:], B, H, Nq, Nk, Co // H)     # [B,H,Nq,Dh] == (B*Nq, Co) raw view
+        ops.gemm_bf16(a.view(B * Nq, Co), P["wo"], P["bo"], EPI_RESID_F32, out=x, resid=x, gate=R.g1, gate_sample_stride=R.gate_stride,
+                      rows_per_sample=rps)
+    return x
+
+
+def _can_ln_mlp(P, R, x):
+    """ldt_ln_mlp_resid: C in {64, 128} with dense W_up [4C][C] (mlp_ratio 4)."""
+    return _ln_fusable(P, R, x) and P["Co"] in (64, 128) and P["wup"].shape == (4 * P["Co"], P["Co"])
+
+
+def _can_next_linear(P, next_P):
+    """ldt_ln_mlp_resid_next: a next block of the same width, dense W [C][C] with N % 64 == 0, and an affine LayerNorm (a plain block)."""
+    Co = P["Co"]
+    return next_P is not None and next_P["C"] == next_P["Co"] == Co and tuple(next_P["wq"].shape) == (Co, Co) and Co % 64 == 0 \
+        and next_P["n1"][0] is not None
+
+
+def _mlp(P, R, x, B, Nq, rps, x_bf16_out, next_P):
+    """x += g2 * MLP(norm2(x)) in place -> q_next, or None without the hand-off.  LN2 + MLP + gated residual in ONE pass over x
+    (csrc/fused_mlp.hip), which also stores x_bf16_out and the next block's LN1 + fc_q; or norm, activation, two GEMMs, one cast."""
+    if _can_ln_mlp(P, R, x):
+        nxt = dict(w=next_P["wq"], bias=next_P["bq"], ln_w=next_P["n1"][0], ln_b=next_P["n1"][1]) if _can_next_linear(P, next_P) else None
+        r = ops.ln_mlp_resid_(x, P["wup"], P["bup"], P["wdn"], P["bdn"], gate=R.g2, x_bf16_out=x_bf16_out, next_linear=nxt, **R.n2)
+        return r[1] if nxt is not None else None
+    h2 = _norm_chain(P, 1, x, B, Nq, R.act, **R.n2)
+    u = ops.gemm_bf16(h2, P["wup"], P["bup"], EPI_GELU_BF16)
+    ops.gemm_bf16(u, P["wdn"], P["bdn"], EPI_RESID_F32, out=x, resid=x, gate=R.g2, gate_sample_stride=R.gate_stride, rows_per_sample=rps)
+    if x_bf16_out is not None:
+        x_bf16_out.copy_(ops.cast_pad_bf16(x, x_bf16_out.shape[1]))
+
+
+def _block(P, x, B, Nq, y_bf16, Nk, c, per_token, x_bf16_out, kv_pre, q_pre=None, next_P=None):
+    rps = 1 if per_token else Nq                                                    # rows that share one modulation row
+    R = _modulation_rows(P, c, rps)
+    q, kv, Nk = _q_kv(P, R, x, B, Nq, y_bf16, Nk, kv_pre, q_pre)
+    x = _attention(P, R, x, q, kv, B, Nq, Nk, rps, per_token)
+    return x, _mlp(P, R, x, B, Nq, rps, x_bf16_out, next_P)
+
+
+def residual_block(P, x, B, Nq, y_bf16=None, Nk=None, c=None, per_token=False, x_bf16_out=None, kv_pre=None):
     """x fp32 [B*Nq, C] updated IN PLACE (and returned) when dim_out == dim_in; a NEW [B*Nq, dim_out] tensor is returned
     for a U-Net down block.  y_bf16: raw K/V source [B*Nk, Ckv] (bf16) or None (self, modulated).
     c: fp32 [B, dim_c] condition (AdaLN) — or [B*Nq, dim_c] with per_token=True (layers.py:210: a (B, dim_c, N) condition
     modulates every token with its own row; the Compressor's `pos_embedding: mlp`) — or None (plain LayerNorm block).
     x_bf16_out: optional bf16 [B*Nq, dim_out] buffer that receives a copy of the block's result (written by the fused MLP
     kernel's own store pass, or by one cast on the unfused path).
-    kv_pre: bf16 [B*Nk, 2*dim_out] = fc_kv(y) computed by the caller (then y_bf16 is not needed: pass Nk).
-    next_P: packed holder of the plain-LayerNorm block that will run next on the same rows with a K/V source of its own (the
-    next decoder level): its LN1 + fc_q is then computed by THIS block's last kernel and `(x, q_next)` is returned — or
-    `(x, None)` when the shapes do not allow it; pass that `q_next` to the next call as `q_pre`."""
-    C, Co, H = P["C"], P["Co"], P["H"]
-    rps = 1 if per_token else Nq                                                    # rows that share one modulation row
-    ln_kw = {}
-    if c is not None and C == Co:
-        mod = ops.sgemm(c, P["wada"], P["bada"], act_in=ACT_SILU)                  # [B, 6C]  layers.py:214
-        sh1, sc1, g1, sh2, sc2, g2 = (mod[:, i * C:(i + 1) * C] for i in range(6))
-        s1 = s2 = 6 * C
-        ln_kw = dict(shift=sh1, scale=sc1, mod_sample_stride=s1, rows_per_sample=rps)
-    elif c is not None:                                                             # layers.py:216-217
-        m1 = ops.sgemm(c, P["wada1"], P["bada1"], act_in=ACT_SILU)                 # [B, 2C]   shift_msa | scale_msa
-        mod = ops.sgemm(c, P["wada2"], P["bada2"], act_in=ACT_SILU)                # [B, 4Co]  gate_msa | shift_mlp | scale_mlp | gate_mlp
-        g1, sh2, sc2, g2 = (mod[:, i * Co:(i + 1) * Co] for i in range(4))
-        s2 = 4 * Co
-        ln_kw = dict(shift=m1[:, :C], scale=m1[:, C:], mod_sample_stride=2 * C, rows_per_sample=rps)
-    else:
-        g1 = g2 = None
-        s2 = 0
-    # no-condition branch with a block activation (layers.py:224-226, `decoder_act`): act(norm1(x)) feeds fc_q (and fc_kv in self-attention),
-    # act(norm2(x)) the MLP — the LayerNorm kernels + one element-wise pass + the GEMMs (the fused LN kernels have no activation slot)
-    act = P.get("act", 0) if c is None else 0
-    kind = P.get("norm", "layer_norm")
-    ln = kind == "layer_norm"                                        # the fused LN kernels are LayerNorm kernels: other norms take the chain below
-    fused_in = FUSED_ATTN and C in (64, 128) and P["wq"].shape[1] == C and Co % 64 == 0 and x.stride(0) % 4 == 0 and not act and ln
-    if fused_in:
-        # LN1 (+ modulate | affine) + fc_q [+ fc_kv on the same normalised input] in ONE kernel (csrc/fused_mlp.hip):
-        # the normalised activations are never written
-        aff = {} if c is not None else dict(ln_w=P["n1"][0], ln_b=P["n1"][1])
-        if y_bf16 is None and kv_pre is None and "wqkv" in P:
-            qkv = ops.ln_linear(x, P["wqkv"], P["bqkv"], **aff, **ln_kw)
-            q, kv, Nk = qkv[:, :Co], qkv[:, Co:], Nq
-        else:
-            # (q_pre: this block's LN1 + fc_q was already computed by the previous block's MLP kernel)
-            ext = y_bf16 is not None or kv_pre is not None                           # K/V come from another tensor
-            q = q_pre if (q_pre is not None and ext) else ops.ln_linear(x, P["wq"], P["bq"], **aff, **ln_kw)
-            if not ext:                                                             # (not reached with the shipped shapes)
-                y_bf16, Nk = ops.layernorm_modulate(x, **({"w": P["n1"][0], "b": P["n1"][1]} if c is None else ln_kw)), Nq
-            kv = kv_pre if kv_pre is not None else ops.gemm_bf16(y_bf16, P["wkv"], P["bkv"], EPI_BF16)
-    else:
-        if c is not None:
-            h = ops.layernorm_modulate(x, **ln_kw) if ln else apply_norm(kind, x, B, Nq, P["n1"], P["groups"][0], **ln_kw)
-        else:
-            h = apply_norm(kind, x, B, Nq, P["n1"], P["groups"][0])
-            if act:
-                ops.block_activation_(h, act)
-        q = ops.gemm_bf16(h, P["wq"], P["bq"], EPI_BF16)
-        if y_bf16 is None and kv_pre is None:
-            y_bf16, Nk = h, Nq
-        kv = kv_pre if kv_pre is not None else ops.gemm_bf16(y_bf16, P["wkv"], P["bkv"], EPI_BF16)   # [B*Nk, 2Co]: K | V  (layers.py:189)
-    if C != Co:                                                                     # shortcut(x): Conv1d dim_in -> dim_out
-        from ._lib import EPI_F32
-        x = ops.gemm_bf16(ops.cast_pad_bf16(x, ops.pad64(C)), P["wsc"], P["bsc"], EPI_F32)
-    if FUSED_ATTN and Co // H == 32 and H in (2, 4) and Nq % H == 0 and P["wo"].shape == (Co, Co) and not (per_token and g1 is not None):
-        # attention + out-projection + gated residual in ONE kernel (csrc/attention.hip, OPROJ): the [B,H,Nq,Dh]
-        # result never goes to HBM — the Compressor's d = 128 blocks
-        ops.attention_oproj_resid_(q, kv[:, :Co], kv[:, Co:], B, H, Nq, Nk, 32, P["wo"], P["bo"], x, gate=g1,
-                                   gate_sample_stride=s2 if g1 is not None else 0)
-    else:
-        a = ops.attention_fwd(q, kv[:, :Co], kv[:, Co:], B, H, Nq, Nk, Co // H)     # [B,H,Nq,Dh] == (B*Nq, Co) raw view
-        ops.gemm_bf16(a.view(B * Nq, Co), P["wo"], P["bo"], EPI_RESID_F32, out=x, resid=x, gate=g1,
-                      gate_sample_stride=s2 if g1 is not None else 0, rows_per_sample=rps)
-    if FUSED_MLP and Co in (64, 128) and P["wup"].shape == (4 * Co, Co) and x.stride(0) % 4 == 0 and not act and ln:
-        # LN2 + MLP + gated residual in ONE pass over x (csrc/fused_mlp.hip) — the Compressor's d = 128 blocks
-        nxt = None
-        if next_P is not None and FUSED_ATTN and next_P["C"] == next_P["Co"] == Co and tuple(next_P["wq"].shape) == (Co, Co) \
-                and Co % 64 == 0 and next_P["n1"][0] is not None:
-            nxt = dict(w=next_P["wq"], bias=next_P["bq"], ln_w=next_P["n1"][0], ln_b=next_P["n1"][1])
-        if c is not None:
-            r = ops.ln_mlp_resid_(x, P["wup"], P["bup"], P["wdn"], P["bdn"], shift=sh2, scale=sc2, gate=g2,
-                                  mod_sample_stride=s2, rows_per_sample=rps, x_bf16_out=x_bf16_out, next_linear=nxt)
-        else:
-            r = ops.ln_mlp_resid_(x, P["wup"], P["bup"], P["wdn"], P["bdn"], ln_w=P["n2"][0], ln_b=P["n2"][1], x_bf16_out=x_bf16_out,
-                                  next_linear=nxt)
-        if next_P is not None:
-            return (x, r[1]) if nxt is not None else (x, None)
-        return x
-    if c is not None:
-        h2 = apply_norm(kind, x, B, Nq, P["n2"], P["groups"][1], shift=sh2, scale=sc2, mod_sample_stride=s2, rows_per_sample=rps)
-    else:
-        h2 = apply_norm(kind, x, B, Nq, P["n2"], P["groups"][1])
-        if act:
-            ops.block_activation_(h2, act)
-    u = ops.gemm_bf16(h2, P["wup"], P["bup"], EPI_GELU_BF16)
-    ops.gemm_bf16(u, P["wdn"], P["bdn"], EPI_RESID_F32, out=x, resid=x, gate=g2,
-                  gate_sample_stride=s2 if g2 is not None else 0, rows_per_sample=rps)
-    if x_bf16_out is not None:
-        x_bf16_out.copy_(ops.cast_pad_bf16(x, x_bf16_out.shape[1]))
-    return (x, None) if next_P is not None else x
+    kv_pre: bf16 [B*Nk, 2*dim_out] = fc_kv(y) computed by the caller (then y_bf16 is not needed: pass Nk)."""
+    return _block(P, x, B, Nq, y_bf16, Nk, c, per_token, x_bf16_out, kv_pre)[0]
+
+
+def residual_block_handoff(P, x, B, Nq, Nk, kv_pre, q_pre=None, next_P=None, c=None, x_bf16_out=None):
+    """A decoder level's block: `residual_block` on the caller's K | V (`kv_pre`) that hands the next level its query projection -> (x, q_next).
+    next_P: packed holder of the plain-LayerNorm block that will run next on the same rows with a K/V source of its own: its LN1 + fc_q is
+    computed by THIS block's last kernel; q_next is None where the shapes do not allow it.  q_pre: the previous level's q_next, or None."""
+    return _block(P, x, B, Nq, None, Nk, c, False, x_bf16_out, kv_pre, q_pre, next_P)
 
 
 def pack_final(fl):
@@ -180,7 +211,6 @@ def pack_final(fl):
 
 def final_layer(P, x, B, N, c, out_dtype=torch.float32, per_token=False):
     """FinalLayer with condition (layers.py:240-246): Conv(mod(LN(x))); c [B, dim_c], or [B*N, dim_c] with per_token."""
-    from ._lib import EPI_F32
     C = P["C"]
     mod = ops.sgemm(c, P["wada"], P["bada"], act_in=ACT_SILU)                      # [B, 2C] shift | scale
     h = apply_norm(P.get("norm", "layer_norm"), x, B, N, P.get("n", (None, None)), P.get("groups", 0), shift=mod[:, :C], scale=mod[:, C:],

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, LdtHipError
-from .blocks import final_layer, pack_block, pack_final, residual_block
+from .blocks import final_layer, pack_block, pack_final, residual_block, residual_block_handoff
 from .layers import ActNorm, FinalLayer, LabelEmbedding, MLP, ResidualBlock, _Holder, conv_w, params_fingerprint
 
 
@@ -378,23 +378,22 @@ class Compressor(nn.Module):
         km = keep_mask.to(prior.device)
         return torch.stack([prior[km[b]] for b in range(Bc)], 0).reshape(Bc * num_points, -1).contiguous()
 
-    def _decoder_level(self, Pd, o, eps_j, Bc, N, T, c=None, o_bf16=None, q_pre=None, next_P=None):
-        """DecoderBlock.forward (Network.py:80-83): o <- att1(o, ln(eps_j), c); c = label embedding in a class-conditional
-        forward, None in `sample` (which never passes one, :263-264: the block then runs its plain-LayerNorm branch)."""
+    def _decoder_level(self, P, j, o, eps_j, Bc, N, T, q, c=None, o_bf16=None):
+        """DecoderBlock.forward (Network.py:80-83) of level j, top-down (reversed(self.decoder), :263): o <- att1(o, ln(eps_j), c); c = label
+        embedding in a class-conditional forward, None in `sample` (which never passes one, :263-264: the block then runs its plain-LayerNorm
+        branch).  q: what level j - 1 returned -> level j + 1's LN1 + fc_q, computed without a condition by this level's last kernel, or None."""
+        Pd = P["dec"][self.n_layers - 1 - j]
+        nxt = P["dec"][self.n_layers - 2 - j]["att1"] if (j + 1 < self.n_layers and c is None) else None
         kv = ops.sgemm(eps_j, Pd["w_zkv"], Pd["b_zkv"], out_bf16=True)           # fc_kv(Conv1d z_dim -> C) on T tokens, composed
-        return residual_block(Pd["att1"], o, Bc, N, kv_pre=kv, Nk=T, c=c, x_bf16_out=o_bf16, q_pre=q_pre, next_P=next_P)
+        return residual_block_handoff(Pd["att1"], o, Bc, N, T, kv, q_pre=q, next_P=nxt, c=c, x_bf16_out=o_bf16)[1]
 
     def _decode_chunk(self, P, eps, N, keep_mask, seed_eps=None):
         Bc, T, _ = eps.shape
         o = self._initial_set(P, Bc, N, keep_mask, seed_eps)
         e2 = eps.view(Bc * T, -1)
         q = None
-        for j in range(self.n_layers):                                             # reversed(self.decoder), :263
-            Pd = P["dec"][self.n_layers - 1 - j]
-            # level j's last kernel also computes level j + 1's LN1 + fc_q on the rows it has just written (no condition here)
-            nxt = P["dec"][self.n_layers - 2 - j]["att1"] if j + 1 < self.n_layers else None
-            r = self._decoder_level(Pd, o, e2[:, self.z_dim * j: self.z_dim * (j + 1)], Bc, N, T, q_pre=q, next_P=nxt)
-            q = r[1] if nxt is not None else None
+        for j in range(self.n_layers):
+            q = self._decoder_level(P, j, o, e2[:, self.z_dim * j: self.z_dim * (j + 1)], Bc, N, T, q)
         return ops.sgemm(o, P["w_out"], P["b_out"]).view(Bc, N, 3)                 # Conv1d C -> 3, :266
 
     @staticmethod
@@ -541,9 +540,7 @@ class Compressor(nn.Module):
                 kls.append(kl.view(B, T, z).transpose(1, 2)); logqz.append(lq.view(B, T, z).transpose(1, 2)); kl_sums.append(ks)
             else:
                 stats.append(ops.reparam(post, nz, ej, self.min_sigma, 10., want_stats))
-            nxt = P["dec"][L - 2 - j]["att1"] if (j + 1 < L and l_emb is None) else None
-            r = self._decoder_level(Pd, o, ej, B, npts, T, c=l_emb, o_bf16=o_bf if j + 1 < L else None, q_pre=q_dec, next_P=nxt)
-            q_dec = r[1] if nxt is not None else None
+            q_dec = self._decoder_level(P, j, o, ej, B, npts, T, q_dec, c=l_emb, o_bf16=o_bf if j + 1 < L else None)
         out = ops.sgemm(o, P["w_out"], P["b_out"]).view(B, npts, 3)
         res = {"set": self.postprocess(out), "all_eps": all_eps.view(B, T, L * z), "max": tok.max(),
                "posteriors": [(all_eps.view(B, T, L * z)[..., z * j: z * (j + 1)],) + tuple(

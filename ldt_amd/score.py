@@ -21,7 +21,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import ACT_NONE, ACT_SILU, MAX_BLOCKS, ScorePlan, check, lib
+from ._lib import ACT_NONE, ACT_SILU, EPI_F32, MAX_BLOCKS, ScorePlan, check, lib
+from .blocks import final_layer, pack_block, pack_final, residual_block
 from .layers import FinalLayer, LabelEmbedding, ResidualBlock, TimeEmbedding, conv_w, params_fingerprint
 
 
@@ -97,29 +98,20 @@ class Score(nn.Module):
         dev = self._device()
         if dev.type != "cuda":
             raise RuntimeError("Score parameters are on %s: the HIP path needs them on the GPU (.to('cuda'))" % dev)
-        if self.unet:
-            from .blocks import pack_block, pack_final
+        with torch.no_grad():
+            P = {"w_in": ops.cast_pad_bf16(conv_w(self.ln_in).float().contiguous(), ops.pad64(self.z_dim)),
+                 "b_in": self.ln_in.bias.detach().float().contiguous()}
+        if self.host_blocks:                                         # host-driven blocks (ldt_amd/blocks.py): the U-Net's three groups, or one stack
             with torch.no_grad():
-                zp = ops.pad64(self.z_dim)
-                P = {"w_in": ops.cast_pad_bf16(conv_w(self.ln_in).float().contiguous(), zp),
-                     "b_in": self.ln_in.bias.detach().float().contiguous(),
-                     "up": [pack_block(b) for b in self.Transformer_Up], "mid": pack_block(self.Transformer_Mid),
-                     "down": [pack_block(b) for b in self.Transformer_Down], "final": pack_final(self.ln_out)}
-            self._pack, self._pack_key = P, key
-            return P
-        if self.host_blocks:
-            from .blocks import pack_block, pack_final
-            with torch.no_grad():
-                P = {"w_in": ops.cast_pad_bf16(conv_w(self.ln_in).float().contiguous(), ops.pad64(self.z_dim)),
-                     "b_in": self.ln_in.bias.detach().float().contiguous(),
-                     "blocks": [pack_block(b) for b in self.Transformer], "final": pack_final(self.ln_out)}
+                if self.unet:
+                    P.update(up=[pack_block(b) for b in self.Transformer_Up], mid=pack_block(self.Transformer_Mid),
+                             down=[pack_block(b) for b in self.Transformer_Down], final=pack_final(self.ln_out))
+                else:
+                    P.update(blocks=[pack_block(b) for b in self.Transformer], final=pack_final(self.ln_out))
             self._pack, self._pack_key = P, key
             return P
         with torch.no_grad():
-            P = {"w_qkv": [], "b_qkv": [], "w_o": [], "b_o": [], "w_up": [], "b_up": [], "w_dn": [], "b_dn": []}
-            zp = ops.pad64(self.z_dim)
-            P["w_in"] = ops.cast_pad_bf16(conv_w(self.ln_in).float().contiguous(), zp)
-            P["b_in"] = self.ln_in.bias.detach().float().contiguous()
+            P.update({"w_qkv": [], "b_qkv": [], "w_o": [], "b_o": [], "w_up": [], "b_up": [], "w_dn": [], "b_dn": []})
             for blk in self.Transformer:
                 wqkv = torch.cat([conv_w(blk.fc_q), conv_w(blk.fc_kv)], 0).float().contiguous()
                 P["w_qkv"].append(ops.cast_pad_bf16(wqkv, wqkv.shape[1]))
@@ -175,8 +167,14 @@ class Score(nn.Module):
         h = ops.sgemm(e, te[0].weight, te[0].bias, act_out=ACT_SILU)
         return ops.sgemm(h, te[2].weight, te[2].bias)
 
-    def condition_embedding(self, label=None, condition=None):
-        """-> (extra [B,t_dim] or None, kv_cond {block: K|V} or None, cond_tokens) for forward()/the fused loop."""
+    def _condition_rows(self, t, extra=None):
+        """c = TimeEmbedding(t) (+ extra: the label / image-condition embedding, score.py:135) -> [n, t_dim] fp32."""
+        c = self.time_embedding(t)
+        return c if extra is None else ops.add_f32(c, extra.expand_as(c))
+
+    def _unpack_condition(self, label, condition):
+        """-> (pts_cond (B, hidden, S) or None, extra [B, t_dim] or None): the embedded point condition, and what is added to the time
+        embedding — the label's embedding, or without a label the image condition's."""
         if isinstance(condition, dict):                              # score.py:129-131: raw ViPC inputs -> ConditionNet
             if not hasattr(self, "c_net"):
                 raise ValueError("a raw condition dict needs cfg.score.condition=True (ConditionNet, score.py:64-65)")
@@ -187,8 +185,13 @@ class Score(nn.Module):
             extra = self.label_embedding(label)                      # a label wins over the image condition (score.py:135)
         elif torch.is_tensor(img_cond):
             extra = img_cond.to(self._device(), torch.float32).contiguous()
+        return (pts_cond if torch.is_tensor(pts_cond) else None), extra
+
+    def condition_embedding(self, label=None, condition=None):
+        """-> (extra [B,t_dim] or None, kv_cond {block: K|V} or None, cond_tokens) for forward()/the fused loop."""
+        pts_cond, extra = self._unpack_condition(label, condition)
         kv, S = (None, 0)
-        if torch.is_tensor(pts_cond):
+        if pts_cond is not None:
             kv, S = self.project_condition(pts_cond)
         return extra, kv, S
 
@@ -286,12 +289,7 @@ class Score(nn.Module):
         """t [n] fp32 on device -> (c [n,t_dim], mod [n,n_mod]) in fp32.
         c = TimeEmbedding(t) (+ extra_c: label / image-condition embedding, score.py:135);
         mod[:, l*6D:(l+1)*6D] = adaLN_l(SiLU(c)); the last 2D columns are FinalLayer's (shift, scale)."""
-        te = self.TimeEmbedding.mlp
-        e = ops.sinusoid(t.contiguous(), self._frequencies())
-        h = ops.sgemm(e, te[0].weight, te[0].bias, act_out=ACT_SILU)
-        c = ops.sgemm(h, te[2].weight, te[2].bias)
-        if extra_c is not None:
-            c = ops.add_f32(c, extra_c.expand_as(c))
+        c = self._condition_rows(t, extra_c)
         D = self.hidden_size
         mod = torch.empty((t.numel(), self.n_mod), dtype=torch.float32, device=t.device)
         for l, blk in enumerate(self.Transformer):
@@ -335,11 +333,8 @@ class Score(nn.Module):
         folding for this model when it exceeds FOLD_MAX_MEAN_RATIO (LDT_LN_FOLD=2 keeps it forced on)."""
         B, T, _ = x.shape
         mon = torch.zeros(1, dtype=torch.float32, device=x.device)
-        step = torch.full((1,), int(step_index), dtype=torch.int32, device=x.device)
         plan = self.plan(B, T, mod, self.n_mod, 0, fold=fold, slot=0, monitor=mon)   # (runs before the loop on the same stream: shares its workspace)
-        out = torch.empty_like(x)
-        check(lib().ldt_score_forward(ctypes.byref(plan), x.contiguous().data_ptr(), out.data_ptr(), step.data_ptr(), ops.stream_ptr()),
-              "ldt_score_forward")
+        self._run(plan, x.contiguous(), step_index)
         return self.note_fold_ratio(float(mon.item()))
 
     def note_fold_ratio(self, ratio):
@@ -401,6 +396,15 @@ class Score(nn.Module):
         h = ops.sgemm(e, le.mlp[0].weight, le.mlp[0].bias, act_out=ACT_SILU)
         return ops.sgemm(h, le.mlp[2].weight, le.mlp[2].bias)
 
+    def _run(self, plan, x, step=None):
+        """`ldt_score_forward` under `plan` on the contiguous fp32 latents x (B, T, z) -> the predicted noise.  step: the row of the plan's
+        multi-step tables to read, handed over in device memory as the sampling loop does (None: row 0)."""
+        out = torch.empty_like(x)
+        step = None if step is None else torch.full((1,), int(step), dtype=torch.int32, device=x.device)
+        check(lib().ldt_score_forward(ctypes.byref(plan), x.data_ptr(), out.data_ptr(), None if step is None else step.data_ptr(),
+                                      ops.stream_ptr()), "ldt_score_forward")
+        return out
+
     @torch.no_grad()
     def forward(self, x, t, label=None, condition=None):
         """x (bs, tokens, z_dim), t (bs,) -> predicted noise (bs, tokens, z_dim)   [score.py:117-151]
@@ -423,11 +427,7 @@ class Score(nn.Module):
             return self._forward_host_blocks(x, t, label, condition)
         extra, kv, S = self.condition_embedding(label, condition)
         _, mod = self.time_table(t.to(x).float(), extra_c=extra)
-        plan = self.plan(B, T, mod, 0, self.n_mod, kv_cond=kv, cond_tokens=S)      # per-sample AdaLN rows
-        out = torch.empty_like(x)
-        check(lib().ldt_score_forward(ctypes.byref(plan), x.data_ptr(), out.data_ptr(), None, ops.stream_ptr()),
-              "ldt_score_forward")
-        return out
+        return self._run(self.plan(B, T, mod, 0, self.n_mod, kv_cond=kv, cond_tokens=S), x)      # per-sample AdaLN rows
 
     @torch.no_grad()
     def forward_shared_t(self, x, t, fold=None):
@@ -444,11 +444,7 @@ class Score(nn.Module):
         x = x.contiguous().float()
         _, mod = self.time_table(torch.tensor([float(t)], dtype=torch.float32, device=x.device))
         use_fold = self.can_fold(B, T) if fold is None else bool(fold)
-        plan = self.plan(B, T, mod, self.n_mod, 0, fold=self.fold_table(mod) if use_fold else None)
-        out = torch.empty_like(x)
-        check(lib().ldt_score_forward(ctypes.byref(plan), x.data_ptr(), out.data_ptr(), None, ops.stream_ptr()),
-              "ldt_score_forward")
-        return out
+        return self._run(self.plan(B, T, mod, self.n_mod, 0, fold=self.fold_table(mod) if use_fold else None), x)
 
     @torch.no_grad()
     def forward_table_row(self, x, step_index, mod, fold=None):
@@ -460,63 +456,39 @@ class Score(nn.Module):
             raise RuntimeError("Score.forward_table_row: x is on %s; the HIP path has no CPU fallback" % x.device)
         B, T, z = x.shape
         assert z == self.z_dim and mod.shape[1] == self.n_mod and 0 <= int(step_index) < mod.shape[0]
-        x = x.contiguous().float()
-        step = torch.full((1,), int(step_index), dtype=torch.int32, device=x.device)
-        plan = self.plan(B, T, mod, self.n_mod, 0, fold=fold)
-        out = torch.empty_like(x)
-        check(lib().ldt_score_forward(ctypes.byref(plan), x.data_ptr(), out.data_ptr(), step.data_ptr(), ops.stream_ptr()),
-              "ldt_score_forward")
-        return out
+        return self._run(self.plan(B, T, mod, self.n_mod, 0, fold=fold), x.contiguous().float(), step_index)
 
     def _forward_host_blocks(self, x, t, label, condition):
         """The plain block stack with `norm` other than layer_norm (score.py:117-151 with get_norm's group_norm / None, tools/utils.py:168-181):
         host-driven, every block the kernel chain of ldt_amd/blocks.py (norm kernel -> GEMMs -> attention -> GEMMs); cross-attention to the
         point condition on the even blocks (:148-149) with K / V from the RAW condition rows."""
-        from ._lib import EPI_F32
-        from .blocks import final_layer, residual_block
-        if isinstance(condition, dict):
-            if not hasattr(self, "c_net"):
-                raise ValueError("a raw condition dict needs cfg.score.condition=True (ConditionNet, score.py:64-65)")
-            condition = self.c_net(condition)
-        pts_cond, img_cond = (None, 0.) if condition is None else condition
+        pts_cond, extra = self._unpack_condition(label, condition)
         B, T, _ = x.shape
         P = self.packed()
-        c = self.time_embedding(t.to(x).float())
-        if label is not None:
-            c = ops.add_f32(c, self.label_embedding(label))
-        elif torch.is_tensor(img_cond):
-            c = ops.add_f32(c, img_cond.to(x).expand_as(c).contiguous())
+        c = self._condition_rows(t.to(x).float(), extra)
         y, S = None, None
-        if torch.is_tensor(pts_cond):                                # (B, hidden, S) channels-first -> token-major raw rows, bf16
+        if pts_cond is not None:                                     # (B, hidden, S) channels-first -> token-major raw rows, bf16
             S = pts_cond.shape[2]
             yt = pts_cond.to(self._device(), torch.float32).transpose(1, 2).contiguous().view(B * S, self.hidden_size)
             y = ops.cast_pad_bf16(yt, self.hidden_size)
         xin = ops.cast_pad_bf16(x.view(B * T, self.z_dim), ops.pad64(self.z_dim))
         h = ops.gemm_bf16(xin, P["w_in"], P["b_in"], EPI_F32)                       # ln_in
         for l, Pb in enumerate(P["blocks"]):
-            if y is not None and l % 2 == 0:
-                residual_block(Pb, h, B, T, y_bf16=y, Nk=S, c=c)
-            else:
-                residual_block(Pb, h, B, T, c=c)
+            yl, Sl = (y, S) if l % 2 == 0 else (None, None)                          # (score.py:149: idx % 2 == 0)
+            residual_block(Pb, h, B, T, y_bf16=yl, Nk=Sl, c=c)
         return final_layer(P["final"], h, B, T, c).view(B, T, self.z_dim)
 
     def _forward_unet(self, x, t, label, condition):
         """`unet: True` variant (score.py:138-146): num_blocks//2 up blocks whose outputs are kept, a mid block, then
         num_blocks//2 down blocks on cat(x, skip) (width 2*hidden -> hidden, conv shortcut, adaLN1/adaLN2).  Host-driven:
         each block is the same sequence of HIP kernels as the Compressor's blocks (ldt_amd/blocks.py)."""
-        from ._lib import EPI_F32
-        from .blocks import final_layer, residual_block
-        pts_cond, img_cond = (None, 0.) if condition is None else (self.c_net(condition) if isinstance(condition, dict) else condition)
-        if torch.is_tensor(pts_cond):
+        pts_cond, extra = self._unpack_condition(label, condition)
+        if pts_cond is not None:
             raise NotImplementedError("unet + point condition: the reference passes the (B,hidden,S) condition as K/V source to "
                                       "down blocks whose fc_kv expects 2*hidden channels (score.py:80,146) and fails there")
         B, T, _ = x.shape
         P = self.packed()
-        c = self.time_embedding(t.to(x).float())
-        if label is not None:
-            c = ops.add_f32(c, self.label_embedding(label))
-        elif torch.is_tensor(img_cond):
-            c = ops.add_f32(c, img_cond.to(x).expand_as(c))
+        c = self._condition_rows(t.to(x).float(), extra)
         xin = ops.cast_pad_bf16(x.view(B * T, self.z_dim), ops.pad64(self.z_dim))
         h = ops.gemm_bf16(xin, P["w_in"], P["b_in"], EPI_F32)                       # ln_in
         skips = [h.clone()]
