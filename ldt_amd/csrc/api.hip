@@ -506,11 +506,20 @@ extern "C" int ldt_score_forward_profile(const ldt_score_plan* p, const float* x
 }
 
 // ------------------------------------------------------------------------------ reverse-SDE loop
-static int enqueue_step(const ldt_score_plan* p, float* x, float* x_mean, float* eps_tmp, const float* coef, int mode,
-                        const float* noise, long noise_step_stride, long elem_offset, uint64_t seed, int* step_counter,
-                        const ldt_cond_args* cond, float* x_traj, hipStream_t s) {
-    if (cond) {                                                 // per-sample AdaLN rows of this step
-        TRY(ldt_cond_rows_launch(cond->temb, cond->extra, cond->c_buf, cond->c_buf_bf16, step_counter, p->batch, cond->t_dim, 1, s));   // c_buf = silu(c)
+// What a step of the loop works on beside its plan; filled once per ldt_sample_loop.  Every step-dependent operand is indexed by *step_counter.
+struct SampleStep {
+    float *x, *x_mean, *eps_tmp, *x_traj;
+    const float *coef, *noise;
+    long noise_step_stride, elem_offset;
+    uint64_t seed;
+    int mode, *step_counter;
+    const ldt_cond_args* cond;                                  // null: batch-shared AdaLN rows, indexed by the step inside the forward
+};
+
+// One step = four launches: (conditioned) AdaLN rows of this step, Score forward, sampler update, ++*step_counter.
+static int enqueue_step(const SampleStep& st, const ldt_score_plan* p, hipStream_t s) {
+    if (const ldt_cond_args* cond = st.cond) {                  // per-sample AdaLN rows of this step
+        TRY(ldt_cond_rows_launch(cond->temb, cond->extra, cond->c_buf, cond->c_buf_bf16, st.step_counter, p->batch, cond->t_dim, 1, s));   // c_buf = silu(c)
         if (cond->w_ada_bf16 && (cond->t_dim % 64 == 0 || !cond->w_ada)) {   // bf16 weight panel: half the bytes of the HBM-bound row GEMM (fp32 accumulation + bias); a width the MFMA GEMM does not take falls back to the fp32 rows when they were given
             const GemmArgs g = gemm_args(BF(cond->c_buf_bf16), cond->t_dim, BF(cond->w_ada_bf16), cond->t_dim, cond->b_ada, cond->mod_buf, cond->n_mod,
                                          p->batch, cond->n_mod, cond->t_dim, p->gemm_wgs);
@@ -521,12 +530,43 @@ static int enqueue_step(const ldt_score_plan* p, float* x, float* x_mean, float*
             TRY(ldt_sgemm_launch(&g, s));
         }
     }
-    TRY(score_forward_impl(p, x, eps_tmp, cond ? nullptr : step_counter, s, nullptr));
+    TRY(score_forward_impl(p, st.x, st.eps_tmp, st.cond ? nullptr : st.step_counter, s, nullptr));
     const long n = (long)p->batch * p->tokens * p->z_dim;
-    StepArgs st{x, eps_tmp, noise, x, x_mean, coef, step_counter, 0, mode, n, elem_offset, noise_step_stride,
-                (uint32_t)seed, (uint32_t)(seed >> 32), 1, 0, x_traj};
-    TRY(ldt_sampler_step_launch(&st, s));
-    return ldt_advance_step_launch(step_counter, s);
+    StepArgs a{st.x, st.eps_tmp, st.noise, st.x, st.x_mean, st.coef, st.step_counter, 0, st.mode, n, st.elem_offset, st.noise_step_stride,
+               (uint32_t)st.seed, (uint32_t)(st.seed >> 32), 1, 0, st.x_traj};
+    TRY(ldt_sampler_step_launch(&a, s));
+    return ldt_advance_step_launch(st.step_counter, s);
+}
+
+static int hip_ok(hipError_t e, const char* what) {
+    if (e != hipSuccess) ldt_set_error("sample_loop: %s: %s", what, hipGetErrorString(e));
+    return (int)e;                                              // (hipSuccess == LDT_OK == 0)
+}
+
+// What the graph path holds while it runs: the private capture stream, its fences against the caller's stream, and the captured step as
+// graph + exec ([0] the plain step, [1] with the fold monitor on).  Whichever way the loop ends, in-flight launches finish before their exec goes.
+struct StepGraphs {
+    hipStream_t gs = nullptr;
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    hipGraph_t graph[2] = {nullptr, nullptr};
+    hipGraphExec_t exec[2] = {nullptr, nullptr};
+    StepGraphs() = default;
+    StepGraphs(const StepGraphs&) = delete;                     // one owner
+    ~StepGraphs() {
+        if (gs) (void)hipStreamSynchronize(gs);
+        for (hipGraphExec_t e : exec) if (e) (void)hipGraphExecDestroy(e);
+        for (hipGraph_t g : graph) if (g) (void)hipGraphDestroy(g);
+        for (hipEvent_t e : {ev_in, ev_out}) if (e) (void)hipEventDestroy(e);
+        if (gs) (void)hipStreamDestroy(gs);
+    }
+};
+
+// Capture one step on `gs`.  A capture that was begun is always ended; a failed launch inside it keeps its own message.
+static int capture_step(const SampleStep& st, const ldt_score_plan* p, hipStream_t gs, hipGraph_t* graph) {
+    TRY(hip_ok(hipStreamBeginCapture(gs, hipStreamCaptureModeThreadLocal), "begin capture"));
+    const int rc = enqueue_step(st, p, gs);
+    const hipError_t e = hipStreamEndCapture(gs, graph);
+    return rc != LDT_OK ? rc : hip_ok(e, "end capture");
 }
 
 extern "C" int ldt_sample_loop(const ldt_score_plan* p, float* x, float* x_mean, float* eps_tmp, const float* coef,
@@ -540,8 +580,8 @@ extern "C" int ldt_sample_loop(const ldt_score_plan* p, float* x, float* x_mean,
                           p->mod_sample_stride == cond->n_mod && cond->t_dim > 0), LDT_EARG,
                 "sample_loop: inconsistent conditioning block (plan->mod must be cond->mod_buf with sample stride n_mod)");
     hipStream_t s = ST(stream);
-    hipError_t e = hipMemsetAsync(step_counter, 0, sizeof(int), s);
-    if (e != hipSuccess) { ldt_set_error("sample_loop: memset: %s", hipGetErrorString(e)); return (int)e; }
+    const SampleStep st{x, x_mean, eps_tmp, x_traj, coef, noise, noise_step_stride, elem_offset, seed, mode, step_counter, cond};
+    TRY(hip_ok(hipMemsetAsync(step_counter, 0, sizeof(int), s), "memset"));
     // LN-fold monitor inside the loop (plan->fold_monitor, every plan->fold_monitor_every steps and on the last one): the other steps run a
     // copy of the plan without it
     ldt_score_plan plain = *p;
@@ -550,61 +590,21 @@ extern "C" int ldt_sample_loop(const ldt_score_plan* p, float* x, float* x_mean,
     const int every = p->fold_monitor_every > 0 ? p->fold_monitor_every : 1;
     auto monitored = [&](int i) { return mon && (i % every == 0 || i == n_steps - 1); };
     if (!use_graph) {
-        for (int i = 0; i < n_steps; ++i)
-            TRY(enqueue_step(monitored(i) ? p : &plain, x, x_mean, eps_tmp, coef, mode, noise, noise_step_stride, elem_offset, seed, step_counter, cond, x_traj, s));
+        for (int i = 0; i < n_steps; ++i) TRY(enqueue_step(st, monitored(i) ? p : &plain, s));
         return LDT_OK;
     }
-    // One step captured, replayed n_steps times; every step-dependent operand is indexed by *step_counter.
-    // Capture runs on a private non-blocking stream (the caller's may be the legacy default stream, which
-    // cannot be captured), fenced against the caller's stream with events on both sides.
-    hipStream_t gs = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    hipGraph_t graph = nullptr, graph_m = nullptr;
-    hipGraphExec_t exec = nullptr, exec_m = nullptr;                     // the plain step and (fold monitor on) the monitored step
-    int status = LDT_OK;
-#define HIPTRY(call, what)                                                                   \
-    do {                                                                                     \
-        const hipError_t _e = (call);                                                        \
-        if (_e != hipSuccess && status == LDT_OK) {                                          \
-            ldt_set_error("sample_loop: %s: %s", what, hipGetErrorString(_e));               \
-            status = (int)_e;                                                                \
-        }                                                                                    \
-    } while (0)
-    HIPTRY(hipStreamCreateWithFlags(&gs, hipStreamNonBlocking), "stream create");
-    HIPTRY(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming), "event create");
-    HIPTRY(hipEventCreateWithFlags(&ev_out, hipEventDisableTiming), "event create");
-    if (status == LDT_OK) {
-        HIPTRY(hipEventRecord(ev_in, s), "event record");
-        HIPTRY(hipStreamWaitEvent(gs, ev_in, 0), "stream wait");
-    }
-    if (status == LDT_OK) {
-        for (int pass = 0; pass < (mon ? 2 : 1) && status == LDT_OK; ++pass) {      // pass 0: the plain step; pass 1: the monitored one
-            HIPTRY(hipStreamBeginCapture(gs, hipStreamCaptureModeThreadLocal), "begin capture");
-            if (status == LDT_OK) {
-                const int rc = enqueue_step(pass ? p : &plain, x, x_mean, eps_tmp, coef, mode, noise, noise_step_stride, elem_offset, seed, step_counter, cond, x_traj, gs);
-                const hipError_t ee = hipStreamEndCapture(gs, pass ? &graph_m : &graph);
-                if (rc != LDT_OK) status = rc;
-                else if (ee != hipSuccess) { ldt_set_error("sample_loop: end capture: %s", hipGetErrorString(ee)); status = (int)ee; }
-            }
-        }
-    }
-    if (status == LDT_OK) HIPTRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0), "graph instantiate");
-    if (status == LDT_OK && mon) HIPTRY(hipGraphInstantiate(&exec_m, graph_m, nullptr, nullptr, 0), "graph instantiate");
-    for (int i = 0; i < n_steps && status == LDT_OK; ++i) HIPTRY(hipGraphLaunch(monitored(i) ? exec_m : exec, gs), "graph launch");
-    if (gs) {
-        if (status == LDT_OK) {
-            HIPTRY(hipEventRecord(ev_out, gs), "event record");
-            HIPTRY(hipStreamWaitEvent(s, ev_out, 0), "stream wait");
-        }
-        (void)hipStreamSynchronize(gs);          // the exec must outlive its in-flight launches
-    }
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (exec_m) (void)hipGraphExecDestroy(exec_m);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (graph_m) (void)hipGraphDestroy(graph_m);
-    if (ev_in) (void)hipEventDestroy(ev_in);
-    if (ev_out) (void)hipEventDestroy(ev_out);
-    if (gs) (void)hipStreamDestroy(gs);
-#undef HIPTRY
-    return status;
+    // One step captured, replayed n_steps times.  Capture runs on a private non-blocking stream (the caller's may be the legacy default
+    // stream, which cannot be captured), fenced against the caller's stream with events on both sides.
+    StepGraphs g;
+    TRY(hip_ok(hipStreamCreateWithFlags(&g.gs, hipStreamNonBlocking), "stream create"));
+    TRY(hip_ok(hipEventCreateWithFlags(&g.ev_in, hipEventDisableTiming), "event create"));
+    TRY(hip_ok(hipEventCreateWithFlags(&g.ev_out, hipEventDisableTiming), "event create"));
+    TRY(hip_ok(hipEventRecord(g.ev_in, s), "event record"));
+    TRY(hip_ok(hipStreamWaitEvent(g.gs, g.ev_in, 0), "stream wait"));
+    TRY(capture_step(st, &plain, g.gs, &g.graph[0]));
+    if (mon) TRY(capture_step(st, p, g.gs, &g.graph[1]));
+    for (int k = 0; k < (mon ? 2 : 1); ++k) TRY(hip_ok(hipGraphInstantiate(&g.exec[k], g.graph[k], nullptr, nullptr, 0), "graph instantiate"));
+    for (int i = 0; i < n_steps; ++i) TRY(hip_ok(hipGraphLaunch(g.exec[monitored(i) ? 1 : 0], g.gs), "graph launch"));
+    TRY(hip_ok(hipEventRecord(g.ev_out, g.gs), "event record"));
+    return hip_ok(hipStreamWaitEvent(s, g.ev_out, 0), "stream wait");
 }

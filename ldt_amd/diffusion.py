@@ -7,18 +7,21 @@ constructor (`args` = cfg.sde Namespace) and `sample_discrete(...)` (:133-338).
 Schedule scalars are host-side fp32 tables computed with the reference's own op order (SURVEY hard
 part 4: var(1e-6) is exactly one ulp in fp32 and must not be recomputed with a different expf) and uploaded.
 
-`sample_discrete` has the reference signature.  Two execution paths, both on HIP kernels:
-  * fused loop — when `score_fn` is the bound `Trainer.score_fn` of an `ldt_amd.Score` (unconditional):
-    one `ldt_sample_loop` call = AdaLN table for all N steps, then N x (Score forward -> fused predictor
-    update with in-kernel Philox noise -> ++step), optionally replayed from one captured hipGraph;
-  * generic loop — any other `score_fn(t, x, label=, condition=) -> (score, params)` callable is driven
-    step by step from Python, the update still done by `ldt_sampler_step` (params, not score, feed it).
-Extra keyword-only arguments (not in the reference): `x0`, `noise` (inject the CPU draws for parity),
-`sample_offset` (global index of this rank's first sample, keeps Philox streams shard-invariant), `streams` (sub-batches
-sampled concurrently on their own HIP streams; default 1, `LDT_STREAMS=2` measured -2.6 % per step at B=64, T=256).
+`sample_discrete` has the reference signature and is a dispatcher: argument rules, `step_table`, the initial latents (`torch.randn` on the
+CPU generator, then — unless `noise` is injected — `torch.randint` for the Philox key), placement, then one of two loops on HIP kernels:
+  * `_sample_fused` — `score_fn` is the bound `Trainer.score_fn` of an `ldt_amd.Score`, no corrector / record / print_steps: `partition`
+    cuts the batch into sub-batches, a builder (`_SharedModulation`: one AdaLN table for all N steps, LN fold, probe, monitor;
+    `_PerSampleModulation`: label / condition rows via `Score.cond_args`) plans each, and `_run_jobs` issues one `ldt_sample_loop` per
+    `_Job` = N x (Score forward -> predictor update with in-kernel Philox noise -> ++step), optionally replayed from a captured hipGraph;
+  * `_sample_generic` — any other `score_fn(t, x, label=, condition=) -> (score, params)`, driven step by step from Python on the device
+    its tensors live on; updates by `ldt_sampler_step` (params, not score, feed it), the corrector chosen once (`_corrector`).
+The partition rule and the draw schedule are held by tests/test_sampler_schedule_host.py.  Extra keyword-only arguments (not in the
+reference): `x0`, `noise` (inject the CPU draws for parity), `sample_offset` (global index of this rank's first sample, keeps Philox
+streams shard-invariant), `streams` (sub-batches sampled concurrently on their own HIP streams; default `LDT_STREAMS` or 1).
 """
 import ctypes
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -30,6 +33,125 @@ PREDICTORS = ("reversediffusion", "ancestral", "eulermaruyama", "ddim")
 # iw_sample_mode names of DiffusionBase.iw_quantities (diffusion_continuous.py:362-417); the second tuple draws t uniformly
 IW_MODES = ("ll_uniform", "ll_iw", "drop_all_uniform", "drop_all_iw", "drop_sigma2t_iw", "drop_sigma2t_uniform", "rescale_iw")
 _IW_UNIFORM_T = ("ll_uniform", "drop_all_uniform", "drop_sigma2t_uniform", "rescale_iw")
+
+
+# ---- environment switches of the fused loop, each read once per call, where no keyword decides
+def _env_streams():                     # sub-batches on concurrent streams; opt-in, so that per-kernel accounting (bench roofline, rocprof)
+    return int(os.environ.get("LDT_STREAMS", "1"))                                    # stays one launch = the whole batch
+
+
+def _env_adaln_bf16():                  # per-sample AdaLN rows from the bf16 weight panel; 0 keeps the fp32 SGEMM (Score.stacked_adaln_bf16)
+    return bool(int(os.environ.get("LDT_ADALN_BF16", "1")))
+
+
+def _env_fold_monitor_every():          # the in-loop LN-fold monitor runs every so many steps and on the last one (default 50: 47 launches
+    return int(os.environ.get("LDT_FOLD_MONITOR_EVERY", "50"))                        # of ~5 us per monitored step = 0.05 % of a call)
+
+
+# ---- set-up every sampler shares
+def _cuda_device(device, who):
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("%s: device %s — the HIP path has no CPU fallback" % (who, device))
+    return dev
+
+
+def _initial_latents(num_samples, shape, given, dev=None):
+    """The initial sample: a CPU-generator draw like the reference (:237) unless `given`; with `dev`, a private fp32 copy placed there."""
+    x = torch.randn((num_samples,) + tuple(shape)) if given is None else given
+    return x if dev is None else x.to(dev, torch.float32).contiguous().clone()
+
+
+# ---- sub-batches of the fused loop
+SubBatch = namedtuple("SubBatch", "lo hi slot gemm_wgs elem_offset")
+_Job = namedtuple("_Job", "plan cond x x_mean eps_tmp counter noise elem_offset traj")       # one ldt_sample_loop call
+
+
+def partition(B, streams, per_sample, elem_offset):
+    """`streams` (clamped to [1, B]) row ranges [lo, hi) = [B i // streams, B (i + 1) // streams) of a batch of B, each with its workspace
+    slot i, the persistent-grid cap of its GEMMs (0 = the whole chip for one stream, else its share of the 256 CUs) and the Philox
+    element offset of its first row, so that the draws do not depend on the split (tests/test_sampler_schedule_host.py)."""
+    streams = max(1, min(int(streams), B))
+    bounds = [B * i // streams for i in range(streams + 1)]
+    return [SubBatch(lo, hi, i, 0 if streams == 1 else max(256 // streams, 1), elem_offset + lo * per_sample)
+            for i, (lo, hi) in enumerate(zip(bounds, bounds[1:]))]
+
+
+class _SharedModulation:
+    """Plans of an unconditional batch: AdaLN rows for every step, shared by the batch, and — where a route exists — the LN-fold table,
+    guarded by a probe before the loop and a monitor inside it.  `monitor`: the running max of mean^2 / variance over the monitored
+    steps (a device scalar), or None when nothing folds."""
+    def __init__(self, model, ts_d, T):
+        self.model, self.T, self.fold, self.monitor, self.every = model, T, None, None, _env_fold_monitor_every()
+        self.mod = model.time_table(ts_d)[1]
+
+    def build(self, sb, xs):
+        model, Bs = self.model, sb.hi - sb.lo
+        if self.fold is None and model.can_fold(Bs, self.T, sb.gemm_wgs):
+            self.fold = model.fold_table(self.mod)                                    # (+ the LN-folding S / C rows)
+            # guard: a monitored forward on the first sub-batch at step 0 (0.1 % of a 1000-step call); rows whose
+            # mean dwarfs their spread switch this model to the LayerNorm kernels (Score.fold_probe)
+            model.fold_probe(xs, 0, self.mod, self.fold)
+        folding = model.can_fold(Bs, self.T, sb.gemm_wgs)                             # (the probe may just have switched it off)
+        if folding and self.monitor is None:
+            self.monitor = torch.zeros(1, dtype=torch.float32, device=xs.device)
+        # inside the loop the same monitor runs every LDT_FOLD_MONITOR_EVERY steps and on the last step; the running maximum is read at the
+        # NEXT call's first can_fold() (a trajectory that passes the bound mid-way is seen, not just its two ends)
+        return model.plan(Bs, self.T, self.mod, model.n_mod, 0, fold=self.fold if folding else None, slot=sb.slot, gemm_wgs=sb.gemm_wgs,
+                          monitor=self.monitor if folding else None, monitor_every=self.every), None
+
+
+class _PerSampleModulation:
+    """Plans of a labelled / conditioned batch: per-sample AdaLN rows, rebuilt every step inside the loop from the time embedding of all
+    steps plus each sample's label / image embedding (`Score.cond_args`); a point condition adds the cross-attention K|V rows."""
+    def __init__(self, model, ts_d, T, label, condition):
+        self.model, self.T, self.monitor = model, T, None                             # (no LN fold with per-sample rows: nothing to monitor)
+        self.extra, self.kv, self.S = model.condition_embedding(label, condition)
+        self.temb, self.weights = model.time_embedding(ts_d), model.adaln_stack(_env_adaln_bf16())
+
+    def build(self, sb, xs):
+        model, (lo, hi), Bs, S = self.model, sb[:2], sb.hi - sb.lo, self.S
+        modb = torch.empty((Bs, model.n_mod), dtype=torch.float32, device=xs.device)
+        ex = None if self.extra is None else self.extra[lo:hi].contiguous()
+        kvs = None if self.kv is None else {l: t.view(-1, S, t.shape[-1])[lo:hi].reshape(Bs * S, -1) for l, t in self.kv.items()}
+        plan = model.plan(Bs, self.T, modb, 0, model.n_mod, kv_cond=kvs, cond_tokens=S, slot=sb.slot, gemm_wgs=sb.gemm_wgs)
+        return plan, model.cond_args(self.weights, self.temb, ex, modb)
+
+
+def _run_jobs(jobs, launch, dev, sync):
+    """`launch(job)` for every sub-batch: one inline on the caller's stream; several each on a stream and a thread of its own, fenced
+    against the caller's stream on both sides, the first error handed back.  `sync`: the caller's scratch must outlive the loop.
+    Why concurrent streams (trajectories are independent): with the persistent GEMM grids capped at half the chip each, one stream's
+    HBM-bound phases (epilogues, attention) run beside the other's MFMA-bound main loops instead of all 256 CUs alternating between the
+    two (measured -2.6 % per SDE step at B=64, T=256; a deliberate phase skew between the streams gained nothing, four quarter batches
+    lose: too few tiles).  Only where a half batch still fills its half of the chip with whole 256x256 tiles."""
+    main = torch.cuda.current_stream()
+    if len(jobs) == 1:
+        launch(jobs[0])
+    else:
+        import threading
+        subs, errs = [torch.cuda.Stream(device=dev) for _ in jobs], []
+
+        def worker(job, st):
+            try:
+                torch.cuda.set_device(dev)
+                st.wait_stream(main)                                                  # tables / x0 were produced on the caller's stream
+                with torch.cuda.stream(st):
+                    launch(job)
+            except BaseException as e:                                                # noqa: BLE001 - re-raised on the caller's thread
+                errs.append(e)
+
+        th = [threading.Thread(target=worker, args=(j, st)) for j, st in zip(jobs, subs)]
+        for t_ in th:
+            t_.start()
+        for t_ in th:
+            t_.join()                                                                 # (ctypes releases the GIL inside the C call)
+        if errs:
+            raise errs[0]
+        for st in subs:
+            main.wait_stream(st)
+    if sync or len(jobs) > 1:
+        main.synchronize()                                                            # scratch / sub-streams must outlive the loop
 
 
 def make_diffusion(args):
@@ -237,21 +359,14 @@ class DiffusionBase:
             coef = torch.stack([beta, self.std(ts), torch.sqrt(1. - beta), torch.sqrt(beta)], 1)
             return ts, coef.contiguous(), 0
         std = self.std(ts).double()
-        if predictor == "reversediffusion":                                 # :141-150
-            dt = (1 - time_eps) / N
+        if predictor in ("reversediffusion", "eulermaruyama"):              # :141-150 (dt = (1 - time_eps) / N), :182-191 (dt = -1 / N)
+            h = ((1 - time_eps) if predictor == "reversediffusion" else 1.0) / N   # |dt|: negation is exact, so one form serves both signs
             g2 = self.g2(ts).double(); ff = self.f(ts).double()     # fp32 like upstream, then folded in fp64
             k = 0.5 if probability_flow else 1.0
-            A = 1 - ff * dt
-            Bc = -g2 * k * dt / std                # x_mean = x - (f x - g2 k score) dt, score = -params/std
-            Cc = torch.zeros_like(g2) if probability_flow else torch.sqrt(g2) * np.sqrt(dt)
-        elif predictor == "eulermaruyama":                                  # :182-191
-            dt = -1.0 / N
-            g2 = self.g2(ts).double(); ff = self.f(ts).double()     # fp32 like upstream, then folded in fp64
-            k = 0.5 if probability_flow else 1.0
-            A = 1 + ff * dt
-            Bc = g2 * k * dt / std
-            Cc = torch.zeros_like(g2) if probability_flow else torch.sqrt(g2) * np.sqrt(-dt)
-        else:                                                               # ddim :164-180 (sigma = 0)
+            A = 1 - ff * h
+            Bc = -g2 * k * h / std                 # x_mean = x - (f x - g2 k score) dt, score = -params/std
+            Cc = torch.zeros_like(g2) if probability_flow else torch.sqrt(g2) * np.sqrt(h)
+        else:                                                              # ddim :164-180 (sigma = 0)
             idx = (ts * (N - 1) / 1.0).long()
             at = self.alphas_cump[idx].double()
             at_next = torch.where(idx - 1 < 0, torch.ones_like(at), self.alphas_cump[(idx - 1).clamp_min(0)].double())
@@ -281,14 +396,12 @@ class DiffusionBase:
         import time
         if solver not in ("scipy", "device"):
             raise ValueError("sample_model_ode: solver=%r (\"scipy\" or \"device\")" % (solver,))
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("sample_model_ode: device %s — the HIP path has no CPU fallback" % (device,))
+        dev = _cuda_device(device, "sample_model_ode")
         if solver == "device":
             return self._sample_model_ode_device(score_fn, num_samples, shape, ode_eps, ode_solver_tol, noise, condition, label, dev,
                                                  shared_t)
         from scipy.integrate import solve_ivp
-        x0 = torch.randn((num_samples,) + tuple(shape)) if noise is None else noise
+        x0 = _initial_latents(num_samples, shape, noise)
         full = tuple(x0.shape)
         nfe = [0]
 
@@ -325,7 +438,7 @@ class DiffusionBase:
         `self.last_ode` keeps {"accepted", "rejected", "t", "route"} of the last call."""
         import time
         from . import ode
-        x0 = torch.randn((num_samples,) + tuple(shape)) if noise is None else noise
+        x0 = _initial_latents(num_samples, shape, noise)
         full = tuple(x0.shape)
         B = full[0]
         model = _fused_model(score_fn)
@@ -387,143 +500,84 @@ class DiffusionBase:
         if predictor == "pndm":
             return self._sample_pndm(score_fn, num_samples, shape, time_eps, device, condition, label, x0)
         ts, coef, mode = self.step_table(N, predictor, time_eps, probability_flow)
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("sample_discrete: device %s — the HIP path has no CPU fallback" % (device,))
-        # initial sample: CPU generator then copy, exactly like the reference (:237)
-        x = torch.randn((num_samples,) + tuple(shape)) if x0 is None else x0
-        x = x.to(dev, torch.float32).contiguous().clone()
+        dev = _cuda_device(device, "sample_discrete")
+        x = _initial_latents(num_samples, shape, x0, dev)      # drawn before the seed: the order on the CPU generator is part of the contract
         if seed is None:                                       # Philox key from the (seedable) CPU generator; not drawn (the
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if noise is None else 0   # reference's stream is kept) when noise is injected
         ncs = corrector_steps if corrector is not None else 0  # noise draws per step: 1 predictor + ncs corrector
         if noise is not None:
             noise = noise.to(dev, torch.float32).contiguous()
             assert noise.shape == (N * (1 + ncs),) + tuple(x.shape), "noise must be [N*(1+corrector_steps), B, tokens, z]"
-        coef_d = coef.to(dev)
-        elem_offset = int(sample_offset) * int(np.prod(shape))
-        nstride = x.numel() if noise is not None else 0
-        x_mean = torch.empty_like(x)
+        run = dict(ts=ts, coef=coef.to(dev), mode=mode, noise=noise, elem_offset=int(sample_offset) * int(np.prod(shape)), seed=seed,
+                   denoise=denoise, condition=condition, label=label, trajectory=trajectory)
         model = _fused_model(score_fn)
         if model is not None and record is None and corrector is None and print_steps is None:
-            from ._lib import CondArgs
-            B, T = x.shape[0], x.shape[1]
-            if use_graph is None:
-                use_graph = B * T <= 4096                                             # launch-bound regime only
-            # Sub-batches on concurrent streams (trajectories are independent): with the persistent GEMM grids capped at
-            # half the chip each, one stream's HBM-bound phases (epilogues, attention) run beside the other's MFMA-bound
-            # main loops instead of all 256 CUs alternating between the two (measured -2.6 % per SDE step at B=64, T=256;
-            # a deliberate phase skew between the streams gained nothing, four quarter batches lose: too few tiles).  Only
-            # where a half batch still fills its half of the chip with whole 256x256 tiles.
-            if streams is None:                                                       # opt-in: per-kernel accounting (bench roofline,
-                streams = int(os.environ.get("LDT_STREAMS", "1"))                     # rocprof) stays one launch = the whole batch
-            streams = max(1, min(int(streams), B))
-            shared = condition is None and label is None
-            if shared:
-                _, mod = model.time_table(ts.to(dev))                                 # AdaLN rows for every step, shared by the batch
-            else:
-                extra, kv, S = model.condition_embedding(label, condition)            # per-sample rows, rebuilt every step
-                temb = model.time_embedding(ts.to(dev))
-                panel = model.stacked_adaln_bf16() if int(os.environ.get("LDT_ADALN_BF16", "1")) else None
-                if panel is not None:                                                 # bf16 weight panel (t_dim % 64 == 0); no fp32 copy kept
-                    (w_ada_bf, b_ada), w_ada = panel, None
-                else:
-                    (w_ada, b_ada), w_ada_bf = model.stacked_adaln(), None
-            bounds = [B * i // streams for i in range(streams + 1)]
-            jobs, keep = [], []
-            fold = None
-            fold_mon = None                                                           # running max of mean^2 / variance over the monitored steps
-            for i in range(streams):
-                lo, hi = bounds[i], bounds[i + 1]
-                Bs = hi - lo
-                xs, xm = x[lo:hi], x_mean[lo:hi]                                      # contiguous row slices, updated in place
-                eps_tmp = torch.empty_like(xs)
-                tj = None if trajectory is None else torch.empty((N,) + tuple(xs.shape), dtype=torch.float32, device=dev)
-                counter = torch.zeros(1, dtype=torch.int32, device=dev)
-                nz = None if noise is None else noise[:, lo:hi]
-                wgs = 0 if streams == 1 else max(256 // streams, 1)
-                cond_ref = None
-                if shared:
-                    if fold is None and model.can_fold(Bs, T, wgs):
-                        fold = model.fold_table(mod)                                  # (+ the LN-folding S / C rows)
-                        # guard: a monitored forward on the first sub-batch at step 0 (0.1 % of a 1000-step call); rows whose
-                        # mean dwarfs their spread switch this model to the LayerNorm kernels (Score.fold_probe)
-                        model.fold_probe(xs, 0, mod, fold)
-                    folding = model.can_fold(Bs, T, wgs)                              # (the probe may just have switched it off)
-                    if folding and fold_mon is None:
-                        fold_mon = torch.zeros(1, dtype=torch.float32, device=dev)
-                    # inside the loop the same monitor runs every LDT_FOLD_MONITOR_EVERY steps (default 50: 47 launches of ~5 us per monitored
-                    # step = 0.05 % of a call) and on the last step; the running maximum is read at the NEXT call's first can_fold() (round 6: a trajectory
-                    # that passes the bound mid-way is seen, not just its two ends)
-                    plan = model.plan(Bs, T, mod, model.n_mod, 0, fold=fold if folding else None, slot=i, gemm_wgs=wgs,
-                                      monitor=fold_mon if folding else None, monitor_every=int(os.environ.get("LDT_FOLD_MONITOR_EVERY", "50")))
-                else:
-                    c_buf = torch.empty((Bs, model.t_dim), dtype=torch.float32, device=dev)
-                    modb = torch.empty((Bs, model.n_mod), dtype=torch.float32, device=dev)
-                    ex = None if extra is None else extra[lo:hi].contiguous()
-                    kvs = None if kv is None else {l: t.view(B, S, -1)[lo:hi].reshape(Bs * S, -1) for l, t in kv.items()}
-                    plan = model.plan(Bs, T, modb, 0, model.n_mod, kv_cond=kvs, cond_tokens=S, slot=i, gemm_wgs=wgs)
-                    c_bf = None if w_ada_bf is None else torch.empty((Bs, model.t_dim), dtype=torch.bfloat16, device=dev)
-                    cond = CondArgs(temb.data_ptr(), ops._p(ex), ops._p(w_ada), b_ada.data_ptr(), c_buf.data_ptr(),
-                                    modb.data_ptr(), model.t_dim, model.n_mod, ops._p(w_ada_bf), ops._p(c_bf))
-                    cond_ref = ctypes.byref(cond)
-                    keep.append((ex, kvs, c_buf, modb, cond, c_bf, w_ada_bf, w_ada, b_ada))
-                if nz is not None and streams > 1:
-                    nz = nz.contiguous()                                              # [N, Bs, T, z] with step stride Bs*T*z
-                jobs.append((plan, xs, xm, eps_tmp, counter, nz, cond_ref, elem_offset + lo * int(np.prod(shape)), tj))
+            return self._sample_fused(model, x, use_graph=use_graph, streams=streams, **run)
+        return self._sample_generic(score_fn, x, corrector=corrector, ncs=ncs, snr=snr, global_batch=gb, sharded=global_batch is not None,
+                                    n_valid=max(0, min(num_samples, gb - int(sample_offset))), print_steps=print_steps, record=record, **run)
 
-            def run(job, stream):
-                plan, xs, xm, eps_tmp, counter, nz, cond_ref, off, tj = job
-                with torch.cuda.stream(stream):
-                    check(lib().ldt_sample_loop(ctypes.byref(plan), xs.data_ptr(), xm.data_ptr(), eps_tmp.data_ptr(),
-                                                coef_d.data_ptr(), mode, ops._p(nz), xs.numel() if nz is not None else 0, off, seed,
-                                                counter.data_ptr(), N, cond_ref, ops._p(tj), int(bool(use_graph)), ops.stream_ptr()),
-                          "ldt_sample_loop")
+    def _sample_fused(self, model, x, *, ts, coef, mode, noise, elem_offset, seed, denoise, condition, label, trajectory, use_graph, streams):
+        """The fused loop over `x` (placed, fp32, updated in place): one `ldt_sample_loop` call per sub-batch.  -> x_mean if `denoise` else x."""
+        dev, N, (B, T) = x.device, ts.numel(), x.shape[:2]
+        if use_graph is None:
+            use_graph = B * T <= 4096                                                 # launch-bound regime only
+        parts = partition(B, _env_streams() if streams is None else streams, int(np.prod(x.shape[1:])), elem_offset)
+        shared = condition is None and label is None
+        plans = _SharedModulation(model, ts.to(dev), T) if shared else _PerSampleModulation(model, ts.to(dev), T, label, condition)
+        x_mean, jobs = torch.empty_like(x), []
+        for sb in parts:
+            xs = x[sb.lo:sb.hi]                                                       # contiguous row slices, updated in place
+            eps_tmp = torch.empty_like(xs)
+            tj = None if trajectory is None else torch.empty((N,) + tuple(xs.shape), dtype=torch.float32, device=dev)
+            counter = torch.zeros(1, dtype=torch.int32, device=dev)
+            plan, cond = plans.build(sb, xs)
+            nz = None if noise is None else noise[:, sb.lo:sb.hi]
+            if nz is not None and len(parts) > 1:
+                nz = nz.contiguous()                                                  # [N, Bs, T, z] with step stride Bs*T*z
+            jobs.append(_Job(plan, cond, xs, x_mean[sb.lo:sb.hi], eps_tmp, counter, nz, sb.elem_offset, tj))
 
-            main = torch.cuda.current_stream()
-            if streams == 1:
-                run(jobs[0], main)
-            else:
-                import threading
-                subs = [torch.cuda.Stream(device=dev) for _ in jobs]
-                errs = []
+        def launch(job):                                                              # (on the current stream)
+            check(lib().ldt_sample_loop(ctypes.byref(job.plan), job.x.data_ptr(), job.x_mean.data_ptr(), job.eps_tmp.data_ptr(),
+                                        coef.data_ptr(), mode, ops._p(job.noise), job.x.numel() if job.noise is not None else 0,
+                                        job.elem_offset, seed, job.counter.data_ptr(), N, None if job.cond is None else ctypes.byref(job.cond),
+                                        ops._p(job.traj), int(bool(use_graph)), ops.stream_ptr()), "ldt_sample_loop")
+        _run_jobs(jobs, launch, dev, sync=not shared)                                 # per-sample scratch must outlive the loop
+        if trajectory is not None:
+            trajectory.append(torch.cat([j.traj for j in jobs], 1))
+        if plans.monitor is not None:
+            model.defer_fold_ratio(plans.monitor)                                     # read (a device sync) at the next can_fold(): affects later calls
+        return x_mean if denoise else x
 
-                def worker(job, st):
-                    try:
-                        torch.cuda.set_device(dev)
-                        st.wait_stream(main)                                          # tables / x0 were produced on the caller's stream
-                        run(job, st)
-                    except BaseException as e:                                        # noqa: BLE001 - re-raised on the caller's thread
-                        errs.append(e)
-
-                th = [threading.Thread(target=worker, args=(j, st)) for j, st in zip(jobs, subs)]
-                for t_ in th:
-                    t_.start()
-                for t_ in th:
-                    t_.join()                                                         # (ctypes releases the GIL inside the C call)
-                if errs:
-                    raise errs[0]
-                for st in subs:
-                    main.wait_stream(st)
-            if keep or streams > 1:
-                main.synchronize()                                                    # scratch / sub-streams must outlive the loop
-            if trajectory is not None:
-                trajectory.append(torch.cat([j[-1] for j in jobs], 1))
-            if fold_mon is not None:
-                model.defer_fold_ratio(fold_mon)                                      # read (a device sync) at the next can_fold(): affects later calls
-            return x_mean if denoise else x
-        # ---- generic loop: any score_fn, correctors, trajectory dumps; every update is still one HIP kernel ----
-        ts_d = ts.to(dev)
-        if corrector == "ancestral":                           # folded AncestralCorrector: x_mean = x - 2 snr^2 std params,
+    def _corrector(self, corrector, ncs, x, x_mean, ts, snr, noise, elem_offset, seed, global_batch, n_valid, sharded):
+        """The update of corrector step j of predictor step i as `(x, params, i, j) -> x`; its draw is noise row / Philox stream
+        i (1 + ncs) + 1 + j."""
+        dev = x.device
+        if corrector == "ancestral":                           # AncestralCorrector :212-229, folded: x_mean = x - 2 snr^2 std params,
             std = self.std(ts).double()                        # x = x_mean + 2 snr std z   (score = -params / std)
             ccoef = torch.stack([torch.ones_like(std), -2.0 * snr * snr * std, 2.0 * snr * std, torch.zeros_like(std)], 1)
             ccoef_d = ccoef.float().contiguous().to(dev)
-        elif corrector == "langevin":                          # step size from batch-mean norms, formed on the device per draw
-            std_host = self.std(ts)
-            lv_coef = torch.empty(4, dtype=torch.float32, device=dev)
-            lv_sums = torch.empty(2, dtype=torch.float32, device=dev)
-            lv_norms = torch.empty(num_samples, dtype=torch.float32, device=dev)
-            per = int(np.prod(shape))
-            n_valid = max(0, min(num_samples, gb - int(sample_offset)))
+            return lambda x, params, i, j: ops.sampler_step(
+                x, params, ccoef_d, i, 1, noise=None if noise is None else noise[i * (1 + ncs) + 1 + j], x_mean_out=x_mean,
+                elem_offset=elem_offset, seed=seed, philox_mul=1 + ncs, philox_add=1 + j)
+        if corrector == "langevin":                            # LangevinCorrector :193-210: step size from batch-mean norms, formed on
+            std_host = self.std(ts)                            # the device per draw
+            scratch = tuple(torch.empty(n, dtype=torch.float32, device=dev) for n in (4, 2, x.shape[0]))   # coef, sums, norms
+
+            def langevin(x, params, i, j):
+                k = i * (1 + ncs) + 1 + j
+                z = noise[k] if noise is not None else ops.philox_normal(x.shape, dev, seed, step=k, elem_offset=elem_offset)
+                return langevin_update(x, params, z, x_mean, float(std_host[i]), snr, global_batch, n_valid, sharded, scratch)
+            return langevin
+
+    def _sample_generic(self, score_fn, x, *, ts, coef, mode, noise, elem_offset, seed, denoise, condition, label, trajectory, corrector, ncs,
+                        snr, global_batch, n_valid, sharded, print_steps, record):
+        """The generic loop: any score_fn, correctors, trajectory dumps; every update is still one HIP kernel, on whatever device `x`
+        (placed, fp32) lives.  Draw schedule: predictor step i uses noise row / Philox stream k = i (1 + ncs), its corrector steps the
+        ncs after it (tests/test_sampler_schedule_host.py)."""
+        dev, N, num_samples = x.device, ts.numel(), x.shape[0]
+        ts_d = ts.to(dev)
+        x_mean = torch.empty_like(x)
+        correct = self._corrector(corrector, ncs, x, x_mean, ts, snr, noise, elem_offset, seed, global_batch, n_valid, sharded)
         out_list, every = None, None
         traj_list = [] if trajectory is not None else None
         if print_steps is not None:
@@ -533,23 +587,13 @@ class DiffusionBase:
             vec_t = torch.ones((num_samples,), device=dev) * ts_d[i]                 # :243-244
             params = params_of(vec_t, x, label=label, condition=condition)
             k = i * (1 + ncs)                                  # index of this step's first draw (noise row / Philox stream id)
-            x_new = ops.sampler_step(x, params.contiguous(), coef_d, i, mode, noise=None if noise is None else noise[k],
+            x_new = ops.sampler_step(x, params.contiguous(), coef, i, mode, noise=None if noise is None else noise[k],
                                      x_mean_out=x_mean, elem_offset=elem_offset, seed=seed, philox_mul=1 + ncs)
             if record is not None:
                 record.append((x, params, x_mean.clone(), x_new))
             x = x_new
             for j in range(ncs):
-                params = params_of(vec_t, x, label=label, condition=condition).contiguous()
-                if corrector == "ancestral":                                         # AncestralCorrector :212-229
-                    x = ops.sampler_step(x, params, ccoef_d, i, 1, noise=None if noise is None else noise[k + 1 + j],
-                                         x_mean_out=x_mean, elem_offset=elem_offset, seed=seed, philox_mul=1 + ncs,
-                                         philox_add=1 + j)
-                    continue
-                # LangevinCorrector :193-210
-                z = noise[k + 1 + j] if noise is not None else \
-                    ops.philox_normal(x.shape, dev, seed, step=i * (1 + ncs) + 1 + j, elem_offset=elem_offset)
-                x = langevin_update(x, params, z, x_mean, float(std_host[i]), snr, gb, n_valid, global_batch is not None,
-                                    (lv_coef, lv_sums, lv_norms))
+                x = correct(x, params_of(vec_t, x, label=label, condition=condition).contiguous(), i, j)
             if traj_list is not None:
                 traj_list.append(x.clone())
             if out_list is not None and (i + 1) % every == 0:
@@ -561,7 +605,6 @@ class DiffusionBase:
             return out_list
         return x_mean if denoise else x
 
-
     @torch.no_grad()
     def _sample_pndm(self, score_fn, num_samples, shape, time_eps, device, condition, label, x0):
         """PNDM (diffusion_continuous.py:260-316) around the HIP Score: the pseudo linear multistep sampler with three
@@ -569,11 +612,9 @@ class DiffusionBase:
         sample sits at the same t, so the (B,1) schedule factors of transfer() (:267-271) are three scalars per call,
         formed here in fp32 exactly as upstream; the element-wise updates are HIP kernels.  Index quirk kept: at the last
         step `timesteps[t_next*2 - 1]` with t_next = 0 reads timesteps[-1] = 1.0 (:307)."""
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("sample_discrete: device %s — the HIP path has no CPU fallback" % (device,))
+        dev = _cuda_device(device, "sample_discrete")
         N, train_N = self.N, self.train_N
-        x = (torch.randn((num_samples,) + tuple(shape)) if x0 is None else x0).to(dev, torch.float32).contiguous().clone()
+        x = _initial_latents(num_samples, shape, x0, dev)
         betas = torch.from_numpy(np.linspace(self.beta_start / train_N, self.beta_end / train_N, train_N,
                                              dtype=np.float64)).to(torch.float32)                    # :310-313
         alphas_cump = torch.cat((torch.ones(1), (1.0 - betas).cumprod(dim=0)))                     # :314-315 (train_N + 1)

@@ -210,18 +210,14 @@ def sampler_step(x, params, coef, step, mode=0, noise=None, noise_step_stride=0,
     _need(noise, torch.float32, "noise"); _need(traj, torch.float32, "traj")
     if x_out is None:
         x_out = torch.empty_like(x)
-    if traj is None:
-        check(lib().ldt_sampler_step(_p(x), _p(params), _p(noise), noise_step_stride, _p(x_out), _p(x_mean_out), _p(coef),
-                                     _p(step_ptr), int(step), mode, x.numel(), elem_offset, seed, philox_mul, philox_add,
-                                     stream_ptr()),
-              "ldt_sampler_step")
-        return x_out
-    if traj.dim() != 2 or traj.shape[1] != x.numel() or not traj.is_contiguous():
+    if traj is not None and (traj.dim() != 2 or traj.shape[1] != x.numel() or not traj.is_contiguous()):
         raise ValueError("sampler_step: traj must be a contiguous fp32 [n_steps, %d] tensor, got %s" % (x.numel(), tuple(traj.shape)))
-    check(lib().ldt_sampler_step_traj(_p(x), _p(params), _p(noise), noise_step_stride, _p(x_out), _p(x_mean_out), _p(traj), _p(coef),
-                                      _p(step_ptr), int(step), mode, x.numel(), elem_offset, seed, philox_mul, philox_add,
-                                      stream_ptr()),
-          "ldt_sampler_step_traj")
+    head = (_p(x), _p(params), _p(noise), noise_step_stride, _p(x_out), _p(x_mean_out))
+    tail = (_p(coef), _p(step_ptr), int(step), mode, x.numel(), elem_offset, seed, philox_mul, philox_add, stream_ptr())
+    if traj is None:                                            # the two entry points differ by the traj operand alone
+        check(lib().ldt_sampler_step(*head, *tail), "ldt_sampler_step")
+    else:
+        check(lib().ldt_sampler_step_traj(*head, _p(traj), *tail), "ldt_sampler_step_traj")
     return x_out
 
 

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import ACT_NONE, ACT_SILU, EPI_F32, MAX_BLOCKS, ScorePlan, check, lib
+from ._lib import ACT_NONE, ACT_SILU, EPI_F32, MAX_BLOCKS, CondArgs, ScorePlan, check, lib
 from .blocks import final_layer, pack_block, pack_final, residual_block
 from .layers import FinalLayer, LabelEmbedding, ResidualBlock, TimeEmbedding, conv_w, params_fingerprint
 
@@ -275,6 +275,26 @@ class Score(nn.Module):
                 p.fold_monitor_every = int(monitor_every)               # ldt_sample_loop: monitored steps (0 = every step)
         p._keep = (P, W, mod, kv_cond, fold, monitor)   # keep the buffers alive as long as the plan
         return p
+
+    def adaln_stack(self, bf16=True):
+        """The stacked adaLN weights as `cond_args` takes them: the bf16 panel where `bf16` and the width allow it (t_dim % 64 == 0; no
+        fp32 copy is kept then), else the fp32 stack."""
+        panel = self.stacked_adaln_bf16() if bf16 else None
+        return (None, panel[1], panel[0]) if panel is not None else self.stacked_adaln() + (None,)
+
+    def cond_args(self, stack, temb, extra, mod_buf):
+        """ctypes `ldt_cond_args` of one (sub-)batch of the conditioned sampling loop, which rebuilds the per-sample AdaLN rows every step:
+        mod_buf [B, n_mod] = adaLN(SiLU(temb[step] + extra)), the buffer the batch's `plan(B, T, mod_buf, 0, n_mod, ...)` reads.
+        stack: `adaln_stack()`; temb: `time_embedding` of every step; extra: [B, t_dim] or None.  The SiLU scratch rows are allocated
+        here and kept alive, with every operand, as long as the struct."""
+        w_ada, b_ada, w_ada_bf = stack
+        B = mod_buf.shape[0]
+        c_buf = torch.empty((B, self.t_dim), dtype=torch.float32, device=mod_buf.device)
+        c_bf = None if w_ada_bf is None else torch.empty((B, self.t_dim), dtype=torch.bfloat16, device=mod_buf.device)
+        cond = CondArgs(temb.data_ptr(), ops._p(extra), ops._p(w_ada), b_ada.data_ptr(), c_buf.data_ptr(), mod_buf.data_ptr(),
+                        self.t_dim, self.n_mod, ops._p(w_ada_bf), ops._p(c_bf))
+        cond._keep = (stack, temb, extra, mod_buf, c_buf, c_bf)
+        return cond
 
     # ------------------------------------------------------------------ AdaLN tables
     def _frequencies(self):
