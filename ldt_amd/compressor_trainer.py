@@ -16,17 +16,15 @@ Compressor step is out of scope: `update` / `compute_loss` raise — the grouper
 `compute_loss` adds `EMD_loss`, which goes through the auction-EMD CUDA extension of evaluation/emd.py that this package does not have
 (and does not imitate).
 
-The encode, the decode, Chamfer / EMD and the KL terms run in HIP kernels (Compressor.forward, ldt_amd.metrics); what is plain torch
-here is bookkeeping on finished clouds: concatenation, the loaders' shift / scale de-normalisation and the category filter.
+The encode, the decode, Chamfer / EMD and the KL terms run in HIP kernels (Compressor.forward, ldt_amd.metrics); the bookkeeping on
+finished clouds — concatenation, the loaders' shift / scale de-normalisation, the category filter, report and dump — is ldt_amd/evalloop.py's,
+shared with the two Score trainers.
 """
-import math
 import os
-import time
 
-import numpy as np
 import torch
 
-from . import ops
+from . import evalloop, ops
 from .metrics import F1Score, L2_ChamferEval_1000, compute_all_metrics
 
 
@@ -53,11 +51,7 @@ class CompressorTrainer:
     last_eps_grad = None                                             # d loss / d eps of the last update_decoder
 
     def warm_up(self, optimizer, itr):
-        """trainer/base.py's linear learning-rate warm-up, as Trainer.warm_up."""
-        if itr < self.cfg.opt.warmup_iters:
-            lr = self.cfg.opt.lr * min(float(itr + 1) / max(self.cfg.opt.warmup_iters, 1), 1.0)
-            for param_group in optimizer.param_groups:
-                param_group["lr"] = lr
+        evalloop.warm_up(self.cfg, optimizer, itr)
 
     # ---- what the three update_* steps share ------------------------------------------------------------------
     def _points(self, who, data):
@@ -245,84 +239,34 @@ class CompressorTrainer:
     def valsample(self, test_loader, sample_points, vis=False):
         """:61-100 — one prior sample per test shape (latents ~ N(0, 1)), the "Sample rate" print, `smp_ep<epoch>.npy` into
         cfg.log.save_path (when one is set), `compute_all_metrics(smp, ref)` and the `{"val/gen/<key>": float}` dict."""
-        if vis:
-            raise NotImplementedError("valsample(vis=True): mitsuba rendering (tools/vis_utils.py) is not on this path")
+        evalloop.refuse_vis("valsample", vis)
         self.model.eval()
-        all_ref, all_smp, use_time = [], [], 0.
-        for data in test_loader:
-            ref_pts = data["te_points"].to(self.device)
-            torch.cuda.synchronize()
-            t0 = time.time()
-            smp = self.sample(num_samples=data["tr_points"].size(0), num_points=sample_points)
-            torch.cuda.synchronize()
-            use_time += time.time() - t0
-            all_smp.append(smp)
-            all_ref.append(ref_pts)
-        smp, ref = torch.cat(all_smp, dim=0), torch.cat(all_ref, dim=0).float()
+        ref, sizes, _ = evalloop.collect_refs(test_loader, self.device, "valsample")
+        smp, use_time = evalloop.sample_clouds(lambda num_samples: self.sample(num_samples=num_samples, num_points=sample_points),
+                                               sizes, self.device)
         print("Sample rate: %.8f " % (smp.shape[0] / max(use_time, 1e-9)))
-        self._save("smp", smp)
-        return self._report(compute_all_metrics(smp, ref, batch_size=128))
+        evalloop.dump(self.cfg, "smp_ep%d.npy" % self.epoch, smp)
+        return evalloop.report(self.epoch, compute_all_metrics(smp, ref, batch_size=128))
 
     # ---- reconstruction ----------------------------------------------------------------------------------------
     @torch.no_grad()
     def reconstrustion(self, test_loader, val_cate=0):
-        """:102-161 — encode and reconstruct the test shapes, de-normalise references and reconstructions by the loader's `shift` /
-        `scale`, write `rec_ep<epoch>.npy`, score with `compute_all_metrics`.  cfg.data.num_categorys == 1: batch by batch as the
-        loader yields them.  Otherwise: the shapes with `cate_idx == val_cate`, re-batched by cfg.data.test_batch_size and encoded with
-        the label `val_cate`.  Nothing synchronises until the dump and the metrics at the end."""
+        """:102-161 — `evalloop.reconstruct` with the model, de-normalised by the loader's `shift` / `scale` in both branches, the
+        by-category batches encoded with the label `val_cate`; then `rec_ep<epoch>.npy` and `compute_all_metrics(rec, ref,
+        batch_size=128)`.  Nothing synchronises until the dump and the metrics at the end."""
         self.model.eval()
-        dev = self.device
-        all_ref, all_rec = [], []
-        if self.cfg.data.num_categorys == 1:
-            for data in test_loader:
-                ref_pts = data["te_points"].to(dev).float()
-                rec_pts = self.model(ref_pts)["set"]
-                shift, scale = data["shift"].float().to(dev), data["scale"].float().to(dev)
-                all_ref.append(ref_pts * scale + shift)
-                all_rec.append(rec_pts * scale + shift)
-            rec, ref = torch.cat(all_rec, dim=0), torch.cat(all_ref, dim=0)
-        else:
-            shift, scale = [], []
-            for data in test_loader:
-                idx = data["cate_idx"] == val_cate
-                shift.append(data["shift"][idx].float())
-                scale.append(data["scale"][idx].float())
-                all_ref.append(data["te_points"][idx])
-            ref = torch.cat(all_ref, dim=0).to(dev).float()
-            if ref.shape[0] == 0:
-                raise ValueError("reconstrustion: no test shape has cate_idx == %r" % (val_cate,))
-            bsize = self.cfg.data.test_batch_size
-            for i in range(math.ceil(ref.shape[0] / bsize)):
-                pts = ref[i * bsize:(i + 1) * bsize]
-                cates = (torch.ones(pts.shape[0]) * val_cate).int().to(dev)
-                all_rec.append(self.model(pts, label=cates)["set"])
-            shift, scale = torch.cat(shift, dim=0).to(dev), torch.cat(scale, dim=0).to(dev)
-            rec = torch.cat(all_rec, dim=0) * scale + shift
-            ref = ref * scale + shift
-        self._save("rec", rec)
+        rec, ref = evalloop.reconstruct(self.model, test_loader, self.cfg, self.device, val_cate, "reconstrustion",
+                                        fields=("shift", "scale"), with_label=True)
+        evalloop.dump(self.cfg, "rec_ep%d.npy" % self.epoch, rec)
         self.last_reconstruction = {"rec": rec, "ref": ref}
-        return self._report(compute_all_metrics(rec, ref, batch_size=128))
-
-    def _save(self, tag, clouds):
-        path = getattr(getattr(self.cfg, "log", None), "save_path", "") or ""
-        if path:
-            np.save(os.path.join(path, "%s_ep%d.npy" % (tag, self.epoch)), clouds.detach().cpu().numpy())
-
-    def _report(self, gen_res):
-        all_res = {("val/gen/%s" % k): (v if isinstance(v, float) else v.item()) for k, v in gen_res.items()}
-        print("Validation Sample (unit) Epoch:%d " % self.epoch, gen_res)
-        return all_res
+        return evalloop.report(self.epoch, compute_all_metrics(rec, ref, batch_size=128))
 
     # ---- checkpoints: the layout trainer/base.py:51-61 `save` writes ---------------------------------------------
     def resume(self, epoch=None, finetune=False, strict=False, load_optim=True):
         """:163-186 — `<cfg.log.save_path>/checkpt_<epoch>.pth` (`epoch` defaults to the last row of `training.csv`): the weights from
         `state_dict`; unless `finetune`, also `epoch` (+ 1), `itr` and `time`.  The optimizer and scheduler entries are ignored
         (`load_optim` is accepted for signature parity): there is no optimizer here.  Ends with `model.init()` like upstream."""
-        if epoch is None:
-            import csv
-            with open(os.path.join(self.cfg.log.save_path, "training.csv")) as f:
-                epoch = int(float(list(csv.DictReader(f))[-1]["epoch"]))
-        path = os.path.join(self.cfg.log.save_path, "checkpt_{:}.pth".format(epoch))
+        path = evalloop.checkpoint_path(self.cfg, epoch)
         checkpt = torch.load(path, map_location="cpu", weights_only=False)      # holds cfg as argparse.Namespace
         if not finetune:
             self.model.load_state_dict(checkpt["state_dict"], strict=strict)
@@ -370,9 +314,9 @@ class CompletionCompressorTrainer(CompressorTrainer):
             all_rec.append(self.model(ref_pts)["set"])
             all_ref.append(ref_pts)
         rec, ref = torch.cat(all_rec, dim=0), torch.cat(all_ref, dim=0)
-        self._save("rec", rec)
+        evalloop.dump(self.cfg, "rec_ep%d.npy" % self.epoch, rec)
         self.last_reconstruction = {"rec": rec, "ref": ref}
-        cd = L2_ChamferEval_1000(rec, ref)
+        cd =L2_ChamferEval_1000(rec, ref)
         f1score, _, _ = F1Score(rec, ref)
         all_res = {"cd": cd, "f1score": f1score.mean()}
         print("Validation Sample (unit) Epoch:%d " % self.epoch, all_res)

@@ -14,16 +14,15 @@ with t drawn by `DiffusionBase.iw_quantities` (or from the discrete grid).  Trai
 The encode, x_t, the Score forward, the two sums of the KL term (ldt_nelbo_terms), Chamfer, the samplers and the decode run in HIP
 kernels; what is plain torch here is bookkeeping on finished tensors and on (B,) host schedules.
 """
-import math
 import os
 import time
 
-import numpy as np
 import torch
 
 from . import dist as ldist
-from . import ops
-from .trainer import Trainer, _sync
+from . import evalloop, ops
+from .evalloop import _sync
+from .trainer import Trainer
 
 
 def _not_trained(name):
@@ -42,7 +41,6 @@ class HybridTrainer(Trainer):
         self.N = cfg.sde.train_N
         self.discrete = cfg.opt.discrete
         self.time_eps = cfg.sde.time_eps
-        self.timesteps = torch.linspace(1.0, self.sample_time_eps, self.N)        # host fp32, like the schedule tables
 
     # ---- training: refused -------------------------------------------------------------------------------
     def update(self, data, condition=None, train_individual=True):
@@ -60,15 +58,12 @@ class HybridTrainer(Trainer):
     # ---- held-out latent NELBO ---------------------------------------------------------------------------------
     @torch.no_grad()
     def val_nelbo(self, data, condition=None, *, discrete=None, rho=None, t_index=None, eta=None, post_noise=None, seed=None):
-        """The forward terms of `clc_compressor` (Hybrid_Trainer.py:117-143) for one held-out batch, EMA weights in and out (also when
-        something in between raises):
+        """The forward terms of `clc_compressor` (Hybrid_Trainer.py:117-143) for one held-out batch, inside `Trainer._ema_weights`:
           1. `compressor(data['te_points'], want_kl=True)`: `all_eps`, the reconstruction, the per-level log q(z);
           2. log q(z) concatenated to the layout of `all_eps` (:119);
-          3. the times — `discrete` (default cfg.opt.discrete) True: `np.random.choice(arange(train_N), B)` on numpy's global generator
-             over `linspace(1, sample_time_eps, train_N)` and w_q = g2 / (2 var) (:122-127); False: `SDE.iw_quantities(B, cfg.sde.time_eps,
-             cfg.sde.iw_sample_q_mode, sde_type == 'sub_vpsde')` (:129-134);
-          4. x_t = eps e2int_f(t) + sqrt(var(t)) eta (ldt_diffuse_q), eta from the device Philox stream keyed by ONE draw of the CPU generator
-             (upstream: `randn_like` on the CUDA generator), as in `Trainer.val_loss`;
+          3. the times (`Trainer._draw_times`) — `discrete` (default cfg.opt.discrete) True: the grid, and w_q = g2 / (2 var) (:122-127);
+             False: cfg.sde.iw_sample_q_mode with its weight (:129-134);
+          4. x_t and eta (`Trainer._diffuse`), as in `Trainer.val_loss`;
           5. `Score(x_t, t, label=, condition=)` with the per-sample times, label from `data['cate_idx']` when cfg.data.num_categorys > 1;
           6. c = 1/2 (1 + log(2 pi var(time_eps))) (:140-141), and the two sums of kl in one pass (ldt_nelbo_terms).
         Returns 0-dim device tensors {'kl': mean(logqz - logpz), 'logqz': mean log q(z), 'score_term': mean |eta - params|^2 w_q,
@@ -84,35 +79,22 @@ class HybridTrainer(Trainer):
         n_layers (B, tokens, z_dim) tensors), `seed` the Philox key of eta.  The pieces stay available as `self.last_val_nelbo`."""
         self.model.eval()
         self.compressor.eval()
-        self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
-        try:
+        with self._ema_weights():
             dev = self.device
             target = data["te_points"].to(dev).float().contiguous()
             kw = {} if post_noise is None else {"post_noise": post_noise}
             out = self.compressor(target, want_kl=True, **kw)
             eps = out["all_eps"]
             logqz = torch.cat(out["all_logqz"], dim=1).transpose(1, 2).contiguous()        # (B, tokens, n_layers * z): all_eps's layout
-            label = data["cate_idx"].to(dev) if self.cfg.data.num_categorys > 1 else None
+            label = self._label(data)
             size = eps.shape[0]
-            if self.discrete if discrete is None else discrete:
-                if t_index is None:
-                    t_index = np.random.choice(np.arange(self.N), size, replace=True)
-                idx = torch.as_tensor(np.asarray(t_index)).long().reshape(-1)
-                if idx.numel() != size:
-                    raise ValueError("val_nelbo: t_index holds %d entries for a batch of %d" % (idx.numel(), size))
-                t = self.timesteps.index_select(0, idx)
-                e2int_f, var = self.SDE.e2int_f(t), self.SDE.var(t)
-                weight_q = self.SDE.g2(t) / (2 * var)
-            else:
-                t, var, e2int_f, weight_q, _, _ = self.SDE.iw_quantities(size, time_eps=self.time_eps,
-                                                                         iw_sample_mode=self.cfg.sde.iw_sample_q_mode,
-                                                                         iw_subvp_like_vp_sde=self.sde_type == "sub_vpsde", rho=rho)
-            var, e2int_f = var.reshape(-1).float(), e2int_f.reshape(-1).float()
+            discrete = self.discrete if discrete is None else discrete
+            t, e2int_f, var, weight_q = self._draw_times(size, discrete, "val_nelbo", t_index=t_index, rho=rho,
+                                                         iw_mode=None if discrete else self.cfg.sde.iw_sample_q_mode)
+            if discrete:
+                weight_q = self.SDE.g2(t) / (2 * var)                                      # (:122-127: the NELBO's weight on the grid)
             weight_q = weight_q.reshape(-1).float().expand(size).contiguous()              # ((1, 1) under 'drop_all_uniform')
-            if eta is None and seed is None:
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            t_dev = t.float().to(dev)
-            xt, eta = ops.diffuse_q(eps, e2int_f.to(dev), var.to(dev), None if eta is None else eta.to(dev, torch.float32), seed=seed or 0)
+            t_dev, xt, eta = self._diffuse(eps, t, e2int_f, var, eta, seed)
             params = self.model(xt, t_dev, condition=condition, label=label)
             w_dev = weight_q.to(dev)
             sums, per_sample = ops.nelbo_terms(eta, params, logqz, w_dev)
@@ -123,8 +105,6 @@ class HybridTrainer(Trainer):
                    "rec_cd": torch.sqrt(d_rec.clamp_min(0)).mean() + torch.sqrt(d_tgt.clamp_min(0)).mean()}
             self.last_val_nelbo = dict(res, t=t_dev, weight_q=w_dev, var=var, e2int_f=e2int_f, eps=eps, logqz=logqz, eta=eta, xt=xt,
                                        params=params, set=out["set"], sample_sums=per_sample, batch_sums=sums)
-        finally:
-            self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
         return res
 
     # ---- generation ------------------------------------------------------------------------------------------
@@ -146,93 +126,37 @@ class HybridTrainer(Trainer):
 
     @torch.no_grad()
     def valsample(self, test_loader, val_cate=0, vis=False):
-        """:187-247, upstream's behaviour kept: cfg.data.num_categorys == 1 samples `len(batch['tr_points'])` clouds per batch against
-        the batches' `te_points`; otherwise ceil(len(ref) / cfg.data.test_batch_size) label-conditioned batches of test_batch_size for
-        the `te_points` with `cate_idx == val_cate`, NOT cut to len(ref) (:223-224).  The "Sample rate" print, the dump into
-        cfg.log.save_path (when one is set) under upstream's literal name 'smp{:}_ep<epoch>.npy' (:228 fills only the %d),
-        `compute_all_metrics(smp, ref, batch_size=64)` and the `{"val/gen/<key>": float}` dict.  vis=True (mitsuba) raises."""
-        if vis:
-            raise NotImplementedError("valsample(vis=True): mitsuba rendering (tools/vis_utils.py) is not on this path")
+        """:187-247, upstream's behaviour kept: `Trainer.valsample`'s references and sampled batches (evalloop.collect_refs / sample_clouds),
+        the label-conditioned ones NOT cut to len(ref) (:223-224).  The "Sample rate" print on every rank, the dump on rank 0 under
+        upstream's literal name 'smp{:}_ep<epoch>.npy' (:228 fills only the %d), `compute_all_metrics(smp, ref, batch_size=64)` and its
+        report.  vis=True (mitsuba) raises."""
+        evalloop.refuse_vis("valsample", vis)
         from .metrics import compute_all_metrics
         self.model.eval()
         self.compressor.eval()
-        dev = self.device
-        all_ref, all_smp, use_time = [], [], 0.
-        if self.cfg.data.num_categorys == 1:
-            for data in test_loader:
-                ref_pts = data["te_points"].to(dev)
-                t0 = time.time()
-                all_smp.append(self.sample(num_samples=data["tr_points"].size(0), condition=None))
-                use_time += time.time() - t0
-                all_ref.append(ref_pts)
-        else:
-            for data in test_loader:
-                all_ref.append(data["te_points"][data["cate_idx"] == val_cate])
-            n_ref = sum(r.shape[0] for r in all_ref)
-            if n_ref == 0:
-                raise ValueError("valsample: no test shape has cate_idx == %r" % (val_cate,))
-            bsize = self.cfg.data.test_batch_size
-            t0 = time.time()
-            for _ in range(math.ceil(n_ref / bsize)):
-                cates = (torch.ones(bsize) * val_cate).int().to(dev)
-                all_smp.append(self.sample(num_samples=bsize, label=cates))
-            use_time += time.time() - t0
-        smp, ref = torch.cat(all_smp, dim=0), torch.cat(all_ref, dim=0).to(dev).float()
+        dev, d = self.device, self.cfg.data
+        cate = None if d.num_categorys == 1 else val_cate
+        ref, sizes, _ = evalloop.collect_refs(test_loader, dev, "valsample", cate, None if cate is None else d.test_batch_size)
+        smp, use_time = evalloop.sample_clouds(self.sample, sizes, dev, cate)
         print("Sample rate: %.8f " % (smp.shape[0] / max(use_time, 1e-9)))
         self.last_valsample = {"samples": smp, "refs": ref}
-        self._dump('smp{:}_ep%d' % self.epoch + ".npy", smp)
-        return self._report(compute_all_metrics(smp, ref, batch_size=64))
+        evalloop.dump(self.cfg, 'smp{:}_ep%d' % self.epoch + ".npy", smp, ldist.world()[0] == 0)
+        return evalloop.report(self.epoch, compute_all_metrics(smp, ref, batch_size=64))
 
     @torch.no_grad()
     def valrecon(self, test_loader, val_cate=0, *args, **kwargs):
-        """:249-308 — encode and reconstruct the test shapes, de-normalise, dump `rec_ep<epoch>.npy`, `compute_all_metrics(rec, ref,
-        batch_size=256)`.  cfg.data.num_categorys == 1: batch by batch, de-normalised by the loader's `shift` / `scale`.  Otherwise: the
-        shapes with `cate_idx == val_cate`, re-batched by cfg.data.test_batch_size, de-normalised by `mean` / `std`.
+        """:249-308 — `evalloop.reconstruct` with the Compressor, without a label, the by-category branch de-normalised by `mean` / `std`;
+        then the `rec_ep<epoch>.npy` dump (rank 0) and `compute_all_metrics(rec, ref, batch_size=256)`.
         Upstream's single-category branch calls `self.model(ref_pts)` (:261) — the Score on a point cloud — and cannot run; what is meant,
         and what the other branch does (:289), is `self.compressor(ref_pts)`, which is what runs here."""
         from .metrics import compute_all_metrics
         self.model.eval()
         self.compressor.eval()
-        dev = self.device
-        all_ref, all_rec = [], []
-        if self.cfg.data.num_categorys == 1:
-            for data in test_loader:
-                ref_pts = data["te_points"].to(dev).float()
-                rec_pts = self.compressor(ref_pts)["set"]
-                shift, scale = data["shift"].float().to(dev), data["scale"].float().to(dev)
-                all_ref.append(ref_pts * scale + shift)
-                all_rec.append(rec_pts * scale + shift)
-            rec, ref = torch.cat(all_rec, dim=0), torch.cat(all_ref, dim=0)
-        else:
-            all_shift, all_scale = [], []
-            for data in test_loader:
-                idx = data["cate_idx"] == val_cate
-                all_shift.append(data["mean"][idx].float())
-                all_scale.append(data["std"][idx].float())
-                all_ref.append(data["te_points"][idx])
-            pts = torch.cat(all_ref, dim=0).to(dev).float()
-            if pts.shape[0] == 0:
-                raise ValueError("valrecon: no test shape has cate_idx == %r" % (val_cate,))
-            shift, scale = torch.cat(all_shift, dim=0).to(dev), torch.cat(all_scale, dim=0).to(dev)
-            ref = pts * scale + shift
-            bsize = self.cfg.data.test_batch_size
-            for i in range(math.ceil(pts.shape[0] / bsize)):
-                all_rec.append(self.compressor(pts[i * bsize:(i + 1) * bsize])["set"])
-            rec = torch.cat(all_rec, dim=0)[:ref.shape[0]]
-            rec = rec * scale + shift
+        rec, ref = evalloop.reconstruct(self.compressor, test_loader, self.cfg, self.device, val_cate, "valrecon",
+                                        fields=("mean", "std"), with_label=False)
         self.last_valrecon = {"rec": rec, "ref": ref}
-        self._dump('rec_ep%d' % self.epoch + ".npy", rec)
-        return self._report(compute_all_metrics(rec, ref, batch_size=256))
-
-    def _dump(self, name, clouds):
-        path = getattr(getattr(self.cfg, "log", None), "save_path", "") or ""
-        if path and ldist.world()[0] == 0:
-            np.save(os.path.join(path, name), clouds.detach().cpu().numpy())
-
-    def _report(self, gen_res):
-        all_res = {("val/gen/%s" % k): (v if isinstance(v, float) else v.item()) for k, v in gen_res.items()}
-        print("Validation Sample (unit) Epoch:%d " % self.epoch, gen_res)
-        return all_res
+        evalloop.dump(self.cfg, 'rec_ep%d' % self.epoch + ".npy", rec, ldist.world()[0] == 0)
+        return evalloop.report(self.epoch, compute_all_metrics(rec, ref, batch_size=256))
 
     # ---- checkpoints: the dict `save` writes upstream (:310-323) -------------------------------------------------
     def resume(self, epoch=None, strict=False, load_optim=True, finetune=False, *, pretrain=None, **kwargs):

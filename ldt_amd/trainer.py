@@ -6,19 +6,23 @@ discrete)` — one Score training step: backward, clip, Adam + EMA (:94-141; ldt
 `sample(num_samples, num_points, label, condition) -> (points, eps)` (:143-165), `valsample`-style "Sample rate"
 timing (:178-181,206), EMA weight swap (:146,164; tools/utils.py:80-101), `save` / `resume` with the reference's checkpoint
 dict (:228-266).  Training covers the Score of the shipped YAMLs (LayerNorm, AdaLN, self-attention, unconditional or labelled);
-the Compressor and the hybrid objective are not trained on this path.
+the Compressor and the hybrid objective are not trained on this path.  The steps the methods (and `HybridTrainer`) share are said once:
+`_ema_weights`, `_draw_times`, `_diffuse`, `_label`, `_update`; the evaluation loop's pieces are ldt_amd/evalloop.py's.
 
 Multi-GPU: when torch.distributed is initialised, `sample(B)` runs rows [lo,hi) of the batch on this rank and
 all-gathers the finished points/latents once (ldt_amd/dist.py); results do not depend on the world size when
 every rank seeds the CPU generator identically (the reference's common_init, tools/utils.py:269-276).
 """
+import contextlib
 import os
 import time
 
 import torch
 
 from . import dist as ldist
+from . import evalloop
 from .diffusion import DiffusionSubVPSDE, DiffusionVESDE, DiffusionVPSDE
+from .evalloop import _sync                              # (kept importable from here)
 
 
 class EMAWeights:
@@ -90,13 +94,61 @@ class Trainer:
             return ops.vpsde_score(params, t.float(), sde.beta_start, sde.beta_end, sde.sigma2_0), params
         return ops.sde_score(params, t.float(), sde.score_kind, *sde.score_consts()), params
 
+    # ---- what sample, val_loss, update / update_score and HybridTrainer.val_nelbo share -------------------------------
+    @contextlib.contextmanager
+    def _ema_weights(self, active=True):
+        """The EMA weights in for the body and out again, also when the body raises (tools/utils.py:80-101); active=False: nothing."""
+        if active:
+            self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
+        try:
+            yield
+        finally:
+            if active:
+                self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
+
+    @property
+    def timesteps(self):
+        """The discrete time grid, host fp32 like the schedule tables."""
+        return torch.linspace(1.0, self.sample_time_eps, self.cfg.sde.train_N)
+
+    def _label(self, data):
+        return data["cate_idx"].to(self.device) if self.cfg.data.num_categorys > 1 else None
+
+    def _draw_times(self, size, discrete, who, *, t_index=None, iw_mode=None, rho=None):
+        """The forward-diffusion times of a batch -> (t, e2int_f, var, iw_weight), host fp32, the first three (size,).
+        discrete: ONE `np.random.choice(arange(train_N), size)` on numpy's global generator (none when `t_index` (size,) is given) into
+        `timesteps`; iw_weight is None.  Otherwise `SDE.iw_quantities(size, cfg.sde.time_eps, iw_mode, sde_type == 'sub_vpsde')` — one
+        `torch.rand(size)` on the CPU generator unless `rho` is given — with its obj_weight_t, shaped as it comes, as iw_weight."""
+        if discrete:
+            import numpy as np
+            if t_index is None:
+                t_index = np.random.choice(np.arange(self.cfg.sde.train_N), size, replace=True)
+            idx = torch.as_tensor(np.asarray(t_index)).long().reshape(-1)
+            if idx.numel() != size:
+                raise ValueError("%s: t_index holds %d entries for a batch of %d" % (who, idx.numel(), size))
+            t = self.timesteps.index_select(0, idx)
+            e2int_f, var, weight = self.SDE.e2int_f(t), self.SDE.var(t), None
+        else:
+            t, var, e2int_f, weight, _, _ = self.SDE.iw_quantities(size, time_eps=self.cfg.sde.time_eps, iw_sample_mode=iw_mode,
+                                                                   iw_subvp_like_vp_sde=self.sde_type == "sub_vpsde", rho=rho)
+        return t.reshape(-1).float(), e2int_f.reshape(-1).float(), var.reshape(-1).float(), weight
+
+    def _diffuse(self, eps, t, e2int_f, var, eta, seed):
+        """x_t = eps e2int_f(t) + sqrt(var(t)) eta (ldt_diffuse_q) -> (t on the device, xt, eta).  Without `eta` the noise comes from the
+        device Philox stream, keyed by `seed` or else by ONE draw of the CPU generator (upstream: `randn_like` on the CUDA generator)."""
+        from . import ops
+        dev = eps.device
+        if eta is None and seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        xt, eta = ops.diffuse_q(eps, e2int_f.to(dev), var.to(dev), None if eta is None else eta.to(dev, torch.float32), seed=seed or 0)
+        return t.to(dev), xt, eta
+
     @torch.no_grad()
     def sample(self, num_samples, num_points=None, label=None, condition=None, *, x0=None, noise=None, seed=None,
                use_graph=None, trajectory=None):
         self.model.eval()
         self.compressor.eval()
-        self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
-        try:
+        with self._ema_weights():
             if self.sample_mode not in ("discrete", "continuous"):
                 raise NotImplementedError("sample_mode %r" % (self.sample_mode,))
             cs = self.cfg.score
@@ -145,52 +197,28 @@ class Trainer:
             if ldist.initialized():                      # the single collective of the path
                 sample = ldist.all_gather_rows(sample, num_samples)
                 eps = ldist.all_gather_rows(eps, num_samples)
-        finally:
-            self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
         return sample, eps
 
     @torch.no_grad()
     def val_loss(self, data, condition=None, *, t_index=None, eta=None, seed=None):
         """The held-out denoising loss of one batch, the reference's method line for line (trainer/Latent_SDE_Trainer.py:63-92;
-        train_Latent_Diffusion.py:76 calls it per test batch): EMA weights in, `compressor(data['te_points'])['all_eps']`, the label
-        from `data['cate_idx']` when cfg.data.num_categorys > 1, `idx = np.random.choice(arange(train_N), B)` on numpy's global
-        generator (so `np.random.seed` reproduces upstream's times), `t = linspace(1, sample_time_eps, train_N)[idx]`,
-        `xt = eps * e2int_f(t) + sqrt(var(t)) * eta` (ldt_diffuse_q), `params = Score(xt, t, label=, condition=)`, |eta - params| for
-        cfg.opt.loss_type "l1" and the square otherwise, the mean over everything (ldt_dsm_loss), EMA weights out — also when
-        something in between raises.  Returns the 0-dim device tensor; nothing is synchronised.
-
-        `eta` is where upstream calls `torch.randn_like` on the CUDA generator, which no other device reproduces: here it comes
-        from the device Philox stream keyed by ONE draw of the CPU generator (the convention of `Compressor.forward`'s posterior
-        noise).  Keyword extensions (not in the reference): `t_index` (B,) replaces the numpy draw, `eta` (B, tokens, z) the
-        noise, `seed` the Philox key.  The pieces stay available as `self.last_val_loss`."""
-        import numpy as np
+        train_Latent_Diffusion.py:76 calls it per test batch): inside `_ema_weights`, `compressor(data['te_points'])['all_eps']`, the label
+        from `data['cate_idx']` when cfg.data.num_categorys > 1, discrete times (`_draw_times`: so `np.random.seed` reproduces upstream's),
+        x_t (`_diffuse`), `params = Score(xt, t, label=, condition=)`, |eta - params| for cfg.opt.loss_type "l1" and the square otherwise,
+        the mean over everything (ldt_dsm_loss).  Returns the 0-dim device tensor; nothing is synchronised.  Keyword extensions (not in the
+        reference): `t_index` (B,) replaces the numpy draw, `eta` (B, tokens, z) the noise, `seed` the Philox key.  The pieces stay
+        available as `self.last_val_loss`."""
         from . import ops
         self.model.eval()
         self.compressor.eval()
-        self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
-        try:
-            dev = self.device
-            eps = self.compressor(data["te_points"].to(dev))["all_eps"]
-            label = data["cate_idx"].to(dev) if self.cfg.data.num_categorys > 1 else None
-            size = eps.shape[0]
-            train_N = self.cfg.sde.train_N
-            if t_index is None:
-                t_index = np.random.choice(np.arange(train_N), size, replace=True)
-            idx = torch.as_tensor(np.asarray(t_index)).long().reshape(-1)
-            if idx.numel() != size:
-                raise ValueError("val_loss: t_index holds %d entries for a batch of %d" % (idx.numel(), size))
-            t = torch.linspace(1.0, self.sample_time_eps, train_N).index_select(0, idx)      # host fp32, like the schedule tables
-            e2int_f, var = self.SDE.e2int_f(t), self.SDE.var(t)
-            if eta is None and seed is None:
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            t_dev = t.to(dev)
-            xt, eta = ops.diffuse_q(eps, e2int_f.float().to(dev), var.float().to(dev),
-                                    None if eta is None else eta.to(dev, torch.float32), seed=seed or 0)
+        with self._ema_weights():
+            eps = self.compressor(data["te_points"].to(self.device))["all_eps"]
+            label = self._label(data)
+            t, e2int_f, var, _ = self._draw_times(eps.shape[0], True, "val_loss", t_index=t_index)
+            t_dev, xt, eta = self._diffuse(eps, t, e2int_f, var, eta, seed)
             params = self.model(xt, t_dev, condition=condition, label=label)
             loss, per_sample = ops.dsm_loss(eta, params, None, l1=self.cfg.opt.loss_type == "l1")
             self.last_val_loss = {"t": t_dev, "eps": eps, "eta": eta, "xt": xt, "params": params, "sample_loss": per_sample}
-        finally:
-            self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
         return loss
 
     @torch.no_grad()
@@ -198,121 +226,77 @@ class Trainer:
         """The reference's validation sampling loop, same signature and return value (trainer/Latent_SDE_Trainer.py:167-226;
         called as `trainer.valsample(test_loader=test_loader, val_cate=13)` by train_Latent_Diffusion.py:60,85).
 
-        `test_loader` is any iterable of the dataset's dict batches (`te_points`, `tr_points`, `cate_idx`):
-          * `cfg.data.num_categorys == 1` (:173-188): one `sample(num_samples=len(batch['tr_points']))` per batch, the
-            references are the batches' `te_points`;
-          * otherwise (:189-205): the `te_points` whose `cate_idx == val_cate` are the references, and
-            ceil(len(ref) / cfg.data.test_batch_size) label-conditioned batches are sampled and cut to len(ref).
-            (Upstream appends `self.sample(...)`'s (points, eps) TUPLE there and would fail in `torch.cat`; the points are
-            what is meant and what is kept here.)
-        Then, as upstream: the "Sample rate" print (:206), the `smp_ep<epoch>.npy` dump into `cfg.log.save_path`
-        (:207-210), `compute_all_metrics(smp, ref, batch_size=64)` (:217-220), the summary print, and the returned
-        `{"val/gen/<key>": float}` dict.  `vis=True` (mitsuba rendering, :211-216) is out of scope and raises.
+        `test_loader` is any iterable of the dataset's dict batches (`te_points`, `tr_points`, `cate_idx`); the references and the sampled
+        batches are `evalloop.collect_refs` / `sample_clouds`: per batch when `cfg.data.num_categorys == 1` (:173-188), otherwise by
+        `cate_idx == val_cate` with label-conditioned batches (:189-205; upstream appends `self.sample(...)`'s (points, eps) TUPLE there and
+        would fail in `torch.cat`: the points are what is meant), cut to len(ref).  Then the "Sample rate" print (:206) and the
+        `smp_ep<epoch>.npy` dump (:207-210), both on rank 0, `compute_all_metrics(smp, ref, batch_size=64)` (:217-220) and its report.  `vis=True` (mitsuba
+        rendering, :211-216) is out of scope and raises.
 
         Keyword extensions (not in the reference): `test_loader` may be an int = that many unconditional batches of
         `batch_size` (default `cfg.data.test_batch_size`) scored against `ref` (N, points, 3) when given; `save_npy`
         False suppresses the dump, None (default) dumps whenever `cfg.log.save_path` is set.  The samples and the rate of
         the last call stay available as `self.last_valsample = {"samples", "refs", "rate"}`."""
-        import math
-        import os
-        import numpy as np
-        if vis:
-            raise NotImplementedError("valsample(vis=True): mitsuba rendering (tools/vis_utils.py) is not on this path")
+        evalloop.refuse_vis("valsample", vis)
         self.model.eval()
         self.compressor.eval()
-        dev = self.device
-        all_ref, all_smp, use_time = [], [], 0.
-
-        def timed_sample(n, label=None):
-            nonlocal use_time
-            _sync(dev)
-            t0 = time.time()
-            pts, _ = self.sample(num_samples=n, label=label)
-            _sync(dev)
-            use_time += time.time() - t0
-            return pts
-
+        dev, d = self.device, self.cfg.data
         if isinstance(test_loader, int):                                   # extension: no dataset at hand
-            bsize = batch_size or self.cfg.data.test_batch_size
-            for _ in range(test_loader):
-                all_smp.append(timed_sample(bsize))
-            smp = torch.cat(all_smp, 0)
-            if ref is not None:
-                ref = ref.to(smp)
-                smp = smp[:ref.shape[0]]
-        elif self.cfg.data.num_categorys == 1:                            # :173-188
-            for data in test_loader:
-                all_ref.append(data["te_points"].to(dev))
-                all_smp.append(timed_sample(data["tr_points"].size(0)))
-            smp, ref = torch.cat(all_smp, 0), torch.cat(all_ref, 0).float()
-        else:                                                              # :189-205
-            for data in test_loader:
-                idx = data["cate_idx"] == val_cate
-                all_ref.append(data["te_points"][idx])
-            ref = torch.cat(all_ref, 0).to(dev).float()
-            bsize = self.cfg.data.test_batch_size
-            for _ in range(math.ceil(ref.shape[0] / bsize)):
-                cates = (torch.ones(bsize) * val_cate).int().to(dev)
-                all_smp.append(timed_sample(bsize, label=cates))
-            if not all_smp:
-                raise ValueError("valsample: no test shape has cate_idx == %r" % (val_cate,))
-            smp = torch.cat(all_smp, 0)[:ref.shape[0]]
+            cate, sizes = None, [batch_size or d.test_batch_size] * test_loader
+        else:                                                              # :173-188 per batch, :189-205 by category
+            cate = None if d.num_categorys == 1 else val_cate
+            ref, sizes, _ = evalloop.collect_refs(test_loader, dev, "valsample", cate, None if cate is None else d.test_batch_size)
+        smp, use_time = evalloop.sample_clouds(lambda **kw: self.sample(**kw)[0], sizes, dev, cate)
+        if ref is not None:
+            ref = ref.to(smp)
+            smp = smp[:ref.shape[0]]
         rate = smp.shape[0] / max(use_time, 1e-9)
         chief = ldist.world()[0] == 0
         if chief:
             print("Sample rate: %.8f " % rate)
         self.last_valsample = {"samples": smp, "refs": ref, "rate": rate}
-        path = getattr(self.cfg.log, "save_path", "") or ""
-        if save_npy and not path:
+        if save_npy and not (getattr(self.cfg.log, "save_path", "") or ""):
             raise ValueError("valsample(save_npy=True) needs cfg.log.save_path (upstream writes smp_ep<epoch>.npy there)")
-        if chief and path and save_npy is not False:
-            np.save(os.path.join(path, "smp_ep%d" % self.epoch + ".npy"), smp.detach().cpu().numpy())
+        if save_npy is not False:
+            evalloop.dump(self.cfg, "smp_ep%d" % self.epoch + ".npy", smp, chief)
         if ref is None:
             return {}
         from .metrics import compute_all_metrics
-        gen_res = compute_all_metrics(smp, ref, batch_size=64)
-        all_res = {("val/gen/%s" % k): (v if isinstance(v, float) else v.item()) for k, v in gen_res.items()}
-        if chief:
-            print("Validation Sample (unit) Epoch:%d " % self.epoch, gen_res)
-        return all_res
+        return evalloop.report(self.epoch, compute_all_metrics(smp, ref, batch_size=64), chief)
 
     # ---- training: one Score step (trainer/Latent_SDE_Trainer.py:94-141, trainer/base.py:32-37) -------------------
     def warm_up(self, optimizer, itr):
-        if itr < self.cfg.opt.warmup_iters:
-            iter_frac = min(float(itr + 1) / max(self.cfg.opt.warmup_iters, 1), 1.0)
-            lr = self.cfg.opt.lr * iter_frac
-            for param_group in optimizer.param_groups:
-                param_group["lr"] = lr
+        evalloop.warm_up(self.cfg, optimizer, itr)
 
     def update(self, data, condition=None):
-        """The reference's `update` line for line (:94-109): labels from `data['cate_idx']` when cfg.data.num_categorys > 1, the EMA swap
-        around the step from the second iteration on, the frozen Compressor's `all_eps` of `data['tr_points']`, `update_score`, `itr += 1`.
-        Returns the 0-dim device loss."""
+        """The reference's `update` line for line (:94-109): labels from `data['cate_idx']` when cfg.data.num_categorys > 1, then
+        `_update` on `data['tr_points']` with cfg.opt.discrete (default False).  Returns the 0-dim device loss."""
         from .train import refuse_untrainable
         refuse_untrainable(self.model, condition, ldist.world()[1])
+        self._refuse_host("Trainer.update")
+        return self._update(self._label(data), data["tr_points"], getattr(self.cfg.opt, "discrete", False), condition)
+
+    def _refuse_host(self, who):
         if not torch.device(self.device).type == "cuda" or not torch.cuda.is_available():
-            raise RuntimeError("Trainer.update: device %s; the HIP path has no CPU fallback" % (self.device,))
-        cates = data["cate_idx"].to(self.device) if self.cfg.data.num_categorys > 1 else None
-        if self.itr > 0:
-            self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
-        try:
+            raise RuntimeError("%s: device %s; the HIP path has no CPU fallback" % (who, self.device))
+
+    def _update(self, cates, point, discrete, condition):
+        """What `update` is after its refusals: the EMA swap around the step from the second iteration on, the frozen Compressor's
+        `all_eps` of the points, `update_score`, `itr += 1` (a raise leaves `itr` as it was)."""
+        with self._ema_weights(self.itr > 0):
             with torch.no_grad():
                 self.compressor.eval()
-                eps = self.compressor(data["tr_points"].to(self.device))["all_eps"]
-            loss = self.update_score(eps, cates=cates, discrete=getattr(self.cfg.opt, "discrete", False), condition=condition)
-        finally:
-            if self.itr > 0:
-                self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
+                eps = self.compressor(point.to(self.device))["all_eps"]
+            loss = self.update_score(eps, cates=cates, discrete=discrete, condition=condition)
         self.itr += 1
         return loss
 
     def update_score(self, eps, condition=None, cates=None, discrete=False, *, t_index=None, eta=None, seed=None):
-        """The reference's `update_score` (:111-141): warm-up of the learning rate, times by `np.random.choice` (discrete) or
-        `SDE.iw_quantities(size, time_eps, cfg.sde.iw_sample_p_mode, ...)` with its per-sample `weight_p`, `xt = eps * e2int_f +
-        sqrt(var) * eta` (ldt_diffuse_q), the Score in training mode with its activations kept, the l1 / l2 loss (ldt_dsm_loss), the
-        backward pass, `clip_grad_norm_(cfg.opt.grad_norm_clip_value)` and `EMA(Adam).step()` in one fused update.  Returns the 0-dim
-        device loss; nothing is synchronised.  Keyword extensions as `val_loss`: `t_index` (B,) replaces the numpy draw of the discrete
-        times, `eta` (B, tokens, z) the noise, `seed` the Philox key of the device noise.  The pieces stay available as `self.last_update`."""
+        """The reference's `update_score` (:111-141): warm-up of the learning rate, the times (`_draw_times`: the discrete grid, or
+        cfg.sde.iw_sample_p_mode with its per-sample `weight_p`), x_t (`_diffuse`), the Score in training mode with its activations kept, the
+        l1 / l2 loss (ldt_dsm_loss), the backward pass, `clip_grad_norm_(cfg.opt.grad_norm_clip_value)` and `EMA(Adam).step()` in one fused
+        update.  Returns the 0-dim device loss; nothing is synchronised.  Keyword extensions `t_index`, `eta`, `seed` as `val_loss`.  The
+        pieces stay available as `self.last_update`."""
         from .train import refuse_untrainable
         refuse_untrainable(self.model, condition, ldist.world()[1])
         return self._score_step(eps, None, cates, discrete, t_index, eta, seed)
@@ -320,37 +304,20 @@ class Trainer:
     def _score_step(self, eps, condition, cates, discrete, t_index, eta, seed):
         """The body of `update_score` after the refusals.  condition: None, or the embedded (pts_condition, img_condition) pair
         (`CompletionTrainer`): the step then keeps the gradient with respect to that pair as `self.last_condition_grad`."""
-        import numpy as np
         from . import ops
         from .train import ScoreTrainStep
         if not torch.is_tensor(eps) or not eps.is_cuda:
             raise RuntimeError("Trainer.update_score: eps is on %s; the HIP path has no CPU fallback"
                                % (eps.device if torch.is_tensor(eps) else type(eps).__name__,))
-        dev = eps.device
         self.warm_up(self.optimizer, self.itr)
         eps = eps.detach().float().contiguous()
         self.model.train()
         self.optimizer.zero_grad()
-        size = eps.shape[0]
-        if discrete:
-            train_N = self.cfg.sde.train_N
-            if t_index is None:
-                t_index = np.random.choice(np.arange(train_N), size, replace=True)
-            idx = torch.as_tensor(np.asarray(t_index)).long().reshape(-1)
-            if idx.numel() != size:
-                raise ValueError("update_score: t_index holds %d entries for a batch of %d" % (idx.numel(), size))
-            t = torch.linspace(1.0, self.sample_time_eps, train_N).index_select(0, idx)
-            e2int_f, var, weight_p = self.SDE.e2int_f(t), self.SDE.var(t), None
-        else:
-            t, var, e2int_f, weight_p, _, _ = self.SDE.iw_quantities(size, time_eps=self.cfg.sde.time_eps,
-                                                                     iw_sample_mode=self.cfg.sde.iw_sample_p_mode,
-                                                                     iw_subvp_like_vp_sde=self.sde_type == "sub_vpsde")
-            weight_p = weight_p.reshape(-1).float().to(dev)
-        if eta is None and seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        t_dev = t.reshape(-1).float().to(dev)
-        xt, eta = ops.diffuse_q(eps, e2int_f.reshape(-1).float().to(dev), var.reshape(-1).float().to(dev),
-                                None if eta is None else eta.to(dev, torch.float32), seed=seed or 0)
+        t, e2int_f, var, weight_p = self._draw_times(eps.shape[0], discrete, "update_score", t_index=t_index,
+                                                     iw_mode=None if discrete else self.cfg.sde.iw_sample_p_mode)
+        if weight_p is not None:
+            weight_p = weight_p.reshape(-1).float().to(eps.device)
+        t_dev, xt, eta = self._diffuse(eps, t, e2int_f, var, eta, seed)
         if condition is None:
             step = ScoreTrainStep(self.model)
             params = step.forward(xt, t_dev, label=cates)
@@ -370,7 +337,7 @@ class Trainer:
 
     def save(self, **kwargs):
         """The reference's checkpoint dict (:228-239) at `<cfg.log.save_path>/checkpt_<epoch>.pth`."""
-        path = os.path.join(self.cfg.log.save_path, "checkpt_{:}.pth".format(self.epoch))
+        path = evalloop.checkpoint_path(self.cfg, self.epoch)
         torch.save({"cfg": self.cfg, "score_state_dict": self.model.state_dict(), "score_optim_state_dict": self.optimizer.state_dict(),
                     "score_scheduler": self.scheduler.state_dict(), "compressor_state_dict": self.compressor.state_dict(),
                     "epoch": self.epoch, "itr": self.itr, "time": self.time}, path)
@@ -383,17 +350,12 @@ class Trainer:
         (A path string passed as `epoch` is accepted as shorthand for `pretrain=`.)  Loads both state dicts, the
         optimizer's state — step, moments and the per-parameter 'ema' tensors — unless finetune / load_optim=False,
         and re-runs `compressor.init()`."""
-        import os
         if finetune:
             load_optim, strict = False, False
         if isinstance(epoch, (str, os.PathLike)):
             pretrain, epoch = epoch, None
         if pretrain is None:
-            if epoch is None:
-                import csv
-                with open(os.path.join(self.cfg.log.save_path, "training.csv")) as f:
-                    epoch = int(float(list(csv.DictReader(f))[-1]["epoch"]))
-            pretrain = os.path.join(self.cfg.log.save_path, "checkpt_{:}.pth".format(epoch))
+            pretrain = evalloop.checkpoint_path(self.cfg, epoch)
         ckpt = torch.load(pretrain, map_location="cpu", weights_only=False)   # holds cfg as argparse.Namespace
         self.model.load_state_dict(ckpt["score_state_dict"], strict=strict)
         self.compressor.load_state_dict(ckpt["compressor_state_dict"], strict=strict)
@@ -449,25 +411,11 @@ class CompletionTrainer(Trainer):
                                       "net would silently decay" % (who, wd))
 
     def update(self, data, condition=None):
-        """The reference's `update` (:99-111): the EMA swap around the step from the second iteration on, the frozen Compressor's `all_eps`
-        of `data` (a tensor as upstream; a dict with `tr_points` is accepted too), `update_score` with cfg.opt.discrete, `itr += 1`.
-        Returns the 0-dim device loss."""
+        """The reference's `update` (:99-111): `Trainer._update` on `data` (a tensor as upstream; a dict with `tr_points` is accepted too)
+        without labels, with cfg.opt.discrete (default True).  Returns the 0-dim device loss."""
         self._refuse_condition(condition, "update")
-        if not torch.device(self.device).type == "cuda" or not torch.cuda.is_available():
-            raise RuntimeError("CompletionTrainer.update: device %s; the HIP path has no CPU fallback" % (self.device,))
-        point = data["tr_points"] if isinstance(data, dict) else data
-        if self.itr > 0:
-            self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
-        try:
-            with torch.no_grad():
-                self.compressor.eval()
-                eps = self.compressor(point.to(self.device))["all_eps"]
-            loss = self.update_score(eps, cates=None, discrete=getattr(self.cfg.opt, "discrete", True), condition=condition)
-        finally:
-            if self.itr > 0:
-                self.optimizer.swap_parameters_with_ema(store_params_in_ema=True)
-        self.itr += 1
-        return loss
+        self._refuse_host("CompletionTrainer.update")
+        return self._update(None, data["tr_points"] if isinstance(data, dict) else data, getattr(self.cfg.opt, "discrete", True), condition)
 
     def update_score(self, eps, condition=None, cates=None, discrete=True, *, t_index=None, eta=None, seed=None):
         """The reference's `update_score` (:113-145) with a condition pair: `Trainer.update_score`'s step (warm-up, times, `xt`, the loss,
@@ -492,22 +440,20 @@ class CompletionTrainer(Trainer):
         are accumulated (:203-205).  The `part_ep / smp_ep / ref_ep<epoch>.npy` dumps of :216-227 are written when
         cfg.log.save_path is set (save_npy=None) or on request (save_npy=True).  vis=True (mitsuba rendering, :208-213) is
         out of scope and raises.  Returns {'cd', 'f1', 'f1score', 'rate', 'samples', 'refs', 'parts'}."""
-        import os
         import numpy as np
         from . import ops
         from .metrics import F1Score, L2_ChamferEval_1000
-        if vis:
-            raise NotImplementedError("valsample(vis=True): mitsuba rendering (tools/vis_utils.py) is not on this path")
+        evalloop.refuse_vis("valsample", vis)
         self.model.eval(); self.compressor.eval()
         all_ref, all_smp, all_part, use_time, count = [], [], [], 0., 0
         for views, pc, pc_part in test_loader:
             pc, pc_part = pc.to(self.device).float().contiguous(), pc_part.to(self.device).float().contiguous()
             ref_pts = ops.gather_rows(pc, ops.fps(pc, min(2048, pc.shape[1])))
             part = ops.gather_rows(pc_part, ops.fps(pc_part, min(2048, pc_part.shape[1])))
-            torch.cuda.synchronize()
+            _sync(self.device)
             t0 = time.time()
             smp = self.sample(num_samples=ref_pts.size(0), condition={"img": views.float(), "pts": part})
-            torch.cuda.synchronize()
+            _sync(self.device)
             use_time += time.time() - t0
             all_smp.append(smp); all_ref.append(ref_pts); all_part.append(part)
             count += smp.shape[0]
@@ -523,11 +469,6 @@ class CompletionTrainer(Trainer):
         print("Validation Sample (unit) Epoch:%d " % self.epoch, {"cd": float(cd), "f1score": float(f1.mean())})
         return {"cd": float(cd), "f1": float(f1.mean()), "f1score": float(f1.mean()), "rate": smp.shape[0] / max(use_time, 1e-9),
                 "samples": smp, "refs": ref, "parts": part}
-
-
-def _sync(device):
-    if torch.device(device).type == "cuda":
-        torch.cuda.synchronize()
 
 
 def _rows(t, lo, hi, per):
