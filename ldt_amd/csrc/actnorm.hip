@@ -1,5 +1,6 @@
-// Backward of ldt_actnorm (gfx950): z = (x - shift) * exp(-log_scale), shift and log_scale shared by the B samples (model/layers.py:103-107;
-// the parameters :66-72).  From the gradient dz and the forward's OUTPUT z (the forward runs in place: z is what the tape holds):
+// ActNorm (gfx950): z = (x - shift) * exp(-log_scale), shift and log_scale shared by the B samples (model/layers.py:103-107; the parameters
+// :66-72).  actnorm_kernel is the forward (ldt_actnorm, in place); actnorm_bwd_kernel and actnorm_bwd_combine_kernel are its backward
+// (ldt_actnorm_bwd).  From the gradient dz and the forward's OUTPUT z (the forward runs in place: z is what the tape holds):
 //     dx[b][i] = dz[b][i] * exp(-log_scale[i]),   dshift[i] = -sum_b dx[b][i],   dlog_scale[i] = -sum_b dz[b][i] * z[b][i].
 // One streaming kernel: a thread owns V columns (V = 4: 16-byte accesses; V = 1: the scalar form of the same kernel) and a contiguous run of
 // rows; what it shares with the reductions of score_bwd.hip:
@@ -11,7 +12,23 @@
 #include "../../include/ldt_hip.h"
 #include "kernels.h"
 
-#define ANB_COLS 16                  // column groups (of V columns) per workgroup
+// forward (eval): y[b,t,c] = (x[b,t,c] - shift[t,c]) * exp(-log_scale[t,c]), in place
+__global__ void actnorm_kernel(float* __restrict__ x, const float* __restrict__ shift, const float* __restrict__ log_scale,
+                               long total, long per_sample) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long j = i % per_sample;
+        x[i] = (x[i] - shift[j]) * expf(-log_scale[j]);
+    }
+}
+extern "C" int ldt_actnorm(float* x, const float* shift, const float* log_scale, int64_t B, int64_t per_sample, void* stream) {
+    LDT_REQUIRE(x && shift && log_scale, LDT_EARG, "actnorm: null pointer");
+    LDT_REQUIRE(B > 0 && per_sample > 0, LDT_ESHAPE, "actnorm: bad shape");
+    const long total = B * per_sample;
+    hipLaunchKernelGGL(actnorm_kernel, dim3(ldt_grid_1d(total, 256, 4096)), dim3(256), 0, ldt_stream(stream), x, shift, log_scale, total, (long)per_sample);
+    return ldt_check_launch("actnorm");
+}
+
+#define ANB_COLS 16                 // column groups (of V columns) per workgroup
 #define ANB_SLICES 16                // row runs per workgroup
 #define ANB_ROWS 512                 // rows per workgroup: more rows take a second stage
 
@@ -109,8 +126,11 @@ __global__ __launch_bounds__(256) void actnorm_bwd_combine_kernel(const double* 
     if (dlog_scale) dlog_scale[i] = (float)(-c);
 }
 
-int ldt_actnorm_bwd_launch(const float* dz, const float* z, const float* log_scale, long B, long per_sample, float* dx, float* dshift,
-                           float* dlog_scale, hipStream_t s) {
+extern "C" int ldt_actnorm_bwd(const float* dz, const float* z, const float* log_scale, int64_t B, int64_t per_sample, float* dx, float* dshift,
+                               float* dlog_scale, void* stream) {
+    LDT_REQUIRE(dz && log_scale && dx && (z || !dlog_scale), LDT_EARG, "actnorm_bwd: null pointer (dlog_scale needs z)");
+    LDT_REQUIRE(B >= 1 && per_sample >= 1, LDT_EARG, "actnorm_bwd: B %ld, per_sample %ld", (long)B, (long)per_sample);
+    hipStream_t s = ldt_stream(stream);
     const bool sums = dshift || dlog_scale;
     const bool vec = per_sample % 4 == 0 && ldt_aligned16(dz) && ldt_aligned16(dx) && ldt_aligned16(log_scale) && (!dlog_scale || ldt_aligned16(z));
     const int V = vec ? 4 : 1;

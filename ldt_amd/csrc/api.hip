@@ -1,5 +1,6 @@
-// C-ABI of libldt_hip.so (include/ldt_hip.h): argument marshalling, error reporting, and the two
-// host-side orchestrators that enqueue the whole Score forward / reverse-SDE loop on one HIP stream.
+// C-ABI of libldt_hip.so (include/ldt_hip.h), the part that is not one op: the error state, the GEMM and attention entries (they build
+// GemmArgs / AttnArgs for the launchers of the kernel families), and the two host-side orchestrators that enqueue the whole Score forward /
+// reverse-SDE loop on one HIP stream.  Every other op's entry is in the file of its kernel.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,10 +31,7 @@ int ldt_check_launch(const char* what) {
 extern "C" const char* ldt_last_error(void) { return g_err; }
 extern "C" int ldt_abi_version(void) { return LDT_ABI_VERSION; }
 
-// ------------------------------------------------------------------------------ internal launchers
-#define BF(p) reinterpret_cast<const bf16_t*>(p)
-#define BFM(p) reinterpret_cast<bf16_t*>(p)
-#define ST(s) reinterpret_cast<hipStream_t>(s)
+// ------------------------------------------------------------------------------ argument blocks
 #define TRY(expr)                   \
     do {                            \
         const int _rc = (expr);     \
@@ -60,23 +58,17 @@ static void gemm_add_attention(GemmArgs& a, bf16_t* attn_o, float scale_log2e, c
     a.attn_o = attn_o; a.attn_scale_log2e = scale_log2e; a.attn_k = k; a.attn_v = v; a.attn_ldkv = ldkv; a.attn_kv_batch_stride = kv_batch_stride;
 }
 
-// ------------------------------------------------------------------------------ primitive ops
-extern "C" int ldt_cast_pad_bf16(const float* src, int64_t ld_src, uint16_t* dst, int64_t ld_dst, int64_t rows,
-                                 int32_t cols, int32_t cols_pad, void* stream) {
-    LDT_REQUIRE(src && dst, LDT_EARG, "cast_pad: null pointer");
-    return ldt_cast_pad_launch(src, ld_src, BFM(dst), ld_dst, rows, cols, cols_pad, ST(stream));
-}
-
+// ------------------------------------------------------------------------------ GEMM and attention entries
 extern "C" int ldt_gemm_bf16(int32_t epilogue, const uint16_t* X, int64_t ldx, const uint16_t* W, int64_t ldw,
                              const float* bias, void* out, int64_t ldo, const float* resid, int64_t ldr,
                              const uint16_t* skip, int64_t ldskip, const float* gate, int64_t gate_sample_stride,
                              int32_t rows_per_sample, const int32_t* step_ptr, int64_t gate_step_stride,
                              int32_t M, int32_t N, int32_t K, void* stream) {
     LDT_REQUIRE(X && W && out, LDT_EARG, "gemm: null pointer");
-    GemmArgs a = gemm_args(BF(X), ldx, BF(W), ldw, bias, out, ldo, M, N, K, 0);
+    GemmArgs a = gemm_args(ldt_bf16(X), ldx, ldt_bf16(W), ldw, bias, out, ldo, M, N, K, 0);
     gemm_add_gated_resid(a, resid, ldr, gate, gate_sample_stride, rows_per_sample, step_ptr, gate_step_stride);
-    a.skip = BF(skip); a.lds_ = ldskip;
-    return ldt_gemm_launch(epilogue, &a, ST(stream));
+    a.skip = ldt_bf16(skip); a.lds_ = ldskip;
+    return ldt_gemm_launch(epilogue, &a, ldt_stream(stream));
 }
 
 extern "C" int ldt_gemm_resid_lnstats(const uint16_t* X, int64_t ldx, const uint16_t* W, int64_t ldw, const float* bias,
@@ -86,10 +78,10 @@ extern "C" int ldt_gemm_resid_lnstats(const uint16_t* X, int64_t ldx, const uint
                                       int64_t ln_step_stride, int32_t M, int32_t N, int32_t K, int32_t stats_parts, void* stream) {
     LDT_REQUIRE(X && W && out && xs && ln_scale && stats_out, LDT_EARG, "gemm_resid_lnstats: null pointer");
     LDT_REQUIRE(stats_parts == N / 256 || stats_parts == N / 32, LDT_EARG, "gemm_resid_lnstats: stats_parts=%d is neither N/256 nor N/32 (N=%d)", stats_parts, N);
-    GemmArgs a = gemm_args(BF(X), ldx, BF(W), ldw, bias, out, ldo, M, N, K, 0);
+    GemmArgs a = gemm_args(ldt_bf16(X), ldx, ldt_bf16(W), ldw, bias, out, ldo, M, N, K, 0);
     gemm_add_gated_resid(a, out, ldo, gate, gate_sample_stride, rows_per_sample, step_ptr, gate_step_stride);
-    gemm_add_fold_producer(a, BFM(xs), ldxs, ln_scale, ln_step_stride, stats_out, stats_parts);
-    return ldt_gemm_lnfold_launch(EPI_RESID_F32, &a, ST(stream));
+    gemm_add_fold_producer(a, ldt_bf16_mut(xs), ldxs, ln_scale, ln_step_stride, stats_out, stats_parts);
+    return ldt_gemm_lnfold_launch(EPI_RESID_F32, &a, ldt_stream(stream));
 }
 
 extern "C" int ldt_gemm_lnfold(int32_t epilogue, const uint16_t* Xs, int64_t ldx, const uint16_t* W, int64_t ldw,
@@ -98,27 +90,18 @@ extern "C" int ldt_gemm_lnfold(int32_t epilogue, const uint16_t* Xs, int64_t ldx
                                void* stream) {
     LDT_REQUIRE(Xs && W && out && stats_in && fold_S && fold_C, LDT_EARG, "gemm_lnfold: null pointer");
     LDT_REQUIRE(stats_parts == K / 256 || stats_parts == K / 32, LDT_EARG, "gemm_lnfold: stats_parts=%d is neither K/256 nor K/32 (K=%d)", stats_parts, K);
-    GemmArgs a = gemm_args(BF(Xs), ldx, BF(W), ldw, nullptr, out, ldo, M, N, K, 0);
+    GemmArgs a = gemm_args(ldt_bf16(Xs), ldx, ldt_bf16(W), ldw, nullptr, out, ldo, M, N, K, 0);
     gemm_add_fold_consumer(a, stats_in, stats_parts, fold_S, fold_C, fold_step_stride, step_ptr);
-    return ldt_gemm_lnfold_launch(epilogue, &a, ST(stream));
-}
-
-extern "C" int ldt_layernorm_modulate(const float* x, int64_t ldx, uint16_t* y, int64_t ldy, const float* w,
-                                      const float* b, const float* shift, const float* scale,
-                                      int64_t mod_sample_stride, int32_t rows_per_sample, const int32_t* step_ptr,
-                                      int64_t mod_step_stride, int64_t M, int32_t C, void* stream) {
-    LDT_REQUIRE(x && y, LDT_EARG, "ln: null pointer");
-    LnArgs a{x, ldx, BFM(y), ldy, w, b, shift, scale, mod_sample_stride, rows_per_sample, step_ptr, mod_step_stride, M, C};
-    return ldt_ln_launch(&a, ST(stream));
+    return ldt_gemm_lnfold_launch(epilogue, &a, ldt_stream(stream));
 }
 
 extern "C" int ldt_attention_fwd(const uint16_t* Q, int64_t ldq, int64_t q_batch_stride, const uint16_t* K,
                                  int64_t ldk, const uint16_t* V, int64_t ldv, int64_t kv_batch_stride, uint16_t* O,
                                  int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim, void* stream) {
     LDT_REQUIRE(Q && K && V && O, LDT_EARG, "attention: null pointer");
-    AttnArgs a{BF(Q), ldq, q_batch_stride, BF(K), ldk, kv_batch_stride, BF(V), ldv, BFM(O), B, H, Nq, Nk,
+    AttnArgs a{ldt_bf16(Q), ldq, q_batch_stride, ldt_bf16(K), ldk, kv_batch_stride, ldt_bf16(V), ldv, ldt_bf16_mut(O), B, H, Nq, Nk,
                1.4426950408889634f / sqrtf((float)head_dim), nullptr, nullptr, nullptr, 0, nullptr, 0};
-    return ldt_attn_launch(&a, head_dim, ST(stream));
+    return ldt_attn_launch(&a, head_dim, ldt_stream(stream));
 }
 extern "C" int ldt_attention_route(int32_t B, int32_t H, int32_t Nq, int32_t Nk, int32_t head_dim) { return ldt_attn_route(B, H, Nq, Nk, head_dim); }
 extern "C" int ldt_gemm_route(int32_t epilogue, int32_t M, int32_t N, int32_t K, int64_t ldo, int32_t fold, int32_t max_wgs) {
@@ -134,156 +117,9 @@ extern "C" int ldt_attention_oproj_resid(const uint16_t* Q, int64_t ldq, int64_t
                                          const uint16_t* Wo, const float* bo, float* X, int64_t ldx, const float* gate,
                                          int64_t gate_sample_stride, void* stream) {
     LDT_REQUIRE(Q && K && V && Wo && bo && X, LDT_EARG, "attention_oproj: null pointer");
-    AttnArgs a{BF(Q), ldq, q_batch_stride, BF(K), ldk, kv_batch_stride, BF(V), ldv, nullptr, B, H, Nq, Nk,
-               1.4426950408889634f / sqrtf((float)head_dim), BF(Wo), bo, X, ldx, gate, gate_sample_stride};
-    return ldt_attn_oproj_launch(&a, head_dim, ST(stream));
-}
-
-extern "C" int ldt_sgemm(const float* A, int64_t lda, const float* Bw, int64_t ldb, const float* bias, void* C,
-                         int64_t ldc, int32_t out_bf16, int32_t act_in, int32_t act_out, int32_t M, int32_t N,
-                         int32_t K, void* stream) {
-    SgemmArgs a{A, lda, Bw, ldb, bias, C, ldc, out_bf16, act_in, act_out, M, N, K};
-    return ldt_sgemm_launch(&a, ST(stream));
-}
-extern "C" int ldt_sgemm_route(int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t misaligned) {
-    return ldt_sgemm_decide(M, N, K, lda, ldb, ldc, misaligned);
-}
-
-extern "C" int ldt_sinusoid(const float* t, const float* freq, float* e, int32_t n, int32_t half, void* stream) {
-    LDT_REQUIRE(t && freq && e, LDT_EARG, "sinusoid: null pointer");
-    return ldt_sinusoid_launch(t, freq, e, n, half, ST(stream));
-}
-
-extern "C" int ldt_sampler_step(const float* x, const float* params, const float* noise, int64_t noise_step_stride,
-                                float* x_out, float* x_mean_out, const float* coef, const int32_t* step_ptr,
-                                int32_t step_host, int32_t mode, int64_t n, int64_t elem_offset, uint64_t seed,
-                                int32_t philox_mul, int32_t philox_add, void* stream) {
-    StepArgs a{x, params, noise, x_out, x_mean_out, coef, step_ptr, step_host, mode, n, elem_offset, noise_step_stride,
-               (uint32_t)seed, (uint32_t)(seed >> 32), philox_mul, philox_add};
-    return ldt_sampler_step_launch(&a, ST(stream));
-}
-extern "C" int ldt_sampler_step_traj(const float* x, const float* params, const float* noise, int64_t noise_step_stride,
-                                     float* x_out, float* x_mean_out, float* traj, const float* coef, const int32_t* step_ptr,
-                                     int32_t step_host, int32_t mode, int64_t n, int64_t elem_offset, uint64_t seed,
-                                     int32_t philox_mul, int32_t philox_add, void* stream) {
-    LDT_REQUIRE(!traj || ldt_aligned16(traj), LDT_EALIGN, "sampler_step_traj: traj must be 16-byte aligned");
-    StepArgs a{x, params, noise, x_out, x_mean_out, coef, step_ptr, step_host, mode, n, elem_offset, noise_step_stride,
-               (uint32_t)seed, (uint32_t)(seed >> 32), philox_mul, philox_add, traj};
-    return ldt_sampler_step_launch(&a, ST(stream));
-}
-
-extern "C" int ldt_philox_normal(float* out, int64_t n, int64_t elem_offset, int32_t step, uint64_t seed, void* stream) {
-    LDT_REQUIRE(out, LDT_EARG, "philox_normal: null pointer");
-    return ldt_philox_normal_launch(out, n, elem_offset, step, (uint32_t)seed, (uint32_t)(seed >> 32), ST(stream));
-}
-
-// ------------------------------------------------------------------------------ Compressor encoder front end
-extern "C" int ldt_fps(const float* xyz, int32_t B, int32_t n, int32_t m, int32_t skip_near_origin, int32_t* idx_out, void* stream) {
-    LDT_REQUIRE(xyz && idx_out, LDT_EARG, "fps: null pointer");
-    return ldt_fps_launch(xyz, B, n, m, skip_near_origin, idx_out, ST(stream));
-}
-extern "C" int ldt_knn(const float* xyz, const float* centers, int32_t B, int32_t n, int32_t S, int32_t k,
-                       int32_t* idx_out, float* dist_out, void* stream) {
-    LDT_REQUIRE(xyz && centers && idx_out, LDT_EARG, "knn: null pointer");
-    return ldt_knn_launch(xyz, centers, B, n, S, k, idx_out, dist_out, ST(stream));
-}
-extern "C" int ldt_group_normalize(const float* feat, const float* xyz, const int32_t* fps_idx, const int32_t* knn_idx,
-                                   const float* alpha, const float* beta, double* stats, int32_t B, int32_t n, int32_t S,
-                                   int32_t k, int32_t D, uint16_t* U, int32_t ldu, int32_t center_mode, float* group_mean,
-                                   void* stream) {
-    LDT_REQUIRE(feat && xyz && fps_idx && knn_idx && alpha && beta && stats && U, LDT_EARG, "group: null pointer");
-    return ldt_group_launch(feat, xyz, fps_idx, knn_idx, alpha, beta, stats, B, n, S, k, D, BFM(U), ldu, center_mode, group_mean,
-                            ST(stream));
-}
-extern "C" int ldt_grouper_mlp(const float* feat, const float* xyz, const int32_t* fps_idx, const int32_t* knn_idx, const float* alpha,
-                               const float* beta, double* stats, int32_t B, int32_t n, int32_t S, int32_t k, int32_t D,
-                               const uint16_t* wimg, const float* b1, const float* b2, const float* b3, float* out, void* stream) {
-    LDT_REQUIRE(feat && xyz && fps_idx && knn_idx && alpha && beta && stats && wimg && b1 && b2 && b3 && out, LDT_EARG, "grouper_mlp: null pointer");
-    LDT_REQUIRE(D == 128, LDT_ESHAPE, "grouper_mlp: the fused kernel is built for 128 channels (got D=%d)", D);
-    const int rc = ldt_group_stats_launch(feat, xyz, fps_idx, knn_idx, stats, B, n, S, k, D, ST(stream));
-    if (rc != LDT_OK) return rc;
-    GroupMlpArgs a{feat, xyz, fps_idx, knn_idx, alpha, beta, stats, BF(wimg), b1, b2, b3, B, n, S, k, 0, out};
-    return ldt_grouper_mlp_launch(&a, ST(stream));
-}
-extern "C" int ldt_norm_points(const float* xyz, int32_t B, int32_t n, float* out, void* stream) {
-    LDT_REQUIRE(xyz && out, LDT_EARG, "norm_points: null pointer");
-    return ldt_norm_points_launch(xyz, B, n, out, ST(stream));
-}
-extern "C" int ldt_mixture_seed(const float* eps, const float* sig, const float* mu, const float* logits, int32_t n_mix, int32_t D, int64_t rows,
-                                float* out, void* stream) {
-    LDT_REQUIRE(eps && sig && mu && logits && out, LDT_EARG, "mixture_seed: null pointer");
-    return ldt_mixture_seed_launch(eps, sig, mu, logits, n_mix, D, rows, out, ST(stream));
-}
-extern "C" int ldt_gather_rows(const float* src, const int32_t* idx, int32_t B, int32_t n, int32_t S, int32_t C, float* out, void* stream) {
-    LDT_REQUIRE(src && idx && out, LDT_EARG, "gather_rows: null pointer");
-    return ldt_gather_rows_launch(src, idx, B, n, S, C, out, ST(stream));
-}
-extern "C" int ldt_maxpool(const void* in, int32_t in_bf16, int64_t ld, int64_t G, int32_t n, int32_t C, float* out, void* stream) {
-    LDT_REQUIRE(in && out, LDT_EARG, "maxpool: null pointer");
-    return ldt_maxpool_launch(in, in_bf16, ld, G, n, C, out, ST(stream));
-}
-extern "C" int ldt_actnorm(float* x, const float* shift, const float* log_scale, int64_t B, int64_t per_sample, void* stream) {
-    LDT_REQUIRE(x && shift && log_scale, LDT_EARG, "actnorm: null pointer");
-    return ldt_actnorm_launch(x, shift, log_scale, B, per_sample, ST(stream));
-}
-extern "C" int ldt_actnorm_bwd(const float* dz, const float* z, const float* log_scale, int64_t B, int64_t per_sample, float* dx, float* dshift,
-                               float* dlog_scale, void* stream) {
-    LDT_REQUIRE(dz && log_scale && dx && (z || !dlog_scale), LDT_EARG, "actnorm_bwd: null pointer (dlog_scale needs z)");
-    LDT_REQUIRE(B >= 1 && per_sample >= 1, LDT_EARG, "actnorm_bwd: B %ld, per_sample %ld", (long)B, (long)per_sample);
-    return ldt_actnorm_bwd_launch(dz, z, log_scale, B, per_sample, dx, dshift, dlog_scale, ST(stream));
-}
-extern "C" int ldt_reparam(const float* post, const float* noise, float* out, int64_t ldo, float* mu_out, float* logvar_out,
-                           int64_t rows, int32_t z, float lo, float hi, void* stream) {
-    LDT_REQUIRE(post && noise && out, LDT_EARG, "reparam: null pointer");
-    return ldt_reparam_launch(post, noise, out, ldo, mu_out, logvar_out, rows, z, lo, hi, ST(stream));
-}
-extern "C" int ldt_chamfer(const float* a, const float* b, int32_t B, int32_t na, int32_t nb, float* dl, float* dr, void* stream) {
-    LDT_REQUIRE(a && b && dl && dr, LDT_EARG, "chamfer: null pointer");
-    return ldt_chamfer_launch(a, b, B, na, nb, dl, dr, ST(stream));
-}
-
-// the arguments that ldt_ln_mlp_resid and ldt_ln_mlp_resid_next share (no chained projection: next.w == null)
-static MlpArgs mlp_args(float* x, int64_t ldx, int64_t M, const float* ln_w, const float* ln_b, const float* shift, const float* scale,
-                        const float* gate, int64_t mod_sample_stride, int32_t rows_per_sample, const uint16_t* w_up, const float* b_up,
-                        const uint16_t* w_dn, const float* b_dn, uint16_t* x_bf16, int64_t ldxb) {
-    return MlpArgs{x, ldx, M, ln_w, ln_b, shift, scale, gate, mod_sample_stride, rows_per_sample, BF(w_up), b_up, BF(w_dn), b_dn, BFM(x_bf16), ldxb};
-}
-extern "C" int ldt_ln_mlp_resid(float* x, int64_t ldx, int64_t M, int32_t C, const float* ln_w, const float* ln_b,
-                                const float* shift, const float* scale, const float* gate, int64_t mod_sample_stride,
-                                int32_t rows_per_sample, const uint16_t* w_up, const float* b_up, const uint16_t* w_dn,
-                                const float* b_dn, uint16_t* x_bf16, int64_t ldxb, void* stream) {
-    LDT_REQUIRE(x && w_up && b_up && w_dn && b_dn, LDT_EARG, "ln_mlp: null pointer");
-    const MlpArgs a = mlp_args(x, ldx, M, ln_w, ln_b, shift, scale, gate, mod_sample_stride, rows_per_sample, w_up, b_up, w_dn, b_dn, x_bf16, ldxb);
-    return ldt_ln_mlp_launch(&a, C, ST(stream));
-}
-extern "C" int ldt_ln_mlp_resid_next(float* x, int64_t ldx, int64_t M, int32_t C, const float* ln_w, const float* ln_b,
-                                     const float* shift, const float* scale, const float* gate, int64_t mod_sample_stride,
-                                     int32_t rows_per_sample, const uint16_t* w_up, const float* b_up, const uint16_t* w_dn,
-                                     const float* b_dn, uint16_t* x_bf16, int64_t ldxb,
-                                     const float* nx_ln_w, const float* nx_ln_b, const float* nx_shift, const float* nx_scale,
-                                     int64_t nx_mod_sample_stride, int32_t nx_rows_per_sample, const uint16_t* nx_w, const float* nx_bias,
-                                     int32_t nx_N, uint16_t* nx_out, int64_t nx_ldo, void* stream) {
-    LDT_REQUIRE(x && w_up && b_up && w_dn && b_dn && nx_w && nx_out, LDT_EARG, "ln_mlp_next: null pointer");
-    MlpArgs a = mlp_args(x, ldx, M, ln_w, ln_b, shift, scale, gate, mod_sample_stride, rows_per_sample, w_up, b_up, w_dn, b_dn, x_bf16, ldxb);
-    a.next = LnLinArgs{nullptr, 0, M, nx_ln_w, nx_ln_b, nx_shift, nx_scale, nx_mod_sample_stride, nx_rows_per_sample, BF(nx_w), nx_bias,
-                       nx_N, BFM(nx_out), nx_ldo};
-    return ldt_ln_mlp_launch(&a, C, ST(stream));
-}
-extern "C" int ldt_ln_linear(const float* x, int64_t ldx, int64_t M, int32_t C, const float* ln_w, const float* ln_b,
-                             const float* shift, const float* scale, int64_t mod_sample_stride, int32_t rows_per_sample,
-                             const uint16_t* w, const float* bias, int32_t N, uint16_t* out, int64_t ldo, void* stream) {
-    LDT_REQUIRE(x && w && out, LDT_EARG, "ln_linear: null pointer");
-    LnLinArgs a{x, ldx, M, ln_w, ln_b, shift, scale, mod_sample_stride, rows_per_sample, BF(w), bias, N, BFM(out), ldo};
-    return ldt_ln_linear_launch(&a, C, ST(stream));
-}
-extern "C" int ldt_chamfer_pairwise(const float* x, const float* y, int32_t S, int32_t R, int32_t n, int32_t m, float* cd, void* stream) {
-    LDT_REQUIRE(x && y && cd, LDT_EARG, "chamfer_pairwise: null pointer");
-    return ldt_chamfer_pairwise_launch(x, y, S, R, n, m, cd, ST(stream));
-}
-extern "C" int ldt_emd_approx(const float* x, const float* y, int32_t S, int32_t R, int32_t n, int32_t m, int32_t pairwise,
-                              float* out, void* stream) {
-    LDT_REQUIRE(x && y && out, LDT_EARG, "emd_approx: null pointer");
-    return ldt_emd_approx_launch(x, y, S, R, n, m, pairwise, out, ST(stream));
+    AttnArgs a{ldt_bf16(Q), ldq, q_batch_stride, ldt_bf16(K), ldk, kv_batch_stride, ldt_bf16(V), ldv, nullptr, B, H, Nq, Nk,
+               1.4426950408889634f / sqrtf((float)head_dim), ldt_bf16(Wo), bo, X, ldx, gate, gate_sample_stride};
+    return ldt_attn_oproj_launch(&a, head_dim, ldt_stream(stream));
 }
 
 // ------------------------------------------------------------------------------ Score forward
@@ -401,11 +237,11 @@ extern "C" int ldt_qkv_attention(const uint16_t* X, int64_t ldx, const uint16_t*
     LDT_REQUIRE(!kv_cond || (cond_tokens > 0 && !stats), LDT_EARG, "qkv_attention: cross-attention needs cond_tokens and has no folded form");
     LDT_REQUIRE(!stats || (fold_S && fold_C && stats_parts > 0 && !bias), LDT_EARG, "qkv_attention: the folded form needs fold_S, fold_C, stats_parts and takes no bias (it is part of fold_C)");
     QkvAttnStep q{};
-    q.X = BF(X); q.ldx = ldx; q.W = BF(W); q.ldw = ldw; q.bias = bias;
+    q.X = ldt_bf16(X); q.ldx = ldx; q.W = ldt_bf16(W); q.ldw = ldw; q.bias = bias;
     q.stats = stats; q.stats_parts = stats_parts; q.fold_S = fold_S; q.fold_C = fold_C; q.fold_step_stride = fold_step_stride;
-    q.kv = BF(kv_cond); q.ldkv = ldkv; q.kv_batch_stride = kv_batch_stride; q.attn_o = BFM(O); q.QKV = BFM(QKV);
+    q.kv = ldt_bf16(kv_cond); q.ldkv = ldkv; q.kv_batch_stride = kv_batch_stride; q.attn_o = ldt_bf16_mut(O); q.QKV = ldt_bf16_mut(QKV);
     q.B = B; q.tokens = tokens; q.cond_tokens = cond_tokens; q.hidden = hidden; q.heads = heads; q.K = K; q.max_wgs = max_wgs; q.step_ptr = step_ptr;
-    return qkv_attention_step(q, ST(stream), nullptr);
+    return qkv_attention_step(q, ldt_stream(stream), nullptr);
 }
 
 static int score_forward_impl(const ldt_score_plan* p, const float* x, float* eps_out, const int32_t* step_ptr,
@@ -424,49 +260,49 @@ static int score_forward_impl(const ldt_score_plan* p, const float* x, float* ep
     const int sparts = D / sf.granule;                          // row-statistics partials per row in plan->stats ([sparts][M][2])
     const long fstep = p->fold_step_stride, fblk = 6L * D + 2L * F;   // per block: S_qkv[3D] | C_qkv[3D] | S_up[F] | C_up[F]
     // ln_in (score.py:136-137): latents fp32 -> bf16 (K padded) -> X fp32
-    LAUNCH(LDT_PROF_OTHER, ldt_cast_pad_launch(x, p->z_dim, BFM(p->xin), p->z_pad, M, p->z_dim, p->z_pad, s));
-    const GemmArgs g_in = gemm_args(BF(p->xin), p->z_pad, BF(p->w_in), p->z_pad, p->b_in, p->X, D, M, D, p->z_pad, p->gemm_wgs);
+    LAUNCH(LDT_PROF_OTHER, ldt_cast_pad_launch(x, p->z_dim, ldt_bf16_mut(p->xin), p->z_pad, M, p->z_dim, p->z_pad, s));
+    const GemmArgs g_in = gemm_args(ldt_bf16(p->xin), p->z_pad, ldt_bf16(p->w_in), p->z_pad, p->b_in, p->X, D, M, D, p->z_pad, p->gemm_wgs);
     LAUNCH(LDT_PROF_GEMM_IO, ldt_gemm_launch(LDT_EPI_F32, &g_in, s));
     for (int l = 0; l < p->blocks; ++l) {                       // score.py:148-149, layers.py:212-219
         const float* m = p->mod + (long)l * 6 * D;              // shift_msa|scale_msa|gate_msa|shift_mlp|scale_mlp|gate_mlp
         const float* fl = fold ? p->fold + (long)l * fblk : nullptr;
         QkvAttnStep qa{};
-        qa.X = BF(p->Hb); qa.ldx = D; qa.ldw = D; qa.attn_o = BFM(p->Ob); qa.QKV = BFM(p->QKV);
+        qa.X = ldt_bf16(p->Hb); qa.ldx = D; qa.ldw = D; qa.attn_o = ldt_bf16_mut(p->Ob); qa.QKV = ldt_bf16_mut(p->QKV);
         qa.B = p->batch; qa.tokens = T; qa.cond_tokens = p->cond_tokens; qa.hidden = D; qa.heads = p->heads; qa.K = D; qa.max_wgs = p->gemm_wgs; qa.step_ptr = step_ptr;
         if (fold && l > 0) {                                    // Hb = x (1 + scale_msa) and the row statistics came from block l-1's mlp.out
-            qa.W = BF(p->w_qkv[l]);
+            qa.W = ldt_bf16(p->w_qkv[l]);
             qa.stats = p->stats; qa.stats_parts = sparts; qa.fold_S = fl; qa.fold_C = fl + 3L * D; qa.fold_step_stride = fstep;
         } else {
-            LnArgs n1{p->X, D, BFM(p->Hb), D, nullptr, nullptr, m, m + D, sstr, T, step_ptr, tstr, M, D};
+            LnArgs n1{p->X, D, ldt_bf16_mut(p->Hb), D, nullptr, nullptr, m, m + D, sstr, T, step_ptr, tstr, M, D};
             LAUNCH(LDT_PROF_LN, ldt_ln_launch(&n1, s));
             if (p->kv_cond[l]) {                                // cross-attention: q from the modulated x, K|V from the condition
-                qa.W = BF(p->w_q[l]); qa.bias = p->b_q[l];
-                qa.kv = BF(p->kv_cond[l]); qa.ldkv = 2L * D; qa.kv_batch_stride = (long)p->cond_tokens * 2 * D;
+                qa.W = ldt_bf16(p->w_q[l]); qa.bias = p->b_q[l];
+                qa.kv = ldt_bf16(p->kv_cond[l]); qa.ldkv = 2L * D; qa.kv_batch_stride = (long)p->cond_tokens * 2 * D;
             } else {                                            // self-attention: fused q|k|v projection of the modulated x
-                qa.W = BF(p->w_qkv[l]); qa.bias = p->b_qkv[l];
+                qa.W = ldt_bf16(p->w_qkv[l]); qa.bias = p->b_qkv[l];
             }
         }
         TRY(qkv_attention_step(qa, s, prof));
         // fc_o + gate + residual.  Folded: it also emits Hb = x (1 + scale_mlp) and the row statistics, which mlp.fc consumes
-        GemmArgs go = gemm_args(BF(p->Ob), D, BF(p->w_o[l]), D, p->b_o[l], p->X, D, M, D, D, p->gemm_wgs);
+        GemmArgs go = gemm_args(ldt_bf16(p->Ob), D, ldt_bf16(p->w_o[l]), D, p->b_o[l], p->X, D, M, D, D, p->gemm_wgs);
         gemm_add_gated_resid(go, p->X, D, m + 2 * D, sstr, T, step_ptr, tstr);
         if (fold) {
-            gemm_add_fold_producer(go, BFM(p->Hb), D, m + 4 * D, tstr, p->stats, sparts);
+            gemm_add_fold_producer(go, ldt_bf16_mut(p->Hb), D, m + 4 * D, tstr, p->stats, sparts);
             LAUNCH(LDT_PROF_GEMM_O, ldt_gemm_lnfold_launch(LDT_EPI_RESID_F32, &go, s));
             if (p->fold_monitor) TRY(ldt_fold_monitor_launch(p->stats, sparts, M, D, p->fold_monitor, s));
         } else {
-            LnArgs n2{p->X, D, BFM(p->Hb), D, nullptr, nullptr, m + 3 * D, m + 4 * D, sstr, T, step_ptr, tstr, M, D};
+            LnArgs n2{p->X, D, ldt_bf16_mut(p->Hb), D, nullptr, nullptr, m + 3 * D, m + 4 * D, sstr, T, step_ptr, tstr, M, D};
             LAUNCH(LDT_PROF_GEMM_O, ldt_gemm_launch(LDT_EPI_RESID_F32, &go, s));
             LAUNCH(LDT_PROF_LN, ldt_ln_launch(&n2, s));
         }
         // mlp.fc + GELU (folded: its bias is part of fold_C)
-        GemmArgs gu = gemm_args(BF(p->Hb), D, BF(p->w_up[l]), D, fold ? nullptr : p->b_up[l], p->U, F, M, F, D, p->gemm_wgs);
+        GemmArgs gu = gemm_args(ldt_bf16(p->Hb), D, ldt_bf16(p->w_up[l]), D, fold ? nullptr : p->b_up[l], p->U, F, M, F, D, p->gemm_wgs);
         if (fold) gemm_add_fold_consumer(gu, p->stats, sparts, fl + 6L * D, fl + 6L * D + F, fstep, step_ptr);
         LAUNCH(LDT_PROF_GEMM_GELU, fold ? ldt_gemm_lnfold_launch(LDT_EPI_GELU_BF16, &gu, s) : ldt_gemm_launch(LDT_EPI_GELU_BF16, &gu, s));
         // mlp.out + gate + residual.  Folded: Hb and the statistics for the next block's scale_msa; the last block's launches unfolded (FinalLayer's LN runs as a kernel)
-        GemmArgs gd = gemm_args(BF(p->U), F, BF(p->w_dn[l]), F, p->b_dn[l], p->X, D, M, D, F, p->gemm_wgs);
+        GemmArgs gd = gemm_args(ldt_bf16(p->U), F, ldt_bf16(p->w_dn[l]), F, p->b_dn[l], p->X, D, M, D, F, p->gemm_wgs);
         gemm_add_gated_resid(gd, p->X, D, m + 5 * D, sstr, T, step_ptr, tstr);
-        if (fold) gemm_add_fold_producer(gd, BFM(p->Hb), D, m + 6 * D + D, tstr, p->stats, sparts);
+        if (fold) gemm_add_fold_producer(gd, ldt_bf16_mut(p->Hb), D, m + 6 * D + D, tstr, p->stats, sparts);
         if (fold && l + 1 < p->blocks) {
             LAUNCH(LDT_PROF_GEMM_DN, ldt_gemm_lnfold_launch(LDT_EPI_RESID_F32, &gd, s));
             if (p->fold_monitor) TRY(ldt_fold_monitor_launch(p->stats, sparts, M, D, p->fold_monitor, s));
@@ -474,24 +310,24 @@ static int score_forward_impl(const ldt_score_plan* p, const float* x, float* ep
     }
     {                                                           // FinalLayer (layers.py:240-248)
         const float* m = p->mod + (long)p->blocks * 6 * D;
-        LnArgs nf{p->X, D, BFM(p->Hb), D, nullptr, nullptr, m, m + D, sstr, T, step_ptr, tstr, M, D};
+        LnArgs nf{p->X, D, ldt_bf16_mut(p->Hb), D, nullptr, nullptr, m, m + D, sstr, T, step_ptr, tstr, M, D};
         LAUNCH(LDT_PROF_LN, ldt_ln_launch(&nf, s));
-        const GemmArgs gf = gemm_args(BF(p->Hb), D, BF(p->w_out), D, p->b_out, eps_out, p->z_dim, M, p->z_dim, D, p->gemm_wgs);
+        const GemmArgs gf = gemm_args(ldt_bf16(p->Hb), D, ldt_bf16(p->w_out), D, p->b_out, eps_out, p->z_dim, M, p->z_dim, D, p->gemm_wgs);
         LAUNCH(LDT_PROF_GEMM_IO, ldt_gemm_launch(LDT_EPI_F32, &gf, s));
     }
     return LDT_OK;
 }
 
 extern "C" int ldt_score_forward(const ldt_score_plan* p, const float* x, float* eps_out, const int32_t* step_ptr, void* stream) {
-    return score_forward_impl(p, x, eps_out, step_ptr, ST(stream), nullptr);
+    return score_forward_impl(p, x, eps_out, step_ptr, ldt_stream(stream), nullptr);
 }
 
 extern "C" int ldt_score_forward_profile(const ldt_score_plan* p, const float* x, float* eps_out, const int32_t* step_ptr,
                                          float* ms_by_class, int32_t* launches_by_class, void* stream) {
     LDT_REQUIRE(ms_by_class && launches_by_class, LDT_EARG, "score_profile: null output");
-    Prof prof{ST(stream), {}, {}};
-    const int rc = score_forward_impl(p, x, eps_out, step_ptr, ST(stream), &prof);
-    (void)hipStreamSynchronize(ST(stream));
+    Prof prof{ldt_stream(stream), {}, {}};
+    const int rc = score_forward_impl(p, x, eps_out, step_ptr, ldt_stream(stream), &prof);
+    (void)hipStreamSynchronize(ldt_stream(stream));
     for (int c = 0; c < LDT_PROF_NCLASS; ++c) { ms_by_class[c] = 0.f; launches_by_class[c] = 0; }
     for (size_t i = 0; i < prof.cls.size(); ++i) {
         float ms = 0.f;
@@ -521,7 +357,7 @@ static int enqueue_step(const SampleStep& st, const ldt_score_plan* p, hipStream
     if (const ldt_cond_args* cond = st.cond) {                  // per-sample AdaLN rows of this step
         TRY(ldt_cond_rows_launch(cond->temb, cond->extra, cond->c_buf, cond->c_buf_bf16, st.step_counter, p->batch, cond->t_dim, 1, s));   // c_buf = silu(c)
         if (cond->w_ada_bf16 && (cond->t_dim % 64 == 0 || !cond->w_ada)) {   // bf16 weight panel: half the bytes of the HBM-bound row GEMM (fp32 accumulation + bias); a width the MFMA GEMM does not take falls back to the fp32 rows when they were given
-            const GemmArgs g = gemm_args(BF(cond->c_buf_bf16), cond->t_dim, BF(cond->w_ada_bf16), cond->t_dim, cond->b_ada, cond->mod_buf, cond->n_mod,
+            const GemmArgs g = gemm_args(ldt_bf16(cond->c_buf_bf16), cond->t_dim, ldt_bf16(cond->w_ada_bf16), cond->t_dim, cond->b_ada, cond->mod_buf, cond->n_mod,
                                          p->batch, cond->n_mod, cond->t_dim, p->gemm_wgs);
             TRY(ldt_gemm_launch(EPI_F32, &g, s));
         } else {
@@ -579,7 +415,7 @@ extern "C" int ldt_sample_loop(const ldt_score_plan* p, float* x, float* x_mean,
     LDT_REQUIRE(!cond || (cond->temb && (cond->w_ada || cond->w_ada_bf16) && cond->b_ada && cond->c_buf && cond->mod_buf && cond->mod_buf == p->mod &&
                           p->mod_sample_stride == cond->n_mod && cond->t_dim > 0), LDT_EARG,
                 "sample_loop: inconsistent conditioning block (plan->mod must be cond->mod_buf with sample stride n_mod)");
-    hipStream_t s = ST(stream);
+    hipStream_t s = ldt_stream(stream);
     const SampleStep st{x, x_mean, eps_tmp, x_traj, coef, noise, noise_step_stride, elem_offset, seed, mode, step_counter, cond};
     TRY(hip_ok(hipMemsetAsync(step_counter, 0, sizeof(int), s), "memset"));
     // LN-fold monitor inside the loop (plan->fold_monitor, every plan->fold_monitor_every steps and on the last one): the other steps run a

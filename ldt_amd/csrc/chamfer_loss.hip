@@ -49,7 +49,7 @@ extern "C" int ldt_chamfer_nn(const float* x1, const float* x2, int32_t B, int32
                               int32_t* idx2, void* stream) {
     LDT_REQUIRE(x1 && x2 && d1 && idx1 && d2 && idx2, LDT_EARG, "chamfer_nn: null pointer");
     LDT_REQUIRE(B > 0 && B <= 65535 && n > 0 && m > 0, LDT_ESHAPE, "chamfer_nn: B %d (1 .. 65535), n %d, m %d", B, n, m);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = ldt_stream(stream);
     hipLaunchKernelGGL(chamfer_nn_kernel, dim3((unsigned)((n + CDL_WG - 1) / CDL_WG), (unsigned)B), dim3(CDL_WG), 0, s, x1, x2, n, m, d1, idx1);
     const int rc = ldt_check_launch("chamfer_nn (x1 -> x2)");
     if (rc != LDT_OK) return rc;
@@ -96,7 +96,7 @@ extern "C" int ldt_cd_loss(const float* d1, int64_t n1, const float* d2, int64_t
     LDT_REQUIRE(d1 && d2 && out, LDT_EARG, "cd_loss: null pointer");
     LDT_REQUIRE(n1 > 0 && n2 > 0, LDT_ESHAPE, "cd_loss: %ld and %ld distances", (long)n1, (long)n2);
     LDT_REQUIRE(type == LDT_CD_L1 || type == LDT_CD_L2, LDT_EARG, "cd_loss: type %d is neither LDT_CD_L1 (1) nor LDT_CD_L2 (2)", type);
-    hipLaunchKernelGGL(cd_loss_kernel, dim3(1), dim3(CDL_WG), 0, reinterpret_cast<hipStream_t>(stream), d1, (long)n1, d2, (long)n2,
+    hipLaunchKernelGGL(cd_loss_kernel, dim3(1), dim3(CDL_WG), 0, ldt_stream(stream), d1, (long)n1, d2, (long)n2,
                        (int)(type == LDT_CD_L1), out);
     return ldt_check_launch("cd_loss");
 }
@@ -160,6 +160,6 @@ extern "C" int ldt_cd_loss_bwd(const float* x1, const float* x2, const int32_t* 
     const double f = (l1 ? 1.0 : 2.0) * (double)upstream;
     const float c1 = (float)(f / ((double)B * n)), c2 = (float)(f / ((double)B * m));
     hipLaunchKernelGGL(cd_loss_bwd_kernel, dim3((unsigned)((n + CDL_WG - 1) / CDL_WG), (unsigned)B), dim3(CDL_WG), 0,
-                       reinterpret_cast<hipStream_t>(stream), x1, x2, idx1, idx2, n, m, l1, c1, c2, dx1);
+                       ldt_stream(stream), x1, x2, idx1, idx2, n, m, l1, c1, c2, dx1);
     return ldt_check_launch("cd_loss_bwd");
 }

@@ -109,6 +109,16 @@ __device__ __forceinline__ f32x2 gelu_erf_fast2(f32x2 x) {
     return x * 0.5f + z * r;
 }
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
+// activation of the fp32 linear (SgemmArgs::act_in / act_out; every kernel form of sgemm.hip, sgemm_mfma.hip and skinny_linear.hip)
+enum { ACT_NONE = 0, ACT_SILU = 1, ACT_RELU = 2, ACT_GELU = 3 };
+__device__ __forceinline__ float ldt_act(float v, int act) {
+    switch (act) {
+        case ACT_SILU: return v / (1.0f + expf(-v));
+        case ACT_RELU: return fmaxf(v, 0.f);
+        case ACT_GELU: return gelu_erf(v);
+        default: return v;
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // Philox4x32-10 (Salmon et al. 2011) + Box-Muller: 4 N(0,1) per counter.
@@ -132,7 +142,7 @@ __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, fl
     z0 = rr * cs; z1 = rr * sn;
 }
 
-// posterior draw (Network.py:26-29): eps = mu + exp(logvar / 2) * noise.  One definition, so that ldt_reparam (pointops.hip) and
-// ldt_reparam_kl (eval_loss.hip) round alike: the product and the sum are ONE fused multiply-add, spelled out — left to contraction, the
-// 4-wide form of a kernel gets v_pk_fma_f32 for some lanes and v_pk_mul_f32 + v_pk_add_f32 for others.
+// posterior draw (Network.py:26-29): eps = mu + exp(logvar / 2) * noise, for ldt_reparam, ldt_reparam_kl and its backward (eval_loss.hip).
+// The product and the sum are ONE fused multiply-add, spelled out — left to contraction, the 4-wide form of a kernel gets v_pk_fma_f32
+// for some lanes and v_pk_mul_f32 + v_pk_add_f32 for others.
 __device__ __forceinline__ float reparam_eps(float mu, float lv, float noise) { return fmaf(noise, expf(lv / 2.f), mu); }

@@ -1,9 +1,12 @@
-// HBM-bound elementwise / row kernels of the LDT hot path (gfx950): cast+pad, LayerNorm+AdaLN
-// modulate, the fused reverse-SDE update with in-kernel Philox noise, sinusoidal time embedding,
-// and a plain fp32 tiled SGEMM for the tiny / precision-critical linears (time MLP, AdaLN tables,
-// K<=64 convs).  All are coalesced 16-B-per-lane where the shape allows (guide G13).
-#include <stdlib.h>
-
+// HBM-bound row and element kernels of the LDT hot path (gfx950), coalesced 16 B per lane where the shape allows (guide G13):
+//   cast_pad           fp32 -> bf16 with zero K-padding (ldt_cast_pad_bf16; the Score forward's first launch)
+//   ln_mod_*           LayerNorm + AdaLN modulate -> bf16 (ldt_layernorm_modulate; the Score forward's LayerNorms)
+//   sinusoid           sinusoidal time embedding (ldt_sinusoid)
+//   cond_rows          per-step AdaLN condition rows (the sampling loop)
+//   group_stats, norm_apply    GroupNorm statistics and the normalise / affine / modulate pass (ldt_group_stats, ldt_norm_apply)
+//   block_act, add_f32, widen_bf16    element passes (ldt_block_activation, ldt_add_f32, ldt_widen_bf16)
+//   fold_mean_ratio, fold_monitor     the LN-fold monitor over the folded GEMMs' row statistics (ldt_fold_mean_ratio; the Score forward)
+#include "../../include/ldt_hip.h"
 #include "kernels.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -28,10 +31,13 @@ int ldt_cast_pad_launch(const float* src, long lds, bf16_t* dst, long ldd, long 
                 "cast_pad: bad shape rows=%ld cols=%d cols_pad=%d ldd=%ld", rows, cols, cols_pad, ldd);
     LDT_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 7) == 0, LDT_EALIGN, "cast_pad: dst must be 8-byte aligned");
     const long total = rows * (long)(cols_pad / 4);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(cast_pad_kernel, dim3(blocks), dim3(256), 0, s, src, lds, dst, ldd, rows, cols, cols_pad);
+    hipLaunchKernelGGL(cast_pad_kernel, dim3(ldt_grid_1d(total, 256, 2048)), dim3(256), 0, s, src, lds, dst, ldd, rows, cols, cols_pad);
     return ldt_check_launch("cast_pad");
+}
+extern "C" int ldt_cast_pad_bf16(const float* src, int64_t ld_src, uint16_t* dst, int64_t ld_dst, int64_t rows,
+                                 int32_t cols, int32_t cols_pad, void* stream) {
+    LDT_REQUIRE(src && dst, LDT_EARG, "cast_pad: null pointer");
+    return ldt_cast_pad_launch(src, ld_src, ldt_bf16_mut(dst), ld_dst, rows, cols, cols_pad, ldt_stream(stream));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -129,102 +135,13 @@ int ldt_ln_launch(const LnArgs* a, hipStream_t s) {
     }
     return ldt_check_launch("ln_modulate");
 }
-
-// ------------------------------------------------------------------------------------------------
-// Philox4x32-10 + Box-Muller (philox4x32_10, box_muller): common.h — shared with the held-out-loss kernels (eval_loss.hip).
-
-// Fused predictor update (one pass over the latents):
-//   mode 0 (ancestral, exact op order of diffusion_continuous.py:152-162 + Latent_SDE_Trainer.py:57-61):
-//       score = -params / std ; x_mean = (x + beta*score) / sqrt(1-beta) ; x = x_mean + sqrt(beta)*z
-//       coef[step] = {beta, std, sqrt(1-beta), sqrt(beta)}   (host fp32 tables, SURVEY hard part 4)
-//   mode 1 (folded; reversediffusion / eulermaruyama / ddim, :141-191):
-//       x_mean = A*x + Bc*params ; x = x_mean + Cc*z        coef[step] = {A, Bc, Cc, 0}
-// z comes from `noise` (parity mode: injected CPU draws) or from Philox keyed by
-// (seed, stream id = step*philox_mul + philox_add, global element index) so that a sample's noise does not depend on how the batch is sharded.
-__global__ __launch_bounds__(256) void sampler_step_kernel(const StepArgs a) {
-    const int step = a.step_ptr ? *a.step_ptr : a.step_host;
-    const f32x4 cf = *reinterpret_cast<const f32x4*>(a.coef + 4L * step);
-    const float* nz = a.noise ? a.noise + (long)step * a.noise_step_stride : nullptr;
-    const long nvec = a.n / 4;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(a.x + 4 * i);
-        const f32x4 p = *reinterpret_cast<const f32x4*>(a.params + 4 * i);
-        f32x4 z;
-        if (nz) {
-            z = *reinterpret_cast<const f32x4*>(nz + 4 * i);
-        } else {
-            const uint64_t e = (uint64_t)(a.elem_offset / 4 + i);
-            uint32_t c[4] = {(uint32_t)e, (uint32_t)(e >> 32), (uint32_t)(step * a.philox_mul + a.philox_add), 0x4C445421u};
-            philox4x32_10(c, a.seed_lo, a.seed_hi);
-            float z0, z1, z2, z3;
-            box_muller(c[0], c[1], z0, z1);
-            box_muller(c[2], c[3], z2, z3);
-            z = (f32x4){z0, z1, z2, z3};
-        }
-        f32x4 xm, xn;
-        {
-#pragma clang fp contract(off)      // the reference's separate mul/add/div roundings, no FMA (HIP's __f*_rn are plain ops)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (a.mode == 0) {
-                    const float score = -p[j] / cf[1];
-                    const float bs = cf[0] * score;
-                    const float num = x[j] + bs;
-                    xm[j] = num / cf[2];
-                } else {
-                    const float ax = cf[0] * x[j];
-                    const float bp = cf[1] * p[j];
-                    xm[j] = ax + bp;
-                }
-                const float cz = (a.mode == 0) ? cf[3] : cf[2];
-                const float nz_ = cz * z[j];
-                xn[j] = xm[j] + nz_;
-            }
-        }
-        *reinterpret_cast<f32x4*>(a.x_out + 4 * i) = xn;
-        if (a.traj) *reinterpret_cast<f32x4*>(a.traj + (long)step * a.n + 4 * i) = xn;
-        if (a.x_mean_out) *reinterpret_cast<f32x4*>(a.x_mean_out + 4 * i) = xm;
-    }
-}
-
-__global__ void advance_step_kernel(int* step_ptr) { if (threadIdx.x == 0 && blockIdx.x == 0) *step_ptr += 1; }
-
-int ldt_sampler_step_launch(const StepArgs* a, hipStream_t s) {
-    LDT_REQUIRE(a->n > 0 && a->n % 4 == 0 && a->elem_offset % 4 == 0, LDT_ESHAPE, "sampler_step: n and elem_offset must be multiples of 4 (n=%ld)", a->n);
-    LDT_REQUIRE(a->x && a->params && a->x_out && a->coef, LDT_EARG, "sampler_step: null pointer");
-    LDT_REQUIRE(ldt_aligned16(a->x) && ldt_aligned16(a->params) && ldt_aligned16(a->x_out) && ldt_aligned16(a->coef) &&
-                (!a->noise || ldt_aligned16(a->noise)) && (!a->x_mean_out || ldt_aligned16(a->x_mean_out)) && a->noise_step_stride % 4 == 0,
-                LDT_EALIGN, "sampler_step: buffers must be 16-byte aligned");
-    LDT_REQUIRE(a->mode == 0 || a->mode == 1, LDT_EARG, "sampler_step: mode %d", a->mode);
-    long blocks = (a->n / 4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(sampler_step_kernel, dim3((unsigned)blocks), dim3(256), 0, s, *a);
-    return ldt_check_launch("sampler_step");
-}
-int ldt_advance_step_launch(int* step_ptr, hipStream_t s) {
-    hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(64), 0, s, step_ptr);
-    return ldt_check_launch("advance_step");
-}
-
-// standalone Philox normal fill (same stream as the fused step; used by tests and Compressor.sample(given_eps=None))
-__global__ void philox_normal_kernel(float* out, long n, long elem_offset, int step, uint32_t k0, uint32_t k1) {
-    const long nvec = n / 4;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
-        const uint64_t e = (uint64_t)(elem_offset / 4 + i);
-        uint32_t c[4] = {(uint32_t)e, (uint32_t)(e >> 32), (uint32_t)step, 0x4C445421u};
-        philox4x32_10(c, k0, k1);
-        float z0, z1, z2, z3;
-        box_muller(c[0], c[1], z0, z1);
-        box_muller(c[2], c[3], z2, z3);
-        *reinterpret_cast<f32x4*>(out + 4 * i) = (f32x4){z0, z1, z2, z3};
-    }
-}
-int ldt_philox_normal_launch(float* out, long n, long elem_offset, int step, uint32_t k0, uint32_t k1, hipStream_t s) {
-    LDT_REQUIRE(n > 0 && n % 4 == 0 && elem_offset % 4 == 0 && ldt_aligned16(out), LDT_ESHAPE, "philox_normal: n/offset %% 4, 16-byte aligned");
-    long blocks = (n / 4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(philox_normal_kernel, dim3((unsigned)blocks), dim3(256), 0, s, out, n, elem_offset, step, k0, k1);
-    return ldt_check_launch("philox_normal");
+extern "C" int ldt_layernorm_modulate(const float* x, int64_t ldx, uint16_t* y, int64_t ldy, const float* w,
+                                      const float* b, const float* shift, const float* scale,
+                                      int64_t mod_sample_stride, int32_t rows_per_sample, const int32_t* step_ptr,
+                                      int64_t mod_step_stride, int64_t M, int32_t C, void* stream) {
+    LDT_REQUIRE(x && y, LDT_EARG, "ln: null pointer");
+    LnArgs a{x, ldx, ldt_bf16_mut(y), ldy, w, b, shift, scale, mod_sample_stride, rows_per_sample, step_ptr, mod_step_stride, M, C};
+    return ldt_ln_launch(&a, ldt_stream(stream));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -238,117 +155,11 @@ __global__ void sinusoid_kernel(const float* __restrict__ t, const float* __rest
         e[(long)i * 2 * half + half + k] = cosf(a);
     }
 }
-int ldt_sinusoid_launch(const float* t, const float* freq, float* e, int n, int half, hipStream_t s) {
+extern "C" int ldt_sinusoid(const float* t, const float* freq, float* e, int32_t n, int32_t half, void* stream) {
+    LDT_REQUIRE(t && freq && e, LDT_EARG, "sinusoid: null pointer");
     LDT_REQUIRE(n > 0 && half > 0, LDT_ESHAPE, "sinusoid: empty");
-    hipLaunchKernelGGL(sinusoid_kernel, dim3(n), dim3(128), 0, s, t, freq, e, n, half);
+    hipLaunchKernelGGL(sinusoid_kernel, dim3(n), dim3(128), 0, ldt_stream(stream), t, freq, e, n, half);
     return ldt_check_launch("sinusoid");
-}
-
-// ------------------------------------------------------------------------------------------------
-// fp32 SGEMM (NT): C[M,N] = act_out( act_in(A[M,K]) · B[N,K]^T + bias[N] ), output fp32 or bf16.
-// 64x64 tile, BK=16, 4x4 outputs per thread.  For the small fp32-critical linears: time MLP
-// (layers.py:17), AdaLN tables (layers.py:172,238), convs with K<=64, MiniPointnet, prior heads.
-__device__ __forceinline__ float apply_act(float v, int act) {
-    switch (act) {
-        case ACT_SILU: return v / (1.0f + expf(-v));
-        case ACT_RELU: return fmaxf(v, 0.f);
-        case ACT_GELU: return gelu_erf(v);
-        default: return v;
-    }
-}
-__global__ __launch_bounds__(256) void sgemm_nt_kernel(const SgemmArgs a) {
-    __shared__ float As[16][68];
-    __shared__ float Bs[16][68];
-    const int tid = threadIdx.x;
-    const int tx = tid & 15, ty = tid >> 4;
-    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
-    float acc[4][4] = {};
-    const int lr = tid >> 2, lk = (tid & 3) * 4;
-    // each thread stages 4 consecutive k of one A row and one B row: one 16-B load each when the rows allow it
-    const bool vec = (a.lda % 4 == 0) && (a.ldb % 4 == 0) && (a.K % 4 == 0) && ldt_aligned16(a.A) && ldt_aligned16(a.B);
-    for (int k0 = 0; k0 < a.K; k0 += 16) {
-        const int m = m0 + lr, n = n0 + lr, kk = k0 + lk;
-        f32x4 va4 = {0.f, 0.f, 0.f, 0.f}, vb4 = {0.f, 0.f, 0.f, 0.f};
-        if (vec) {
-            if (m < a.M && kk < a.K) va4 = *reinterpret_cast<const f32x4*>(a.A + (long)m * a.lda + kk);
-            if (n < a.N && kk < a.K) vb4 = *reinterpret_cast<const f32x4*>(a.B + (long)n * a.ldb + kk);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (m < a.M && kk + j < a.K) va4[j] = a.A[(long)m * a.lda + kk + j];
-                if (n < a.N && kk + j < a.K) vb4[j] = a.B[(long)n * a.ldb + kk + j];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            As[lk + j][lr] = a.act_in ? apply_act(va4[j], a.act_in) : va4[j];
-            Bs[lk + j][lr] = vb4[j];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const f32x4 av = *reinterpret_cast<const f32x4*>(&As[k][ty * 4]);
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(&Bs[k][tx * 4]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(av[i], bv[j], acc[i][j]);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + ty * 4 + i;
-        if (m >= a.M) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + tx * 4 + j;
-            if (n >= a.N) continue;
-            float v = acc[i][j] + (a.bias ? a.bias[n] : 0.f);
-            v = apply_act(v, a.act_out);
-            if (a.out_bf16) reinterpret_cast<bf16_t*>(a.C)[(long)m * a.ldc + n] = (bf16_t)v;
-            else reinterpret_cast<float*>(a.C)[(long)m * a.ldc + n] = v;
-        }
-    }
-}
-// The seven forms in the order they are tried (the rule is stated in include/ldt_hip.h at ldt_sgemm_route):
-//   streaming forms (skinny_linear.hip), M >= 8192 only: small N (N <= 8, K % 4 == 0, 16-byte rows of A and B), then small K (K <= 8, N / 4 in
-//   8..256 dividing 256, 16-byte rows of C and bias);  MFMA forms (sgemm_mfma.hip): K % 4 == 0, K >= 8, 16-byte rows of A and B, M N >= 4096,
-//   32 x 128 tiles when M <= 48, else 128 x 128;  the scalar-FMA kernel above for everything else its grid can hold.
-int ldt_sgemm_decide(int M, int N, int K, long lda, long ldb, long ldc, int misaligned) {
-    static const bool no_mfma = getenv("LDT_SGEMM_VALU") != nullptr;      // tools/dbg A/B: force the scalar-FMA kernel
-    static const bool no_skinny = getenv("LDT_SGEMM_SKINNY") && atoi(getenv("LDT_SGEMM_SKINNY")) == 0;
-    if (M <= 0 || N <= 0 || K <= 0) return SGEMM_ROUTE_NONE;
-    const bool rows_ab = K % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && !(misaligned & 3);      // 16-B loads of A and B rows
-    if (!no_skinny && M >= 8192) {                                        // short problems: the tiled kernels are fine
-        if (N <= 8 && rows_ab) return N <= 4 ? SGEMM_ROUTE_SMALLN_4 : SGEMM_ROUTE_SMALLN_8;
-        const int nq = N / 4;
-        if (K <= 8 && N % 4 == 0 && nq >= 8 && nq <= 256 && 256 % nq == 0 && ldc % 4 == 0 && !(misaligned & 12))   // 16-B loads of bias, 16-B / 8-B stores
-            return K <= 4 ? SGEMM_ROUTE_SMALLK_4 : SGEMM_ROUTE_SMALLK_8;
-    }
-    if (!no_mfma && rows_ab && K >= 8 && (long)M * N >= 64 * 64) {        // (tiny problems: launch-bound either way, keep the simple kernel)
-        if (M <= 48) return SGEMM_ROUTE_MFMA_32;
-        if ((M + 127) / 128 < 65536) return SGEMM_ROUTE_MFMA_128;
-    }
-    return (M + 63) / 64 < 65536 ? SGEMM_ROUTE_NT : SGEMM_ROUTE_NONE;     // grid.y limit
-}
-int ldt_sgemm_launch(const SgemmArgs* a, hipStream_t s) {
-    LDT_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0, LDT_ESHAPE, "sgemm: empty problem");
-    LDT_REQUIRE(a->A && a->B && a->C, LDT_EARG, "sgemm: null pointer");
-    const int misaligned = (ldt_aligned16(a->A) ? 0 : 1) | (ldt_aligned16(a->B) ? 0 : 2) | (ldt_aligned16(a->C) ? 0 : 4) |
-                           (!a->bias || ldt_aligned16(a->bias) ? 0 : 8);
-    const int route = ldt_sgemm_decide(a->M, a->N, a->K, a->lda, a->ldb, a->ldc, misaligned);
-    switch (route) {
-        case SGEMM_ROUTE_SMALLN_4: case SGEMM_ROUTE_SMALLN_8: case SGEMM_ROUTE_SMALLK_4: case SGEMM_ROUTE_SMALLK_8:
-            return ldt_skinny_linear_launch(a, route, s);
-        case SGEMM_ROUTE_MFMA_128: case SGEMM_ROUTE_MFMA_32:
-            return ldt_sgemm_mfma_launch(a, route, s);
-        case SGEMM_ROUTE_NT: break;
-        default: LDT_REQUIRE(false, LDT_ESHAPE, "sgemm: M too large for this kernel (M=%d)", a->M);
-    }
-    dim3 grid((a->N + 63) / 64, (a->M + 63) / 64), block(256);
-    hipLaunchKernelGGL(sgemm_nt_kernel, grid, block, 0, s, *a);
-    return ldt_check_launch("sgemm_nt");
 }
 
 // c[b][k] = silu?(temb[step][k] + extra[b][k])   (score.py:135: c = t_emb + l_emb | img condition; the SiLU that opens every AdaLN
@@ -367,7 +178,176 @@ __global__ void cond_rows_kernel(const float* __restrict__ temb, const float* __
 }
 int ldt_cond_rows_launch(const float* temb, const float* extra, float* c, void* c_bf16, const int* step_ptr, int batch, int t_dim, int silu_out, hipStream_t s) {
     LDT_REQUIRE(temb && c && batch > 0 && t_dim > 0, LDT_EARG, "cond_rows: bad arguments");
-    int blocks = (batch * t_dim + 255) / 256; if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(cond_rows_kernel, dim3(blocks), dim3(256), 0, s, temb, extra, c, reinterpret_cast<bf16_t*>(c_bf16), step_ptr, batch, t_dim, silu_out);
+    hipLaunchKernelGGL(cond_rows_kernel, dim3(ldt_grid_1d(batch * t_dim, 256, 1024)), dim3(256), 0, s, temb, extra, c, ldt_bf16_mut(c_bf16), step_ptr, batch, t_dim, silu_out);
     return ldt_check_launch("cond_rows");
+}
+
+// ------------------------------------------------------------------------------------------------- group norm / identity norm
+// tools/utils.py:168-181 get_norm: `group_norm` -> nn.GroupNorm(min(C/4, 16), C, eps=1e-6) on the channels-first activations (statistics per
+// sample and group over C/G channels x all tokens), `None` -> Identity.  Rows are token-major here: x[b*T + t][c].
+__global__ void group_stats_kernel(const float* __restrict__ x, long ldx, int T, int C, int G, float eps, float* __restrict__ stats) {
+    const int b = blockIdx.x / G, g = blockIdx.x % G, cg = C / G;
+    const float* xb = x + (long)b * T * ldx + g * cg;
+    double s1 = 0.0, s2 = 0.0;
+    for (int i = threadIdx.x; i < T * cg; i += blockDim.x) {
+        const float v = xb[(long)(i / cg) * ldx + i % cg];
+        s1 += v; s2 += (double)v * v;
+    }
+    __shared__ double r1[256], r2[256];
+    r1[threadIdx.x] = s1; r2[threadIdx.x] = s2;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { r1[threadIdx.x] += r1[threadIdx.x + o]; r2[threadIdx.x] += r2[threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double n = (double)T * cg, mean = r1[0] / n;
+        double var = r2[0] / n - mean * mean;
+        var = var > 0.0 ? var : 0.0;
+        stats[(long)blockIdx.x * 2] = (float)mean;
+        stats[(long)blockIdx.x * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    }
+}
+extern "C" int ldt_group_stats(const float* x, int64_t ldx, int32_t B, int32_t T, int32_t C, int32_t G, float eps, float* stats, void* stream) {
+    LDT_REQUIRE(x && stats && B > 0 && T > 0 && C > 0 && G > 0 && C % G == 0 && ldx >= C, LDT_EARG, "group_stats: bad argument (B=%d T=%d C=%d G=%d)", B, T, C, G);
+    hipLaunchKernelGGL(group_stats_kernel, dim3((unsigned)(B * G)), dim3(256), 0, ldt_stream(stream), x, (long)ldx, T, C, G, eps, stats);
+    return ldt_check_launch("group_stats");
+}
+
+__global__ void norm_apply_kernel(const float* __restrict__ x, long ldx, bf16_t* __restrict__ y, long ldy, long M, int C, const float* __restrict__ stats,
+                                  int G, int rows_per_stat, const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ shift,
+                                  const float* __restrict__ scale, long mod_sample_stride, int rows_per_sample) {
+    const long n4 = M * (C / 4);
+    const int cg = C / (G > 0 ? G : 1);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const long m = i / (C / 4);
+        const int c = (int)(i % (C / 4)) * 4;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + m * ldx + c);
+        const long moff = (m / rows_per_sample) * mod_sample_stride + c;
+        bf16x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float mean = 0.f, rstd = 1.f;
+            if (stats) {
+                const float* st = stats + ((m / rows_per_stat) * G + (c + j) / cg) * 2;
+                mean = st[0]; rstd = st[1];
+            }
+            float h = (v[j] - mean) * rstd;
+            if (w) h = h * w[c + j] + b[c + j];
+            if (scale) h = h * (1.0f + scale[moff + j]) + shift[moff + j];
+            o[j] = (bf16_t)h;
+        }
+        *reinterpret_cast<bf16x4*>(y + m * ldy + c) = o;
+    }
+}
+extern "C" int ldt_norm_apply(const float* x, int64_t ldx, uint16_t* y, int64_t ldy, int64_t M, int32_t C, const float* stats, int32_t G,
+                              int32_t rows_per_stat, const float* w, const float* b, const float* shift, const float* scale,
+                              int64_t mod_sample_stride, int32_t rows_per_sample, void* stream) {
+    LDT_REQUIRE(x && y && M > 0 && C > 0 && C % 4 == 0 && ldx >= C && ldy >= C && ldx % 4 == 0 && ldy % 4 == 0, LDT_EARG, "norm_apply: bad argument (M=%ld C=%d)", (long)M, C);
+    LDT_REQUIRE(ldt_aligned16(x) && (reinterpret_cast<uintptr_t>(y) & 7u) == 0, LDT_EALIGN, "norm_apply: x must be 16-byte, y 8-byte aligned");
+    LDT_REQUIRE(!stats || (G > 0 && C % G == 0 && rows_per_stat > 0), LDT_EARG, "norm_apply: statistics need G | C and rows_per_stat > 0");
+    LDT_REQUIRE(!w == !b && !shift == !scale && rows_per_sample > 0, LDT_EARG, "norm_apply: w / b and shift / scale go in pairs; rows_per_sample > 0");
+    hipLaunchKernelGGL(norm_apply_kernel, dim3(ldt_grid_1d(M * (C / 4), 256, 4096)), dim3(256), 0, ldt_stream(stream), x, (long)ldx, ldt_bf16_mut(y), (long)ldy,
+                       (long)M, C, stats, stats ? G : 1, stats ? rows_per_stat : 1, w, b, shift, scale, (long)mod_sample_stride, rows_per_sample);
+    return ldt_check_launch("norm_apply");
+}
+
+// ------------------------------------------------------------------------------------------------
+// x = act(x) in place on bf16 rows [M][C] (row stride ld): the block activation of the reference's no-condition ResidualBlock branches
+// (`decoder_act`, model/layers.py:224-226 via tools/utils.py:104-124), applied to the LayerNorm output the projections read.  kind = enum
+// ldt_block_act; the arithmetic runs in fp32.  rrelu is its eval-mode form (slope (1/8 + 1/3) / 2).
+__device__ __forceinline__ float block_act(float v, int kind) {
+    switch (kind) {
+        case LDT_BACT_GELU: return gelu_erf(v);
+        case LDT_BACT_SILU: return silu(v);
+        case LDT_BACT_RELU: return (v > 0.f || v != v) ? v : 0.f;      // (fmaxf would turn a NaN into 0: torch.relu keeps it)
+        case LDT_BACT_LEAKY_001: return v > 0.f ? v : 0.01f * v;
+        case LDT_BACT_LEAKY_02: return v > 0.f ? v : 0.2f * v;
+        case LDT_BACT_RRELU_EVAL: return v > 0.f ? v : v * ((1.0f / 8.0f + 1.0f / 3.0f) * 0.5f);
+        case LDT_BACT_HARDSWISH: return v * fminf(fmaxf(v + 3.0f, 0.f), 6.0f) * (1.0f / 6.0f);
+        case LDT_BACT_SELU: return 1.0507009873554804934193349852946f * (v > 0.f ? v : 1.6732632423543772848170429916717f * (expf(v) - 1.0f));
+        default: return v;
+    }
+}
+__global__ __launch_bounds__(256) void block_act_kernel(bf16_t* __restrict__ x, long ld, long M, int C, int kind) {
+    const long n = M * C;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        bf16_t* p = x + (i / C) * ld + (i % C);
+        *p = (bf16_t)block_act((float)*p, kind);
+    }
+}
+extern "C" int ldt_block_activation(uint16_t* x, int64_t ld, int64_t M, int32_t C, int32_t kind, void* stream) {
+    LDT_REQUIRE(x && M > 0 && C > 0 && ld >= C, LDT_EARG, "block_activation: bad argument");
+    LDT_REQUIRE(kind > LDT_BACT_NONE && kind <= LDT_BACT_SELU, LDT_EARG, "block_activation: unknown activation %d", kind);
+    hipLaunchKernelGGL(block_act_kernel, dim3(ldt_grid_1d(M * C, 256, 4096)), dim3(256), 0, ldt_stream(stream),
+                       ldt_bf16_mut(x), (long)ld, (long)M, (int)C, (int)kind);
+    return ldt_check_launch("block_activation");
+}
+
+// out = a + b (fp32; c = t_emb + label / image-condition embedding, model/scorenet/score.py:135).  out may alias a or b.
+__global__ __launch_bounds__(256) void add_f32_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, long n) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[i] = a[i] + b[i];
+}
+extern "C" int ldt_add_f32(const float* a, const float* b, float* out, int64_t n, void* stream) {
+    LDT_REQUIRE(a && b && out && n > 0, LDT_EARG, "add_f32: bad argument");
+    hipLaunchKernelGGL(add_f32_kernel, dim3(ldt_grid_1d(n, 256, 2048)), dim3(256), 0, ldt_stream(stream), a, b, out, (long)n);
+    return ldt_check_launch("add_f32");
+}
+
+// bf16 -> fp32 widening of a packed weight panel (exact), for the fp32 table builds that must see the SAME rounded weights
+// the MFMAs multiply by (Score.fold_table).
+__global__ __launch_bounds__(256) void widen_bf16_kernel(const bf16_t* __restrict__ src, float* __restrict__ dst, long n) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = (float)src[i];
+}
+extern "C" int ldt_widen_bf16(const uint16_t* src, float* dst, int64_t n, void* stream) {
+    LDT_REQUIRE(src && dst && n > 0, LDT_EARG, "widen_bf16: bad argument");
+    hipLaunchKernelGGL(widen_bf16_kernel, dim3(ldt_grid_1d(n, 256, 4096)), dim3(256), 0, ldt_stream(stream), ldt_bf16(src), dst, (long)n);
+    return ldt_check_launch("widen_bf16");
+}
+
+// ------------------------------------------------------------------------------------------------
+// LN-folding monitor: max over rows of mean^2 / variance from the producer's row statistics stats[parts][M][2] (partial
+// (sum, sum of squares) per 256-column tile).  The folded projections round x (1 + scale) to bf16 BEFORE the mean is removed,
+// so their error variance is (1 + mean^2 / variance) x the LayerNorm kernel's; the sampler reads this once per
+// sample() call and falls back to the LayerNorm kernels when the ratio says the 1e-4 parity bar is at risk.
+// One workgroup of 256 threads, fixed order: deterministic.  *out = the maximum ratio (0 when M == 0).
+__global__ __launch_bounds__(256) void fold_mean_ratio_kernel(const float* __restrict__ stats, int parts, long M, int K, float* __restrict__ out) {
+    float best = 0.f;
+    const float invk = 1.0f / (float)K;
+    for (long r = threadIdx.x; r < M; r += 256) {
+        float s1 = 0.f, s2 = 0.f;
+        for (int p = 0; p < parts; ++p) { s1 += stats[((long)p * M + r) * 2]; s2 += stats[((long)p * M + r) * 2 + 1]; }
+        const float mean = s1 * invk;
+        const float var = fmaxf(s2 * invk - mean * mean, 0.f) + 1e-6f;
+        best = fmaxf(best, mean * mean / var);
+    }
+    best = wave_max(best);
+    __shared__ float part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) *out = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
+}
+// the same, accumulated into *out by atomic max (ratios are non-negative: their bit patterns order like ints); the Score
+// forward calls it after every folded residual GEMM when plan->fold_monitor is set
+__global__ __launch_bounds__(256) void fold_monitor_kernel(const float* __restrict__ stats, int parts, long M, int K, float* __restrict__ out) {
+    float best = 0.f;
+    const float invk = 1.0f / (float)K;
+    for (long r = blockIdx.x * 256L + threadIdx.x; r < M; r += (long)gridDim.x * 256) {
+        float s1 = 0.f, s2 = 0.f;
+        for (int p = 0; p < parts; ++p) { s1 += stats[((long)p * M + r) * 2]; s2 += stats[((long)p * M + r) * 2 + 1]; }
+        const float mean = s1 * invk;
+        const float var = fmaxf(s2 * invk - mean * mean, 0.f) + 1e-6f;
+        best = fmaxf(best, mean * mean / var);
+    }
+    best = wave_max(best);
+    if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<int*>(out), __float_as_int(best));
+}
+int ldt_fold_monitor_launch(const float* stats, int parts, long M, int K, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(fold_monitor_kernel, dim3(ldt_grid_1d(M, 256, 64)), dim3(256), 0, s, stats, parts, M, K, out);
+    return ldt_check_launch("fold_monitor");
+}
+extern "C" int ldt_fold_mean_ratio(const float* stats, int32_t parts, int64_t M, int32_t K, float* out, void* stream) {
+    LDT_REQUIRE(stats && out && parts >= 1 && M > 0 && K > 0, LDT_EARG, "fold_mean_ratio: bad argument");
+    hipLaunchKernelGGL(fold_mean_ratio_kernel, dim3(1), dim3(256), 0, ldt_stream(stream), stats, parts, (long)M, K, out);
+    return ldt_check_launch("fold_mean_ratio");
 }

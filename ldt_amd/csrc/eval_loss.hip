@@ -1,10 +1,11 @@
-// Loss arithmetic of held-out evaluation, between kernels that already exist (encode, Score forward, Chamfer):
+// The posterior draw and the loss arithmetic of held-out evaluation, between kernels that already exist (encode, Score forward, Chamfer):
+//   ldt_reparam      posterior draw alone, into a strided slice of all_eps   (model/Compressor/Network.py:26-29,75-77)
 //   ldt_reparam_kl   posterior draw + per-element log q(z), KL and the per-sample KL sum   (model/Compressor/Network.py:12-29,221-224)
 //   ldt_reparam_kl_bwd   its backward for training: d(draw) and d(kl_scale x sum kl) with respect to mu | logvar, in closed form
 //   ldt_diffuse_q    x_t = m_t x_0 + sqrt(var_t) eta with per-sample scalars, eta injected or drawn from the Philox stream
 //                    (diffusion/diffusion_continuous.py:78-81; trainer/Latent_SDE_Trainer.py:79-81)
 //   ldt_dsm_loss     denoising score-matching distance, per-sample and overall mean   (trainer/Latent_SDE_Trainer.py:83-87)
-// All three are single-pass fp32 streaming kernels over a few MB, far below the encode / Score forward they sit next to.  They are written for
+// All are single-pass fp32 streaming kernels over a few MB, far below the encode / Score forward they sit next to.  They are written for
 // determinism: every sum has a fixed order (per-thread strided partial -> wave shuffle -> LDS partials added in index order), no atomics,
 // so two runs of the same input are bit-identical.  Where the reference's fp32 operation order is restated, FMA contraction is off.
 #include "../../include/ldt_hip.h"
@@ -39,7 +40,30 @@ template <int V> __device__ __forceinline__ typename Pack<V>::T ld(const float* 
 template <int V> __device__ __forceinline__ void st(float* p, const typename Pack<V>::T& v) { *reinterpret_cast<typename Pack<V>::T*>(p) = v; }
 
 // ------------------------------------------------------------------------------------------------
-// One workgroup per sample; V = 4 when z, ldo and every pointer allow 16-byte accesses (a group of 4 never crosses a row), else 1.
+// posterior draw (Network.py:26-29,75-77): mu = post[:, :z], logvar = clamp(post[:, z:], lo, hi);
+// eps = mu + exp(logvar / 2) * noise   -> written into a strided slice of all_eps
+__global__ void reparam_kernel(const float* __restrict__ post, const float* __restrict__ noise, float* __restrict__ out,
+                               long ldo, float* __restrict__ mu_out, float* __restrict__ lv_out, long rows, int z, float lo, float hi) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < rows * z; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / z; const int c = (int)(i % z);
+        const float mu = post[r * 2 * z + c];
+        const float lv = fminf(fmaxf(post[r * 2 * z + z + c], lo), hi);
+        out[r * ldo + c] = reparam_eps(mu, lv, noise[i]);
+        if (mu_out) { mu_out[i] = mu; lv_out[i] = lv; }
+    }
+}
+extern "C" int ldt_reparam(const float* post, const float* noise, float* out, int64_t ldo, float* mu_out, float* logvar_out,
+                           int64_t rows, int32_t z, float lo, float hi, void* stream) {
+    LDT_REQUIRE(post && noise && out, LDT_EARG, "reparam: null pointer");
+    LDT_REQUIRE(rows > 0 && z > 0 && ldo >= z, LDT_ESHAPE, "reparam: bad shape");
+    LDT_REQUIRE((mu_out == nullptr) == (logvar_out == nullptr), LDT_EARG, "reparam: mu/logvar outputs go together");
+    hipLaunchKernelGGL(reparam_kernel, dim3(ldt_grid_1d(rows * z, 256, 4096)), dim3(256), 0, ldt_stream(stream), post, noise, out, (long)ldo, mu_out,
+                       logvar_out, (long)rows, (int)z, lo, hi);
+    return ldt_check_launch("reparam");
+}
+
+// ------------------------------------------------------------------------------------------------
+// posterior draw with its loss terms.  One workgroup per sample; V = 4 when z, ldo and every pointer allow 16-byte accesses (a group of 4 never crosses a row), else 1.
 template <int V>
 __global__ __launch_bounds__(EVAL_WG) void reparam_kl_kernel(const float* __restrict__ post, const float* __restrict__ noise, float* __restrict__ out,
                                                              long ldo, float* __restrict__ mu_out, float* __restrict__ lv_out,
@@ -97,7 +121,7 @@ extern "C" int ldt_reparam_kl(const float* post, const float* noise, float* out,
     LDT_REQUIRE(B <= 0x7fffffffL, LDT_ESHAPE, "reparam_kl: %ld samples", B);
     const bool vec = z % 4 == 0 && ldo % 4 == 0 && ldt_aligned16(post) && ldt_aligned16(noise) && ldt_aligned16(out) &&
                      ldt_aligned16(mu_out) && ldt_aligned16(logvar_out) && ldt_aligned16(kl_out) && ldt_aligned16(logqz_out);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = ldt_stream(stream);
     if (vec)
         hipLaunchKernelGGL(reparam_kl_kernel<4>, dim3((unsigned)B), dim3(EVAL_WG), 0, s, post, noise, out, (long)ldo, mu_out, logvar_out, kl_out,
                            logqz_out, kl_sample_sum, (long)rows_per_sample, z, lo, hi);
@@ -146,7 +170,7 @@ extern "C" int ldt_reparam_kl_bwd(const float* post, const float* noise, const f
     const bool vec = z % 4 == 0 && ldd % 4 == 0 && ldt_aligned16(post) && ldt_aligned16(noise) && ldt_aligned16(d_eps) && ldt_aligned16(dpost);
     const long threads = rows * z / (vec ? 4 : 1), wgs = (threads + 255) / 256;
     LDT_REQUIRE(wgs <= 0x7fffffffL, LDT_ESHAPE, "reparam_kl_bwd: %ld elements", (long)rows * z);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = ldt_stream(stream);
     if (vec)
         hipLaunchKernelGGL(reparam_kl_bwd_kernel<4>, dim3((unsigned)wgs), dim3(256), 0, s, post, noise, d_eps, (long)ldd, kl_scale, dpost, (long)rows, z, lo, hi);
     else
@@ -200,9 +224,7 @@ extern "C" int ldt_diffuse_q(const float* x0, const float* eta_in, const float* 
     LDT_REQUIRE(ldt_aligned16(x0) && ldt_aligned16(eta_in) && ldt_aligned16(xt) && ldt_aligned16(eta_out), LDT_EALIGN,
                 "diffuse_q: buffers must be 16-byte aligned");
     const long nvec = B * per_sample / 4;
-    long blocks = (nvec + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(diffuse_q_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x0, eta_in, m, var, xt, eta_out,
+    hipLaunchKernelGGL(diffuse_q_kernel, dim3(ldt_grid_1d(nvec, 256, 2048)), dim3(256), 0, ldt_stream(stream), x0, eta_in, m, var, xt, eta_out,
                        nvec, (long)per_sample, step, (uint32_t)seed, (uint32_t)(seed >> 32));
     return ldt_check_launch("diffuse_q");
 }
@@ -244,7 +266,7 @@ extern "C" int ldt_dsm_loss(const float* eta, const float* params, const float* 
                             float* sample_loss, float* mean_loss, void* stream) {
     LDT_REQUIRE(eta && params && sample_loss, LDT_EARG, "dsm_loss: null pointer (sample_loss is the first stage's output and is required)");
     LDT_REQUIRE(B > 0 && B <= 0x7fffffffL && per_sample > 0, LDT_ESHAPE, "dsm_loss: B %ld, per_sample %ld", (long)B, (long)per_sample);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = ldt_stream(stream);
     if (per_sample % 4 == 0 && ldt_aligned16(eta) && ldt_aligned16(params))
         hipLaunchKernelGGL(dsm_sample_kernel<4>, dim3((unsigned)B), dim3(EVAL_WG), 0, s, eta, params, weight, (long)per_sample, l1, sample_loss);
     else

@@ -19,8 +19,28 @@
 //        U = GELU(U + b_up) -> bf16 -> LDS       hidden units of one row -> one 8-B LDS store)
 //        O^T[C x 32] += W_dn_c · U^T           (a lane holds 4 consecutive output channels of one row)
 //   3. epilogue from registers, 16 B per lane: the accumulators ARE the new x (no gate), or x + gate * (O + b_dn).
-#include "common.h"
+#include "../../include/ldt_hip.h"
 #include "kernels.h"
+
+// fused LayerNorm + linear (bf16 out)
+struct LnLinArgs {
+    const float* x; long ldx; long M;
+    const float* ln_w; const float* ln_b; const float* shift; const float* scale; long mod_sample_stride; int rows_per_sample;
+    const bf16_t* w; const float* bias; int N;          // [N][C], [N] (nullable)
+    bf16_t* out; long ldo;
+};
+// fused LayerNorm + MLP + gated residual
+struct MlpArgs {
+    float* x; long ldx; long M;
+    const float* ln_w; const float* ln_b;              // affine LayerNorm (no-condition blocks) or null
+    const float* shift; const float* scale;            // AdaLN modulation (per sample) or null
+    const float* gate;                                 // per-sample gate or null (= 1)
+    long mod_sample_stride; int rows_per_sample;
+    const bf16_t* w_up; const float* b_up;             // [4C][C], [4C]
+    const bf16_t* w_dn; const float* b_dn;             // [C][4C], [C]
+    bf16_t* x_bf16; long ldxb;                          // optional bf16 mirror of the updated x (the next block's K/V source) or null
+    LnLinArgs next;                                     // optional (next.w != null): LN + linear of the block that follows, on the new x (next.x unused)
+};
 
 namespace {
 
@@ -412,7 +432,7 @@ int check_ln_src(const Src& s, const float* gate, const char* who, int mod_code,
 
 }  // namespace
 
-int ldt_ln_mlp_launch(const MlpArgs* a, int C, hipStream_t st) {
+static int ldt_ln_mlp_launch(const MlpArgs* a, int C, hipStream_t st) {
     LDT_REQUIRE(a->M > 0 && a->M < (1L << 31) * 128, LDT_ESHAPE, "ln_mlp: bad row count %ld", a->M);
     LDT_REQUIRE(C == 64 || C == 128, LDT_ESHAPE, "ln_mlp: the fused kernel is built for 64 or 128 channels (got %d)", C);
     LDT_REQUIRE(a->ldx >= C && a->ldx % 4 == 0 && ldt_aligned16(a->x), LDT_EALIGN, "ln_mlp: x rows must be 16-byte aligned");
@@ -430,7 +450,7 @@ int ldt_ln_mlp_launch(const MlpArgs* a, int C, hipStream_t st) {
     return C == 128 ? launch_mlp<128, false>(a, st) : launch_mlp<64, false>(a, st);
 }
 
-int ldt_ln_linear_launch(const LnLinArgs* a, int C, hipStream_t st) {
+static int ldt_ln_linear_launch(const LnLinArgs* a, int C, hipStream_t st) {
     LDT_REQUIRE(a->M > 0 && a->M < (1L << 31) * 128, LDT_ESHAPE, "ln_linear: bad row count %ld", a->M);
     LDT_REQUIRE(C == 64 || C == 128, LDT_ESHAPE, "ln_linear: the fused kernel is built for 64 or 128 channels (got %d)", C);
     LDT_REQUIRE(a->N > 0 && a->N % 64 == 0, LDT_ESHAPE, "ln_linear: N=%d must be a multiple of 64", a->N);
@@ -438,4 +458,39 @@ int ldt_ln_linear_launch(const LnLinArgs* a, int C, hipStream_t st) {
                 ldt_aligned16(a->w) && ldt_aligned16(a->bias), LDT_EALIGN, "ln_linear: rows must be 16-byte aligned");
     if (const int rc = check_ln_src(*a, nullptr, "ln_linear", LDT_EARG, LDT_EALIGN)) return rc;
     return C == 128 ? launch_ln_linear<128>(a, st) : launch_ln_linear<64>(a, st);
+}
+
+// the arguments that ldt_ln_mlp_resid and ldt_ln_mlp_resid_next share (no chained projection: next.w == null)
+static MlpArgs mlp_args(float* x, int64_t ldx, int64_t M, const float* ln_w, const float* ln_b, const float* shift, const float* scale,
+                        const float* gate, int64_t mod_sample_stride, int32_t rows_per_sample, const uint16_t* w_up, const float* b_up,
+                        const uint16_t* w_dn, const float* b_dn, uint16_t* x_bf16, int64_t ldxb) {
+    return MlpArgs{x, ldx, M, ln_w, ln_b, shift, scale, gate, mod_sample_stride, rows_per_sample, ldt_bf16(w_up), b_up, ldt_bf16(w_dn), b_dn, ldt_bf16_mut(x_bf16), ldxb};
+}
+extern "C" int ldt_ln_mlp_resid(float* x, int64_t ldx, int64_t M, int32_t C, const float* ln_w, const float* ln_b,
+                                const float* shift, const float* scale, const float* gate, int64_t mod_sample_stride,
+                                int32_t rows_per_sample, const uint16_t* w_up, const float* b_up, const uint16_t* w_dn,
+                                const float* b_dn, uint16_t* x_bf16, int64_t ldxb, void* stream) {
+    LDT_REQUIRE(x && w_up && b_up && w_dn && b_dn, LDT_EARG, "ln_mlp: null pointer");
+    const MlpArgs a = mlp_args(x, ldx, M, ln_w, ln_b, shift, scale, gate, mod_sample_stride, rows_per_sample, w_up, b_up, w_dn, b_dn, x_bf16, ldxb);
+    return ldt_ln_mlp_launch(&a, C, ldt_stream(stream));
+}
+extern "C" int ldt_ln_mlp_resid_next(float* x, int64_t ldx, int64_t M, int32_t C, const float* ln_w, const float* ln_b,
+                                     const float* shift, const float* scale, const float* gate, int64_t mod_sample_stride,
+                                     int32_t rows_per_sample, const uint16_t* w_up, const float* b_up, const uint16_t* w_dn,
+                                     const float* b_dn, uint16_t* x_bf16, int64_t ldxb,
+                                     const float* nx_ln_w, const float* nx_ln_b, const float* nx_shift, const float* nx_scale,
+                                     int64_t nx_mod_sample_stride, int32_t nx_rows_per_sample, const uint16_t* nx_w, const float* nx_bias,
+                                     int32_t nx_N, uint16_t* nx_out, int64_t nx_ldo, void* stream) {
+    LDT_REQUIRE(x && w_up && b_up && w_dn && b_dn && nx_w && nx_out, LDT_EARG, "ln_mlp_next: null pointer");
+    MlpArgs a = mlp_args(x, ldx, M, ln_w, ln_b, shift, scale, gate, mod_sample_stride, rows_per_sample, w_up, b_up, w_dn, b_dn, x_bf16, ldxb);
+    a.next = LnLinArgs{nullptr, 0, M, nx_ln_w, nx_ln_b, nx_shift, nx_scale, nx_mod_sample_stride, nx_rows_per_sample, ldt_bf16(nx_w), nx_bias,
+                       nx_N, ldt_bf16_mut(nx_out), nx_ldo};
+    return ldt_ln_mlp_launch(&a, C, ldt_stream(stream));
+}
+extern "C" int ldt_ln_linear(const float* x, int64_t ldx, int64_t M, int32_t C, const float* ln_w, const float* ln_b,
+                             const float* shift, const float* scale, int64_t mod_sample_stride, int32_t rows_per_sample,
+                             const uint16_t* w, const float* bias, int32_t N, uint16_t* out, int64_t ldo, void* stream) {
+    LDT_REQUIRE(x && w && out, LDT_EARG, "ln_linear: null pointer");
+    LnLinArgs a{x, ldx, M, ln_w, ln_b, shift, scale, mod_sample_stride, rows_per_sample, ldt_bf16(w), bias, N, ldt_bf16_mut(out), ldo};
+    return ldt_ln_linear_launch(&a, C, ldt_stream(stream));
 }

@@ -18,11 +18,24 @@
 // Numerics are those of the unfused chain (bf16 operands, fp32 accumulation, bf16 rounding of U, h1, r and the result), only
 // the k order of the sums differs.  Weights live in LDS for the whole (persistent) kernel as ready-made 1 KB MFMA fragments
 // (host-built image: Compressor.pack); the XCD that owns a cloud keeps its 1 MB of features in its own L2.
+#include "../../include/ldt_hip.h"
 #include "kernels.h"
+
+// D = 128 channels, k in {8, 16, 32 m}, 'anchor' mode
+struct GroupMlpArgs {
+    const float* feat; const float* xyz;               // [B][n][128], [B][n][3]
+    const int* fps_idx; const int* knn_idx;            // [B][S], [B][S][k]
+    const float* alpha; const float* beta;             // [131]
+    const double* stats;                               // [2B] from ldt_group_stats_launch
+    const bf16_t* wimg;                                // MFMA fragment image of the three weight panels (132 x 1 KB)
+    const float* b1; const float* b2; const float* b3; // [128] each
+    int B, n, S, k, flat;
+    float* out;                                        // [B*S][128]
+};
 
 namespace {
 
-constexpr int GF_S1 = 17;                                   // layer-1 k-steps: 8 normalised features | 8 anchor features | xyz
+constexpr int GF_S1 = 17;                                  // layer-1 k-steps: 8 normalised features | 8 anchor features | xyz
 constexpr int GF_L2 = GF_S1 * 4, GF_L3 = GF_L2 + 32, GF_NFRAG = GF_L3 + 32;
 constexpr int GF_W_BYTES = GF_NFRAG * 1024;
 constexpr int GF_BIAS = GF_W_BYTES;                         // b1 | b2 | b3: 3 x 128 floats
@@ -238,7 +251,7 @@ __global__ __launch_bounds__(512) void grouper_mlp_kernel(const GroupMlpArgs a) 
 
 }  // namespace
 
-int ldt_grouper_mlp_launch(const GroupMlpArgs* a, hipStream_t st) {
+static int ldt_grouper_mlp_launch(const GroupMlpArgs* a, hipStream_t st) {
     LDT_REQUIRE(a->B > 0 && a->n > 0 && a->S > 0, LDT_ESHAPE, "grouper_mlp: bad shape");
     LDT_REQUIRE(a->k == 8 || a->k == 16 || (a->k > 0 && a->k % 32 == 0), LDT_ESHAPE,
                 "grouper_mlp: k = %d neighbours (built for 8, 16 and multiples of 32)", a->k);
@@ -265,4 +278,15 @@ int ldt_grouper_mlp_launch(const GroupMlpArgs* a, hipStream_t st) {
     if (gpt == 1) GF_LAUNCH(1); else if (gpt == 2) GF_LAUNCH(2); else GF_LAUNCH(4);
 #undef GF_LAUNCH
     return ldt_check_launch("grouper_mlp");
+}
+
+extern "C" int ldt_grouper_mlp(const float* feat, const float* xyz, const int32_t* fps_idx, const int32_t* knn_idx, const float* alpha,
+                               const float* beta, double* stats, int32_t B, int32_t n, int32_t S, int32_t k, int32_t D,
+                               const uint16_t* wimg, const float* b1, const float* b2, const float* b3, float* out, void* stream) {
+    LDT_REQUIRE(feat && xyz && fps_idx && knn_idx && alpha && beta && stats && wimg && b1 && b2 && b3 && out, LDT_EARG, "grouper_mlp: null pointer");
+    LDT_REQUIRE(D == 128, LDT_ESHAPE, "grouper_mlp: the fused kernel is built for 128 channels (got D=%d)", D);
+    const int rc = ldt_group_stats_launch(feat, xyz, fps_idx, knn_idx, stats, B, n, S, k, D, ldt_stream(stream));
+    if (rc != LDT_OK) return rc;
+    GroupMlpArgs a{feat, xyz, fps_idx, knn_idx, alpha, beta, stats, ldt_bf16(wimg), b1, b2, b3, B, n, S, k, 0, out};
+    return ldt_grouper_mlp_launch(&a, ldt_stream(stream));
 }

@@ -1,4 +1,6 @@
-// Internal argument blocks + launcher prototypes shared by the kernel files and api.hip.
+// Internal argument blocks, host helpers and the launcher prototypes that a second caller inside the library needs (the Score forward and
+// the sampling loop of api.hip, the GEMM and attention families among themselves).  An op with one caller has no launcher: its extern "C"
+// entry (include/ldt_hip.h) checks, sizes the grid and launches in the file of its kernel.
 #pragma once
 #include "common.h"
 
@@ -8,7 +10,15 @@ enum { EPI_F32 = 0, EPI_BF16 = 1, EPI_GELU_BF16 = 2, EPI_RELU_BF16 = 3, EPI_RESI
 static inline int ldt_wg_limit(int max_wgs) { return (max_wgs > 0 && max_wgs < LDT_NUM_CUS) ? max_wgs : LDT_NUM_CUS; }
 // THE fill rule: a persistent kernel is worth it when its tiles fill at least 5/8 of those workgroups (each caller counts its own tiles)
 static inline bool ldt_fills_workgroups(long tiles, int max_wgs) { return tiles * 8 >= (long)ldt_wg_limit(max_wgs) * 5; }
-enum { ACT_NONE = 0, ACT_SILU = 1, ACT_RELU = 2, ACT_GELU = 3 };
+// the C-ABI's opaque handles as the types the launches use: the stream, bf16 rows passed as uint16_t* / void*
+static inline hipStream_t ldt_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+static inline const bf16_t* ldt_bf16(const void* p) { return reinterpret_cast<const bf16_t*>(p); }
+static inline bf16_t* ldt_bf16_mut(void* p) { return reinterpret_cast<bf16_t*>(p); }
+// THE grid rule of a grid-stride launch: one workgroup per `per_block` items, at most `cap` of them (each kernel states its own cap)
+static inline unsigned ldt_grid_1d(long items, int per_block, long cap) {
+    const long blocks = (items + per_block - 1) / per_block;
+    return (unsigned)(blocks < cap ? blocks : cap);
+}
 
 struct GemmArgs {
     const bf16_t* X; long ldx;
@@ -77,6 +87,14 @@ struct SgemmArgs {
     void* C; long ldc; int out_bf16; int act_in; int act_out;
     int M, N, K;
 };
+// element `at` of SgemmArgs::C, fp32 or bf16 by out_bf16 (the three tiled kernels and the small-N form; the small-K form stores vectors).
+// A macro: as an inline function the same lines compile to other code in those kernels (profiles/small_kernels_refactor_codegen.txt).
+#define SGEMM_STORE(a, at, val)                                                  \
+    do {                                                                         \
+        const float _v = (val);                                                  \
+        if ((a).out_bf16) reinterpret_cast<bf16_t*>((a).C)[at] = (bf16_t)_v;     \
+        else reinterpret_cast<float*>((a).C)[at] = _v;                           \
+    } while (0)
 
 int ldt_gemm_launch(int epi, const GemmArgs* a, hipStream_t stream);
 // Which kernel a GEMM runs on: THE dispatch rule.  ldt_gemm_launch, ldt_gemm_lnfold_launch and the ldt_gemm_route query (include/ldt_hip.h)
@@ -132,10 +150,8 @@ __device__ __forceinline__ void narrow_halve(float* v, int lr) {
 int ldt_cast_pad_launch(const float* src, long lds, bf16_t* dst, long ldd, long rows, int cols, int cols_pad, hipStream_t s);
 int ldt_sampler_step_launch(const StepArgs* a, hipStream_t s);
 int ldt_advance_step_launch(int* step_ptr, hipStream_t s);
-int ldt_philox_normal_launch(float* out, long n, long elem_offset, int step, uint32_t k0, uint32_t k1, hipStream_t s);
-int ldt_sinusoid_launch(const float* t, const float* freq, float* e, int n, int half, hipStream_t s);
 int ldt_sgemm_launch(const SgemmArgs* a, hipStream_t s);
-// Which of its seven kernel forms the fp32 linear runs on: THE dispatch rule (elementwise.hip).  ldt_sgemm_launch and the ldt_sgemm_route
+// Which of its seven kernel forms the fp32 linear runs on: THE dispatch rule (sgemm.hip).  ldt_sgemm_launch and the ldt_sgemm_route
 // query (include/ldt_hip.h, which states the rule) call it and nothing else chooses a form.  misaligned: bit 0 A, 1 B, 2 C, 3 bias not
 // 16-byte aligned.  Reads the LDT_SGEMM_VALU / LDT_SGEMM_SKINNY switches once per process; touches no device and no pointer's target.
 enum { SGEMM_ROUTE_NONE = 0, SGEMM_ROUTE_NT = 1, SGEMM_ROUTE_MFMA_128 = 2, SGEMM_ROUTE_MFMA_32 = 3, SGEMM_ROUTE_SMALLN_4 = 4,
@@ -144,58 +160,9 @@ int ldt_sgemm_decide(int M, int N, int K, long lda, long ldb, long ldc, int misa
 int ldt_sgemm_mfma_launch(const SgemmArgs* a, int route, hipStream_t s);      // sgemm_mfma.hip: SGEMM_ROUTE_MFMA_128 / _32 (grid and launch)
 int ldt_skinny_linear_launch(const SgemmArgs* a, int route, hipStream_t s);   // skinny_linear.hip: SGEMM_ROUTE_SMALLN_* / SMALLK_* (grid sized to the device, launch)
 
-int ldt_fps_launch(const float* xyz, int B, int n, int m, int skip_near_origin, int* idx, hipStream_t s);
-int ldt_fps_wave_launch(const float* xyz, int B, int n, int m, int skip_near_origin, int* idx, hipStream_t s);   // fps_wave.hip
-int ldt_knn_launch(const float* xyz, const float* centers, int B, int n, int S, int k, int* out, float* dist_out, hipStream_t s);
-int ldt_group_launch(const float* feat, const float* xyz, const int* fps_idx, const int* knn_idx, const float* alpha,
-                     const float* beta, double* stats, int B, int n, int S, int k, int D, bf16_t* U, int ldu,
-                     int center_mode, float* gmean, hipStream_t s);
+int ldt_fps_wave_launch(const float* xyz, int B, int n, int m, int skip_near_origin, int* idx, hipStream_t s);   // fps_wave.hip (ldt_fps of pointops.hip routes to it)
+// per-sample sums of the 'anchor' grouping (pointops.hip): ldt_group_normalize and ldt_grouper_mlp (grouper_mlp.hip) both start with it
 int ldt_group_stats_launch(const float* feat, const float* xyz, const int* fps_idx, const int* knn_idx, double* stats,
                            int B, int n, int S, int k, int D, hipStream_t s);
-// grouping + PreExtraction + neighbour max in one kernel (grouper_mlp.hip): D = 128 channels, k in {8, 16, 32 m}, 'anchor' mode
-struct GroupMlpArgs {
-    const float* feat; const float* xyz;               // [B][n][128], [B][n][3]
-    const int* fps_idx; const int* knn_idx;            // [B][S], [B][S][k]
-    const float* alpha; const float* beta;             // [131]
-    const double* stats;                               // [2B] from ldt_group_stats_launch
-    const bf16_t* wimg;                                // MFMA fragment image of the three weight panels (132 x 1 KB)
-    const float* b1; const float* b2; const float* b3; // [128] each
-    int B, n, S, k, flat;
-    float* out;                                        // [B*S][128]
-};
-int ldt_grouper_mlp_launch(const GroupMlpArgs* a, hipStream_t s);
-int ldt_norm_points_launch(const float* xyz, int B, int n, float* out, hipStream_t s);
-int ldt_mixture_seed_launch(const float* eps, const float* sig, const float* mu, const float* logits, int n_mix, int D, long rows, float* out, hipStream_t s);
-int ldt_gather_rows_launch(const float* src, const int* idx, int B, int n, int S, int C, float* out, hipStream_t s);
-int ldt_maxpool_launch(const void* in, int in_bf16, long ld, long G, int n, int C, float* out, hipStream_t s);
-int ldt_actnorm_launch(float* x, const float* shift, const float* log_scale, long B, long per_sample, hipStream_t s);
-int ldt_actnorm_bwd_launch(const float* dz, const float* z, const float* log_scale, long B, long per_sample, float* dx, float* dshift,
-                           float* dlog_scale, hipStream_t s);   // actnorm_bwd.hip
-int ldt_reparam_launch(const float* post, const float* noise, float* out, long ldo, float* mu_out, float* lv_out,
-                       long rows, int z, float lo, float hi, hipStream_t s);
-int ldt_chamfer_launch(const float* a, const float* b, int B, int na, int nb, float* dl, float* dr, hipStream_t s);
-// fused LayerNorm + MLP + gated residual for narrow blocks (fused_mlp.hip)
-struct LnLinArgs {
-    const float* x; long ldx; long M;
-    const float* ln_w; const float* ln_b; const float* shift; const float* scale; long mod_sample_stride; int rows_per_sample;
-    const bf16_t* w; const float* bias; int N;          // [N][C], [N] (nullable)
-    bf16_t* out; long ldo;
-};
-struct MlpArgs {
-    float* x; long ldx; long M;
-    const float* ln_w; const float* ln_b;              // affine LayerNorm (no-condition blocks) or null
-    const float* shift; const float* scale;            // AdaLN modulation (per sample) or null
-    const float* gate;                                 // per-sample gate or null (= 1)
-    long mod_sample_stride; int rows_per_sample;
-    const bf16_t* w_up; const float* b_up;             // [4C][C], [4C]
-    const bf16_t* w_dn; const float* b_dn;             // [C][4C], [C]
-    bf16_t* x_bf16; long ldxb;                          // optional bf16 mirror of the updated x (the next block's K/V source) or null
-    LnLinArgs next;                                     // optional (next.w != null): LN + linear of the block that follows, on the new x (next.x unused)
-};
-int ldt_ln_mlp_launch(const MlpArgs* a, int C, hipStream_t st);
-// fused LayerNorm + linear (bf16 out) for narrow blocks (fused_mlp.hip)
-int ldt_ln_linear_launch(const LnLinArgs* a, int C, hipStream_t st);
-int ldt_chamfer_pairwise_launch(const float* x, const float* y, int S, int R, int n, int m, float* cd, hipStream_t st);
-int ldt_emd_approx_launch(const float* x, const float* y, int S, int R, int n, int m, int pairwise, float* out, hipStream_t st);
-int ldt_fold_monitor_launch(const float* stats, int parts, long M, int K, float* out, hipStream_t s);   // samplers.hip
+int ldt_fold_monitor_launch(const float* stats, int parts, long M, int K, float* out, hipStream_t s);   // elementwise.hip
 int ldt_cond_rows_launch(const float* temb, const float* extra, float* c, void* c_bf16, const int* step_ptr, int batch, int t_dim, int silu_out, hipStream_t s);

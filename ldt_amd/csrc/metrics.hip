@@ -1,10 +1,8 @@
 // Generation-quality metrics of the reference's validation loop (evaluation/evaluation_metrics.py:112-277) as gfx950
 // kernels: all-pairs Chamfer distance and the approximate-matching EMD.  VALU / LDS-broadcast bound (3-D points: no
 // GEMM shape worth MFMA), one workgroup per cloud pair, both clouds resident in LDS, nothing materialised in HBM.
-#include "common.h"
+#include "../../include/ldt_hip.h"
 #include "kernels.h"
-
-#define TRY_LAUNCH(what) do { const int _rc = ldt_check_launch(what); if (_rc != LDT_OK) return _rc; } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------
 // All-pairs Chamfer: cd[s][r] = mean_j min_i P + mean_i min_j P with P[i][j] = |x_i|^2 + |y_j|^2 - 2 x_i.y_j — the
@@ -69,9 +67,10 @@ __global__ __launch_bounds__(256) void chamfer_pairwise_kernel(const float* __re
     if (threadIdx.x == 0) cd[(long)s * R + r] = dl + dr;
 }
 
-int ldt_chamfer_pairwise_launch(const float* x, const float* y, int S, int R, int n, int m, float* cd, hipStream_t st) {
+extern "C" int ldt_chamfer_pairwise(const float* x, const float* y, int32_t S, int32_t R, int32_t n, int32_t m, float* cd, void* stream) {
+    LDT_REQUIRE(x && y && cd, LDT_EARG, "chamfer_pairwise: null pointer");
     LDT_REQUIRE(S > 0 && R > 0 && n > 0 && m > 0 && S <= 65535, LDT_ESHAPE, "chamfer_pairwise: bad shape S=%d R=%d n=%d m=%d", S, R, n, m);
-    hipLaunchKernelGGL(chamfer_pairwise_kernel, dim3(R, S), dim3(256), 0, st, x, y, n, m, R, cd);
+    hipLaunchKernelGGL(chamfer_pairwise_kernel, dim3(R, S), dim3(256), 0, ldt_stream(stream), x, y, n, m, R, cd);
     return ldt_check_launch("chamfer_pairwise");
 }
 
@@ -161,14 +160,15 @@ __global__ __launch_bounds__(1024) void emd_approx_kernel(const float* __restric
     }
 }
 
-int ldt_emd_approx_launch(const float* x, const float* y, int S, int R, int n, int m, int pairwise, float* out, hipStream_t st) {
+extern "C" int ldt_emd_approx(const float* x, const float* y, int32_t S, int32_t R, int32_t n, int32_t m, int32_t pairwise,
+                              float* out, void* stream) {
+    LDT_REQUIRE(x && y && out, LDT_EARG, "emd_approx: null pointer");
     LDT_REQUIRE(S > 0 && R > 0 && n > 0 && m > 0, LDT_ESHAPE, "emd_approx: bad shape");
     LDT_REQUIRE(pairwise || S == R, LDT_ESHAPE, "emd_approx: batched mode pairs cloud b with cloud b (S=%d != R=%d)", S, R);
     const size_t lds = (size_t)(n + m) * (sizeof(float4) + sizeof(float));
     LDT_REQUIRE(lds <= 150 * 1024, LDT_ESHAPE, "emd_approx: n + m = %d points exceed the LDS-resident limit (7680)", n + m);
     LDT_ENSURE_LDS(emd_approx_kernel, 150 * 1024, "emd_approx");
     const long npairs = pairwise ? (long)S * R : S;
-    const int grid = (int)(npairs < 4096 ? npairs : 4096);
-    hipLaunchKernelGGL(emd_approx_kernel, dim3(grid), dim3(1024), lds, st, x, y, S, R, n, m, pairwise, out);
+    hipLaunchKernelGGL(emd_approx_kernel, dim3(ldt_grid_1d(npairs, 1, 4096)), dim3(1024), lds, ldt_stream(stream), x, y, S, R, n, m, pairwise, out);
     return ldt_check_launch("emd_approx");
 }

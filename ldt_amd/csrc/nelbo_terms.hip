@@ -87,7 +87,7 @@ extern "C" int ldt_nelbo_terms(const float* eta, const float* params, const floa
     LDT_REQUIRE(eta && params && logqz && sample_sums, LDT_EARG,
                 "nelbo_terms: null pointer (sample_sums is the first stage's output and is required)");
     LDT_REQUIRE(B > 0 && B <= 0x7fffffffL && per_sample > 0, LDT_ESHAPE, "nelbo_terms: B %ld, per_sample %ld", (long)B, (long)per_sample);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = ldt_stream(stream);
     if (per_sample % 4 == 0 && ldt_aligned16(eta) && ldt_aligned16(params) && ldt_aligned16(logqz))
         hipLaunchKernelGGL(nelbo_sample_kernel<4>, dim3((unsigned)B), dim3(NELBO_WG), 0, s, eta, params, logqz, weight, (long)per_sample, sample_sums);
     else

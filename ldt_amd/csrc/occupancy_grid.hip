@@ -81,7 +81,7 @@ extern "C" int ldt_occupancy_grid(const float* pts, int32_t S, int32_t n, const 
     LDT_REQUIRE(pts && cells && counters && bernoulli, LDT_EARG, "occupancy_grid: null pointer");
     LDT_REQUIRE(S > 0 && n > 0 && G > 0 && G <= OCC_MAX_CELLS && (long)n * 3 <= 0x7fffffffL, LDT_ESHAPE,
                 "occupancy_grid: S %d clouds of n %d points, G %d cells (1..%d)", S, n, G, OCC_MAX_CELLS);
-    hipLaunchKernelGGL(occupancy_grid_kernel, dim3((unsigned)S), dim3(OCC_WG), 0, reinterpret_cast<hipStream_t>(stream), pts, n, cells, G, counters,
+    hipLaunchKernelGGL(occupancy_grid_kernel, dim3((unsigned)S), dim3(OCC_WG), 0, ldt_stream(stream), pts, n, cells, G, counters,
                        bernoulli);
     return ldt_check_launch("occupancy_grid");
 }

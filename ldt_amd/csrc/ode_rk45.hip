@@ -13,10 +13,6 @@ typedef double f64x2 __attribute__((ext_vector_type(2)));
 #define ODE_MAX_GRID 1024          // = LDT_ODE_SUMSQ_SCRATCH: one fp64 partial per workgroup of the norm's first stage
 
 __host__ __device__ static inline bool ode_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-static inline unsigned ode_grid(long npair) {
-    long blocks = (npair + ODE_THREADS - 1) / ODE_THREADS;
-    return (unsigned)(blocks > ODE_MAX_GRID ? ODE_MAX_GRID : blocks);
-}
 
 // ------------------------------------------------------------------------------------------------
 // y_s = y + h * (((a0 K0 + a1 K1) + a2 K2) + ...), 1..6 terms left to right in fp64; x_s = (float)y_s is the Score's input.
@@ -62,8 +58,8 @@ extern "C" int ldt_ode_stage(const double* y, const double* k0, const double* k1
     for (int s = 0; s < nterms; ++s) al = al && ldt_aligned16(g.k[s]);
     LDT_REQUIRE(al, LDT_EALIGN, "ode_stage: fp64 buffers must be 16-byte aligned, x_out 8-byte aligned");
     g.npair = n / 2;
-    const dim3 grid(ode_grid(g.npair)), block(ODE_THREADS);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(ldt_grid_1d(g.npair, ODE_THREADS, ODE_MAX_GRID)), block(ODE_THREADS);
+    hipStream_t s = ldt_stream(stream);
     switch (nterms) {
         case 1: hipLaunchKernelGGL(ode_stage_kernel<1>, grid, block, 0, s, g); break;
         case 2: hipLaunchKernelGGL(ode_stage_kernel<2>, grid, block, 0, s, g); break;
@@ -106,7 +102,7 @@ extern "C" int ldt_ode_rhs(const float* x, const float* p, int32_t is_score, flo
     LDT_REQUIRE(n > 0 && n % 2 == 0, LDT_ESHAPE, "ode_rhs: n=%ld must be a positive multiple of 2 (two fp64 per 16-byte access)", (long)n);
     LDT_REQUIRE(ode_aligned8(x) && ode_aligned8(p) && ldt_aligned16(k_out), LDT_EALIGN, "ode_rhs: x / p must be 8-byte, k_out 16-byte aligned");
     const float hg2 = 0.5f * g2;                               // `0.5 * self.g2(t)` (exact)
-    hipLaunchKernelGGL(ode_rhs_kernel, dim3(ode_grid(n / 2)), dim3(ODE_THREADS), 0, reinterpret_cast<hipStream_t>(stream), x, p, (int)is_score, f,
+    hipLaunchKernelGGL(ode_rhs_kernel, dim3(ldt_grid_1d(n / 2, ODE_THREADS, ODE_MAX_GRID)), dim3(ODE_THREADS), 0, ldt_stream(stream), x, p, (int)is_score, f,
                        hg2, sd, k_out, (long)(n / 2));
     return ldt_check_launch("ode_rhs");
 }
@@ -182,10 +178,10 @@ extern "C" int ldt_ode_scaled_sumsq(const double* v0, const double* v1, const do
     for (int s = 0; s < nvec; ++s) al = al && ldt_aligned16(g.v[s]);
     LDT_REQUIRE(al, LDT_EALIGN, "ode_scaled_sumsq: fp64 vectors must be 16-byte aligned, scratch / out 8-byte aligned");
     g.npair = n / 2;
-    unsigned blocks = ode_grid(g.npair);
+    unsigned blocks = ldt_grid_1d(g.npair, ODE_THREADS, ODE_MAX_GRID);
     if (blocks > (unsigned)scratch_len) blocks = (unsigned)scratch_len;
     const dim3 grid(blocks), block(ODE_THREADS);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = ldt_stream(stream);
     switch (nvec) {
         case 1: hipLaunchKernelGGL(ode_sumsq_partial_kernel<1>, grid, block, 0, s, g); break;
         case 2: hipLaunchKernelGGL(ode_sumsq_partial_kernel<2>, grid, block, 0, s, g); break;

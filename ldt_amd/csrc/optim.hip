@@ -51,7 +51,7 @@ __global__ __launch_bounds__(SUMSQ_WG) void sumsq_final_kernel(const double* __r
 extern "C" int ldt_sumsq(const float* x, int64_t n, double* scratch, int32_t scratch_len, float max_norm, float* out, void* stream) {
     LDT_REQUIRE(x && scratch && out, LDT_EARG, "sumsq: null pointer");
     LDT_REQUIRE(n > 0 && scratch_len > 0, LDT_ESHAPE, "sumsq: n %ld, scratch_len %d", (long)n, scratch_len);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = ldt_stream(stream);
     long parts = (n + SUMSQ_WG - 1) / SUMSQ_WG;
     if (parts > scratch_len) parts = scratch_len;
     if (parts > LDT_ODE_SUMSQ_SCRATCH) parts = LDT_ODE_SUMSQ_SCRATCH;
@@ -107,9 +107,7 @@ extern "C" int ldt_adam_ema_step(float* param, float* grad, float* exp_avg, floa
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
     const float neg_step_size = (float)(-(lr / bc1));
     const float bc2_sqrt = (float)sqrt(bc2);
-    long blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(adam_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), param, grad, exp_avg, exp_avg_sq,
+    hipLaunchKernelGGL(adam_ema_kernel, dim3(ldt_grid_1d(n, 256, 4096)), dim3(256), 0, ldt_stream(stream), param, grad, exp_avg, exp_avg_sq,
                        ema, (long)n, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, weight_decay, neg_step_size, bc2_sqrt,
                        (float)(1.0 - ema_decay), ema_init, clip_factor);
     return ldt_check_launch("adam_ema_step");

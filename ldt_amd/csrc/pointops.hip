@@ -1,10 +1,16 @@
-// Point-cloud front end of the Compressor encoder (gfx950): farthest point sampling, kNN (distance + top-k
-// selection), neighbourhood gather + anchor normalisation, max-pooling, ActNorm and the reparameterised
-// posterior draw.  Integer/index work is exact; floating point follows the operation order stated per kernel.
+// Point-cloud ops of the Compressor (gfx950).  Integer/index work is exact; floating point follows the operation order stated per kernel.
+//   fps                     farthest point sampling (ldt_fps; many small clouds go to fps_wave.hip)
+//   knn                     distance + exact top-k selection (ldt_knn)
+//   group_mean, group_stats, group_stats_vec, group_build    neighbourhood gather + anchor / centre normalisation (ldt_group_normalize;
+//                           ldt_group_stats_launch also opens ldt_grouper_mlp, grouper_mlp.hip)
+//   gather_rows, maxpool    index_points and the max over neighbours / points (ldt_gather_rows, ldt_maxpool)
+//   chamfer_min             per-point Chamfer minima (ldt_chamfer)
+//   norm_points, mixture_seed    the input normalisation and the decoder's seed rows (ldt_norm_points, ldt_mixture_seed)
 // Reference: model/Compressor/layers.py:65-112 (square_distance / knn_point / cluster), :288-319
-// (LocalGrouper.forward), model/functional/src/sampling/sampling.cu:86-167 (FPS twin), Network.py:26-29,76.
+// (LocalGrouper.forward), model/functional/src/sampling/sampling.cu:86-167 (FPS twin), Network.py:170-174.
 #include <stdlib.h>
 
+#include "../../include/ldt_hip.h"
 #include "kernels.h"
 
 #define TRY_LAUNCH(what) do { const int _rc = ldt_check_launch(what); if (_rc != LDT_OK) return _rc; } while (0)
@@ -93,7 +99,9 @@ __global__ __launch_bounds__(512) void fps_kernel(const float* __restrict__ xyz,
     }
 }
 
-int ldt_fps_launch(const float* xyz, int B, int n, int m, int skip_near_origin, int* idx, hipStream_t s) {
+extern "C" int ldt_fps(const float* xyz, int32_t B, int32_t n, int32_t m, int32_t skip_near_origin, int32_t* idx, void* stream) {
+    LDT_REQUIRE(xyz && idx, LDT_EARG, "fps: null pointer");
+    hipStream_t s = ldt_stream(stream);
     LDT_REQUIRE(B > 0 && n > 0 && m > 0 && m <= n, LDT_ESHAPE, "fps: B=%d n=%d m=%d", B, n, m);
     LDT_REQUIRE(n <= 512 * 16, LDT_ESHAPE, "fps: n=%d > 8192 points per cloud not built", n);
     static const int wave_env = getenv("LDT_FPS_WAVE") ? atoi(getenv("LDT_FPS_WAVE")) : -1;   // 0 / 1 force (tools/dbg)
@@ -237,7 +245,10 @@ __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ xyz,
     }
 }
 
-int ldt_knn_launch(const float* xyz, const float* centers, int B, int n, int S, int k, int* out, float* dist_out, hipStream_t s) {
+extern "C" int ldt_knn(const float* xyz, const float* centers, int32_t B, int32_t n, int32_t S, int32_t k,
+                       int32_t* out, float* dist_out, void* stream) {
+    LDT_REQUIRE(xyz && centers && out, LDT_EARG, "knn: null pointer");
+    hipStream_t s = ldt_stream(stream);
     LDT_REQUIRE(B > 0 && n > 0 && S > 0 && k > 0 && k <= n, LDT_ESHAPE, "knn: B=%d n=%d S=%d k=%d", B, n, S, k);
     LDT_REQUIRE(n <= 64 * 128, LDT_ESHAPE, "knn: n=%d > 8192 points per cloud not built", n);
     const long nq = (long)B * S;
@@ -385,27 +396,27 @@ int ldt_group_stats_launch(const float* feat, const float* xyz, const int* fps_i
     LDT_REQUIRE(B > 0 && n > 0 && S > 0 && k > 0 && D > 0, LDT_ESHAPE, "group_stats: bad shape");
     hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * 2 * B, s);
     if (e != hipSuccess) { ldt_set_error("group: memset: %s", hipGetErrorString(e)); return (int)e; }
-    const long rows = (long)S * k;
-    int bx = (int)((rows + 3) / 4); if (bx > 256) bx = 256;
-    int gx = (S + 3) / 4; if (gx > 64) gx = 64;
+    const unsigned bx = ldt_grid_1d((long)S * k, 4, 256), gx = ldt_grid_1d(S, 4, 64);
     if (D == 128 && ldt_aligned16(feat)) hipLaunchKernelGGL(group_stats_vec_kernel<32>, dim3(gx, B), dim3(256), 0, s, feat, xyz, fps_idx, knn_idx, n, S, k, stats);
     else if (D == 64 && ldt_aligned16(feat)) hipLaunchKernelGGL(group_stats_vec_kernel<16>, dim3(gx, B), dim3(256), 0, s, feat, xyz, fps_idx, knn_idx, n, S, k, stats);
     else hipLaunchKernelGGL(group_stats_kernel<false>, dim3(bx, B), dim3(256), 0, s, feat, xyz, fps_idx, knn_idx, nullptr, n, S, k, D, stats);
     return ldt_check_launch("group_stats");
 }
 
-int ldt_group_launch(const float* feat, const float* xyz, const int* fps_idx, const int* knn_idx, const float* alpha,
-                     const float* beta, double* stats, int B, int n, int S, int k, int D, bf16_t* U, int ldu,
-                     int center_mode, float* gmean, hipStream_t s) {
+extern "C" int ldt_group_normalize(const float* feat, const float* xyz, const int32_t* fps_idx, const int32_t* knn_idx,
+                                   const float* alpha, const float* beta, double* stats, int32_t B, int32_t n, int32_t S,
+                                   int32_t k, int32_t D, uint16_t* U_bits, int32_t ldu, int32_t center_mode, float* gmean,
+                                   void* stream) {
+    LDT_REQUIRE(feat && xyz && fps_idx && knn_idx && alpha && beta && stats && U_bits, LDT_EARG, "group: null pointer");
     LDT_REQUIRE(B > 0 && n > 0 && S > 0 && k > 0 && D > 0 && ldu >= 2 * D + 3, LDT_ESHAPE, "group: bad shape");
     LDT_REQUIRE(center_mode == 0 || (center_mode == 1 && gmean), LDT_EARG, "group: mode 1 ('center') needs the group-mean workspace");
-    const long rows = (long)S * k;
-    int bx = (int)((rows + 3) / 4); if (bx > 256) bx = 256;
+    hipStream_t s = ldt_stream(stream);
+    bf16_t* U = ldt_bf16_mut(U_bits);
+    const unsigned bx = ldt_grid_1d((long)S * k, 4, 256);
     if (center_mode) {
         hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * 2 * B, s);
         if (e != hipSuccess) { ldt_set_error("group: memset: %s", hipGetErrorString(e)); return (int)e; }
-        long mb = ((long)S * (D + 3) + 255) / 256; if (mb > 1024) mb = 1024;
-        hipLaunchKernelGGL(group_mean_kernel, dim3((unsigned)mb, B), dim3(256), 0, s, feat, xyz, knn_idx, n, S, k, D, gmean);
+        hipLaunchKernelGGL(group_mean_kernel, dim3(ldt_grid_1d((long)S * (D + 3), 256, 1024), B), dim3(256), 0, s, feat, xyz, knn_idx, n, S, k, D, gmean);
         TRY_LAUNCH("group_mean");
         hipLaunchKernelGGL(group_stats_kernel<true>, dim3(bx, B), dim3(256), 0, s, feat, xyz, fps_idx, knn_idx, gmean, n, S, k, D, stats);
         TRY_LAUNCH("group_stats");
@@ -427,11 +438,11 @@ __global__ void gather_rows_kernel(const float* __restrict__ src, const int* __r
         out[i] = src[(b * n + idx[row]) * C + c];
     }
 }
-int ldt_gather_rows_launch(const float* src, const int* idx, int B, int n, int S, int C, float* out, hipStream_t s) {
+extern "C" int ldt_gather_rows(const float* src, const int32_t* idx, int32_t B, int32_t n, int32_t S, int32_t C, float* out, void* stream) {
+    LDT_REQUIRE(src && idx && out, LDT_EARG, "gather_rows: null pointer");
     LDT_REQUIRE(B > 0 && n > 0 && S > 0 && C > 0, LDT_ESHAPE, "gather_rows: bad shape");
     const long total = (long)B * S * C;
-    long blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, idx, n, S, C, out, total);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(ldt_grid_1d(total, 256, 4096)), dim3(256), 0, ldt_stream(stream), src, idx, n, S, C, out, total);
     return ldt_check_launch("gather_rows");
 }
 
@@ -447,49 +458,13 @@ __global__ void maxpool_kernel(const TI* __restrict__ in, long ld, int n, int C,
         out[i] = m;
     }
 }
-int ldt_maxpool_launch(const void* in, int in_bf16, long ld, long G, int n, int C, float* out, hipStream_t s) {
+extern "C" int ldt_maxpool(const void* in, int32_t in_bf16, int64_t ld, int64_t G, int32_t n, int32_t C, float* out, void* stream) {
+    LDT_REQUIRE(in && out, LDT_EARG, "maxpool: null pointer");
     LDT_REQUIRE(G > 0 && n > 0 && C > 0 && ld >= C, LDT_ESHAPE, "maxpool: bad shape");
-    long blocks = (G * C + 255) / 256; if (blocks > 4096) blocks = 4096;
-    if (in_bf16) hipLaunchKernelGGL(maxpool_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)in, ld, n, C, out, G);
-    else hipLaunchKernelGGL(maxpool_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)in, ld, n, C, out, G);
+    const dim3 grid(ldt_grid_1d(G * C, 256, 4096)), block(256);
+    if (in_bf16) hipLaunchKernelGGL(maxpool_kernel<bf16_t>, grid, block, 0, ldt_stream(stream), ldt_bf16(in), (long)ld, n, C, out, (long)G);
+    else hipLaunchKernelGGL(maxpool_kernel<float>, grid, block, 0, ldt_stream(stream), (const float*)in, (long)ld, n, C, out, (long)G);
     return ldt_check_launch("maxpool");
-}
-
-// ActNorm (model/layers.py:103-107, eval): y[b,t,c] = (x[b,t,c] - shift[t,c]) * exp(-log_scale[t,c]), in place
-__global__ void actnorm_kernel(float* __restrict__ x, const float* __restrict__ shift, const float* __restrict__ log_scale,
-                               long total, long per_sample) {
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const long j = i % per_sample;
-        x[i] = (x[i] - shift[j]) * expf(-log_scale[j]);
-    }
-}
-int ldt_actnorm_launch(float* x, const float* shift, const float* log_scale, long B, long per_sample, hipStream_t s) {
-    LDT_REQUIRE(B > 0 && per_sample > 0, LDT_ESHAPE, "actnorm: bad shape");
-    const long total = B * per_sample;
-    long blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(actnorm_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, shift, log_scale, total, per_sample);
-    return ldt_check_launch("actnorm");
-}
-
-// posterior draw (Network.py:26-29,75-77): mu = post[:, :z], logvar = clamp(post[:, z:], lo, hi);
-// eps = mu + exp(logvar / 2) * noise   -> written into a strided slice of all_eps
-__global__ void reparam_kernel(const float* __restrict__ post, const float* __restrict__ noise, float* __restrict__ out,
-                               long ldo, float* __restrict__ mu_out, float* __restrict__ lv_out, long rows, int z, float lo, float hi) {
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < rows * z; i += (long)gridDim.x * blockDim.x) {
-        const long r = i / z; const int c = (int)(i % z);
-        const float mu = post[r * 2 * z + c];
-        const float lv = fminf(fmaxf(post[r * 2 * z + z + c], lo), hi);
-        out[r * ldo + c] = reparam_eps(mu, lv, noise[i]);
-        if (mu_out) { mu_out[i] = mu; lv_out[i] = lv; }
-    }
-}
-int ldt_reparam_launch(const float* post, const float* noise, float* out, long ldo, float* mu_out, float* lv_out,
-                       long rows, int z, float lo, float hi, hipStream_t s) {
-    LDT_REQUIRE(rows > 0 && z > 0 && ldo >= z, LDT_ESHAPE, "reparam: bad shape");
-    LDT_REQUIRE((mu_out == nullptr) == (lv_out == nullptr), LDT_EARG, "reparam: mu/logvar outputs go together");
-    long blocks = (rows * z + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(reparam_kernel, dim3((unsigned)blocks), dim3(256), 0, s, post, noise, out, ldo, mu_out, lv_out, rows, z, lo, hi);
-    return ldt_check_launch("reparam");
 }
 
 // Chamfer distance (evaluation/evaluation_metrics.py:23-33,88): dl[b,j] = min_i |a_i - b_j|^2, dr[b,i] = min_j |a_i - b_j|^2
@@ -511,8 +486,10 @@ __global__ void chamfer_min_kernel(const float* __restrict__ q, const float* __r
     }
     out[(long)b * nq + i] = m;
 }
-int ldt_chamfer_launch(const float* a, const float* b, int B, int na, int nb, float* dl, float* dr, hipStream_t s) {
+extern "C" int ldt_chamfer(const float* a, const float* b, int32_t B, int32_t na, int32_t nb, float* dl, float* dr, void* stream) {
+    LDT_REQUIRE(a && b && dl && dr, LDT_EARG, "chamfer: null pointer");
     LDT_REQUIRE(B > 0 && na > 0 && nb > 0, LDT_ESHAPE, "chamfer: bad shape");
+    hipStream_t s = ldt_stream(stream);
     // dl (P.min(1)): for every point of b the nearest a ; dr (P.min(2)): for every point of a the nearest b
     hipLaunchKernelGGL(chamfer_min_kernel, dim3((nb + 255) / 256, B), dim3(256), 0, s, b, a, nb, na, dl);
     TRY_LAUNCH("chamfer_dl");
@@ -553,9 +530,10 @@ __global__ __launch_bounds__(256) void norm_points_kernel(const float* __restric
     __syncthreads();
     for (int i = threadIdx.x; i < 3 * n; i += 256) { const int c = i % 3; o[i] = (p[i] - mean_s[c]) * inv_s[c]; }
 }
-int ldt_norm_points_launch(const float* xyz, int B, int n, float* out, hipStream_t s) {
+extern "C" int ldt_norm_points(const float* xyz, int32_t B, int32_t n, float* out, void* stream) {
+    LDT_REQUIRE(xyz && out, LDT_EARG, "norm_points: null pointer");
     LDT_REQUIRE(B > 0 && n > 1, LDT_ESHAPE, "norm_points: B=%d n=%d", B, n);
-    hipLaunchKernelGGL(norm_points_kernel, dim3(B), dim3(256), 0, s, xyz, n, out);
+    hipLaunchKernelGGL(norm_points_kernel, dim3(B), dim3(256), 0, ldt_stream(stream), xyz, n, out);
     return ldt_check_launch("norm_points");
 }
 
@@ -577,9 +555,10 @@ __global__ __launch_bounds__(256) void mixture_seed_kernel(const float* __restri
         out[i] = acc;
     }
 }
-int ldt_mixture_seed_launch(const float* eps, const float* sig, const float* mu, const float* logits, int n_mix, int D, long rows, float* out, hipStream_t s) {
-    LDT_REQUIRE(n_mix >= 1 && n_mix <= 8 && D > 0 && rows > 0, LDT_ESHAPE, "mixture_seed: n_mix=%d (<= 8) D=%d rows=%ld", n_mix, D, rows);
-    long blocks = (rows * D + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(mixture_seed_kernel, dim3((unsigned)blocks), dim3(256), 0, s, eps, sig, mu, logits, n_mix, D, rows, out);
+extern "C" int ldt_mixture_seed(const float* eps, const float* sig, const float* mu, const float* logits, int32_t n_mix, int32_t D, int64_t rows,
+                                float* out, void* stream) {
+    LDT_REQUIRE(eps && sig && mu && logits && out, LDT_EARG, "mixture_seed: null pointer");
+    LDT_REQUIRE(n_mix >= 1 && n_mix <= 8 && D > 0 && rows > 0, LDT_ESHAPE, "mixture_seed: n_mix=%d (<= 8) D=%d rows=%ld", n_mix, D, (long)rows);
+    hipLaunchKernelGGL(mixture_seed_kernel, dim3(ldt_grid_1d(rows * D, 256, 4096)), dim3(256), 0, ldt_stream(stream), eps, sig, mu, logits, n_mix, D, (long)rows, out);
     return ldt_check_launch("mixture_seed");
 }

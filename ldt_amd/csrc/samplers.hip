@@ -1,8 +1,125 @@
-// Device ops of the remaining samplers around the Score forward: LangevinCorrector (diffusion/diffusion_continuous.py:193-210)
-// and PNDM (:260-316).  All are HBM-streaming passes over the latents [B][tokens*z] fp32 — a few MB, far below the
-// Score forward they sit next to — written for determinism (fixed reduction order, no atomics) rather than speed.
+// Device ops of the samplers around the Score forward.  All are HBM-streaming passes over the latents [B][tokens*z] fp32 — a few MB, far
+// below the Score forward they sit next to — written for determinism (fixed reduction order, no atomics) rather than speed:
+//   sampler_step, advance_step    the fused predictor update with in-kernel Philox noise and the device-side step counter (ldt_sampler_step,
+//                                 ldt_sampler_step_traj; the sampling loop of api.hip)
+//   philox_normal                 the stand-alone normal fill on the same Philox stream (ldt_philox_normal)
+//   batch_norms, norm_sum, langevin_coef    LangevinCorrector (diffusion/diffusion_continuous.py:193-210: ldt_batch_norm_sum, ldt_langevin_coef)
+//   pndm_transfer, lincomb4       PNDM (:260-316: ldt_pndm_transfer, ldt_lincomb4)
+//   vpsde_score, sde_score        score = -params / sqrt(var(t)) per SDE family (ldt_vpsde_score, ldt_sde_score)
 #include "../../include/ldt_hip.h"
 #include "kernels.h"
+
+// ------------------------------------------------------------------------------------------------
+// Philox4x32-10 + Box-Muller (philox4x32_10, box_muller): common.h — shared with the held-out-loss kernels (eval_loss.hip).
+
+// Fused predictor update (one pass over the latents):
+//   mode 0 (ancestral, exact op order of diffusion_continuous.py:152-162 + Latent_SDE_Trainer.py:57-61):
+//       score = -params / std ; x_mean = (x + beta*score) / sqrt(1-beta) ; x = x_mean + sqrt(beta)*z
+//       coef[step] = {beta, std, sqrt(1-beta), sqrt(beta)}   (host fp32 tables, SURVEY hard part 4)
+//   mode 1 (folded; reversediffusion / eulermaruyama / ddim, :141-191):
+//       x_mean = A*x + Bc*params ; x = x_mean + Cc*z        coef[step] = {A, Bc, Cc, 0}
+// z comes from `noise` (parity mode: injected CPU draws) or from Philox keyed by
+// (seed, stream id = step*philox_mul + philox_add, global element index) so that a sample's noise does not depend on how the batch is sharded.
+__global__ __launch_bounds__(256) void sampler_step_kernel(const StepArgs a) {
+    const int step = a.step_ptr ? *a.step_ptr : a.step_host;
+    const f32x4 cf = *reinterpret_cast<const f32x4*>(a.coef + 4L * step);
+    const float* nz = a.noise ? a.noise + (long)step * a.noise_step_stride : nullptr;
+    const long nvec = a.n / 4;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(a.x + 4 * i);
+        const f32x4 p = *reinterpret_cast<const f32x4*>(a.params + 4 * i);
+        f32x4 z;
+        if (nz) {
+            z = *reinterpret_cast<const f32x4*>(nz + 4 * i);
+        } else {
+            const uint64_t e = (uint64_t)(a.elem_offset / 4 + i);
+            uint32_t c[4] = {(uint32_t)e, (uint32_t)(e >> 32), (uint32_t)(step * a.philox_mul + a.philox_add), 0x4C445421u};
+            philox4x32_10(c, a.seed_lo, a.seed_hi);
+            float z0, z1, z2, z3;
+            box_muller(c[0], c[1], z0, z1);
+            box_muller(c[2], c[3], z2, z3);
+            z = (f32x4){z0, z1, z2, z3};
+        }
+        f32x4 xm, xn;
+        {
+#pragma clang fp contract(off)      // the reference's separate mul/add/div roundings, no FMA (HIP's __f*_rn are plain ops)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (a.mode == 0) {
+                    const float score = -p[j] / cf[1];
+                    const float bs = cf[0] * score;
+                    const float num = x[j] + bs;
+                    xm[j] = num / cf[2];
+                } else {
+                    const float ax = cf[0] * x[j];
+                    const float bp = cf[1] * p[j];
+                    xm[j] = ax + bp;
+                }
+                const float cz = (a.mode == 0) ? cf[3] : cf[2];
+                const float nz_ = cz * z[j];
+                xn[j] = xm[j] + nz_;
+            }
+        }
+        *reinterpret_cast<f32x4*>(a.x_out + 4 * i) = xn;
+        if (a.traj) *reinterpret_cast<f32x4*>(a.traj + (long)step * a.n + 4 * i) = xn;
+        if (a.x_mean_out) *reinterpret_cast<f32x4*>(a.x_mean_out + 4 * i) = xm;
+    }
+}
+
+__global__ void advance_step_kernel(int* step_ptr) { if (threadIdx.x == 0 && blockIdx.x == 0) *step_ptr += 1; }
+
+int ldt_sampler_step_launch(const StepArgs* a, hipStream_t s) {
+    LDT_REQUIRE(a->n > 0 && a->n % 4 == 0 && a->elem_offset % 4 == 0, LDT_ESHAPE, "sampler_step: n and elem_offset must be multiples of 4 (n=%ld)", a->n);
+    LDT_REQUIRE(a->x && a->params && a->x_out && a->coef, LDT_EARG, "sampler_step: null pointer");
+    LDT_REQUIRE(ldt_aligned16(a->x) && ldt_aligned16(a->params) && ldt_aligned16(a->x_out) && ldt_aligned16(a->coef) &&
+                (!a->noise || ldt_aligned16(a->noise)) && (!a->x_mean_out || ldt_aligned16(a->x_mean_out)) && a->noise_step_stride % 4 == 0,
+                LDT_EALIGN, "sampler_step: buffers must be 16-byte aligned");
+    LDT_REQUIRE(a->mode == 0 || a->mode == 1, LDT_EARG, "sampler_step: mode %d", a->mode);
+    hipLaunchKernelGGL(sampler_step_kernel, dim3(ldt_grid_1d(a->n / 4, 256, 2048)), dim3(256), 0, s, *a);
+    return ldt_check_launch("sampler_step");
+}
+int ldt_advance_step_launch(int* step_ptr, hipStream_t s) {
+    hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(64), 0, s, step_ptr);
+    return ldt_check_launch("advance_step");
+}
+extern "C" int ldt_sampler_step(const float* x, const float* params, const float* noise, int64_t noise_step_stride,
+                                float* x_out, float* x_mean_out, const float* coef, const int32_t* step_ptr,
+                                int32_t step_host, int32_t mode, int64_t n, int64_t elem_offset, uint64_t seed,
+                                int32_t philox_mul, int32_t philox_add, void* stream) {
+    StepArgs a{x, params, noise, x_out, x_mean_out, coef, step_ptr, step_host, mode, n, elem_offset, noise_step_stride,
+               (uint32_t)seed, (uint32_t)(seed >> 32), philox_mul, philox_add};
+    return ldt_sampler_step_launch(&a, ldt_stream(stream));
+}
+extern "C" int ldt_sampler_step_traj(const float* x, const float* params, const float* noise, int64_t noise_step_stride,
+                                     float* x_out, float* x_mean_out, float* traj, const float* coef, const int32_t* step_ptr,
+                                     int32_t step_host, int32_t mode, int64_t n, int64_t elem_offset, uint64_t seed,
+                                     int32_t philox_mul, int32_t philox_add, void* stream) {
+    LDT_REQUIRE(!traj || ldt_aligned16(traj), LDT_EALIGN, "sampler_step_traj: traj must be 16-byte aligned");
+    StepArgs a{x, params, noise, x_out, x_mean_out, coef, step_ptr, step_host, mode, n, elem_offset, noise_step_stride,
+               (uint32_t)seed, (uint32_t)(seed >> 32), philox_mul, philox_add, traj};
+    return ldt_sampler_step_launch(&a, ldt_stream(stream));
+}
+
+// standalone Philox normal fill (same stream as the fused step; used by tests and Compressor.sample(given_eps=None))
+__global__ void philox_normal_kernel(float* out, long n, long elem_offset, int step, uint32_t k0, uint32_t k1) {
+    const long nvec = n / 4;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
+        const uint64_t e = (uint64_t)(elem_offset / 4 + i);
+        uint32_t c[4] = {(uint32_t)e, (uint32_t)(e >> 32), (uint32_t)step, 0x4C445421u};
+        philox4x32_10(c, k0, k1);
+        float z0, z1, z2, z3;
+        box_muller(c[0], c[1], z0, z1);
+        box_muller(c[2], c[3], z2, z3);
+        *reinterpret_cast<f32x4*>(out + 4 * i) = (f32x4){z0, z1, z2, z3};
+    }
+}
+extern "C" int ldt_philox_normal(float* out, int64_t n, int64_t elem_offset, int32_t step, uint64_t seed, void* stream) {
+    LDT_REQUIRE(out, LDT_EARG, "philox_normal: null pointer");
+    LDT_REQUIRE(n > 0 && n % 4 == 0 && elem_offset % 4 == 0 && ldt_aligned16(out), LDT_ESHAPE, "philox_normal: n/offset %% 4, 16-byte aligned");
+    hipLaunchKernelGGL(philox_normal_kernel, dim3(ldt_grid_1d(n / 4, 256, 2048)), dim3(256), 0, ldt_stream(stream), out, (long)n, (long)elem_offset,
+                       (int)step, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return ldt_check_launch("philox_normal");
+}
 
 // ------------------------------------------------------------------------------------------------
 // per-sample L2 norms (torch.norm(v.reshape(B, -1), dim=-1), :204-205): one 256-thread workgroup per sample,
@@ -32,7 +149,7 @@ extern "C" int ldt_batch_norm_sum(const float* x, int32_t B, int64_t per_sample,
     LDT_REQUIRE(x && norms_scratch && sum_out, LDT_EARG, "batch_norm_sum: null pointer");
     LDT_REQUIRE(B > 0 && per_sample > 0 && per_sample % 4 == 0 && ldt_aligned16(x), LDT_ESHAPE,
                 "batch_norm_sum: per_sample=%ld must be a multiple of 4, x 16-byte aligned", (long)per_sample);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = ldt_stream(stream);
     hipLaunchKernelGGL(batch_norms_kernel, dim3((unsigned)B), dim3(256), 0, s, x, (long)per_sample, norms_scratch);
     hipLaunchKernelGGL(norm_sum_kernel, dim3(1), dim3(64), 0, s, norms_scratch, B, sum_out);
     return ldt_check_launch("batch_norm_sum");
@@ -53,7 +170,7 @@ __global__ void langevin_coef_kernel(const float* __restrict__ sums, int n_total
 }
 extern "C" int ldt_langevin_coef(const float* sums, int32_t n_total, float snr, float std_t, float* coef_out, void* stream) {
     LDT_REQUIRE(sums && coef_out && n_total > 0 && std_t > 0.f, LDT_EARG, "langevin_coef: bad argument");
-    hipLaunchKernelGGL(langevin_coef_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), sums, n_total, snr, std_t, coef_out);
+    hipLaunchKernelGGL(langevin_coef_kernel, dim3(1), dim3(64), 0, ldt_stream(stream), sums, n_total, snr, std_t, coef_out);
     return ldt_check_launch("langevin_coef");
 }
 
@@ -83,9 +200,7 @@ extern "C" int ldt_pndm_transfer(const float* x, const float* et, float d, float
     LDT_REQUIRE(x && et && out, LDT_EARG, "pndm_transfer: null pointer");
     LDT_REQUIRE(n > 0 && n % 4 == 0 && ldt_aligned16(x) && ldt_aligned16(et) && ldt_aligned16(out), LDT_EALIGN,
                 "pndm_transfer: n %% 4 and 16-byte aligned buffers");
-    long blocks = (n / 4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(pndm_transfer_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, et, d, p, q, out, n / 4);
+    hipLaunchKernelGGL(pndm_transfer_kernel, dim3(ldt_grid_1d(n / 4, 256, 2048)), dim3(256), 0, ldt_stream(stream), x, et, d, p, q, out, n / 4);
     return ldt_check_launch("pndm_transfer");
 }
 
@@ -119,9 +234,7 @@ extern "C" int ldt_lincomb4(const float* a0, const float* a1, const float* a2, c
     LDT_REQUIRE(n > 0 && n % 4 == 0 && ldt_aligned16(a0) && ldt_aligned16(a1) && ldt_aligned16(a2) && ldt_aligned16(a3) && ldt_aligned16(out),
                 LDT_EALIGN, "lincomb4: n %% 4 and 16-byte aligned buffers");
     Lin4Args g{{a0, a1, a2, a3}, {c0, c1, c2, c3}, s, out, n / 4};
-    long blocks = (n / 4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(lincomb4_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g);
+    hipLaunchKernelGGL(lincomb4_kernel, dim3(ldt_grid_1d(n / 4, 256, 2048)), dim3(256), 0, ldt_stream(stream), g);
     return ldt_check_launch("lincomb4");
 }
 
@@ -155,9 +268,7 @@ extern "C" int ldt_vpsde_score(const float* params, const float* t, float beta0,
     LDT_REQUIRE(params && t && out, LDT_EARG, "vpsde_score: null pointer");
     LDT_REQUIRE(B > 0 && B <= 65535 && per_sample > 0 && per_sample % 4 == 0 && ldt_aligned16(params) && ldt_aligned16(out), LDT_ESHAPE,
                 "vpsde_score: B=%d in [1, 65535], per_sample=%ld a multiple of 4, 16-byte aligned buffers", B, (long)per_sample);
-    long bx = (per_sample / 4 + 255) / 256;
-    if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(vpsde_score_kernel, dim3((unsigned)bx, (unsigned)B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), params, t,
+    hipLaunchKernelGGL(vpsde_score_kernel, dim3(ldt_grid_1d(per_sample / 4, 256, 64), (unsigned)B), dim3(256), 0, ldt_stream(stream), params, t,
                        beta0, beta1, sigma2_0, out, (long)(per_sample / 4));
     return ldt_check_launch("vpsde_score");
 }
@@ -204,191 +315,7 @@ extern "C" int ldt_sde_score(const float* params, const float* t, int32_t kind, 
     LDT_REQUIRE(kind >= 0 && kind <= 2, LDT_EARG, "sde_score: kind=%d (0 vpsde, 1 sub_vpsde, 2 vesde / geometric_sde)", kind);
     LDT_REQUIRE(B > 0 && B <= 65535 && per_sample > 0 && per_sample % 4 == 0 && ldt_aligned16(params) && ldt_aligned16(out), LDT_ESHAPE,
                 "sde_score: B=%d in [1, 65535], per_sample=%ld a multiple of 4, 16-byte aligned buffers", B, (long)per_sample);
-    long bx = (per_sample / 4 + 255) / 256;
-    if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(sde_score_kernel, dim3((unsigned)bx, (unsigned)B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), params, t,
+    hipLaunchKernelGGL(sde_score_kernel, dim3(ldt_grid_1d(per_sample / 4, 256, 64), (unsigned)B), dim3(256), 0, ldt_stream(stream), params, t,
                        (int)kind, c0, c1, c2, out, (long)(per_sample / 4));
     return ldt_check_launch("sde_score");
-}
-
-// x = act(x) in place on bf16 rows [M][C] (row stride ld): the block activation of the reference's no-condition ResidualBlock branches
-// (`decoder_act`, model/layers.py:224-226 via tools/utils.py:104-124), applied to the LayerNorm output the projections read.  kind = enum
-// ldt_block_act; the arithmetic runs in fp32.  rrelu is its eval-mode form (slope (1/8 + 1/3) / 2).
-__device__ __forceinline__ float block_act(float v, int kind) {
-    switch (kind) {
-        case LDT_BACT_GELU: return gelu_erf(v);
-        case LDT_BACT_SILU: return silu(v);
-        case LDT_BACT_RELU: return (v > 0.f || v != v) ? v : 0.f;      // (fmaxf would turn a NaN into 0: torch.relu keeps it)
-        case LDT_BACT_LEAKY_001: return v > 0.f ? v : 0.01f * v;
-        case LDT_BACT_LEAKY_02: return v > 0.f ? v : 0.2f * v;
-        case LDT_BACT_RRELU_EVAL: return v > 0.f ? v : v * ((1.0f / 8.0f + 1.0f / 3.0f) * 0.5f);
-        case LDT_BACT_HARDSWISH: return v * fminf(fmaxf(v + 3.0f, 0.f), 6.0f) * (1.0f / 6.0f);
-        case LDT_BACT_SELU: return 1.0507009873554804934193349852946f * (v > 0.f ? v : 1.6732632423543772848170429916717f * (expf(v) - 1.0f));
-        default: return v;
-    }
-}
-__global__ __launch_bounds__(256) void block_act_kernel(bf16_t* __restrict__ x, long ld, long M, int C, int kind) {
-    const long n = M * C;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        bf16_t* p = x + (i / C) * ld + (i % C);
-        *p = (bf16_t)block_act((float)*p, kind);
-    }
-}
-extern "C" int ldt_block_activation(uint16_t* x, int64_t ld, int64_t M, int32_t C, int32_t kind, void* stream) {
-    LDT_REQUIRE(x && M > 0 && C > 0 && ld >= C, LDT_EARG, "block_activation: bad argument");
-    LDT_REQUIRE(kind > LDT_BACT_NONE && kind <= LDT_BACT_SELU, LDT_EARG, "block_activation: unknown activation %d", kind);
-    long blocks = (M * C + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(block_act_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       reinterpret_cast<bf16_t*>(x), (long)ld, (long)M, (int)C, (int)kind);
-    return ldt_check_launch("block_activation");
-}
-
-// out = a + b (fp32; c = t_emb + label / image-condition embedding, model/scorenet/score.py:135).  out may alias a or b.
-__global__ __launch_bounds__(256) void add_f32_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, long n) {
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[i] = a[i] + b[i];
-}
-extern "C" int ldt_add_f32(const float* a, const float* b, float* out, int64_t n, void* stream) {
-    LDT_REQUIRE(a && b && out && n > 0, LDT_EARG, "add_f32: bad argument");
-    long blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(add_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, b, out, (long)n);
-    return ldt_check_launch("add_f32");
-}
-
-// bf16 -> fp32 widening of a packed weight panel (exact), for the fp32 table builds that must see the SAME rounded weights
-// the MFMAs multiply by (Score.fold_table).
-__global__ __launch_bounds__(256) void widen_bf16_kernel(const bf16_t* __restrict__ src, float* __restrict__ dst, long n) {
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = (float)src[i];
-}
-extern "C" int ldt_widen_bf16(const uint16_t* src, float* dst, int64_t n, void* stream) {
-    LDT_REQUIRE(src && dst && n > 0, LDT_EARG, "widen_bf16: bad argument");
-    long blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(widen_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       reinterpret_cast<const bf16_t*>(src), dst, (long)n);
-    return ldt_check_launch("widen_bf16");
-}
-
-// ------------------------------------------------------------------------------------------------
-// LN-folding monitor: max over rows of mean^2 / variance from the producer's row statistics stats[parts][M][2] (partial
-// (sum, sum of squares) per 256-column tile).  The folded projections round x (1 + scale) to bf16 BEFORE the mean is removed,
-// so their error variance is (1 + mean^2 / variance) x the LayerNorm kernel's; the sampler reads this once per
-// sample() call and falls back to the LayerNorm kernels when the ratio says the 1e-4 parity bar is at risk.
-// One workgroup of 256 threads, fixed order: deterministic.  *out = the maximum ratio (0 when M == 0).
-__global__ __launch_bounds__(256) void fold_mean_ratio_kernel(const float* __restrict__ stats, int parts, long M, int K, float* __restrict__ out) {
-    float best = 0.f;
-    const float invk = 1.0f / (float)K;
-    for (long r = threadIdx.x; r < M; r += 256) {
-        float s1 = 0.f, s2 = 0.f;
-        for (int p = 0; p < parts; ++p) { s1 += stats[((long)p * M + r) * 2]; s2 += stats[((long)p * M + r) * 2 + 1]; }
-        const float mean = s1 * invk;
-        const float var = fmaxf(s2 * invk - mean * mean, 0.f) + 1e-6f;
-        best = fmaxf(best, mean * mean / var);
-    }
-    best = wave_max(best);
-    __shared__ float part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) *out = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
-}
-// the same, accumulated into *out by atomic max (ratios are non-negative: their bit patterns order like ints); the Score
-// forward calls it after every folded residual GEMM when plan->fold_monitor is set
-__global__ __launch_bounds__(256) void fold_monitor_kernel(const float* __restrict__ stats, int parts, long M, int K, float* __restrict__ out) {
-    float best = 0.f;
-    const float invk = 1.0f / (float)K;
-    for (long r = blockIdx.x * 256L + threadIdx.x; r < M; r += (long)gridDim.x * 256) {
-        float s1 = 0.f, s2 = 0.f;
-        for (int p = 0; p < parts; ++p) { s1 += stats[((long)p * M + r) * 2]; s2 += stats[((long)p * M + r) * 2 + 1]; }
-        const float mean = s1 * invk;
-        const float var = fmaxf(s2 * invk - mean * mean, 0.f) + 1e-6f;
-        best = fmaxf(best, mean * mean / var);
-    }
-    best = wave_max(best);
-    if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<int*>(out), __float_as_int(best));
-}
-int ldt_fold_monitor_launch(const float* stats, int parts, long M, int K, float* out, hipStream_t s) {
-    long blocks = (M + 255) / 256;
-    if (blocks > 64) blocks = 64;
-    hipLaunchKernelGGL(fold_monitor_kernel, dim3((unsigned)blocks), dim3(256), 0, s, stats, parts, M, K, out);
-    return ldt_check_launch("fold_monitor");
-}
-
-extern "C" int ldt_fold_mean_ratio(const float* stats, int32_t parts, int64_t M, int32_t K, float* out, void* stream) {
-    LDT_REQUIRE(stats && out && parts >= 1 && M > 0 && K > 0, LDT_EARG, "fold_mean_ratio: bad argument");
-    hipLaunchKernelGGL(fold_mean_ratio_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), stats, parts, (long)M, K, out);
-    return ldt_check_launch("fold_mean_ratio");
-}
-
-
-// ------------------------------------------------------------------------------------------------- group norm / identity norm
-// tools/utils.py:168-181 get_norm: `group_norm` -> nn.GroupNorm(min(C/4, 16), C, eps=1e-6) on the channels-first activations (statistics per
-// sample and group over C/G channels x all tokens), `None` -> Identity.  Rows are token-major here: x[b*T + t][c].
-__global__ void group_stats_kernel(const float* __restrict__ x, long ldx, int T, int C, int G, float eps, float* __restrict__ stats) {
-    const int b = blockIdx.x / G, g = blockIdx.x % G, cg = C / G;
-    const float* xb = x + (long)b * T * ldx + g * cg;
-    double s1 = 0.0, s2 = 0.0;
-    for (int i = threadIdx.x; i < T * cg; i += blockDim.x) {
-        const float v = xb[(long)(i / cg) * ldx + i % cg];
-        s1 += v; s2 += (double)v * v;
-    }
-    __shared__ double r1[256], r2[256];
-    r1[threadIdx.x] = s1; r2[threadIdx.x] = s2;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { r1[threadIdx.x] += r1[threadIdx.x + o]; r2[threadIdx.x] += r2[threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const double n = (double)T * cg, mean = r1[0] / n;
-        double var = r2[0] / n - mean * mean;
-        var = var > 0.0 ? var : 0.0;
-        stats[(long)blockIdx.x * 2] = (float)mean;
-        stats[(long)blockIdx.x * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
-    }
-}
-extern "C" int ldt_group_stats(const float* x, int64_t ldx, int32_t B, int32_t T, int32_t C, int32_t G, float eps, float* stats, void* stream) {
-    LDT_REQUIRE(x && stats && B > 0 && T > 0 && C > 0 && G > 0 && C % G == 0 && ldx >= C, LDT_EARG, "group_stats: bad argument (B=%d T=%d C=%d G=%d)", B, T, C, G);
-    hipLaunchKernelGGL(group_stats_kernel, dim3((unsigned)(B * G)), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, T, C, G, eps, stats);
-    return ldt_check_launch("group_stats");
-}
-
-__global__ void norm_apply_kernel(const float* __restrict__ x, long ldx, bf16_t* __restrict__ y, long ldy, long M, int C, const float* __restrict__ stats,
-                                  int G, int rows_per_stat, const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ shift,
-                                  const float* __restrict__ scale, long mod_sample_stride, int rows_per_sample) {
-    const long n4 = M * (C / 4);
-    const int cg = C / (G > 0 ? G : 1);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        const long m = i / (C / 4);
-        const int c = (int)(i % (C / 4)) * 4;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + m * ldx + c);
-        const long moff = (m / rows_per_sample) * mod_sample_stride + c;
-        bf16x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float mean = 0.f, rstd = 1.f;
-            if (stats) {
-                const float* st = stats + ((m / rows_per_stat) * G + (c + j) / cg) * 2;
-                mean = st[0]; rstd = st[1];
-            }
-            float h = (v[j] - mean) * rstd;
-            if (w) h = h * w[c + j] + b[c + j];
-            if (scale) h = h * (1.0f + scale[moff + j]) + shift[moff + j];
-            o[j] = (bf16_t)h;
-        }
-        *reinterpret_cast<bf16x4*>(y + m * ldy + c) = o;
-    }
-}
-extern "C" int ldt_norm_apply(const float* x, int64_t ldx, uint16_t* y, int64_t ldy, int64_t M, int32_t C, const float* stats, int32_t G,
-                              int32_t rows_per_stat, const float* w, const float* b, const float* shift, const float* scale,
-                              int64_t mod_sample_stride, int32_t rows_per_sample, void* stream) {
-    LDT_REQUIRE(x && y && M > 0 && C > 0 && C % 4 == 0 && ldx >= C && ldy >= C && ldx % 4 == 0 && ldy % 4 == 0, LDT_EARG, "norm_apply: bad argument (M=%ld C=%d)", (long)M, C);
-    LDT_REQUIRE(ldt_aligned16(x) && (reinterpret_cast<uintptr_t>(y) & 7u) == 0, LDT_EALIGN, "norm_apply: x must be 16-byte, y 8-byte aligned");
-    LDT_REQUIRE(!stats || (G > 0 && C % G == 0 && rows_per_stat > 0), LDT_EARG, "norm_apply: statistics need G | C and rows_per_stat > 0");
-    LDT_REQUIRE(!w == !b && !shift == !scale && rows_per_sample > 0, LDT_EARG, "norm_apply: w / b and shift / scale go in pairs; rows_per_sample > 0");
-    long blocks = (M * (C / 4) + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(norm_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, reinterpret_cast<bf16_t*>(y), (long)ldy,
-                       (long)M, C, stats, stats ? G : 1, stats ? rows_per_stat : 1, w, b, shift, scale, (long)mod_sample_stride, rows_per_sample);
-    return ldt_check_launch("norm_apply");
 }

@@ -56,7 +56,7 @@ extern "C" int ldt_transpose_cast_bf16(const void* src, int32_t src_bf16, int64_
     LDT_REQUIRE(R > 0 && C > 0 && R_pad >= R && ld_src >= C && ld_dst >= R_pad && (R_pad + 31) / 32 <= 0x7fffffffL && (C + 31) / 32 <= 65535,
                 LDT_ESHAPE, "transpose_cast: R %ld, C %d, R_pad %ld, ld_src %ld, ld_dst %ld", (long)R, C, (long)R_pad, (long)ld_src, (long)ld_dst);
     hipLaunchKernelGGL(transpose_cast_kernel, dim3((unsigned)((R_pad + 31) / 32), (unsigned)((C + 31) / 32)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), src, src_bf16, (long)ld_src, reinterpret_cast<bf16_t*>(dst), (long)ld_dst, (long)R, C,
+                       ldt_stream(stream), src, src_bf16, (long)ld_src, reinterpret_cast<bf16_t*>(dst), (long)ld_dst, (long)R, C,
                        (long)R_pad);
     return ldt_check_launch("transpose_cast");
 }
@@ -77,7 +77,7 @@ extern "C" int ldt_colsum(const void* dy, int32_t dy_bf16, int64_t ld, int64_t M
     LDT_REQUIRE(dy && out, LDT_EARG, "colsum: null pointer");
     LDT_REQUIRE(M > 0 && C > 0 && ld >= C, LDT_ESHAPE, "colsum: M %ld, C %d, ld %ld", (long)M, C, (long)ld);
     hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((C + RED_COLS - 1) / RED_COLS)), dim3(RED_COLS, RED_SLICES), 0,
-                       reinterpret_cast<hipStream_t>(stream), dy, dy_bf16, (long)ld, (long)M, C, out);
+                       ldt_stream(stream), dy, dy_bf16, (long)ld, (long)M, C, out);
     return ldt_check_launch("colsum");
 }
 
@@ -147,7 +147,7 @@ extern "C" int ldt_layernorm_modulate_bwd(const float* x, int64_t ldx, const flo
     LDT_REQUIRE((dshift == nullptr) == (dscale == nullptr), LDT_EARG, "layernorm_modulate_bwd: dshift and dscale go together");
     LDT_REQUIRE(M > 0 && C > 0 && rows_per_sample > 0 && M % rows_per_sample == 0 && M / rows_per_sample <= 65535 && ldx >= C && lddy >= C && lddx >= C &&
                 (!dshift || dmod_sample_stride >= C), LDT_ESHAPE, "layernorm_modulate_bwd: M %ld, C %d, rows_per_sample %d", (long)M, C, rows_per_sample);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = ldt_stream(stream);
     hipLaunchKernelGGL(ln_mod_bwd_rows_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, x, (long)ldx, dy, (long)lddy, scale,
                        (long)mod_sample_stride, rows_per_sample, dx, (long)lddx, stats, (long)M, C);
     int rc = ldt_check_launch("layernorm_modulate_bwd (rows)");
@@ -177,9 +177,7 @@ extern "C" int ldt_gelu_bwd(const uint16_t* u, int64_t ldu, const void* dh, int3
                             int32_t C, void* stream) {
     LDT_REQUIRE(u && dh && du, LDT_EARG, "gelu_bwd: null pointer");
     LDT_REQUIRE(M > 0 && C > 0 && ldu >= C && lddh >= C && lddu >= C, LDT_ESHAPE, "gelu_bwd: M %ld, C %d", (long)M, C);
-    long blocks = (M * (long)C + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(gelu_bwd_kernel, dim3(ldt_grid_1d(M * (long)C, 256, 4096)), dim3(256), 0, ldt_stream(stream),
                        reinterpret_cast<const bf16_t*>(u), (long)ldu, dh, dh_bf16, (long)lddh, reinterpret_cast<bf16_t*>(du), (long)lddu, (long)M, C);
     return ldt_check_launch("gelu_bwd");
 }
@@ -215,7 +213,7 @@ extern "C" int ldt_gate_residual_bwd(const float* dy, int64_t lddy, const void* 
                 (!dgate || (lda >= C && dgate_sample_stride >= C)), LDT_ESHAPE, "gate_residual_bwd: M %ld, C %d, rows_per_sample %d", (long)M, C,
                 rows_per_sample);
     hipLaunchKernelGGL(gate_bwd_kernel, dim3((unsigned)((C + RED_COLS - 1) / RED_COLS), (unsigned)(M / rows_per_sample)), dim3(RED_COLS, RED_SLICES), 0,
-                       reinterpret_cast<hipStream_t>(stream), dy, (long)lddy, a, a_bf16, (long)lda, gate, (long)gate_sample_stride, rows_per_sample, C,
+                       ldt_stream(stream), dy, (long)lddy, a, a_bf16, (long)lda, gate, (long)gate_sample_stride, rows_per_sample, C,
                        reinterpret_cast<bf16_t*>(da), (long)ldda, dgate, (long)dgate_sample_stride);
     return ldt_check_launch("gate_residual_bwd");
 }
@@ -236,9 +234,7 @@ __global__ __launch_bounds__(256) void silu_bwd_kernel(const float* __restrict__
 extern "C" int ldt_silu_bwd(const float* c, const float* dy, float* dc, float* act, int64_t n, void* stream) {
     LDT_REQUIRE(c && (dc || act) && (dy || !dc), LDT_EARG, "silu_bwd: null pointer (dc needs dy; one of dc, act is required)");
     LDT_REQUIRE(n > 0, LDT_ESHAPE, "silu_bwd: n %ld", (long)n);
-    long blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(silu_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), c, dy, dc, act, (long)n);
+    hipLaunchKernelGGL(silu_bwd_kernel, dim3(ldt_grid_1d(n, 256, 2048)), dim3(256), 0, ldt_stream(stream), c, dy, dc, act, (long)n);
     return ldt_check_launch("silu_bwd");
 }
 
@@ -261,9 +257,7 @@ extern "C" int ldt_dsm_loss_bwd(const float* eta, const float* params, const flo
     LDT_REQUIRE(eta && params && dparams, LDT_EARG, "dsm_loss_bwd: null pointer");
     LDT_REQUIRE(B > 0 && per_sample > 0, LDT_ESHAPE, "dsm_loss_bwd: B %ld, per_sample %ld", (long)B, (long)per_sample);
     const long n = B * per_sample;
-    long blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(dsm_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), eta, params, weight, (long)per_sample,
+    hipLaunchKernelGGL(dsm_bwd_kernel, dim3(ldt_grid_1d(n, 256, 2048)), dim3(256), 0, ldt_stream(stream), eta, params, weight, (long)per_sample,
                        n, l1, dparams);
     return ldt_check_launch("dsm_loss_bwd");
 }
@@ -285,7 +279,7 @@ __global__ __launch_bounds__(256) void embedding_grad_kernel(const float* __rest
 extern "C" int ldt_embedding_grad(const float* dc, int64_t ld, const int32_t* label, int32_t B, int32_t D, int32_t n_classes, float* dE, void* stream) {
     LDT_REQUIRE(dc && label && dE, LDT_EARG, "embedding_grad: null pointer");
     LDT_REQUIRE(B > 0 && D > 0 && n_classes > 0 && n_classes <= 65535 && ld >= D, LDT_ESHAPE, "embedding_grad: B %d, D %d, classes %d", B, D, n_classes);
-    hipLaunchKernelGGL(embedding_grad_kernel, dim3((unsigned)((D + 255) / 256), (unsigned)n_classes), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(embedding_grad_kernel, dim3((unsigned)((D + 255) / 256), (unsigned)n_classes), dim3(256), 0, ldt_stream(stream),
                        dc, (long)ld, label, B, D, dE);
     return ldt_check_launch("embedding_grad");
 }
@@ -311,7 +305,7 @@ extern "C" int ldt_rows_gather_sum(const float* dy, int64_t ld, const int32_t* s
     LDT_REQUIRE(dy && src && dprior, LDT_EARG, "rows_gather_sum: null pointer");
     LDT_REQUIRE(B > 0 && N > 0 && R > 0 && R <= 65535 && C > 0 && ld >= C, LDT_ESHAPE, "rows_gather_sum: B %d, N %d, R %d (1 .. 65535), C %d, ld %ld",
                 B, N, R, C, (long)ld);
-    hipLaunchKernelGGL(rows_gather_sum_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)R), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(rows_gather_sum_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)R), dim3(256), 0, ldt_stream(stream),
                        dy, (long)ld, src, B, N, R, C, dprior);
     return ldt_check_launch("rows_gather_sum");
 }

@@ -19,15 +19,6 @@
 
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ float sg_act(float v, int act) {
-    switch (act) {
-        case ACT_SILU: return v / (1.0f + expf(-v));
-        case ACT_RELU: return fmaxf(v, 0.f);
-        case ACT_GELU: return gelu_erf(v);
-        default: return v;
-    }
-}
-
 template <int TM, int TN, int WGM, int WGN, int SG_BK = 16>    // WG tile, wave grid (WGM x WGN = 4 waves), k-slab depth
 __global__ __launch_bounds__(256) void sgemm_mfma_kernel(const SgemmArgs a) {
     constexpr int SG_LD = SG_BK + 4, CPR = SG_BK / 4;                  // floats per staged row, 16-B chunks per slab row
@@ -73,7 +64,7 @@ __global__ __launch_bounds__(256) void sgemm_mfma_kernel(const SgemmArgs a) {
             f32x4 v = ra[c];
             if (a.act_in) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = sg_act(v[j], a.act_in);
+                for (int j = 0; j < 4; ++j) v[j] = ldt_act(v[j], a.act_in);
             }
             if (ch < TM * CPR) *reinterpret_cast<f32x4*>(&As[row * SG_LD + kc]) = v;
         }
@@ -120,9 +111,7 @@ __global__ __launch_bounds__(256) void sgemm_mfma_kernel(const SgemmArgs a) {
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * WM + bi * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
                 if (m >= a.M) continue;
-                const float v = sg_act(acc[bi][bj][r] + bv, a.act_out);
-                if (a.out_bf16) reinterpret_cast<bf16_t*>(a.C)[(long)m * a.ldc + n] = (bf16_t)v;
-                else reinterpret_cast<float*>(a.C)[(long)m * a.ldc + n] = v;
+                SGEMM_STORE(a, (long)m * a.ldc + n, ldt_act(acc[bi][bj][r] + bv, a.act_out));
             }
         }
 }

@@ -3,7 +3,7 @@
 //     out[M][N] = act_out( act_in(A[M][K]) . W[N][K]^T + bias )
 // A 128-wide MFMA tile spends 98 % of its work on zero padding there (N = 3) or cannot be used at all (K = 3), and the generic kernels
 // ran at 0.04 – 0.3 of the HBM rate.  Two forms, both fp32 FMA chains (the fp32 parity bars of ldt_sgemm hold), both bandwidth-bound:
-// (which problems take which form: ldt_sgemm_decide in elementwise.hip, stated at ldt_sgemm_route in include/ldt_hip.h)
+// (which problems take which form: ldt_sgemm_decide in sgemm.hip, stated at ldt_sgemm_route in include/ldt_hip.h)
 //   * small K (<= 8), N / 4 in 8..256 dividing 256 (N = 32 ... 1024): a thread owns 4 consecutive outputs of a row with its K x 4 weights in
 //     registers for the whole (grid-strided) launch; the row's K inputs are broadcast loads; 16-B (fp32) or 8-B (bf16) stores, whole rows
 //     per 32 lanes;
@@ -11,15 +11,6 @@
 #include "kernels.h"
 
 namespace {
-
-__device__ __forceinline__ float sk_act(float v, int act) {
-    switch (act) {
-        case ACT_SILU: return v / (1.0f + expf(-v));
-        case ACT_RELU: return fmaxf(v, 0.f);
-        case ACT_GELU: return gelu_erf(v);
-        default: return v;
-    }
-}
 
 template <int KP>   // K padded to KP (weights of the padding are zero, its inputs are not loaded)
 __global__ __launch_bounds__(256) void linear_smallk_kernel(const SgemmArgs a) {
@@ -50,13 +41,13 @@ __global__ __launch_bounds__(256) void linear_smallk_kernel(const SgemmArgs a) {
             f32x4 o = b4;
 #pragma unroll
             for (int k = 0; k < KP; ++k) {
-                const float xv = a.act_in ? sk_act(x[r][k], a.act_in) : x[r][k];
+                const float xv = a.act_in ? ldt_act(x[r][k], a.act_in) : x[r][k];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) o[j] = fmaf(xv, w[k][j], o[j]);
             }
             if (a.act_out) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = sk_act(o[j], a.act_out);
+                for (int j = 0; j < 4; ++j) o[j] = ldt_act(o[j], a.act_out);
             }
             if (a.out_bf16) {
                 const bf16x4 p = {(bf16_t)o[0], (bf16_t)o[1], (bf16_t)o[2], (bf16_t)o[3]};
@@ -90,7 +81,7 @@ __global__ __launch_bounds__(256) void linear_smalln_kernel(const SgemmArgs a) {
 #pragma unroll
                 for (int r = 0; r < R; ++r)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) x[r][j] = sk_act(x[r][j], a.act_in);
+                    for (int j = 0; j < 4; ++j) x[r][j] = ldt_act(x[r][j], a.act_in);
             }
 #pragma unroll
             for (int n = 0; n < NP; ++n) {
@@ -117,11 +108,7 @@ __global__ __launch_bounds__(256) void linear_smalln_kernel(const SgemmArgs a) {
             for (int rr = 0; rr < R; ++rr)
 #pragma unroll
                 for (int nn = 0; nn < NP; ++nn) v = (rr == r && nn == n) ? acc[rr][nn] : v;
-            if (r < R && n < a.N && row0 + r < a.M) {
-                v = sk_act(v + (a.bias ? a.bias[n] : 0.f), a.act_out);
-                if (a.out_bf16) reinterpret_cast<bf16_t*>(a.C)[(row0 + r) * a.ldc + n] = (bf16_t)v;
-                else reinterpret_cast<float*>(a.C)[(row0 + r) * a.ldc + n] = v;
-            }
+            if (r < R && n < a.N && row0 + r < a.M) SGEMM_STORE(a, (row0 + r) * a.ldc + n, ldt_act(v + (a.bias ? a.bias[n] : 0.f), a.act_out));
         }
     }
 }
@@ -135,17 +122,14 @@ int ldt_skinny_linear_launch(const SgemmArgs* a, int route, hipStream_t s) {
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (route == SGEMM_ROUTE_SMALLN_4 || route == SGEMM_ROUTE_SMALLN_8) {
-        long blocks = ((long)a->M + 31) / 32;
-        if (blocks > (long)cus * 16) blocks = (long)cus * 16;
-        if (route == SGEMM_ROUTE_SMALLN_4) hipLaunchKernelGGL(linear_smalln_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, *a);
-        else hipLaunchKernelGGL(linear_smalln_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, s, *a);
+        const dim3 g(ldt_grid_1d(a->M, 32, (long)cus * 16)), b(256);
+        if (route == SGEMM_ROUTE_SMALLN_4) hipLaunchKernelGGL(linear_smalln_kernel<4>, g, b, 0, s, *a);
+        else hipLaunchKernelGGL(linear_smalln_kernel<8>, g, b, 0, s, *a);
         return ldt_check_launch("linear_smalln");
     }
     LDT_REQUIRE(route == SGEMM_ROUTE_SMALLK_4 || route == SGEMM_ROUTE_SMALLK_8, LDT_EARG, "skinny_linear: route %d is not a streaming form", route);
     const int rpb = 256 / (a->N / 4);
-    long blocks = ((long)a->M + rpb * 4 - 1) / (rpb * 4);
-    if (blocks > (long)cus * 8) blocks = (long)cus * 8;
-    const dim3 g((unsigned)blocks), b(256);
+    const dim3 g(ldt_grid_1d(a->M, rpb * 4, (long)cus * 8)), b(256);
     if (route == SGEMM_ROUTE_SMALLK_4) hipLaunchKernelGGL(linear_smallk_kernel<4>, g, b, 0, s, *a);
     else hipLaunchKernelGGL(linear_smallk_kernel<8>, g, b, 0, s, *a);
     return ldt_check_launch("linear_smallk");

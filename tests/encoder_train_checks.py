@@ -3,7 +3,7 @@ tools/gen_encoder_train_golden.py): the float64 reference of the ActNorm backwar
 kernel's arithmetic with the faults the host test plants, and the float64 restatement of the encoder from the oracle's pieces with its
 bf16 twin.  None of a bound is taken from what a kernel returned.
 
-ActNorm backward (csrc/actnorm_bwd.hip, ldt_actnorm_bwd), counted from the kernel's operation order:
+ActNorm backward (csrc/actnorm.hip, ldt_actnorm_bwd), counted from the kernel's operation order:
   dx[b][i] = fl(dz[b][i] * expf(-log_scale[i])): the negation is exact, expf is within LIBM["expf"] ulp of its result, the product is one
     rounding; the bound allows two roundings plus the libm constant, relative to |dz exp(-log_scale)|.
   dshift[i] = -sum_b dx[b][i]: the kernel adds the fp32 values it stored, in float64, and rounds once: one final rounding of |dshift| plus
@@ -25,7 +25,7 @@ U53 = 2.0 ** -53
 # of 4 (the scalar form, with a tail behind the last full group of 16 columns); the 'set' form (per_sample = C) past one workgroup's 512 rows
 # (two stages: 2 and 10 partials, the last one partial)
 ANB_CASES = [(1, 5), (3, 8 * 64), (16, 32 * 128), (2, 4101), (700, 64), (5000, 64)]
-ANB_ROWS = 512                     # csrc/actnorm_bwd.hip: rows per workgroup; more rows take the second stage
+ANB_ROWS = 512                     # csrc/actnorm.hip: rows per workgroup; more rows take the second stage
 
 
 def actnorm_case(B, per, ls_max=1.0, seed=None, big_sample=None):

@@ -819,7 +819,7 @@ def mlp_selection_probe(M, C, rows_per_sample, seed, gated, device="cpu"):
 
 
 # ------------------------------------------------------------------------------------------------------------- stream, encoder and metric helpers
-# (csrc/elementwise.hip, samplers.hip, metrics.hip and the lower half of pointops.hip; test_gpu_stream_kernels_exact.py; validated without a
+# (csrc/elementwise.hip, samplers.hip, metrics.hip, pointops.hip, actnorm.hip, eval_loss.hip's reparam; test_gpu_stream_kernels_exact.py; validated without a
 # GPU, planted faults included, by test_kernel_checks_host.py)
 #
 # Three kinds of check.  EXACT: kernels that promise the reference's operation order (`fp contract(off)`), copies, casts and selections are
@@ -836,7 +836,7 @@ LIBM = {"expf": 1.0, "logf": 1.0, "sincosf": 1.0, "powf": 1.0, "erff": 1.0}
 SLACK = 1 + 2.0 ** -10            # second-order terms of the first-order bounds below
 
 PHILOX_M0, PHILOX_M1, PHILOX_W0, PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
-PHILOX_TAG = 0x4C445421           # the constant fourth counter word of csrc/elementwise.hip
+PHILOX_TAG = 0x4C445421           # the constant fourth counter word of csrc/samplers.hip
 
 
 def philox4x32_10_np(ctr, k0, k1, swap_key_increments=False):
@@ -948,7 +948,7 @@ def resolved_by_bf16(ref64, acc):
     return torch.isfinite(ref64) & (acc <= 0.25 * bf16_ulp(ref64))
 
 
-# ---- block activations (samplers.hip block_act): float64 definition and what the fp32 evaluation may move
+# ---- block activations (elementwise.hip block_act): float64 definition and what the fp32 evaluation may move
 BLOCK_ACT_KINDS = {"gelu": 1, "silu": 2, "relu": 3, "leakyrelu": 4, "leakyrelu0.2": 5, "rrelu": 6, "hardswish": 7, "selu": 8}
 SELU_SCALE, SELU_ALPHA = 1.0507009873554804934193349852946, 1.6732632423543772848170429916717
 RRELU_EVAL_SLOPE = float((torch.tensor(1.0 / 8.0, dtype=torch.float32) + torch.tensor(1.0 / 3.0, dtype=torch.float32)) * 0.5)

@@ -1,6 +1,6 @@
 """CPU (no GPU needed): the encoder training step's host side (ldt_amd/compressor_train.py: EncoderTrainStep, encoder_parameters,
 refuse_untrainable_encoder; CompressorTrainer.update_encoder; Compressor.front), the ActNorm backward's entry point (ldt_actnorm_bwd:
-csrc/actnorm_bwd.hip) and the helpers of tests/encoder_train_checks.py.
+csrc/actnorm.hip) and the helpers of tests/encoder_train_checks.py.
 
   * ldt_actnorm_bwd is in the header, in the binding's table and in the built library; the ABI stays 26; its argument errors come back as
     LDT_EARG with a message: no launch

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the ActNorm backward alone, per element against float64 (ldt_actnorm_bwd: csrc/actnorm_bwd.hip).  The cases, the float64
+"""GPU (-m gpu): the ActNorm backward alone, per element against float64 (ldt_actnorm_bwd: csrc/actnorm.hip).  The cases, the float64
 reference and the bounds counted from the kernel's operation order: tests/encoder_train_checks.py (dx: two roundings plus the libm
 constant of expf; the sums: one final rounding plus the summed bounds of their terms).
 

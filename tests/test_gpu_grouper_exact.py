@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the grouping kernels (csrc/pointops.hip: group_stats_vec / group_stats / group_mean / group_build) and the one-kernel grouper
+"""GPU (-m gpu): the grouping kernels (csrc/pointops.hip: group_stats_vec / group_stats / group_mean / group_build, entry ldt_group_normalize) and the one-kernel grouper
 (csrc/grouper_mlp.hip) driven alone on CRAFTED indices — no FPS or kNN in the loop — and judged per element.
 
   (1) ldt_group_normalize: the per-cloud sums against float64 at a tolerance derived from the kernels' summation; every normalised element inside

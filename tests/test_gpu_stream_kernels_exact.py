@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the small streaming kernels of csrc/elementwise.hip, samplers.hip, metrics.hip and the lower half of pointops.hip, each driven
+"""GPU (-m gpu): the small streaming kernels of csrc/elementwise.hip, samplers.hip, metrics.hip, pointops.hip, actnorm.hip and eval_loss.hip (reparam), each driven
 alone and judged per element, at sizes that make every grid-stride loop take a second (and a partial third) pass.
 
   EXACT    torch.equal with the reference's expression evaluated in fp32 by torch on the CPU (kernel_checks.*_expr): sampler_step modes 0 / 1

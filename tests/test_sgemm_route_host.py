@@ -1,4 +1,4 @@
-"""Host: the dispatch rule of the fp32 linear (ldt_sgemm_decide in ldt_amd/csrc/elementwise.hip, queried through ldt_sgemm_route) against a
+"""Host: the dispatch rule of the fp32 linear (ldt_sgemm_decide in ldt_amd/csrc/sgemm.hip, queried through ldt_sgemm_route) against a
 restatement written from the description in include/ldt_hip.h, not from the C++.  The query launches nothing and touches no device: no GPU.
 
 The rule.  A problem with M, N or K below 1 has no kernel.  "A and W rows load 16 bytes" means K, lda and ldb are multiples of 4 and neither
