@@ -1305,8 +1305,9 @@ def all_bf16_patterns():
 
 
 # ------------------------------------------------------------------------------------------------------------- Score training step
-# (csrc/score_bwd.hip, attention_bwd.hip; test_gpu_train_kernels.py holds each kernel alone with these, test_gpu_train_tape.py every call of a
-# whole backward on that call's own recorded operands; validated without a GPU, planted faults included, by test_train_tape_host.py)
+# (csrc/score_bwd.hip, attention_bwd.hip, optim.hip; test_gpu_train_kernels.py holds each kernel alone with these, test_gpu_train_tape.py every call of a
+# whole backward on that call's own recorded operands, test_gpu_train_stream_exact.py the stream kernels at width and past their grid caps;
+# validated without a GPU, planted faults included, by test_train_tape_host.py and test_train_stream_host.py)
 #
 # Every function takes the operands the kernel read and returns (float64 reference, componentwise bound), or two dicts of them for a kernel
 # with several outputs.  The bounds are built the way gemm_tol is:
@@ -1452,6 +1453,47 @@ def embedding_grad_ref(dc, label, K):
     mag = torch.zeros(K, D, dtype=torch.float64, device=dc.device).index_add_(0, label, dc.double().abs())
     nk = torch.bincount(label, minlength=K).double()[:, None]
     return ref, (nk - 1).clamp_min(0) * U24 * mag
+
+
+def adam_ema_ref(st32, grad, step, lr, b1, b2, eps, weight_decay, decay, ema_init, moment_rounding=False):
+    """One step of torch.optim.Adam + the reference's EMA lines (tools/utils.py:49-62) in float64 from the fp32 state st32 = {'p', 'm', 'v',
+    'ema'} ('ema' may be None: no EMA is kept) and the fp32 gradient Adam is FED (after clip_grad_norm_'s in-place scaling).  step: the step
+    being taken, from 1; ema_init: the EMA starts as a clone of the updated parameter (a parameter's first step).
+    -> ({'p', 'exp_avg', 'exp_avg_sq', 'ema'} float64 references, the same of bounds; no 'ema' without one).
+    bound: 2^-24 |value| (the rounding of the STORED fp32 value against an exact result) + 8 x 2 x 2^-24 |value - its previous value|: eight
+    roundings in the update chain, doubled because the device's sqrt and divide need not be correctly rounded; for p, exp_avg and
+    exp_avg_sq alike, each with its own step delta.  The EMA is a function of the NEW parameter, ema = ema_old d + (1 - d) p: with ema_init
+    ema_old = p, so the EMA IS the new parameter and is held to the parameter's bound; otherwise it inherits p's error with the factor
+    d ema / d p = 1 - d and adds its own rounding plus the roundings of its change.
+    moment_rounding: what `8 roundings relative to |delta p|` omits.  delta p = -step_size m_new / denom, and m_new = m + w1 (g - m) is
+    formed from fl(g - m): a rounding of 2^-24 |g - m| that enters m_new scaled by w1, 2^-24 |delta m| — relative to the CHANGE of the
+    moment, not to m_new.  From zero state (steps 1-3 of test_adam_ema_step_against_torch_adam) |delta m| <= |m_new| and the eight roundings cover it; from a
+    late state m + w1 (g - m) can cancel (g ~ -m (1 - w1) / w1), |m_new| << |delta m|, and the rounding of the difference alone exceeds
+    16 x 2^-24 |delta p| (a faithful fp32 emulation leaves the plain bound at 2 of 2,097,411 elements of train_stream_checks.adam_main_case:
+    test_train_stream_host.py).  With weight decay the fed gradient g + wd p is itself rounded once, 2^-24 |g'| <= 2^-24 (|g' - m| + |m|),
+    which adds w1 2^-24 |g'| <= 2^-24 ((1 + w1) |delta m| + w1 |m_new|).  moment_rounding=True therefore adds to p's bound
+    3 x 2^-24 |delta m| step_size / denom (1 + (1 + w1) <= 3; the |m_new| part is one of the eight), with step_size and denom of the float64
+    reference; the EMA inherits it through p's bound.  exp_avg_sq is a sum of non-negative terms and cannot cancel."""
+    p = torch.nn.Parameter(st32["p"].double())
+    opt = torch.optim.Adam([p], lr=lr, betas=(b1, b2), eps=eps, weight_decay=weight_decay)
+    if step > 1:
+        opt.state[p] = {"step": torch.tensor(float(step - 1)), "exp_avg": st32["m"].double(), "exp_avg_sq": st32["v"].double()}
+    p.grad = grad.double()
+    opt.step()
+    st = opt.state[p]
+    assert int(st["step"]) == step
+    ref = {"p": p.data, "exp_avg": st["exp_avg"], "exp_avg_sq": st["exp_avg_sq"]}
+    tol = {nm: U24 * ref[nm].abs() + 8 * 2 * U24 * (ref[nm] - st32[old].double()).abs() for nm, old in (("p", "p"), ("exp_avg", "m"), ("exp_avg_sq", "v"))}
+    if moment_rounding:
+        step_size = lr / (1.0 - b1 ** step)
+        denom = ref["exp_avg_sq"].sqrt() / (1.0 - b2 ** step) ** 0.5 + eps
+        tol["p"] = tol["p"] + 3 * U24 * (ref["exp_avg"] - st32["m"].double()).abs() * step_size / denom
+    if st32.get("ema") is not None:
+        ema = p.data.clone() if ema_init else st32["ema"].double()
+        ema.mul_(decay).add_(p.data, alpha=1. - decay)
+        ref["ema"] = ema
+        tol["ema"] = tol["p"] if ema_init else U24 * ema.abs() + 8 * 2 * U24 * (ema - st32["ema"].double()).abs() + (1.0 - decay) * tol["p"]
+    return ref, tol
 
 
 def attn_bwd_ref(q, k, v, o, do, B, H, Nq, Nk, Dh=64, rounded=True):

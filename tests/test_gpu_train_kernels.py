@@ -292,15 +292,9 @@ def test_adam_ema_step_against_torch_adam(weight_decay, clip):
         grad = torch.randn(n, generator=g) * (0.1 if step == 2 else 1.0)
         use_clip = clip != 1.0 or step == 2                                            # (a factor of exactly 1 is also passed once)
         # CPU: clip_grad_norm_'s in-place fp32 scaling (one IEEE product: the device's is held to torch.equal below), then in float64
-        # torch.optim.Adam and the EMA lines
-        p = torch.nn.Parameter(st32["p"].double())
-        opt = torch.optim.Adam([p], lr=lr, betas=(b1, b2), eps=eps, weight_decay=weight_decay)
-        if step > 1:
-            opt.state[p] = {"step": torch.tensor(float(step - 1)), "exp_avg": st32["m"].double(), "exp_avg_sq": st32["v"].double()}
-        p.grad = ((grad * coef) if use_clip else grad).double()                      # clip_grad_norm_ ran in fp32: THE gradient Adam is fed
-        opt.step()
-        ema = p.data.clone() if step == 1 else st32["ema"].double()
-        ema.mul_(decay).add_(p.data, alpha=1. - decay)
+        # torch.optim.Adam and the EMA lines (kernel_checks.adam_ema_ref, which also forms the bound stated above)
+        fed = (grad * coef) if use_clip else grad                                    # clip_grad_norm_ ran in fp32: THE gradient Adam is fed
+        ref, tol = kc.adam_ema_ref(st32, fed, step, lr, b1, b2, eps, weight_decay, decay, ema_init=step == 1)
         # device
         d = {k: v.clone().cuda() for k, v in st32.items()}
         gd = grad.clone().cuda()
@@ -310,23 +304,13 @@ def test_adam_ema_step_against_torch_adam(weight_decay, clip):
             assert torch.equal(gd.cpu(), grad * coef)                                  # the gradient is scaled in place
         else:
             assert torch.equal(gd.cpu(), grad)
-        st = opt.state[p]
-        assert int(st["step"]) == step
-        dp = (p.data - st32["p"].double()).abs()
-        tol_p = U24 * p.data.abs() + 8 * 2 * U24 * dp
-        for nm, got, want, delta in (("p", d["p"], p.data, dp), ("exp_avg", d["m"], st["exp_avg"], (st["exp_avg"] - st32["m"].double()).abs()),
-                                     ("exp_avg_sq", d["v"], st["exp_avg_sq"], (st["exp_avg_sq"] - st32["v"].double()).abs())):
-            tol = U24 * want.abs() + 8 * 2 * U24 * delta
-            worst = max(worst, kc.assert_elementwise(got.cpu(), want, tol, "adam_ema_step %s, step %d" % (nm, step)))
+        for nm, got in (("p", d["p"]), ("exp_avg", d["m"]), ("exp_avg_sq", d["v"])):
+            worst = max(worst, kc.assert_elementwise(got.cpu(), ref[nm], tol[nm], "adam_ema_step %s, step %d" % (nm, step)))
         # the EMA is a function of the NEW parameter: ema = ema_old d + (1 - d) p.  On a parameter's first step ema_old = p, so the EMA IS the
         # new parameter: bit-equal to it on the device, and held to the parameter's bound.  After that it inherits p's error with the factor
         # d ema / d p = 1 - d and adds its own rounding plus the roundings of its change (the issue's form, on the EMA's own delta).
         if step == 1:
             assert torch.equal(d["ema"], d["p"])
-            tol = tol_p
-        else:
-            d_ema = (ema - st32["ema"].double()).abs()
-            tol = U24 * ema.abs() + 8 * 2 * U24 * d_ema + (1.0 - decay) * tol_p
-        worst = max(worst, kc.assert_elementwise(d["ema"].cpu(), ema, tol, "adam_ema_step ema, step %d" % step))
+        worst = max(worst, kc.assert_elementwise(d["ema"].cpu(), ref["ema"], tol["ema"], "adam_ema_step ema, step %d" % step))
         st32 = {"p": d["p"].cpu(), "m": d["m"].cpu(), "v": d["v"].cpu(), "ema": d["ema"].cpu()}
     report("adam_ema_step wd%g clip%g" % (weight_decay, clip), worst)
