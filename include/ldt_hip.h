@@ -527,6 +527,51 @@ int ldt_attention_bwd_wide(const uint16_t* Q, int64_t ldq, int64_t q_batch_strid
 int ldt_reparam_kl_bwd(const float* post, const float* noise, const float* d_eps, int64_t ldd, float kl_scale, float* dpost, int64_t rows,
                        int32_t z, float lo, float hi, void* stream);
 
+/* ---- training the Compressor's front: training-mode BatchNorm + ReLU, the max over neighbours and the 'anchor' grouping, backward ----
+ * (batchnorm.hip, grouper_bwd.hip; model/Compressor/layers.py:115-160 PreExtraction, :186 the neighbour max, :288-319 LocalGrouper.forward;
+ * Network.py:86-101 MiniPointnet.)  The training kernels' contract: status codes before any launch, every sum in a fixed order with float64
+ * partials and one rounding, no floating-point atomics, a second call gives the same bits.
+ * ldt_bn_stats: stats fp32 [2][C] = (mean[c], rstd[c] = 1 / sqrt(biased variance + eps)) over the M >= 2 rows of x fp32 [M][ldx] (torch
+ *   refuses one value per channel in training).  Two passes: the mean in float64, then the float64 mean of (x - mean)^2, so a column of equal
+ *   values has rstd = 1 / sqrt(eps).  running_mean / running_var (each nullable) are updated in place as nn.BatchNorm1d does in training:
+ *   r = (1 - momentum) r + momentum (mean | variance M / (M - 1)), from the float64 statistics with one rounding.
+ * ldt_bn_relu_fwd: y[m][c] = ReLU(gamma[c] xhat + beta[c]), xhat = (x[m][c] - mean[c]) * rstd[c] in fp32, to bf16 (out_bf16) or fp32
+ *   [M][ldy]; the columns C <= c < cols_pad of y are written 0 (the K padding of a bf16 GEMM operand; cols_pad = C: none).
+ * ldt_bn_relu_bwd: from dy fp32, the SAVED x, the statistics, gamma and beta: dyh = dy where gamma xhat + beta > 0, else 0 (xhat and the mask
+ *   are recomputed with the forward's own operations, never stored); dgamma[c] = sum_m dyh xhat, dbeta[c] = sum_m dyh (each nullable);
+ *   dx[m][c] = gamma rstd ((dyh - dbeta / M) - xhat dgamma / M), fp32 [M][lddx]; dx may alias dy.  Two passes: column sums, then rows.
+ * ldt_maxpool_argmax: ldt_maxpool (the same bits in out) with arg int32 [G][C] = the row j of [G][n][C] that holds the maximum; on equal
+ *   values the smallest j (torch.max on the CPU), a NaN wins and the first one is kept.  relu != 0: out = ReLU(the maximum), which is
+ *   max_j ReLU(z_j) without the ReLU'd rows ever stored; arg is the arg-max of z itself.
+ * ldt_maxpool_relu_bwd: backward of out = max_j ReLU(z[g][j][c]) from d_out, out fp32 [G][C] and arg: dz[g][j][c] = d_out[g][c] where
+ *   j == arg[g][c] and out[g][c] > 0, else 0; EVERY element of dz fp32 [G n][ld] (columns < C) is written.
+ * ldt_group_normalize_bwd: backward of ldt_group_normalize with center_mode 0 ('anchor') from dU, fp32 or bf16 [B S k][ld], ld >= 2 D + 3.
+ *   Per sample b: d = g - anchor (fp32, as the forward rounds it), n_el = S k (D + 3), m = mean(d), sigma = unbiased std(d) and
+ *   inv = 1 / (sigma + 1e-5) from the forward's own statistics kernel, q = alpha dU[:, :D+3], P_b = sum q d.
+ *     dbeta[c] = sum dU[:, c],  dalpha[c] = sum_b inv_b sum dU[:, c] d[:, c]                      fp32 [D + 3], each nullable
+ *     dd = q inv - P_b inv^2 (d - m) / ((n_el - 1) sigma)
+ *     dfeat[b][p][c] = sum over the (s, j) with knn[b][s][j] == p of dd[s][j][c], in ascending (s, j),
+ *                    + sum over the s with fps[b][s] == p of (-sum_j dd[s][j][c] + sum_j dU[s][j][D + 3 + c]), in ascending s    fp32 [B][n][D]
+ *   (nullable; every element is written, a point in no group gets exactly 0; xyz is data and has no gradient).  inv_start int32 [B][n + 1]
+ *   and inv_entry int32 [B][S k] are the inverted index of knn_idx: the entries s k + j of point p of sample b are
+ *   inv_entry[b][inv_start[b][p] .. inv_start[b][p + 1]), ascending (a stable sort of knn_idx: integer bookkeeping, the caller's).  The sums
+ *   run in float64 in those orders and are rounded once: no atomics.  sigma == 0 (every d of a sample equal) has no defined gradient
+ *   upstream (inf * 0): the kernel then writes dd = q inv, the statistics term dropped.  An index outside its range contributes nothing.
+ *   The shape must leave n_el >= 2. */
+int ldt_bn_stats(const float* x, int64_t ldx, int64_t M, int32_t C, double eps, float* stats, float* running_mean, float* running_var,
+                 double momentum, void* stream);
+int ldt_bn_relu_fwd(const float* x, int64_t ldx, int64_t M, int32_t C, const float* stats, const float* gamma, const float* beta, void* y,
+                    int64_t ldy, int32_t out_bf16, int32_t cols_pad, void* stream);
+int ldt_bn_relu_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t M, int32_t C, const float* stats, const float* gamma,
+                    const float* beta, float* dx, int64_t lddx, float* dgamma, float* dbeta, void* stream);
+int ldt_maxpool_argmax(const void* in, int32_t in_bf16, int64_t ld, int64_t G, int32_t n, int32_t C, float* out, int32_t* arg, int32_t relu,
+                       void* stream);
+int ldt_maxpool_relu_bwd(const float* d_out, const float* out, const int32_t* arg, int64_t G, int32_t n, int32_t C, float* dz, int64_t ld,
+                         void* stream);
+int ldt_group_normalize_bwd(const void* dU, int32_t dU_bf16, int64_t ld, const float* feat, const float* xyz, const int32_t* fps_idx,
+                            const int32_t* knn_idx, const int32_t* inv_start, const int32_t* inv_entry, const float* alpha, int32_t B,
+                            int32_t n, int32_t S, int32_t k, int32_t D, float* dalpha, float* dbeta, float* dfeat, void* stream);
+
 /* ---- fused MLP half of a narrow ResidualBlock (the Compressor's d = 128 blocks; model/layers.py:219,226 + :110-133) ----
  * In place on x fp32 [M][ldx]:  x += gate * (W_dn . GELU(W_up . h + b_up) + b_dn),  h = LN(x) * ln_w + ln_b  (affine,
  * no-condition blocks) or LN(x) * (1 + scale) + shift (AdaLN; shift/scale/gate are per-sample vectors, sample =

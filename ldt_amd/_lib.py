@@ -127,6 +127,12 @@ SIGNATURES = {
     "ldt_attention_bwd_wide": [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64,
                                _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
     "ldt_reparam_kl_bwd": [_vp, _vp, _vp, _i64, C.c_float, _vp, _i64, _i32, C.c_float, C.c_float, _vp],
+    "ldt_bn_stats": [_vp, _i64, _i64, _i32, C.c_double, _vp, _vp, _vp, C.c_double, _vp],
+    "ldt_bn_relu_fwd": [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
+    "ldt_bn_relu_bwd": [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "ldt_maxpool_argmax": [_vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _vp],
+    "ldt_maxpool_relu_bwd": [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp],
+    "ldt_group_normalize_bwd": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "ldt_chamfer_nn": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "ldt_cd_loss": [_vp, _i64, _vp, _i64, _i32, _vp, _vp],
     "ldt_cd_loss_bwd": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp],

@@ -1,4 +1,4 @@
-"""Training the Compressor on the HIP path from the grouped tokens up, in three steps around train_block's one block: here is what is
+"""Training the Compressor on the HIP path, in four steps (three of them around train_block's one block): here is what is
 particular to each — the operand checks and refusals, the conditioning row, the level / stage loops and the order in which the stream
 gradients are added — plus `_centred_keys` and the composed `w_zkv` linear's backward.
 
@@ -20,7 +20,13 @@ T on T is `ldt_attention_bwd_cross`), `ldt_reparam_kl_bwd`, `ldt_silu_bwd`.  It 
 ActNorm, then per stage the AdaLN-form blocks (K / V from the RAW token stream) and the FinalLayer `conv_out`, all modulated by rows of ONE
 fp32 linear on SiLU(pos).  Its backward starts from `d_enc_out`, runs the stages in reverse with the FinalLayer's gradient ADDED to the
 running stream gradient (the stream runs on into the next stage), and ends in `ldt_actnorm_bwd`; it returns (d_tokens, d_pos), where the
-grouper's and the position embedding's backward would start.
+grouper's and the position embedding's backward start.
+
+`FrontTrainStep` (section 4.19): the front itself (Network.py:189-198) in TRAINING mode — the input conv, FPS / kNN grouping with 'anchor'
+normalisation, the three PreExtraction convs with batch-statistics BatchNorm (`ldt_bn_stats`, `ldt_bn_relu_fwd`), the max over the
+neighbours with its arg-max kept (`ldt_maxpool_argmax`), MiniPointnet on the centres.  Its backward starts from (d_tokens, d_pos):
+`ldt_maxpool_relu_bwd`, `ldt_bn_relu_bwd`, the bf16 linears' backward of train_block, `ldt_group_normalize_bwd`, the fp32 linears through
+`ldt_sgemm` on transposed operands.  The cloud is data: nothing is returned.
 """
 import torch
 
@@ -488,3 +494,177 @@ class EncoderTrainStep:
                             dlog_scale=ci.log_scale.grad.view(-1))
         self.d_tokens, self.d_pos = dX.view(B, T, C), d_pos
         return self.d_tokens, self.d_pos
+
+
+# ---------------------------------------------------------------- the front: input conv, grouper, position embedding
+def front_parameters(model):
+    """The parameters a front step trains, in module order: the input conv, the LocalGrouper (affine vectors, the three PreExtraction convs
+    and their two BatchNorms) and the MiniPointnet position embedding."""
+    return [(name, p) for name, p in model.named_parameters() if name.split(".")[0] in ("input", "group", "pos_embedding")]
+
+
+def refuse_untrainable_front(model, num_points=None):
+    """The configurations the front step does not cover, each refused with its reason before anything is launched.  num_points: the cloud
+    size of the call (default: cfg.outsize)."""
+    from .layers import MLP
+    if model.pre_group:
+        raise NotImplementedError("training the front with pre_group: True is not on this path: the gradient of the second grouper's points "
+                                  "would have to run through the first grouper's neighbour max (two chained groupers)")
+    if isinstance(model.pos_embedding, MLP):
+        raise NotImplementedError("training the front with pos_embedding: mlp is not on this path: only the MiniPointnet position embedding "
+                                  "has a backward (and the encoder step refuses a per-token position condition)")
+    if getattr(model, "class_condition", False):
+        raise NotImplementedError("training the front with class_condition is not on this path: the label embedding added to the position "
+                                  "condition has no backward here")
+    if model.group.normalize != "anchor":
+        raise NotImplementedError("training the front with cluster_norm=%r is not on this path: ldt_group_normalize_bwd covers 'anchor' only"
+                                  % (model.group.normalize,))
+    N = model.outsize if num_points is None else int(num_points)
+    T = model.z_scales
+    k = N // T * 2
+    if not 1 <= k <= N:
+        raise NotImplementedError("training the front with %d points in %d groups is not on this path: k = N // T * 2 = %d neighbours of %d points"
+                                  % (N, T, k, N))
+    if model.input.weight.device.type != "cuda":
+        raise RuntimeError("training the front: the parameters are on %s; the HIP path has no CPU fallback" % model.input.weight.device)
+
+
+def _vec(t):
+    """A small parameter vector as a fresh fp32 tensor (an optimizer's flat views are only 4-byte aligned: the kernels' 16-byte form wants more)."""
+    return t.detach().float().reshape(-1).clone()
+
+
+class FrontTrainStep:
+    """One forward + backward of the Compressor's front (Network.py:189-198) in TRAINING mode: every BatchNorm normalises with the batch
+    statistics and updates its running buffers (momentum, unbiased variance, num_batches_tracked), whatever `model.training` says.
+    `forward(x)` takes the clouds (B, N, 3) and returns (tokens (B, T, hidden) BEFORE ActNorm, pos (B, p_dim)) — EncoderTrainStep.forward's
+    operands — keeping the tape, the arg-max of the neighbour max and of MiniPointnet's max included; `fps_idx`, `knn_idx` and `centers`
+    stay as attributes.  `backward(d_tokens, d_pos)` fills every `.grad` of front_parameters(model); the cloud is data and gets no gradient.
+    The chain is unfused (ldt_grouper_mlp and the eval-folded panels are the evaluation path's): ldt_group_normalize, per BatchNorm layer a GEMM
+    with fp32 output, ldt_bn_stats and ldt_bn_relu_fwd, the residual GEMM in fp32, ldt_maxpool_argmax with the ReLU on the maximum."""
+
+    def __init__(self, model):
+        refuse_untrainable_front(model)
+        self.m = model
+        self.saved = None
+        self.fps_idx = self.knn_idx = self.centers = None
+
+    def _bn(self, bn, z):
+        """Batch statistics of z with the running buffers of `bn` updated as nn.BatchNorm1d does in training -> stats fp32 [2, C]."""
+        if bn.momentum is None or not bn.track_running_stats:
+            raise NotImplementedError("FrontTrainStep: a BatchNorm with momentum None or without running statistics is not on this path")
+        st = ops.bn_stats(z, bn.eps, bn.running_mean, bn.running_var, bn.momentum)
+        bn.num_batches_tracked += 1
+        return st
+
+    # ---------------------------------------------------------------- forward
+    @torch.no_grad()
+    def forward(self, x):
+        from ._lib import EPI_F32, EPI_RESID_F32
+        from .compressor import _bf16_panel
+        m = self.m
+        refuse_host("FrontTrainStep.forward", "the cloud", x)
+        self.saved = None
+        if x.dim() != 3 or x.shape[2] != 3:
+            raise ValueError("FrontTrainStep.forward: x %s is not (B, N, 3)" % (tuple(x.shape),))
+        B, N, _ = x.shape
+        refuse_untrainable_front(m, N)
+        T, D = m.z_scales, m.hidden_dim
+        k = N // T * 2
+        if B * T < 2:
+            raise ValueError("FrontTrainStep.forward: training-mode BatchNorm needs more than one centre per batch (B = %d, tokens = %d)" % (B, T))
+        pts = x.detach().float().contiguous()
+        if m.norm_input:
+            pts = ops.norm_points(pts)                                  # a transform of data: no parameters
+        S = {"B": B, "N": N, "T": T, "k": k, "pts": pts}
+        S["feat"] = feat = ops.sgemm(pts.view(B * N, 3), _f32(conv_w(m.input)), _f32(m.input.bias)).view(B, N, D)     # Conv1d 3 -> D (:192)
+        self.fps_idx = fps_idx = ops.fps(pts, T)
+        self.centers = centers = ops.gather_rows(pts, fps_idx)
+        self.knn_idx = knn_idx = ops.knn(pts, centers, k)
+        g = m.group
+        ex = g.extraction
+        c1, bn1 = ex.transfer.net[0], ex.transfer.net[1]
+        c2, bn2 = ex.operation[0].net1[0], ex.operation[0].net1[1]
+        c3 = ex.operation[0].net2[0]
+        S["alpha"] = _vec(g.affine_alpha)
+        S["U"] = U = ops.group_normalize(feat, pts, fps_idx, knn_idx, S["alpha"], _vec(g.affine_beta), normalize="anchor")
+        # transfer: Conv -> BatchNorm (batch statistics) -> ReLU
+        S["w1"] = _bf16_panel(_f32(conv_w(c1)))                          # bf16 [D, pad64(2 D + 3)], kept for dU
+        S["z1"] = z1 = ops.gemm_bf16(U, S["w1"], _f32(c1.bias), EPI_F32)
+        S["st1"], S["g1"], S["b1"] = self._bn(bn1, z1), _vec(bn1.weight), _vec(bn1.bias)
+        S["h1"] = h1 = ops.bn_relu_fwd(z1, S["st1"], S["g1"], S["b1"])
+        # net1: Conv -> BatchNorm -> ReLU; net2: Conv, + the block's input, ReLU
+        S["z2"] = z2 = ops.gemm_bf16(h1, _bf16_panel(_f32(conv_w(c2))), _f32(c2.bias), EPI_F32)
+        S["st2"], S["g2"], S["b2"] = self._bn(bn2, z2), _vec(bn2.weight), _vec(bn2.bias)
+        S["r"] = r = ops.bn_relu_fwd(z2, S["st2"], S["g2"], S["b2"])
+        # only the GEMM operands are bf16: the residual takes h1 in fp32 and the sum stays fp32 up to the max, so that the tokens carry
+        # the operand roundings alone (the evaluation path's EPI_RELU_BF16 rounds the skip and the sum as well)
+        z3 = ops.bn_relu_fwd(z1, S["st1"], S["g1"], S["b1"], out_bf16=False)
+        ops.gemm_bf16(r, _bf16_panel(_f32(conv_w(c3))), _f32(c3.bias), EPI_RESID_F32, out=z3, resid=z3)                # z3 = net2(r) + h1
+        S["tok"], S["arg"] = ops.maxpool_argmax(z3, B * T, k, relu=True)  # max_j ReLU(z3_j) over the k neighbours (:186) = ReLU(max_j z3_j)
+        # MiniPointnet on the centres (Network.py:86-101), fp32
+        pe = m.pos_embedding
+        S["ctr"] = ctr = centers.view(B * T, 3)
+        S["y1"] = y1 = ops.sgemm(ctr, _f32(conv_w(pe.conv1)), _f32(pe.conv1.bias))
+        S["sp1"], S["gp1"], S["bp1"] = self._bn(pe.bn1, y1), _vec(pe.bn1.weight), _vec(pe.bn1.bias)
+        S["a1"] = a1 = ops.bn_relu_fwd(y1, S["sp1"], S["gp1"], S["bp1"], out_bf16=False)
+        S["y2"] = y2 = ops.sgemm(a1, _f32(conv_w(pe.conv2)), _f32(pe.conv2.bias))
+        S["sp2"], S["gp2"], S["bp2"] = self._bn(pe.bn2, y2), _vec(pe.bn2.weight), _vec(pe.bn2.bias)
+        a2 = ops.bn_relu_fwd(y2, S["sp2"], S["gp2"], S["bp2"], out_bf16=False)
+        S["pool"], S["argp"] = ops.maxpool_argmax(a2, B, T)              # the max over the tokens (:97)
+        pos = ops.sgemm(S["pool"], _f32(pe.fc.weight), _f32(pe.fc.bias))
+        m.invalidate_packed()                                            # the evaluation path folds the running buffers written above
+        self.saved = S
+        return S["tok"].view(B, T, D), pos
+
+    # ---------------------------------------------------------------- backward
+    def _fp32_linear_bwd(self, layer, dy, x_in, want_dx=True):
+        """An fp32 linear through ldt_sgemm on transposed operands (as TrainBlock.adaln_bwd): dW, db into the .grad views -> dX = dy W."""
+        ops.sgemm(_t(dy), _t(x_in), out=_grad2d(layer.weight))
+        ops.colsum(dy, out=layer.bias.grad)
+        return ops.sgemm(dy, _t(_f32(conv_w(layer)))) if want_dx else None
+
+    @torch.no_grad()
+    def backward(self, d_tokens, d_pos):
+        m, S = self.m, self.saved
+        if S is None:
+            raise RuntimeError("FrontTrainStep.backward before forward")
+        self.saved = None
+        B, N, T, k = S["B"], S["N"], S["T"], S["k"]
+        D = m.hidden_dim
+        if not torch.is_tensor(d_tokens) or tuple(d_tokens.shape) != (B, T, D) or not torch.is_tensor(d_pos) or tuple(d_pos.shape) != (B, m.p_dim):
+            raise ValueError("FrontTrainStep.backward: d_tokens / d_pos are not (%d, %d, %d) / (%d, %d)" % (B, T, D, B, m.p_dim))
+        refuse_host("FrontTrainStep.backward", "a gradient", d_tokens, d_pos)
+        for _, p in front_parameters(m):
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        tb = TrainBlock(ops)
+        g = m.group
+        ex = g.extraction
+        c1, bn1 = ex.transfer.net[0], ex.transfer.net[1]
+        c2, bn2 = ex.operation[0].net1[0], ex.operation[0].net1[1]
+        c3 = ex.operation[0].net2[0]
+        # tok = max_j ReLU(net2(r) + h1): the gradient goes to the kept neighbour, where the token is positive
+        dz3 = ops.maxpool_relu_bwd(d_tokens.detach().float().contiguous().view(B * T, D), S["tok"], S["arg"], k)          # [M, D] fp32
+        dr = tb.linear_bwd(c3, dz3, S["r"][:, :D])
+        ops.bn_relu_bwd(dr, S["z2"], S["st2"], S["g2"], S["b2"], dx=dr, dgamma=bn2.weight.grad, dbeta=bn2.bias.grad)      # dr becomes dz2
+        dh1 = tb.linear_bwd(c2, dr, S["h1"][:, :D])
+        ops.add_f32(dh1, dz3, out=dh1)                                   # the residual: net2's input h1 is also added to its output
+        ops.bn_relu_bwd(dh1, S["z1"], S["st1"], S["g1"], S["b1"], dx=dh1, dgamma=bn1.weight.grad, dbeta=bn1.bias.grad)    # dh1 becomes dz1
+        # the transfer conv at the padded width of U (2 D + 3 columns are no 16-byte row for a GEMM's output): dW's padding columns are
+        # dropped, dU's are zero (the panel's padding rows) and ldt_group_normalize_bwd reads the first 2 D + 3 only
+        _grad2d(c1.weight).copy_(ops.wgrad(dh1, S["U"])[:, :2 * D + 3])
+        ops.colsum(dh1, out=c1.bias.grad)
+        dU = ops.dgrad(ops.cast_pad_bf16(dh1, ops.pad64(D)), ops.transpose_cast_bf16(S["w1"]))       # [M, pad64(2 D + 3)] fp32
+        dalpha, dbeta, dfeat = ops.group_normalize_bwd(dU, S["feat"], S["pts"], self.fps_idx, self.knn_idx, S["alpha"])
+        g.affine_alpha.grad.view(-1).copy_(dalpha)
+        g.affine_beta.grad.view(-1).copy_(dbeta)
+        self._fp32_linear_bwd(m.input, dfeat.view(B * N, D), S["pts"].view(B * N, 3), want_dx=False)                      # the cloud is data
+        # MiniPointnet
+        pe = m.pos_embedding
+        dpool = self._fp32_linear_bwd(pe.fc, d_pos.detach().float().contiguous(), S["pool"])
+        da2 = ops.maxpool_relu_bwd(dpool, S["pool"], S["argp"], T)
+        ops.bn_relu_bwd(da2, S["y2"], S["sp2"], S["gp2"], S["bp2"], dx=da2, dgamma=pe.bn2.weight.grad, dbeta=pe.bn2.bias.grad)
+        da1 = self._fp32_linear_bwd(pe.conv2, da2, S["a1"])
+        ops.bn_relu_bwd(da1, S["y1"], S["sp1"], S["gp1"], S["bp1"], dx=da1, dgamma=pe.bn1.weight.grad, dbeta=pe.bn1.bias.grad)
+        self._fp32_linear_bwd(pe.conv1, da1, S["ctr"], want_dx=False)     # the centres are data

@@ -11,8 +11,9 @@ Adam without EMA over the decoder-side parameters, and the gradient with respect
 decoder — with the bottom-up half frozen (compressor_train.TopDownTrainStep; section 4.16): loss = kl_weight * kl_loss + the Chamfer term,
 the gradient with respect to the encoder outputs kept as `last_enc_out_grad`; and `update_encoder`, that step with ActNorm and the encoder
 in the graph and only the front (input conv, grouper, position embedding) frozen (compressor_train.EncoderTrainStep; section 4.17), the
-gradients with respect to the grouped tokens and the position condition kept as `last_tokens_grad` / `last_pos_grad`.  The whole
-Compressor step is out of scope: `update` / `compute_loss` raise — the grouper backward is not built, and
+gradients with respect to the grouped tokens and the position condition kept as `last_tokens_grad` / `last_pos_grad`; and `update_front`,
+that step with the front in the graph too, in training mode for its BatchNorms (compressor_train.FrontTrainStep; section 4.19): every
+parameter of the Compressor receives a gradient.  The reference's own step stays out of scope: `update` / `compute_loss` raise —
 `compute_loss` adds `EMD_loss`, which goes through the auction-EMD CUDA extension of evaluation/emd.py that this package does not have
 (and does not imitate).
 
@@ -198,20 +199,59 @@ class CompressorTrainer:
             tokens = fr["tokens"] if tokens is None else tokens
             pos = fr["pos"] if pos is None else pos
         tokens, pos = tokens.to(self.device).float().contiguous(), pos.to(self.device).float().contiguous()
-        if m.ActNorm is not None and not bool(m.conv_in.initialized):
-            with torch.no_grad():                                    # ActNorm.data_init (layers.py:74-79) on these tokens
-                ci = m.conv_in
-                x = tokens.view(-1, 1, tokens.shape[2]) if ci.feature_type == "set" else tokens
-                ci.shift.data.copy_(torch.mean(x, dim=0, keepdim=True))
-                ci.log_scale.data.copy_(torch.log(torch.std(x, dim=0, keepdim=True) + ci.eps))
-                ci.initialized += 1.
-            m.invalidate_packed()
+        self._actnorm_data_init(tokens)
         keep_mask, post_noise = self._draws(points.shape[0], points.shape[1], tokens.shape[1], post_noise)
         optimizer = self._begin("encoder_optimizer", lambda: encoder_parameters(m) + topdown_parameters(m))
         enc = EncoderTrainStep(m)
         enc_out = enc.forward(tokens, pos)
         losses, d_enc_out = self._topdown_pass(points, enc_out, post_noise, keep_mask, tokens.shape[1])
         self.last_tokens_grad, self.last_pos_grad = enc.backward(d_enc_out)
+        self._finish(optimizer)
+        return losses
+
+    def _actnorm_data_init(self, tokens):
+        """While `model.conv_in.initialized` is 0: ActNorm.data_init (layers.py:74-79) on these tokens, torch on the device, once."""
+        m = self.model
+        if m.ActNorm is None or bool(m.conv_in.initialized):
+            return
+        with torch.no_grad():
+            ci = m.conv_in
+            x = tokens.view(-1, 1, tokens.shape[2]) if ci.feature_type == "set" else tokens
+            ci.shift.data.copy_(torch.mean(x, dim=0, keepdim=True))
+            ci.log_scale.data.copy_(torch.log(torch.std(x, dim=0, keepdim=True) + ci.eps))
+            ci.initialized += 1.
+        m.invalidate_packed()
+
+    # ---- training the whole Compressor: the front in the graph too -------------------------------------------
+    front_optimizer = None                                           # AdamEMA over every parameter, created by the first update_front
+
+    def update_front(self, data, *, post_noise=None):
+        """`update_encoder` with the front in the graph (compressor_train.FrontTrainStep), so that every parameter of
+        the Compressor receives a gradient: the input conv, the grouper and the position embedding run on data['tr_points'] in TRAINING mode
+        with their tape — every BatchNorm normalises with the batch statistics and updates its running buffers as nn.BatchNorm1d does — then
+        the data-dependent ActNorm init (while `initialized` is 0), the draws, the encoder and the top-down pass, `CD_loss` of type 'l1', the
+        three backwards in reverse, clip_grad_norm_ and Adam without EMA over all parameters (`self.front_optimizer`, apart from the other
+        three), `itr += 1`.  -> (loss, kl_loss, rec_loss) as update_encoder: rec_loss IS the Chamfer term (compute_loss says why).
+        `self.last_tokens_grad` / `self.last_pos_grad` keep what the front's backward started from."""
+        from .compressor_train import (EncoderTrainStep, FrontTrainStep, encoder_parameters, front_parameters, refuse_untrainable_encoder,
+                                       refuse_untrainable_front, refuse_untrainable_topdown, topdown_parameters)
+        if self.kl_weight is None:
+            raise ValueError("CompressorTrainer.update_front: cfg.opt.kl_weight is not set; the loss is kl_weight * kl_loss + rec_loss")
+        m = self.model
+        refuse_untrainable_front(m)
+        refuse_untrainable_encoder(m)
+        refuse_untrainable_topdown(m)
+        points = self._points("update_front", data)
+        front = FrontTrainStep(m)
+        tokens, pos = front.forward(points)
+        self._actnorm_data_init(tokens)
+        keep_mask, post_noise = self._draws(points.shape[0], points.shape[1], tokens.shape[1], post_noise)
+        optimizer = self._begin("front_optimizer", lambda: front_parameters(m) + encoder_parameters(m) + topdown_parameters(m))
+        enc = EncoderTrainStep(m)
+        enc_out = enc.forward(tokens, pos)
+        losses, d_enc_out = self._topdown_pass(points, enc_out, post_noise, keep_mask, tokens.shape[1])
+        self.last_tokens_grad, self.last_pos_grad = enc.backward(d_enc_out)
+        front.backward(self.last_tokens_grad, self.last_pos_grad)
         self._finish(optimizer)
         return losses
 
@@ -296,6 +336,10 @@ class CompletionCompressorTrainer(CompressorTrainer):
 
     def update_encoder(self, data, *, tokens=None, pos=None, post_noise=None):
         raise NotImplementedError("CompletionCompressorTrainer.update_encoder: the encoder step is built and held for CompressorTrainer "
+                                  "alone; training is not on this path for the completion trainer")
+
+    def update_front(self, data, *, post_noise=None):
+        raise NotImplementedError("CompletionCompressorTrainer.update_front: the front step is built and held for CompressorTrainer "
                                   "alone; training is not on this path for the completion trainer")
 
     def compute_loss(self, target_set):

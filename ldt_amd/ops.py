@@ -556,6 +556,160 @@ def actnorm_bwd(dz, z, log_scale, B, dx=None, dshift=None, dlog_scale=None, want
     return dx, dshift, dlog_scale
 
 
+# ---- training the Compressor's front: training-mode BatchNorm + ReLU, the max with its arg-max, the 'anchor' grouping's backward
+def _rows2d(t, name, dtypes=(torch.float32,)):
+    if t.dim() != 2:
+        raise ValueError("%s must be [rows, columns], got %s" % (name, tuple(t.shape)))
+    if not t.is_cuda:
+        raise _lib.LdtHipError("%s must be a device tensor (got %s): the HIP path has no CPU fallback" % (name, t.device))
+    if t.dtype not in dtypes:
+        raise TypeError("%s must be %s, got %s" % (name, " or ".join(str(d) for d in dtypes), t.dtype))
+    _rowmajor(t, name)
+
+
+def _vecC(t, C, name):
+    _need(t, torch.float32, name)
+    if t is not None and (t.numel() != C or not t.is_contiguous()):
+        raise ValueError("%s must be contiguous with %d elements, got %s" % (name, C, tuple(t.shape)))
+
+
+def bn_stats(x, eps=1e-5, running_mean=None, running_var=None, momentum=0.1, out=None):
+    """Training-mode BatchNorm statistics of x fp32 [M, C] (M >= 2) -> fp32 [2, C] = (mean, rstd = 1 / sqrt(biased var + eps)).  running_mean /
+    running_var fp32 [C]: updated in place as nn.BatchNorm1d does ((1 - momentum) r + momentum (mean | unbiased var))."""
+    _rows2d(x, "x")
+    M, Cc = x.shape
+    if M < 2:
+        raise ValueError("bn_stats: training-mode BatchNorm needs more than one value per channel, got %d rows" % M)
+    _vecC(running_mean, Cc, "running_mean"); _vecC(running_var, Cc, "running_var")
+    if out is None:
+        out = torch.empty((2, Cc), dtype=torch.float32, device=x.device)
+    _need(out, torch.float32, "out")
+    if tuple(out.shape) != (2, Cc) or not out.is_contiguous():
+        raise ValueError("bn_stats: out must be a contiguous fp32 [2, %d]" % Cc)
+    check(lib().ldt_bn_stats(_p(x), x.stride(0), M, Cc, float(eps), _p(out), _p(running_mean), _p(running_var), float(momentum), stream_ptr()),
+          "ldt_bn_stats")
+    return out
+
+
+def _bn_operands(who, x, stats, gamma, beta):
+    _rows2d(x, "x")
+    M, Cc = x.shape
+    _need(stats, torch.float32, "stats")
+    if tuple(stats.shape) != (2, Cc) or not stats.is_contiguous():
+        raise ValueError("%s: stats must be a contiguous fp32 [2, %d]" % (who, Cc))
+    _vecC(gamma, Cc, "gamma"); _vecC(beta, Cc, "beta")
+    return M, Cc
+
+
+def bn_relu_fwd(x, stats, gamma, beta, out_bf16=True, cols_pad=None, out=None):
+    """y = ReLU(gamma (x - mean) rstd + beta): x fp32 [M, C], stats from bn_stats -> bf16 (or fp32) [M, cols_pad], columns past C zero
+    (cols_pad default: pad64(C) for bf16, C for fp32)."""
+    M, Cc = _bn_operands("bn_relu_fwd", x, stats, gamma, beta)
+    if out is None:
+        cp = (pad64(Cc) if out_bf16 else Cc) if cols_pad is None else int(cols_pad)
+        out = torch.empty((M, cp), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=x.device)
+    else:
+        _rows2d(out, "out", (torch.float32, torch.bfloat16))
+        cp = out.shape[1] if cols_pad is None else int(cols_pad)
+        if out.shape[0] != M or not Cc <= cp <= out.shape[1]:
+            raise ValueError("bn_relu_fwd: out %s does not hold [%d, %d <= cols_pad = %d]" % (tuple(out.shape), M, Cc, cp))
+    check(lib().ldt_bn_relu_fwd(_p(x), x.stride(0), M, Cc, _p(stats), _p(gamma), _p(beta), _p(out), out.stride(0), int(out.dtype == torch.bfloat16),
+                                cp, stream_ptr()), "ldt_bn_relu_fwd")
+    return out
+
+
+def bn_relu_bwd(dy, x, stats, gamma, beta, dx=None, dgamma=None, dbeta=None):
+    """Backward of bn_relu_fwd from dy fp32 [M, C] and the saved x -> (dx fp32 [M, C] (`dx` given: written there, dy itself allowed),
+    dgamma, dbeta fp32 [C] into the buffers given or fresh ones)."""
+    M, Cc = _bn_operands("bn_relu_bwd", x, stats, gamma, beta)
+    _rows2d(dy, "dy")
+    if tuple(dy.shape) != (M, Cc) or M < 2:
+        raise ValueError("bn_relu_bwd: dy %s and x %s must share one [M >= 2, C] shape" % (tuple(dy.shape), tuple(x.shape)))
+    if dx is None:
+        dx = torch.empty((M, Cc), dtype=torch.float32, device=x.device)
+    _rows2d(dx, "dx")
+    if tuple(dx.shape) != (M, Cc):
+        raise ValueError("bn_relu_bwd: dx %s is not [%d, %d]" % (tuple(dx.shape), M, Cc))
+    dgamma = torch.empty(Cc, dtype=torch.float32, device=x.device) if dgamma is None else dgamma
+    dbeta = torch.empty(Cc, dtype=torch.float32, device=x.device) if dbeta is None else dbeta
+    _vecC(dgamma, Cc, "dgamma"); _vecC(dbeta, Cc, "dbeta")
+    check(lib().ldt_bn_relu_bwd(_p(dy), dy.stride(0), _p(x), x.stride(0), M, Cc, _p(stats), _p(gamma), _p(beta), _p(dx), dx.stride(0), _p(dgamma),
+                                _p(dbeta), stream_ptr()), "ldt_bn_relu_bwd")
+    return dx, dgamma, dbeta
+
+
+def maxpool_argmax(x, G, n, relu=False):
+    """maxpool with the arg-max kept: x [G*n, C] (bf16 or fp32) -> (fp32 [G, C], int32 [G, C]); on equal values the smallest row index.
+    relu: the values are ReLU(max) = max over the rows of ReLU(x); the arg-max is x's own."""
+    _rows2d(x, "x", (torch.float32, torch.bfloat16))
+    Cc = x.shape[1]
+    if G < 1 or n < 1 or x.shape[0] != G * n:
+        raise ValueError("maxpool_argmax: x %s is not [G = %d x n = %d, C]" % (tuple(x.shape), G, n))
+    out = torch.empty((G, Cc), dtype=torch.float32, device=x.device)
+    arg = torch.empty((G, Cc), dtype=torch.int32, device=x.device)
+    check(lib().ldt_maxpool_argmax(_p(x), int(x.dtype == torch.bfloat16), x.stride(0), G, n, Cc, _p(out), _p(arg), int(bool(relu)), stream_ptr()),
+          "ldt_maxpool_argmax")
+    return out, arg
+
+
+def maxpool_relu_bwd(d_out, out, arg, n, dz=None):
+    """Backward of out = max over n rows of ReLU(z): d_out, out fp32 [G, C], arg int32 [G, C] -> dz fp32 [G*n, C], every element written."""
+    _need(d_out, torch.float32, "d_out"); _need(out, torch.float32, "out"); _need(arg, torch.int32, "arg")
+    G, Cc = out.shape
+    for t, nm in ((d_out, "d_out"), (out, "out"), (arg, "arg")):
+        if tuple(t.shape) != (G, Cc) or not t.is_contiguous():
+            raise ValueError("maxpool_relu_bwd: %s %s is not a contiguous [%d, %d]" % (nm, tuple(t.shape), G, Cc))
+    if dz is None:
+        dz = torch.empty((G * n, Cc), dtype=torch.float32, device=out.device)
+    _rows2d(dz, "dz")
+    if n < 1 or tuple(dz.shape) != (G * n, Cc):
+        raise ValueError("maxpool_relu_bwd: dz %s is not [%d, %d]" % (tuple(dz.shape), G * n, Cc))
+    check(lib().ldt_maxpool_relu_bwd(_p(d_out), _p(out), _p(arg), G, n, Cc, _p(dz), dz.stride(0), stream_ptr()), "ldt_maxpool_relu_bwd")
+    return dz
+
+
+def knn_inverted_index(knn_idx, n):
+    """The inverted index of knn_idx int32 [B, S, k] over the n points of each cloud -> (inv_start int32 [B, n + 1], inv_entry int32 [B, S k]):
+    the entries s k + j with knn_idx[b, s, j] == p are inv_entry[b, inv_start[b, p]: inv_start[b, p + 1]], ascending.  Integer bookkeeping:
+    a stable sort and a binary search in torch on the indices' device."""
+    B = knn_idx.shape[0]
+    flat = knn_idx.reshape(B, -1)
+    vals, order = torch.sort(flat, dim=1, stable=True)
+    edges = torch.arange(n + 1, dtype=flat.dtype, device=flat.device).unsqueeze(0).expand(B, -1).contiguous()
+    start = torch.searchsorted(vals.contiguous(), edges)
+    return start.to(torch.int32).contiguous(), order.to(torch.int32).contiguous()
+
+
+def group_normalize_bwd(dU, feat, xyz, fps_idx, knn_idx, alpha, want_dfeat=True, index=None):
+    """Backward of group_normalize('anchor'): dU fp32 | bf16 [B*S*k, >= 2D+3] -> (dalpha, dbeta fp32 [D+3], dfeat fp32 [B, n, D] or None).
+    index: knn_inverted_index(knn_idx, n), built here when not given."""
+    _rows2d(dU, "dU", (torch.float32, torch.bfloat16))
+    for t, nm in ((feat, "feat"), (xyz, "xyz"), (alpha, "alpha")):
+        _need(t, torch.float32, nm)
+    _need(fps_idx, torch.int32, "fps_idx"); _need(knn_idx, torch.int32, "knn_idx")
+    B, n, D = feat.shape
+    S, k = knn_idx.shape[1], knn_idx.shape[2]
+    if tuple(xyz.shape) != (B, n, 3) or tuple(fps_idx.shape) != (B, S) or knn_idx.shape[0] != B or alpha.numel() != D + 3:
+        raise ValueError("group_normalize_bwd: feat %s, xyz %s, fps_idx %s, knn_idx %s, alpha %s do not fit" % (
+            tuple(feat.shape), tuple(xyz.shape), tuple(fps_idx.shape), tuple(knn_idx.shape), tuple(alpha.shape)))
+    if dU.shape[0] != B * S * k or dU.shape[1] < 2 * D + 3:
+        raise ValueError("group_normalize_bwd: dU %s is not [%d, >= %d]" % (tuple(dU.shape), B * S * k, 2 * D + 3))
+    if not (feat.is_contiguous() and xyz.is_contiguous() and fps_idx.is_contiguous() and knn_idx.is_contiguous() and alpha.is_contiguous()):
+        raise ValueError("group_normalize_bwd: operands must be contiguous")
+    dalpha = torch.empty(D + 3, dtype=torch.float32, device=feat.device)
+    dbeta = torch.empty(D + 3, dtype=torch.float32, device=feat.device)
+    dfeat = start = entry = None
+    if want_dfeat:
+        start, entry = knn_inverted_index(knn_idx, n) if index is None else index
+        _need(start, torch.int32, "inv_start"); _need(entry, torch.int32, "inv_entry")
+        if tuple(start.shape) != (B, n + 1) or tuple(entry.shape) != (B, S * k) or not (start.is_contiguous() and entry.is_contiguous()):
+            raise ValueError("group_normalize_bwd: the inverted index is not ([%d, %d], [%d, %d])" % (B, n + 1, B, S * k))
+        dfeat = torch.empty((B, n, D), dtype=torch.float32, device=feat.device)
+    check(lib().ldt_group_normalize_bwd(_p(dU), int(dU.dtype == torch.bfloat16), dU.stride(0), _p(feat), _p(xyz), _p(fps_idx), _p(knn_idx), _p(start),
+                                        _p(entry), _p(alpha), B, n, S, k, D, _p(dalpha), _p(dbeta), _p(dfeat), stream_ptr()), "ldt_group_normalize_bwd")
+    return dalpha, dbeta, dfeat
+
+
 def reparam(post, noise, out, lo, hi, want_stats=False):
     """post fp32 [rows, 2z], noise [rows, z] -> out[rows, z] (strided slice ok) = mu + exp(clamp(logvar)/2)*noise."""
     rows, z2 = post.shape
