@@ -466,7 +466,8 @@ class Compressor(nn.Module):
         tok_pre = tok.clone() if want_stats else None
         per_tok = "w_pm1" in P
         if self.ActNorm is not None:
-            ops.actnorm_(tok, P["an_shift"], P["an_logs"], B)
+            # per-token parameters (1, T, D), or with `ActNorm: set` one (1, 1, D) row that every token shares (layers.py:95-101)
+            ops.actnorm_(tok, P["an_shift"], P["an_logs"], tok.numel() // P["an_shift"].numel())
         enc_out = []
         for Pe in P["enc"]:                                                         # Network.py:203-205, 41-45
             for Pa in Pe["atts"]:

@@ -24,8 +24,11 @@ import torch
 import kernel_checks as kc
 
 INPLACE = ("out", "dx", "dshift", "dscale", "dgate",
-           "dq_out", "dkv_out", "dlog_scale", "stats_out")      # the Compressor steps' entry points (tests/compressor_tape.py)
+           "dq_out", "dkv_out", "dlog_scale", "stats_out",      # the Compressor steps' entry points (tests/compressor_tape.py)
+           "x_bf16_out")                                        # the inference forwards' (tests/infer_tape.py): no training step passes one;
+#                                                                 `resid` where it aliases `out` is held through `out`'s before / after
 PLAIN = ("pad64", "stream_ptr")                      # no tensors: forwarded unrecorded
+WRITES = {"attention_oproj_resid_": "x"}             # a `..._` entry point whose in-place operand is not its first (inference only)
 
 
 def _epilogues():
@@ -52,6 +55,8 @@ def _snap(v):
         return Rec(v)
     if isinstance(v, (tuple, list)):
         return type(v)(_snap(x) for x in v)
+    if isinstance(v, dict):                              # ln_mlp_resid_'s `next_linear` (inference only)
+        return {k: _snap(x) for k, x in v.items()}
     return v
 
 
@@ -106,7 +111,7 @@ class Tape:
             call = Call(len(self.calls), name, {k: _snap(v) for k, v in bound.arguments.items()})
             dest = {k: v for k, v in bound.arguments.items() if k in INPLACE and torch.is_tensor(v)}
             if name.endswith("_"):
-                first = next(iter(bound.arguments))
+                first = WRITES.get(name) or next(iter(bound.arguments))
                 dest[first] = bound.arguments[first]
             for k, v in dest.items():
                 call.inplace[k] = {"before": call.args[k], "base_before": _whole_storage(v)}
@@ -126,6 +131,14 @@ def install_ops(mp, proxy):
     to the block (`TrainBlock(ops)`); train_block's attribute is what a TrainBlock built without one falls back to, so no path is left out."""
     import importlib
     for name in ("train", "compressor_train", "train_block"):
+        mp.setattr(importlib.import_module("ldt_amd." + name), "ops", proxy)
+
+
+def install_infer_ops(mp, proxy):
+    """`proxy` as the module attribute `ops` of the two modules the inference forwards (`Compressor.forward`, `Compressor.sample`) reach their
+    kernels through: ldt_amd.compressor and ldt_amd.blocks (tests/infer_tape.py)."""
+    import importlib
+    for name in ("compressor", "blocks"):
         mp.setattr(importlib.import_module("ldt_amd." + name), "ops", proxy)
 
 
